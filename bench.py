@@ -25,6 +25,9 @@ synchronize on both sides and the maximum over ranks:
     headline's arithmetic, with the other mode nested as ITS sub-record.
 The injected-mask parity of the timed configurations against the CPU oracle (all 600 frames when the CPU sample
 covers them), including the bf16 Postnet of configs[2], is reported under "parity".
+
+--dump-outputs DIR writes the headline leg's last-step outputs as .npy files (inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output); the line's "dump_outputs" says what was written.
 """
 import argparse
 import hashlib
@@ -172,11 +175,11 @@ def vits2_flops(Tx, Ty, d):
     return te, d["n_flows"] * per_flow
 
 
-def bench_vits2(args, T, torch, dist, dev, world, rank, cpu_baseline=True):
+def bench_vits2(args, T, torch, dist, dev, world, rank, cpu_baseline=True, dump_dir=None):
     """Second hot path: one step = TextEncoder over [B, 120] tokens + the reverse
     flow over [B, 192, 600] latent frames.  Utterances are independent: ranks take equal shares, no collective.
     Returns the record (rank 0 prints it when this is the invocation's workload; the tacotron workload carries it as
-    its "vits2" sub-record)."""
+    its "vits2" sub-record).  With dump_dir, rank 0 writes the headline leg's last-step outputs there (dump_outputs)."""
     import warnings
 
     warnings.filterwarnings("ignore", category=FutureWarning)
@@ -206,6 +209,7 @@ def bench_vits2(args, T, torch, dist, dev, world, rank, cpu_baseline=True):
 
     Bg = B * world
     f_te, f_fl = vits2_flops(Tx, Ty, D)
+    last = {}  # what the last timed step returned
 
     def timed(precision, steps, warmup):
         """K timed passes in one arithmetic mode: exact fp32 (the reference's own) or the library's split-fp16."""
@@ -225,7 +229,7 @@ def bench_vits2(args, T, torch, dist, dev, world, rank, cpu_baseline=True):
         t0 = time.perf_counter()
         for _ in range(steps):
             with torch.no_grad():
-                ev[0].record(); te(ids, xl); ev[1].record(); out = fl(z, ym, reverse=True); ev[2].record()
+                ev[0].record(); enc = te(ids, xl); ev[1].record(); out = fl(z, ym, reverse=True); ev[2].record()
             ev[2].synchronize()
             te_ms += ev[0].elapsed_time(ev[1]); fl_ms += ev[1].elapsed_time(ev[2])
         fence()
@@ -235,6 +239,7 @@ def bench_vits2(args, T, torch, dist, dev, world, rank, cpu_baseline=True):
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
         assert bool(torch.isfinite(out).all())
+        last.update(zip(("x", "m_p", "logs_p", "x_mask"), enc), z_reverse=out)
         fl_s = fl_ms / steps * 1e-3
         if precision == "f32":
             peak, note = 157.3, "fp32 matrix instruction (v_mfma_f32_32x32x2_f32), 157.3 TFLOP/s"
@@ -257,6 +262,7 @@ def bench_vits2(args, T, torch, dist, dev, world, rank, cpu_baseline=True):
 
     prec = getattr(args, "vits2_precision", None) or ("f32" if args.precision == "f32" else "split_f16")
     head = timed(prec, args.steps, args.warmup)
+    dumped = dump_outputs(dump_dir, last) if dump_dir and rank == 0 else None
     res = {
         "metric": METRIC, "value": head["value"], "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": head["dtype"],
@@ -266,6 +272,8 @@ def bench_vits2(args, T, torch, dist, dev, world, rank, cpu_baseline=True):
                    "precision": prec},
         "rtf": head["rtf"], "text_encoder_ms": head["text_encoder_ms"], "flow_reverse_ms": head["flow_reverse_ms"], "roofline": head["roofline"],
     }
+    if dumped:
+        res["dump_outputs"] = dumped
     if not args.no_extra_legs:  # the other arithmetic mode as a named sub-record
         other = "split_f16" if prec == "f32" else "f32"
         leg = timed(other, args.steps, args.warmup)
@@ -317,6 +325,7 @@ class Workload:
             self.peng.ensure_packed(self.post.weight_tensors())
         self.R = self.cfg["model"]["decoder"]["r"]
         self._inputs = {}
+        self.last_outputs = None  # what the last timed step of the last leg returned (until the next decode overwrites io)
 
     def inputs(self, B):
         """ids -> stock encoder -> memory for this rank's shard of the global batch (B per GPU), plus output buffers."""
@@ -385,6 +394,7 @@ class Workload:
         elapsed = time.perf_counter() - t0
         assert io["t_out"].tolist() == [io["NS"], 0], f"decode ended early or saturated: {io['t_out'].tolist()}"
         assert bool(torch.isfinite(y_post).all())
+        self.last_outputs = {"y": io["y"], "s": io["s"], "w": io["w"], "y_post": y_post}
         if world > 1:
             tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -562,6 +572,31 @@ class Workload:
         return cpu, parity
 
 
+DUMP_BUDGET_BYTES = 60 * 2**20  # --dump-outputs writes at most this much (under 64 MB)
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Writes what the timed path returned in its last step as <out_dir>/<name>.npy (float32).  Every array has the utterance
+    axis first; when the whole set is larger than DUMP_BUDGET_BYTES, the same fixed, seeded sample of utterances is taken from
+    each array.  Returns the record that goes on the result line."""
+    import numpy as np
+
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    B = next(iter(arrays.values())).shape[0]
+    assert all(a.shape[0] == B for a in arrays.values()), {k: a.shape for k, a in arrays.items()}
+    keep = min(B, int(DUMP_BUDGET_BYTES // (sum(a.nbytes for a in arrays.values()) / B)))
+    if keep < 1:
+        raise SystemExit(f"--dump-outputs: one utterance's outputs exceed {DUMP_BUDGET_BYTES} bytes")
+    rows = np.arange(B) if keep == B else np.sort(np.random.default_rng(seed).choice(B, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[rows]))
+        files[name] = [len(rows), *a.shape[1:]]
+    return {"dir": out_dir, "files": files, "dtype": "float32", "utterances": "all" if keep == B else rows.tolist(),
+            "sample_seed": None if keep == B else seed, "rank": 0}
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -591,7 +626,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline and the parity record")
     ap.add_argument("--no-extra-legs", action="store_true", help="time only the headline leg (no split_f16 / b64_f32 / vits2 sub-records)")
     ap.add_argument("--cpu-frames", type=int, default=0, help="decode frames for the CPU baseline sample (0 = auto)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the headline leg's last step returned as DIR/<name>.npy (float32, rank 0's "
+                         "utterances; a fixed, seeded sample of them when the whole exceeds 60 MiB): y, s, w, y_post for the tacotron "
+                         "workload, x, m_p, logs_p, x_mask, z_reverse for vits2")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -636,7 +677,7 @@ def main():
             dist.destroy_process_group()
 
     if args.workload == "vits2":
-        res = bench_vits2(args, T, torch, dist, dev, world, rank)
+        res = bench_vits2(args, T, torch, dist, dev, world, rank, dump_dir=args.dump_outputs)
         res["distributed"] = dict(dist_info, collectives="none (every rank builds the same weights from the seed)")
         return finish(res)
 
@@ -645,6 +686,7 @@ def main():
     lj = args.config == "ljspeech"
 
     head = wk.time_leg(dist, B, args.precision, args.postnet, args.steps, args.warmup, args.dropout)
+    dumped = dump_outputs(args.dump_outputs, wk.last_outputs) if args.dump_outputs and rank == 0 else None
     out = {
         "metric": METRIC, "value": head["value"], "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -661,6 +703,8 @@ def main():
         "decode_only_frames_per_s": head["decode_only_frames_per_s"],
         "roofline": wk.roofline(B, args.precision, head["decode_step_ms"]),
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     legs = []
     if lj and not args.no_extra_legs:
         if args.precision != "split_f16":

@@ -246,38 +246,31 @@ def test_lengths_to_mask_and_build_tacotron_surface():
         T.build_tacotron(cfg)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/tacotron"), reason="reference checkout not present (GPU box)")
 def test_integration_recipe_drops_in_under_the_reference_tacotron_py():
-    """alias the three hot-path classes in the reference's own modules and
-    let the reference's build_tacotron assemble the model - run in a subprocess so the reference's
-    top-level module names (decoder, modules, ...) do not leak into this test session."""
-    import subprocess
-    import sys
+    """the reference's build_tacotron with the three hot-path classes aliased to the drop-ins.
+    tests/golden/integration_ljspeech.json (make_golden_integration.py) holds the constructor calls the reference's
+    build_tacotron makes for the LJSpeech config and the state-dict keys / shapes of the model it builds: the calls are
+    replayed on the drop-in classes, and both that model and the package's own build_tacotron must match the reference's."""
+    import json
 
-    code = r'''
-import sys, yaml
-sys.dont_write_bytecode = True
-sys.path.insert(0, %r)
-import torch_tts_amd as T
-sys.path.insert(0, "/root/reference/tacotron")
-import decoder_cell, decoder
-import modules.modules as ref_modules
-ref_keys = None
-import tacotron as ref_tacotron
-cfg = yaml.safe_load(open("/root/reference/configs/config-ljspeech.yaml"))
-ref_keys = set(ref_tacotron.build_tacotron(cfg).state_dict().keys())
-ref_tacotron.Taco2ProdDecoderCell = decoder_cell.Taco2ProdDecoderCell = T.Taco2ProdDecoderCell
-ref_tacotron.Decoder = decoder.Decoder = T.Decoder
-ref_tacotron.MelPostnet = ref_modules.MelPostnet = T.MelPostnet
-model = ref_tacotron.build_tacotron(cfg)
-assert isinstance(model.decoder, T.Decoder) and isinstance(model.decoder.decoder_cell, T.Taco2ProdDecoderCell)
-assert isinstance(model.postnet, T.MelPostnet)
-assert set(model.state_dict().keys()) == ref_keys, set(model.state_dict().keys()) ^ ref_keys
-print("OK", len(ref_keys))
-''' % ROOT
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
+    g = json.load(open(os.path.join(ROOT, "tests", "golden", "integration_ljspeech.json")))
+    classes = {"Taco2ProdDecoderCell": T.Taco2ProdDecoderCell, "Decoder": T.Decoder, "MelPostnet": T.MelPostnet,
+               "Encoder2": T.Encoder2, "Tacotron": T.Tacotron}
+    built = {}
+
+    def arg(a):  # "<ClassName>" = the module built by the earlier call of that class
+        return built[a[1:-1]] if isinstance(a, str) and a.startswith("<") else a
+
+    for c in g["calls"]:
+        built[c["class"]] = classes[c["class"]](*[arg(a) for a in c["args"]], **{k: arg(v) for k, v in c["kwargs"].items()})
+    model = built["Tacotron"]
+    assert isinstance(model.decoder, T.Decoder) and isinstance(model.decoder.decoder_cell, T.Taco2ProdDecoderCell)
+    assert isinstance(model.postnet, T.MelPostnet)
+    ref = {k: tuple(v) for k, v in g["state_dict"].items()}
+    for m in (model, T.build_tacotron(g["config"])):
+        got = {k: tuple(v.shape) for k, v in m.state_dict().items()}
+        assert set(got) == set(ref), set(got) ^ set(ref)
+        assert got == ref, {k: (got[k], ref[k]) for k in ref if got[k] != ref[k]}
 
 
 def test_vits2_modules_keys_tensor_counts_and_refusals():
@@ -430,6 +423,34 @@ def test_bench_byte_and_flop_model_follows_the_selected_config():
     assert rd["taco2"] and rd["P0"] == 128 and rd["D"] == 512 and rd["Kq"] == 2048
     # MelPostnet of the LJSpeech / rdh configs: 3 x conv(k = 5) 80 -> 512 -> 512 -> 512 and the 512 -> 80 Linear, 2 FLOP per weight and frame
     assert bench.postnet_flops_per_frame(bench.CONFIGS["ljspeech"]) == 2 * (5 * 80 * 512 + 2 * 5 * 512 * 512 + 512 * 80)
+
+
+def test_bench_dump_outputs_stays_under_its_budget_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs at the headline's shapes (256 utterances x 600 frames: ~165 MiB of outputs): float32 files under
+    64 MB in all, the same seeded utterances from every array, and the same sample from run to run; small outputs go whole."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    B, NF, L = 256, 600, 120
+    outs = {"y": torch.randn(B, NF, 80, generator=g), "s": torch.randn(B, NF, generator=g), "w": torch.rand(B, NF, L, generator=g)}
+    outs["y_post"] = outs["y"] * 2
+    recs = [bench.dump_outputs(str(tmp_path / d), outs) for d in ("a", "b")]
+    rows = recs[0]["utterances"]
+    assert rows == recs[1]["utterances"] and rows == sorted(set(rows)) and 0 < len(rows) < B
+    total = 0
+    for name, t in outs.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b) and np.array_equal(a, t[rows].numpy())
+        assert recs[0]["files"][name] == list(a.shape)
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+    assert total <= 64e6, total
+    small = bench.dump_outputs(str(tmp_path / "c"), {"z": torch.ones(3, 4, dtype=torch.float64)})
+    assert small["utterances"] == "all" and np.load(tmp_path / "c" / "z.npy").shape == (3, 4)
 
 
 def test_no_kernel_of_the_library_uses_scratch_memory():
