@@ -1,5 +1,6 @@
 """Shared helpers for the GPU parity tests: build the product modules (the drop-in
-mirrors of the reference's classes) from an oracle-style weight dict."""
+mirrors of the reference's classes) from an oracle-style weight dict; pick the utterances a CPU oracle checks at bench-sized
+shapes; restate conv256's launch schedule; emulate the bf16 Postnet's arithmetic on the CPU."""
 import torch
 
 import torch_tts_amd as T
@@ -98,3 +99,97 @@ def assert_argmax(w, ow, what="attention argmax", tie=2e-6):
     err = (w[bad] - ow[bad]).abs().max(dim=-1).values
     print(f"{what}: {int(bad.sum())} of {bad.numel()} rows differ; reference top-2 gaps {gap.tolist()[:8]}, max |w - ow| there {err.tolist()[:8]}")
     assert bool((gap < tie).all()), f"{what}: argmax differs on a row whose top-2 gap is {float(gap.max()):.3e}"
+
+
+# --------------------------------------------------------------------------
+# bench-shape parity on a sample: utterances never interact (the decode step is row-wise; Encoder2, the Postnet convs and
+# the VITS2 convs, attention and LayerNorm are per utterance), so the GPU runs the whole batch and the oracle a few rows of it
+# --------------------------------------------------------------------------
+def sample_utterances(B, T, boundaries=(), k_random=2, seed=0):
+    """Sorted, deduplicated utterance indices of a [B, T]-row batch: the first, the last, the one holding each row index in
+    `boundaries` (rows of the flattened [B * T] matrix where a kernel changes tile or launch) and `k_random` seeded others."""
+    assert B >= 1 and T >= 1
+    picked = {0, B - 1}
+    for r in boundaries:
+        assert 0 <= r < B * T, (r, B, T)
+        picked.add(int(r) // T)
+    rest = [b for b in torch.randperm(B, generator=torch.Generator().manual_seed(seed)).tolist() if b not in picked]
+    picked.update(rest[:k_random])
+    return sorted(picked)
+
+
+def last_tile_rows(M, *tiles):
+    """The first row of the last tile of each height in `tiles` over M rows (where a ragged last tile's row mask starts)."""
+    return [((M - 1) // t) * t for t in tiles]
+
+
+def conv256_schedule(M, cus, *, Cin=512, N=512, taps=5, elem_bytes=2, force=False):
+    """The row schedule launch_conv256_abl (torch-tts_amd/csrc/conv256.hip) gives a [M, Cin] -> [M, N] layer on a device of
+    `cus` CUs: None where the library keeps the shared GEMM tile, else {"full", "h", "nmt", "n_short"}: `full` whole 256-row
+    tiles (conv256_kernel<., ., 4>), then `n_short` short tiles of `h` rows from row full * 256 (conv256_kernel<., ., nmt>).
+    A restatement - the source it mirrors:
+
+        if (M <= 0 || T <= 0 || ((Cin * EB) % kRowB) || (N % kT256) || !(taps & 1) || taps > 15) return false;
+        if ((size_t)M * Cin * EB >= kOob || (size_t)N * taps * Cin * EB >= kOob) return false;  // 32-bit buffer offsets
+        ...
+        if (cus <= 0) return false;
+        const int n_rt = (M + kT256 - 1) / kT256, slots = cus / g.n_col_tiles > 0 ? cus / g.n_col_tiles : 1;
+        const int full = (n_rt / slots) * slots;        // row tiles of the whole rounds
+        const int rem = M - full * kT256;               // rows left for the last round (<= 0: none)
+        int h = 0, nmt = 0, n_short = 0;
+        if (rem > 0) {
+          h = (rem + slots - 1) / slots;
+          h = (h + 7) & ~7;                             // (whole 8-row DMA groups)
+          nmt = (h + 63) >> 6;
+          n_short = (rem + h - 1) / h;
+        }
+        {
+          const double ideal = (double)M / kT256 / slots, cost = (double)(full / slots) + (rem > 0 ? nmt / 4.0 : 0.0);
+          const char* force = getenv("TTSDEC_CONV256_FORCE");
+          if (ABL == 0 && !(force && force[0] == '1') && ideal < 0.86 * cost) return false;
+        }
+        if (full > 0) launch_conv256_tiles<ABL, kF32, 4>(g, 0, kT256, full, st);
+        if (rem > 0) { ... nmt >= 4 ? 4 : nmt ... }
+    """
+    kT256, kRowB, kOob = 256, 128, 0x7FFFF000
+    if M <= 0 or (Cin * elem_bytes) % kRowB or N % kT256 or not taps & 1 or taps > 15:
+        return None
+    if M * Cin * elem_bytes >= kOob or N * taps * Cin * elem_bytes >= kOob or cus <= 0:
+        return None
+    n_col = N // kT256
+    n_rt = (M + kT256 - 1) // kT256
+    slots = cus // n_col if cus // n_col > 0 else 1
+    full = (n_rt // slots) * slots
+    rem = M - full * kT256
+    h = nmt = n_short = 0
+    if rem > 0:
+        h = (rem + slots - 1) // slots
+        h = (h + 7) & ~7
+        nmt = (h + 63) >> 6
+        n_short = (rem + h - 1) // h
+    ideal, cost = M / kT256 / slots, (full // slots) + (nmt / 4.0 if rem > 0 else 0.0)
+    if not force and ideal < 0.86 * cost:
+        return None
+    return {"full": full, "h": h, "nmt": min(nmt, 4), "n_short": n_short}
+
+
+def device_cus(device=0):
+    return torch.cuda.get_device_properties(device).multi_processor_count
+
+
+def postnet_bf16_emulation(y, pw, num_layers=3):
+    """The bf16 Postnet's own arithmetic on the CPU: operands rounded to bf16 between the layers, fp32 accumulation, fp32 BN +
+    isru, the residual in fp32.  y [B, T, d_mel] fp32; pw: oracle-style MelPostnet weights."""
+    from oracle import tacotron_oracle as O
+
+    def rb(x):
+        return x.to(torch.bfloat16).to(torch.float32)
+
+    xc = rb(y).transpose(1, 2)
+    for i in range(num_layers):
+        xc = torch.nn.functional.conv1d(xc, rb(pw[f"conv.{i}.0.weight"]), None, padding=2)
+        inv = 1.0 / torch.sqrt(pw[f"conv.{i}.1.running_var"] + 1e-5)
+        alpha = pw[f"conv.{i}.1.weight"] * inv
+        beta = pw[f"conv.{i}.1.bias"] - pw[f"conv.{i}.1.running_mean"] * alpha
+        xc = rb(O.isru(xc * alpha[None, :, None] + beta[None, :, None]))
+    return y + torch.nn.functional.linear(xc.transpose(1, 2), rb(pw["fc_out.weight"]))

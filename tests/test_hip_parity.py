@@ -533,18 +533,7 @@ def test_postnet_bf16_vs_its_own_rounding_emulated_on_the_cpu(H, B, T):
     pw = O.random_postnet_weights(80, 512, 3, seed=9)
     g = torch.Generator().manual_seed(2)
     y = torch.randn(B, T, 80, generator=g)
-
-    def rb(x):
-        return x.to(torch.bfloat16).to(torch.float32)
-
-    xc = rb(y).transpose(1, 2)
-    for i in range(3):
-        xc = torch.nn.functional.conv1d(xc, rb(pw[f"conv.{i}.0.weight"]), None, padding=2)
-        inv = 1.0 / torch.sqrt(pw[f"conv.{i}.1.running_var"] + 1e-5)
-        alpha = pw[f"conv.{i}.1.weight"] * inv
-        beta = pw[f"conv.{i}.1.bias"] - pw[f"conv.{i}.1.running_mean"] * alpha
-        xc = rb(O.isru(xc * alpha[None, :, None] + beta[None, :, None]))
-    ref = y + torch.nn.functional.linear(xc.transpose(1, 2), rb(pw["fc_out.weight"]))
+    ref = H.postnet_bf16_emulation(y, pw, 3)
     pn = H.make_postnet(80, 512, 3, pw)
     pn.precision = "bf16"
     os.environ["TTSDEC_CONV256_FORCE"] = "1"  # (the library takes that kernel only where its tiles fill the chip: csrc/conv256.hip)
@@ -576,6 +565,85 @@ def test_postnet_fp32_on_the_256_wide_conv_kernel_vs_oracle(H, B, T):
     H.assert_close(out, ref, RTOL, ATOL, "postnet fp32 (conv256)")
 
 
+# ---- conv256 at every instantiation the library launches: conv256_kernel<0, kF32, NMT> for NMT = 4 (whole 256-row tiles)
+# and the short tiles of a last, partial round (NMT = 1 ... 4).  Which ones run follows from M and the CU count
+# (H.conv256_schedule restates launch_conv256_abl); the batch that reaches each is looked up from the device's CU count, and a
+# target no batch up to 256 utterances reaches is skipped, named.
+def _conv256_batch(H, B0, nmt, *, elem_bytes, force, T=600):
+    """B0 if it gives the wanted schedule (whole rounds first unless forced, then short tiles of `nmt` blocks), else the
+    nearest batch up to 256 that does; (B, schedule)."""
+    cus = H.device_cus()
+    for B in sorted(range(1, 257), key=lambda b: abs(b - B0)):
+        sch = H.conv256_schedule(B * T, cus, elem_bytes=elem_bytes, force=force)
+        if sch is not None and sch["nmt"] == nmt and (sch["full"] == 0) == force:
+            return B, sch
+    pytest.skip(f"{cus} CUs: no batch of <= 256 x {T} frames gives conv256 {'only' if force else 'whole rounds plus'} short tiles of "
+                f"{nmt} MFMA blocks per wave")
+
+
+def _postnet_on_conv256(H, pw, y, mode, force):
+    pn = H.make_postnet(80, 512, 3, pw)
+    pn.precision = mode
+    if force:
+        os.environ["TTSDEC_CONV256_FORCE"] = "1"
+    try:
+        with torch.no_grad():
+            return pn(y.cuda()).cpu()
+    finally:
+        if force:
+            del os.environ["TTSDEC_CONV256_FORCE"]
+
+
+@pytest.mark.parametrize("B0,nmt", [(256, 3), (64, 1), (128, 2)])  # (at 256 CUs: 512 whole tiles + 176-row short tiles, 128 + 48, 256 + 88)
+def test_postnet_bf16_whole_rounds_and_short_tiles_at_600_frames(H, B0, nmt):
+    """The bf16 Postnet (BASELINE.json configs[2]'s named mode) where the library itself takes conv256: whole rounds of 256-row
+    tiles, then one round of short tiles; sampled utterances against the CPU emulation of its bf16 arithmetic (the bar of
+    test_postnet_bf16_vs_its_own_rounding_emulated_on_the_cpu).  The sample holds the utterance with row full * 256, where
+    the short tiles begin."""
+    B, sch = _conv256_batch(H, B0, nmt, elem_bytes=2, force=False)
+    T = 600
+    pw = O.random_postnet_weights(80, 512, 3, seed=9)
+    y = torch.randn(B, T, 80, generator=torch.Generator().manual_seed(2))
+    out = _postnet_on_conv256(H, pw, y, "bf16", force=False)
+    sample = H.sample_utterances(B, T, [sch["full"] * 256], k_random=2, seed=B)
+    ref = H.postnet_bf16_emulation(y[sample], pw, 3)
+    err = float((out[sample] - ref).abs().max())
+    print(f"postnet bf16, B = {B} x {T}, schedule {sch}: utterances {sample}, max abs err vs bf16 emulation {err:.3e}")
+    assert err < 8e-3, err
+
+
+def test_postnet_fp32_whole_rounds_and_two_block_short_tiles_at_600_frames(H):
+    """Exact fp32 on conv256 with short tiles of two 32-row blocks per wave (128 x 600 at 256 CUs: 256 whole tiles + 88-row
+    tiles) - the one fp32 short-tile count the headline sizes (256: three blocks, 64: one) do not reach - against the oracle."""
+    B, sch = _conv256_batch(H, 128, 2, elem_bytes=4, force=False)
+    T = 600
+    pw = O.random_postnet_weights(80, 512, 3, seed=9)
+    y = torch.randn(B, T, 80, generator=torch.Generator().manual_seed(2))
+    out = _postnet_on_conv256(H, pw, y, "f32", force=False)
+    sample = H.sample_utterances(B, T, [sch["full"] * 256], k_random=2, seed=B)
+    print(f"postnet f32, B = {B} x {T}, schedule {sch}: utterances {sample}")
+    H.assert_close(out[sample], O.mel_postnet(y[sample], pw, 3), RTOL, ATOL, "postnet fp32 (conv256, whole rounds + short tiles)")
+
+
+@pytest.mark.parametrize("B0,nmt", [(16, 2), (32, 3), (48, 4)])  # (at 256 CUs: short tiles of 80, 152, 232 rows, no whole round)
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+def test_postnet_forced_conv256_short_tiles_only(H, mode, B0, nmt):
+    """TTSDEC_CONV256_FORCE=1 below the size the library takes conv256 at: one round of short tiles only, two to four blocks
+    per wave; the whole batch against the oracle (fp32) or the bf16 emulation."""
+    B, sch = _conv256_batch(H, B0, nmt, elem_bytes=4 if mode == "f32" else 2, force=True)
+    T = 600
+    pw = O.random_postnet_weights(80, 512, 3, seed=9)
+    y = torch.randn(B, T, 80, generator=torch.Generator().manual_seed(2))
+    out = _postnet_on_conv256(H, pw, y, mode, force=True)
+    print(f"postnet {mode} forced, B = {B} x {T}, schedule {sch}")
+    if mode == "f32":
+        H.assert_close(out, O.mel_postnet(y, pw, 3), RTOL, ATOL, "postnet fp32 (conv256 short tiles)")
+    else:
+        err = float((out - H.postnet_bf16_emulation(y, pw, 3)).abs().max())
+        print(f"  max abs err vs bf16 emulation {err:.3e}")
+        assert err < 8e-3, err
+
+
 def test_philox_mode_matches_oracle_masks(H):
     """On-device dropout: the same Philox function restated in the oracle gives the masks;
     the decode must match the oracle run with those masks injected."""
@@ -601,20 +669,25 @@ def test_philox_mode_matches_oracle_masks(H):
 _HEADLINE = {}
 
 
+def _bench_model():
+    """bench.py's model: LJSpeech dims, init seed 42 (built once)."""
+    if "model" not in _HEADLINE:
+        import bench
+        import torch_tts_amd as T
+
+        torch.manual_seed(42)
+        _HEADLINE["model"] = T.build_tacotron(bench.LJSPEECH).eval().cuda()
+    return _HEADLINE["model"]
+
+
 def _headline_case(B, mask_kind):
     """bench.py's workload (LJSpeech dims, init seed 42, ids seed 1234 through the encoder), the oracle's
     outputs for all 600 frames (computed once per case) and the masks that produced them."""
     key = (B, mask_kind)
     if key in _HEADLINE:
         return _HEADLINE[key]
-    import bench
-    import torch_tts_amd as T
-
     L, NF = 120, 600
-    if "model" not in _HEADLINE:
-        torch.manual_seed(42)
-        _HEADLINE["model"] = T.build_tacotron(bench.LJSPEECH).eval().cuda()
-    model = _HEADLINE["model"]
+    model = _bench_model()
     g = torch.Generator().manual_seed(1234)
     ids = torch.randint(1, 40, (B, L), generator=g).cuda()
     lens = torch.full((B,), L, dtype=torch.long).cuda()
@@ -666,21 +739,89 @@ def test_headline_600_frames_vs_oracle(H, B, prec):
     assert worst <= 1.0
 
 
-def test_headline_600_frames_philox_vs_oracle(H):
-    """The configuration bench.py times by default: B = 256, split-fp16, on-device Philox dropout (seed 123)."""
+@pytest.mark.parametrize("prec", ["f32", "split_f16"])
+def test_headline_600_frames_philox_vs_oracle(H, prec):
+    """B = 256, on-device Philox dropout (seed 123), in both arithmetic modes: exact fp32 decode and Postnet is the configuration
+    bench.py's headline leg times; split-fp16 is its named sub-record."""
     model, mem, masks, oy, os_, ow, opost = _headline_case(256, "philox")
     dec = model.decoder
-    dec.precision, dec.dropout_source, dec.dropout_seed = "split_f16", "philox", 123
+    dec.precision, dec.dropout_source, dec.dropout_seed = prec, "philox", 123
     with torch.no_grad():
         y, s, w = dec(mem, None, None, 599)
-        model.postnet.precision = "split_f16"
+        model.postnet.precision = prec
         yp = model.postnet(y).cpu()
+    assert dec.engine(torch.device("cuda:0")).precision() == prec
     y, s, w = y.cpu(), s.cpu(), w.cpu()
-    print("B=256 split_f16 philox:")
+    print(f"B=256 {prec} philox:")
     for n, a, b in (("y", y, oy), ("s", s, os_), ("w", w, ow), ("y_post", yp, opost)):
         _drift_report(n, a, b)
         H.assert_close(a, b, RTOL, ATOL, n)
     assert torch.equal(w.argmax(-1), ow.argmax(-1))
+
+
+_BIG = {}
+
+
+@pytest.mark.parametrize("prec", ["f32", "split_f16"])
+def test_configs3_unsharded_2048_utterances_600_frames_vs_oracle_on_a_sample(H, prec):
+    """BASELINE.json configs[3] on one GPU: B = 2048, L = 120, 600 frames, on-device Philox dropout (seed 123), bench.py's model
+    and inputs.  Rows never interact, so the oracle decodes a sample of the utterances (the first, the last, the ones holding
+    the first row of the last 64- and 128-row tiles, the one where conv256's short tiles begin, one seeded) with the Philox
+    masks of the whole batch.  The stop rule is batch-global: the comparison needs all 600 steps run.  Then the Postnet on that
+    mel: fp32 past conv256's 32-bit offset bound (2048 x 600 x 512 x 4 bytes: the shared tile), bf16 on conv256's many whole
+    rounds."""
+    model = _bench_model()
+    B, L, NF = 2048, 120, 600
+    cus = H.device_cus()
+    sch_bf16 = H.conv256_schedule(B * NF, cus, elem_bytes=2)
+    assert H.conv256_schedule(B * NF, cus, elem_bytes=4) is None, "fp32 at 2048 x 600 must lie past conv256's offset bound"
+    assert sch_bf16 is not None and sch_bf16["full"] > 0, sch_bf16
+    if not _BIG:
+        g = torch.Generator().manual_seed(1234)
+        ids = torch.randint(1, 40, (B, L), generator=g).cuda()  # (bench.py Workload.inputs)
+        lens = torch.full((B,), L, dtype=torch.long).cuda()
+        with torch.no_grad():
+            mem = torch.cat([model.encoder(ids[i : i + 64], lens[i : i + 64]) for i in range(0, B, 64)]).contiguous()
+        rows = [r * NF for r in H.last_tile_rows(B, 64, 128)] + [sch_bf16["full"] * 256]
+        sample = H.sample_utterances(B, NF, rows, k_random=1, seed=2048)
+        s = torch.tensor(sample)
+        masks = torch.stack([O.philox_keep_masks(123, t, B, 256) for t in range(NF)])[:, :, s].contiguous()
+        sd = {k: v.detach().cpu() for k, v in model.decoder.state_dict().items()}
+        with torch.no_grad():
+            oy, os_, ow = O.decode(sd, O.DecoderDims(), mem.cpu()[s], max_steps=NF - 1, masks=masks)
+        assert oy.shape == (len(sample), NF, 80)
+        _BIG.update(mem=mem, sample=sample, sd=sd, oy=oy, os=os_, ow=ow)
+    mem, sample, s = _BIG["mem"], _BIG["sample"], torch.tensor(_BIG["sample"])
+    dec = H.make_decoder(O.DecoderDims(), _BIG["sd"])  # (its own engine: a fallback after a role timeout stays with it)
+    dec.precision, dec.dropout_source, dec.dropout_seed = prec, "philox", 123
+    import warnings
+
+    with warnings.catch_warnings(record=True) as caught, torch.no_grad():
+        warnings.simplefilter("always")
+        y, st, w = dec(mem, None, None, NF - 1)
+    for wn in caught:
+        if "producer role" in str(wn.message):
+            print(f"B = 2048 {prec}: a two-role launch timed out and the call was repeated one role per launch ({wn.message})")
+    assert y.shape == (B, NF, 80), f"the decode stopped after {y.shape[1]} of {NF} frames: a sample comparison needs them all"
+    yc = y.cpu()
+    print(f"B = 2048 {prec}: utterances {sample}")
+    for n, a, b in (("y", yc[s], _BIG["oy"]), ("s", st.cpu()[s], _BIG["os"]), ("w", w.cpu()[s], _BIG["ow"])):
+        _drift_report(n, a, b)
+        H.assert_close(a, b, RTOL, ATOL, f"{n}, B = 2048 ({prec})")
+    assert torch.equal(w.cpu()[s].argmax(-1), _BIG["ow"].argmax(-1)), "attention argmax must be bit-exact"
+    # the Postnet on this mel, the sample against the oracle / the bf16 emulation
+    pw = {k: v.detach().cpu() for k, v in model.postnet.state_dict().items()}
+    pn = H.make_postnet(80, 512, 3, pw)
+    with torch.no_grad():
+        pn.precision = "f32"
+        yp = pn(y)[s].cpu()
+        pn.precision = "bf16"
+        yb = pn(y)[s].cpu()
+    del y
+    H.assert_close(yp, O.mel_postnet(yc[s], pw, 3), RTOL, ATOL, "y_post fp32, B = 2048 (shared tile)")
+    err = float((yb - H.postnet_bf16_emulation(yc[s], pw, 3)).abs().max())
+    print(f"  y_post bf16 (conv256 {sch_bf16}): max abs err vs bf16 emulation {err:.3e}")
+    assert err < 8e-3, err
 
 
 # --------------------------------------------------------------------------
@@ -780,6 +921,42 @@ def test_encoder2_golden_and_ljspeech_dims(H):
         encl.use_hip = False
         stock = encl(ids.cuda(), lens)
         H.assert_close(out.cpu(), stock.cpu(), RTOL, ATOL, "HIP vs stock ops")
+
+
+@pytest.mark.parametrize("kind", ["full", "ragged"])
+@pytest.mark.parametrize("prec", ["f32", "split_f16"])
+def test_encoder2_at_the_benchmarked_batch_vs_oracle(H, prec, kind):
+    """bench.py's encoder (its model, its ids) over B = 64 x 120 tokens: 7680 rows put the convs on the 64x64 tiles (fp32:
+    ceil(M / 64) * ceil(N / 64) >= 512, csrc/decode_kernels.hip launch_gemm_cfg) that the small case above never reaches.  The
+    whole batch runs; a sample of utterances (the first, the last, the one holding the last 64- and 128-row tiles, two seeded)
+    is compared with the oracle.  "ragged": the sample holds lengths 120 and 1, the other lengths are drawn."""
+    model = _bench_model()
+    enc = model.encoder
+    B, L = 64, 120
+    g = torch.Generator().manual_seed(1234)
+    ids = torch.randint(1, 40, (B, L), generator=g)  # (bench.py Workload.inputs)
+    sample = H.sample_utterances(B, L, H.last_tile_rows(B * L, 64, 128), k_random=2, seed=3)
+    lens = torch.full((B,), L, dtype=torch.long)
+    if kind == "ragged":
+        lens = torch.randint(1, L + 1, (B,), generator=torch.Generator().manual_seed(5))
+        lens[sample[0]], lens[sample[-1]] = L, 1
+        for b in range(B):
+            ids[b, lens[b]:] = 0
+    wts = {k: v.detach().cpu() for k, v in enc.state_dict().items()}
+    s = torch.tensor(sample)
+    ref = O.encoder2(ids[s], lens[s], wts)
+    try:
+        enc.precision = prec
+        with torch.no_grad():
+            out = enc(ids.cuda(), lens.cuda()).cpu()
+    finally:
+        enc.precision = "f32"  # (the shared model's default: _headline_case's memory is computed with it)
+    assert out.shape == (B, int(lens.max()), 512)
+    print(f"encoder {prec} {kind}: utterances {sample}, lengths {lens[s].tolist()}")
+    H.assert_close(out[s, : ref.shape[1]], ref, RTOL, ATOL, f"memory, B = 64 x 120 ({prec}, {kind})")
+    for b in range(B):
+        n = int(lens[b])
+        assert not bool(out[b, n:].ne(0).any()), f"padded rows of utterance {b} must be exactly zero (rnn.py:126)"
 
 
 def test_tacotron_forward_glue_sandra_style_config(H):

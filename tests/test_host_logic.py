@@ -541,3 +541,54 @@ def test_committed_traffic_captures_belong_to_these_kernel_sources():
         for name, v in tj["per_launch"].items():
             assert v["hbm_bytes"] > 0, (fn, name)
     assert {("f32", 256), ("f32", 64), ("split_f16", 256)} <= seen, seen
+
+
+# ---- the helpers the bench-shape parity tests pick their sample and their batch sizes with (tests/hip_helpers.py) ----
+def test_sample_utterances_holds_the_edges_the_boundaries_and_seeded_others():
+    import hip_helpers as H
+
+    s = H.sample_utterances(2048, 600, [1984 * 600, 1920 * 600 + 599, 4736 * 256], k_random=2, seed=5)
+    assert s == sorted(set(s)) and {0, 2047, 1984, 1920, 4736 * 256 // 600} <= set(s) and len(s) == 7
+    assert s == H.sample_utterances(2048, 600, [1984 * 600, 1920 * 600 + 599, 4736 * 256], k_random=2, seed=5)
+    assert H.sample_utterances(1, 600, [0, 599], k_random=3) == [0]
+    assert H.sample_utterances(3, 5, [], k_random=9, seed=1) == [0, 1, 2]
+    assert len(H.sample_utterances(64, 120, [], k_random=3, seed=2)) == 5
+    with pytest.raises(AssertionError):
+        H.sample_utterances(4, 10, [40])
+    assert H.last_tile_rows(38400, 64, 128) == [38336, 38272] and H.last_tile_rows(2107, 64, 128) == [2048, 2048]
+
+
+def test_conv256_schedule_restatement():
+    """At 256 CUs (MI355X; 2 column tiles of N = 512 -> 128 slots): the batches the parity tests use reach the instantiations
+    named in their comments, every row is covered exactly once, and the gate and the offset bound are where conv256.hip puts
+    them."""
+    import hip_helpers as H
+
+    cases = {(256, False, 2): (512, 176, 3), (64, False, 2): (128, 48, 1), (128, False, 2): (256, 88, 2), (128, False, 4): (256, 88, 2),
+             (16, True, 2): (0, 80, 2), (32, True, 4): (0, 152, 3), (48, True, 2): (0, 232, 4), (2048, False, 2): (4736, 128, 2)}
+    for (B, force, eb), (full, h, nmt) in cases.items():
+        M = B * 600
+        sch = H.conv256_schedule(M, 256, elem_bytes=eb, force=force)
+        assert (sch["full"], sch["h"], sch["nmt"]) == (full, h, nmt), (B, force, eb, sch)
+        rem = M - full * 256
+        assert sch["n_short"] * h >= rem > (sch["n_short"] - 1) * h and sch["n_short"] <= 128
+    assert H.conv256_schedule(2048 * 600, 256, elem_bytes=4) is None        # 2048 x 600 x 512 x 4 bytes >= 0x7FFFF000
+    assert H.conv256_schedule(16 * 600, 256, elem_bytes=2) is None          # below the gate: the shared tile ...
+    assert H.conv256_schedule(3 * 600, 256, elem_bytes=4, force=True)["full"] == 0  # ... unless forced
+    assert H.conv256_schedule(600, 256, Cin=80) is None                     # the Postnet's first layer (80 channels)
+    assert H.conv256_schedule(256 * 600, 0) is None
+    # rows that fill whole rounds exactly: no short tiles
+    assert H.conv256_schedule(128 * 256, 256) == {"full": 128, "h": 0, "nmt": 0, "n_short": 0}
+
+
+def test_conv256_schedule_quotes_the_dispatcher_it_restates():
+    """Every code line quoted in conv256_schedule's docstring is still in csrc/conv256.hip: an edit of the dispatcher breaks this
+    test instead of leaving the parity tests on batches that no longer reach the instantiations they name."""
+    import hip_helpers as H
+
+    src = " ".join(open(os.path.join(ROOT, "torch-tts_amd", "csrc", "conv256.hip")).read().split())
+    doc = H.conv256_schedule.__doc__.split("the source it mirrors:", 1)[1]
+    quoted = [" ".join(l.split()) for l in doc.splitlines() if l.strip() and l.strip() != "..." and "{ ..." not in l]
+    assert len(quoted) >= 15
+    for line in quoted:
+        assert line in src, line

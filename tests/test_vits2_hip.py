@@ -217,3 +217,73 @@ def test_speaker_conditioning_refusals():
             plain(x, mk, g=torch.zeros(2, 8, 1, device="cuda"), reverse=True)  # g for a module built without gin_channels
     with pytest.raises(AssertionError):
         T.vits2.TextEncoder(11, 16, 32, 48, 2, 2, 3, 0.1, gin_channels=8)  # attentions.py:50-52: cond_layer_idx 2 needs 3 layers
+
+
+# ---- bench.py's VITS2 shapes (BASELINE.json configs[4]): TextEncoder [64, 120], reverse flow [64, 192, 600] ----
+# At 64 x 600 = 38400 rows the flow's fp32 GEMMs take the 64x64 tile with the generic epilogue (csrc/decode_kernels.hip
+# launch_gemm_cfg: ceil(M / 64) * ceil(N / 64) >= 512), split-fp16 the 128x128 and the lean short-K 64x64 tiles (M >= 2048);
+# the TextEncoder's 7680 rows move its qkv / FFN / proj GEMMs to the 64x64 tile too.  None of these is reached at the sizes
+# above.  Utterances never interact, so the GPU runs the whole batch and the oracle a sample of it.
+_BENCH_B, _BENCH_TX, _BENCH_TY = 64, 120, 600
+_BENCH_VITS2 = {}
+
+
+def _bench_vits2_case(kind):
+    """Weights, inputs, lengths, the sampled utterances and the oracle's outputs on them (fp32 TextEncoder, fp32 and fp64 flow);
+    kind "full": every utterance full length, as bench.py runs; "ragged": lengths 1 and full among the sample, the others' last
+    valid row inside a 64-row tile."""
+    if kind in _BENCH_VITS2:
+        return _BENCH_VITS2[kind]
+    import hip_helpers as H
+
+    d = V.Vits2Dims()
+    wts = V.random_vits2_weights(d, seed=6)  # (post weights non-zero: the coupling does real work, as bench.py arranges)
+    assert float(wts["flow.flows.0.post.weight"].abs().max()) > 0.0
+    B, Tx, Ty = _BENCH_B, _BENCH_TX, _BENCH_TY
+    gen = torch.Generator().manual_seed(11)
+    ids = torch.randint(0, d.n_vocab, (B, Tx), generator=gen)
+    z = torch.randn(B, d.inter_channels, Ty, generator=gen)
+    bounds = H.last_tile_rows(B * Ty, 64, 128)
+    sample = H.sample_utterances(B, Ty, bounds + [(r // Tx) * Ty for r in H.last_tile_rows(B * Tx, 64, 128)], k_random=3, seed=7)
+    xl, yl = torch.full((B,), Tx), torch.full((B,), Ty)
+    if kind == "ragged":
+        xl = torch.randint(1, Tx + 1, (B,), generator=gen)
+        yl = torch.randint(1, Ty + 1, (B,), generator=gen)
+        xl[sample[0]], yl[sample[0]] = Tx, Ty
+        xl[sample[-1]], yl[sample[-1]] = 1, 1
+        for b in sample[1:-1]:  # the last valid row 20 rows into a 64-row tile of the [B * T] matrix
+            xl[b] = next(n for n in range(Tx, 0, -1) if (b * Tx + n - 1) % 64 == 20)
+            yl[b] = next(n for n in range(Ty, 0, -1) if (b * Ty + n - 1) % 64 == 20)
+    ymask = V.sequence_mask(yl, Ty).unsqueeze(1).float()
+    s = torch.tensor(sample)
+    w64 = {k: v.double() for k, v in wts.items()}
+    ox, om, ol, _ = V.text_encoder(ids[s], xl[s], wts, d)
+    oz = V.flow_reverse(z[s], ymask[s], wts, d)
+    oz64 = V.flow_reverse(z[s].double(), ymask[s].double(), w64, d).float()
+    _BENCH_VITS2[kind] = dict(d=d, wts=wts, ids=ids, z=z, xl=xl, yl=yl, ymask=ymask, sample=sample, ox=ox, om=om, ol=ol, oz=oz, oz64=oz64)
+    return _BENCH_VITS2[kind]
+
+
+@pytest.mark.parametrize("kind", ["full", "ragged"])
+@pytest.mark.parametrize("prec", ["f32", "split_f16"])
+def test_vits2_at_the_benchmarked_batch_vs_oracle(prec, kind):
+    c = _bench_vits2_case(kind)
+    d, s = c["d"], torch.tensor(c["sample"])
+    te, fl = _text_encoder({**d.__dict__}, c["wts"]), _flow({**d.__dict__}, c["wts"])
+    te.precision = fl.precision = prec
+    with torch.no_grad():
+        x, m, logs, _ = te(c["ids"].cuda(), c["xl"].cuda())
+        out = fl(c["z"].cuda(), c["ymask"].cuda(), reverse=True)
+    assert x.shape == (_BENCH_B, d.hidden_channels, _BENCH_TX) and out.shape == (_BENCH_B, d.inter_channels, _BENCH_TY)
+    x, m, logs, out = (t.cpu()[s] for t in (x, m, logs, out))
+    print(f"{prec} {kind}: utterances {c['sample']}, text lengths {c['xl'][s].tolist()}, frame lengths {c['yl'][s].tolist()}")
+    _close(x, c["ox"], f"{prec} x")
+    _close(m, c["om"], f"{prec} m")
+    _close(logs, c["ol"], f"{prec} logs")
+    _close(out, c["oz64"], f"{prec} flow out vs fp64 oracle", rtol=1e-4, atol=1e-5)
+    _close(out, c["oz"], f"{prec} flow out", rtol=2e-4, atol=2e-5)
+    for i, b in enumerate(c["sample"]):  # padded frames are exactly zero (the oracle's are)
+        nx, ny = int(c["xl"][b]), int(c["yl"][b])
+        for name, t in (("x", x), ("m", m), ("logs", logs)):
+            assert not bool(t[i, :, nx:].ne(0).any()), (prec, kind, b, name)
+        assert not bool(out[i, :, ny:].ne(0).any()), (prec, kind, b, "flow out")
