@@ -194,7 +194,9 @@ enum {
                                 * (overlap 2, at most 512 utterances) instead of a launch of its own                          */
   TTSDEC_OPT_MERGED_TUNE,      /* "merged_tune": measurement knobs of the one-launch step (overlap = 3): bit 0 = the decoder LSTM waits for
                                 * h_att before its first tile, bit 1 = wave priority 2 / 0 for the attention / decoder LSTM roles,
-                                * bits 8-15 = extra sleeps between the query role's polls for h_att                              */
+                                * bits 8-15 = extra sleeps between the query role's polls for h_att; bits 16-19 (two-launch
+                                * step, exact fp32, 64 x 16 LSTM tile): the attention pass's form - 1 = base, 2 = one row
+                                * (ablation), 3 = plain sum (ablation), 4 = base with swapped wave priorities, 5 = lean     */
   TTSDEC_OPT_PROFILE_ABLATION, /* "profile_ablation": ttsdec_profile_step only, kernel-internal ablation switches              */
   TTSDEC_OPT_DEBUG_FLAGS,      /* "debug_flags": TEST HOOK. bit 0 / 1 / 2 / 3: the frame / attention / projection-head role of a
                                 * two-role launch / the attention LSTM's tiles of the one-launch step do not signal their

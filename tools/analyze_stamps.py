@@ -62,6 +62,14 @@ for kind, name in ((0, "frame || lstm_att"), (1, "attention || lstm_dec")):
                         ghz = (c[okc, 1] - c[okc, 0]).astype(np.float64) / ((t32[okc] - t16[okc]) * 100.0) * 0.1
                         print(f"           in-kernel clock over K tiles 16..32: median {np.median(ghz):5.3f} GHz (min {ghz.min():5.3f}, max {ghz.max():5.3f}); "
                               f"{(t32[okc] - t16[okc]).mean() / 16 * 1e3:6.1f} ns = {np.median((c[okc, 1] - c[okc, 0]) / 16.0):7.1f} cycles per K tile")
+                    tk = {8: c[:, 2], 24: c[:, 3], 48: c[:, 4]}
+                    if all((v > 0).any() for v in tk.values()):
+                        at = {k: (v[v > 0].astype(np.int64) - t0) / 100.0 for k, v in tk.items()}
+                        at[0], at[16], at[32] = st_, t16, t32
+                        ks = sorted(at)
+                        print("           K tile " + ", ".join(f"{k} at {at[k].mean():6.2f}" for k in ks[1:]) + " (means)")
+                        print("           us per K tile: " + ", ".join(f"{a}-{b} {(at[b].mean() - at[a].mean()) / (b - a):5.3f}" for a, b in zip(ks, ks[1:]))
+                              + f", 48-gate {(gi.mean() - at[48].mean()) / 16:5.3f} (if the gate is at tile 64)")
                 slow = np.argsort(-gi)[:32]
                 fast = np.argsort(gi)[:32]
                 for nm, idx in (("32 slowest", slow), ("32 fastest", fast)):

@@ -582,6 +582,7 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
     return pa;
   };
 
+  const int attn_variant = ((h->merged_tune > 0 ? h->merged_tune : 0) >> 16) & 0xf;  // (measurement: fused_kernels.hip attn_lstm_f32_wide)
   switch (node) {
     case N_F:
     case N_FIN:
@@ -596,12 +597,12 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
     case N_TD: {
       AttnArgs a = attn_args();
       a.dep_signal = 1; a.dep_cnt = dep(DEP_ATTN);
-      launch_attn_lstm(a, lstm_args(1, PART_GATED), nullptr, st);
+      launch_attn_lstm(a, lstm_args(1, PART_GATED), nullptr, st, attn_variant);
       break;
     }
     case N_QTD: {
       const ProjArgs pq = query_role_args();
-      launch_attn_lstm(query_attn_args(pq), lstm_args(1, PART_GATED), &pq, st);
+      launch_attn_lstm(query_attn_args(pq), lstm_args(1, PART_GATED), &pq, st, attn_variant);
       break;
     }
     case N_STEP: {
@@ -824,6 +825,9 @@ bool head_proj(const ttsdec_handle* h, int B) {
 // roles do not share CUs there: the hop costs more than the launch), B = 1 175 / 38 (one workgroup would run all 32 tiles); exact
 // fp32 B = 256 125.0 / 125.0, B = 32 58.6 / 55.3.  So: split-fp16, 64..384 utterances, at most one tile per workgroup (option
 // query_role = 1 forces it wherever it is possible at all).
+// Round 5, exact fp32 B = 256 beside the decoder LSTM's 64 x 16 tile (profiles/r05_a_*, same process, 5 interleaved rounds): with
+// the lean attention pass (step_bodies.h ATTN_LEAN) 101.0 against 101.8 us per step; with the base pass 102.3 against 102.2 -
+// the lean pass ends 2.5 us earlier, and that slack is what absorbs the query tiles.  So also: exact fp32, 192..256 utterances.
 bool query_role(const ttsdec_handle* h, int B) {
   const ttsdec_dims& d = h->d;
   if (overlap_level(h, B) < 2 || h->query_role == 0) return false;
@@ -831,7 +835,8 @@ bool query_role(const ttsdec_handle* h, int B) {
   const int ps = proj_split(query_k(d));
   if (!(ps > 0 && ps <= kQuerySplit && !(d.h_att & 7))) return false;
   if (h->query_role > 0) return true;
-  return lstm_prec(h) && B >= 64 && B <= 384 && proj_grid_size(B, d.d_ctx, ps) <= B;
+  const bool range = lstm_prec(h) ? (B >= 64 && B <= 384) : (B >= 192 && B <= 256);
+  return range && proj_grid_size(B, d.d_ctx, ps) <= B;
 }
 // The one-launch step (option overlap = 3): split-fp16 Prod cell with the projection as a head role and the query on the
 // register-weight body, at batches whose attention workgroups fit the chip at once.

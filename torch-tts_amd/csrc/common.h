@@ -11,6 +11,7 @@ namespace ttsdec {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kGemmThreads = 512;  // 4 MFMA waves + 4 loader waves
 constexpr int kAttnThreads = 512;
@@ -62,7 +63,7 @@ __device__ __forceinline__ void loop_stamp(const Ctrl* c, int slot, int node) {
     if (p != nullptr && slot < kLoopStampSlots) p[slot * kLoopStampNodes + node] = __builtin_amdgcn_s_memrealtime();
   }
 }
-constexpr int kStampKinds = 5;  // 3, 4: shader-clock readings (s_memtime) of kinds 0 / 1 at K tiles 16 and 32, for the in-kernel clock
+constexpr int kStampKinds = 5;  // 3, 4: shader-clock readings (s_memtime) of kinds 0 / 1 at K tiles 16 and 32, for the in-kernel clock (slots 0, 1), and the time at K tiles 8, 24, 48 (slots 2-4)
 // stamps[(kind * 1024 + block) * 8 + k]; kind 0 = frame || lstm_att, 1 = attention || lstm_dec, 2 = the projection role at the head of
 // kind 0's launch (k: 2 = entry, 3 = control block and operands arrived, 4 = partial tile reduced, 5 = signalled);
 // k: 0 = role << 32 | HW_ID, 1 = XCC_ID, 2 = start, 3 = gate reached, 4 = gate passed, 5 = end (s_memrealtime, 10 ns units)

@@ -115,21 +115,25 @@ __global__ __launch_bounds__(kGemmThreads, WPE) void frame_lstm_kernel(FrameArgs
 // on a role that has slack: the decoder LSTM reaches its gate at ~22 us, the attention pass used to end at ~15.
 // All attention-role workgroups must be resident together for this (they have the lowest block ids; B <= the chip's two
 // workgroups per CU): the host only asks for it then.
-template <int NJ, class Cfg, int WPE>
+// kVar: the attention pass's form (step_bodies.h AttnVariant), or ATTN_PRIO_SWAP (measurement: the base pass at wave priority 0,
+// the decoder LSTM at 3).
+constexpr int ATTN_PRIO_SWAP = 4;
+template <int NJ, class Cfg, int WPE, int kVar = ATTN_BASE>
 __global__ __launch_bounds__(kGemmThreads, WPE) void attn_lstm_kernel(AttnArgs a, LstmArgs l, ProjArgs pq, int n_attn, int lstm_cols) {
   __shared__ __attribute__((aligned(16))) float smem[cmax<cmax<Cfg::kLdsFloats, attn_lds_floats<NJ>()>(), kProjLdsFloats>()];
   loop_stamp(a.ctrl, a.slot, a.node);
   const int id = blockIdx.x;
   if (id < n_attn) {
-    __builtin_amdgcn_s_setprio(3);  // (as above: the decoder LSTM's last segment waits for every one of these)
+    if constexpr (kVar != ATTN_PRIO_SWAP) __builtin_amdgcn_s_setprio(3);  // (as above: the decoder LSTM's last segment waits for every one of these)
     if (a.q_tiles > 0) {
       for (int tile = id; tile < a.q_tiles; tile += n_attn) {
         proj_body<Cfg::kPrec>(pq, smem, tile);
         __syncthreads();  // (the reduction tile in LDS is reused by the next tile / the attention pass)
       }
     }
-    attn_body<NJ>(a, smem, id);
+    attn_body<NJ, kVar == ATTN_PRIO_SWAP ? ATTN_BASE : kVar>(a, smem, id);
   } else {
+    if constexpr (kVar == ATTN_PRIO_SWAP) __builtin_amdgcn_s_setprio(3);
     const int j = id - n_attn;
     lstm_body<Cfg, true, true>(l, smem, j % lstm_cols, j / lstm_cols);
   }
@@ -291,21 +295,37 @@ static int resident_slots(const void* fn) {
 }
 
 typedef void (*attn_lstm_fn)(AttnArgs, LstmArgs, ProjArgs, int, int);
+// The attention pass per regime: ATTN_LEAN beside the exact-fp32 LSTM on the 64 x 16 tile (B > 96), whose fp32 MFMA chain shares
+// each SIMD with the attention waves; ATTN_BASE elsewhere (split-fp16: 16-bit MFMAs leave the vector ALU alone; small batches:
+// the roles rarely share a CU).  variant (measurement, option merged_tune bits 16-19, exact fp32 64 x 16 tile only): 1 = ATTN_BASE,
+// 2 = ATTN_ONE_ROW, 3 = ATTN_PLAIN_SUM, 4 = ATTN_PRIO_SWAP, 5 = ATTN_LEAN.
+template <int NJ>
+static attn_lstm_fn attn_lstm_f32_wide(int variant) {
+  using C = LeanTiles<PREC_F32>::Lean64x16;
+  switch (variant) {
+    case 1: return attn_lstm_kernel<NJ, C, 4, ATTN_BASE>;
+    case 2: return attn_lstm_kernel<NJ, C, 4, ATTN_ONE_ROW>;
+    case 3: return attn_lstm_kernel<NJ, C, 4, ATTN_PLAIN_SUM>;
+    case 4: return attn_lstm_kernel<NJ, C, 4, ATTN_PRIO_SWAP>;
+    default: return attn_lstm_kernel<NJ, C, 4, ATTN_LEAN>;
+  }
+}
 template <int NJ, int PREC>
-static attn_lstm_fn attn_lstm_kernel_of(LeanKind kind) {
+static attn_lstm_fn attn_lstm_kernel_of(LeanKind kind, int variant) {
   using TL = LeanTiles<PREC>;
   if (kind == SMALL_FAT) return attn_lstm_kernel<NJ, typename TL::SmallFat, 2>;
   if (kind == LEAN_64x8) return attn_lstm_kernel<NJ, typename TL::Lean64x8, 4>;
+  if constexpr (PREC == PREC_F32) return attn_lstm_f32_wide<NJ>(variant);
   return attn_lstm_kernel<NJ, typename TL::Lean64x16, 4>;
 }
-static attn_lstm_fn attn_lstm_kernel_for(int D, bool f16, LeanKind kind) {
-  if (D / 4 <= 64) return f16 ? attn_lstm_kernel_of<1, PREC_F16S>(kind) : attn_lstm_kernel_of<1, PREC_F32>(kind);
-  return f16 ? attn_lstm_kernel_of<2, PREC_F16S>(kind) : attn_lstm_kernel_of<2, PREC_F32>(kind);
+static attn_lstm_fn attn_lstm_kernel_for(int D, bool f16, LeanKind kind, int variant = 0) {
+  if (D / 4 <= 64) return f16 ? attn_lstm_kernel_of<1, PREC_F16S>(kind, variant) : attn_lstm_kernel_of<1, PREC_F32>(kind, variant);
+  return f16 ? attn_lstm_kernel_of<2, PREC_F16S>(kind, variant) : attn_lstm_kernel_of<2, PREC_F32>(kind, variant);
 }
 int attn_lstm_resident_slots(int B, int H, int D, bool f16) {
   return resident_slots(reinterpret_cast<const void*>(attn_lstm_kernel_for(D, f16, lean_kind(B, B, H, f16))));
 }
-void launch_attn_lstm(const AttnArgs& a, const LstmArgs& l, const ProjArgs* q, hipStream_t st) {
+void launch_attn_lstm(const AttnArgs& a, const LstmArgs& l, const ProjArgs* q, hipStream_t st, int variant) {
   if (a.B <= 0) return;
   ProjArgs pq;
   if (q != nullptr) pq = *q;
@@ -315,7 +335,7 @@ void launch_attn_lstm(const AttnArgs& a, const LstmArgs& l, const ProjArgs* q, h
   const int bm = l.prec == 1 ? lean_bm<PREC_F16S>(kind) : lean_bm<PREC_F32>(kind);
   const int lrows = (l.M + bm - 1) / bm;
   dim3 grid(a.B + lcols * lrows), block(kGemmThreads);
-  hipLaunchKernelGGL(attn_lstm_kernel_for(a.D, l.prec == 1, kind), grid, block, 0, st, a, l, pq, a.B, lcols);
+  hipLaunchKernelGGL(attn_lstm_kernel_for(a.D, l.prec == 1, kind, variant), grid, block, 0, st, a, l, pq, a.B, lcols);
 }
 
 // ---- one-launch step ----

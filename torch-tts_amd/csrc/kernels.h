@@ -247,7 +247,8 @@ void launch_frame_lstm(const FrameArgs& f, const LstmArgs& l, hipStream_t st);  
 // ... with the previous step's mel/stop projection as a role at its head: proj(t-1) -> frame(t) || lstm_att(t)
 void launch_proj_frame_lstm(const ProjArgs& pj, const FrameArgs& f, const LstmArgs& l, hipStream_t st);
 int proj_grid_size(int M, int N, int ksplit);  // workgroups of the projection kernel / role
-void launch_attn_lstm(const AttnArgs& a, const LstmArgs& l, const ProjArgs* q, hipStream_t st);  // [query ->] attention || decoder LSTM
+// [query ->] attention || decoder LSTM; variant: measurement forms of the attention pass (fused_kernels.hip attn_lstm_f32_wide)
+void launch_attn_lstm(const AttnArgs& a, const LstmArgs& l, const ProjArgs* q, hipStream_t st, int variant = 0);
 void launch_lstm_lean(const LstmArgs& l, hipStream_t st);                       // an LSTM on the lean tile alone (profiling)
 // The whole step as ONE launch: [proj(t-1) | frame | lstm_att | query -> attention | lstm_dec] by block id, every role waiting
 // only for roles with lower ids (fused_kernels.hip step_kernel).  False: the configuration is not covered (nothing launched).

@@ -102,9 +102,13 @@ struct RoleGateT {
   Ctrl* ctrl;
   int kind;
   stamp_ptr st;  // (loaded by the caller, once: see common.h stamp)
-  // K-loop progress (measurement only): the time at K tiles 16 and 32, stamps 6 and 7 (the second gate's slots: not both at once)
+  // K-loop progress (measurement only): the time at K tiles 16 and 32, stamps 6 and 7 (the second gate's slots: not both at once);
+  // at K tiles 8, 24 and 48 in slots 2-4 of the shader-clock row
   __device__ __forceinline__ void mark(int t) const {
     if (st != nullptr && seg2 < 0) {
+      if (t == 8) stamp(st, kind + 3, 2, now_rt());
+      if (t == 24) stamp(st, kind + 3, 3, now_rt());
+      if (t == 48) stamp(st, kind + 3, 4, now_rt());
       // (with the shader clock beside the 100-MHz one: in-kernel clock = d s_memtime / d s_memrealtime x 100 MHz, MI355X_MICROARCH.md DVFS (6))
       if (t == 16) { stamp(st, kind, 6, now_rt()); stamp(st, kind + 3, 0, __builtin_amdgcn_s_memtime()); }
       if (t == 32) { stamp(st, kind, 7, now_rt()); stamp(st, kind + 3, 1, __builtin_amdgcn_s_memtime()); }
@@ -297,9 +301,39 @@ __device__ __forceinline__ void lstm_body(LstmArgs g, float* smem, int bx, int b
 // is still in registers.  Row l needs p0[l-1], so a wave recomputes the energy
 // of the row just before its range.
 // ===========================================================================
+// Forms of the pass (kVar).  ATTN_LEAN is the same arithmetic in the same order on fewer vector-ALU instructions, for the
+// exact-fp32 launch beside the decoder LSTM: there every vector-ALU instruction of this role waits behind the partner's fp32
+// MFMA chain on the same SIMD (4.5, round 5).  It loads every row of a group of four without a branch
+// (rows past the wave's range re-read its last one), so the four wave sums interleave and the DPP moves fold into the adds;
+// it evaluates the four rows' ISRU sigmoids on four lanes of ONE instruction sequence, and accumulates the context with packed
+// fp32 FMAs (v_pk_fma_f32: two independent fused multiply-adds, rounded as fmaf).  y, s and w stay bit-identical.
+// ATTN_ONE_ROW and ATTN_PLAIN_SUM are measurement ablations (wrong results): every row load reads the wave's first row
+// (L1 / L2-resident: the arithmetic stays, the memory stream goes), or the loads stay and the context becomes a plain sum
+// of the rows under the previous weights (the energy, ISRU and FMA work goes).
+enum AttnVariant { ATTN_BASE = 0, ATTN_LEAN = 1, ATTN_ONE_ROW = 2, ATTN_PLAIN_SUM = 3 };
+
+// wave_sum with the four full-row DPP steps folded into v_add_f32_dpp (same adds, same order: bit-identical)
+__device__ __forceinline__ float wave_sum_folded(float v) {
+  auto dpp = [](float x, auto ctrl) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), decltype(ctrl)::value, 0xf, 0xf, true));
+  };
+  using std::integral_constant;
+  v = v + dpp(v, integral_constant<int, 0xB1>{});   // quad_perm [1,0,3,2]
+  v = v + dpp(v, integral_constant<int, 0x4E>{});   // quad_perm [2,3,0,1]
+  v = v + dpp(v, integral_constant<int, 0x141>{});  // row_half_mirror
+  v = v + dpp(v, integral_constant<int, 0x140>{});  // row_mirror
+  auto dpp0 = [](float x, auto ctrl, auto row_mask) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, decltype(row_mask)::value, 0xf, true));
+  };
+  v += dpp0(v, integral_constant<int, 0x142>{}, integral_constant<int, 0xa>{});  // (as wave_sum)
+  v += dpp0(v, integral_constant<int, 0x143>{}, integral_constant<int, 0xc>{});
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+
 // part: kAttnThreads / 64 * NJ * 256 floats of LDS (the caller's ONE shared array); b: the utterance.
-template <int NJ>
+template <int NJ, int kVar = ATTN_BASE>
 __device__ __forceinline__ void attn_body(AttnArgs g, float* part, int b) {
+  constexpr bool kLean = kVar == ATTN_LEAN;
   // Rows that can carry weight at this step: the stepwise-monotonic update (attention.py:119-123) moves weight by at most one
   // row per step from the one-hot start, so after t steps w_prev is EXACTLY zero beyond row t, w_new beyond row t + 1 - rows
   // past that add exact zeros to the context and need neither their energies nor their memory (245 KB per utterance and step
@@ -339,6 +373,8 @@ __device__ __forceinline__ void attn_body(AttnArgs g, float* part, int b) {
     if (wv == 0) role_poll(g.q_cnt + (b / 32) * kDepLine, (unsigned int)(g.t_rel + 1) * (unsigned int)g.q_wait_n, g.ctrl);
     lds_barrier();
   }
+  const int chunk = (L + NW - 1) / NW;
+  const int l0 = wv * chunk;
   auto load_q4 = [&](const float* p) {
     if (q_here) return make_float4(load_wt(p), load_wt(p + 1), load_wt(p + 2), load_wt(p + 3));
     return *reinterpret_cast<const float4*>(p);
@@ -364,13 +400,14 @@ __device__ __forceinline__ void attn_body(AttnArgs g, float* part, int b) {
     }
   }
   auto load_row = [&](int l, float4 (&r)[NJ]) {
+    if constexpr (kVar == ATTN_ONE_ROW) l = l0;  // (measurement: see AttnVariant)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int c4 = lane + 64 * j;
       if (c4 < D4) {
         const f32x4 v = *reinterpret_cast<__attribute__((address_space(1))) const f32x4*>(mem + (size_t)l * D + c4 * 4);
         r[j] = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
+      } else if constexpr (!kLean) {
         r[j] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
@@ -384,11 +421,8 @@ __device__ __forceinline__ void attn_body(AttnArgs g, float* part, int b) {
       s = fmaf(r[j].z, qv[j].z, s);
       s = fmaf(r[j].w, qv[j].w, s);
     }
-    return wave_sum(s);
+    return kLean ? wave_sum_folded(s) : wave_sum(s);
   };
-
-  const int chunk = (L + NW - 1) / NW;
-  const int l0 = wv * chunk;
   const int l1_all = (l0 + chunk < L) ? l0 + chunk : L;  // this wave's rows [l0, l1_all): all get their (possibly zero) weight stored
 
   float4 acc[NJ];
@@ -412,27 +446,67 @@ __device__ __forceinline__ void attn_body(AttnArgs g, float* part, int b) {
     float w1_prev = 0.f;  // w[l-1] * (1 - p0[l-1])   attention.py:120
     if (l0 > 0) {
       float4 r[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) r[j] = make_float4(0.f, 0.f, 0.f, 0.f);  // (ATTN_LEAN's load_row leaves lanes past D alone)
       load_row(l0 - 1, r);
       const float p0 = isru_sigmoid(dot_row(r));  // l0-1 < L-1, never the overridden column
       w1_prev = mul_rn(w_prev_of(l0 - 1), sub_rn(1.0f, p0));
     }
     constexpr int G = 4;  // rows in flight per wave (8 measured slower, 17.2 vs 15.2 us; all 15 rows of a wave at once 18.2 vs 15.6 us at
                           // B = 256 and no faster at B = 1: the pass runs at the Infinity-Cache rate, not at a latency chain's)
+    // (ATTN_LEAN: the row registers live across the groups, zeroed once - a lane past D is never loaded and keeps its zeros)
+    float4 r_keep[G][NJ];
+    if constexpr (kLean) {
+#pragma unroll
+      for (int i = 0; i < G; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) r_keep[i][j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     for (int lb = l0; lb < l1; lb += G) {
-      float4 r[G][NJ];
+      float4 r_own[G][NJ];
+      float4 (&r)[G][NJ] = kLean ? r_keep : r_own;
       float e[G];
+      float p0_lanes = 0.f;  // ATTN_LEAN: lane i holds p0 of row lb + i
+      if constexpr (kLean) {
 #pragma unroll
-      for (int i = 0; i < G; ++i)
-        if (lb + i < l1) load_row(lb + i, r[i]);
+        for (int i = 0; i < G; ++i) load_row(lb + i < l1 ? lb + i : l1 - 1, r[i]);
 #pragma unroll
-      for (int i = 0; i < G; ++i)
-        if (lb + i < l1) e[i] = dot_row(r[i]);
+        for (int i = 0; i < G; ++i) e[i] = dot_row(r[i]);
+        float ev = e[0];
+#pragma unroll
+        for (int i = 1; i < G; ++i) ev = lane == i ? e[i] : ev;
+        p0_lanes = isru_sigmoid((lb + lane == L - 1) ? 1e4f : ev);  // attention.py:117-118, lanes 0..G-1
+      } else {
+#pragma unroll
+        for (int i = 0; i < G; ++i)
+          if (lb + i < l1) load_row(lb + i, r[i]);
+        if constexpr (kVar != ATTN_PLAIN_SUM) {
+#pragma unroll
+          for (int i = 0; i < G; ++i)
+            if (lb + i < l1) e[i] = dot_row(r[i]);
+        }
+      }
 #pragma unroll
       for (int i = 0; i < G; ++i) {
         const int l = lb + i;
+        if constexpr (kVar == ATTN_PLAIN_SUM) {  // (measurement: see AttnVariant)
+          if (l < l1) {
+            if (lanes_hold_w && lane == l - l0) wn_lane = w_prev_of(l);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+              acc[j].x += r[i][j].x; acc[j].y += r[i][j].y; acc[j].z += r[i][j].z; acc[j].w += r[i][j].w;
+            }
+          }
+          continue;
+        }
         if (l < l1) {
-          const float en = (l == L - 1) ? 1e4f : e[i];  // attention.py:117
-          const float p0 = isru_sigmoid(en);            // attention.py:118
+          float p0;
+          if constexpr (kLean) {
+            p0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, p0_lanes), i));
+          } else {
+            const float en = (l == L - 1) ? 1e4f : e[i];  // attention.py:117
+            p0 = isru_sigmoid(en);                        // attention.py:118
+          }
           const float wl = w_prev_of(l);
           const float w0 = mul_rn(wl, p0);                      // :119
           float wn = (l > 0) ? add_rn(w0, w1_prev) : w0;        // :122-123
@@ -446,10 +520,17 @@ __device__ __forceinline__ void attn_body(AttnArgs g, float* part, int b) {
           }
 #pragma unroll
           for (int j = 0; j < NJ; ++j) {
-            acc[j].x = fmaf(wn, r[i][j].x, acc[j].x);
-            acc[j].y = fmaf(wn, r[i][j].y, acc[j].y);
-            acc[j].z = fmaf(wn, r[i][j].z, acc[j].z);
-            acc[j].w = fmaf(wn, r[i][j].w, acc[j].w);
+            if constexpr (kLean) {
+              const f32x2 w2 = {wn, wn};
+              const f32x2 lo = __builtin_elementwise_fma(w2, f32x2{r[i][j].x, r[i][j].y}, f32x2{acc[j].x, acc[j].y});
+              const f32x2 hi = __builtin_elementwise_fma(w2, f32x2{r[i][j].z, r[i][j].w}, f32x2{acc[j].z, acc[j].w});
+              acc[j] = make_float4(lo[0], lo[1], hi[0], hi[1]);
+            } else {
+              acc[j].x = fmaf(wn, r[i][j].x, acc[j].x);
+              acc[j].y = fmaf(wn, r[i][j].y, acc[j].y);
+              acc[j].z = fmaf(wn, r[i][j].z, acc[j].z);
+              acc[j].w = fmaf(wn, r[i][j].w, acc[j].w);
+            }
           }
         }
       }
