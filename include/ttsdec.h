@@ -39,6 +39,8 @@ extern "C" {
  * then); ttsenc_set_precision / ttsenc_get_precision added, and exact fp32 became the default arithmetic of the ttsenc_ / ttsvits_
  * handles as it always was of the ttsdec_ ones (split-fp16 is opt-in everywhere).  The Python binding refuses a library whose ttsdec_version() differs from the version it was written for. */
 #define TTSDEC_VERSION 2
+/* (The ttsgen_ family below - the HiFi-GAN generator - was added later without a bump: it adds entry points and a struct of its
+ * own and changes none that existed, so a version-2 binding still binds every entry point it knows.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -453,6 +455,71 @@ size_t ttsvits_flow_workspace_bytes(const ttsvits_handle* h, int B, int T);
  * [B, gin_channels] (the reference's g [B, gin, 1], models.py:506, 511; modules.py:185-199), as above. */
 int ttsvits_flow_reverse(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * VITS2 HiFi-GAN generator (latent z -> waveform): Generator.forward, vits2/models.py:900-974, with ResBlock1.forward
+ * modules.py:221-315 called without x_mask - the `self.dec(...)` of SynthesizerTrn.infer, models.py:1322.  Eval mode, exact fp32
+ * (the fp32-input matrix instruction for every conv, fp32 vector ALU elsewhere).  Activations are CHANNEL-LAST: z [B, T, C].
+ *   conv_pre (7 taps) [+ cond(g)]; per upsampling stage i: leaky_relu(0.1), ConvTranspose1d(k = 2u, stride u) as a 3-tap conv
+ *   producing u output phases per input frame, then the mean of n_res ResBlock1 (three (dilated conv, conv) pairs each);
+ *   leaky_relu(0.01) (models.py:963: the default slope), conv_post (7 taps, no bias), tanh.
+ * Every conv is an implicit-im2col GEMM of the library's GEMM core; the leaky ReLUs, residual adds, branch sum and the
+ * division by n_res ride in the GEMM epilogues, conv_post + tanh is a streaming kernel (one output sample per lane).
+ * Utterances are processed in groups of G = min(B, floor((2^31 - 4096) / (4 F)), floor(65535 * 64 / T')) utterances, F = the
+ * largest activation of one utterance in floats (max(T * upsample_initial_channel, max_i T_i * C_i), T_i = T * u_0 * ... * u_i,
+ * C_i = upsample_initial_channel >> (i + 1)), T' = T * prod(up_rates): no activation buffer of a launch reaches 2 GiB, no launch
+ * has more than 65535 row tiles, and the workspace is sized for one group, not for B (ModelConfig dims at T = 600: F = 4.9 M
+ * floats, G = 27).
+ * ------------------------------------------------------------------------------------- */
+#define TTSGEN_MAX_UP 8
+#define TTSGEN_MAX_RES 4
+typedef struct ttsgen_dims {
+  int32_t initial_channel;          /* inter_channels (192): channels of z                                        */
+  int32_t upsample_initial_channel; /* 512; stage i has upsample_initial_channel >> (i + 1) channels (multiples of 4) */
+  int32_t n_up;                     /* len(upsample_rates) (4), 1..TTSGEN_MAX_UP                                   */
+  int32_t up_rates[TTSGEN_MAX_UP];  /* [8, 8, 2, 2]: even u                                                        */
+  int32_t up_kernels[TTSGEN_MAX_UP];/* [16, 16, 4, 4]: k = 2u is the only form built                               */
+  int32_t n_res;                    /* len(resblock_kernel_sizes) (3), 1..TTSGEN_MAX_RES                           */
+  int32_t res_kernels[TTSGEN_MAX_RES];       /* [3, 7, 11]: odd, <= 31                                             */
+  int32_t res_dilations[TTSGEN_MAX_RES][3];  /* [[1, 3, 5]] x 3: 1..16; a dilation > 1 needs stage channels that divide
+                                              * 32 or are multiples of 32                                         */
+  int32_t n_dil;                    /* dilations per ResBlock1: 3 (the only count built)                           */
+  int32_t resblock;                 /* 1 = ResBlock1; 2 (ResBlock2) is not built                                   */
+  int32_t gin_channels;             /* 0, or the speaker-embedding width of cond (models.py:944-945)               */
+} ttsgen_dims;
+typedef struct ttsgen_handle ttsgen_handle;
+
+/* Dimensions not built (ResBlock2, k != 2u or odd u, n_dil != 3, even resblock kernels, channels that are not multiples of 4,
+ * ...) are refused with TTSDEC_ERR_DIMS. */
+int ttsgen_create(const ttsgen_dims* dims, ttsgen_handle** out);
+int ttsgen_destroy(ttsgen_handle* h);
+const char* ttsgen_last_hip_error(const ttsgen_handle* h);
+/* Source tensors for ttsgen_pack_weights (device fp32, the reference's parameter shapes, EFFECTIVE weights - g * v / ||v|| of
+ * weight_norm folded, as after Generator.remove_weight_norm(), models.py:970-974), in this order:
+ *   conv_pre.weight [C0, initial_channel, 7], conv_pre.bias [C0];
+ *   per stage i: ups.i.weight [C_{i-1}, C_i, k_i] (ConvTranspose1d layout [in, out, k]), ups.i.bias [C_i];
+ *   per stage i, per ResBlock1 j (resblocks.{i * n_res + j}): convs1.{0,1,2}.{weight [C_i, C_i, k_j], bias},
+ *       then convs2.{0,1,2}.{weight, bias}                                                              (12 per block);
+ *   conv_post.weight [1, C_last, 7];
+ *   when gin_channels > 0: cond.weight [C0, gin, 1], cond.bias [C0].
+ * (C0 = upsample_initial_channel, C_i = C0 >> (i + 1).)  155 tensors at the ModelConfig dims. */
+int ttsgen_num_weight_tensors(const ttsgen_handle* h);
+size_t ttsgen_packed_bytes(const ttsgen_handle* h);
+int ttsgen_pack_weights(ttsgen_handle* h, const float* const* src, int n_src, void* blob, void* stream);
+int ttsgen_bind_weights(ttsgen_handle* h, const void* blob);
+/* Scratch of one call: one group of min(B, G) utterances (above); 0 when one utterance of T frames does not fit a group. */
+size_t ttsgen_workspace_bytes(const ttsgen_handle* h, int B, int T);
+/* Generator.forward (models.py:947-968): z [B, T, initial_channel] channel-last (the reference's x [B, C, T] transposed),
+ * g NULL or [B, gin_channels] (the reference's g [B, gin, 1]); out [B, T * prod(up_rates)] (the reference's [B, 1, T']).
+ * Frames are not masked (the reference's dec call has no mask): every frame of every utterance is computed.  Enqueues only -
+ * no synchronisation, no host reads.  TTSDEC_ERR_DIMS when one utterance exceeds a group's bound. */
+int ttsgen_forward(ttsgen_handle* h, const float* z, const float* g, int B, int T, float* out, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* Test aid: the same call stopped after n_stages upsampling stages (0 = after conv_pre).  B must fit one group.  The stage's
+ * activated output - leaky_relu(x, 0.1), or 0.01 after the last stage - is left at the start of the workspace as
+ * [B * T_s, C_s] fp32 (T_s = T * u_0 * ... * u_{n_stages-1}, C_s its channels; conv_pre: [B * T, C0]); nothing is written to out. */
+int ttsgen_forward_stages(ttsgen_handle* h, const float* z, const float* g, int B, int T, int n_stages, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 #ifdef __cplusplus
 }

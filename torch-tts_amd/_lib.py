@@ -82,6 +82,20 @@ SYMBOLS = (
     "ttsvits_flow_workspace_bytes",
     "ttsvits_flow_reverse",
 )
+# the HiFi-GAN generator's family (include/ttsdec.h ttsgen_*), kept apart from SYMBOLS: tests/test_host_logic.py matches SYMBOLS against
+# the header's ttsdec_ / ttsenc_ / ttsvits_ declarations
+GEN_SYMBOLS = (
+    "ttsgen_create",
+    "ttsgen_destroy",
+    "ttsgen_last_hip_error",
+    "ttsgen_num_weight_tensors",
+    "ttsgen_packed_bytes",
+    "ttsgen_pack_weights",
+    "ttsgen_bind_weights",
+    "ttsgen_workspace_bytes",
+    "ttsgen_forward",
+    "ttsgen_forward_stages",
+)
 ENC_W_COUNT = 20
 
 
@@ -119,6 +133,16 @@ class VitsDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_vocab", "inter_channels", "hidden_channels", "filter_channels", "n_heads", "n_layers", "kernel_size", "window_size",
         "flow_hidden", "flow_kernel", "flow_wn_layers", "n_flows", "flow_tf_layers", "flow_tf_heads", "flow_tf_kernel", "gin_channels", "cond_layer_idx")]
+
+
+GEN_MAX_UP, GEN_MAX_RES = 8, 4  # include/ttsdec.h TTSGEN_MAX_UP / TTSGEN_MAX_RES
+
+
+class GenDims(C.Structure):  # include/ttsdec.h ttsgen_dims
+    _fields_ = [("initial_channel", C.c_int32), ("upsample_initial_channel", C.c_int32), ("n_up", C.c_int32),
+                ("up_rates", C.c_int32 * GEN_MAX_UP), ("up_kernels", C.c_int32 * GEN_MAX_UP), ("n_res", C.c_int32),
+                ("res_kernels", C.c_int32 * GEN_MAX_RES), ("res_dilations", (C.c_int32 * 3) * GEN_MAX_RES), ("n_dil", C.c_int32),
+                ("resblock", C.c_int32), ("gin_channels", C.c_int32)]
 
 
 class TtsdecError(RuntimeError):
@@ -270,6 +294,26 @@ def load() -> C.CDLL:
         lib.ttsvits_flow_workspace_bytes.argtypes = [vp, i32, i32]
         lib.ttsvits_flow_reverse.restype = i32
         lib.ttsvits_flow_reverse.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
+        lib.ttsgen_create.restype = i32
+        lib.ttsgen_create.argtypes = [C.POINTER(GenDims), C.POINTER(vp)]
+        lib.ttsgen_destroy.restype = i32
+        lib.ttsgen_destroy.argtypes = [vp]
+        lib.ttsgen_last_hip_error.restype = C.c_char_p
+        lib.ttsgen_last_hip_error.argtypes = [vp]
+        lib.ttsgen_num_weight_tensors.restype = i32
+        lib.ttsgen_num_weight_tensors.argtypes = [vp]
+        lib.ttsgen_packed_bytes.restype = sz
+        lib.ttsgen_packed_bytes.argtypes = [vp]
+        lib.ttsgen_pack_weights.restype = i32
+        lib.ttsgen_pack_weights.argtypes = [vp, C.POINTER(vp), i32, vp, vp]
+        lib.ttsgen_bind_weights.restype = i32
+        lib.ttsgen_bind_weights.argtypes = [vp, vp]
+        lib.ttsgen_workspace_bytes.restype = sz
+        lib.ttsgen_workspace_bytes.argtypes = [vp, i32, i32]
+        lib.ttsgen_forward.restype = i32
+        lib.ttsgen_forward.argtypes = [vp, vp, vp, i32, i32, vp, vp, sz, vp]
+        lib.ttsgen_forward_stages.restype = i32
+        lib.ttsgen_forward_stages.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, vp]
         _lib = lib
         return _lib
 

@@ -48,6 +48,42 @@ struct LoaderConv {
   __device__ __forceinline__ unsigned row_off(int r, int) const { return (unsigned)r * (unsigned)Cin * EB; }
 };
 
+// ... and with dilation d (GemmArgs A_CONV_DIL; buffer-descriptor loads only): tap j of frame m reads frame m + (j - taps/2)*d, so
+// k = j*Cin + c sits at byte (k + j*(d-1)*Cin)*EB from the window's base.  When Cin is a multiple of the K tile KT, a tile lies in
+// one tap and the walk jumps (d-1)*Cin*EB every Cin/KT tiles (gemm_tile kTapJump); when Cin divides KT, a tile holds KT/Cin whole
+// taps: each tile advances KT*d elements and a lane adds its own column's tap offset once (col_off).
+template <int EB>
+struct LoaderConvDil {
+  const void* x;
+  int m0, M, T, Cin, taps, K, d;  // d >= 1
+  static constexpr bool kRange = true, kTapJump = true;
+  __device__ __forceinline__ int nseg() const { return 1; }
+  __device__ __forceinline__ int seglen(int i) const { return i == 0 ? K : 0; }
+  __device__ __forceinline__ bool row_ok(int r) const { return m0 + r < M; }
+  __device__ __forceinline__ gbyte* row_ptr(int r, int, int) const {
+    return as_global(x) + (((long)(m0 + r) - (taps >> 1) * d) * Cin) * EB;
+  }
+  // valid taps of frame t: 0 <= t + (j - taps/2)*d < T
+  __device__ __forceinline__ int k_lo(int r) const {
+    const int t = (m0 + r) % T, lo = (taps >> 1) - t / d;
+    return (lo > 0 ? lo : 0) * Cin;
+  }
+  __device__ __forceinline__ int k_hi(int r) const {
+    const int t = (m0 + r) % T;
+    const int hi = ((taps >> 1) + (T - 1 - t) / d + 1) * Cin;
+    return hi < K ? hi : K;
+  }
+  __device__ __forceinline__ long col_off(int c16) const { return (long)c16 * 16 + (long)((c16 * 16 / EB) / Cin) * (d - 1) * Cin * EB; }
+  // (Cin == KT takes the tap-jump walk: one tile per tap)
+  __device__ __forceinline__ long tile_inc(int rowb) const { return Cin < rowb / EB ? (long)rowb * d : rowb; }
+  __device__ __forceinline__ int tap_tiles(int kt) const { return Cin >= kt ? Cin / kt : 0x7fffffff; }
+  __device__ __forceinline__ unsigned tap_jump(int) const { return (unsigned)((d - 1) * Cin * EB); }
+  __device__ __forceinline__ const void* seg_base(int, int) const {
+    return static_cast<const char*>(x) + ((long)m0 - (taps >> 1) * d) * Cin * EB;
+  }
+  __device__ __forceinline__ unsigned row_off(int r, int) const { return (unsigned)r * (unsigned)Cin * EB; }
+};
+
 // rows n0.. of a PyTorch-layout weight [N, K] cut into the same K segments as A
 template <int EB>
 struct LoaderW {
@@ -110,7 +146,7 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void gemm_rows_ke
   // different XCDs and each L2 fetches that A tile again.  Remap so that all column tiles of a row tile
   // run on the same XCD: id -> (xcd = id % 8, slot = id / 8) -> row tile (slot / nx) * 8 + xcd.
   int bx = blockIdx.x, by = blockIdx.y;
-  if (AK == A_CONV || Cfg::kBig) {
+  if (AK != A_PLAIN || Cfg::kBig) {
     const int nx = gridDim.x, ny = gridDim.y;
     const int id = by * nx + bx, full = (ny / 8) * 8;
     if (id < full * nx) {
@@ -174,7 +210,11 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void gemm_rows_ke
   }
 
   constexpr int EB = Cfg::EB;
-  if (AK == A_CONV) {
+  if constexpr (AK == A_CONV_DIL) {
+    const LoaderConvDil<EB> la{g.a.p0, m0, g.M, g.T, g.Cin, g.taps, g.K, g.dil > 1 ? g.dil : 1};
+    const LoaderW<EB> lb{make_seg1(g.W, g.ldw, g.K), make_seg1(g.W_lo, g.ldw, g.K), n0, g.N};
+    gemm_tile<Cfg, LoaderConvDil<EB>, LoaderW<EB>, NoGate, 2>(la, lb, smem, live);
+  } else if (AK == A_CONV) {
     const LoaderConv<EB> la{g.a.p0, g.a_lo.p0, m0, g.M, g.T, g.Cin, g.taps, g.K};
     const LoaderW<EB> lb{make_seg1(g.W, g.ldw, g.K), make_seg1(g.W_lo, g.ldw, g.K), n0, g.N};
     // (one K segment, both operands based at the workgroup's own first row: the buffer-descriptor loaders of gemm_tile.h apply
@@ -308,6 +348,15 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void gemm_rows_ke
       v = add_rn(pr, v);
       g.out[o] = v;
       store16(v);
+    } else if (EK == EPI_LRELU2) {
+      // vits2/models.py:949-963, modules.py:296-309 (generator.hip): conv (+ cond(g)) (+ x) (xs +) (/ num_kernels), then the value
+      // and / or its leaky ReLU
+      if (g.rowvec != nullptr) v = add_rn(v, g.rowvec[(size_t)(m / g.T) * g.N + n]);
+      if (g.resid != nullptr) v = add_rn(v, g.resid[o]);
+      if (g.sum != nullptr) v = add_rn(g.sum[o], v);
+      if (g.div != 0.f) v = div_rn(v, g.div);
+      if (g.out != nullptr) g.out[o] = v;
+      if (g.out2 != nullptr) g.out2[o] = v > 0.f ? v : mul_rn(v, g.slope2);
     }
   }
   // the 16-bit copies in a loop of their own per kind: the kind is the same for every output, and tested per output it cut
@@ -387,6 +436,21 @@ static void launch_gemm_cfg(const GemmArgs& a, hipStream_t st) {
   }
 }
 
+// the generator's convs (A_CONV_DIL + EPI_LRELU2, exact fp32): a 128 x 32 tile where N is 32 (HiFi-GAN's last stage - the 64 x 64
+// tile would leave half its columns empty), the 64 x 64 tile elsewhere; both have 32-k tiles (LoaderConvDil's tap walk)
+static void launch_gemm_dil(const GemmArgs& a, hipStream_t st) {
+  constexpr int AK = A_CONV_DIL, EK = EPI_LRELU2;
+  if (a.N <= 32) {
+    using Cfg = TileCfg<4, 1, 1, 4>;
+    dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM);
+    hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
+  } else {
+    using Cfg = TileCfg<2, 2, 1, 4>;
+    dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM);
+    hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
+  }
+}
+
 template <int AK, int EK>
 static void launch_gemm_prec(const GemmArgs& a, hipStream_t st) {
   if (a.prec == PREC_F16S) return launch_gemm_cfg<AK, EK, PREC_F16S>(a, st);
@@ -396,6 +460,10 @@ static void launch_gemm_prec(const GemmArgs& a, hipStream_t st) {
 
 void launch_gemm(const GemmArgs& a, AKind ak, EpiKind ek, hipStream_t st) {
   if (a.M <= 0 || a.N <= 0) return;
+  if (ak == A_CONV_DIL) {
+    if (ek == EPI_LRELU2 && a.prec == PREC_F32) launch_gemm_dil(a, st);
+    return;
+  }
   if (ak == A_CONV && ek == EPI_BN_ISRU) return launch_gemm_prec<A_CONV, EPI_BN_ISRU>(a, st);
   if (ak == A_CONV && ek == EPI_BN_LRELU) return launch_gemm_prec<A_CONV, EPI_BN_LRELU>(a, st);
   if (ak == A_CONV && ek == EPI_BN_ISRLU) return launch_gemm_prec<A_CONV, EPI_BN_ISRLU>(a, st);

@@ -178,6 +178,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
   return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, (int)kBufRange, 0x00020000);
 }
 
+// Dilated implicit im2col (decode_kernels.hip LoaderConvDil): an A loader with kTapJump = true steps its K walk by
+// tile_inc(ROWB) per tile and, every tap_tiles(KT) tiles, by tap_jump(KT) bytes more (the (d - 1) * Cin frames a dilated tap
+// skips).  Buffer-descriptor form only (kBufDma); loaders without the member keep the plain walk.
+template <class L, class = void>
+struct TapJumpOf { static constexpr bool value = false; };
+template <class L>
+struct TapJumpOf<L, std::void_t<decltype(L::kTapJump)>> { static constexpr bool value = L::kTapJump; };
+
 template <class Cfg, class LoaderA, class LoaderB, class Gate = NoGate, int kBufDma = 0>
 __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, float* smem, bool live = true,
                                           int dbg = 0, const Gate gate = Gate()) {
@@ -354,6 +362,14 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
     enter_seg(0);
     int seg = 0, left = nt0, seg_len = len0, kpos = 0, istage = 0;
     unsigned soa = 0, sob = 0;  // scalar byte offsets of the current tile inside the segment
+    constexpr bool kTap = TapJumpOf<LoaderA>::value;
+    int tap_tiles = 0;
+    unsigned tap_jump = 0;
+    if constexpr (kTap) {
+      tap_tiles = la.tap_tiles(KT);
+      tap_jump = (unsigned)__builtin_amdgcn_readfirstlane((int)la.tap_jump(KT));
+    }
+    int tap_left = tap_tiles;
 
     auto dma_a = [&](const __amdgpu_buffer_rsrc_t& r, char* dst, unsigned voff, unsigned soff) {
       // (size, immediate offset and cache-policy arguments of the builtin must be literals)
@@ -412,6 +428,12 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
       kpos += KT;
       soa += inca;
       sob += incb;
+      if constexpr (kTap) {
+        if (--tap_left == 0) {
+          soa += tap_jump;
+          tap_left = tap_tiles;
+        }
+      }
       if (--left == 0) {  // next segment (or, past the last one, out-of-range loads that keep vmcnt uniform)
         ++seg;
         kpos = 0;

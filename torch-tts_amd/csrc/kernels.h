@@ -5,13 +5,17 @@
 namespace ttsdec {
 
 // ---- generic row-GEMM (PreNet layers, query projection, mel/stop projection, postnet) ----
-enum AKind { A_PLAIN = 0, A_CONV = 1 };
-enum EpiKind { EPI_PLAIN = 0, EPI_RELU_DROPOUT = 1, EPI_PROJ = 2, EPI_BN_ISRU = 3, EPI_RESIDUAL = 4, EPI_BN_LRELU = 5, EPI_BN_ISRLU = 6, EPI_GENERIC = 7 };
+// A_CONV_DIL: A_CONV with dilation `dil` (exact fp32, EPI_LRELU2 only; the HiFi-GAN generator, generator.hip)
+enum AKind { A_PLAIN = 0, A_CONV = 1, A_CONV_DIL = 2 };
+enum EpiKind { EPI_PLAIN = 0, EPI_RELU_DROPOUT = 1, EPI_PROJ = 2, EPI_BN_ISRU = 3, EPI_RESIDUAL = 4, EPI_BN_LRELU = 5, EPI_BN_ISRLU = 6, EPI_GENERIC = 7,
+               EPI_LRELU2 = 8 };
 
 struct GemmArgs {
   // A operand.  A_PLAIN: up to three K segments of an [M, K] activation.
   // A_CONV: implicit im2col of x [Bc*T, Cin] with `taps` taps centred on the row's frame:
   //         A[m][tap*Cin + c] = x[b, t + tap - taps/2, c] (zero outside [0, T)).
+  // A_CONV_DIL: A[m][tap*Cin + c] = x[b, t + (tap - taps/2)*d, c], d = max(dil, 1) (below; padding get_padding(k, d) =
+  //         d(k-1)/2 keeps the conv centred); needs Cin % 4 == 0 and, for d > 1, Cin | 32 or 32 | Cin (the K tile of its tiles).
   Seg3 a;
   Seg3 a_lo;            // second plane of A (split-fp16 lo), same shape; 16-bit modes only
   int T, Cin, taps;
@@ -68,6 +72,18 @@ struct GemmArgs {
   int slot;
   int node;  // position of the launch in the step order (measurement: common.h loop_stamp)
   int t;  // absolute step index when ctrl == nullptr
+  // A_CONV_DIL: the dilation (0 and 1 both mean none, so a zero-initialised GemmArgs stays an undilated conv)
+  int dil;
+  // EPI_LRELU2 (exact fp32; the HiFi-GAN generator's layers, generator.hip):
+  //   v = acc + bias[n];  v = v + rowvec[(m / T) * N + n]  (rowvec: one row per utterance, e.g. cond(g));
+  //   v = v + resid[m, n];  v = sum[m, n] + v;  v = v / div  (a true division; div = 0: none);
+  //   out[m, n] = v;  out2[m, n] = leaky_relu(v, slope2) = v > 0 ? v : v * slope2.
+  // bias / rowvec / resid / sum / out / out2 may each be nullptr; resid, sum, out and out2 share ldo, and may alias out / out2
+  // elementwise (every element is read and written by one thread).
+  float* out2;
+  float slope2, div;
+  const float* sum;
+  const float* rowvec;
 };
 
 void launch_gemm(const GemmArgs& a, AKind ak, EpiKind ek, hipStream_t st);

@@ -4,9 +4,11 @@
                                              ``forward(x, x_lengths, g=None) -> (x, m, logs, x_mask)``)
 * ``ResidualCouplingTransformersBlock``   - vits2/models.py:681-810 with ``transformer_flow_type="pre_conv"``
                                              (``forward(x, x_mask, g=None, reverse=True)``)
+* ``Generator`` (+ ``ResBlock1``)         - the HiFi-GAN generator, vits2/models.py:900-974 and modules.py:221-315
+                                             (``forward(x, g=None) -> [B, 1, T * prod(upsample_rates)]``; ``ttsgen_*``)
 
-Both hold the reference's parameters (so checkpoints load) and run inference through the HIP library
-(``ttsvits_*`` in include/ttsdec.h).  The library works on channel-last activations; the [B, C, T]
+All hold the reference's parameters (so checkpoints load) and run inference through the HIP library
+(``ttsvits_*`` / ``ttsgen_*`` in include/ttsdec.h).  The library works on channel-last activations; the [B, C, T]
 tensors of the reference API are transposed here.  Training / the forward (non-reverse) direction of
 the flow / speaker conditioning are outside the path and raise."""
 from __future__ import annotations
@@ -372,3 +374,252 @@ class ResidualCouplingTransformersBlock(PackedWeightsMixin, nn.Module):
         lengths = x_mask[:, 0, :].sum(dim=1).round().to(torch.int32)  # sequence_mask is a prefix mask
         out = eng.flow_reverse(x.transpose(1, 2), lengths, g)
         return out.transpose(1, 2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# HiFi-GAN generator (models.py:900-974): z -> waveform through ttsgen_* (include/ttsdec.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+LRELU_SLOPE = 0.1  # modules.LRELU_SLOPE
+
+
+def _get_padding(kernel_size, dilation=1):  # commons.py:14-15
+    return int((kernel_size * dilation - dilation) / 2)
+
+
+def _effective_weight(conv: nn.Module) -> torch.Tensor:
+    """The weight a conv applies: g * v / ||v|| while torch.nn.utils.weight_norm is on (dim 0 - for a ConvTranspose1d weight
+    [in, out, k] that is per INPUT channel, as the reference's ups.i.weight_g [in, 1, 1] says), else the plain weight."""
+    if hasattr(conv, "weight_g"):
+        return torch._weight_norm(conv.weight_v, conv.weight_g, 0)
+    return conv.weight
+
+
+class ResBlock1(nn.Module):
+    """modules.ResBlock1 parameter layout (modules.py:221-294): convs1 (dilated) and convs2, weight-normalised.  Runs only as a
+    part of ``Generator`` (the library fuses its layers into the generator's GEMM epilogues)."""
+
+    def __init__(self, channels, kernel_size=3, dilation=(1, 3, 5)):
+        super().__init__()
+        wn = nn.utils.weight_norm
+        self.channels, self.kernel_size, self.dilation = channels, kernel_size, tuple(dilation)
+        self.convs1 = nn.ModuleList(wn(nn.Conv1d(channels, channels, kernel_size, 1, dilation=d, padding=_get_padding(kernel_size, d)))
+                                    for d in dilation)
+        self.convs2 = nn.ModuleList(wn(nn.Conv1d(channels, channels, kernel_size, 1, dilation=1, padding=_get_padding(kernel_size, 1)))
+                                    for _ in dilation)
+        for c in list(self.convs1) + list(self.convs2):  # commons.init_weights
+            c.weight_v.data.normal_(0.0, 0.01)
+
+    def remove_weight_norm(self):
+        for c in list(self.convs1) + list(self.convs2):
+            nn.utils.remove_weight_norm(c)
+
+    def weight_tensors(self) -> List[torch.Tensor]:
+        out = []
+        for c in list(self.convs1) + list(self.convs2):
+            out += [_effective_weight(c), c.bias]
+        return out
+
+
+class GenEngine:
+    """One ttsgen handle on one device."""
+
+    def __init__(self, dims: Dict, device: torch.device):
+        self._lib = _lib.load()
+        self.device = device
+        self.dims = dims
+        d = _lib.GenDims()
+        d.initial_channel, d.upsample_initial_channel = dims["initial_channel"], dims["upsample_initial_channel"]
+        d.n_up, d.n_res = len(dims["upsample_rates"]), len(dims["resblock_kernel_sizes"])
+        if d.n_up > _lib.GEN_MAX_UP or d.n_res > _lib.GEN_MAX_RES:
+            raise NotImplementedError("more upsampling stages / resblocks than the library's ttsgen_dims holds")
+        for i, (u, k) in enumerate(zip(dims["upsample_rates"], dims["upsample_kernel_sizes"])):
+            d.up_rates[i], d.up_kernels[i] = u, k
+        n_dil = {len(ds) for ds in dims["resblock_dilation_sizes"]}
+        d.n_dil = n_dil.pop() if len(n_dil) == 1 else -1
+        for j, (k, ds) in enumerate(zip(dims["resblock_kernel_sizes"], dims["resblock_dilation_sizes"])):
+            d.res_kernels[j] = k
+            for l, dl in enumerate(list(ds)[:3]):
+                d.res_dilations[j][l] = dl
+        d.resblock = 1 if str(dims["resblock"]) == "1" else 2
+        d.gin_channels = dims["gin_channels"]
+        h = C.c_void_p()
+        with torch.cuda.device(device):
+            rc = self._lib.ttsgen_create(C.byref(d), C.byref(h))
+        if rc == _lib.ERR_DIMS:
+            raise NotImplementedError(f"these generator dimensions are not built in the HIP library (include/ttsdec.h ttsgen_dims): {dims}")
+        _lib.check(rc, "ttsgen_create")
+        self._h = h
+        self.blob: Optional[torch.Tensor] = None
+        self._fingerprint = None
+        self._ws: Optional[torch.Tensor] = None
+        self.up_total = math.prod(dims["upsample_rates"])
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ttsgen_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _err(self, rc, what):
+        if rc != _lib.OK:
+            raise _lib.TtsdecError(rc, what, self._lib.ttsgen_last_hip_error(self._h).decode())
+
+    def ensure_packed(self, tensors, key_tensors) -> None:
+        fp = weights_fingerprint(list(key_tensors))
+        if self.blob is not None and fp == self._fingerprint:
+            return
+        tensors = tensors()
+        n = len(tensors)
+        assert n == int(self._lib.ttsgen_num_weight_tensors(self._h)), (n, int(self._lib.ttsgen_num_weight_tensors(self._h)))
+        arr = (C.c_void_p * n)()
+        keep = []
+        for i, t in enumerate(tensors):
+            _require_device(t, "generator weights")
+            tc = t.detach().to(torch.float32).contiguous()
+            keep.append(tc)
+            arr[i] = tc.data_ptr()
+        with torch.cuda.device(self.device):
+            blob = torch.empty(self._lib.ttsgen_packed_bytes(self._h), dtype=torch.uint8, device=self.device)
+            rc = self._lib.ttsgen_pack_weights(self._h, arr, n, blob.data_ptr(), _stream(self.device))
+            torch.cuda.current_stream(self.device).synchronize()  # `keep` must outlive the packing kernels
+        self._err(rc, "ttsgen_pack_weights")
+        self.blob, self._fingerprint = blob, fp
+
+    def workspace(self, B: int, T: int) -> torch.Tensor:
+        nbytes = int(self._lib.ttsgen_workspace_bytes(self._h, B, T))
+        if nbytes == 0:
+            raise NotImplementedError(f"one utterance of {T} frames exceeds the generator's 2-GiB group bound")
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def forward(self, z_cl: torch.Tensor, g: Optional[torch.Tensor], n_stages: Optional[int] = None) -> torch.Tensor:
+        """z_cl [B, T, C] channel-last fp32 -> [B, T * prod(u)]; n_stages (test aid): the activated output of that many stages,
+        [B * T_s, C_s], read from the workspace (ttsgen_forward_stages)."""
+        B, T, _ = z_cl.shape
+        ws = self.workspace(B, T)
+        gp = g.data_ptr() if g is not None else None
+        with torch.cuda.device(self.device):
+            if n_stages is None:
+                out = torch.empty(B, T * self.up_total, device=self.device)
+                rc = self._lib.ttsgen_forward(self._h, z_cl.data_ptr(), gp, B, T, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
+                self._err(rc, "ttsgen_forward")
+                return out
+            rc = self._lib.ttsgen_forward_stages(self._h, z_cl.data_ptr(), gp, B, T, n_stages, ws.data_ptr(), ws.numel(), _stream(self.device))
+        self._err(rc, "ttsgen_forward_stages")
+        rates = self.dims["upsample_rates"][:n_stages]
+        Ts = T * math.prod(rates)
+        Cs = self.dims["upsample_initial_channel"] >> n_stages
+        return ws[: B * Ts * Cs * 4].view(torch.float32).view(B, Ts, Cs).clone()
+
+
+class _GenEngCache(_EngCache):
+    def get(self, dims, device) -> GenEngine:
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        eng = self.by_dev.get(key)
+        if eng is None:
+            eng = GenEngine(dims, torch.device("cuda", key))
+            self.by_dev[key] = eng
+        return eng
+
+    def __deepcopy__(self, memo):
+        return _GenEngCache()
+
+
+class Generator(PackedWeightsMixin, nn.Module):
+    """models.Generator (models.py:900-974): same constructor, parameters and state-dict keys (weight-normalised ``ups`` and
+    ``resblocks``; ``remove_weight_norm()`` turns them into plain ``weight``s, and both forms load and run).  ``forward(x
+    [B, C, T], g=None) -> [B, 1, T * prod(upsample_rates)]`` runs in the HIP library in exact fp32; inference only."""
+
+    def __init__(self, initial_channel, resblock, resblock_kernel_sizes, resblock_dilation_sizes, upsample_rates, upsample_initial_channel,
+                 upsample_kernel_sizes, gin_channels=0):
+        super().__init__()
+        self._watch_state_dict_loads()
+        if str(resblock) != "1":
+            raise NotImplementedError("only ResBlock1 (resblock='1', the ModelConfig default) is built in the HIP library")
+        self.num_kernels = len(resblock_kernel_sizes)
+        self.num_upsamples = len(upsample_rates)
+        self._cfg = dict(initial_channel=initial_channel, resblock=str(resblock), resblock_kernel_sizes=list(resblock_kernel_sizes),
+                         resblock_dilation_sizes=[list(d) for d in resblock_dilation_sizes], upsample_rates=list(upsample_rates),
+                         upsample_initial_channel=upsample_initial_channel, upsample_kernel_sizes=list(upsample_kernel_sizes),
+                         gin_channels=gin_channels)
+        self.conv_pre = nn.Conv1d(initial_channel, upsample_initial_channel, 7, 1, padding=3)
+        self.ups = nn.ModuleList()
+        for i, (u, k) in enumerate(zip(upsample_rates, upsample_kernel_sizes)):
+            self.ups.append(nn.utils.weight_norm(nn.ConvTranspose1d(upsample_initial_channel // (2**i), upsample_initial_channel // (2 ** (i + 1)),
+                                                                    k, u, padding=(k - u) // 2)))
+        self.resblocks = nn.ModuleList()
+        ch = upsample_initial_channel
+        for i in range(len(self.ups)):
+            ch = upsample_initial_channel // (2 ** (i + 1))
+            for k, d in zip(resblock_kernel_sizes, resblock_dilation_sizes):
+                self.resblocks.append(ResBlock1(ch, k, d))
+        self.conv_post = nn.Conv1d(ch, 1, 7, 1, padding=3, bias=False)
+        for u in self.ups:  # commons.init_weights
+            u.weight_v.data.normal_(0.0, 0.01)
+        self.gin_channels = gin_channels
+        if gin_channels != 0:
+            self.cond = nn.Conv1d(gin_channels, upsample_initial_channel, 1)
+        self._engines = _GenEngCache()
+
+    def remove_weight_norm(self):
+        for l in self.ups:
+            nn.utils.remove_weight_norm(l)
+        for l in self.resblocks:
+            l.remove_weight_norm()
+        self.invalidate()
+
+    def weight_tensors(self) -> List[torch.Tensor]:
+        """The effective fp32 weights in ttsgen_pack_weights' order (include/ttsdec.h)."""
+        out = [self.conv_pre.weight, self.conv_pre.bias]
+        for u in self.ups:
+            out += [_effective_weight(u), u.bias]
+        for rb in self.resblocks:
+            out += rb.weight_tensors()
+        out.append(self.conv_post.weight)
+        if self.gin_channels:
+            out += [self.cond.weight, self.cond.bias]
+        return out
+
+    def _engine(self, x: torch.Tensor) -> GenEngine:
+        if not x.is_cuda or any(not p.is_cuda for p in self.parameters()):
+            raise NotImplementedError("the HIP generator runs on a ROCm device only: move the module and its input there")
+        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
+            raise NotImplementedError("the HIP generator is exact fp32: input and parameters must be torch.float32")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("the HIP generator is inference-only: call under torch.no_grad()")
+        eng = self._engines.get(self._cfg, x.device)
+        eng.ensure_packed(self.weight_tensors, key_tensors=list(self.parameters()))
+        return eng
+
+    def _speaker(self, g: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
+        if g is None:
+            return None
+        if not self.gin_channels:
+            raise ValueError("g was given to a generator built with gin_channels = 0")
+        _require_device(g, "g")
+        if g.dim() == 3:
+            if g.shape[2] != 1:
+                raise NotImplementedError("a time-varying g [B, gin, T] is outside the HIP path (the reference's callers pass [B, gin, 1])")
+            g = g[:, :, 0]
+        if tuple(g.shape) != (B, self.gin_channels):
+            raise ValueError(f"g must be [B, gin_channels(, 1)] = [{B}, {self.gin_channels}(, 1)], got {tuple(g.shape)}")
+        return g.to(torch.float32).contiguous()
+
+    def forward(self, x, g=None):
+        eng = self._engine(x)
+        B = x.shape[0]
+        out = eng.forward(x.transpose(1, 2).contiguous(), self._speaker(g, B))  # (a copy also makes infer's sliced z contiguous)
+        return out.unsqueeze(1)
+
+    def stage_outputs(self, x, g=None, n_stages=0) -> torch.Tensor:
+        """Test aid: the activated output of the first ``n_stages`` upsampling stages (0: conv_pre's), channel-last
+        [B, T_s, C_s] - leaky_relu(x, 0.1), or 0.01 after the last stage."""
+        eng = self._engine(x)
+        return eng.forward(x.transpose(1, 2).contiguous(), self._speaker(g, x.shape[0]), n_stages=n_stages)
