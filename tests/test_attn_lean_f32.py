@@ -1,7 +1,7 @@
 """The exact-fp32 attention pass beside the decoder LSTM (fused_kernels.hip attn_lstm_kernel, 64 x 16 LSTM tile, B > 96).
 
 The shipped form (step_bodies.h ATTN_LEAN) does the base pass's arithmetic in the base pass's order on fewer vector-ALU
-instructions, so it must match the base form (option merged_tune bits 16-19 = 1) bit for bit; and the schedule bench.py's
+instructions, so it must match the base form (option attn_form = 1) bit for bit; and the schedule bench.py's
 headline runs must match the oracle over a full 600-frame Philox decode."""
 import pytest
 import torch
@@ -9,7 +9,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 RTOL, ATOL = 1e-4, 1e-5
-BASE_FORM = 1 << 16  # merged_tune: the attention pass in its base form
+BASE_FORM = 1  # attn_form: the attention pass in its base form
 
 
 @pytest.fixture(scope="module")
@@ -56,8 +56,8 @@ def test_lean_attention_pass_is_bit_identical_to_the_base_pass(H, B, L):
     g = torch.Generator().manual_seed(1234)
     mem = torch.tanh(torch.randn(B, L, 512, generator=g) * 0.5).to(dev)
     NF = 600
-    shipped = _decode(eng, mem, NF, {"merged_tune": -1})
-    base = _decode(eng, mem, NF, {"merged_tune": BASE_FORM})
+    shipped = _decode(eng, mem, NF, {"attn_form": -1})
+    base = _decode(eng, mem, NF, {"attn_form": BASE_FORM})
     assert eng.precision() == "f32"
     for name, a, b in zip("ysw", shipped, base):
         assert torch.isfinite(a).all(), name
@@ -73,7 +73,7 @@ def test_shipped_f32_b256_schedule_vs_oracle_600_frames_philox(H):
     dec = model.decoder
     dec.precision, dec.dropout_source, dec.dropout_seed = "f32", "philox", 123
     eng = dec.engine(torch.device("cuda:0"))
-    eng.set_option("merged_tune", -1)
+    eng.set_option("attn_form", -1)
     eng.set_option("query_role", -1)
     with torch.no_grad():
         y, s, w = dec(mem, None, None, 599)

@@ -360,7 +360,7 @@ def test_blob_key_sees_invalidate_but_not_data_edits():
 def test_options_api_and_env_presets_host_only(monkeypatch):
     """ttsdec_set_option / get_option / option_name and the TTSDEC_OPTIONS preset (include/ttsdec.h): host-only, no GPU."""
     ids = _lib.option_ids()
-    assert {"graph", "overlap", "chunk_a", "chunk_b", "proj_regw", "head_proj", "query_role", "profile_ablation", "debug_flags", "spin_limit"} <= set(ids)
+    assert {"graph", "overlap", "chunk_a", "chunk_b", "proj_regw", "head_proj", "query_role", "attn_form", "profile_ablation", "debug_flags", "spin_limit"} <= set(ids)
     assert _lib.load().ttsdec_option_name(len(ids)) is None and _lib.load().ttsdec_option_name(-1) is None
     e = T.Engine(T.EngineDims(postnet_layers=3), None)
     assert all(e.get_option(n) in (-1, 0) for n in ids)  # library defaults

@@ -86,13 +86,13 @@ struct ttsdec_handle {
   // moved from ds_bpermute to DPP (common.h wave_sum) level 2 LOST from 192 utterances on (B = 256: 80.8 / 86.1): the role's
   // LDS-path shuffles queued behind the co-resident LSTM workgroup's LDS traffic, the attention workgroups finished late and
   // every LSTM workgroup waited for the slowest of them.  (Split-fp16; exact fp32: see overlap_level.)
-  // Option "overlap" = 0 / 1 / 2.
+  // Option "overlap" = 0 / 1 / 2 (a larger value means 2).
   int overlap;
   bool chunk_a, chunk_b;  // chunked layout of the activation planes / LSTM weight planes (options "chunk_a" / "chunk_b")
   bool proj_regw;         // mel/stop projection on the register-weight kernel where it applies (option "proj_regw")
   int opt_graph, opt_chunk_a, opt_chunk_b, opt_proj_regw;  // the options behind those four: -1 = default (on), 0, 1
   int head_proj;          // that projection as a role at the head of the NEXT step's frame launch: 1 / 0, -1 = by batch size; TTSDEC_HEAD_PROJ
-  int merged_tune;        // measurement: knobs of the one-launch step (include/ttsdec.h)
+  int attn_form;          // measurement: the form of the exact-fp32 attention pass on the 64 x 16 tile (include/ttsdec.h)
   int query_role;         // attention query as a job of the attention role's workgroups (step_order): 1 / 0, -1 = default
   int profile_ablation;   // ttsdec_profile_step only: the kernels' dbg switches (measurement ablations)
   int debug_flags;        // test hooks, copied into Ctrl::debug_flags: bit 0 = the frame role does not signal, bit 1 = the attention
@@ -375,9 +375,8 @@ struct StepIo {
 // N_AG / N_DG are those LSTMs alone on the lean tile (profiling).  N_JFA = N_FA with the PREVIOUS step's mel/stop projection as a
 // role at its head (then no N_J in the step), N_JFIN = the projection of a call's last step.
 // N_QTD = N_TD whose attention-role workgroups first compute the query GEMM between them (then no N_Q in the step).
-// N_STEP = N_JFA + N_QTD as one launch.
 // N_JF = [proj(t-1) | frame] as one launch (no LSTM role).
-enum Node { N_F, N_FIN, N_P0, N_P1, N_A, N_Q, N_T, N_D, N_J, N_FA, N_TD, N_AG, N_DG, N_JFA, N_JFIN, N_QTD, N_STEP, N_JF };
+enum Node { N_F, N_FIN, N_P0, N_P1, N_A, N_Q, N_T, N_D, N_J, N_FA, N_TD, N_AG, N_DG, N_JFA, N_JFIN, N_QTD, N_JF };
 // PART_GATED: the whole cell with the segment that waits for the other role of the launch LAST
 enum LstmPart { PART_WHOLE = 0, PART_EARLY = 1, PART_LATE = 2, PART_GATED = 3 };
 
@@ -394,7 +393,6 @@ bool split_ok(const ttsdec_dims& d) { return !((d.d_pre | d.d_ctx | d.h_att | d.
 const StepOrder& step_order(const ttsdec_handle* h, int B);
 bool head_proj(const ttsdec_handle* h, int B);
 bool query_role(const ttsdec_handle* h, int B);
-bool step_merged(const ttsdec_handle* h, int B);
 int& option_ref(ttsdec_handle* h, int o);
 void apply_env_options(ttsdec_handle* h);
 void drop_graph(ttsdec_handle* h);
@@ -502,8 +500,8 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
       a.dep_cnt = dep(DEP_FRAME);
       a.live_lag = 1;  // (same launch as the frame kernel: see lstm_body)
     } else if (part == PART_GATED) {
-      // [h_dec | h_att | ctx]: ctx is written by the attention role of the same launch; h_att second, so that the one-launch
-      // step (N_STEP), where it comes from the attention LSTM's tiles of the same launch, starts on the segment nobody is waited for
+      // [h_dec | h_att | ctx]: ctx is written by the attention role of the same launch, so it goes last; the exact-fp32 outputs
+      // are pinned to this summation order
       a.a = act(make_seg3(x2, H, H, x0, k0, k0, x1, D, D)); a.a_lo = act(make_seg3(x2l, H, H, x0l, k0, k0, x1l, D, D));
       a.w = make_seg3(W2(false), wld_hh, H, W0(false), wld_ih, k0, W1(false), wld_ih, D);
       a.w_lo = make_seg3(W2(true), wld_hh, H, W0(true), wld_ih, k0, W1(true), wld_ih, D);
@@ -582,7 +580,7 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
     return pa;
   };
 
-  const int attn_variant = ((h->merged_tune > 0 ? h->merged_tune : 0) >> 16) & 0xf;  // (measurement: fused_kernels.hip attn_lstm_f32_wide)
+  const int attn_variant = h->attn_form > 0 ? h->attn_form : 0;  // (measurement: fused_kernels.hip attn_lstm_f32_wide)
   switch (node) {
     case N_F:
     case N_FIN:
@@ -603,32 +601,6 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
     case N_QTD: {
       const ProjArgs pq = query_role_args();
       launch_attn_lstm(query_attn_args(pq), lstm_args(1, PART_GATED), &pq, st, attn_variant);
-      break;
-    }
-    case N_STEP: {
-      // the whole step as one launch (fused_kernels.hip step_kernel): N_JFA's and N_QTD's roles, the boundary between the two
-      // launches replaced by the DEP_HATT hand-off; every role live by t - 1 <= stop_t
-      ProjArgs pa = head_proj_args(1 - p, PROJ_HEAD);
-      FrameArgs f = frame_args(false);
-      f.dep_signal = 1; f.dep_cnt = dep(DEP_FRAME);
-      pa.dep_cnt = f.wait_cnt = dep(DEP_PROJ);
-      f.wait_n = proj_grid_size(32, pa.N, pa.ksplit);
-      LstmArgs la = lstm_args(0, PART_GATED);
-      la.sig_cnt = dep(DEP_HATT);
-      const int bu = B <= 64 ? 8 : 16;  // (units per LSTM tile: fused_kernels.hip Lean64x8 / Lean64x16)
-      const int la_tiles = (Ha + bu - 1) / bu;  // attention-LSTM tiles per 32-row block and step
-      ProjArgs pq = query_role_args();
-      pq.wait_cnt = dep(DEP_HATT); pq.wait_n = la_tiles; pq.live_lag = 1;
-      AttnArgs a = query_attn_args(pq);
-      a.live_lag = 1;
-      LstmArgs ld = lstm_args(1, PART_GATED);
-      ld.live_lag = 1;
-      ld.dep2_seg = 1; ld.dep2_n = la_tiles; ld.dep2_cnt = dep(DEP_HATT);
-      const int tune = h->merged_tune > 0 ? h->merged_tune : 0;  // (measurement option)
-      if (tune & 1) ld.dep2_seg = 0;  // the decoder LSTM starts nothing before its rows' h_att is complete
-      f.dbg |= (tune & 0xff) << 8;
-      pq.wait_sleep = (tune >> 8) & 0xff;
-      launch_step_merged(pa, f, la, pq, a, ld, st);
       break;
     }
     case N_AG:
@@ -776,8 +748,6 @@ const StepOrder kOrderProdH2 = {3, {N_JFA, N_Q, N_TD}, {"proj+prenet+lstm_att", 
 // ... and with the query as a job of the attention role's workgroups: two launches per step
 const StepOrder kOrderProdO2Q = {3, {N_FA, N_QTD, N_J}, {"prenet+lstm_att", "query+attention+lstm_dec", "proj"}};
 const StepOrder kOrderProdH2Q = {2, {N_JFA, N_QTD}, {"proj+prenet+lstm_att", "query+attention+lstm_dec"}};
-// ... and the boundary between those two replaced by a hand-off: one launch per step
-const StepOrder kOrderProdS = {1, {N_STEP}, {"step"}};
 // the two-role step: LJSpeech-type cell, either arithmetic mode
 int overlap_level(const ttsdec_handle* h, int B) {
   const ttsdec_dims& d = h->d;
@@ -792,7 +762,7 @@ int overlap_level(const ttsdec_handle* h, int B) {
     // (round 4, with the 32-row fp32 lean tile: exact fp32 B = 64 69.9 / 62.9, B = 128 86.9 / 82.7 - level 1 at every batch size now)
     return 1;
   }
-  if (h->overlap >= 0) return h->overlap;
+  if (h->overlap >= 0) return h->overlap > 2 ? 2 : h->overlap;
   // Round 3 (after the sc1 hand-offs and the per-row-block counters; profiles/r03_t_levels_sweep.txt, us per step, levels 0 / 1 / 2):
   // split-fp16 B = 96 78.3 / 62.4 / 48.8, 192 80.1 / 64.8 / 59.3, 320 128.5 / 102.5 / 88.8, 384 131.1 / 110.0 / 98.3, 512 147.7 / 131.6 /
   // 117.8, 1024 - / 262.6 / 235.0, 2048 - / 504.1 / 455.8: level 2 at every batch size (round 2 had level 1 above 320, +-1.5 % then).
@@ -838,20 +808,10 @@ bool query_role(const ttsdec_handle* h, int B) {
   const bool range = lstm_prec(h) ? (B >= 64 && B <= 384) : (B >= 192 && B <= 256);
   return range && proj_grid_size(B, d.d_ctx, ps) <= B;
 }
-// The one-launch step (option overlap = 3): split-fp16 Prod cell with the projection as a head role and the query on the
-// register-weight body, at batches whose attention workgroups fit the chip at once.
-bool step_merged(const ttsdec_handle* h, int B) {
-  const ttsdec_dims& d = h->d;
-  if (overlap_level(h, B) < 3 || !lstm_prec(h) || !head_proj(h, B)) return false;
-  const int ps = proj_split(query_k(d));  // (the query on the register-weight body: whole K slices)
-  if (!(ps > 0 && ps <= kQuerySplit && !(d.h_att & 7))) return false;
-  return step_merged_supported(B, d.h_att, d.h_dec, pre_hidden(d), d.d_pre, d.d_ctx, proj_n(d), proj_parts(h, lstm_prec(h), B));
-}
 const StepOrder& step_order(const ttsdec_handle* h, int B) {
   const ttsdec_dims& d = h->d;
   if (const int lv = overlap_level(h, B)) {
     if (is_taco2(d)) return head_proj(h, B) ? kOrderTaco2H : kOrderTaco2O;
-    if (step_merged(h, B)) return kOrderProdS;
     if (lv >= 2 && query_role(h, B)) return head_proj(h, B) ? kOrderProdH2Q : kOrderProdO2Q;
     if (head_proj(h, B)) return lv >= 2 ? kOrderProdH2 : kOrderProdH;
     return lv >= 2 ? kOrderProdO2 : kOrderProdO;
@@ -923,7 +883,7 @@ int ensure_graph(ttsdec_handle* h, const StepBufs& sb, const void* ws, int B, in
 
 // ---- options (include/ttsdec.h TTSDEC_OPT_*) ----
 const char* const kOptionNames[TTSDEC_OPT_COUNT] = {"graph",     "overlap",    "chunk_a",          "chunk_b",     "proj_regw",
-                                                    "head_proj", "query_role", "merged_tune", "profile_ablation", "debug_flags", "spin_limit"};
+                                                    "head_proj", "query_role", "attn_form",        "profile_ablation", "debug_flags", "spin_limit"};
 int& option_ref(ttsdec_handle* h, int o) {
   switch (o) {
     case TTSDEC_OPT_OVERLAP: return h->overlap;
@@ -932,7 +892,7 @@ int& option_ref(ttsdec_handle* h, int o) {
     case TTSDEC_OPT_PROJ_REGW: return h->opt_proj_regw;
     case TTSDEC_OPT_HEAD_PROJ: return h->head_proj;
     case TTSDEC_OPT_QUERY_ROLE: return h->query_role;
-    case TTSDEC_OPT_MERGED_TUNE: return h->merged_tune;
+    case TTSDEC_OPT_ATTN_FORM: return h->attn_form;
     case TTSDEC_OPT_PROFILE_ABLATION: return h->profile_ablation;
     case TTSDEC_OPT_DEBUG_FLAGS: return h->debug_flags;
     case TTSDEC_OPT_SPIN_LIMIT: return h->spin_limit;
@@ -1013,7 +973,7 @@ int ttsdec_create(const ttsdec_dims* dims, ttsdec_handle** out) {
   // measured SLOWER on MI355X - 126 vs 96 us per step at B=256: the early GEMM's 256 workgroups hold every CU's LDS, so
   // the small kernels queue behind them - and was removed; see DESIGN.md.)
   for (int o = 0; o < TTSDEC_OPT_COUNT; ++o) option_ref(h, o) = -1;
-  h->profile_ablation = 0; h->debug_flags = 0; h->spin_limit = 0; h->merged_tune = 0;
+  h->profile_ablation = 0; h->debug_flags = 0; h->spin_limit = 0; h->attn_form = 0;
   apply_env_options(h);
   h->device = current_device_or_minus1();
   *out = h;

@@ -46,8 +46,7 @@ struct Ctrl {
   // measurement only (TTSDEC_STAMPS=1): per-workgroup wall-clock stamps of the two-role launches, else nullptr
   unsigned long long* stamps;
   // test hooks (include/ttsdec.h TTSDEC_OPT_DEBUG_FLAGS / _SPIN_LIMIT): bit 0 = the frame role does not signal, bit 1 = the
-  // attention role does not, bit 2 = the projection head role does not, bit 3 = the attention LSTM's tiles (one-launch step) do
-  // not; polls before role_wait gives up
+  // attention role does not, bit 2 = the projection head role does not; polls before role_wait gives up
   int debug_flags, spin_limit;
   // measurement only (ttsdec_profile_loop): when set, workgroup 0 of every step kernel stores its entry time at
   // loop_stamps[slot * kLoopStampNodes + position of the launch in the step order] - the launches' start times inside the
@@ -325,13 +324,6 @@ __device__ __forceinline__ void role_signal(unsigned int* counter) {
   __syncthreads();
   if (threadIdx.x == 0) __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// a producer whose rows span two of the consumers' 32-row blocks (c1 may be nullptr)
-__device__ __forceinline__ void role_signal2(unsigned int* c0, unsigned int* c1) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(c0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (threadIdx.x == 64 && c1 != nullptr) __hip_atomic_fetch_add(c1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // Polls before a consumer role gives up: x (~0.25 us of s_sleep + the poll's round trip) ~ 1-4 ms - three orders of magnitude
 // beyond any producer role's run time (they end within tens of microseconds of the launch's start), and short enough that a
 // call that does time out (an over-subscribed or partitioned GPU on which the producers are not resident) costs ONE such wait:
@@ -344,12 +336,11 @@ constexpr int kRoleSpinLimit = 1 << 12;
 // workgroup waits for the slowest producer of the whole chip, and no counter takes more than 64 adds per step (96 adds to
 // ONE word took the projection role's signal ~1.5 us; MI355X_MICROARCH.md "fanin").
 constexpr int kDepLine = 32;  // unsigned ints per counter line
-// (DEP_HATT: the attention LSTM's tiles -> the query role and the decoder LSTM, in the one-launch step - fused_kernels.hip step_kernel)
-enum DepKind { DEP_FRAME = 0, DEP_ATTN = 1, DEP_PROJ = 2, DEP_QUERY = 3, DEP_HATT = 4, DEP_KINDS = 5 };
+enum DepKind { DEP_FRAME = 0, DEP_ATTN = 1, DEP_PROJ = 2, DEP_QUERY = 3, DEP_KINDS = 4 };
 // the poll alone: for a consumer that takes every handed-off byte with sc1 loads (load_wt), or that only wants to know.
 // Two counters (c1 may be nullptr): a consumer whose rows span two of the producers' 32-row blocks.
 __device__ __forceinline__ void role_poll(const unsigned int* c0, unsigned int target0, Ctrl* ctrl, const unsigned int* c1 = nullptr,
-                                          unsigned int target1 = 0, int long_sleep = 0) {
+                                          unsigned int target1 = 0) {
   if (target0 == 0 && (c1 == nullptr || target1 == 0)) return;
   int spins = 0;
   // Has a hand-off of this call already timed out (Ctrl::range_err bit 1)?  Then its arrival targets - cumulative over the
@@ -361,7 +352,6 @@ __device__ __forceinline__ void role_poll(const unsigned int* c0, unsigned int t
     if (v0 >= target0 && v1 >= target1) break;
     if (gave_up) break;
     __builtin_amdgcn_s_sleep(8);
-    for (int i = 0; i < long_sleep; ++i) __builtin_amdgcn_s_sleep(8);  // (waits known to be long: fewer polls beside the tile streams)
     if (++spins > (ctrl != nullptr ? ctrl->spin_limit : kRoleSpinLimit)) {
       if (ctrl != nullptr) atomicOr(&ctrl->range_err, 2);
       break;

@@ -139,74 +139,6 @@ __global__ __launch_bounds__(kGemmThreads, WPE) void attn_lstm_kernel(AttnArgs a
   }
 }
 
-// ---- the whole step as ONE launch ----
-// [proj(t-1) | frame(t) | lstm_att(t) | query(t) -> attention(t) | lstm_dec(t)] by block id: the two launches above back to back
-// inside one grid, so the step loses the boundary between them (the first launch's drain, the release / acquire pair and the
-// second's dispatch: ~4.5-5.4 us of the step at B = 256, time stamps) and the decoder LSTM's workgroups take over a CU's slot the
-// moment an attention-LSTM workgroup leaves it instead of after the slowest one of the chip.
-// What the boundary ordered is ordered by one more hand-off: every attention-LSTM tile stores its split planes write-through
-// and signals the DEP_HATT counter(s) of the 32-row block(s) it covers (lstm_body, LstmArgs::sig_cnt); the query tiles of a
-// row block (proj_body, ProjArgs::wait_cnt) and the decoder LSTM's h_att segment (a second gate, LstmArgs::dep2_*) wait for
-// all of that block's tiles and read them with sc1 loads.
-// Progress: every role waits only for roles with lower block ids (the attention workgroups also for each other's query tiles),
-// the grid dispatches in id order, and the roles in front of the attention role end without it - so every attention workgroup
-// becomes resident (n_attn <= the chip's 512 slots, checked by the host) and everything a workgroup waits for is resident or
-// done.  Every poll is bounded regardless (common.h role_poll).
-// Liveness: all roles of the launch go by t - 1 <= stop_t (live_lag), because the frame role may lower stop_t to t - 1 while
-// they read it: the step after the one at which the stop rule fires is still computed (and never read).
-// Small batches (the stand-alone small-batch LSTM tile, one workgroup per CU, WPE = 2): fewer attention workgroups than query
-// tiles, so the query tiles get workgroups of their own (n_q of them, between the attention LSTM and the attention role);
-// nothing shares a CU there, and the decoder LSTM's h_dec segment streams on the CUs the first half of the step leaves idle.
-struct StepGrid {
-  int n_proj, n_frame, frame_cols, n_la, la_cols, n_q, n_attn, ld_cols;
-  int tune;  // measurement (option merged_tune): bit 1 = wave priorities 2 / 0 for the attention / decoder LSTM roles
-};
-template <int K0H, int PH, class Cfg, int NJ, int WPE>
-__global__ __launch_bounds__(kGemmThreads, WPE) void step_kernel(FrameArgs f, LstmArgs la, ProjArgs pj, AttnArgs a, LstmArgs ld, ProjArgs pq,
-                                                                  StepGrid n) {
-  constexpr int PREC = Cfg::kPrec;
-  __shared__ __attribute__((aligned(16)))
-  float smem[cmax<cmax<Cfg::kLdsFloats, FrameLds<K0H, PH, PREC>::kFloats>(), cmax<kProjLdsFloats, attn_lds_floats<NJ>()>()>()];
-  loop_stamp(f.ctrl, f.slot, f.node);
-  int id = blockIdx.x;
-  if (id < n.n_proj) {
-    __builtin_amdgcn_s_setprio(3);
-    proj_body<PREC>(pj, smem, id);
-    return;
-  }
-  id -= n.n_proj;
-  if (id < n.n_frame) {
-    __builtin_amdgcn_s_setprio(3);
-    frame_body<K0H, PH, PREC, 6, WPE == 4, true>(f, smem, id % n.frame_cols, id / n.frame_cols);
-    return;
-  }
-  id -= n.n_frame;
-  if (id < n.n_la) {
-    if (n.tune & 2) __builtin_amdgcn_s_setprio(2);
-    lstm_body<Cfg, true, true>(la, smem, id % n.la_cols, id / n.la_cols);
-    return;
-  }
-  id -= n.n_la;
-  if (id < n.n_q + n.n_attn) {
-    __builtin_amdgcn_s_setprio(3);
-    const bool is_q = id < n.n_q;  // a query-tile workgroup (small batches), else the attention workgroup of utterance id - n_q
-    const int aid = id - n.n_q;
-    const stamp_ptr st = stamps_of(a.ctrl);  // measurement only (TTSDEC_STAMPS)
-    if (threadIdx.x == 0 && !is_q) stamp(st, 1, 6, now_rt());
-    // query tiles: this workgroup's one (query workgroups), none (attention workgroups beside them), or tiles aid, aid + n_attn, ...
-    const int t0 = n.n_q > 0 ? (is_q ? id : 0) : aid, t1 = n.n_q > 0 ? (is_q ? id + 1 : 0) : a.q_tiles, ts = n.n_q > 0 ? 1 : n.n_attn;
-    for (int tile = t0; tile < t1; tile += ts) {
-      proj_body<PREC>(pq, smem, tile);
-      __syncthreads();  // (the reduction tile in LDS is reused by the next tile / the attention pass)
-    }
-    if (is_q) return;
-    attn_body<NJ>(a, smem, aid);
-    return;
-  }
-  id -= n.n_q + n.n_attn;
-  lstm_body<Cfg, true, true>(ld, smem, id % n.ld_cols, id / n.ld_cols);
-}
-
 // the early part on its own (profiling / ablation: what the role costs without a partner)
 template <class Cfg>
 __global__ __launch_bounds__(kGemmThreads, 4) void lstm_lean_kernel(LstmArgs l) {
@@ -273,9 +205,9 @@ void launch_proj_frame_lstm(const ProjArgs& pj, const FrameArgs& f, const LstmAr
 
 // Workgroups of a multi-role kernel the device holds AT ONCE, as its runtime says: CUs x hipOccupancyMaxActiveBlocksPerMultiprocessor
 // (registers, LDS and the wave limit of THIS kernel on THIS device - a partitioned or smaller part answers for itself).  The
-// schedules in which workgroups of one role wait for EACH OTHER (the query role, the one-launch step) are only taken when all
-// of them fit that number; they further assume the GPU is not shared with another process's kernels (what the number cannot
-// know - the bounded spin and Decoder.forward's fallback cover that case).  0 when the query fails: those schedules stay off.
+// schedule in which workgroups of one role wait for EACH OTHER (the query role) is only taken when all of them fit that
+// number; it further assumes the GPU is not shared with another process's kernels (what the number cannot know - the
+// bounded spin and Decoder.forward's fallback cover that case).  0 when the query fails: that schedule stays off.
 static int resident_slots(const void* fn) {
   static std::mutex mu;
   static std::map<std::pair<int, const void*>, int> cache;
@@ -297,7 +229,7 @@ static int resident_slots(const void* fn) {
 typedef void (*attn_lstm_fn)(AttnArgs, LstmArgs, ProjArgs, int, int);
 // The attention pass per regime: ATTN_LEAN beside the exact-fp32 LSTM on the 64 x 16 tile (B > 96), whose fp32 MFMA chain shares
 // each SIMD with the attention waves; ATTN_BASE elsewhere (split-fp16: 16-bit MFMAs leave the vector ALU alone; small batches:
-// the roles rarely share a CU).  variant (measurement, option merged_tune bits 16-19, exact fp32 64 x 16 tile only): 1 = ATTN_BASE,
+// the roles rarely share a CU).  variant (measurement, option attn_form, exact fp32 64 x 16 tile only): 1 = ATTN_BASE,
 // 2 = ATTN_ONE_ROW, 3 = ATTN_PLAIN_SUM, 4 = ATTN_PRIO_SWAP, 5 = ATTN_LEAN.
 template <int NJ>
 static attn_lstm_fn attn_lstm_f32_wide(int variant) {
@@ -336,53 +268,6 @@ void launch_attn_lstm(const AttnArgs& a, const LstmArgs& l, const ProjArgs* q, h
   const int lrows = (l.M + bm - 1) / bm;
   dim3 grid(a.B + lcols * lrows), block(kGemmThreads);
   hipLaunchKernelGGL(attn_lstm_kernel_for(a.D, l.prec == 1, kind, variant), grid, block, 0, st, a, l, pq, a.B, lcols);
-}
-
-// ---- one-launch step ----
-typedef void (*step_fn)(FrameArgs, LstmArgs, ProjArgs, AttnArgs, LstmArgs, ProjArgs, StepGrid);
-struct StepKernel {
-  step_fn fn;
-  int bm, bu;  // batch rows / hidden units of an LSTM tile
-};
-template <int PH, int NJ>
-static StepKernel step_kernel_of(LeanKind kind) {
-  using TL = LeanTiles<PREC_F16S>;
-  if (kind == SMALL_FAT) return {step_kernel<40, PH, TL::SmallFat, NJ, 2>, TL::SmallFat::BM, TL::SmallFat::BN / 4};
-  if (kind == LEAN_64x8) return {step_kernel<40, PH, TL::Lean64x8, NJ, 4>, TL::Lean64x8::BM, TL::Lean64x8::BN / 4};
-  return {step_kernel<40, PH, TL::Lean64x16, NJ, 4>, TL::Lean64x16::BM, TL::Lean64x16::BN / 4};
-}
-static StepKernel step_kernel_for(int Ph, int D, LeanKind kind) {
-  if (Ph == 256) return D / 4 <= 64 ? step_kernel_of<256, 1>(kind) : step_kernel_of<256, 2>(kind);
-  return D / 4 <= 64 ? step_kernel_of<128, 1>(kind) : step_kernel_of<128, 2>(kind);
-}
-static int step_roles_in_front(int B, int P, int n_out, int ksplit) {  // the workgroups in front of the attention LSTM's
-  return proj_grid_size(B, n_out, ksplit) + frame_grid_size(B, P);
-}
-bool step_merged_supported(int B, int Ha, int Hd, int Ph, int P, int D, int n_out, int ksplit) {
-  // The attention role's workgroups - one per utterance - wait for each other's query tiles: all of them resident at once,
-  // beside workgroups of the roles in front of them that have not ended yet - so at most HALF of what the device holds of this
-  // kernel (resident_slots: 2 x 256 on an MI355X).
-  if (B < 1) return false;
-  const LeanKind kind = lean_kind(B, step_roles_in_front(B, P, n_out, ksplit), Ha > Hd ? Ha : Hd);
-  return B <= resident_slots(reinterpret_cast<const void*>(step_kernel_for(Ph, D, kind).fn)) / 2;
-}
-void launch_step_merged(const ProjArgs& pj, const FrameArgs& f, const LstmArgs& la, const ProjArgs& pq, const AttnArgs& a, const LstmArgs& ld,
-                        hipStream_t st) {
-  if (f.M <= 0 || la.prec != 1) return;  // (split-fp16 only: the host never asks for it otherwise)
-  const LeanKind kind = lean_kind(la.M, step_roles_in_front(f.M, f.P, pj.N, pj.ksplit), la.H > ld.H ? la.H : ld.H);
-  const StepKernel k = step_kernel_for(f.Ph, a.D, kind);
-  StepGrid n;
-  n.tune = f.dbg >> 8;
-  n.frame_cols = (f.P + kFrameCols - 1) / kFrameCols;
-  n.n_frame = n.frame_cols * ((f.M + kFrameRows - 1) / kFrameRows);
-  n.n_proj = proj_grid_size(pj.M, pj.N, pj.ksplit);
-  const int lrows = (la.M + k.bm - 1) / k.bm;
-  n.la_cols = (la.H + k.bu - 1) / k.bu; n.n_la = n.la_cols * lrows;
-  n.ld_cols = (ld.H + k.bu - 1) / k.bu;
-  n.n_attn = a.B;
-  n.n_q = a.q_tiles > a.B ? a.q_tiles : 0;  // (fewer attention workgroups than query tiles: the tiles get workgroups of their own)
-  dim3 grid(n.n_proj + n.n_frame + n.n_la + n.n_q + n.n_attn + n.ld_cols * lrows), block(kGemmThreads);
-  hipLaunchKernelGGL(k.fn, grid, block, 0, st, f, la, pj, a, ld, pq, n);
 }
 
 void launch_lstm_lean(const LstmArgs& l, hipStream_t st) {

@@ -145,11 +145,10 @@ __device__ __forceinline__ void wait_vmcnt() {
 // polling one counter saturated its memory channel and slowed the producers - 110 vs 88 us per step.)
 // gate.seg = -1: no gate.
 // kAuxA: cache policy of the A operand's LDS-DMA (16 = sc1: past this CU's vector L1, for operands handed over inside the launch).
-// gate.seg2 (< gate.seg, or -1): a second gated segment, waited for with gate.wait(1) (the one-launch step's decoder LSTM).
 struct NoGate {
   static constexpr int kAuxA = 0;
-  int seg = -1, seg2 = -1;
-  __device__ __forceinline__ void wait(int) const {}
+  int seg = -1;
+  __device__ __forceinline__ void wait() const {}
   __device__ __forceinline__ void mark(int) const {}
 };
 
@@ -211,18 +210,16 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
   const int nk = nt0 + (nseg > 1 ? nt1 : 0) + (nseg > 2 ? nt2 : 0);
   // first tile of the gated segment (uniform), or -1
   auto first_tile = [&](int seg) { return (!live || seg < 0 || seg >= nseg) ? -1 : (seg == 0 ? 0 : (seg == 1 ? nt0 : nt0 + nt1)); };
-  const int gate_tile = first_tile(gate.seg), gate_tile2 = first_tile(gate.seg2);
-  auto gate_sync1 = [&](int which) {  // every wave of the workgroup, at the same point of the tile sequence
-    if (wave8 == 4) gate.wait(which);
+  const int gate_tile = first_tile(gate.seg);
+  auto gate_sync = [&]() {  // every wave of the workgroup, at the same point of the tile sequence
+    if (wave8 == 4) gate.wait();
     __builtin_amdgcn_s_barrier();
   };
   auto gate_at = [&](int tile) {  // in front of the issue of K tile `tile` (uniform)
-    if (tile == gate_tile2) gate_sync1(1);
-    if (tile == gate_tile) gate_sync1(0);
+    if (tile == gate_tile) gate_sync();
   };
-  // (segments that start inside the prologue tiles)
-  if (gate_tile2 >= 0 && gate_tile2 < S - 1) gate_sync1(1);
-  if (gate_tile >= 0 && gate_tile < S - 1) gate_sync1(0);
+  // (a segment that starts inside the prologue tiles)
+  if (gate_tile >= 0 && gate_tile < S - 1) gate_sync();
 
   f32x16 acc, acc2;
 #pragma unroll
