@@ -41,6 +41,7 @@ extern "C" {
 #define TTSDEC_VERSION 2
 /* (The ttsgen_ family below - the HiFi-GAN generator - was added later without a bump: it adds entry points and a struct of its
  * own and changes none that existed, so a version-2 binding still binds every entry point it knows.) */
+/* (So was the ttsdur_ family at the end - the duration predictors and the length regulator - for the same reason.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -516,6 +517,76 @@ int ttsgen_forward(ttsgen_handle* h, const float* z, const float* g, int B, int 
  * [B * T_s, C_s] fp32 (T_s = T * u_0 * ... * u_{n_stages-1}, C_s its channels; conv_pre: [B * T, C0]); nothing is written to out. */
 int ttsgen_forward_stages(ttsgen_handle* h, const float* z, const float* g, int B, int T, int n_stages, void* workspace, size_t workspace_bytes,
                           void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * VITS2 duration predictors and length regulation: the `self.dp(...)` and the prior expansion of SynthesizerTrn.infer,
+ * vits2/models.py:1288-1320.  Eval mode, exact fp32 (fp32 vector ALU throughout).  Activations are CHANNEL-LAST: the text
+ * encoder's x [B, T, C], m / logs [B, T, inter] feed in as ttsvits_text_encoder writes them.
+ *   kind 0, StochasticDurationPredictor reverse (models.py:29-137): conditioning x' = proj(DDSConv(pre(x) [+ cond(g)])) * mask;
+ *     z = noise * noise_scale; the flows [Flip, ConvFlow_n, Flip, ..., ConvFlow_2, Flip, ElementwiseAffine] (flows.1 is dropped,
+ *     :127-128) with ConvFlow reverse = pre (1 -> C) on x0, DDSConv(+ x'), proj (C -> 29) * mask, the inverse rational-quadratic
+ *     spline (transforms.py:50-209, linear tails at +-5) on x1; logw = channel 0.
+ *   kind 1, DurationPredictor (models.py:140-180): (x [+ cond(g)]) -> conv k3 on x * mask, ReLU, LayerNorm, twice -> proj (F -> 1)
+ *     on x * mask, * mask.
+ * DDSConv layer i (modules.py:84-127, dilation 3^i): one launch per layer over tiles of 16 frames: the depthwise conv (zero
+ * padding per utterance), LayerNorm, GELU (erf), the 1x1 C x C conv, LayerNorm, GELU and the residual.  A ConvFlow's pre and
+ * `+ g` ride in its first layer's load; proj, the spline, Flip and ElementwiseAffine in its last layer's epilogue.
+ * Frames at or beyond lengths[b] are masked as the reference masks them; the outputs there are 0.
+ * ------------------------------------------------------------------------------------- */
+typedef struct ttsdur_dims {
+  int32_t kind;             /* 0 = StochasticDurationPredictor (reverse only), 1 = DurationPredictor                     */
+  int32_t in_channels;      /* hidden_channels (192): width of x; the SDP's width everywhere (models.py:40)               */
+  int32_t filter_channels;  /* DurationPredictor: 256 (SynthesizerTrn); ignored by kind 0                                */
+  int32_t kernel_size;      /* 3 (the only size built)                                                                   */
+  int32_t n_flows;          /* kind 0: 4 (2..8); ignored by kind 1                                                       */
+  int32_t gin_channels;     /* 0, or the width of the speaker vector g (cond, 1x1)                                       */
+} ttsdur_dims;
+typedef struct ttsdur_handle ttsdur_handle;
+
+/* Dimensions not built (kernel_size != 3, channels not multiples of 4 or above 256, n_flows < 2 or > 8) are refused with
+ * TTSDEC_ERR_DIMS. */
+int ttsdur_create(const ttsdur_dims* dims, ttsdur_handle** out);
+int ttsdur_destroy(ttsdur_handle* h);
+const char* ttsdur_last_hip_error(const ttsdur_handle* h);
+/* Source tensors for ttsdur_pack_weights (device fp32, the reference's parameter shapes), in this order (C = in_channels):
+ *  kind 0:  pre.weight [C, C, 1], pre.bias [C];
+ *           convs (DDSConv), per layer i in 0..2: convs_sep.i.weight [C, 1, 3], convs_sep.i.bias [C], convs_1x1.i.weight
+ *               [C, C, 1], convs_1x1.i.bias [C], norms_1.i.gamma, norms_1.i.beta, norms_2.i.gamma, norms_2.i.beta   (8 per layer);
+ *           proj.weight [C, C, 1], proj.bias [C];  flows.0.m [2, 1], flows.0.logs [2, 1];
+ *           per ConvFlow flows.{2k+1}, k = 1 .. n_flows-1 (flows.1 is unused by reverse and not passed): pre.weight [C, 1, 1],
+ *               pre.bias [C], its DDSConv's 24 tensors as above, proj.weight [29, C, 1], proj.bias [29];
+ *           when gin_channels > 0: cond.weight [C, gin, 1], cond.bias [C].          (114 tensors at n_flows = 4 without g)
+ *  kind 1:  conv_1.weight [F, C, 3], conv_1.bias [F], norm_1.gamma, norm_1.beta [F], conv_2.weight [F, F, 3], conv_2.bias,
+ *           norm_2.gamma, norm_2.beta, proj.weight [1, F, 1], proj.bias [1];
+ *           when gin_channels > 0: cond.weight [C, gin, 1], cond.bias [C].          (10 tensors without g) */
+int ttsdur_num_weight_tensors(const ttsdur_handle* h);
+size_t ttsdur_packed_bytes(const ttsdur_handle* h);
+int ttsdur_pack_weights(ttsdur_handle* h, const float* const* src, int n_src, void* blob, void* stream);
+int ttsdur_bind_weights(ttsdur_handle* h, const void* blob);
+/* Scratch of one ttsdur_sdp_reverse / ttsdur_dp_forward call of B utterances of T tokens. */
+size_t ttsdur_workspace_bytes(const ttsdur_handle* h, int B, int T);
+/* StochasticDurationPredictor.forward(x, x_mask, g=g, reverse=True, noise_scale) (kind 0): x [B, T, C] channel-last,
+ * lengths [B] int32 device (x_mask = t < lengths[b]), g NULL or [B, gin], noise [B, 2, T] (the reference's torch.randn(B, 2, T),
+ * channel-first, before the noise_scale factor); logw out [B, T] (the reference's [B, 1, T]).  Enqueues only. */
+int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths, const float* g, const float* noise, float noise_scale,
+                       int B, int T, float* logw, void* workspace, size_t workspace_bytes, void* stream);
+/* DurationPredictor.forward(x, x_mask, g) (kind 1): the same tensors, no noise. */
+int ttsdur_dp_forward(ttsdur_handle* h, const float* x, const int32_t* lengths, const float* g, int B, int T, float* logw,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* Length regulation, first half (models.py:1304-1306): w = exp(logw) * mask * length_scale, w_ceil = ceil(w);
+ * cum [B, T] int32 = the running sum of w_ceil over an utterance's tokens (padded tokens add w_ceil = 0 as in the reference),
+ * y_len [B] int32 = max(1, sum w_ceil); status [2] int32 = { max_b y_len, flags }: flag 1 = a non-finite w, flag 2 = a sum beyond
+ * 2^24 frames (where fp32 stops counting exactly; cum / y_len are then meaningless).  One workgroup; the caller reads status
+ * once (the reference's host sync for T_y = max y_len) and must not call ttsdur_expand when flags != 0. */
+int ttsdur_lengths(ttsdur_handle* h, const float* logw, const int32_t* lengths, float length_scale, int B, int T, int32_t* cum,
+                   int32_t* y_len, int32_t* status, void* stream);
+/* Length regulation, second half (models.py:1307-1320 without the dense path matmul): for frame t < T_y of utterance b,
+ * token j with cum[j-1] <= t < cum[j] (none when t >= cum[T-1]):  m_p[b, t, :] = m[b, j, :], logs_p[b, t, :] = logs[b, j, :]
+ * (zeros without a token), z_p[b, t, c] = m_p + eps[b, c, t] * exp(logs_p) * noise_scale, channel-last [B, T_y, inter]
+ * (the flow's input layout); attn [B, T_y, T] = 1 at (t, j), else 0 (NULL: not written).  eps [B, inter, eps_T] is the
+ * reference's torch.randn_like(m_p) with eps_T >= T_y frames per channel row.  m, logs [B, T, inter] channel-last. */
+int ttsdur_expand(ttsdur_handle* h, const int32_t* cum, const float* m, const float* logs, const float* eps, int eps_T, float noise_scale,
+                  int B, int T, int inter, int T_y, float* z_p, float* m_p, float* logs_p, float* attn, void* stream);
 
 #ifdef __cplusplus
 }

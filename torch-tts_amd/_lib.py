@@ -96,6 +96,21 @@ GEN_SYMBOLS = (
     "ttsgen_forward",
     "ttsgen_forward_stages",
 )
+# the duration predictors' and length regulator's family (include/ttsdec.h ttsdur_*), kept apart like GEN_SYMBOLS
+DUR_SYMBOLS = (
+    "ttsdur_create",
+    "ttsdur_destroy",
+    "ttsdur_last_hip_error",
+    "ttsdur_num_weight_tensors",
+    "ttsdur_packed_bytes",
+    "ttsdur_pack_weights",
+    "ttsdur_bind_weights",
+    "ttsdur_workspace_bytes",
+    "ttsdur_sdp_reverse",
+    "ttsdur_dp_forward",
+    "ttsdur_lengths",
+    "ttsdur_expand",
+)
 ENC_W_COUNT = 20
 
 
@@ -143,6 +158,13 @@ class GenDims(C.Structure):  # include/ttsdec.h ttsgen_dims
                 ("up_rates", C.c_int32 * GEN_MAX_UP), ("up_kernels", C.c_int32 * GEN_MAX_UP), ("n_res", C.c_int32),
                 ("res_kernels", C.c_int32 * GEN_MAX_RES), ("res_dilations", (C.c_int32 * 3) * GEN_MAX_RES), ("n_dil", C.c_int32),
                 ("resblock", C.c_int32), ("gin_channels", C.c_int32)]
+
+
+DUR_SDP, DUR_DP = 0, 1  # include/ttsdec.h ttsdur_dims.kind
+
+
+class DurDims(C.Structure):  # include/ttsdec.h ttsdur_dims
+    _fields_ = [(n, C.c_int32) for n in ("kind", "in_channels", "filter_channels", "kernel_size", "n_flows", "gin_channels")]
 
 
 class TtsdecError(RuntimeError):
@@ -314,6 +336,30 @@ def load() -> C.CDLL:
         lib.ttsgen_forward.argtypes = [vp, vp, vp, i32, i32, vp, vp, sz, vp]
         lib.ttsgen_forward_stages.restype = i32
         lib.ttsgen_forward_stages.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, vp]
+        lib.ttsdur_create.restype = i32
+        lib.ttsdur_create.argtypes = [C.POINTER(DurDims), C.POINTER(vp)]
+        lib.ttsdur_destroy.restype = i32
+        lib.ttsdur_destroy.argtypes = [vp]
+        lib.ttsdur_last_hip_error.restype = C.c_char_p
+        lib.ttsdur_last_hip_error.argtypes = [vp]
+        lib.ttsdur_num_weight_tensors.restype = i32
+        lib.ttsdur_num_weight_tensors.argtypes = [vp]
+        lib.ttsdur_packed_bytes.restype = sz
+        lib.ttsdur_packed_bytes.argtypes = [vp]
+        lib.ttsdur_pack_weights.restype = i32
+        lib.ttsdur_pack_weights.argtypes = [vp, C.POINTER(vp), i32, vp, vp]
+        lib.ttsdur_bind_weights.restype = i32
+        lib.ttsdur_bind_weights.argtypes = [vp, vp]
+        lib.ttsdur_workspace_bytes.restype = sz
+        lib.ttsdur_workspace_bytes.argtypes = [vp, i32, i32]
+        lib.ttsdur_sdp_reverse.restype = i32
+        lib.ttsdur_sdp_reverse.argtypes = [vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, sz, vp]
+        lib.ttsdur_dp_forward.restype = i32
+        lib.ttsdur_dp_forward.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
+        lib.ttsdur_lengths.restype = i32
+        lib.ttsdur_lengths.argtypes = [vp, vp, vp, f32, i32, i32, vp, vp, vp, vp]
+        lib.ttsdur_expand.restype = i32
+        lib.ttsdur_expand.argtypes = [vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
         _lib = lib
         return _lib
 

@@ -1,0 +1,796 @@
+// C ABI of the VITS2 duration predictors and the length regulator (include/ttsdec.h ttsdur_*): the `self.dp(...)` and the prior
+// expansion of SynthesizerTrn.infer, vits2/models.py:1288-1320.
+//
+// Exact fp32 on the vector ALU.  The predictors are ~1 MFLOP per token: the path is latency, not FLOPs, so every stage is one
+// launch over tiles of kRows frames (256 threads, one column per lane, the tile's activations in LDS, weights from L2):
+//   pw_conv_kernel   a 1- or 3-tap conv (K-major weight), optional ReLU + LayerNorm + a folded 1-column projection
+//                    (DurationPredictor: two launches; the SDP's pre (+ cond(g)): one)
+//   dds_layer_kernel one DDSConv layer (modules.py:84-127): depthwise dilated conv of x * mask, LN, GELU, 1x1 conv, LN, GELU,
+//                    x + y; a ConvFlow's pre (1 -> C) and `+ g` in the load of its first layer; the conditioning path's proj or a
+//                    ConvFlow's proj (C -> 29), inverse spline, Flip bookkeeping and the closing ElementwiseAffine in the
+//                    epilogue of the last
+//   lengths_kernel   w = exp(logw) * mask * length_scale, ceil, running sums, y_len, one workgroup
+//   expand_kernel    the frame-rate prior (m_p, logs_p, z_p channel-last; attn) from the running sums, no dense matmul
+// SDP reverse at n_flows = 4: 1 (cond(g)) + 1 (pre) + 3 (DDSConv) + 3 x 3 (ConvFlows) = 14 launches (13 without g).
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <new>
+#include <string>
+
+#include "kernels.h"
+
+using namespace ttsdec;
+
+namespace {
+constexpr size_t kAlign = 64;  // floats
+constexpr int kRows = 16;      // frames per workgroup tile
+constexpr int kThreads = 256;
+constexpr int kMaxC = 256;     // LDS: 3 x kRows x C floats (DDSConv), kRows x (3 C_in + N) floats (pw_conv) <= 64 KiB
+constexpr int kBins = 10;      // ConvFlow num_bins
+constexpr int kProj = 3 * kBins - 1;
+constexpr float kTail = 5.f;   // ConvFlow tail_bound
+inline size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+struct DdsW {  // one DDSConv (3 layers), offsets in floats
+  size_t dw_w[3], dw_b[3];     // [3][C] tap-major, [C]
+  size_t pw_w[3], pw_b[3];     // [C][C] K-major, [C]
+  size_t n1g[3], n1b[3], n2g[3], n2b[3];
+};
+struct DurBlob {
+  // kind 0
+  size_t pre_w, pre_b;               // [C][C] K-major, [C]
+  DdsW convs;
+  size_t proj_w, proj_b;             // [C][C] K-major, [C]
+  size_t ea_m, ea_logs;              // [2], [2]
+  size_t f_pre_w[8], f_pre_b[8];     // [C], [C] (flows.{2k+1}, k = 1 .. n_flows-1)
+  DdsW f_convs[8];
+  size_t f_proj_w[8], f_proj_b[8];   // [C][29] K-major, [29]
+  // kind 1
+  size_t c1_w, c1_b, n1g, n1b, c2_w, c2_b, n2g, n2b, p_w, p_b;  // [3C][F], [F], ..., [3F][F], ..., [F], [1]
+  size_t cond_w, cond_b;             // [C, gin] (as given), [C]
+  size_t total;
+};
+}  // namespace
+
+struct ttsdur_handle {
+  ttsdur_dims d;
+  DurBlob bl;
+  const float* blob;
+  int device;
+  std::string hip_err;
+};
+
+namespace {
+
+bool dims_ok(const ttsdur_dims& d) {
+  if (d.kind != 0 && d.kind != 1) return false;
+  if (d.kernel_size != 3) return false;
+  if (d.in_channels < 4 || (d.in_channels & 3) || d.in_channels > kMaxC) return false;
+  if (d.gin_channels < 0 || d.gin_channels > 4096) return false;
+  if (d.kind == 0 && (d.n_flows < 2 || d.n_flows > 8)) return false;
+  if (d.kind == 1 && (d.filter_channels < 4 || (d.filter_channels & 3) || d.filter_channels > kMaxC)) return false;
+  return true;
+}
+
+DurBlob make_layout(const ttsdur_dims& d) {
+  DurBlob L;
+  memset(&L, 0, sizeof(L));
+  size_t off = 0;
+  auto take = [&](size_t n) { const size_t o = off; off = up(off + n, kAlign); return o; };
+  const size_t C = d.in_channels;
+  auto dds = [&](DdsW& w) {
+    for (int i = 0; i < 3; ++i) {
+      w.dw_w[i] = take(3 * C);
+      w.dw_b[i] = take(C);
+      w.pw_w[i] = take(C * C);
+      w.pw_b[i] = take(C);
+      w.n1g[i] = take(C);
+      w.n1b[i] = take(C);
+      w.n2g[i] = take(C);
+      w.n2b[i] = take(C);
+    }
+  };
+  if (d.kind == 0) {
+    L.pre_w = take(C * C);
+    L.pre_b = take(C);
+    dds(L.convs);
+    L.proj_w = take(C * C);
+    L.proj_b = take(C);
+    L.ea_m = take(2);
+    L.ea_logs = take(2);
+    for (int k = 0; k < d.n_flows - 1; ++k) {
+      L.f_pre_w[k] = take(C);
+      L.f_pre_b[k] = take(C);
+      dds(L.f_convs[k]);
+      L.f_proj_w[k] = take(C * kProj);
+      L.f_proj_b[k] = take(kProj);
+    }
+  } else {
+    const size_t F = d.filter_channels;
+    L.c1_w = take(3 * C * F);
+    L.c1_b = take(F);
+    L.n1g = take(F);
+    L.n1b = take(F);
+    L.c2_w = take(3 * F * F);
+    L.c2_b = take(F);
+    L.n2g = take(F);
+    L.n2b = take(F);
+    L.p_w = take(F);
+    L.p_b = take(1);
+  }
+  if (d.gin_channels > 0) {
+    L.cond_w = take(C * d.gin_channels);
+    L.cond_b = take(C);
+  }
+  L.total = off;
+  return L;
+}
+
+int n_tensors(const ttsdur_dims& d) {
+  const int g = d.gin_channels > 0 ? 2 : 0;
+  return d.kind == 0 ? 2 + 24 + 2 + 2 + (d.n_flows - 1) * 28 + g : 10 + g;
+}
+
+size_t ws_floats(const ttsdur_dims& d, int B, int T) {
+  const size_t M = (size_t)B * T, C = d.in_channels;
+  const size_t cond = up((size_t)B * C, kAlign);
+  if (d.kind == 0) return 4 * up(M * C, kAlign) + up(2 * M, kAlign) + cond;
+  return up(M * d.filter_channels, kAlign) + cond;
+}
+
+int dur_fail(ttsdur_handle* h, const char* where) {
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return TTSDEC_OK;
+  if (h) h->hip_err = std::string(where) + ": " + hipGetErrorString(e);
+  return TTSDEC_ERR_HIP;
+}
+
+// ===========================================================================
+// device helpers
+// ===========================================================================
+__device__ inline float wave_sum(float v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ inline float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }  // F.gelu, approximate='none'
+__device__ inline float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }                     // F.softplus, beta 1, threshold 20
+
+// LayerNorm over the channels of the rows of buf [kRows][n] in place (modules.LayerNorm, eps 1e-5), one wave per row, then
+// act: 0 none, 1 GELU.  relu_first: ReLU before the norm (DurationPredictor).
+__device__ void rows_layernorm(float* buf, int n, const float* gamma, const float* beta, int act, bool relu_first) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int r = wave; r < kRows; r += kThreads / 64) {
+    float* row = buf + (size_t)r * n;
+    if (relu_first)
+      for (int c = lane; c < n; c += 64) row[c] = fmaxf(row[c], 0.f);
+    float s = 0.f;
+    for (int c = lane; c < n; c += 64) s += row[c];
+    const float mean = wave_sum(s) / (float)n;
+    float q = 0.f;
+    for (int c = lane; c < n; c += 64) {
+      const float dv = row[c] - mean;
+      q += dv * dv;
+    }
+    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)n + 1e-5f);
+    for (int c = lane; c < n; c += 64) {
+      float y = (row[c] - mean) * rstd * gamma[c] + beta[c];
+      row[c] = act == 1 ? gelu_erf(y) : y;
+    }
+  }
+}
+
+// out[r][n] = sum_k At[k][r] * W[k][n] for the tile's rows, one column per lane (K-major W from L2, At in LDS: a k step reads
+// kRows contiguous floats, a broadcast); ldo: row stride of out in LDS
+__device__ void tile_gemm(const float* __restrict__ At, const float* __restrict__ W, const float* __restrict__ bias, int K, int N, float* out,
+                          int ldo) {
+  for (int n = threadIdx.x; n < N; n += kThreads) {
+    float acc[kRows];
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) acc[r] = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) {
+      const float w = W[(size_t)k * N + n];
+      const float4* a = reinterpret_cast<const float4*>(At + (size_t)k * kRows);
+#pragma unroll
+      for (int q = 0; q < kRows / 4; ++q) {
+        const float4 v = a[q];
+        acc[4 * q + 0] = fmaf(v.x, w, acc[4 * q + 0]);
+        acc[4 * q + 1] = fmaf(v.y, w, acc[4 * q + 1]);
+        acc[4 * q + 2] = fmaf(v.z, w, acc[4 * q + 2]);
+        acc[4 * q + 3] = fmaf(v.w, w, acc[4 * q + 3]);
+      }
+    }
+    const float b = bias ? bias[n] : 0.f;
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) out[(size_t)r * ldo + n] = acc[r] + b;
+  }
+}
+
+// The inverse of transforms.unconstrained_rational_quadratic_spline (tails "linear", tail_bound 5) for one input, with the
+// reference's fp32 operation order.  h: the 29 projected values of the row (already masked).
+__device__ float spline_inverse(float x, const float* h, float sqrt_c) {
+  if (!(x >= -kTail && x <= kTail)) return x;  // outside_interval_mask: identity
+  const float kMin = 1e-3f;
+  float cw[kBins + 1], ch[kBins + 1], der[kBins + 1];
+  auto cum = [&](int base, float* cu) {
+    float mx = -INFINITY, e[kBins], s = 0.f;
+    for (int i = 0; i < kBins; ++i) mx = fmaxf(mx, h[base + i] / sqrt_c);
+    for (int i = 0; i < kBins; ++i) {
+      e[i] = expf(h[base + i] / sqrt_c - mx);
+      s += e[i];
+    }
+    float c = 0.f;
+    cu[0] = -kTail;
+    for (int i = 0; i < kBins; ++i) {
+      const float wv = kMin + (1.f - kMin * kBins) * (e[i] / s);
+      c += wv;
+      cu[i + 1] = (2.f * kTail) * c + (-kTail);
+    }
+    cu[kBins] = kTail;
+  };
+  cum(0, cw);
+  cum(kBins, ch);
+  const float edge = (float)0.5397424172369522;  // np.log(np.exp(1 - 1e-3) - 1), padded at both ends (transforms.py:71-74)
+  der[0] = kMin + softplus(edge);
+  der[kBins] = der[0];
+  for (int i = 1; i < kBins; ++i) der[i] = kMin + softplus(h[2 * kBins + i - 1]);
+  // searchsorted(cumheights, x) with the eps on the last edge (transforms.py:45-47)
+  int idx = -1;
+  for (int i = 0; i <= kBins; ++i) {
+    const float e = i == kBins ? ch[kBins] + 1e-6f : ch[i];
+    idx += x >= e ? 1 : 0;
+  }
+  idx = idx < 0 ? 0 : (idx > kBins - 1 ? kBins - 1 : idx);
+  const float icw = cw[idx], ibw = cw[idx + 1] - cw[idx];
+  const float ich = ch[idx], ih = ch[idx + 1] - ch[idx];
+  const float delta = ih / ibw;
+  const float d0 = der[idx], d1 = der[idx + 1];
+  const float xs = x - ich;
+  const float t = d0 + d1 - 2.f * delta;
+  const float a = xs * t + ih * (delta - d0);
+  const float b = ih * d0 - xs * t;
+  const float c = -delta * xs;
+  const float disc = b * b - 4.f * a * c;
+  const float root = (2.f * c) / (-b - sqrtf(disc));
+  return root * ibw + icw;
+}
+
+// ===========================================================================
+// kernels
+// ===========================================================================
+// cond(g): out[b, n] = bias[n] + sum_k W[n, k] g[b, k]
+__global__ void dur_cond_kernel(const float* g, const float* W, const float* bias, float* out, int B, int N, int K) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * N) return;
+  const int b = i / N, n = i % N;
+  float acc = 0.f;
+  for (int k = 0; k < K; ++k) acc = fmaf(W[(size_t)n * K + k], g[(size_t)b * K + k], acc);
+  out[i] = acc + bias[n];
+}
+
+// src [N, Cin, taps] (a Conv1d weight) -> dst [taps * Cin][N] (K-major: row tap * Cin + ci)
+__global__ void pack_kmajor_kernel(const float* src, float* dst, int N, int Cin, int taps) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t total = (size_t)N * Cin * taps;
+  if (i >= total) return;
+  const int n = (int)(i % N);
+  const size_t k = i / N;
+  const int tap = (int)(k / Cin), ci = (int)(k % Cin);
+  dst[i] = src[((size_t)n * Cin + ci) * taps + tap];
+}
+
+struct PwArgs {
+  const float* x;          // [M, Cin] channel-last
+  int Cin, taps;           // taps 1 or 3 (padding 1)
+  const float* in_rowvec;  // [B, Cin]: x + in_rowvec before the conv (DurationPredictor's cond), or null
+  int in_mask;             // the conv reads x * mask (zero at frames >= lengths[b] and outside the utterance)
+  const float* W;          // [taps * Cin][N] K-major
+  const float* bias;       // [N]
+  int N;
+  const float* out_rowvec; // [B, N] added after the bias (the SDP's pre(x) + cond(g)), or null
+  int relu_ln;             // ReLU then LayerNorm(gamma, beta)
+  const float *gamma, *beta;
+  const float *proj_w, *proj_b;  // when set: logw[m] = mask * (proj_b + sum_n proj_w[n] * y[n])  instead of out
+  float* proj_out;
+  float* out;              // [M, N]
+  const int* lengths;
+  int T, M;
+};
+
+__global__ __launch_bounds__(kThreads) void pw_conv_kernel(PwArgs a) {
+  extern __shared__ float lds[];
+  const int K = a.taps * a.Cin;
+  float* At = lds;                         // [K][kRows]
+  float* Z = lds + (size_t)K * kRows;      // [kRows][N]
+  const int m0 = blockIdx.x * kRows;
+  const int half = a.taps / 2;
+  for (int idx = threadIdx.x; idx < K * kRows; idx += kThreads) {
+    const int r = idx % kRows, k = idx / kRows;
+    const int m = m0 + r;
+    float v = 0.f;
+    if (m < a.M) {
+      const int b = m / a.T, t = m % a.T;
+      const int tap = k / a.Cin, c = k % a.Cin;
+      const int tt = t + tap - half;
+      const int lim = a.in_mask ? min(a.lengths[b], a.T) : a.T;  // (a length beyond T reads no frame outside the utterance)
+      if (tt >= 0 && tt < lim) {
+        v = a.x[((size_t)b * a.T + tt) * a.Cin + c];
+        if (a.in_rowvec) v = v + a.in_rowvec[(size_t)b * a.Cin + c];
+      }
+    }
+    At[idx] = v;
+  }
+  __syncthreads();
+  tile_gemm(At, a.W, a.bias, K, a.N, Z, a.N);
+  __syncthreads();
+  if (a.out_rowvec)
+    for (int idx = threadIdx.x; idx < kRows * a.N; idx += kThreads) {
+      const int m = m0 + idx / a.N;
+      if (m < a.M) Z[idx] = Z[idx] + a.out_rowvec[(size_t)(m / a.T) * a.N + idx % a.N];
+    }
+  if (a.relu_ln) {
+    __syncthreads();
+    rows_layernorm(Z, a.N, a.gamma, a.beta, 0, true);
+  }
+  __syncthreads();
+  if (a.proj_out) {  // one wave per row: proj (N -> 1) on y * mask, then * mask
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int r = wave; r < kRows; r += kThreads / 64) {
+      const int m = m0 + r;
+      if (m >= a.M) continue;
+      float s = 0.f;
+      for (int n = lane; n < a.N; n += 64) s = fmaf(a.proj_w[n], Z[(size_t)r * a.N + n], s);
+      s = wave_sum(s);
+      if (lane == 0) a.proj_out[m] = (m % a.T) < a.lengths[m / a.T] ? s + a.proj_b[0] : 0.f;
+    }
+    return;
+  }
+  for (int idx = threadIdx.x; idx < kRows * a.N; idx += kThreads) {
+    const int m = m0 + idx / a.N;
+    if (m < a.M) a.out[(size_t)m * a.N + idx % a.N] = Z[idx];
+  }
+}
+
+enum { TAIL_NONE = 0, TAIL_PROJ = 1, TAIL_FLOW = 2 };
+
+struct DdsArgs {
+  const float* xin;        // [M, C] the layer's input x (layer > 0, or the conditioning path's first layer)
+  // head (a ConvFlow's first layer, xin null): x[m, c] = (pre_w[c] * x0[m] + pre_b[c]) + gadd[m, c], x0 = zin[b, c0, t] * zscale
+  const float *zin, *pre_w, *pre_b, *gadd;
+  float zscale;
+  int c0;                  // physical channel of the flow's x0 in zin / zout (the Flips before it, counted)
+  const float *dw_w, *dw_b, *pw_w, *pw_b, *n1g, *n1b, *n2g, *n2b;
+  int dil, last;           // last: the DDSConv output is x * mask
+  float* xout;             // [M, C] (layers before the last)
+  int tail;
+  const float *tw, *tb;    // TAIL_PROJ: [C][C], [C] -> xout = (proj(x) + b) * mask;  TAIL_FLOW: [C][29], [29]
+  float* zout;             // TAIL_FLOW: [B, 2, T] (may be zin)
+  const float *ea_m, *ea_logs;  // TAIL_FLOW of the last ConvFlow: logw = (spline(x1) - m[0]) * exp(-logs[0]) * mask
+  float* logw;
+  float sqrt_c;
+  const int* lengths;
+  int C, T, M;
+};
+
+__device__ inline float dds_input(const DdsArgs& a, int b, int t, int c) {
+  const size_t m = (size_t)b * a.T + t;
+  if (a.xin) return a.xin[m * a.C + c];
+  const float x0 = a.zin[((size_t)b * 2 + a.c0) * a.T + t] * a.zscale;
+  return (a.pre_w[c] * x0 + a.pre_b[c]) + a.gadd[m * a.C + c];
+}
+
+__global__ __launch_bounds__(kThreads) void dds_layer_kernel(DdsArgs a) {
+  extern __shared__ float lds[];
+  const int C = a.C;
+  float* X = lds;                          // [kRows][C] the layer's input x, then its output
+  float* Y = lds + (size_t)kRows * C;      // [kRows][C]
+  float* Tt = lds + (size_t)2 * kRows * C; // [C][kRows] GEMM operand
+  const int m0 = blockIdx.x * kRows;
+  // depthwise conv of x * mask (kernel 3, dilation d, zero padding d), and the residual x
+  for (int idx = threadIdx.x; idx < kRows * C; idx += kThreads) {
+    const int r = idx / C, c = idx % C;
+    const int m = m0 + r;
+    float xv = 0.f, y = 0.f;
+    if (m < a.M) {
+      const int b = m / a.T, t = m % a.T, len = min(a.lengths[b], a.T);
+      xv = dds_input(a, b, t, c);
+      float acc = 0.f;
+      for (int tap = 0; tap < 3; ++tap) {
+        const int tt = t + (tap - 1) * a.dil;
+        const float v = tt == t ? (t < len ? xv : 0.f) : (tt >= 0 && tt < len ? dds_input(a, b, tt, c) : 0.f);
+        acc = fmaf(a.dw_w[tap * C + c], v, acc);
+      }
+      y = acc + a.dw_b[c];
+    }
+    X[idx] = xv;
+    Y[idx] = y;
+  }
+  __syncthreads();
+  rows_layernorm(Y, C, a.n1g, a.n1b, 1, false);
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < kRows * C; idx += kThreads) {
+    const int r = idx % kRows, c = idx / kRows;
+    Tt[idx] = Y[r * C + c];
+  }
+  __syncthreads();
+  tile_gemm(Tt, a.pw_w, a.pw_b, C, C, Y, C);
+  __syncthreads();
+  rows_layernorm(Y, C, a.n2g, a.n2b, 1, false);
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < kRows * C; idx += kThreads) {
+    const int r = idx / C;
+    const int m = m0 + r;
+    float v = X[idx] + Y[idx];
+    if (a.last && (m >= a.M || (m % a.T) >= a.lengths[m / a.T])) v = 0.f;
+    X[idx] = v;
+    if (a.tail == TAIL_NONE && m < a.M) a.xout[(size_t)m * C + idx % C] = v;
+  }
+  if (a.tail == TAIL_NONE) return;
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < kRows * C; idx += kThreads) {
+    const int r = idx % kRows, c = idx / kRows;
+    Tt[idx] = X[r * C + c];
+  }
+  __syncthreads();
+  if (a.tail == TAIL_PROJ) {
+    tile_gemm(Tt, a.tw, a.tb, C, C, Y, C);
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < kRows * C; idx += kThreads) {
+      const int m = m0 + idx / C;
+      if (m < a.M) a.xout[(size_t)m * C + idx % C] = (m % a.T) < a.lengths[m / a.T] ? Y[idx] : 0.f;
+    }
+    return;
+  }
+  // TAIL_FLOW: h = proj(x) * mask [kRows][29]; x1 -> spline^-1; cat([x0, x1]) * mask
+  tile_gemm(Tt, a.tw, a.tb, C, kProj, Y, kProj);
+  __syncthreads();
+  if (threadIdx.x < kRows) {
+    const int r = threadIdx.x, m = m0 + r;
+    if (m < a.M) {
+      const int b = m / a.T, t = m % a.T;
+      const bool on = t < a.lengths[b];
+      float h[kProj];
+      for (int j = 0; j < kProj; ++j) h[j] = on ? Y[r * kProj + j] : 0.f;
+      const size_t i0 = ((size_t)b * 2 + a.c0) * a.T + t, i1 = ((size_t)b * 2 + (1 - a.c0)) * a.T + t;
+      const float x0 = a.zin[i0] * a.zscale, x1 = a.zin[i1] * a.zscale;
+      const float y1 = on ? spline_inverse(x1, h, a.sqrt_c) : 0.f;
+      if (a.logw) {  // Flip, then ElementwiseAffine reverse on channel 0 (= this flow's x1)
+        a.logw[m] = on ? (y1 - a.ea_m[0]) * expf(-a.ea_logs[0]) : 0.f;
+      } else {
+        a.zout[i0] = on ? x0 : 0.f;
+        a.zout[i1] = y1;
+      }
+    }
+  }
+}
+
+// w = exp(logw) * mask * length_scale, w_ceil = ceil(w), cum = running sum over the utterance's tokens, y_len = max(1, sum):
+// one lane per utterance (sums of integers below 2^24 are exact in fp32 in any order; counted in fp64 here to detect overflow)
+__global__ __launch_bounds__(256) void lengths_kernel(const float* logw, const int* lengths, float ls, int B, int T, int* cum, int* y_len,
+                                                       int* status) {
+  __shared__ int smax[256], sflag[256];
+  int mx = 0, fl = 0;
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const int len = lengths[b];
+    double s = 0.0;
+    for (int j = 0; j < T; ++j) {
+      const float w = expf(logw[(size_t)b * T + j]) * (j < len ? 1.f : 0.f) * ls;
+      if (!isfinite(w)) fl |= 1;
+      const float wc = ceilf(w);
+      if (isfinite(wc)) s += (double)wc;
+      if (s > 16777216.0) fl |= 2;
+      cum[(size_t)b * T + j] = s > 16777216.0 || !(s >= 0.0) ? 0 : (int)s;
+    }
+    const int yl = s > 16777216.0 || !(s >= 1.0) ? 1 : (int)s;
+    y_len[b] = yl;
+    mx = yl > mx ? yl : mx;
+  }
+  smax[threadIdx.x] = mx;
+  sflag[threadIdx.x] = fl;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      smax[threadIdx.x] = smax[threadIdx.x] > smax[threadIdx.x + o] ? smax[threadIdx.x] : smax[threadIdx.x + o];
+      sflag[threadIdx.x] |= sflag[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    status[0] = smax[0];
+    status[1] = sflag[0];
+  }
+}
+
+// the frame-rate prior of kExpFrames frames of one utterance: grid (ceil(T_y / kExpFrames), B)
+constexpr int kExpFrames = 32;
+__global__ __launch_bounds__(256) void expand_kernel(const int* cum, const float* m, const float* logs, const float* eps, int eps_T, float ns,
+                                                      int T, int Cc, int Ty, float* z_p, float* m_p, float* logs_p, float* attn) {
+  extern __shared__ float lds[];
+  float* E = lds;                                         // [Cc][kExpFrames + 1]
+  int* tok = reinterpret_cast<int*>(lds + (size_t)Cc * (kExpFrames + 1));  // [kExpFrames]
+  const int b = blockIdx.y, t0 = blockIdx.x * kExpFrames;
+  const int* cb = cum + (size_t)b * T;
+  if (threadIdx.x < kExpFrames) {
+    const int t = t0 + threadIdx.x;
+    // first j with cum[j] > t (t < cum[T-1] has one); -1: no token
+    int j = -1;
+    if (t < Ty && t < cb[T - 1]) {
+      int lo = 0, hi = T - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cb[mid] > t) hi = mid; else lo = mid + 1;
+      }
+      j = lo;
+    }
+    tok[threadIdx.x] = j;
+  }
+  for (int idx = threadIdx.x; idx < Cc * kExpFrames; idx += blockDim.x) {
+    const int c = idx / kExpFrames, tt = idx % kExpFrames;
+    const int t = t0 + tt;
+    E[c * (kExpFrames + 1) + tt] = t < Ty ? eps[((size_t)b * Cc + c) * eps_T + t] : 0.f;
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < Cc * kExpFrames; idx += blockDim.x) {
+    const int tt = idx / Cc, c = idx % Cc;
+    const int t = t0 + tt;
+    if (t >= Ty) break;
+    const int j = tok[tt];
+    const float mv = j >= 0 ? m[((size_t)b * T + j) * Cc + c] : 0.f;
+    const float lv = j >= 0 ? logs[((size_t)b * T + j) * Cc + c] : 0.f;
+    const size_t o = ((size_t)b * Ty + t) * Cc + c;
+    m_p[o] = mv;
+    logs_p[o] = lv;
+    z_p[o] = mv + E[c * (kExpFrames + 1) + tt] * expf(lv) * ns;
+  }
+  if (attn)
+    for (int idx = threadIdx.x; idx < T * kExpFrames; idx += blockDim.x) {
+      const int tt = idx / T, j = idx % T;
+      const int t = t0 + tt;
+      if (t >= Ty) break;
+      attn[((size_t)b * Ty + t) * T + j] = tok[tt] == j ? 1.f : 0.f;
+    }
+}
+
+size_t dds_lds(int C) { return (size_t)3 * kRows * C * sizeof(float); }
+size_t pw_lds(int Cin, int taps, int N) { return (size_t)kRows * (taps * Cin + N) * sizeof(float); }
+
+void run_dds(const ttsdur_handle* h, const DdsW& w, DdsArgs a, const float* x_first, float* bufA, float* bufB, int tail, hipStream_t st) {
+  const float* b = h->blob;
+  const unsigned nblk = (unsigned)((a.M + kRows - 1) / kRows);
+  const float* in = x_first;
+  for (int i = 0; i < 3; ++i) {
+    DdsArgs l = a;
+    l.xin = i > 0 ? in : x_first;  // (zin stays: the head reads it in layer 0, the spline epilogue in layer 2)
+    l.dw_w = b + w.dw_w[i]; l.dw_b = b + w.dw_b[i]; l.pw_w = b + w.pw_w[i]; l.pw_b = b + w.pw_b[i];
+    l.n1g = b + w.n1g[i]; l.n1b = b + w.n1b[i]; l.n2g = b + w.n2g[i]; l.n2b = b + w.n2b[i];
+    l.dil = i == 0 ? 1 : (i == 1 ? 3 : 9);  // kernel_size ** i
+    l.last = i == 2;
+    l.tail = i == 2 ? tail : TAIL_NONE;
+    float* out = (i % 2 == 0) ? bufA : bufB;
+    if (i < 2) l.xout = out;
+    hipLaunchKernelGGL(dds_layer_kernel, dim3(nblk), dim3(kThreads), dds_lds(a.C), st, l);
+    in = out;
+  }
+}
+
+int check_call(ttsdur_handle* h, int kind, const float* x, const int* lengths, const float* g, int B, int T, float* logw, void* ws,
+               size_t ws_bytes) {
+  if (!h || !x || !lengths || !logw || !ws || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (h->d.kind != kind) return TTSDEC_ERR_INVALID_ARG;
+  if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
+  if ((size_t)B * T > (size_t)1 << 30) return TTSDEC_ERR_DIMS;
+  if (ws_bytes < ws_floats(h->d, B, T) * sizeof(float) || (reinterpret_cast<uintptr_t>(ws) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  return TTSDEC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ttsdur_create(const ttsdur_dims* dims, ttsdur_handle** out) {
+  if (!dims || !out) return TTSDEC_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (!dims_ok(*dims)) return TTSDEC_ERR_DIMS;
+  ttsdur_handle* h = new (std::nothrow) ttsdur_handle();
+  if (!h) return TTSDEC_ERR_INVALID_ARG;
+  h->d = *dims;
+  h->bl = make_layout(*dims);
+  h->blob = nullptr;
+  h->device = current_device_or_minus1();
+  *out = h;
+  return TTSDEC_OK;
+}
+int ttsdur_destroy(ttsdur_handle* h) {
+  delete h;
+  return TTSDEC_OK;
+}
+const char* ttsdur_last_hip_error(const ttsdur_handle* h) { return h ? h->hip_err.c_str() : ""; }
+int ttsdur_num_weight_tensors(const ttsdur_handle* h) { return h ? n_tensors(h->d) : TTSDEC_ERR_INVALID_ARG; }
+size_t ttsdur_packed_bytes(const ttsdur_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
+
+int ttsdur_pack_weights(ttsdur_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
+  if (!h || !src || !blob || n_src != ttsdur_num_weight_tensors(h)) return TTSDEC_ERR_INVALID_ARG;
+  for (int i = 0; i < n_src; ++i)
+    if (!src[i]) return TTSDEC_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(blob) & 255) return TTSDEC_ERR_WORKSPACE;
+  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ttsdur_dims& d = h->d;
+  const DurBlob& L = h->bl;
+  float* b = static_cast<float*>(blob);
+  if (hipMemsetAsync(blob, 0, L.total * sizeof(float), st) != hipSuccess) return dur_fail(h, "memset");
+  const int C = d.in_channels;
+  int k = 0;
+  auto kmajor = [&](size_t off, int N, int Cin, int taps) {
+    hipLaunchKernelGGL(pack_kmajor_kernel, grid1((size_t)N * Cin * taps), dim3(256), 0, st, src[k++], b + off, N, Cin, taps);
+  };
+  auto copy = [&](size_t off, size_t n) { launch_copy(src[k++], b + off, n, st); };
+  auto dds = [&](const DdsW& w) {
+    for (int i = 0; i < 3; ++i) {
+      kmajor(w.dw_w[i], C, 1, 3);  // [C, 1, 3] -> [3][C]
+      copy(w.dw_b[i], C);
+      kmajor(w.pw_w[i], C, C, 1);
+      copy(w.pw_b[i], C);
+      copy(w.n1g[i], C);
+      copy(w.n1b[i], C);
+      copy(w.n2g[i], C);
+      copy(w.n2b[i], C);
+    }
+  };
+  if (d.kind == 0) {
+    kmajor(L.pre_w, C, C, 1);
+    copy(L.pre_b, C);
+    dds(L.convs);
+    kmajor(L.proj_w, C, C, 1);
+    copy(L.proj_b, C);
+    copy(L.ea_m, 2);
+    copy(L.ea_logs, 2);
+    for (int f = 0; f < d.n_flows - 1; ++f) {
+      copy(L.f_pre_w[f], C);  // [C, 1, 1]
+      copy(L.f_pre_b[f], C);
+      dds(L.f_convs[f]);
+      kmajor(L.f_proj_w[f], kProj, C, 1);
+      copy(L.f_proj_b[f], kProj);
+    }
+  } else {
+    const int F = d.filter_channels;
+    kmajor(L.c1_w, F, C, 3);
+    copy(L.c1_b, F);
+    copy(L.n1g, F);
+    copy(L.n1b, F);
+    kmajor(L.c2_w, F, F, 3);
+    copy(L.c2_b, F);
+    copy(L.n2g, F);
+    copy(L.n2b, F);
+    copy(L.p_w, F);
+    copy(L.p_b, 1);
+  }
+  if (d.gin_channels > 0) {
+    copy(L.cond_w, (size_t)C * d.gin_channels);
+    copy(L.cond_b, C);
+  }
+  const int rc = dur_fail(h, "pack_weights");
+  if (rc == TTSDEC_OK) h->blob = b;
+  return rc;
+}
+
+int ttsdur_bind_weights(ttsdur_handle* h, const void* blob) {
+  if (!h || !blob || (reinterpret_cast<uintptr_t>(blob) & 255)) return TTSDEC_ERR_INVALID_ARG;
+  h->blob = static_cast<const float*>(blob);
+  return TTSDEC_OK;
+}
+
+size_t ttsdur_workspace_bytes(const ttsdur_handle* h, int B, int T) {
+  if (!h || B <= 0 || T <= 0) return 0;
+  return ws_floats(h->d, B, T) * sizeof(float);
+}
+
+int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths, const float* g, const float* noise, float noise_scale, int B,
+                       int T, float* logw, void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = check_call(h, 0, x, lengths, g, B, T, logw, workspace, workspace_bytes);
+  if (rc != TTSDEC_OK) return rc;
+  if (!noise) return TTSDEC_ERR_INVALID_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ttsdur_dims& d = h->d;
+  const DurBlob& L = h->bl;
+  const float* b = h->blob;
+  const int C = d.in_channels, M = B * T;
+  const size_t F = up((size_t)M * C, kAlign);
+  float* ws = static_cast<float*>(workspace);
+  float *XP = ws, *XA = ws + F, *XB = ws + 2 * F, *XC = ws + 3 * F;
+  float* Z = ws + 4 * F;                       // [B, 2, T]
+  float* condv = Z + up((size_t)2 * M, kAlign);  // [B, C]
+  const unsigned nblk = (unsigned)((M + kRows - 1) / kRows);
+  if (g) hipLaunchKernelGGL(dur_cond_kernel, grid1((size_t)B * C), dim3(256), 0, st, g, b + L.cond_w, b + L.cond_b, condv, B, C, d.gin_channels);
+  {  // models.py:80-84: x = pre(x) (+ cond(g))
+    PwArgs p;
+    memset(&p, 0, sizeof(p));
+    p.x = x; p.Cin = C; p.taps = 1; p.W = b + L.pre_w; p.bias = b + L.pre_b; p.N = C; p.out_rowvec = g ? condv : nullptr;
+    p.out = XP; p.lengths = lengths; p.T = T; p.M = M;
+    hipLaunchKernelGGL(pw_conv_kernel, dim3(nblk), dim3(kThreads), pw_lds(C, 1, C), st, p);
+  }
+  DdsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.lengths = lengths; a.C = C; a.T = T; a.M = M; a.zscale = 1.f; a.sqrt_c = sqrtf((float)C);
+  {  // :85-86: x = proj(convs(x, x_mask)) * x_mask -> XC
+    DdsArgs c = a;
+    c.tw = b + L.proj_w; c.tb = b + L.proj_b; c.xout = XC;
+    run_dds(h, L.convs, c, XP, XA, XB, TAIL_PROJ, st);
+    // (run_dds hands layer 2 xout = XC through c.xout: the tail writes it)
+  }
+  // :127-133: [Flip, ConvFlow_{n-1}, Flip, ..., ConvFlow_1, Flip, ElementwiseAffine]; z = noise * noise_scale
+  int c0 = 1;  // the first Flip
+  for (int f = d.n_flows - 2; f >= 0; --f) {
+    DdsArgs c = a;
+    c.zin = f == d.n_flows - 2 ? noise : Z;
+    c.zscale = f == d.n_flows - 2 ? noise_scale : 1.f;
+    c.c0 = c0;
+    c.pre_w = b + L.f_pre_w[f]; c.pre_b = b + L.f_pre_b[f]; c.gadd = XC;
+    c.tw = b + L.f_proj_w[f]; c.tb = b + L.f_proj_b[f];
+    c.zout = Z;
+    if (f == 0) {
+      c.logw = logw;
+      c.ea_m = b + L.ea_m;
+      c.ea_logs = b + L.ea_logs;
+    }
+    run_dds(h, L.f_convs[f], c, nullptr, XA, XB, TAIL_FLOW, st);
+    c0 ^= 1;  // the Flip after it
+  }
+  return dur_fail(h, "sdp_reverse");
+}
+
+int ttsdur_dp_forward(ttsdur_handle* h, const float* x, const int32_t* lengths, const float* g, int B, int T, float* logw, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  int rc = check_call(h, 1, x, lengths, g, B, T, logw, workspace, workspace_bytes);
+  if (rc != TTSDEC_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ttsdur_dims& d = h->d;
+  const DurBlob& L = h->bl;
+  const float* b = h->blob;
+  const int C = d.in_channels, Fc = d.filter_channels, M = B * T;
+  float* ws = static_cast<float*>(workspace);
+  float* H1 = ws;
+  float* condv = ws + up((size_t)M * Fc, kAlign);
+  const unsigned nblk = (unsigned)((M + kRows - 1) / kRows);
+  if (g) hipLaunchKernelGGL(dur_cond_kernel, grid1((size_t)B * C), dim3(256), 0, st, g, b + L.cond_w, b + L.cond_b, condv, B, C, d.gin_channels);
+  PwArgs p;
+  memset(&p, 0, sizeof(p));
+  p.lengths = lengths; p.T = T; p.M = M; p.taps = 3; p.in_mask = 1; p.relu_ln = 1;
+  // models.py:171-174: x = norm_1(relu(conv_1((x + cond(g)) * x_mask)))
+  p.x = x; p.Cin = C; p.in_rowvec = g ? condv : nullptr; p.W = b + L.c1_w; p.bias = b + L.c1_b; p.N = Fc;
+  p.gamma = b + L.n1g; p.beta = b + L.n1b; p.out = H1;
+  hipLaunchKernelGGL(pw_conv_kernel, dim3(nblk), dim3(kThreads), pw_lds(C, 3, Fc), st, p);
+  // :175-180: x = norm_2(relu(conv_2(x * x_mask))); proj(x * x_mask) * x_mask
+  p.x = H1; p.Cin = Fc; p.in_rowvec = nullptr; p.W = b + L.c2_w; p.bias = b + L.c2_b;
+  p.gamma = b + L.n2g; p.beta = b + L.n2b; p.out = nullptr;
+  p.proj_w = b + L.p_w; p.proj_b = b + L.p_b; p.proj_out = logw;
+  hipLaunchKernelGGL(pw_conv_kernel, dim3(nblk), dim3(kThreads), pw_lds(Fc, 3, Fc), st, p);
+  return dur_fail(h, "dp_forward");
+}
+
+int ttsdur_lengths(ttsdur_handle* h, const float* logw, const int32_t* lengths, float length_scale, int B, int T, int32_t* cum,
+                   int32_t* y_len, int32_t* status, void* stream) {
+  if (!h || !logw || !lengths || !cum || !y_len || !status || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  hipLaunchKernelGGL(lengths_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), logw, lengths, length_scale, B, T, cum, y_len,
+                     status);
+  return dur_fail(h, "lengths");
+}
+
+int ttsdur_expand(ttsdur_handle* h, const int32_t* cum, const float* m, const float* logs, const float* eps, int eps_T, float noise_scale,
+                  int B, int T, int inter, int T_y, float* z_p, float* m_p, float* logs_p, float* attn, void* stream) {
+  if (!h || !cum || !m || !logs || !eps || !z_p || !m_p || !logs_p || B <= 0 || T <= 0 || T_y <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (inter <= 0 || inter > kMaxC || eps_T < T_y || B > 65535) return TTSDEC_ERR_DIMS;
+  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  const size_t lds = (size_t)inter * (kExpFrames + 1) * sizeof(float) + kExpFrames * sizeof(int);
+  hipLaunchKernelGGL(expand_kernel, dim3((unsigned)((T_y + kExpFrames - 1) / kExpFrames), (unsigned)B), dim3(256), lds,
+                     static_cast<hipStream_t>(stream), cum, m, logs, eps, eps_T, noise_scale, T, inter, T_y, z_p, m_p, logs_p, attn);
+  return dur_fail(h, "expand");
+}
+
+}  // extern "C"

@@ -6,9 +6,14 @@
                                              (``forward(x, x_mask, g=None, reverse=True)``)
 * ``Generator`` (+ ``ResBlock1``)         - the HiFi-GAN generator, vits2/models.py:900-974 and modules.py:221-315
                                              (``forward(x, g=None) -> [B, 1, T * prod(upsample_rates)]``; ``ttsgen_*``)
+* ``StochasticDurationPredictor``         - vits2/models.py:29-137, reverse only (``forward(x, x_mask, g=None, reverse=True,
+                                             noise_scale=1.0) -> logw [B, 1, T]``; ``ttsdur_*``)
+* ``DurationPredictor``                   - vits2/models.py:140-180 (``forward(x, x_mask, g=None) -> logw [B, 1, T]``)
+* ``infer(net_g, x, x_lengths, ...)``     - SynthesizerTrn.infer (models.py:1288-1323) over the four drop-ins, channel-last
+                                             from the ids to the waveform
 
 All hold the reference's parameters (so checkpoints load) and run inference through the HIP library
-(``ttsvits_*`` / ``ttsgen_*`` in include/ttsdec.h).  The library works on channel-last activations; the [B, C, T]
+(``ttsvits_*`` / ``ttsgen_*`` / ``ttsdur_*`` in include/ttsdec.h).  The library works on channel-last activations; the [B, C, T]
 tensors of the reference API are transposed here.  Training / the forward (non-reverse) direction of
 the flow / speaker conditioning are outside the path and raise."""
 from __future__ import annotations
@@ -269,16 +274,20 @@ class TextEncoder(PackedWeightsMixin, nn.Module):
         return d
 
     def forward(self, x, x_lengths, g=None):
+        xo, m, logs = self.forward_cl(x, x_lengths, g)
+        T = x.shape[1]
+        x_mask = (torch.arange(T, device=x.device)[None, :] < x_lengths.to(x.device)[:, None]).unsqueeze(1).to(xo.dtype)
+        return xo.transpose(1, 2), m.transpose(1, 2), logs.transpose(1, 2), x_mask
+
+    def forward_cl(self, x, x_lengths, g=None):
+        """forward's x, m, logs channel-last [B, T, C] (the library's own layout; ``infer`` chains it)."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError("the HIP text encoder is inference-only: call under torch.no_grad()")
         eng = self._engines.get(self._dims(), x.device)
         eng.set_precision(self.precision)
         spk = [self.encoder.spk_emb_linear.weight, self.encoder.spk_emb_linear.bias] if self.gin_channels else []
         eng.ensure_packed([self.emb.weight] + spk + self.encoder.weight_tensors() + [self.proj.weight, self.proj.bias])
-        xo, m, logs = eng.text_encoder(x, x_lengths, g)
-        T = x.shape[1]
-        x_mask = (torch.arange(T, device=x.device)[None, :] < x_lengths.to(x.device)[:, None]).unsqueeze(1).to(xo.dtype)
-        return xo.transpose(1, 2), m.transpose(1, 2), logs.transpose(1, 2), x_mask
+        return eng.text_encoder(x, x_lengths, g)
 
 
 class _WN(nn.Module):
@@ -358,9 +367,15 @@ class ResidualCouplingTransformersBlock(PackedWeightsMixin, nn.Module):
     def forward(self, x, x_mask, g=None, reverse=False):
         if not reverse:
             raise NotImplementedError("only the reverse (inference) direction is on the HIP path")
+        lengths = x_mask[:, 0, :].sum(dim=1).round().to(torch.int32)  # sequence_mask is a prefix mask
+        out = self.reverse_cl(x.transpose(1, 2), lengths, g)
+        return out.transpose(1, 2)
+
+    def reverse_cl(self, z_cl, lengths, g=None):
+        """The reverse pass on channel-last z [B, T, channels] with lengths [B] (``infer`` chains it)."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError("the HIP flow is inference-only: call under torch.no_grad()")
-        eng = self._engines.get(self._dims(), x.device)
+        eng = self._engines.get(self._dims(), z_cl.device)
         eng.set_precision(self.precision)
 
         def tensors() -> List[Optional[torch.Tensor]]:
@@ -371,9 +386,7 @@ class ResidualCouplingTransformersBlock(PackedWeightsMixin, nn.Module):
             return ts
 
         eng.ensure_packed(tensors, key_tensors=list(self.parameters()))
-        lengths = x_mask[:, 0, :].sum(dim=1).round().to(torch.int32)  # sequence_mask is a prefix mask
-        out = eng.flow_reverse(x.transpose(1, 2), lengths, g)
-        return out.transpose(1, 2)
+        return eng.flow_reverse(z_cl, lengths, g)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -618,8 +631,374 @@ class Generator(PackedWeightsMixin, nn.Module):
         out = eng.forward(x.transpose(1, 2).contiguous(), self._speaker(g, B))  # (a copy also makes infer's sliced z contiguous)
         return out.unsqueeze(1)
 
+    def forward_cl(self, z_cl, g=None):
+        """forward on channel-last z [B, T, C] -> [B, T * prod(upsample_rates)] (``infer`` chains it)."""
+        eng = self._engine(z_cl)
+        return eng.forward(z_cl.contiguous(), self._speaker(g, z_cl.shape[0]))
+
     def stage_outputs(self, x, g=None, n_stages=0) -> torch.Tensor:
         """Test aid: the activated output of the first ``n_stages`` upsampling stages (0: conv_pre's), channel-last
         [B, T_s, C_s] - leaky_relu(x, 0.1), or 0.01 after the last stage."""
         eng = self._engine(x)
         return eng.forward(x.transpose(1, 2).contiguous(), self._speaker(g, x.shape[0]), n_stages=n_stages)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Duration predictors (models.py:29-180) and text -> waveform inference (SynthesizerTrn.infer, models.py:1288-1323) through
+# ttsdur_* (include/ttsdec.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+class _DDSConv(nn.Module):
+    """modules.DDSConv parameter layout (modules.py:84-115)."""
+
+    def __init__(self, channels, kernel_size, n_layers, p_dropout=0.0):
+        super().__init__()
+        self.channels, self.kernel_size, self.n_layers, self.p_dropout = channels, kernel_size, n_layers, p_dropout
+        self.drop = nn.Dropout(p_dropout)
+        self.convs_sep, self.convs_1x1 = nn.ModuleList(), nn.ModuleList()
+        self.norms_1, self.norms_2 = nn.ModuleList(), nn.ModuleList()
+        for i in range(n_layers):
+            dilation = kernel_size**i
+            padding = (kernel_size * dilation - dilation) // 2
+            self.convs_sep.append(nn.Conv1d(channels, channels, kernel_size, groups=channels, dilation=dilation, padding=padding))
+            self.convs_1x1.append(nn.Conv1d(channels, channels, 1))
+            self.norms_1.append(_LayerNorm(channels))
+            self.norms_2.append(_LayerNorm(channels))
+
+    def weight_tensors(self) -> List[torch.Tensor]:
+        out = []
+        for i in range(self.n_layers):
+            out += [self.convs_sep[i].weight, self.convs_sep[i].bias, self.convs_1x1[i].weight, self.convs_1x1[i].bias,
+                    self.norms_1[i].gamma, self.norms_1[i].beta, self.norms_2[i].gamma, self.norms_2[i].beta]
+        return out
+
+
+class _ConvFlow(nn.Module):
+    """modules.ConvFlow parameter layout (modules.py:459-482), num_bins 10."""
+
+    def __init__(self, in_channels, filter_channels, kernel_size, n_layers, num_bins=10, tail_bound=5.0):
+        super().__init__()
+        self.in_channels, self.filter_channels, self.kernel_size, self.n_layers = in_channels, filter_channels, kernel_size, n_layers
+        self.num_bins, self.tail_bound, self.half_channels = num_bins, tail_bound, in_channels // 2
+        self.pre = nn.Conv1d(self.half_channels, filter_channels, 1)
+        self.convs = _DDSConv(filter_channels, kernel_size, n_layers, p_dropout=0.0)
+        self.proj = nn.Conv1d(filter_channels, self.half_channels * (num_bins * 3 - 1), 1)
+        self.proj.weight.data.zero_()
+        self.proj.bias.data.zero_()
+
+    def weight_tensors(self) -> List[torch.Tensor]:
+        return [self.pre.weight, self.pre.bias] + self.convs.weight_tensors() + [self.proj.weight, self.proj.bias]
+
+
+class _ElementwiseAffine(nn.Module):  # modules.ElementwiseAffine (modules.py:384-390)
+    def __init__(self, channels):
+        super().__init__()
+        self.channels = channels
+        self.m = nn.Parameter(torch.zeros(channels, 1))
+        self.logs = nn.Parameter(torch.zeros(channels, 1))
+
+
+class _Log(nn.Module):  # modules.Log: no parameters (training direction only)
+    pass
+
+
+class DurEngine:
+    """One ttsdur handle on one device."""
+
+    def __init__(self, dims: Dict, device: torch.device):
+        self._lib = _lib.load()
+        self.device = device
+        self.dims = dims
+        d = _lib.DurDims(*[int(dims[n]) for n, _ in _lib.DurDims._fields_])
+        h = C.c_void_p()
+        with torch.cuda.device(device):
+            rc = self._lib.ttsdur_create(C.byref(d), C.byref(h))
+        if rc == _lib.ERR_DIMS:
+            raise NotImplementedError(f"these duration-predictor dimensions are not built in the HIP library (include/ttsdec.h ttsdur_dims): {dims}")
+        _lib.check(rc, "ttsdur_create")
+        self._h = h
+        self.blob: Optional[torch.Tensor] = None
+        self._fingerprint = None
+        self._ws: Optional[torch.Tensor] = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ttsdur_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _err(self, rc, what):
+        if rc != _lib.OK:
+            raise _lib.TtsdecError(rc, what, self._lib.ttsdur_last_hip_error(self._h).decode())
+
+    def ensure_packed(self, tensors: List[torch.Tensor]) -> None:
+        fp = weights_fingerprint(tensors)
+        if self.blob is not None and fp == self._fingerprint:
+            return
+        n = len(tensors)
+        assert n == int(self._lib.ttsdur_num_weight_tensors(self._h)), (n, int(self._lib.ttsdur_num_weight_tensors(self._h)))
+        arr = (C.c_void_p * n)()
+        keep = []
+        for i, t in enumerate(tensors):
+            _require_device(t, "duration predictor weights")
+            tc = t.detach().to(torch.float32).contiguous()
+            keep.append(tc)
+            arr[i] = tc.data_ptr()
+        with torch.cuda.device(self.device):
+            blob = torch.empty(self._lib.ttsdur_packed_bytes(self._h), dtype=torch.uint8, device=self.device)
+            rc = self._lib.ttsdur_pack_weights(self._h, arr, n, blob.data_ptr(), _stream(self.device))
+            torch.cuda.current_stream(self.device).synchronize()  # `keep` must outlive the packing kernels
+        self._err(rc, "ttsdur_pack_weights")
+        self.blob, self._fingerprint = blob, fp
+
+    def workspace(self, B: int, T: int) -> torch.Tensor:
+        nbytes = int(self._lib.ttsdur_workspace_bytes(self._h, B, T))
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def logw(self, x_cl: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor], noise: Optional[torch.Tensor] = None,
+             noise_scale: float = 1.0) -> torch.Tensor:
+        """x_cl [B, T, C] contiguous fp32, lengths [B] int32 (device), g [B, gin] or None; noise [B, 2, T] (SDP) -> logw [B, T]."""
+        B, T, _ = x_cl.shape
+        ws = self.workspace(B, T)
+        out = torch.empty(B, T, device=self.device)
+        gp = g.data_ptr() if g is not None else None
+        with torch.cuda.device(self.device):
+            if self.dims["kind"] == _lib.DUR_SDP:
+                rc = self._lib.ttsdur_sdp_reverse(self._h, x_cl.data_ptr(), lengths.data_ptr(), gp, noise.data_ptr(), float(noise_scale), B, T,
+                                                  out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
+            else:
+                rc = self._lib.ttsdur_dp_forward(self._h, x_cl.data_ptr(), lengths.data_ptr(), gp, B, T, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 _stream(self.device))
+        self._err(rc, "ttsdur_sdp_reverse" if self.dims["kind"] == _lib.DUR_SDP else "ttsdur_dp_forward")
+        return out
+
+    def lengths(self, logw: torch.Tensor, x_lengths: torch.Tensor, length_scale: float):
+        """-> cum [B, T] int32, y_len [B] int32 and (max y_len, flags) read back: the call's one host sync."""
+        B, T = logw.shape
+        cum = torch.empty(B, T, dtype=torch.int32, device=self.device)
+        y_len = torch.empty(B, dtype=torch.int32, device=self.device)
+        status = torch.empty(2, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsdur_lengths(self._h, logw.data_ptr(), x_lengths.data_ptr(), float(length_scale), B, T, cum.data_ptr(), y_len.data_ptr(),
+                                          status.data_ptr(), _stream(self.device))
+        self._err(rc, "ttsdur_lengths")
+        T_y, flags = status.tolist()
+        if flags & 1:
+            raise ValueError("non-finite duration: exp(logw) * length_scale is inf or nan for some token")
+        if flags & 2:
+            raise ValueError("the durations of an utterance sum beyond 2^24 frames, where fp32 stops counting frames exactly")
+        return cum, y_len, T_y
+
+    def expand(self, cum, m_cl, logs_cl, eps, noise_scale, T_y, with_attn=True):
+        """-> z_p, m_p, logs_p [B, T_y, C] channel-last and attn [B, T_y, T] (include/ttsdec.h ttsdur_expand)."""
+        B, T, Cc = m_cl.shape
+        if eps.dim() != 3 or eps.shape[0] != B or eps.shape[1] != Cc or eps.shape[2] < T_y:
+            raise ValueError(f"the prior noise must be [B, C, >= T_y] = [{B}, {Cc}, >= {T_y}], got {tuple(eps.shape)}")
+        eps = eps.to(device=self.device, dtype=torch.float32).contiguous()
+        z_p = torch.empty(B, T_y, Cc, device=self.device)
+        m_p = torch.empty_like(z_p)
+        logs_p = torch.empty_like(z_p)
+        attn = torch.empty(B, T_y, T, device=self.device) if with_attn else None
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsdur_expand(self._h, cum.data_ptr(), m_cl.data_ptr(), logs_cl.data_ptr(), eps.data_ptr(), eps.shape[2], float(noise_scale),
+                                         B, T, Cc, T_y, z_p.data_ptr(), m_p.data_ptr(), logs_p.data_ptr(),
+                                         attn.data_ptr() if attn is not None else None, _stream(self.device))
+        self._err(rc, "ttsdur_expand")
+        return z_p, m_p, logs_p, attn
+
+
+class _DurEngCache(_EngCache):
+    def get(self, dims, device) -> DurEngine:
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        eng = self.by_dev.get(key)
+        if eng is None:
+            eng = DurEngine(dims, torch.device("cuda", key))
+            self.by_dev[key] = eng
+        return eng
+
+    def __deepcopy__(self, memo):
+        return _DurEngCache()
+
+
+class _DurationBase(PackedWeightsMixin, nn.Module):
+    def _check(self, x: torch.Tensor) -> None:
+        if not x.is_cuda or any(not p.is_cuda for p in self.parameters()):
+            raise NotImplementedError("the HIP duration predictor runs on a ROCm device only: move the module and its input there")
+        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
+            raise NotImplementedError("the HIP duration predictor is exact fp32: input and parameters must be torch.float32")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("the HIP duration predictor is inference-only: call under torch.no_grad()")
+
+    def _speaker(self, g: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
+        if g is None:
+            return None
+        if not self.gin_channels:
+            raise ValueError("g was given to a duration predictor built with gin_channels = 0")
+        _require_device(g, "g")
+        if g.dim() == 3:
+            if g.shape[2] != 1:
+                raise NotImplementedError("a time-varying g [B, gin, T] is outside the HIP path (the reference's callers pass [B, gin, 1])")
+            g = g[:, :, 0]
+        if tuple(g.shape) != (B, self.gin_channels):
+            raise ValueError(f"g must be [B, gin_channels(, 1)] = [{B}, {self.gin_channels}(, 1)], got {tuple(g.shape)}")
+        return g.to(torch.float32).contiguous()
+
+    def _engine(self, device) -> DurEngine:
+        eng = self._engines.get(self._cfg, device)
+        eng.ensure_packed(self.weight_tensors())
+        return eng
+
+    @staticmethod
+    def _channel_last(x: torch.Tensor) -> torch.Tensor:
+        """[B, C, T] -> [B, T, C] contiguous; a transposed view of a channel-last buffer (what TextEncoder returns) is not copied."""
+        xc = x.transpose(1, 2)
+        return xc if xc.is_contiguous() else xc.contiguous()
+
+    @staticmethod
+    def _lengths(x_mask: torch.Tensor) -> torch.Tensor:
+        return x_mask[:, 0, :].sum(dim=1).round().to(torch.int32)  # sequence_mask is a prefix mask
+
+
+class StochasticDurationPredictor(_DurationBase):
+    """models.StochasticDurationPredictor (models.py:29-137): same constructor, parameters and state-dict keys (the training-only
+    post_* modules and flows.1 included, unused).  ``forward(x, x_mask, g=g, reverse=True, noise_scale=...) -> logw [B, 1, T]``
+    runs in the HIP library in exact fp32; the forward (training) direction raises.  ``noise=`` (keyword, test hook) replaces the
+    reference's draw torch.randn(B, 2, T) on the CPU generator."""
+
+    def __init__(self, in_channels, filter_channels, kernel_size, p_dropout, n_flows=4, gin_channels=0):
+        super().__init__()
+        self._watch_state_dict_loads()
+        filter_channels = in_channels  # models.py:40
+        self.in_channels, self.filter_channels, self.kernel_size, self.p_dropout = in_channels, filter_channels, kernel_size, p_dropout
+        self.n_flows, self.gin_channels = n_flows, gin_channels
+        self.log_flow = _Log()
+        self.flows = nn.ModuleList()
+        self.flows.append(_ElementwiseAffine(2))
+        for _ in range(n_flows):
+            self.flows.append(_ConvFlow(2, filter_channels, kernel_size, n_layers=3))
+            self.flows.append(_Flip())
+        self.post_pre = nn.Conv1d(1, filter_channels, 1)
+        self.post_proj = nn.Conv1d(filter_channels, filter_channels, 1)
+        self.post_convs = _DDSConv(filter_channels, kernel_size, n_layers=3, p_dropout=p_dropout)
+        self.post_flows = nn.ModuleList()
+        self.post_flows.append(_ElementwiseAffine(2))
+        for _ in range(4):
+            self.post_flows.append(_ConvFlow(2, filter_channels, kernel_size, n_layers=3))
+            self.post_flows.append(_Flip())
+        self.pre = nn.Conv1d(in_channels, filter_channels, 1)
+        self.proj = nn.Conv1d(filter_channels, filter_channels, 1)
+        self.convs = _DDSConv(filter_channels, kernel_size, n_layers=3, p_dropout=p_dropout)
+        if gin_channels != 0:
+            self.cond = nn.Conv1d(gin_channels, filter_channels, 1)
+        self._cfg = dict(kind=_lib.DUR_SDP, in_channels=in_channels, filter_channels=filter_channels, kernel_size=kernel_size, n_flows=n_flows,
+                         gin_channels=gin_channels)
+        self._engines = _DurEngCache()
+
+    def weight_tensors(self) -> List[torch.Tensor]:
+        """ttsdur_pack_weights' order (include/ttsdec.h): the reverse path's parameters; flows.1 and post_* are not read."""
+        out = [self.pre.weight, self.pre.bias] + self.convs.weight_tensors() + [self.proj.weight, self.proj.bias]
+        out += [self.flows[0].m, self.flows[0].logs]
+        for k in range(1, self.n_flows):
+            out += self.flows[2 * k + 1].weight_tensors()
+        if self.gin_channels:
+            out += [self.cond.weight, self.cond.bias]
+        return out
+
+    def logw_cl(self, x_cl, lengths, g=None, noise_scale=1.0, noise=None) -> torch.Tensor:
+        """Reverse pass on channel-last x [B, T, C] with lengths [B] -> logw [B, T] (``infer`` chains it)."""
+        self._check(x_cl)
+        B, T, _ = x_cl.shape
+        if noise is None:
+            noise = torch.randn(B, 2, T)  # models.py:129-132: drawn on the CPU generator, then moved
+        if tuple(noise.shape) != (B, 2, T):
+            raise ValueError(f"noise must be [B, 2, T] = [{B}, 2, {T}], got {tuple(noise.shape)}")
+        noise = noise.to(device=x_cl.device, dtype=torch.float32).contiguous()
+        eng = self._engine(x_cl.device)
+        return eng.logw(x_cl.to(torch.float32).contiguous(), lengths.to(device=x_cl.device, dtype=torch.int32).contiguous(),
+                        self._speaker(g, B), noise, noise_scale)
+
+    def forward(self, x, x_mask, w=None, g=None, reverse=False, noise_scale=1.0, *, noise=None):
+        if not reverse:
+            raise NotImplementedError("only the reverse (inference) direction of the stochastic duration predictor is on the HIP path")
+        self._check(x)
+        return self.logw_cl(self._channel_last(x), self._lengths(x_mask), g, noise_scale, noise).unsqueeze(1)
+
+
+class DurationPredictor(_DurationBase):
+    """models.DurationPredictor (models.py:140-180): same constructor, parameters and state-dict keys; ``forward(x, x_mask,
+    g=None) -> logw [B, 1, T]`` in the HIP library in exact fp32, inference only."""
+
+    def __init__(self, in_channels, filter_channels, kernel_size, p_dropout, gin_channels=0):
+        super().__init__()
+        self._watch_state_dict_loads()
+        self.in_channels, self.filter_channels, self.kernel_size, self.p_dropout, self.gin_channels = (
+            in_channels, filter_channels, kernel_size, p_dropout, gin_channels)
+        self.drop = nn.Dropout(p_dropout)
+        self.conv_1 = nn.Conv1d(in_channels, filter_channels, kernel_size, padding=kernel_size // 2)
+        self.norm_1 = _LayerNorm(filter_channels)
+        self.conv_2 = nn.Conv1d(filter_channels, filter_channels, kernel_size, padding=kernel_size // 2)
+        self.norm_2 = _LayerNorm(filter_channels)
+        self.proj = nn.Conv1d(filter_channels, 1, 1)
+        if gin_channels != 0:
+            self.cond = nn.Conv1d(gin_channels, in_channels, 1)
+        self._cfg = dict(kind=_lib.DUR_DP, in_channels=in_channels, filter_channels=filter_channels, kernel_size=kernel_size, n_flows=0,
+                         gin_channels=gin_channels)
+        self._engines = _DurEngCache()
+
+    def weight_tensors(self) -> List[torch.Tensor]:
+        out = [self.conv_1.weight, self.conv_1.bias, self.norm_1.gamma, self.norm_1.beta, self.conv_2.weight, self.conv_2.bias,
+               self.norm_2.gamma, self.norm_2.beta, self.proj.weight, self.proj.bias]
+        if self.gin_channels:
+            out += [self.cond.weight, self.cond.bias]
+        return out
+
+    def logw_cl(self, x_cl, lengths, g=None, noise_scale=1.0, noise=None) -> torch.Tensor:
+        """forward on channel-last x [B, T, C] with lengths [B] -> logw [B, T] (noise_scale / noise: unused)."""
+        self._check(x_cl)
+        eng = self._engine(x_cl.device)
+        return eng.logw(x_cl.to(torch.float32).contiguous(), lengths.to(device=x_cl.device, dtype=torch.int32).contiguous(),
+                        self._speaker(g, x_cl.shape[0]))
+
+    def forward(self, x, x_mask, g=None):
+        self._check(x)
+        return self.logw_cl(self._channel_last(x), self._lengths(x_mask), g).unsqueeze(1)
+
+
+def infer(net_g, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1.0, max_len=None, *, noise=None):
+    """SynthesizerTrn.infer (models.py:1288-1323) for a model whose enc_p / dp / flow / dec are this module's drop-ins (emb_g,
+    when present, is the reference's nn.Embedding): -> (o [B, 1, T'], attn [B, 1, T_y, T_x], y_mask [B, 1, T_y],
+    (z, z_p, m_p, logs_p) [B, inter, T_y]).  Channel-last from the text encoder to the generator; one host sync (T_y).
+    ``noise=(e_w, e_z)`` (test hook) replaces the two draws: e_w [B, 2, T_x] of the stochastic duration predictor, e_z
+    [B, inter, >= T_y] of the prior (torch.randn_like(m_p))."""
+    parts = {"enc_p": TextEncoder, "dp": (StochasticDurationPredictor, DurationPredictor), "flow": ResidualCouplingTransformersBlock,
+             "dec": Generator}
+    for name, cls in parts.items():
+        mod = getattr(net_g, name, None)
+        if not isinstance(mod, cls):
+            raise TypeError(f"net_g.{name} is {type(mod).__name__}, not the HIP drop-in: swap it in (INTEGRATION.md) - there is no fallback")
+    enc_p, dp, flow, dec = net_g.enc_p, net_g.dp, net_g.flow, net_g.dec
+    if not x.is_cuda:
+        raise NotImplementedError("vits2.infer runs on a ROCm device only: move the model and the ids there")
+    e_w, e_z = noise if noise is not None else (None, None)
+    g = None if sid is None else net_g.emb_g(sid).unsqueeze(-1)  # [b, h, 1]
+    dev = x.device
+    xs, m_cl, logs_cl = enc_p.forward_cl(x, x_lengths, g=g if enc_p.gin_channels else None)  # (models.py:1154-1157: g reaches the
+    # text encoder's layers only when it was built speaker-conditioned)
+    lengths = x_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    logw = dp.logw_cl(xs, lengths, g, noise_scale_w, e_w)
+    eng = dp._engines.get(dp._cfg, dev)
+    cum, y_len, T_y = eng.lengths(logw, lengths, length_scale)
+    if e_z is None:
+        e_z = torch.randn(x.shape[0], m_cl.shape[2], T_y, device=dev)  # torch.randn_like(m_p)
+    z_p, m_p, logs_p, attn = eng.expand(cum, m_cl, logs_cl, e_z, noise_scale, T_y)
+    y_mask = (torch.arange(T_y, device=dev)[None, :] < y_len[:, None]).unsqueeze(1).to(torch.float32)
+    z = flow.reverse_cl(z_p, y_len, g)
+    o = dec.forward_cl((z * y_mask.transpose(1, 2))[:, :max_len], g).unsqueeze(1)
+    return o, attn.unsqueeze(1), y_mask, (z.transpose(1, 2), z_p.transpose(1, 2), m_p.transpose(1, 2), logs_p.transpose(1, 2))
