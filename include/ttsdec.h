@@ -42,6 +42,7 @@ extern "C" {
 /* (The ttsgen_ family below - the HiFi-GAN generator - was added later without a bump: it adds entry points and a struct of its
  * own and changes none that existed, so a version-2 binding still binds every entry point it knows.) */
 /* (So was the ttsdur_ family at the end - the duration predictors and the length regulator - for the same reason.) */
+/* (And ttsvits_flow_forward and the ttspost_ family - the posterior encoder - for voice conversion.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -452,6 +453,13 @@ size_t ttsvits_flow_workspace_bytes(const ttsvits_handle* h, int B, int T);
  * [B, gin_channels] (the reference's g [B, gin, 1], models.py:506, 511; modules.py:185-199), as above. */
 int ttsvits_flow_reverse(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out,
                          void* workspace, size_t workspace_bytes, void* stream);
+/* The forward direction, ResidualCouplingTransformersBlock.forward(reverse=False) (models.py:803-806) over
+ * ResidualCouplingTransformersLayer.forward (models.py:506-526, mean-only: x1 = m + x1 * exp(0) * x_mask) - the `self.flow(z, y_mask,
+ * g=g_src)` of SynthesizerTrn.voice_conversion, models.py:1334.  Flows run layer_0, Flip, layer_1, Flip, ..., layer_{n-1}, Flip.
+ * Same tensors, workspace (ttsvits_flow_workspace_bytes), precisions and errors as ttsvits_flow_reverse; the logdet of the
+ * training forward is not computed (mean-only: it is 0). */
+int ttsvits_flow_forward(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * VITS2 HiFi-GAN generator (latent z -> waveform): Generator.forward, vits2/models.py:900-974, with ResBlock1.forward
@@ -587,6 +595,54 @@ int ttsdur_lengths(ttsdur_handle* h, const float* logw, const int32_t* lengths, 
  * reference's torch.randn_like(m_p) with eps_T >= T_y frames per channel row.  m, logs [B, T, inter] channel-last. */
 int ttsdur_expand(ttsdur_handle* h, const int32_t* cum, const float* m, const float* logs, const float* eps, int eps_T, float noise_scale,
                   int B, int T, int inter, int T_y, float* z_p, float* m_p, float* logs_p, float* attn, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * VITS2 posterior encoder: PosteriorEncoder.forward, vits2/models.py:858-897 - the `self.enc_q(y, y_lengths, g=g_src)` of
+ * SynthesizerTrn.voice_conversion, models.py:1333.  Eval mode, dilation_rate 1 (the ModelConfig's), g constant over time.
+ *   x_mask = sequence_mask(lengths, T);  x = pre(y) * x_mask (1x1, spec -> hidden);  x = WN(x, x_mask, g) (modules.py:185-210,
+ *   n_layers layers of a kernel_size-tap hidden -> 2 hidden conv, the gate [+ cond_layer(g)], a 1x1 res/skip conv);
+ *   stats = proj(x) * x_mask (1x1, hidden -> 2 inter);  m, logs = split(stats);  z = (m + eps * exp(logs)) * x_mask.
+ * The spectrogram comes in as the reference receives it, channel-first [B, spec, T]; one staging kernel writes the channel-last
+ * GEMM operand (channels zero-padded to a multiple of 8, so any spec width works - 513 for a linear-spectrogram posterior).
+ * Every conv runs on the library's GEMM core (ttspost_set_precision), the WN loop is the flow's (ttsvits_flow_*).  Outputs are
+ * CHANNEL-LAST [B, T, inter]; padded frames are zero.
+ * ------------------------------------------------------------------------------------- */
+typedef struct ttspost_dims {
+  int32_t spec_channels;    /* 80 (mel posterior) or 513 (linear spectrogram, n_fft 1024): channels of y, 1..4096        */
+  int32_t inter_channels;   /* 192: channels of z, m and logs (proj emits 2 inter); a multiple of 4                       */
+  int32_t hidden_channels;  /* 192: WN width; a multiple of 4                                                             */
+  int32_t kernel_size;      /* 5: WN conv taps (odd)                                                                      */
+  int32_t n_layers;         /* 16: WN layers, 1..32                                                                       */
+  int32_t gin_channels;     /* 0, or the speaker-embedding width of WN.cond_layer (a multiple of 4, <= 4096)              */
+} ttspost_dims;
+typedef struct ttspost_handle ttspost_handle;
+
+/* Dimensions outside the ranges above are refused with TTSDEC_ERR_DIMS. */
+int ttspost_create(const ttspost_dims* dims, ttspost_handle** out);
+int ttspost_destroy(ttspost_handle* h);
+const char* ttspost_last_hip_error(const ttspost_handle* h);
+/* TTSDEC_PREC_F32 (default, exact fp32 matrix instruction) or TTSDEC_PREC_SPLIT_F16 (hi + lo fp16 planes, fp32 accumulate), as
+ * ttsvits_set_precision; the elementwise math is fp32 in both. */
+int ttspost_set_precision(ttspost_handle* h, int precision);
+int ttspost_get_precision(const ttspost_handle* h);
+/* Source tensors for ttspost_pack_weights (device fp32, the reference's parameter shapes), in this order:
+ *   pre.weight [hidden, spec, 1], pre.bias [hidden];
+ *   when gin_channels > 0: enc.cond_layer EFFECTIVE weight (g * v / ||v||) [2 hidden n_layers, gin, 1], bias;
+ *   per WN layer j: enc.in_layers.j effective weight [2 hidden, hidden, k], bias, enc.res_skip_layers.j effective weight
+ *       [2 hidden (hidden for the last layer), hidden, 1], bias;
+ *   proj.weight [2 inter, hidden, 1], proj.bias [2 inter].
+ * (4 + 4 n_layers tensors, + 2 with gin_channels > 0: 70 at the ModelConfig dims with a speaker embedding.) */
+int ttspost_num_weight_tensors(const ttspost_handle* h);
+size_t ttspost_packed_bytes(const ttspost_handle* h);
+int ttspost_pack_weights(ttspost_handle* h, const float* const* src, int n_src, void* blob, void* stream);
+int ttspost_bind_weights(ttspost_handle* h, const void* blob);
+/* Scratch of one ttspost_forward call of B utterances of T frames (256-byte aligned). */
+size_t ttspost_workspace_bytes(const ttspost_handle* h, int B, int T);
+/* y [B, spec, T] channel-first fp32 (device), lengths [B] int32 (device), g NULL or [B, gin_channels] (the reference's g [B, gin, 1];
+ * TTSDEC_ERR_INVALID_ARG on a handle with gin_channels == 0), eps [B, inter, eps_T] channel-first with eps_T >= T (the reference's
+ * torch.randn_like(m), read as ttsdur_expand reads its eps).  z, m, logs out [B, T, inter] channel-last.  Enqueues only. */
+int ttspost_forward(ttspost_handle* h, const float* y, const int32_t* lengths, const float* g, const float* eps, int eps_T, int B, int T,
+                    float* z, float* m, float* logs, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

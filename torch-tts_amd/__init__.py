@@ -8,13 +8,14 @@ from .decoder_cell import LSTMZoneoutCell, PreNet, StepwiseMonotonicAttention, T
 from .engine import Engine, EngineDims
 from .postnet import Conv1dFix, MelPostnet, MelPostnet2
 from .tacotron import Encoder2, Tacotron, build_tacotron, lengths_to_mask
-from . import vits2  # noqa: F401  (TextEncoder, ResidualCouplingTransformersBlock, Generator, StochasticDurationPredictor, DurationPredictor, infer)
-from .vits2 import DurationPredictor, Generator, StochasticDurationPredictor
+from . import vits2  # noqa: F401  (TextEncoder, ResidualCouplingTransformersBlock, Generator, StochasticDurationPredictor, DurationPredictor, infer,
+#                             PosteriorEncoder, voice_conversion)
+from .vits2 import DurationPredictor, Generator, PosteriorEncoder, StochasticDurationPredictor
 from . import audio  # noqa: F401  (AudioFrontend.mel_inv / decode, m_rev, synth_audio)
 from . import train_util  # noqa: F401  (load_state_dict: the reference's partial checkpoint loader + blob invalidation)
 
 __all__ = [
     "Decoder", "Taco2ProdDecoderCell", "Taco2DecoderCell", "PreNet", "LSTMZoneoutCell", "StepwiseMonotonicAttention", "MelPostnet", "MelPostnet2",
     "Tacotron", "Encoder2", "build_tacotron", "lengths_to_mask", "Engine", "EngineDims",
-    "Generator", "StochasticDurationPredictor", "DurationPredictor",
+    "Generator", "StochasticDurationPredictor", "DurationPredictor", "PosteriorEncoder",
 ]

@@ -81,6 +81,7 @@ SYMBOLS = (
     "ttsvits_text_encoder",
     "ttsvits_flow_workspace_bytes",
     "ttsvits_flow_reverse",
+    "ttsvits_flow_forward",
 )
 # the HiFi-GAN generator's family (include/ttsdec.h ttsgen_*), kept apart from SYMBOLS: tests/test_host_logic.py matches SYMBOLS against
 # the header's ttsdec_ / ttsenc_ / ttsvits_ declarations
@@ -110,6 +111,20 @@ DUR_SYMBOLS = (
     "ttsdur_dp_forward",
     "ttsdur_lengths",
     "ttsdur_expand",
+)
+# the posterior encoder's family (include/ttsdec.h ttspost_*), kept apart like GEN_SYMBOLS
+POST_SYMBOLS = (
+    "ttspost_create",
+    "ttspost_destroy",
+    "ttspost_last_hip_error",
+    "ttspost_set_precision",
+    "ttspost_get_precision",
+    "ttspost_num_weight_tensors",
+    "ttspost_packed_bytes",
+    "ttspost_pack_weights",
+    "ttspost_bind_weights",
+    "ttspost_workspace_bytes",
+    "ttspost_forward",
 )
 ENC_W_COUNT = 20
 
@@ -165,6 +180,10 @@ DUR_SDP, DUR_DP = 0, 1  # include/ttsdec.h ttsdur_dims.kind
 
 class DurDims(C.Structure):  # include/ttsdec.h ttsdur_dims
     _fields_ = [(n, C.c_int32) for n in ("kind", "in_channels", "filter_channels", "kernel_size", "n_flows", "gin_channels")]
+
+
+class PostDims(C.Structure):  # include/ttsdec.h ttspost_dims
+    _fields_ = [(n, C.c_int32) for n in ("spec_channels", "inter_channels", "hidden_channels", "kernel_size", "n_layers", "gin_channels")]
 
 
 class TtsdecError(RuntimeError):
@@ -316,6 +335,30 @@ def load() -> C.CDLL:
         lib.ttsvits_flow_workspace_bytes.argtypes = [vp, i32, i32]
         lib.ttsvits_flow_reverse.restype = i32
         lib.ttsvits_flow_reverse.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
+        lib.ttsvits_flow_forward.restype = i32
+        lib.ttsvits_flow_forward.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
+        lib.ttspost_create.restype = i32
+        lib.ttspost_create.argtypes = [C.POINTER(PostDims), C.POINTER(vp)]
+        lib.ttspost_destroy.restype = i32
+        lib.ttspost_destroy.argtypes = [vp]
+        lib.ttspost_last_hip_error.restype = C.c_char_p
+        lib.ttspost_last_hip_error.argtypes = [vp]
+        lib.ttspost_set_precision.restype = i32
+        lib.ttspost_set_precision.argtypes = [vp, i32]
+        lib.ttspost_get_precision.restype = i32
+        lib.ttspost_get_precision.argtypes = [vp]
+        lib.ttspost_num_weight_tensors.restype = i32
+        lib.ttspost_num_weight_tensors.argtypes = [vp]
+        lib.ttspost_packed_bytes.restype = sz
+        lib.ttspost_packed_bytes.argtypes = [vp]
+        lib.ttspost_pack_weights.restype = i32
+        lib.ttspost_pack_weights.argtypes = [vp, C.POINTER(vp), i32, vp, vp]
+        lib.ttspost_bind_weights.restype = i32
+        lib.ttspost_bind_weights.argtypes = [vp, vp]
+        lib.ttspost_workspace_bytes.restype = sz
+        lib.ttspost_workspace_bytes.argtypes = [vp, i32, i32]
+        lib.ttspost_forward.restype = i32
+        lib.ttspost_forward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]
         lib.ttsgen_create.restype = i32
         lib.ttsgen_create.argtypes = [C.POINTER(GenDims), C.POINTER(vp)]
         lib.ttsgen_destroy.restype = i32

@@ -1,6 +1,8 @@
 // C ABI of the VITS2 second hot path (BASELINE.json configs[4]):
 //   ttsvits_text_encoder   TextEncoder.forward                      vits2/models.py:369-380
 //   ttsvits_flow_reverse   ResidualCouplingTransformersBlock.forward(reverse=True)   models.py:506-531, 803-810
+//   ttsvits_flow_forward   ResidualCouplingTransformersBlock.forward(reverse=False)  models.py:506-526, 803-806
+//   ttspost_forward        PosteriorEncoder.forward                                  models.py:858-897 (own handle, ttspost_*)
 // built on the decoder path's GEMM core (1x1 convs are row GEMMs, k-tap convs implicit GEMMs over
 // channel-last activations, bias / ReLU / frame mask / residual in the epilogue) plus four small
 // kernels of its own: channel LayerNorm, relative-position multi-head attention, the WN gate and the
@@ -1093,6 +1095,124 @@ __global__ void couple4_kernel(float* xf, const float* mm, const float* mask, ui
   for (int e = 0; e < 4; ++e) v[e] = mul_rn(mul_rn(sub_rn(a[e], b[e]), 1.0f), mk);
   *p = v;
 }
+// The forward direction (models.py:506-526, 803-806): flows run layer_0, Flip, layer_1, Flip, ... - no Flip in front of the first
+// coupling, so its split copies x as it stands (the Flips between couplings are the flip_split kernels above, the last one is
+// folded into the copy-out, flip_copy_kernel).  split: xf = x; x0m = x[:, :half] * mask
+__global__ void split_kernel(const float* x, const float* mask, float* xf, float* x0m, f16* x0m_p, int M, int I) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)M * I) return;
+  const size_t m = i / I, c = i % I;
+  const float v = x[i];
+  xf[i] = v;
+  const int half = I / 2;
+  if ((int)c < half) {
+    const float vm = mul_rn(v, mask[m]);
+    const size_t o = m * half + c;
+    x0m[o] = vm;
+    if (x0m_p) split_f16(vm, x0m_p[o], x0m_p[(size_t)M * half + o]);
+  }
+}
+__global__ void split4_kernel(const float* x, const float* mask, float* xf, float* x0m, f16* x0m_p, uint32_t M, uint32_t I4) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= M * I4) return;
+  const uint32_t m = i / I4, c4 = i - m * I4, half4 = I4 / 2;
+  const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+  reinterpret_cast<f32x4*>(xf)[i] = v;
+  if (c4 < half4) {
+    const float mk = mask[m];
+    f32x4 vm;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) vm[e] = mul_rn(v[e], mk);
+    const size_t o = (size_t)m * half4 + c4;
+    reinterpret_cast<f32x4*>(x0m)[o] = vm;
+    if (x0m_p) split4_store(vm, x0m_p, (size_t)M * half4 * 4, o);
+  }
+}
+// x1 = m + x1 * exp(0) * mask (models.py:522, mean-only: logs = 0): xf[:, half:] updated in place; mm is post(h) * mask
+__global__ void couple_add_kernel(float* xf, const float* mm, const float* mask, int M, int I) {
+  const int half = I / 2;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)M * half) return;
+  const size_t m = i / half, c = i % half;
+  float* p = xf + m * I + half + c;
+  *p = add_rn(mm[i], mul_rn(mul_rn(*p, 1.0f), mask[m]));
+}
+__global__ void couple_add4_kernel(float* xf, const float* mm, const float* mask, uint32_t M, uint32_t I4) {
+  const uint32_t half4 = I4 / 2;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= M * half4) return;
+  const uint32_t m = i / half4, c4 = i - m * half4;
+  f32x4* p = reinterpret_cast<f32x4*>(xf) + (size_t)m * I4 + half4 + c4;
+  const f32x4 a = *p, b = reinterpret_cast<const f32x4*>(mm)[i];
+  const float mk = mask[m];
+  f32x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = add_rn(b[e], mul_rn(mul_rn(a[e], 1.0f), mk));
+  *p = v;
+}
+// the last Flip of the forward direction (modules.py:374-381) as the copy-out: out[m, c] = x[m, I - 1 - c]
+__global__ void flip_copy_kernel(const float* x, float* out, int M, int I) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)M * I) return;
+  const size_t m = i / I, c = i % I;
+  out[i] = x[m * I + (I - 1 - c)];
+}
+__global__ void flip_copy4_kernel(const float* x, float* out, uint32_t M, uint32_t I4) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= M * I4) return;
+  const uint32_t m = i / I4, c4 = i - m * I4;
+  const f32x4 s = reinterpret_cast<const f32x4*>(x)[(size_t)m * I4 + (I4 - 1 - c4)];
+  reinterpret_cast<f32x4*>(out)[i] = f32x4{s[3], s[2], s[1], s[0]};
+}
+
+// PosteriorEncoder staging (models.py:890): the spectrogram y [B, S, T] as the reference takes it -> the channel-last operand of
+// the pre GEMM, xs [B*T, Sp] (Sp = S rounded up to the GEMM core's 8-element granularity; channels S .. Sp-1 are zero), and its
+// split-fp16 planes (hi at xs_p, lo M*Sp halfs later) when xs_p != nullptr.  A 32 x 32 (frame, channel) tile per workgroup
+// through LDS: the reads run along the frames, the writes along the channels.
+constexpr int kTr = 32;
+__global__ __launch_bounds__(256) void post_stage_kernel(const float* y, float* xs, f16* xs_p, int S, int Sp, int T, int M) {
+  __shared__ float tile[kTr][kTr + 1];
+  const int b = blockIdx.z, t0 = blockIdx.x * kTr, c0 = blockIdx.y * kTr;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+  for (int r = ty; r < kTr; r += 8) {  // r: channel, tx: frame
+    const int c = c0 + r, t = t0 + tx;
+    tile[r][tx] = (c < S && t < T) ? y[((size_t)b * S + c) * T + t] : 0.f;
+  }
+  __syncthreads();
+  for (int r = ty; r < kTr; r += 8) {  // r: frame, tx: channel
+    const int t = t0 + r, c = c0 + tx;
+    if (t < T && c < Sp) {
+      const size_t o = ((size_t)b * T + t) * Sp + c;
+      const float v = tile[tx][r];
+      xs[o] = v;
+      if (xs_p) split_f16(v, xs_p[o], xs_p[(size_t)M * Sp + o]);
+    }
+  }
+}
+// PosteriorEncoder.forward:894-896: m, logs = split(stats); z = (m + eps * exp(logs)) * mask, in the reference's order of
+// operations.  stats [B*T, 2I] (already proj(x) * mask); eps [B, I, eps_T] channel-first (torch.randn_like(m)); z, m, logs
+// [B, T, I] channel-last.  Tiles of 32 frames x 32 channels: eps goes through LDS so both its reads and the writes are coalesced.
+__global__ __launch_bounds__(256) void post_sample_kernel(const float* stats, const float* eps, int eps_T, const float* mask, float* z, float* m,
+                                                          float* logs, int I, int T) {
+  __shared__ float tile[kTr][kTr + 1];
+  const int b = blockIdx.z, t0 = blockIdx.x * kTr, c0 = blockIdx.y * kTr;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int r = ty; r < kTr; r += 8) {  // r: channel, tx: frame
+    const int c = c0 + r, t = t0 + tx;
+    tile[r][tx] = (c < I && t < T) ? eps[((size_t)b * I + c) * eps_T + t] : 0.f;
+  }
+  __syncthreads();
+  for (int r = ty; r < kTr; r += 8) {  // r: frame, tx: channel
+    const int t = t0 + r, c = c0 + tx;
+    if (t < T && c < I) {
+      const size_t row = (size_t)b * T + t, o = row * I + c;
+      const float mv = stats[row * 2 * I + c], lv = stats[row * 2 * I + I + c];
+      m[o] = mv;
+      logs[o] = lv;
+      z[o] = mul_rn(add_rn(mv, mul_rn(tile[tx][r], expf(lv))), mask[row]);
+    }
+  }
+}
 __global__ void copy_f_kernel(const float* a, float* b, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) b[i] = a[i];
@@ -1290,6 +1410,46 @@ int pack_stack(const float* const* src, int& k, float* b, const StackBlob& s, co
   return TTSDEC_OK;
 }
 
+// modules.WN.forward (modules.py:185-210), dilation_rate 1, eval mode, shared by the flow's coupling layers and the posterior
+// encoder: ws.hx [M, H] (and its planes ws.hx_p, when the GEMMs run on planes) in - overwritten - and ws.ho [M, H] = WN(hx) * mask
+// (and its planes ws.ho_p) out.  Per layer j: in_layers.j (kernel taps) -> the gate [+ g_l] -> res_skip_layers.j -> the update.
+// g: NULL or [B, gin]: cond_layer(g) (a 1x1 conv of [B, gin, 1]) first, one small exact-fp32 GEMM into ws.cond [B, 2 H layers].
+struct WnLayout {
+  int H, kernel, layers, gin;
+  const size_t *in_w, *in_b, *rs_w, *rs_b;  // per layer: float offsets into the blob
+  size_t cond_w, cond_b;                    // read when g != nullptr
+};
+struct WnWs {
+  float *hx, *ho, *acts, *xin, *rs, *cond;  // [M,H] [M,H] [M,H] [M,2H] [M,2H] [B, 2 H layers]
+  f16 *hx_p, *acts_p, *ho_p;                // planes of hx / acts / ho, written by their producers
+};
+void run_wn(const float* blob, const WnLayout& w, const WnWs& ws, const GemmCtx& fcx, const float* g, const float* mask, int B, int T,
+            hipStream_t st) {
+  const int M = B * T, Fh = w.H;
+  const int ncond = 2 * Fh * w.layers;
+  GemmCtx exact;
+  exact.planes = nullptr; exact.split = false;
+  float *hx = ws.hx, *ho = ws.ho, *acts = ws.acts, *xin = ws.xin, *rs = ws.rs, *cond = ws.cond;
+  f16 *hx_p = ws.hx_p, *acts_p = ws.acts_p, *ho_p = ws.ho_p;
+  if (g != nullptr)  // g = cond_layer(g)  (modules.py:189-190; a 1x1 conv of [B, gin, 1]: one small GEMM per WN)
+    gemm_generic(exact, g, nullptr, w.gin, w.gin, blob + w.cond_w, (size_t)ncond * w.gin, blob + w.cond_b, B, ncond,
+                 cond, nullptr, ncond, 0, nullptr, nullptr, 1, 1, st);
+  for (int j = 0; j < w.layers; ++j) {
+    const float* gl = g != nullptr ? cond + (size_t)j * 2 * Fh : nullptr;  // g_l = g[:, 2 Fh j : 2 Fh (j + 1)]      modules.py:194-196
+    const bool last = j == w.layers - 1;
+    gemm_generic(fcx, hx, hx_p, Fh, Fh, blob + w.in_w[j], (size_t)2 * Fh * w.kernel * Fh, blob + w.in_b[j], M, 2 * Fh, xin, nullptr, 2 * Fh, 0,
+                 nullptr, nullptr, w.kernel, T, st);
+    const bool vec4 = Fh % 4 == 0 && (size_t)M * Fh < ((size_t)1 << 32);
+    if (vec4 && fcx.split) hipLaunchKernelGGL(wn_gate4_kernel<true>, grid1((size_t)M * Fh / 4), dim3(256), 0, st, xin, (Fh & 7) ? acts : (float*)nullptr, acts_p, (uint32_t)M, (uint32_t)Fh / 4, gl, (uint32_t)T, (uint32_t)ncond);
+    else if (vec4) hipLaunchKernelGGL(wn_gate4_kernel<false>, grid1((size_t)M * Fh / 4), dim3(256), 0, st, xin, acts, acts_p, (uint32_t)M, (uint32_t)Fh / 4, gl, (uint32_t)T, (uint32_t)ncond);
+    else hipLaunchKernelGGL(wn_gate_kernel, grid1((size_t)M * Fh), dim3(256), 0, st, xin, acts, acts_p, M, Fh, gl, T, ncond);
+    const int cr = last ? Fh : 2 * Fh;
+    gemm_generic(fcx, acts, acts_p, Fh, Fh, blob + w.rs_w[j], (size_t)cr * Fh, blob + w.rs_b[j], M, cr, rs, nullptr, cr, 0, nullptr, nullptr, 1, T, st);
+    if (vec4) hipLaunchKernelGGL(wn_update4_kernel, grid1((size_t)M * Fh / 4), dim3(256), 0, st, hx, ho, rs, mask, hx_p, ho_p, (uint32_t)M, (uint32_t)Fh / 4, last ? 1 : 0, j == 0 ? 1 : 0);
+    else hipLaunchKernelGGL(wn_update_kernel, grid1((size_t)M * Fh), dim3(256), 0, st, hx, ho, rs, mask, hx_p, ho_p, M, Fh, last ? 1 : 0, j == 0 ? 1 : 0);
+  }
+}
+
 bool dims_ok(const ttsvits_dims& d) {
   const int v[] = {d.inter_channels, d.hidden_channels, d.filter_channels, d.flow_hidden};
   for (int x : v)
@@ -1308,6 +1468,88 @@ bool dims_ok(const ttsvits_dims& d) {
   return true;
 }
 
+}  // namespace
+
+namespace {
+// ResidualCouplingTransformersBlock.forward (models.py:803-810) in either direction.  Reverse: Flip, layer_{n-1}, ..., Flip,
+// layer_0 with x1 = (x1 - m) * mask; forward: layer_0, Flip, ..., layer_{n-1}, Flip with x1 = m + x1 * mask.  The Flip in front
+// of a coupling rides in its split (flip_split), the forward direction's last Flip in the copy-out (flip_copy; no flows: a plain copy).
+int run_flow(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out, void* workspace,
+             size_t workspace_bytes, void* stream, bool forward) {
+  if (!h || !z || !lengths || !out || !workspace || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
+  if (workspace_bytes < ttsvits_flow_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ttsvits_dims& d = h->d;
+  const VitsBlob& L = h->bl;
+  const float* blob = h->blob;
+  const int M = B * T, I = d.inter_channels, half = I / 2, Fh = d.flow_hidden;
+  float* p = static_cast<float*>(workspace);
+  const StackDims sd = tf_dims(d);
+  StackWs sw = carve_stack(p, sd, (size_t)M, h->precision == TTSDEC_PREC_SPLIT_F16);
+  auto take = [&](size_t n) { float* r = p; p += up(n, kAlign); return r; };
+  float* mask = take(M);
+  float* xa = take((size_t)M * I);   // current x (ping)
+  float* xb = take((size_t)M * I);   // flipped x (pong)
+  float* mm = take((size_t)M * half);
+  float* hx = take((size_t)M * Fh);   // WN running x
+  float* ho = take((size_t)M * Fh);   // WN output accumulator
+  float* acts = take((size_t)M * Fh);
+  float* xin = take((size_t)M * 2 * Fh);
+  float* rs = take((size_t)M * 2 * Fh);
+  GemmCtx fcx;
+  fcx.planes = reinterpret_cast<f16*>(take((size_t)M * (Fh > half ? Fh : half)));
+  fcx.split = h->precision == TTSDEC_PREC_SPLIT_F16;
+  f16* hx_p = reinterpret_cast<f16*>(take((size_t)M * Fh));  // planes of hx / acts / ho, written by their producers
+  f16* acts_p = reinterpret_cast<f16*>(take((size_t)M * Fh));
+  f16* ho_p = reinterpret_cast<f16*>(take((size_t)M * Fh));
+  const int ncond = 2 * Fh * d.flow_wn_layers;
+  float* cond = take((size_t)B * ncond);  // WN.cond_layer(g) of the current coupling layer, [B, 2 Fh n_layers]
+  hipLaunchKernelGGL(frame_mask_kernel, grid1(M), dim3(256), 0, st, lengths, T, mask, M);
+  const float* cur = z;
+  WnWs wws;
+  wws.hx = hx; wws.ho = ho; wws.acts = acts; wws.xin = xin; wws.rs = rs; wws.cond = cond;
+  wws.hx_p = hx_p; wws.acts_p = acts_p; wws.ho_p = ho_p;
+  for (int n = 0; n < d.n_flows; ++n) {
+    // models.py:804-805: flows = layer_0, Flip, layer_1, Flip, ...;  807-809: reversed(flows) = Flip, layer_{n-1}, ..., Flip, layer_0
+    const int f = forward ? n : d.n_flows - 1 - n;
+    const FlowBlob& fb = L.flow[f];
+    const bool i4 = I % 8 == 0 && (size_t)M * I < ((size_t)1 << 32) && reinterpret_cast<uintptr_t>(cur) % 16 == 0;  // (cur may be the caller's z)
+    const bool flip = !forward || n > 0;  // (forward: no Flip in front of the first coupling)
+    if (i4 && flip) hipLaunchKernelGGL(flip_split4_kernel, grid1((size_t)M * I / 4), dim3(256), 0, st, cur, mask, xb, sw.xm, sw.xm_p, (uint32_t)M, (uint32_t)I / 4);
+    else if (flip) hipLaunchKernelGGL(flip_split_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, mask, xb, sw.xm, sw.xm_p, M, I);
+    else if (i4) hipLaunchKernelGGL(split4_kernel, grid1((size_t)M * I / 4), dim3(256), 0, st, cur, mask, xb, sw.xm, sw.xm_p, (uint32_t)M, (uint32_t)I / 4);
+    else hipLaunchKernelGGL(split_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, mask, xb, sw.xm, sw.xm_p, M, I);
+    // x0_ = pre_transformer(x0 * mask, mask) + x0                                   models.py:508-509
+    int rc = run_stack(h, fb.tf, sd, sw, mask, B, T, st);
+    if (rc != TTSDEC_OK) return rc;
+    if (i4) hipLaunchKernelGGL(add_x04_kernel, grid1((size_t)M * half / 4), dim3(256), 0, st, sw.xm, sw.xm_p, xb, (uint32_t)M, (uint32_t)I / 4);
+    else hipLaunchKernelGGL(add_x0_kernel, grid1((size_t)M * half), dim3(256), 0, st, sw.xm, sw.xm_p, xb, M, I);
+    // h = pre(x0_) * mask                                                           :510
+    gemm_generic(fcx, sw.xm, sw.xm_p, half, half, blob + fb.pre_w, (size_t)Fh * half, blob + fb.pre_b, M, Fh, hx, hx_p, Fh, 0, mask, nullptr, 1, T, st);
+    // h = WN(h, mask, g)                                                            :511, modules.py:185-210
+    WnLayout wl;
+    wl.H = Fh; wl.kernel = d.flow_kernel; wl.layers = d.flow_wn_layers; wl.gin = d.gin_channels;
+    wl.in_w = fb.in_w; wl.in_b = fb.in_b; wl.rs_w = fb.rs_w; wl.rs_b = fb.rs_b; wl.cond_w = fb.cond_w; wl.cond_b = fb.cond_b;
+    run_wn(blob, wl, wws, fcx, g, mask, B, T, st);
+    // m = post(h) * mask ; reverse: x1 = (x1 - m) * mask, forward: x1 = m + x1 * mask   :517, 522, 529
+    gemm_generic(fcx, ho, ho_p, Fh, Fh, blob + fb.post_w, (size_t)half * Fh, blob + fb.post_b, M, half, mm, nullptr, half, 0, mask, nullptr, 1, T, st);
+    if (i4 && forward) hipLaunchKernelGGL(couple_add4_kernel, grid1((size_t)M * half / 4), dim3(256), 0, st, xb, mm, mask, (uint32_t)M, (uint32_t)I / 4);
+    else if (forward) hipLaunchKernelGGL(couple_add_kernel, grid1((size_t)M * half), dim3(256), 0, st, xb, mm, mask, M, I);
+    else if (i4) hipLaunchKernelGGL(couple4_kernel, grid1((size_t)M * half / 4), dim3(256), 0, st, xb, mm, mask, (uint32_t)M, (uint32_t)I / 4);
+    else hipLaunchKernelGGL(couple_kernel, grid1((size_t)M * half), dim3(256), 0, st, xb, mm, mask, M, I);
+    float* t = xa; xa = xb; xb = t;  // the coupled tensor becomes the next layer's input
+    cur = xa;
+  }
+  const bool o4 = I % 4 == 0 && (size_t)M * I < ((size_t)1 << 32) && reinterpret_cast<uintptr_t>(out) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(cur) % 16 == 0;
+  if (!forward || d.n_flows == 0) hipLaunchKernelGGL(copy_f_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, out, (size_t)M * I);
+  else if (o4) hipLaunchKernelGGL(flip_copy4_kernel, grid1((size_t)M * I / 4), dim3(256), 0, st, cur, out, (uint32_t)M, (uint32_t)I / 4);
+  else hipLaunchKernelGGL(flip_copy_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, out, M, I);
+  return vits_fail(h, forward ? "flow_forward" : "flow_reverse");
+}
 }  // namespace
 
 extern "C" {
@@ -1459,80 +1701,212 @@ size_t ttsvits_flow_workspace_bytes(const ttsvits_handle* h, int B, int T) {
 
 int ttsvits_flow_reverse(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out,
                          void* workspace, size_t workspace_bytes, void* stream) {
-  if (!h || !z || !lengths || !out || !workspace || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
-  if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
-  if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
-  if (workspace_bytes < ttsvits_flow_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  return run_flow(h, z, lengths, g, B, T, out, workspace, workspace_bytes, stream, false);
+}
+
+int ttsvits_flow_forward(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  return run_flow(h, z, lengths, g, B, T, out, workspace, workspace_bytes, stream, true);
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// PosteriorEncoder (models.py:858-897): ttspost_*
+// ===========================================================================
+namespace {
+constexpr int kMaxPostWn = 32;
+struct PostBlob {  // offsets in floats; GEMM weights take 2n floats (fp32 | hi | lo), as in make_layout
+  size_t pre_w, pre_b, cond_w, cond_b;
+  size_t in_w[kMaxPostWn], in_b[kMaxPostWn], rs_w[kMaxPostWn], rs_b[kMaxPostWn];
+  size_t proj_w, proj_b;
+  size_t total;
+};
+}  // namespace
+
+struct ttspost_handle {
+  ttspost_dims d;
+  int spec_pad;  // spec_channels rounded up to 8: K of the pre GEMM (the 16-byte granularity of its split-fp16 operand)
+  PostBlob bl;
+  const float* blob;
+  int device;
+  int precision;
+  std::string hip_err;
+};
+
+namespace {
+PostBlob make_post_layout(const ttspost_dims& d, int spec_pad) {
+  PostBlob L;
+  memset(&L, 0, sizeof(L));
+  size_t off = 0;
+  auto take = [&](size_t n) { const size_t o = off; off = up(off + n, kAlign); return o; };
+  auto take_w = [&](size_t n) { return take(2 * n); };
+  const size_t H = d.hidden_channels, I = d.inter_channels, nl = d.n_layers;
+  L.pre_w = take_w(H * spec_pad); L.pre_b = take(H);  // [H, spec_pad]: columns spec .. spec_pad-1 stay zero
+  if (d.gin_channels > 0) { L.cond_w = take_w(2 * H * nl * d.gin_channels); L.cond_b = take(2 * H * nl); }
+  for (int j = 0; j < d.n_layers; ++j) {
+    const size_t cr = j < d.n_layers - 1 ? 2 * H : H;
+    L.in_w[j] = take_w(2 * H * d.kernel_size * H); L.in_b[j] = take(2 * H);
+    L.rs_w[j] = take_w(cr * H); L.rs_b[j] = take(cr);
+  }
+  L.proj_w = take_w(2 * I * H); L.proj_b = take(2 * I);
+  L.total = off;
+  return L;
+}
+bool post_dims_ok(const ttspost_dims& d) {
+  if (d.spec_channels < 1 || d.spec_channels > 4096) return false;
+  if (d.inter_channels <= 0 || (d.inter_channels & 3) || d.inter_channels > 2048) return false;
+  if (d.hidden_channels <= 0 || (d.hidden_channels & 3) || d.hidden_channels > 1024) return false;
+  if (d.kernel_size < 1 || !(d.kernel_size & 1) || d.kernel_size > 31) return false;
+  if (d.n_layers < 1 || d.n_layers > kMaxPostWn) return false;
+  if (d.gin_channels < 0 || (d.gin_channels & 3) || d.gin_channels > 4096) return false;
+  return true;
+}
+int post_fail(ttspost_handle* h, const char* where) {
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return TTSDEC_OK;
+  if (h) h->hip_err = std::string(where) + ": " + hipGetErrorString(e);
+  return TTSDEC_ERR_HIP;
+}
+}  // namespace
+
+extern "C" {
+
+int ttspost_create(const ttspost_dims* dims, ttspost_handle** out) {
+  if (!dims || !out) return TTSDEC_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (!post_dims_ok(*dims)) return TTSDEC_ERR_DIMS;
+  ttspost_handle* h = new (std::nothrow) ttspost_handle();
+  if (!h) return TTSDEC_ERR_INVALID_ARG;
+  h->d = *dims;
+  h->spec_pad = (int)up((size_t)dims->spec_channels, 8);
+  h->bl = make_post_layout(*dims, h->spec_pad);
+  h->blob = nullptr;
+  h->device = current_device_or_minus1();
+  h->precision = TTSDEC_PREC_F32;
+  *out = h;
+  return TTSDEC_OK;
+}
+int ttspost_destroy(ttspost_handle* h) {
+  delete h;
+  return TTSDEC_OK;
+}
+const char* ttspost_last_hip_error(const ttspost_handle* h) { return h ? h->hip_err.c_str() : ""; }
+int ttspost_set_precision(ttspost_handle* h, int precision) {
+  if (!h || (precision != TTSDEC_PREC_F32 && precision != TTSDEC_PREC_SPLIT_F16)) return TTSDEC_ERR_INVALID_ARG;
+  h->precision = precision;
+  return TTSDEC_OK;
+}
+int ttspost_get_precision(const ttspost_handle* h) { return h ? h->precision : TTSDEC_ERR_INVALID_ARG; }
+int ttspost_num_weight_tensors(const ttspost_handle* h) {
+  return h ? 4 + 4 * h->d.n_layers + (h->d.gin_channels > 0 ? 2 : 0) : TTSDEC_ERR_INVALID_ARG;
+}
+size_t ttspost_packed_bytes(const ttspost_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
+
+int ttspost_pack_weights(ttspost_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
+  if (!h || !src || !blob || n_src != ttspost_num_weight_tensors(h)) return TTSDEC_ERR_INVALID_ARG;
+  for (int i = 0; i < n_src; ++i)
+    if (!src[i]) return TTSDEC_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(blob) & 255) return TTSDEC_ERR_WORKSPACE;
   if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const ttsvits_dims& d = h->d;
-  const VitsBlob& L = h->bl;
+  const ttspost_dims& d = h->d;
+  const PostBlob& L = h->bl;
+  float* b = static_cast<float*>(blob);
+  if (hipMemsetAsync(blob, 0, L.total * sizeof(float), st) != hipSuccess) return post_fail(h, "memset");
+  const size_t H = d.hidden_channels, I = d.inter_channels, S = d.spec_channels, Sp = h->spec_pad;
+  int k = 0;
+  // pre.weight [H, S, 1] -> rows of Sp floats (the padding columns stay zero)
+  if (hipMemcpy2DAsync(b + L.pre_w, Sp * sizeof(float), src[k++], S * sizeof(float), S * sizeof(float), H, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return post_fail(h, "copy pre.weight");
+  launch_copy(src[k++], b + L.pre_b, H, st);
+  pack_planes(b, L.pre_w, H * Sp, st);
+  if (d.gin_channels > 0) {
+    const size_t nc = 2 * H * d.n_layers;
+    launch_copy(src[k++], b + L.cond_w, nc * d.gin_channels, st);
+    launch_copy(src[k++], b + L.cond_b, nc, st);
+    pack_planes(b, L.cond_w, nc * d.gin_channels, st);
+  }
+  for (int j = 0; j < d.n_layers; ++j) {
+    const size_t cr = j < d.n_layers - 1 ? 2 * H : H;
+    launch_conv_transpose(src[k], b + L.in_w[j], (int)(2 * H), (int)H, d.kernel_size, st);
+    launch_copy(src[k + 1], b + L.in_b[j], 2 * H, st);
+    launch_copy(src[k + 2], b + L.rs_w[j], cr * H, st);
+    launch_copy(src[k + 3], b + L.rs_b[j], cr, st);
+    pack_planes(b, L.in_w[j], 2 * H * d.kernel_size * H, st);
+    pack_planes(b, L.rs_w[j], cr * H, st);
+    k += 4;
+  }
+  launch_copy(src[k++], b + L.proj_w, 2 * I * H, st);
+  launch_copy(src[k++], b + L.proj_b, 2 * I, st);
+  pack_planes(b, L.proj_w, 2 * I * H, st);
+  const int rc = post_fail(h, "pack_weights");
+  if (rc == TTSDEC_OK) h->blob = b;
+  return rc;
+}
+
+int ttspost_bind_weights(ttspost_handle* h, const void* blob) {
+  if (!h || !blob || (reinterpret_cast<uintptr_t>(blob) & 255)) return TTSDEC_ERR_INVALID_ARG;
+  h->blob = static_cast<const float*>(blob);
+  return TTSDEC_OK;
+}
+
+size_t ttspost_workspace_bytes(const ttspost_handle* h, int B, int T) {
+  if (!h || B <= 0 || T <= 0) return 0;
+  const size_t M = (size_t)B * T, H = h->d.hidden_channels, I = h->d.inter_channels, Sp = h->spec_pad;
+  const size_t f = up(M, kAlign) + 2 * up(M * Sp, kAlign) + 3 * up(M * H, kAlign) + 2 * up(M * 2 * H, kAlign) +
+                   up(M * (H > Sp ? H : Sp), kAlign) + 3 * up(M * H, kAlign) + up((size_t)B * 2 * H * h->d.n_layers, kAlign) +
+                   up(M * 2 * I, kAlign);
+  return f * sizeof(float);
+}
+
+int ttspost_forward(ttspost_handle* h, const float* y, const int32_t* lengths, const float* g, const float* eps, int eps_T, int B, int T,
+                    float* z, float* m, float* logs, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!h || !y || !lengths || !eps || !z || !m || !logs || !workspace || B <= 0 || T <= 0 || eps_T < T) return TTSDEC_ERR_INVALID_ARG;
+  if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
+  if (workspace_bytes < ttspost_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  if ((size_t)B * T > (size_t)INT32_MAX / 4096) return TTSDEC_ERR_DIMS;  // (row counts and offsets of the GEMM core are 32-bit)
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ttspost_dims& d = h->d;
+  const PostBlob& L = h->bl;
   const float* blob = h->blob;
-  const int M = B * T, I = d.inter_channels, half = I / 2, Fh = d.flow_hidden;
+  const int M = B * T, H = d.hidden_channels, I = d.inter_channels, S = d.spec_channels, Sp = h->spec_pad;
+  const bool split = h->precision == TTSDEC_PREC_SPLIT_F16;
   float* p = static_cast<float*>(workspace);
-  const StackDims sd = tf_dims(d);
-  StackWs sw = carve_stack(p, sd, (size_t)M, h->precision == TTSDEC_PREC_SPLIT_F16);
   auto take = [&](size_t n) { float* r = p; p += up(n, kAlign); return r; };
   float* mask = take(M);
-  float* xa = take((size_t)M * I);   // current x (ping)
-  float* xb = take((size_t)M * I);   // flipped x (pong)
-  float* mm = take((size_t)M * half);
-  float* hx = take((size_t)M * Fh);   // WN running x
-  float* ho = take((size_t)M * Fh);   // WN output accumulator
-  float* acts = take((size_t)M * Fh);
-  float* xin = take((size_t)M * 2 * Fh);
-  float* rs = take((size_t)M * 2 * Fh);
+  float* xs = take((size_t)M * Sp);
+  f16* xs_p = reinterpret_cast<f16*>(take((size_t)M * Sp));
+  WnWs ws;
+  ws.hx = take((size_t)M * H); ws.ho = take((size_t)M * H); ws.acts = take((size_t)M * H);
+  ws.xin = take((size_t)M * 2 * H); ws.rs = take((size_t)M * 2 * H);
   GemmCtx fcx;
-  fcx.planes = reinterpret_cast<f16*>(take((size_t)M * (Fh > half ? Fh : half)));
-  fcx.split = h->precision == TTSDEC_PREC_SPLIT_F16;
-  f16* hx_p = reinterpret_cast<f16*>(take((size_t)M * Fh));  // planes of hx / acts / ho, written by their producers
-  f16* acts_p = reinterpret_cast<f16*>(take((size_t)M * Fh));
-  f16* ho_p = reinterpret_cast<f16*>(take((size_t)M * Fh));
-  const int ncond = 2 * Fh * d.flow_wn_layers;
-  float* cond = take((size_t)B * ncond);  // WN.cond_layer(g) of the current coupling layer, [B, 2 Fh n_layers]
-  GemmCtx exact;
-  exact.planes = nullptr; exact.split = false;
+  fcx.planes = reinterpret_cast<f16*>(take((size_t)M * (H > Sp ? H : Sp)));
+  fcx.split = split;
+  ws.hx_p = reinterpret_cast<f16*>(take((size_t)M * H)); ws.acts_p = reinterpret_cast<f16*>(take((size_t)M * H));
+  ws.ho_p = reinterpret_cast<f16*>(take((size_t)M * H));
+  ws.cond = take((size_t)B * 2 * H * d.n_layers);
+  float* stats = take((size_t)M * 2 * I);
   hipLaunchKernelGGL(frame_mask_kernel, grid1(M), dim3(256), 0, st, lengths, T, mask, M);
-  const float* cur = z;
-  for (int f = d.n_flows - 1; f >= 0; --f) {  // models.py:807-809: reversed(flows) = Flip, layer_f, ...
-    const FlowBlob& fb = L.flow[f];
-    const bool i4 = I % 8 == 0 && (size_t)M * I < ((size_t)1 << 32) && reinterpret_cast<uintptr_t>(cur) % 16 == 0;  // (cur may be the caller's z)
-    if (i4) hipLaunchKernelGGL(flip_split4_kernel, grid1((size_t)M * I / 4), dim3(256), 0, st, cur, mask, xb, sw.xm, sw.xm_p, (uint32_t)M, (uint32_t)I / 4);
-    else hipLaunchKernelGGL(flip_split_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, mask, xb, sw.xm, sw.xm_p, M, I);
-    // x0_ = pre_transformer(x0 * mask, mask) + x0                                   models.py:508-509
-    int rc = run_stack(h, fb.tf, sd, sw, mask, B, T, st);
-    if (rc != TTSDEC_OK) return rc;
-    if (i4) hipLaunchKernelGGL(add_x04_kernel, grid1((size_t)M * half / 4), dim3(256), 0, st, sw.xm, sw.xm_p, xb, (uint32_t)M, (uint32_t)I / 4);
-    else hipLaunchKernelGGL(add_x0_kernel, grid1((size_t)M * half), dim3(256), 0, st, sw.xm, sw.xm_p, xb, M, I);
-    // h = pre(x0_) * mask                                                           :510
-    gemm_generic(fcx, sw.xm, sw.xm_p, half, half, blob + fb.pre_w, (size_t)Fh * half, blob + fb.pre_b, M, Fh, hx, hx_p, Fh, 0, mask, nullptr, 1, T, st);
-    // h = WN(h, mask, g)                                                            :511, modules.py:185-210
-    if (g != nullptr)  // g = cond_layer(g)  (modules.py:189-190; a 1x1 conv of [B, gin, 1]: one small GEMM per coupling layer)
-      gemm_generic(exact, g, nullptr, d.gin_channels, d.gin_channels, blob + fb.cond_w, (size_t)ncond * d.gin_channels, blob + fb.cond_b, B, ncond,
-                   cond, nullptr, ncond, 0, nullptr, nullptr, 1, 1, st);
-    for (int j = 0; j < d.flow_wn_layers; ++j) {
-      const float* gl = g != nullptr ? cond + (size_t)j * 2 * Fh : nullptr;  // g_l = g[:, 2 Fh j : 2 Fh (j + 1)]      modules.py:194-196
-      const bool last = j == d.flow_wn_layers - 1;
-      gemm_generic(fcx, hx, hx_p, Fh, Fh, blob + fb.in_w[j], (size_t)2 * Fh * d.flow_kernel * Fh, blob + fb.in_b[j], M, 2 * Fh, xin, nullptr, 2 * Fh, 0,
-                   nullptr, nullptr, d.flow_kernel, T, st);
-      const bool vec4 = Fh % 4 == 0 && (size_t)M * Fh < ((size_t)1 << 32);
-      if (vec4 && fcx.split) hipLaunchKernelGGL(wn_gate4_kernel<true>, grid1((size_t)M * Fh / 4), dim3(256), 0, st, xin, (Fh & 7) ? acts : (float*)nullptr, acts_p, (uint32_t)M, (uint32_t)Fh / 4, gl, (uint32_t)T, (uint32_t)ncond);
-      else if (vec4) hipLaunchKernelGGL(wn_gate4_kernel<false>, grid1((size_t)M * Fh / 4), dim3(256), 0, st, xin, acts, acts_p, (uint32_t)M, (uint32_t)Fh / 4, gl, (uint32_t)T, (uint32_t)ncond);
-      else hipLaunchKernelGGL(wn_gate_kernel, grid1((size_t)M * Fh), dim3(256), 0, st, xin, acts, acts_p, M, Fh, gl, T, ncond);
-      const int cr = last ? Fh : 2 * Fh;
-      gemm_generic(fcx, acts, acts_p, Fh, Fh, blob + fb.rs_w[j], (size_t)cr * Fh, blob + fb.rs_b[j], M, cr, rs, nullptr, cr, 0, nullptr, nullptr, 1, T, st);
-      if (vec4) hipLaunchKernelGGL(wn_update4_kernel, grid1((size_t)M * Fh / 4), dim3(256), 0, st, hx, ho, rs, mask, hx_p, ho_p, (uint32_t)M, (uint32_t)Fh / 4, last ? 1 : 0, j == 0 ? 1 : 0);
-      else hipLaunchKernelGGL(wn_update_kernel, grid1((size_t)M * Fh), dim3(256), 0, st, hx, ho, rs, mask, hx_p, ho_p, M, Fh, last ? 1 : 0, j == 0 ? 1 : 0);
-    }
-    // m = post(h) * mask ; x1 = (x1 - m) * mask                                     :517, 529
-    gemm_generic(fcx, ho, ho_p, Fh, Fh, blob + fb.post_w, (size_t)half * Fh, blob + fb.post_b, M, half, mm, nullptr, half, 0, mask, nullptr, 1, T, st);
-    if (i4) hipLaunchKernelGGL(couple4_kernel, grid1((size_t)M * half / 4), dim3(256), 0, st, xb, mm, mask, (uint32_t)M, (uint32_t)I / 4);
-    else hipLaunchKernelGGL(couple_kernel, grid1((size_t)M * half), dim3(256), 0, st, xb, mm, mask, M, I);
-    float* t = xa; xa = xb; xb = t;  // the coupled tensor becomes the next layer's input
-    cur = xa;
-  }
-  hipLaunchKernelGGL(copy_f_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, out, (size_t)M * I);
-  return vits_fail(h, "flow_reverse");
+  // x = pre(y) * x_mask                                                             models.py:890
+  const dim3 tgrid((T + kTr - 1) / kTr, (Sp + kTr - 1) / kTr, B);
+  hipLaunchKernelGGL(post_stage_kernel, tgrid, dim3(256), 0, st, y, xs, split ? xs_p : (f16*)nullptr, S, Sp, T, M);
+  gemm_generic(fcx, xs, split ? xs_p : nullptr, Sp, Sp, blob + L.pre_w, (size_t)H * Sp, blob + L.pre_b, M, H, ws.hx, ws.hx_p, H, 0, mask, nullptr, 1,
+               T, st);
+  // x = enc(x, x_mask, g=g)                                                         :891
+  WnLayout wl;
+  wl.H = H; wl.kernel = d.kernel_size; wl.layers = d.n_layers; wl.gin = d.gin_channels;
+  wl.in_w = L.in_w; wl.in_b = L.in_b; wl.rs_w = L.rs_w; wl.rs_b = L.rs_b; wl.cond_w = L.cond_w; wl.cond_b = L.cond_b;
+  run_wn(blob, wl, ws, fcx, g, mask, B, T, st);
+  // stats = proj(x) * x_mask                                                        :892
+  gemm_generic(fcx, ws.ho, ws.ho_p, H, H, blob + L.proj_w, (size_t)2 * I * H, blob + L.proj_b, M, 2 * I, stats, nullptr, 2 * I, 0, mask, nullptr,
+               1, T, st);
+  // m, logs = split(stats); z = (m + eps * exp(logs)) * x_mask                      :893-894
+  const dim3 sgrid((T + kTr - 1) / kTr, (I + kTr - 1) / kTr, B);
+  hipLaunchKernelGGL(post_sample_kernel, sgrid, dim3(256), 0, st, stats, eps, eps_T, mask, z, m, logs, I, T);
+  return post_fail(h, "post_forward");
 }
 
 }  // extern "C"

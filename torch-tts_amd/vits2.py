@@ -11,11 +11,15 @@
 * ``DurationPredictor``                   - vits2/models.py:140-180 (``forward(x, x_mask, g=None) -> logw [B, 1, T]``)
 * ``infer(net_g, x, x_lengths, ...)``     - SynthesizerTrn.infer (models.py:1288-1323) over the four drop-ins, channel-last
                                              from the ids to the waveform
+* ``PosteriorEncoder``                    - vits2/models.py:858-897 (``forward(x, x_lengths, g=None) -> (z, m, logs, x_mask)``;
+                                             ``ttspost_*``)
+* ``voice_conversion(net_g, y, ...)``     - SynthesizerTrn.voice_conversion (models.py:1328-1336) over enc_q, flow (both
+                                             directions) and dec
 
 All hold the reference's parameters (so checkpoints load) and run inference through the HIP library
-(``ttsvits_*`` / ``ttsgen_*`` / ``ttsdur_*`` in include/ttsdec.h).  The library works on channel-last activations; the [B, C, T]
-tensors of the reference API are transposed here.  Training / the forward (non-reverse) direction of
-the flow / speaker conditioning are outside the path and raise."""
+(``ttsvits_*`` / ``ttsgen_*`` / ``ttsdur_*`` / ``ttspost_*`` in include/ttsdec.h).  The library works on channel-last activations;
+the [B, C, T] tensors of the reference API are transposed here.  Training (gradients, logdet) and time-varying speaker
+conditioning are outside the path and raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -227,6 +231,21 @@ class VitsEngine:
         self._err(rc, "ttsvits_flow_reverse")
         return out
 
+    def flow_forward(self, z_cl: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The forward direction (ttsvits_flow_forward) on z_cl [B, T, inter] channel-last; same workspace as flow_reverse."""
+        _require_device(z_cl, "z")
+        B, T, _ = z_cl.shape
+        g = self._speaker(g, B)
+        z_cl = z_cl.to(torch.float32).contiguous()
+        lens = lengths.to(device=self.device, dtype=torch.int32).contiguous()
+        out = torch.empty_like(z_cl)
+        ws = self._workspace("flow", self._lib.ttsvits_flow_workspace_bytes(self._h, B, T))
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsvits_flow_forward(self._h, z_cl.data_ptr(), lens.data_ptr(), g.data_ptr() if g is not None else None, B, T,
+                                                out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
+        self._err(rc, "ttsvits_flow_forward")
+        return out
+
 
 class _EngCache:
     def __init__(self):
@@ -366,13 +385,24 @@ class ResidualCouplingTransformersBlock(PackedWeightsMixin, nn.Module):
 
     def forward(self, x, x_mask, g=None, reverse=False):
         if not reverse:
-            raise NotImplementedError("only the reverse (inference) direction is on the HIP path")
+            # (the reference's forward direction also returns the training logdet; its inference use - the flow step of
+            # voice_conversion - is forward_cl)
+            raise NotImplementedError("forward(reverse=False) is the training direction and is not on the HIP path: call forward_cl(x_cl, "
+                                      "lengths, g) for the forward pass without logdet, or vits2.voice_conversion")
         lengths = x_mask[:, 0, :].sum(dim=1).round().to(torch.int32)  # sequence_mask is a prefix mask
         out = self.reverse_cl(x.transpose(1, 2), lengths, g)
         return out.transpose(1, 2)
 
     def reverse_cl(self, z_cl, lengths, g=None):
         """The reverse pass on channel-last z [B, T, channels] with lengths [B] (``infer`` chains it)."""
+        return self._engine(z_cl).flow_reverse(z_cl, lengths, g)
+
+    def forward_cl(self, x_cl, lengths, g=None):
+        """The forward direction (models.py:803-806: layer_0, Flip, ..., layer_{n-1}, Flip) on channel-last x [B, T, channels] with
+        lengths [B] -> [B, T, channels]; the logdet is not computed (``voice_conversion`` chains it)."""
+        return self._engine(x_cl).flow_forward(x_cl, lengths, g)
+
+    def _engine(self, z_cl) -> VitsEngine:
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError("the HIP flow is inference-only: call under torch.no_grad()")
         eng = self._engines.get(self._dims(), z_cl.device)
@@ -386,7 +416,7 @@ class ResidualCouplingTransformersBlock(PackedWeightsMixin, nn.Module):
             return ts
 
         eng.ensure_packed(tensors, key_tensors=list(self.parameters()))
-        return eng.flow_reverse(z_cl, lengths, g)
+        return eng
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1002,3 +1032,198 @@ def infer(net_g, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_sc
     z = flow.reverse_cl(z_p, y_len, g)
     o = dec.forward_cl((z * y_mask.transpose(1, 2))[:, :max_len], g).unsqueeze(1)
     return o, attn.unsqueeze(1), y_mask, (z.transpose(1, 2), z_p.transpose(1, 2), m_p.transpose(1, 2), logs_p.transpose(1, 2))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Posterior encoder (models.py:858-897) through ttspost_* and voice conversion (SynthesizerTrn.voice_conversion, models.py:1328-1336)
+# ---------------------------------------------------------------------------------------------------------------------------
+class PostEngine:
+    """One ttspost handle on one device."""
+
+    def __init__(self, dims: Dict, device: torch.device):
+        self._lib = _lib.load()
+        self.device = device
+        self.dims = dims
+        d = _lib.PostDims(*[int(dims[n]) for n, _ in _lib.PostDims._fields_])
+        h = C.c_void_p()
+        with torch.cuda.device(device):
+            rc = self._lib.ttspost_create(C.byref(d), C.byref(h))
+        if rc == _lib.ERR_DIMS:
+            raise NotImplementedError(f"these posterior-encoder dimensions are not built in the HIP library (include/ttsdec.h ttspost_dims): {dims}")
+        _lib.check(rc, "ttspost_create")
+        self._h = h
+        self.blob: Optional[torch.Tensor] = None
+        self._fingerprint = None
+        self._ws: Optional[torch.Tensor] = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ttspost_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _err(self, rc, what):
+        if rc != _lib.OK:
+            raise _lib.TtsdecError(rc, what, self._lib.ttspost_last_hip_error(self._h).decode())
+
+    def set_precision(self, mode: str) -> None:
+        self._err(self._lib.ttspost_set_precision(self._h, {"f32": _lib.PREC_F32, "split_f16": _lib.PREC_SPLIT_F16}[mode]), "ttspost_set_precision")
+
+    def ensure_packed(self, tensors, key_tensors) -> None:
+        fp = weights_fingerprint(list(key_tensors))
+        if self.blob is not None and fp == self._fingerprint:
+            return
+        tensors = tensors()
+        n = len(tensors)
+        assert n == int(self._lib.ttspost_num_weight_tensors(self._h)), (n, int(self._lib.ttspost_num_weight_tensors(self._h)))
+        arr = (C.c_void_p * n)()
+        keep = []
+        for i, t in enumerate(tensors):
+            _require_device(t, "posterior encoder weights")
+            tc = t.detach().to(torch.float32).contiguous()
+            keep.append(tc)
+            arr[i] = tc.data_ptr()
+        with torch.cuda.device(self.device):
+            blob = torch.empty(self._lib.ttspost_packed_bytes(self._h), dtype=torch.uint8, device=self.device)
+            rc = self._lib.ttspost_pack_weights(self._h, arr, n, blob.data_ptr(), _stream(self.device))
+            torch.cuda.current_stream(self.device).synchronize()  # `keep` must outlive the packing kernels
+        self._err(rc, "ttspost_pack_weights")
+        self.blob, self._fingerprint = blob, fp
+
+    def workspace(self, B: int, T: int) -> torch.Tensor:
+        nbytes = int(self._lib.ttspost_workspace_bytes(self._h, B, T))
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def forward(self, y: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor], eps: torch.Tensor):
+        """y [B, spec, T] contiguous fp32, lengths [B] int32 (device), g [B, gin] or None, eps [B, inter, >= T] -> z, m, logs
+        [B, T, inter] channel-last."""
+        B, _, T = y.shape
+        I = self.dims["inter_channels"]
+        ws = self.workspace(B, T)
+        z = torch.empty(B, T, I, device=self.device)
+        m = torch.empty_like(z)
+        logs = torch.empty_like(z)
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttspost_forward(self._h, y.data_ptr(), lengths.data_ptr(), g.data_ptr() if g is not None else None, eps.data_ptr(),
+                                           eps.shape[2], B, T, z.data_ptr(), m.data_ptr(), logs.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           _stream(self.device))
+        self._err(rc, "ttspost_forward")
+        return z, m, logs
+
+
+class _PostEngCache(_EngCache):
+    def get(self, dims, device) -> PostEngine:
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        eng = self.by_dev.get(key)
+        if eng is None:
+            eng = PostEngine(dims, torch.device("cuda", key))
+            self.by_dev[key] = eng
+        return eng
+
+    def __deepcopy__(self, memo):
+        return _PostEngCache()
+
+
+class PosteriorEncoder(PackedWeightsMixin, nn.Module):
+    """models.PosteriorEncoder (models.py:858-897): same constructor, parameters and state-dict keys (``enc`` is the weight-normed
+    modules.WN).  ``forward(x [B, spec, T], x_lengths, g=None) -> (z, m, logs, x_mask)`` runs in the HIP library; inference only,
+    dilation_rate 1.  ``noise=`` (keyword, test hook) replaces the reference's draw torch.randn_like(m): [B, out_channels, >= T]."""
+
+    def __init__(self, in_channels, out_channels, hidden_channels, kernel_size, dilation_rate, n_layers, gin_channels=0):
+        super().__init__()
+        self._watch_state_dict_loads()
+        if dilation_rate != 1:
+            raise NotImplementedError("PosteriorEncoder with dilation_rate != 1 is outside the HIP path")
+        self.in_channels, self.out_channels, self.hidden_channels = in_channels, out_channels, hidden_channels
+        self.kernel_size, self.dilation_rate, self.n_layers, self.gin_channels = kernel_size, dilation_rate, n_layers, gin_channels
+        self.pre = nn.Conv1d(in_channels, hidden_channels, 1)
+        self.enc = _WN(hidden_channels, kernel_size, dilation_rate, n_layers, gin_channels=gin_channels)
+        self.proj = nn.Conv1d(hidden_channels, out_channels * 2, 1)
+        self.precision = "f32"  # arithmetic of the GEMMs: "f32" (the reference's own: exact fp32, default) or "split_f16" (two fp16 planes, opt-in)
+        self._cfg = dict(spec_channels=in_channels, inter_channels=out_channels, hidden_channels=hidden_channels, kernel_size=kernel_size,
+                         n_layers=n_layers, gin_channels=gin_channels)
+        self._engines = _PostEngCache()
+
+    def weight_tensors(self) -> List[torch.Tensor]:
+        """ttspost_pack_weights' order (include/ttsdec.h), weight-normed convs as their effective weights."""
+        return [self.pre.weight, self.pre.bias] + self.enc.weight_tensors() + [self.proj.weight, self.proj.bias]
+
+    def _speaker(self, g: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
+        if g is None:
+            return None
+        if not self.gin_channels:
+            raise ValueError("g was given to a posterior encoder built with gin_channels = 0")
+        _require_device(g, "g")
+        if g.dim() == 3:
+            if g.shape[2] != 1:
+                raise NotImplementedError("a time-varying g [B, gin, T] is outside the HIP path (the reference's callers pass [B, gin, 1])")
+            g = g[:, :, 0]
+        if tuple(g.shape) != (B, self.gin_channels):
+            raise ValueError(f"g must be [B, gin_channels(, 1)] = [{B}, {self.gin_channels}(, 1)], got {tuple(g.shape)}")
+        return g.to(torch.float32).contiguous()
+
+    def forward_cl(self, x, x_lengths, g=None, *, noise=None):
+        """forward on the reference's x [B, spec, T] -> z, m, logs channel-last [B, T, out_channels] (``voice_conversion`` chains it)."""
+        if not x.is_cuda or any(not p.is_cuda for p in self.parameters()):
+            raise NotImplementedError("the HIP posterior encoder runs on a ROCm device only: move the module and its input there")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("the HIP posterior encoder is inference-only: call under torch.no_grad()")
+        B, S, T = x.shape
+        if S != self.in_channels:
+            raise ValueError(f"x must be [B, in_channels, T] with in_channels = {self.in_channels}, got {tuple(x.shape)}")
+        dev = x.device
+        if noise is None:
+            noise = torch.randn(B, self.out_channels, T, device=dev)  # torch.randn_like(m), models.py:894
+        if noise.dim() != 3 or noise.shape[0] != B or noise.shape[1] != self.out_channels or noise.shape[2] < T:
+            raise ValueError(f"noise must be [B, out_channels, >= T] = [{B}, {self.out_channels}, >= {T}], got {tuple(noise.shape)}")
+        g = self._speaker(g, B)
+        eng = self._engines.get(self._cfg, dev)
+        eng.set_precision(self.precision)
+        eng.ensure_packed(self.weight_tensors, key_tensors=list(self.parameters()))
+        lengths = x_lengths.to(device=dev, dtype=torch.int32).contiguous()
+        return eng.forward(x.to(torch.float32).contiguous(), lengths, g, noise.to(device=dev, dtype=torch.float32).contiguous())
+
+    def forward(self, x, x_lengths, g=None, *, noise=None):
+        z, m, logs = self.forward_cl(x, x_lengths, g, noise=noise)
+        T = x.shape[2]
+        x_mask = (torch.arange(T, device=x.device)[None, :] < x_lengths.to(x.device)[:, None]).unsqueeze(1).to(z.dtype)
+        return z.transpose(1, 2), m.transpose(1, 2), logs.transpose(1, 2), x_mask
+
+
+def voice_conversion(net_g, y, y_lengths, sid_src, sid_tgt, *, noise=None):
+    """SynthesizerTrn.voice_conversion (models.py:1328-1336) for a model whose enc_q / flow / dec are this module's drop-ins (emb_g is the
+    reference's nn.Embedding): y [B, spec, T] -> (o_hat [B, 1, T * hop], y_mask [B, 1, T], (z, z_p, z_hat) [B, inter, T]).
+    Channel-last from the posterior encoder to the generator, no host sync.  ``noise`` (test hook) replaces the posterior's draw
+    torch.randn_like(m): [B, inter, >= T]."""
+    parts = {"enc_q": PosteriorEncoder, "flow": ResidualCouplingTransformersBlock, "dec": Generator}
+    for name, cls in parts.items():
+        mod = getattr(net_g, name, None)
+        if not isinstance(mod, cls):
+            raise TypeError(f"net_g.{name} is {type(mod).__name__}, not the HIP drop-in: swap it in (INTEGRATION.md) - there is no fallback")
+    # (models.py:1329 asserts on self.n_speakers, which SynthesizerTrn.__init__ does not store: without the attribute, the speaker count
+    # is emb_g's - a model built with n_speakers <= 1 has no emb_g)
+    emb_g = getattr(net_g, "emb_g", None)
+    n_speakers = getattr(net_g, "n_speakers", emb_g.num_embeddings if emb_g is not None else 0)
+    assert n_speakers > 0, "n_speakers have to be larger than 0."
+    enc_q, flow, dec = net_g.enc_q, net_g.flow, net_g.dec
+    if not y.is_cuda:
+        raise NotImplementedError("vits2.voice_conversion runs on a ROCm device only: move the model and the spectrogram there")
+    g_src = net_g.emb_g(sid_src).unsqueeze(-1)
+    g_tgt = net_g.emb_g(sid_tgt).unsqueeze(-1)
+    dev = y.device
+    lengths = y_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    z, _, _ = enc_q.forward_cl(y, lengths, g=g_src, noise=noise)
+    z_p = flow.forward_cl(z, lengths, g_src)
+    z_hat = flow.reverse_cl(z_p, lengths, g_tgt)
+    T = y.shape[2]
+    y_mask = (torch.arange(T, device=dev)[None, :] < lengths[:, None]).unsqueeze(1).to(torch.float32)
+    o_hat = dec.forward_cl(z_hat * y_mask.transpose(1, 2), g_tgt).unsqueeze(1)
+    return o_hat, y_mask, (z.transpose(1, 2), z_p.transpose(1, 2), z_hat.transpose(1, 2))
