@@ -115,7 +115,7 @@ def test_above_2gib_bound_and_group_size(full_gen, monkeypatch):
     for b in (0, 26, 27, 108, 109, B - 1):
         _close(y[b : b + 1], reference_forward(sd, FULL, z[b : b + 1]), f"b={b}")
     eng = gen._engines.get(gen._cfg, torch.device("cuda", 0))
-    eng._ws = None  # (free the large workspace before the forced-group run)
+    eng.release_workspaces()  # (free the large workspace before the forced-group run)
     monkeypatch.setenv("TTSGEN_GROUP_FORCE", "7")
     with torch.no_grad():
         yf = gen(z[100:120].cuda()).cpu()

@@ -383,7 +383,7 @@ def test_c_abi_rejects_bad_arguments(H):
         eng.decode(mem, t_begin=0, n_steps=5, dropout_mode=_lib.DROPOUT_OFF, masks=None, **kw)
     assert ei.value.code == _lib.ERR_INVALID_ARG
     lib = _lib.load()
-    ws = eng.workspace(2, 5)
+    ws = eng.step_workspace(2, 5)
     rc = lib.ttsdec_decode(eng._h, mem.data_ptr(), 2, 5, 0, 4, 4, -2.0, 1, 0, None, 0, None, 0, None, y.data_ptr(), s.data_ptr(),
                            w.data_ptr(), t_out.data_ptr(), ws.data_ptr(), 128, None)  # workspace too small
     assert rc == _lib.ERR_WORKSPACE

@@ -1,6 +1,7 @@
 """CPU tests of the host side: the C-ABI library loads and exports every symbol the
 header declares (no compute without a GPU), host-only queries, the reference-compatible
 RNG replay, the module API surface / state-dict keys, and the loud failure on CPU tensors."""
+import json
 import os
 import re
 
@@ -26,6 +27,20 @@ def test_library_exports_every_declared_symbol():
     assert lib.ttsdec_version() == _lib.ABI_VERSION == 2
     assert lib.ttsdec_strerror(0) == b"ok"
     assert b"multiples of 4" in lib.ttsdec_strerror(_lib.ERR_DIMS)
+
+
+def test_every_family_is_declared_bound_and_exported():
+    """Every tts*_ function include/ttsdec.h declares, in every family, is bound (_lib.FAMILIES) and exported by the library."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ttsdec.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(tts[a-z]+_[a-z_0-9]+)\s*\(", hdr))
+    assert declared == set(_lib.ALL_SYMBOLS) and len(_lib.ALL_SYMBOLS) == len(declared), declared ^ set(_lib.ALL_SYMBOLS)
+    fams = _lib.FAMILY_SYMBOLS
+    assert set(fams) == {"ttsdec", "ttsenc", "ttsvits", "ttsgen", "ttsdur", "ttspost"}
+    for prefix, syms in fams.items():  # disjoint, each under its own prefix
+        assert all(s.startswith(prefix + "_") for s in syms), prefix
+    lib = _lib.load()
+    for sym in declared:
+        assert hasattr(lib, sym), sym
 
 
 def test_host_only_queries_and_layout_sizes():
@@ -55,6 +70,28 @@ def test_host_only_queries_and_layout_sizes():
     e2.set_precision("split_f16")
     assert e2.precision() == "f32"
     e.close()
+
+
+def test_bad_dims_raise_dims_not_built_in_every_family():
+    """ERR_DIMS from any family's create is one exception: a TtsdecError with that code, and a NotImplementedError."""
+    from torch_tts_amd.encoder import EncoderEngine
+
+    V = T.vits2
+    vits = json.load(open(os.path.join(ROOT, "tests", "golden", "vits2_meta.json")))["dims"]
+    gen = dict(initial_channel=192, resblock="1", resblock_kernel_sizes=[3, 7, 11], resblock_dilation_sizes=[[1, 3, 5]] * 3,
+               upsample_rates=[8, 8, 2, 2], upsample_initial_channel=510, upsample_kernel_sizes=[16, 16, 4, 4], gin_channels=0)
+    cases = [
+        (T.Engine, T.EngineDims(d_pre=255)),
+        (EncoderEngine, dict(alphabet_size=10, d_emb=30, d_out=64, conv_kernel=5, bn_eps=1e-5)),
+        (V.VitsEngine, dict(vits, inter_channels=18)),
+        (V.GenEngine, gen),
+        (V.DurEngine, dict(kind=0, in_channels=190, filter_channels=190, kernel_size=3, n_flows=4, gin_channels=0)),
+        (V.PostEngine, dict(spec_channels=80, inter_channels=192, hidden_channels=192, kernel_size=4, n_layers=16, gin_channels=0)),
+    ]
+    for cls, dims in cases:
+        with pytest.raises(NotImplementedError) as ei:
+            cls(dims, None)
+        assert isinstance(ei.value, _lib.TtsdecError) and ei.value.code == _lib.ERR_DIMS, cls
 
 
 def test_bad_dims_and_unbound_handle_are_errors_not_crashes():

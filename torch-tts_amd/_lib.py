@@ -5,6 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+from typing import Dict, NamedTuple, Tuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # (TTSDEC_LIB: another build of the same library, for same-box A/B measurements of two source states - tools/ only)
@@ -34,98 +35,6 @@ def option_ids():
         out[n.decode()] = i
         i += 1
 
-# every symbol include/ttsdec.h declares
-SYMBOLS = (
-    "ttsdec_version",
-    "ttsdec_strerror",
-    "ttsdec_last_hip_error",
-    "ttsdec_create",
-    "ttsdec_destroy",
-    "ttsdec_set_precision",
-    "ttsdec_get_precision",
-    "ttsdec_set_option",
-    "ttsdec_get_option",
-    "ttsdec_option_name",
-    "ttsdec_num_weight_tensors",
-    "ttsdec_packed_bytes",
-    "ttsdec_pack_weights",
-    "ttsdec_bind_weights",
-    "ttsdec_workspace_bytes",
-    "ttsdec_decode",
-    "ttsdec_postnet_workspace_bytes",
-    "ttsdec_postnet",
-    "ttsdec_cell_step",
-    "ttsdec_profile_step",
-    "ttsdec_profile_loop",
-    "ttsenc_create",
-    "ttsenc_destroy",
-    "ttsenc_last_hip_error",
-    "ttsenc_num_weight_tensors",
-    "ttsenc_packed_bytes",
-    "ttsenc_pack_weights",
-    "ttsenc_bind_weights",
-    "ttsenc_workspace_bytes",
-    "ttsenc_forward",
-    "ttsenc_set_precision",
-    "ttsenc_get_precision",
-    "ttsvits_create",
-    "ttsvits_destroy",
-    "ttsvits_set_precision",
-    "ttsvits_get_precision",
-    "ttsvits_last_hip_error",
-    "ttsvits_num_weight_tensors",
-    "ttsvits_packed_bytes",
-    "ttsvits_pack_weights",
-    "ttsvits_bind_weights",
-    "ttsvits_text_encoder_workspace_bytes",
-    "ttsvits_text_encoder",
-    "ttsvits_flow_workspace_bytes",
-    "ttsvits_flow_reverse",
-    "ttsvits_flow_forward",
-)
-# the HiFi-GAN generator's family (include/ttsdec.h ttsgen_*), kept apart from SYMBOLS: tests/test_host_logic.py matches SYMBOLS against
-# the header's ttsdec_ / ttsenc_ / ttsvits_ declarations
-GEN_SYMBOLS = (
-    "ttsgen_create",
-    "ttsgen_destroy",
-    "ttsgen_last_hip_error",
-    "ttsgen_num_weight_tensors",
-    "ttsgen_packed_bytes",
-    "ttsgen_pack_weights",
-    "ttsgen_bind_weights",
-    "ttsgen_workspace_bytes",
-    "ttsgen_forward",
-    "ttsgen_forward_stages",
-)
-# the duration predictors' and length regulator's family (include/ttsdec.h ttsdur_*), kept apart like GEN_SYMBOLS
-DUR_SYMBOLS = (
-    "ttsdur_create",
-    "ttsdur_destroy",
-    "ttsdur_last_hip_error",
-    "ttsdur_num_weight_tensors",
-    "ttsdur_packed_bytes",
-    "ttsdur_pack_weights",
-    "ttsdur_bind_weights",
-    "ttsdur_workspace_bytes",
-    "ttsdur_sdp_reverse",
-    "ttsdur_dp_forward",
-    "ttsdur_lengths",
-    "ttsdur_expand",
-)
-# the posterior encoder's family (include/ttsdec.h ttspost_*), kept apart like GEN_SYMBOLS
-POST_SYMBOLS = (
-    "ttspost_create",
-    "ttspost_destroy",
-    "ttspost_last_hip_error",
-    "ttspost_set_precision",
-    "ttspost_get_precision",
-    "ttspost_num_weight_tensors",
-    "ttspost_packed_bytes",
-    "ttspost_pack_weights",
-    "ttspost_bind_weights",
-    "ttspost_workspace_bytes",
-    "ttspost_forward",
-)
 ENC_W_COUNT = 20
 
 
@@ -186,6 +95,104 @@ class PostDims(C.Structure):  # include/ttsdec.h ttspost_dims
     _fields_ = [(n, C.c_int32) for n in ("spec_channels", "inter_channels", "hidden_channels", "kernel_size", "n_layers", "gin_channels")]
 
 
+# One row per C-ABI family (include/ttsdec.h): its prefix, its dims struct, whether it has <prefix>_set_precision /
+# _get_precision, and (restype, argtypes) of its own entry points.  Every family also has the shared ones of SHARED below.
+vp, i32, u64, sz, f32 = C.c_void_p, C.c_int, C.c_uint64, C.c_size_t, C.c_float
+_ws_bytes = (sz, [vp, i32, i32])  # <prefix>_*workspace_bytes(h, B, T)
+
+
+class Family(NamedTuple):
+    prefix: str
+    dims: type
+    has_precision: bool
+    own: Dict[str, Tuple[type, list]]
+
+
+FAMILIES = (
+    Family("ttsdec", Dims, True, {
+        "version": (i32, []),
+        "strerror": (C.c_char_p, [i32]),
+        "set_option": (i32, [vp, i32, i32]),
+        "get_option": (i32, [vp, i32, C.POINTER(i32)]),
+        "option_name": (C.c_char_p, [i32]),
+        "workspace_bytes": _ws_bytes,
+        "decode": (i32, [
+            vp, vp, i32, i32, i32, i32, i32,  # h, memory, B, L, t_begin, n_steps, t_stride
+            f32, i32, i32, vp, u64,           # stop_threshold, check_stop, dropout_mode, masks, seed
+            vp, i32, vp,                      # teacher, teacher_T, teacher_flags
+            vp, vp, vp, vp,                   # y, s, w, T_out
+            vp, sz, vp,                       # workspace, workspace_bytes, stream
+        ]),
+        "postnet_workspace_bytes": _ws_bytes,
+        "postnet": (i32, [vp, vp, i32, i32, i32, vp, vp, sz, vp]),
+        "cell_step": (i32, [
+            vp, vp, vp, i32, i32,             # h, x, memory, B, L
+            vp, vp, vp, vp, vp, vp,           # w, ctx, h_att, c_att, h_dec, c_dec
+            i32, vp, u64, i32,                # dropout_mode, masks, seed, step
+            vp, vp, sz, vp,                   # x_dec, workspace, workspace_bytes, stream
+        ]),
+        "profile_step": (i32, [
+            vp, vp, i32, i32, i32, i32, vp, u64,  # h, memory, B, L, iters, dropout_mode, masks, seed
+            vp, vp, vp, vp, sz, vp,               # y, s, w, workspace, workspace_bytes, stream
+            C.POINTER(f32), C.POINTER(C.c_char_p), i32, C.POINTER(i32),
+        ]),
+        "profile_loop": (i32, [
+            vp, vp, i32, i32, i32, i32, vp, u64,       # h, memory, B, L, n_steps, dropout_mode, masks, seed
+            vp, vp, vp, vp, vp, sz, vp,                 # y, s, w, T_out, workspace, workspace_bytes, stream
+            C.POINTER(f32), C.POINTER(C.c_char_p), i32, C.POINTER(i32), C.POINTER(f32),
+        ]),
+    }),
+    Family("ttsenc", EncDims, True, {
+        "workspace_bytes": _ws_bytes,
+        "forward": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, sz, vp, vp]),
+    }),
+    Family("ttsvits", VitsDims, True, {
+        "text_encoder_workspace_bytes": _ws_bytes,
+        "text_encoder": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp, vp]),
+        "flow_workspace_bytes": _ws_bytes,
+        "flow_reverse": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
+        "flow_forward": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
+    }),
+    Family("ttsgen", GenDims, False, {
+        "workspace_bytes": _ws_bytes,
+        "forward": (i32, [vp, vp, vp, i32, i32, vp, vp, sz, vp]),
+        "forward_stages": (i32, [vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+    }),
+    Family("ttsdur", DurDims, False, {
+        "workspace_bytes": _ws_bytes,
+        "sdp_reverse": (i32, [vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, sz, vp]),
+        "dp_forward": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
+        "lengths": (i32, [vp, vp, vp, f32, i32, i32, vp, vp, vp, vp]),
+        "expand": (i32, [vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    }),
+    Family("ttspost", PostDims, True, {
+        "workspace_bytes": _ws_bytes,
+        "forward": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    }),
+)
+SHARED = {
+    "destroy": (i32, [vp]),
+    "last_hip_error": (C.c_char_p, [vp]),
+    "num_weight_tensors": (i32, [vp]),
+    "packed_bytes": (sz, [vp]),
+    "pack_weights": (i32, [vp, C.POINTER(vp), i32, vp, vp]),
+    "bind_weights": (i32, [vp, vp]),
+}
+PRECISION = {"set_precision": (i32, [vp, i32]), "get_precision": (i32, [vp])}
+
+
+def _entry_points(fam: Family) -> Dict[str, Tuple[type, list]]:
+    eps = {"create": (i32, [C.POINTER(fam.dims), C.POINTER(vp)]), **SHARED, **(PRECISION if fam.has_precision else {}), **fam.own}
+    return {f"{fam.prefix}_{n}": sig for n, sig in eps.items()}
+
+
+FAMILY_SYMBOLS = {fam.prefix: tuple(_entry_points(fam)) for fam in FAMILIES}
+ALL_SYMBOLS = tuple(s for syms in FAMILY_SYMBOLS.values() for s in syms)  # every symbol include/ttsdec.h declares
+# the same, under the names callers know: the decoder / encoder / VITS2 text-encoder-and-flow families, then one list per later family
+SYMBOLS = FAMILY_SYMBOLS["ttsdec"] + FAMILY_SYMBOLS["ttsenc"] + FAMILY_SYMBOLS["ttsvits"]
+GEN_SYMBOLS, DUR_SYMBOLS, POST_SYMBOLS = (FAMILY_SYMBOLS[p] for p in ("ttsgen", "ttsdur", "ttspost"))
+
+
 class TtsdecError(RuntimeError):
     def __init__(self, code: int, what: str, detail: str = ""):
         self.code = code
@@ -193,6 +200,10 @@ class TtsdecError(RuntimeError):
         if detail:
             msg += f" [{detail}]"
         super().__init__(msg)
+
+
+class DimsNotBuilt(TtsdecError, NotImplementedError):
+    """ERR_DIMS from a family's create: dimensions the library has no kernels for."""
 
 
 _lib = None
@@ -221,195 +232,20 @@ def load() -> C.CDLL:
                 "There is no CPU fallback for this path."
             )
         lib = C.CDLL(LIB_PATH)
-        vp, i32, u64, sz, f32 = C.c_void_p, C.c_int, C.c_uint64, C.c_size_t, C.c_float
         lib.ttsdec_version.restype = i32
         lib.ttsdec_version.argtypes = []
         got = lib.ttsdec_version()
         if got != ABI_VERSION:  # (an older or newer build, e.g. through TTSDEC_LIB: its entry points take other argument lists)
             raise RuntimeError(f"{LIB_PATH} has ABI version {got}, these bindings are for version {ABI_VERSION}: rebuild it "
                                "(python torch-tts_amd/build.py --force)")
-        lib.ttsdec_strerror.restype = C.c_char_p
-        lib.ttsdec_strerror.argtypes = [i32]
-        lib.ttsdec_last_hip_error.restype = C.c_char_p
-        lib.ttsdec_last_hip_error.argtypes = [vp]
-        lib.ttsdec_create.restype = i32
-        lib.ttsdec_create.argtypes = [C.POINTER(Dims), C.POINTER(vp)]
-        lib.ttsdec_destroy.restype = i32
-        lib.ttsdec_destroy.argtypes = [vp]
-        lib.ttsdec_set_precision.restype = i32
-        lib.ttsdec_set_precision.argtypes = [vp, i32]
-        lib.ttsdec_get_precision.restype = i32
-        lib.ttsdec_get_precision.argtypes = [vp]
-        lib.ttsdec_set_option.restype = i32
-        lib.ttsdec_set_option.argtypes = [vp, i32, i32]
-        lib.ttsdec_get_option.restype = i32
-        lib.ttsdec_get_option.argtypes = [vp, i32, C.POINTER(i32)]
-        lib.ttsdec_option_name.restype = C.c_char_p
-        lib.ttsdec_option_name.argtypes = [i32]
-        lib.ttsdec_num_weight_tensors.restype = i32
-        lib.ttsdec_num_weight_tensors.argtypes = [vp]
-        lib.ttsdec_packed_bytes.restype = sz
-        lib.ttsdec_packed_bytes.argtypes = [vp]
-        lib.ttsdec_pack_weights.restype = i32
-        lib.ttsdec_pack_weights.argtypes = [vp, C.POINTER(vp), i32, vp, vp]
-        lib.ttsdec_bind_weights.restype = i32
-        lib.ttsdec_bind_weights.argtypes = [vp, vp]
-        lib.ttsdec_workspace_bytes.restype = sz
-        lib.ttsdec_workspace_bytes.argtypes = [vp, i32, i32]
-        lib.ttsdec_decode.restype = i32
-        lib.ttsdec_decode.argtypes = [
-            vp, vp, i32, i32, i32, i32, i32,  # h, memory, B, L, t_begin, n_steps, t_stride
-            f32, i32, i32, vp, u64,           # stop_threshold, check_stop, dropout_mode, masks, seed
-            vp, i32, vp,                      # teacher, teacher_T, teacher_flags
-            vp, vp, vp, vp,                   # y, s, w, T_out
-            vp, sz, vp,                       # workspace, workspace_bytes, stream
-        ]
-        lib.ttsdec_postnet_workspace_bytes.restype = sz
-        lib.ttsdec_postnet_workspace_bytes.argtypes = [vp, i32, i32]
-        lib.ttsdec_postnet.restype = i32
-        lib.ttsdec_postnet.argtypes = [vp, vp, i32, i32, i32, vp, vp, sz, vp]
-        lib.ttsdec_cell_step.restype = i32
-        lib.ttsdec_cell_step.argtypes = [
-            vp, vp, vp, i32, i32,             # h, x, memory, B, L
-            vp, vp, vp, vp, vp, vp,           # w, ctx, h_att, c_att, h_dec, c_dec
-            i32, vp, u64, i32,                # dropout_mode, masks, seed, step
-            vp, vp, sz, vp,                   # x_dec, workspace, workspace_bytes, stream
-        ]
-        lib.ttsdec_profile_step.restype = i32
-        lib.ttsdec_profile_step.argtypes = [
-            vp, vp, i32, i32, i32, i32, vp, u64,  # h, memory, B, L, iters, dropout_mode, masks, seed
-            vp, vp, vp, vp, sz, vp,               # y, s, w, workspace, workspace_bytes, stream
-            C.POINTER(f32), C.POINTER(C.c_char_p), i32, C.POINTER(i32),
-        ]
-        lib.ttsdec_profile_loop.restype = i32
-        lib.ttsdec_profile_loop.argtypes = [
-            vp, vp, i32, i32, i32, i32, vp, u64,       # h, memory, B, L, n_steps, dropout_mode, masks, seed
-            vp, vp, vp, vp, vp, sz, vp,                 # y, s, w, T_out, workspace, workspace_bytes, stream
-            C.POINTER(f32), C.POINTER(C.c_char_p), i32, C.POINTER(i32), C.POINTER(f32),
-        ]
-        lib.ttsenc_create.restype = i32
-        lib.ttsenc_create.argtypes = [C.POINTER(EncDims), C.POINTER(vp)]
-        lib.ttsenc_destroy.restype = i32
-        lib.ttsenc_destroy.argtypes = [vp]
-        lib.ttsenc_last_hip_error.restype = C.c_char_p
-        lib.ttsenc_last_hip_error.argtypes = [vp]
-        lib.ttsenc_num_weight_tensors.restype = i32
-        lib.ttsenc_num_weight_tensors.argtypes = [vp]
-        lib.ttsenc_packed_bytes.restype = sz
-        lib.ttsenc_packed_bytes.argtypes = [vp]
-        lib.ttsenc_pack_weights.restype = i32
-        lib.ttsenc_pack_weights.argtypes = [vp, C.POINTER(vp), i32, vp, vp]
-        lib.ttsenc_bind_weights.restype = i32
-        lib.ttsenc_bind_weights.argtypes = [vp, vp]
-        lib.ttsenc_workspace_bytes.restype = sz
-        lib.ttsenc_workspace_bytes.argtypes = [vp, i32, i32]
-        lib.ttsenc_forward.restype = i32
-        lib.ttsenc_forward.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, sz, vp, vp]
-        lib.ttsvits_create.restype = i32
-        lib.ttsvits_create.argtypes = [C.POINTER(VitsDims), C.POINTER(vp)]
-        lib.ttsvits_destroy.restype = i32
-        lib.ttsvits_destroy.argtypes = [vp]
-        lib.ttsenc_set_precision.restype = i32
-        lib.ttsenc_set_precision.argtypes = [vp, i32]
-        lib.ttsenc_get_precision.restype = i32
-        lib.ttsenc_get_precision.argtypes = [vp]
-        lib.ttsvits_set_precision.restype = i32
-        lib.ttsvits_set_precision.argtypes = [vp, i32]
-        lib.ttsvits_get_precision.restype = i32
-        lib.ttsvits_get_precision.argtypes = [vp]
-        lib.ttsvits_last_hip_error.restype = C.c_char_p
-        lib.ttsvits_last_hip_error.argtypes = [vp]
-        lib.ttsvits_num_weight_tensors.restype = i32
-        lib.ttsvits_num_weight_tensors.argtypes = [vp]
-        lib.ttsvits_packed_bytes.restype = sz
-        lib.ttsvits_packed_bytes.argtypes = [vp]
-        lib.ttsvits_pack_weights.restype = i32
-        lib.ttsvits_pack_weights.argtypes = [vp, C.POINTER(vp), i32, vp, vp]
-        lib.ttsvits_bind_weights.restype = i32
-        lib.ttsvits_bind_weights.argtypes = [vp, vp]
-        lib.ttsvits_text_encoder_workspace_bytes.restype = sz
-        lib.ttsvits_text_encoder_workspace_bytes.argtypes = [vp, i32, i32]
-        lib.ttsvits_text_encoder.restype = i32
-        lib.ttsvits_text_encoder.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp, vp]
-        lib.ttsvits_flow_workspace_bytes.restype = sz
-        lib.ttsvits_flow_workspace_bytes.argtypes = [vp, i32, i32]
-        lib.ttsvits_flow_reverse.restype = i32
-        lib.ttsvits_flow_reverse.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
-        lib.ttsvits_flow_forward.restype = i32
-        lib.ttsvits_flow_forward.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
-        lib.ttspost_create.restype = i32
-        lib.ttspost_create.argtypes = [C.POINTER(PostDims), C.POINTER(vp)]
-        lib.ttspost_destroy.restype = i32
-        lib.ttspost_destroy.argtypes = [vp]
-        lib.ttspost_last_hip_error.restype = C.c_char_p
-        lib.ttspost_last_hip_error.argtypes = [vp]
-        lib.ttspost_set_precision.restype = i32
-        lib.ttspost_set_precision.argtypes = [vp, i32]
-        lib.ttspost_get_precision.restype = i32
-        lib.ttspost_get_precision.argtypes = [vp]
-        lib.ttspost_num_weight_tensors.restype = i32
-        lib.ttspost_num_weight_tensors.argtypes = [vp]
-        lib.ttspost_packed_bytes.restype = sz
-        lib.ttspost_packed_bytes.argtypes = [vp]
-        lib.ttspost_pack_weights.restype = i32
-        lib.ttspost_pack_weights.argtypes = [vp, C.POINTER(vp), i32, vp, vp]
-        lib.ttspost_bind_weights.restype = i32
-        lib.ttspost_bind_weights.argtypes = [vp, vp]
-        lib.ttspost_workspace_bytes.restype = sz
-        lib.ttspost_workspace_bytes.argtypes = [vp, i32, i32]
-        lib.ttspost_forward.restype = i32
-        lib.ttspost_forward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]
-        lib.ttsgen_create.restype = i32
-        lib.ttsgen_create.argtypes = [C.POINTER(GenDims), C.POINTER(vp)]
-        lib.ttsgen_destroy.restype = i32
-        lib.ttsgen_destroy.argtypes = [vp]
-        lib.ttsgen_last_hip_error.restype = C.c_char_p
-        lib.ttsgen_last_hip_error.argtypes = [vp]
-        lib.ttsgen_num_weight_tensors.restype = i32
-        lib.ttsgen_num_weight_tensors.argtypes = [vp]
-        lib.ttsgen_packed_bytes.restype = sz
-        lib.ttsgen_packed_bytes.argtypes = [vp]
-        lib.ttsgen_pack_weights.restype = i32
-        lib.ttsgen_pack_weights.argtypes = [vp, C.POINTER(vp), i32, vp, vp]
-        lib.ttsgen_bind_weights.restype = i32
-        lib.ttsgen_bind_weights.argtypes = [vp, vp]
-        lib.ttsgen_workspace_bytes.restype = sz
-        lib.ttsgen_workspace_bytes.argtypes = [vp, i32, i32]
-        lib.ttsgen_forward.restype = i32
-        lib.ttsgen_forward.argtypes = [vp, vp, vp, i32, i32, vp, vp, sz, vp]
-        lib.ttsgen_forward_stages.restype = i32
-        lib.ttsgen_forward_stages.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, vp]
-        lib.ttsdur_create.restype = i32
-        lib.ttsdur_create.argtypes = [C.POINTER(DurDims), C.POINTER(vp)]
-        lib.ttsdur_destroy.restype = i32
-        lib.ttsdur_destroy.argtypes = [vp]
-        lib.ttsdur_last_hip_error.restype = C.c_char_p
-        lib.ttsdur_last_hip_error.argtypes = [vp]
-        lib.ttsdur_num_weight_tensors.restype = i32
-        lib.ttsdur_num_weight_tensors.argtypes = [vp]
-        lib.ttsdur_packed_bytes.restype = sz
-        lib.ttsdur_packed_bytes.argtypes = [vp]
-        lib.ttsdur_pack_weights.restype = i32
-        lib.ttsdur_pack_weights.argtypes = [vp, C.POINTER(vp), i32, vp, vp]
-        lib.ttsdur_bind_weights.restype = i32
-        lib.ttsdur_bind_weights.argtypes = [vp, vp]
-        lib.ttsdur_workspace_bytes.restype = sz
-        lib.ttsdur_workspace_bytes.argtypes = [vp, i32, i32]
-        lib.ttsdur_sdp_reverse.restype = i32
-        lib.ttsdur_sdp_reverse.argtypes = [vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, sz, vp]
-        lib.ttsdur_dp_forward.restype = i32
-        lib.ttsdur_dp_forward.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
-        lib.ttsdur_lengths.restype = i32
-        lib.ttsdur_lengths.argtypes = [vp, vp, vp, f32, i32, i32, vp, vp, vp, vp]
-        lib.ttsdur_expand.restype = i32
-        lib.ttsdur_expand.argtypes = [vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+        for fam in FAMILIES:
+            for name, (restype, argtypes) in _entry_points(fam).items():
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
         return _lib
 
 
-def check(code: int, what: str, handle=None) -> None:
+def check(code: int, what: str) -> None:
     if code != OK:
-        detail = ""
-        if handle is not None and code == ERR_HIP:
-            detail = load().ttsdec_last_hip_error(handle).decode()
-        raise TtsdecError(code, what, detail)
+        raise TtsdecError(code, what)

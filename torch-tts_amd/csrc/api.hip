@@ -23,6 +23,43 @@ bool device_is_current(int device) {
   int cur = -1;
   return hipGetDevice(&cur) == hipSuccess && cur == device;
 }
+
+int hip_fail(HandleBase* h, hipError_t e, const char* where) {
+  if (h) h->hip_err = std::string(where) + ": " + hipGetErrorString(e);
+  return TTSDEC_ERR_HIP;
+}
+int record_hip_error(HandleBase* h, const char* where) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? TTSDEC_OK : hip_fail(h, e, where);
+}
+
+int pack_begin(HandleBase* h, const float* const* src, int n_src, int n_expected, bool null_ok, void* blob, size_t blob_bytes,
+               hipStream_t st) {
+  if (!h || !src || !blob || n_src != n_expected) return TTSDEC_ERR_INVALID_ARG;
+  for (int i = 0; i < n_src && !null_ok; ++i)
+    if (!src[i]) return TTSDEC_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(blob) & 255) return TTSDEC_ERR_WORKSPACE;
+  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  const hipError_t e = hipMemsetAsync(blob, 0, blob_bytes, st);
+  return e == hipSuccess ? TTSDEC_OK : hip_fail(h, e, "memset");
+}
+int pack_end(HandleBase* h, const float* blob) {
+  const int rc = record_hip_error(h, "pack_weights");
+  if (rc == TTSDEC_OK) h->blob = blob;
+  return rc;
+}
+int bind_blob(HandleBase* h, const void* blob) {
+  if (!h || !blob || (reinterpret_cast<uintptr_t>(blob) & 255)) return TTSDEC_ERR_INVALID_ARG;
+  h->blob = static_cast<const float*>(blob);
+  return TTSDEC_OK;
+}
+int set_precision(HandleBase* h, int precision) {
+  if (!h || (precision != TTSDEC_PREC_F32 && precision != TTSDEC_PREC_SPLIT_F16)) return TTSDEC_ERR_INVALID_ARG;
+  h->precision = precision;
+  return TTSDEC_OK;
+}
+int get_precision(const HandleBase* h) { return h ? h->precision : TTSDEC_ERR_INVALID_ARG; }
+const char* last_hip_error(const HandleBase* h) { return h ? h->hip_err.c_str() : ""; }
 }  // namespace ttsdec
 
 namespace {
@@ -72,13 +109,9 @@ constexpr int kGraphSlots = 30;  // decode steps per captured graph (even: buffe
 constexpr int kQuerySplit = 4;  // (upper bound: 2 slices for K = 1024, 4 for the Taco2 cell's K = 2048)
 constexpr int kProjSplit = 4;
 
-struct ttsdec_handle {
+struct ttsdec_handle : HandleBase {  // (device -1: no HIP device was available at create; host-only queries still work)
   ttsdec_dims d;
-  int precision;  // TTSDEC_PREC_*
-  int device;  // -1: no HIP device was available at create (host-only queries still work)
   BlobLayout bl;
-  const float* blob;
-  std::string hip_err;
   bool use_graph;   // replay a captured hipGraph instead of launching every kernel (option "graph")
   // Two-role launches (fused_kernels.hip) where they apply: 1 = frame || lstm_att; 2 = also attention || lstm_dec;
   // 0 = off; -1 (default) = by batch size: level 2 up to 320 utterances, level 1 above.  Measured us per step for levels
@@ -297,11 +330,6 @@ int check_dims(const ttsdec_dims& d) {
   return TTSDEC_OK;
 }
 
-int hip_fail(ttsdec_handle* h, hipError_t e, const char* where) {
-  if (h) h->hip_err = std::string(where) + ": " + hipGetErrorString(e);
-  return TTSDEC_ERR_HIP;
-}
-
 #define HIP_TRY(h, expr)                                  \
   do {                                                    \
     hipError_t _e = (expr);                               \
@@ -309,12 +337,6 @@ int hip_fail(ttsdec_handle* h, hipError_t e, const char* where) {
   } while (0)
 
 int check_device(ttsdec_handle* h) { return device_is_current(h->device) ? TTSDEC_OK : TTSDEC_ERR_DEVICE; }
-
-int check_launch(ttsdec_handle* h, const char* where) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(h, e, where);
-  return TTSDEC_OK;
-}
 
 struct StepBufs {
   Ctrl* ctrl;
@@ -948,7 +970,7 @@ const char* ttsdec_strerror(int code) {
   }
 }
 
-const char* ttsdec_last_hip_error(const ttsdec_handle* h) { return h ? h->hip_err.c_str() : ""; }
+const char* ttsdec_last_hip_error(const ttsdec_handle* h) { return last_hip_error(h); }
 
 int ttsdec_create(const ttsdec_dims* dims, ttsdec_handle** out) {
   if (!dims || !out) return TTSDEC_ERR_INVALID_ARG;
@@ -958,9 +980,7 @@ int ttsdec_create(const ttsdec_dims* dims, ttsdec_handle** out) {
   ttsdec_handle* h = new (std::nothrow) ttsdec_handle();
   if (!h) return TTSDEC_ERR_INVALID_ARG;
   h->d = *dims;
-  h->precision = TTSDEC_PREC_F32;
   h->bl = make_blob_layout(*dims);
-  h->blob = nullptr;
   h->streams_ready = false;
   h->gexec = nullptr;
   h->graph = nullptr;
@@ -996,11 +1016,7 @@ int ttsdec_num_weight_tensors(const ttsdec_handle* h) {
   return TTSDEC_W_DECODER_COUNT + TTSDEC_W_POSTNET_PER_LAYER * h->d.postnet_layers + 1;
 }
 
-int ttsdec_set_precision(ttsdec_handle* h, int precision) {
-  if (!h || (precision != TTSDEC_PREC_F32 && precision != TTSDEC_PREC_SPLIT_F16)) return TTSDEC_ERR_INVALID_ARG;
-  h->precision = precision;
-  return TTSDEC_OK;
-}
+int ttsdec_set_precision(ttsdec_handle* h, int precision) { return set_precision(h, precision); }
 
 int ttsdec_get_precision(const ttsdec_handle* h) {
   if (!h) return TTSDEC_ERR_INVALID_ARG;
@@ -1025,20 +1041,16 @@ const char* ttsdec_option_name(int option) { return (option >= 0 && option < TTS
 size_t ttsdec_packed_bytes(const ttsdec_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
 
 int ttsdec_pack_weights(ttsdec_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
-  if (!h || !src || !blob) return TTSDEC_ERR_INVALID_ARG;
-  if (n_src != ttsdec_num_weight_tensors(h)) return TTSDEC_ERR_INVALID_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   // a NULL entry leaves that tensor's region zero (a module that owns only part of the
   // parameters - a bare decoder cell, a postnet - packs what it has)
-  if (reinterpret_cast<uintptr_t>(blob) & 255) return TTSDEC_ERR_WORKSPACE;
-  int rc = check_device(h);
+  int rc = pack_begin(h, src, n_src, ttsdec_num_weight_tensors(h), true, blob, ttsdec_packed_bytes(h), st);
   if (rc != TTSDEC_OK) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   const ttsdec_dims& d = h->d;
   const BlobLayout& L = h->bl;
   float* b = static_cast<float*>(blob);
   const size_t Ha = d.h_att, Hd = d.h_dec, D = d.d_ctx, P = d.d_pre, Mel = d.d_mel, R = d.r, Ph = pre_hidden(d);
   const size_t Dp = proj_ld(d);
-  HIP_TRY(h, hipMemsetAsync(blob, 0, L.total * sizeof(float), st));
   launch_copy(src[TTSDEC_W_PRE0_W], b + L.pre0_w, Ph * Mel, st);
   launch_copy(src[TTSDEC_W_PRE0_B], b + L.pre0_b, Ph, st);
   launch_copy(src[TTSDEC_W_PRE1_W], b + L.pre1_w, P * Ph, st);
@@ -1147,9 +1159,8 @@ int ttsdec_pack_weights(ttsdec_handle* h, const float* const* src, int n_src, vo
       if (d.postnet_layers > 0) launch_absmax(b + L.fc_w, Mel * (size_t)d.postnet_hidden, wm + 1, st);
     }
   }
-  rc = check_launch(h, "pack_weights");
+  rc = pack_end(h, b);
   if (rc != TTSDEC_OK) return rc;
-  h->blob = b;
   return read_wmax(h, st);
 }
 
@@ -1251,7 +1262,7 @@ static int decode_impl(ttsdec_handle* h, const float* memory, int B, int L, int 
     HIP_TRY(h, hipMemcpy(&buf[0], ca.stamps, buf.size(), hipMemcpyDeviceToHost));
     if (FILE* f = fopen(stamp_file, "wb")) { fwrite(buf.data(), 1, buf.size(), f); fclose(f); }
   }
-  return check_launch(h, "decode");
+  return record_hip_error(h, "decode");
 }
 
 int ttsdec_decode(ttsdec_handle* h, const float* memory, int B, int L, int t_begin, int n_steps, int t_stride,
@@ -1399,7 +1410,7 @@ int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision
       launch_gemm(g, A_CONV, EPI_RESIDUAL, st);
       xcur = xnew;
     }
-    return check_launch(h, "postnet2");
+    return record_hip_error(h, "postnet2");
   }
 
   // current layer input as (plane 0, plane 1)
@@ -1468,7 +1479,7 @@ int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision
   g.ldw = cin; g.K = cin; g.M = (int)M; g.N = d.d_mel;
   g.resid = y; g.out = y_post; g.ldo = d.d_mel;
   launch_gemm(g, A_PLAIN, EPI_RESIDUAL, st);
-  return check_launch(h, "postnet");
+  return record_hip_error(h, "postnet");
 }
 
 int ttsdec_cell_step(ttsdec_handle* h, const float* x, const float* memory, int B, int L, float* w, float* ctx,
@@ -1559,7 +1570,7 @@ int ttsdec_cell_step(ttsdec_handle* h, const float* x, const float* memory, int 
     HIP_TRY(h, hipMemcpy2DAsync(x_dec + d.h_dec, ld, sb.ctx, (size_t)d.d_ctx * sizeof(float), (size_t)d.d_ctx * sizeof(float), b,
                                 hipMemcpyDeviceToDevice, st));
   }
-  return check_launch(h, "cell_step");
+  return record_hip_error(h, "cell_step");
 }
 
 int ttsdec_profile_step(ttsdec_handle* h, const float* memory, int B, int L, int iters, int dropout_mode,
@@ -1615,7 +1626,7 @@ int ttsdec_profile_step(ttsdec_handle* h, const float* memory, int B, int L, int
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
-  return check_launch(h, "profile_step");
+  return record_hip_error(h, "profile_step");
 }
 
 }  // extern "C"

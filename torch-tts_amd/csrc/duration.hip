@@ -55,12 +55,9 @@ struct DurBlob {
 };
 }  // namespace
 
-struct ttsdur_handle {
+struct ttsdur_handle : HandleBase {
   ttsdur_dims d;
   DurBlob bl;
-  const float* blob;
-  int device;
-  std::string hip_err;
 };
 
 namespace {
@@ -139,13 +136,6 @@ size_t ws_floats(const ttsdur_dims& d, int B, int T) {
   const size_t cond = up((size_t)B * C, kAlign);
   if (d.kind == 0) return 4 * up(M * C, kAlign) + up(2 * M, kAlign) + cond;
   return up(M * d.filter_channels, kAlign) + cond;
-}
-
-int dur_fail(ttsdur_handle* h, const char* where) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return TTSDEC_OK;
-  if (h) h->hip_err = std::string(where) + ": " + hipGetErrorString(e);
-  return TTSDEC_ERR_HIP;
 }
 
 // ===========================================================================
@@ -600,7 +590,6 @@ int ttsdur_create(const ttsdur_dims* dims, ttsdur_handle** out) {
   if (!h) return TTSDEC_ERR_INVALID_ARG;
   h->d = *dims;
   h->bl = make_layout(*dims);
-  h->blob = nullptr;
   h->device = current_device_or_minus1();
   *out = h;
   return TTSDEC_OK;
@@ -609,21 +598,17 @@ int ttsdur_destroy(ttsdur_handle* h) {
   delete h;
   return TTSDEC_OK;
 }
-const char* ttsdur_last_hip_error(const ttsdur_handle* h) { return h ? h->hip_err.c_str() : ""; }
+const char* ttsdur_last_hip_error(const ttsdur_handle* h) { return last_hip_error(h); }
 int ttsdur_num_weight_tensors(const ttsdur_handle* h) { return h ? n_tensors(h->d) : TTSDEC_ERR_INVALID_ARG; }
 size_t ttsdur_packed_bytes(const ttsdur_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
 
 int ttsdur_pack_weights(ttsdur_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
-  if (!h || !src || !blob || n_src != ttsdur_num_weight_tensors(h)) return TTSDEC_ERR_INVALID_ARG;
-  for (int i = 0; i < n_src; ++i)
-    if (!src[i]) return TTSDEC_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(blob) & 255) return TTSDEC_ERR_WORKSPACE;
-  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = pack_begin(h, src, n_src, ttsdur_num_weight_tensors(h), false, blob, ttsdur_packed_bytes(h), st);
+  if (rc != TTSDEC_OK) return rc;
   const ttsdur_dims& d = h->d;
   const DurBlob& L = h->bl;
   float* b = static_cast<float*>(blob);
-  if (hipMemsetAsync(blob, 0, L.total * sizeof(float), st) != hipSuccess) return dur_fail(h, "memset");
   const int C = d.in_channels;
   int k = 0;
   auto kmajor = [&](size_t off, int N, int Cin, int taps) {
@@ -674,16 +659,10 @@ int ttsdur_pack_weights(ttsdur_handle* h, const float* const* src, int n_src, vo
     copy(L.cond_w, (size_t)C * d.gin_channels);
     copy(L.cond_b, C);
   }
-  const int rc = dur_fail(h, "pack_weights");
-  if (rc == TTSDEC_OK) h->blob = b;
-  return rc;
+  return pack_end(h, b);
 }
 
-int ttsdur_bind_weights(ttsdur_handle* h, const void* blob) {
-  if (!h || !blob || (reinterpret_cast<uintptr_t>(blob) & 255)) return TTSDEC_ERR_INVALID_ARG;
-  h->blob = static_cast<const float*>(blob);
-  return TTSDEC_OK;
-}
+int ttsdur_bind_weights(ttsdur_handle* h, const void* blob) { return bind_blob(h, blob); }
 
 size_t ttsdur_workspace_bytes(const ttsdur_handle* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
@@ -741,7 +720,7 @@ int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths,
     run_dds(h, L.f_convs[f], c, nullptr, XA, XB, TAIL_FLOW, st);
     c0 ^= 1;  // the Flip after it
   }
-  return dur_fail(h, "sdp_reverse");
+  return record_hip_error(h, "sdp_reverse");
 }
 
 int ttsdur_dp_forward(ttsdur_handle* h, const float* x, const int32_t* lengths, const float* g, int B, int T, float* logw, void* workspace,
@@ -770,7 +749,7 @@ int ttsdur_dp_forward(ttsdur_handle* h, const float* x, const int32_t* lengths, 
   p.gamma = b + L.n2g; p.beta = b + L.n2b; p.out = nullptr;
   p.proj_w = b + L.p_w; p.proj_b = b + L.p_b; p.proj_out = logw;
   hipLaunchKernelGGL(pw_conv_kernel, dim3(nblk), dim3(kThreads), pw_lds(Fc, 3, Fc), st, p);
-  return dur_fail(h, "dp_forward");
+  return record_hip_error(h, "dp_forward");
 }
 
 int ttsdur_lengths(ttsdur_handle* h, const float* logw, const int32_t* lengths, float length_scale, int B, int T, int32_t* cum,
@@ -779,7 +758,7 @@ int ttsdur_lengths(ttsdur_handle* h, const float* logw, const int32_t* lengths, 
   if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   hipLaunchKernelGGL(lengths_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), logw, lengths, length_scale, B, T, cum, y_len,
                      status);
-  return dur_fail(h, "lengths");
+  return record_hip_error(h, "lengths");
 }
 
 int ttsdur_expand(ttsdur_handle* h, const int32_t* cum, const float* m, const float* logs, const float* eps, int eps_T, float noise_scale,
@@ -790,7 +769,7 @@ int ttsdur_expand(ttsdur_handle* h, const int32_t* cum, const float* m, const fl
   const size_t lds = (size_t)inter * (kExpFrames + 1) * sizeof(float) + kExpFrames * sizeof(int);
   hipLaunchKernelGGL(expand_kernel, dim3((unsigned)((T_y + kExpFrames - 1) / kExpFrames), (unsigned)B), dim3(256), lds,
                      static_cast<hipStream_t>(stream), cum, m, logs, eps, eps_T, noise_scale, T, inter, T_y, z_p, m_p, logs_p, attn);
-  return dur_fail(h, "expand");
+  return record_hip_error(h, "expand");
 }
 
 }  // extern "C"

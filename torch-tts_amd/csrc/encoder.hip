@@ -26,13 +26,9 @@ struct EncWs {  // offsets in bytes
 };
 }  // namespace
 
-struct ttsenc_handle {
+struct ttsenc_handle : HandleBase {  // (precision: that of the convs and the input projection)
   ttsenc_dims d;
   EncBlob bl;
-  const float* blob;
-  int device;  // HIP device current at create (-1: none); must be current for every later call
-  int precision;  // TTSDEC_PREC_F32 (default: the reference's arithmetic) or TTSDEC_PREC_SPLIT_F16 for the convs and the input projection
-  std::string hip_err;
 };
 
 namespace {
@@ -72,12 +68,6 @@ EncWs make_ws(const ttsenc_dims& d, int B, int Lm) {
   W.total = off;
   return W;
 }
-int enc_fail(ttsenc_handle* h, const char* where) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return TTSDEC_OK;
-  if (h) h->hip_err = std::string(where) + ": " + hipGetErrorString(e);
-  return TTSDEC_ERR_HIP;
-}
 }  // namespace
 
 extern "C" {
@@ -92,9 +82,7 @@ int ttsenc_create(const ttsenc_dims* dims, ttsenc_handle** out) {
   if (!h) return TTSDEC_ERR_INVALID_ARG;
   h->d = d;
   h->bl = make_layout(d);
-  h->blob = nullptr;
   h->device = current_device_or_minus1();
-  h->precision = TTSDEC_PREC_F32;
   *out = h;
   return TTSDEC_OK;
 }
@@ -104,13 +92,9 @@ int ttsenc_destroy(ttsenc_handle* h) {
   return TTSDEC_OK;
 }
 
-const char* ttsenc_last_hip_error(const ttsenc_handle* h) { return h ? h->hip_err.c_str() : ""; }
-int ttsenc_set_precision(ttsenc_handle* h, int precision) {
-  if (!h || (precision != TTSDEC_PREC_F32 && precision != TTSDEC_PREC_SPLIT_F16)) return TTSDEC_ERR_INVALID_ARG;
-  h->precision = precision;
-  return TTSDEC_OK;
-}
-int ttsenc_get_precision(const ttsenc_handle* h) { return h ? h->precision : TTSDEC_ERR_INVALID_ARG; }
+const char* ttsenc_last_hip_error(const ttsenc_handle* h) { return last_hip_error(h); }
+int ttsenc_set_precision(ttsenc_handle* h, int precision) { return set_precision(h, precision); }
+int ttsenc_get_precision(const ttsenc_handle* h) { return get_precision(h); }
 int ttsenc_num_weight_tensors(const ttsenc_handle* h) { return h ? TTSENC_W_COUNT : TTSDEC_ERR_INVALID_ARG; }
 size_t ttsenc_packed_bytes(const ttsenc_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
 size_t ttsenc_workspace_bytes(const ttsenc_handle* h, int B, int L) {
@@ -119,17 +103,13 @@ size_t ttsenc_workspace_bytes(const ttsenc_handle* h, int B, int L) {
 }
 
 int ttsenc_pack_weights(ttsenc_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
-  if (!h || !src || !blob || n_src != TTSENC_W_COUNT) return TTSDEC_ERR_INVALID_ARG;
-  for (int i = 0; i < n_src; ++i)
-    if (!src[i]) return TTSDEC_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(blob) & 255) return TTSDEC_ERR_WORKSPACE;
-  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = pack_begin(h, src, n_src, TTSENC_W_COUNT, false, blob, ttsenc_packed_bytes(h), st);
+  if (rc != TTSDEC_OK) return rc;
   const ttsenc_dims& d = h->d;
   const EncBlob& L = h->bl;
   float* b = static_cast<float*>(blob);
   const size_t E = d.d_emb, H = d.d_out / 2;
-  if (hipMemsetAsync(blob, 0, L.total * sizeof(float), st) != hipSuccess) return enc_fail(h, "memset");
   launch_copy(src[TTSENC_W_EMB], b + L.emb, (size_t)d.alphabet_size * E, st);
   // conv.{0,3,6}.weight -> [C_out][tap][C_in]; BatchNorm1d (the third has no affine) -> (alpha, beta)
   launch_conv_transpose(src[TTSENC_W_CONV0], b + L.conv_w[0], (int)E, (int)E, d.conv_kernel, st);
@@ -156,16 +136,10 @@ int ttsenc_pack_weights(ttsenc_handle* h, const float* const* src, int n_src, vo
   launch_copy(src[TTSENC_W_HH_REV], b + L.w_hh[1], 4 * H * H, st);
   launch_copy(src[TTSENC_W_H0], b + L.h0, 2 * H, st);
   launch_copy(src[TTSENC_W_C0], b + L.c0, 2 * H, st);
-  const int rc = enc_fail(h, "pack_weights");
-  if (rc == TTSDEC_OK) h->blob = b;
-  return rc;
+  return pack_end(h, b);
 }
 
-int ttsenc_bind_weights(ttsenc_handle* h, const void* blob) {
-  if (!h || !blob || (reinterpret_cast<uintptr_t>(blob) & 255)) return TTSDEC_ERR_INVALID_ARG;
-  h->blob = static_cast<const float*>(blob);
-  return TTSDEC_OK;
-}
+int ttsenc_bind_weights(ttsenc_handle* h, const void* blob) { return bind_blob(h, blob); }
 
 int ttsenc_forward(ttsenc_handle* h, const int64_t* ids, const int32_t* lengths, int B, int L, int L_out, float* memory,
                    void* workspace, size_t workspace_bytes, void* stream, int32_t* status) {
@@ -235,7 +209,7 @@ int ttsenc_forward(ttsenc_handle* h, const int64_t* ids, const int32_t* lengths,
     launch_fill_rows(F(W.h[dir][0]), blob + bl.h0 + dir * H, B, H, st);
     launch_fill_rows(F(W.c[dir]), blob + bl.c0 + dir * H, B, H, st);
   }
-  if (hipMemsetAsync(memory, 0, (size_t)B * L_out * 2 * H * sizeof(float), st) != hipSuccess) return enc_fail(h, "memset");
+  if (hipMemsetAsync(memory, 0, (size_t)B * L_out * 2 * H * sizeof(float), st) != hipSuccess) return record_hip_error(h, "memset");
   // the recurrence: step t advances every utterance that is still running; the reverse direction
   // walks each utterance from its own last token (packed-sequence semantics, rnn.py:113-126)
   for (int t = 0; t < L_out; ++t) {
@@ -254,7 +228,7 @@ int ttsenc_forward(ttsenc_handle* h, const int64_t* ids, const int32_t* lengths,
     }
     launch_lstm_pair(dirs[0], dirs[1], st);  // both directions of step t in one launch
   }
-  return enc_fail(h, "encoder forward");
+  return record_hip_error(h, "encoder forward");
 }
 
 }  // extern "C"

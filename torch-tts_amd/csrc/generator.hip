@@ -42,12 +42,9 @@ struct GenBlob {  // offsets in floats
 };
 }  // namespace
 
-struct ttsgen_handle {
+struct ttsgen_handle : HandleBase {
   ttsgen_dims d;
   GenBlob bl;
-  const float* blob;
-  int device;
-  std::string hip_err;
 };
 
 namespace {
@@ -142,13 +139,6 @@ int group_size(const ttsgen_dims& d, int B, int T) {
 
 size_t ws_floats(const ttsgen_dims& d, int G, int T) {
   return 6 * up((size_t)G * utt_floats(d, T), kAlign) + up((size_t)G * d.upsample_initial_channel, kAlign);
-}
-
-int gen_fail(ttsgen_handle* h, const char* where) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return TTSDEC_OK;
-  if (h) h->hip_err = std::string(where) + ": " + hipGetErrorString(e);
-  return TTSDEC_ERR_HIP;
 }
 
 // ===========================================================================
@@ -300,7 +290,6 @@ int ttsgen_create(const ttsgen_dims* dims, ttsgen_handle** out) {
   if (!h) return TTSDEC_ERR_INVALID_ARG;
   h->d = *dims;
   h->bl = make_layout(*dims);
-  h->blob = nullptr;
   h->device = current_device_or_minus1();
   *out = h;
   return TTSDEC_OK;
@@ -309,21 +298,17 @@ int ttsgen_destroy(ttsgen_handle* h) {
   delete h;
   return TTSDEC_OK;
 }
-const char* ttsgen_last_hip_error(const ttsgen_handle* h) { return h ? h->hip_err.c_str() : ""; }
+const char* ttsgen_last_hip_error(const ttsgen_handle* h) { return last_hip_error(h); }
 int ttsgen_num_weight_tensors(const ttsgen_handle* h) { return h ? n_tensors(h->d) : TTSDEC_ERR_INVALID_ARG; }
 size_t ttsgen_packed_bytes(const ttsgen_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
 
 int ttsgen_pack_weights(ttsgen_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
-  if (!h || !src || !blob || n_src != ttsgen_num_weight_tensors(h)) return TTSDEC_ERR_INVALID_ARG;
-  for (int i = 0; i < n_src; ++i)
-    if (!src[i]) return TTSDEC_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(blob) & 255) return TTSDEC_ERR_WORKSPACE;
-  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = pack_begin(h, src, n_src, ttsgen_num_weight_tensors(h), false, blob, ttsgen_packed_bytes(h), st);
+  if (rc != TTSDEC_OK) return rc;
   const ttsgen_dims& d = h->d;
   const GenBlob& L = h->bl;
   float* b = static_cast<float*>(blob);
-  if (hipMemsetAsync(blob, 0, L.total * sizeof(float), st) != hipSuccess) return gen_fail(h, "memset");
   const int C0 = d.upsample_initial_channel;
   int k = 0;
   launch_conv_transpose(src[k++], b + L.pre_w, C0, d.initial_channel, 7, st);  // [Co, Ci, 7] -> [Co, 7, Ci]
@@ -346,16 +331,10 @@ int ttsgen_pack_weights(ttsgen_handle* h, const float* const* src, int n_src, vo
     launch_copy(src[k++], b + L.cond_w, (size_t)C0 * d.gin_channels, st);
     launch_copy(src[k++], b + L.cond_b, C0, st);
   }
-  const int rc = gen_fail(h, "pack_weights");
-  if (rc == TTSDEC_OK) h->blob = b;
-  return rc;
+  return pack_end(h, b);
 }
 
-int ttsgen_bind_weights(ttsgen_handle* h, const void* blob) {
-  if (!h || !blob || (reinterpret_cast<uintptr_t>(blob) & 255)) return TTSDEC_ERR_INVALID_ARG;
-  h->blob = static_cast<const float*>(blob);
-  return TTSDEC_OK;
-}
+int ttsgen_bind_weights(ttsgen_handle* h, const void* blob) { return bind_blob(h, blob); }
 
 size_t ttsgen_workspace_bytes(const ttsgen_handle* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
@@ -382,7 +361,7 @@ static int gen_call(ttsgen_handle* h, const float* z, const float* g, int B, int
     run_group(h, z + (size_t)b0 * T * h->d.initial_channel, g != nullptr ? g + (size_t)b0 * h->d.gin_channels : nullptr, n, T, n_stages,
               out != nullptr ? out + (size_t)b0 * T * up_all : nullptr, static_cast<float*>(workspace), st);
   }
-  return gen_fail(h, "forward");
+  return record_hip_error(h, "forward");
 }
 
 int ttsgen_forward(ttsgen_handle* h, const float* z, const float* g, int B, int T, float* out, void* workspace, size_t workspace_bytes,

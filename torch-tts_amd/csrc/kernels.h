@@ -1,5 +1,7 @@
 // Internal launch interface between the C ABI (api.hip) and the kernels.
 #pragma once
+#include <string>
+
 #include "common.h"
 
 namespace ttsdec {
@@ -311,9 +313,26 @@ void launch_absmax(const float* src, size_t n, float* out, hipStream_t st);
 // (ids outside [0, n_table) are clamped and reported: bit 0 of *status, a device word that may be nullptr)
 void launch_embed(const long long* ids, const float* table, int n_table, int n_rows, int E, float* out_a, int lda, float* out_b,
                   int ldb, int* status, hipStream_t st);
-// device bookkeeping shared by the three handle types
+// host plumbing shared by the C-ABI handle families (defined in api.hip)
 int current_device_or_minus1();
 bool device_is_current(int device);
+struct HandleBase {  // what every family's handle holds besides its dims and blob layout
+  const float* blob = nullptr;      // packed weights (*_pack_weights / *_bind_weights)
+  int device = -1;                  // HIP device current at create (-1: none); must be current for every later call
+  int precision = TTSDEC_PREC_F32;  // TTSDEC_PREC_* of the families that have *_set_precision
+  std::string hip_err;              // *_last_hip_error
+};
+int hip_fail(HandleBase* h, hipError_t e, const char* where);  // records e: TTSDEC_ERR_HIP
+int record_hip_error(HandleBase* h, const char* where);        // hipGetLastError(): TTSDEC_OK, or hip_fail
+// *_pack_weights before its launches: arguments, tensor count, NULL sources (refused unless null_ok), 256-byte alignment, device,
+// then the blob zeroed on st
+int pack_begin(HandleBase* h, const float* const* src, int n_src, int n_expected, bool null_ok, void* blob, size_t blob_bytes,
+               hipStream_t st);
+int pack_end(HandleBase* h, const float* blob);  // after them: the launch error, or the blob bound
+int bind_blob(HandleBase* h, const void* blob);
+int set_precision(HandleBase* h, int precision);
+int get_precision(const HandleBase* h);
+const char* last_hip_error(const HandleBase* h);
 void launch_fill_rows(float* dst, const float* row, int n_rows, int n_cols, hipStream_t st);  // dst[m, :] = row[:]
 void launch_conv_transpose(const float* w /*[Co,Ci,k]*/, float* out /*[Co,k,Ci]*/, int Co, int Ci, int k, hipStream_t st);
 // Conv1dFix (mps_fixes.py:22-29) pairs flat-weight column n*Ci + c with x[c, t + pad - n]:

@@ -49,13 +49,9 @@ struct VitsBlob {  // offsets in floats
 };
 }  // namespace
 
-struct ttsvits_handle {
+struct ttsvits_handle : HandleBase {  // (precision: that of every GEMM)
   ttsvits_dims d;
   VitsBlob bl;
-  const float* blob;
-  int device;  // HIP device current at create (-1: none); must be current for every later call
-  int precision;  // TTSDEC_PREC_F32 (default) or TTSDEC_PREC_SPLIT_F16: arithmetic of every GEMM (ttsvits_set_precision)
-  std::string hip_err;
 };
 
 namespace {
@@ -109,13 +105,6 @@ int n_cond_tensors(const ttsvits_dims& d) { return d.gin_channels > 0 ? 2 : 0; }
 int n_text_tensors(const ttsvits_dims& d) { return 1 + n_cond_tensors(d) + n_stack_tensors(enc_dims(d)) + 2; }
 int n_flow_tensors(const ttsvits_dims& d) {
   return d.n_flows * (n_stack_tensors(tf_dims(d)) + 2 + n_cond_tensors(d) + 4 * d.flow_wn_layers + 2);
-}
-
-int vits_fail(ttsvits_handle* h, const char* where) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return TTSDEC_OK;
-  if (h) h->hip_err = std::string(where) + ": " + hipGetErrorString(e);
-  return TTSDEC_ERR_HIP;
 }
 
 // ===========================================================================
@@ -1305,7 +1294,7 @@ int run_stack(ttsvits_handle* h, const StackBlob& sb, const StackDims& sd, const
                    : dk == 48 ? (const void*)mha_mfma_kernel<24>
                    : dk == 16 ? (const void*)mha_mfma_kernel<8> : (const void*)mha_mfma_kernel<4>;
   if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return vits_fail(h, "hipFuncSetAttribute(mha kernel)");
+    return record_hip_error(h, "hipFuncSetAttribute(mha kernel)");
   const float* xin = sw.xm;  // layer 0 attends over x * mask; later layers over the unmasked LayerNorm output
   for (int i = 0; i < sd.layers; ++i) {
     float* xa = i == 0 ? sw.xm : sw.x;
@@ -1548,7 +1537,7 @@ int run_flow(ttsvits_handle* h, const float* z, const int32_t* lengths, const fl
   if (!forward || d.n_flows == 0) hipLaunchKernelGGL(copy_f_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, out, (size_t)M * I);
   else if (o4) hipLaunchKernelGGL(flip_copy4_kernel, grid1((size_t)M * I / 4), dim3(256), 0, st, cur, out, (uint32_t)M, (uint32_t)I / 4);
   else hipLaunchKernelGGL(flip_copy_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, out, M, I);
-  return vits_fail(h, forward ? "flow_forward" : "flow_reverse");
+  return record_hip_error(h, forward ? "flow_forward" : "flow_reverse");
 }
 }  // namespace
 
@@ -1562,35 +1551,27 @@ int ttsvits_create(const ttsvits_dims* dims, ttsvits_handle** out) {
   if (!h) return TTSDEC_ERR_INVALID_ARG;
   h->d = *dims;
   h->bl = make_layout(*dims);
-  h->blob = nullptr;
   h->device = current_device_or_minus1();
-  h->precision = TTSDEC_PREC_F32;  // (the reference's arithmetic; ttsvits_set_precision opts into split-fp16)
   *out = h;
   return TTSDEC_OK;
 }
-int ttsvits_set_precision(ttsvits_handle* h, int precision) {
-  if (!h || (precision != TTSDEC_PREC_F32 && precision != TTSDEC_PREC_SPLIT_F16)) return TTSDEC_ERR_INVALID_ARG;
-  h->precision = precision;
-  return TTSDEC_OK;
-}
-int ttsvits_get_precision(const ttsvits_handle* h) { return h ? h->precision : TTSDEC_ERR_INVALID_ARG; }
+int ttsvits_set_precision(ttsvits_handle* h, int precision) { return set_precision(h, precision); }
+int ttsvits_get_precision(const ttsvits_handle* h) { return get_precision(h); }
 int ttsvits_destroy(ttsvits_handle* h) {
   delete h;
   return TTSDEC_OK;
 }
-const char* ttsvits_last_hip_error(const ttsvits_handle* h) { return h ? h->hip_err.c_str() : ""; }
+const char* ttsvits_last_hip_error(const ttsvits_handle* h) { return last_hip_error(h); }
 int ttsvits_num_weight_tensors(const ttsvits_handle* h) { return h ? n_text_tensors(h->d) + n_flow_tensors(h->d) : TTSDEC_ERR_INVALID_ARG; }
 size_t ttsvits_packed_bytes(const ttsvits_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
 
 int ttsvits_pack_weights(ttsvits_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
-  if (!h || !src || !blob || n_src != ttsvits_num_weight_tensors(h)) return TTSDEC_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(blob) & 255) return TTSDEC_ERR_WORKSPACE;
-  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = pack_begin(h, src, n_src, ttsvits_num_weight_tensors(h), true, blob, ttsvits_packed_bytes(h), st);
+  if (rc != TTSDEC_OK) return rc;
   const ttsvits_dims& d = h->d;
   const VitsBlob& L = h->bl;
   float* b = static_cast<float*>(blob);
-  if (hipMemsetAsync(blob, 0, L.total * sizeof(float), st) != hipSuccess) return vits_fail(h, "memset");
   const size_t H = d.hidden_channels, I = d.inter_channels, half = I / 2, Fh = d.flow_hidden;
   int k = 0;
   // (launch_copy / launch_conv_transpose skip NULL sources: a module that owns only the text encoder
@@ -1631,16 +1612,10 @@ int ttsvits_pack_weights(ttsvits_handle* h, const float* const* src, int n_src, 
     launch_copy(src[k++], b + fb.post_b, half, st);
     pack_planes(b, fb.post_w, half * Fh, st);
   }
-  const int rc = vits_fail(h, "pack_weights");
-  if (rc == TTSDEC_OK) h->blob = b;
-  return rc;
+  return pack_end(h, b);
 }
 
-int ttsvits_bind_weights(ttsvits_handle* h, const void* blob) {
-  if (!h || !blob || (reinterpret_cast<uintptr_t>(blob) & 255)) return TTSDEC_ERR_INVALID_ARG;
-  h->blob = static_cast<const float*>(blob);
-  return TTSDEC_OK;
-}
+int ttsvits_bind_weights(ttsvits_handle* h, const void* blob) { return bind_blob(h, blob); }
 
 size_t ttsvits_text_encoder_workspace_bytes(const ttsvits_handle* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
@@ -1680,14 +1655,14 @@ int ttsvits_text_encoder(ttsvits_handle* h, const int64_t* ids, const int32_t* l
   // models.py:377-379: stats = proj(x) * x_mask; m, logs = split(stats)
   gemm_generic(sw.cx, sw.xm, sw.xm_p, H, H, h->blob + L.proj_w, (size_t)2 * I * H, h->blob + L.proj_b, M, 2 * I, stats, nullptr, 2 * I, 0, mask,
                nullptr, 1, T, st);
-  if (hipMemcpyAsync(x, sw.xm, (size_t)M * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return vits_fail(h, "copy x");
+  if (hipMemcpyAsync(x, sw.xm, (size_t)M * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return record_hip_error(h, "copy x");
   if (hipMemcpy2DAsync(m, (size_t)I * sizeof(float), stats, (size_t)2 * I * sizeof(float), (size_t)I * sizeof(float), M,
                        hipMemcpyDeviceToDevice, st) != hipSuccess)
-    return vits_fail(h, "copy m");
+    return record_hip_error(h, "copy m");
   if (hipMemcpy2DAsync(logs, (size_t)I * sizeof(float), stats + I, (size_t)2 * I * sizeof(float), (size_t)I * sizeof(float), M,
                        hipMemcpyDeviceToDevice, st) != hipSuccess)
-    return vits_fail(h, "copy logs");
-  return vits_fail(h, "text_encoder");
+    return record_hip_error(h, "copy logs");
+  return record_hip_error(h, "text_encoder");
 }
 
 size_t ttsvits_flow_workspace_bytes(const ttsvits_handle* h, int B, int T) {
@@ -1724,14 +1699,10 @@ struct PostBlob {  // offsets in floats; GEMM weights take 2n floats (fp32 | hi 
 };
 }  // namespace
 
-struct ttspost_handle {
+struct ttspost_handle : HandleBase {
   ttspost_dims d;
   int spec_pad;  // spec_channels rounded up to 8: K of the pre GEMM (the 16-byte granularity of its split-fp16 operand)
   PostBlob bl;
-  const float* blob;
-  int device;
-  int precision;
-  std::string hip_err;
 };
 
 namespace {
@@ -1762,12 +1733,6 @@ bool post_dims_ok(const ttspost_dims& d) {
   if (d.gin_channels < 0 || (d.gin_channels & 3) || d.gin_channels > 4096) return false;
   return true;
 }
-int post_fail(ttspost_handle* h, const char* where) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return TTSDEC_OK;
-  if (h) h->hip_err = std::string(where) + ": " + hipGetErrorString(e);
-  return TTSDEC_ERR_HIP;
-}
 }  // namespace
 
 extern "C" {
@@ -1781,9 +1746,7 @@ int ttspost_create(const ttspost_dims* dims, ttspost_handle** out) {
   h->d = *dims;
   h->spec_pad = (int)up((size_t)dims->spec_channels, 8);
   h->bl = make_post_layout(*dims, h->spec_pad);
-  h->blob = nullptr;
   h->device = current_device_or_minus1();
-  h->precision = TTSDEC_PREC_F32;
   *out = h;
   return TTSDEC_OK;
 }
@@ -1791,34 +1754,26 @@ int ttspost_destroy(ttspost_handle* h) {
   delete h;
   return TTSDEC_OK;
 }
-const char* ttspost_last_hip_error(const ttspost_handle* h) { return h ? h->hip_err.c_str() : ""; }
-int ttspost_set_precision(ttspost_handle* h, int precision) {
-  if (!h || (precision != TTSDEC_PREC_F32 && precision != TTSDEC_PREC_SPLIT_F16)) return TTSDEC_ERR_INVALID_ARG;
-  h->precision = precision;
-  return TTSDEC_OK;
-}
-int ttspost_get_precision(const ttspost_handle* h) { return h ? h->precision : TTSDEC_ERR_INVALID_ARG; }
+const char* ttspost_last_hip_error(const ttspost_handle* h) { return last_hip_error(h); }
+int ttspost_set_precision(ttspost_handle* h, int precision) { return set_precision(h, precision); }
+int ttspost_get_precision(const ttspost_handle* h) { return get_precision(h); }
 int ttspost_num_weight_tensors(const ttspost_handle* h) {
   return h ? 4 + 4 * h->d.n_layers + (h->d.gin_channels > 0 ? 2 : 0) : TTSDEC_ERR_INVALID_ARG;
 }
 size_t ttspost_packed_bytes(const ttspost_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
 
 int ttspost_pack_weights(ttspost_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
-  if (!h || !src || !blob || n_src != ttspost_num_weight_tensors(h)) return TTSDEC_ERR_INVALID_ARG;
-  for (int i = 0; i < n_src; ++i)
-    if (!src[i]) return TTSDEC_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(blob) & 255) return TTSDEC_ERR_WORKSPACE;
-  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = pack_begin(h, src, n_src, ttspost_num_weight_tensors(h), false, blob, ttspost_packed_bytes(h), st);
+  if (rc != TTSDEC_OK) return rc;
   const ttspost_dims& d = h->d;
   const PostBlob& L = h->bl;
   float* b = static_cast<float*>(blob);
-  if (hipMemsetAsync(blob, 0, L.total * sizeof(float), st) != hipSuccess) return post_fail(h, "memset");
   const size_t H = d.hidden_channels, I = d.inter_channels, S = d.spec_channels, Sp = h->spec_pad;
   int k = 0;
   // pre.weight [H, S, 1] -> rows of Sp floats (the padding columns stay zero)
   if (hipMemcpy2DAsync(b + L.pre_w, Sp * sizeof(float), src[k++], S * sizeof(float), S * sizeof(float), H, hipMemcpyDeviceToDevice, st) != hipSuccess)
-    return post_fail(h, "copy pre.weight");
+    return record_hip_error(h, "copy pre.weight");
   launch_copy(src[k++], b + L.pre_b, H, st);
   pack_planes(b, L.pre_w, H * Sp, st);
   if (d.gin_channels > 0) {
@@ -1840,16 +1795,10 @@ int ttspost_pack_weights(ttspost_handle* h, const float* const* src, int n_src, 
   launch_copy(src[k++], b + L.proj_w, 2 * I * H, st);
   launch_copy(src[k++], b + L.proj_b, 2 * I, st);
   pack_planes(b, L.proj_w, 2 * I * H, st);
-  const int rc = post_fail(h, "pack_weights");
-  if (rc == TTSDEC_OK) h->blob = b;
-  return rc;
+  return pack_end(h, b);
 }
 
-int ttspost_bind_weights(ttspost_handle* h, const void* blob) {
-  if (!h || !blob || (reinterpret_cast<uintptr_t>(blob) & 255)) return TTSDEC_ERR_INVALID_ARG;
-  h->blob = static_cast<const float*>(blob);
-  return TTSDEC_OK;
-}
+int ttspost_bind_weights(ttspost_handle* h, const void* blob) { return bind_blob(h, blob); }
 
 size_t ttspost_workspace_bytes(const ttspost_handle* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
@@ -1906,7 +1855,7 @@ int ttspost_forward(ttspost_handle* h, const float* y, const int32_t* lengths, c
   // m, logs = split(stats); z = (m + eps * exp(logs)) * x_mask                      :893-894
   const dim3 sgrid((T + kTr - 1) / kTr, (I + kTr - 1) / kTr, B);
   hipLaunchKernelGGL(post_sample_kernel, sgrid, dim3(256), 0, st, stats, eps, eps_T, mask, z, m, logs, I, T);
-  return post_fail(h, "post_forward");
+  return record_hip_error(h, "post_forward");
 }
 
 }  // extern "C"

@@ -5,14 +5,13 @@ GEMM convs, one input-projection GEMM, packed-sequence LSTM steps); training kee
 PyTorch ops so gradients flow (the encoder is outside the inference hot path)."""
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, Optional
+from typing import Dict
 
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import PackedWeightsMixin, _require_device, _stream, weights_fingerprint
+from .engine import EngineCache, Handle, PackedWeightsMixin, _require_device, _stream
 
 
 class _ISRLU(nn.Module):
@@ -36,58 +35,15 @@ class _BiDiLSTM(nn.Module):
         return x, h
 
 
-class EncoderEngine:
-    """One ttsenc handle on one device."""
+class EncoderEngine(Handle):
+    """One ttsenc handle on one device; dims: the fields of _lib.EncDims."""
 
-    def __init__(self, alphabet_size: int, d_emb: int, d_out: int, bn_eps: float, device: torch.device):
-        self._lib = _lib.load()
-        self.device = device
-        h = C.c_void_p()
-        dims = _lib.EncDims(alphabet_size, d_emb, d_out, 5, bn_eps)
-        with torch.cuda.device(device):  # the handle binds to the device current at create
-            _lib.check(self._lib.ttsenc_create(C.byref(dims), C.byref(h)), "ttsenc_create")
-        self.alphabet_size = alphabet_size
-        self._h = h
-        self.d_out = d_out
-        self.blob: Optional[torch.Tensor] = None
-        self._fingerprint = None
-        self._ws: Dict = {}
+    PREFIX = "ttsenc"
+
+    def __init__(self, dims: Dict, device: torch.device):
+        super().__init__(dims, _lib.EncDims(**dims), device)
         self.status = torch.zeros(1, dtype=torch.int32, device=device)  # bit 0: an id outside the table (ttsenc_forward)
         self._status_pending = False
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ttsenc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def ensure_packed(self, tensors) -> None:
-        fp = weights_fingerprint(tensors)
-        if self.blob is not None and fp == self._fingerprint:
-            return
-        n = len(tensors)
-        arr = (C.c_void_p * n)()
-        keep = []
-        for i, t in enumerate(tensors):
-            _require_device(t, "encoder weights")
-            tc = t.detach().to(torch.float32).contiguous()
-            keep.append(tc)
-            arr[i] = tc.data_ptr()
-        with torch.cuda.device(self.device):
-            blob = torch.empty(self._lib.ttsenc_packed_bytes(self._h), dtype=torch.uint8, device=self.device)
-            rc = self._lib.ttsenc_pack_weights(self._h, arr, n, blob.data_ptr(), _stream(self.device))
-        if rc != _lib.OK:
-            raise _lib.TtsdecError(rc, "ttsenc_pack_weights", self._lib.ttsenc_last_hip_error(self._h).decode())
-        self.blob, self._fingerprint = blob, fp
-
-    def set_precision(self, mode: str) -> None:
-        """"f32" (exact, default) or "split_f16": arithmetic of the conv / input-projection GEMMs (include/ttsdec.h ttsenc_set_precision)."""
-        _lib.check(self._lib.ttsenc_set_precision(self._h, {"f32": _lib.PREC_F32, "split_f16": _lib.PREC_SPLIT_F16}[mode]), "ttsenc_set_precision")
 
     def check_ids(self) -> None:
         """Raises IndexError if the last forward met a token id outside the table (nn.Embedding does, encoder.py:69).  Reads the
@@ -96,7 +52,7 @@ class EncoderEngine:
         if self._status_pending:
             self._status_pending = False
             if int(self.status) & 1:
-                raise IndexError(f"token id out of range [0, {self.alphabet_size}) in the encoder's last input")
+                raise IndexError(f"token id out of range [0, {self.dims['alphabet_size']}) in the encoder's last input")
 
     def forward(self, ids: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
         _require_device(ids, "ids")
@@ -106,33 +62,13 @@ class EncoderEngine:
         self.status.zero_()
         self._status_pending = True
         lens = lengths.to(device=self.device, dtype=torch.int32).contiguous()
-        key = (B, L)
-        ws = self._ws.get(key)
-        if ws is None:
-            self._ws.clear()
-            ws = torch.empty(self._lib.ttsenc_workspace_bytes(self._h, B, L), dtype=torch.uint8, device=self.device)
-            self._ws[key] = ws
-        memory = torch.empty(B, l_out, self.d_out, dtype=torch.float32, device=self.device)
+        ws = self.workspace("forward", self._lib.ttsenc_workspace_bytes(self._h, B, L))
+        memory = torch.empty(B, l_out, self.dims["d_out"], dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             rc = self._lib.ttsenc_forward(self._h, ids.data_ptr(), lens.data_ptr(), B, L, l_out, memory.data_ptr(), ws.data_ptr(),
                                           ws.numel(), _stream(self.device), self.status.data_ptr())
-        if rc != _lib.OK:
-            raise _lib.TtsdecError(rc, "ttsenc_forward", self._lib.ttsenc_last_hip_error(self._h).decode())
+        self._err(rc, "ttsenc_forward")
         return memory
-
-
-class _EncCache:
-    def __init__(self):
-        self.by_dev: Dict[int, EncoderEngine] = {}
-
-    def __getstate__(self):
-        return {}
-
-    def __setstate__(self, st):
-        self.by_dev = {}
-
-    def __deepcopy__(self, memo):
-        return _EncCache()
 
 
 class Encoder2(PackedWeightsMixin, nn.Module):
@@ -155,7 +91,7 @@ class Encoder2(PackedWeightsMixin, nn.Module):
         # forward reads it before returning (one host sync); True: the caller reads it later through check_ids()
         # (Tacotron.forward does, at the decoder's own sync)
         self.defer_id_check = False
-        self._engines = _EncCache()
+        self._engines = EngineCache(EncoderEngine)
 
     def weight_tensors(self):
         c, r = self.conv, self.rnn.rnn
@@ -185,11 +121,8 @@ class Encoder2(PackedWeightsMixin, nn.Module):
         )
         if not hip_ok:
             return self._stock_forward(x, x_lengths)
-        idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        eng = self._engines.by_dev.get(idx)
-        if eng is None:
-            eng = EncoderEngine(self.emb.num_embeddings, self.dim_emb, self.dim_out, float(self.conv[1].eps), torch.device("cuda", idx))
-            self._engines.by_dev[idx] = eng
+        dims = dict(alphabet_size=self.emb.num_embeddings, d_emb=self.dim_emb, d_out=self.dim_out, conv_kernel=5, bn_eps=float(self.conv[1].eps))
+        eng = self._engines.get(dims, x.device)
         eng.ensure_packed(self.weight_tensors())
         eng.set_precision(self.precision)
         memory = eng.forward(x, x_lengths)
@@ -199,5 +132,5 @@ class Encoder2(PackedWeightsMixin, nn.Module):
 
     def check_ids(self) -> None:
         """The deferred id range check of the last HIP forward (see defer_id_check)."""
-        for eng in self._engines.by_dev.values():
+        for eng in self._engines.engines():
             eng.check_ids()

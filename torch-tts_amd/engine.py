@@ -3,6 +3,7 @@ kernel blob, holds workspaces (PyTorch caching allocator memory) and issues the
 C-ABI calls on torch's current HIP stream."""
 from __future__ import annotations
 
+import copy
 import ctypes as C
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -97,31 +98,44 @@ def weights_fingerprint(tensors: Sequence[Optional[Tensor]]) -> Tuple:
     return (_EPOCH[0],) + tuple((None if t is None else (t.data_ptr(), t._version, tuple(t.shape))) for t in tensors)
 
 
-class Engine:
-    """One ttsdec handle bound to one device.  Not thread-safe (the C ABI asks the
-    caller to serialise calls per handle)."""
+class Handle:
+    """One handle of a C-ABI family (include/ttsdec.h ``<prefix>_*``) bound to one device: create / close, the family's own
+    HIP error text, weight packing and grow-only workspaces.  Subclasses add the family's compute calls.  Not thread-safe
+    (the C ABI asks the caller to serialise calls per handle)."""
 
-    def __init__(self, dims: EngineDims, device: Optional[torch.device]):
+    PREFIX = ""  # the family: "ttsdec", "ttsenc", ...
+
+    def __init__(self, dims, c_dims, device: Optional[torch.device]):
+        """dims: the family's dims as the module holds them, c_dims: the same as the C struct; device None: a handle for
+        host-only queries (sizes, counts), which work without a GPU."""
         self.dims = dims
         self.device = device
         self._lib = _lib.load()
         h = C.c_void_p()
-        cd = dims.to_c()
+        create = self._fn("create")
         if device is not None:
-            with torch.cuda.device(device):
-                rc = self._lib.ttsdec_create(C.byref(cd), C.byref(h))
+            with torch.cuda.device(device):  # the handle binds to the device current at create
+                rc = create(C.byref(c_dims), C.byref(h))
         else:
-            rc = self._lib.ttsdec_create(C.byref(cd), C.byref(h))
-        _lib.check(rc, "ttsdec_create")
+            rc = create(C.byref(c_dims), C.byref(h))
+        if rc == _lib.ERR_DIMS:
+            raise _lib.DimsNotBuilt(rc, f"{self.PREFIX}_create", f"not built in the HIP library (include/ttsdec.h {self.PREFIX}_dims): {dims}")
+        _lib.check(rc, f"{self.PREFIX}_create")
         self._h = h
         self.blob: Optional[Tensor] = None
         self._fingerprint = None
-        self._ws: Dict[Tuple[int, int], Tensor] = {}
-        self._pws: Dict[Tuple[int, int], Tensor] = {}
+        self._ws: Optional[Dict[str, Tensor]] = None  # kind -> workspace; None: none held
+
+    def _fn(self, name: str):
+        return getattr(self._lib, f"{self.PREFIX}_{name}")
+
+    def _err(self, rc: int, what: str) -> None:
+        if rc != _lib.OK:
+            raise _lib.TtsdecError(rc, what, self._fn("last_hip_error")(self._h).decode() if rc == _lib.ERR_HIP else "")
 
     def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.ttsdec_destroy(self._h)
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __del__(self):  # pragma: no cover
@@ -132,25 +146,85 @@ class Engine:
 
     # ---- host-only queries (work without a GPU) ----
     def num_weight_tensors(self) -> int:
-        return self._lib.ttsdec_num_weight_tensors(self._h)
+        return int(self._fn("num_weight_tensors")(self._h))
 
     def packed_bytes(self) -> int:
-        return self._lib.ttsdec_packed_bytes(self._h)
+        return int(self._fn("packed_bytes")(self._h))
+
+    # ---- arithmetic of the GEMMs (the families that have the switch) ----
+    def set_precision(self, mode: str) -> None:
+        """"f32" (exact fp32 matrix instruction, default) or "split_f16" (hi/lo fp16 planes, 3 products)."""
+        code = {"f32": _lib.PREC_F32, "split_f16": _lib.PREC_SPLIT_F16}[mode]
+        self._err(self._fn("set_precision")(self._h, code), f"{self.PREFIX}_set_precision")
+
+    def precision(self) -> str:
+        return {_lib.PREC_F32: "f32", _lib.PREC_SPLIT_F16: "split_f16"}[int(self._fn("get_precision")(self._h))]
+
+    # ---- weights ----
+    def pack(self, tensors: Sequence[Optional[Tensor]]) -> Tensor:
+        """tensors: in the family's pack order; None = not owned by the calling module (the library leaves that region zero
+        where the family allows it - ttsdec_, ttsvits_ - and refuses it elsewhere)."""
+        n = self.num_weight_tensors()
+        if len(tensors) != n:
+            raise ValueError(f"expected {n} weight tensors, got {len(tensors)}")
+        keep: List[Tensor] = []
+        arr = (C.c_void_p * n)()
+        for i, t in enumerate(tensors):
+            if t is None:
+                continue
+            _require_device(t, "weights")
+            tc = t.detach().to(torch.float32).contiguous()
+            keep.append(tc)
+            arr[i] = tc.data_ptr()
+        with torch.cuda.device(self.device):
+            blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=self.device)
+            rc = self._fn("pack_weights")(self._h, arr, n, blob.data_ptr(), _stream(self.device))
+            torch.cuda.current_stream(self.device).synchronize()  # `keep` must outlive the packing kernels
+        self._err(rc, f"{self.PREFIX}_pack_weights")
+        self.blob, self._fingerprint = blob, weights_fingerprint(tensors)
+        return blob
+
+    def ensure_packed(self, tensors, key_tensors: Optional[Sequence[Optional[Tensor]]] = None) -> None:
+        """Packs unless the blob is current.  tensors: pack's list, or a callable producing it (called only when a repack is
+        needed); key_tensors: the parameters whose identity / version decide that (default: the list itself - derived tensors
+        such as weight-normed weights are new objects on every call and must not be the key)."""
+        fp = weights_fingerprint(key_tensors if key_tensors is not None else tensors)
+        if self.blob is not None and fp == self._fingerprint:
+            return
+        self.pack(tensors() if callable(tensors) else tensors)
+        self._fingerprint = fp
+
+    # ---- workspaces (caching-allocator memory, one grow-only buffer per kind) ----
+    def workspace(self, kind: str, nbytes: int) -> Tensor:
+        if self._ws is None:
+            self._ws = {}
+        ws = self._ws.get(kind)
+        if ws is None or ws.numel() < nbytes:
+            self._ws.pop(kind, None)  # (the old buffer goes back to the allocator first)
+            ws = self._ws[kind] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def release_workspaces(self) -> None:
+        """Drops every workspace (the next call allocates afresh); assigning None to ``_ws`` does the same."""
+        self._ws = None
+
+
+class Engine(Handle):
+    """One ttsdec handle bound to one device."""
+
+    PREFIX = "ttsdec"
+
+    def __init__(self, dims: EngineDims, device: Optional[torch.device]):
+        super().__init__(dims, dims.to_c(), device)
+        # exact-shape workspaces of the decode steps and the postnet, keyed by (B, L) / (B, T) (a captured graph holds the pointer)
+        self._step_ws: Dict[Tuple[int, int], Tensor] = {}
+        self._pws: Dict[Tuple[int, int], Tensor] = {}
 
     def workspace_bytes(self, B: int, L: int) -> int:
         return self._lib.ttsdec_workspace_bytes(self._h, B, L)
 
     def postnet_workspace_bytes(self, B: int, T: int) -> int:
         return self._lib.ttsdec_postnet_workspace_bytes(self._h, B, T)
-
-    # ---- arithmetic of the LSTM gate GEMMs ----
-    def set_precision(self, mode: str) -> None:
-        """"f32" (exact fp32 matrix instruction) or "split_f16" (hi/lo fp16 planes, 3 products)."""
-        code = {"f32": _lib.PREC_F32, "split_f16": _lib.PREC_SPLIT_F16}[mode]
-        _lib.check(self._lib.ttsdec_set_precision(self._h, code), "ttsdec_set_precision")
-
-    def precision(self) -> str:
-        return {_lib.PREC_F32: "f32", _lib.PREC_SPLIT_F16: "split_f16"}[self._lib.ttsdec_get_precision(self._h)]
 
     # ---- tuning / measurement options (include/ttsdec.h TTSDEC_OPT_*; -1 = library default) ----
     def set_option(self, name: str, value: int) -> None:
@@ -162,36 +236,6 @@ class Engine:
         return int(v.value)
 
     # ---- weights ----
-    def pack(self, tensors: Sequence[Optional[Tensor]]) -> Tensor:
-        """tensors: in TTSDEC_W_* order (None = not owned by the calling module)."""
-        n = self.num_weight_tensors()
-        if len(tensors) != n:
-            raise ValueError(f"expected {n} weight tensors, got {len(tensors)}")
-        keep: List[Tensor] = []
-        arr = (C.c_void_p * n)()
-        for i, t in enumerate(tensors):
-            if t is None:
-                arr[i] = None
-                continue
-            _require_device(t, "weights")
-            tc = t.detach()
-            if tc.dtype != torch.float32 or not tc.is_contiguous():
-                tc = tc.to(torch.float32).contiguous()
-            keep.append(tc)
-            arr[i] = tc.data_ptr()
-        with torch.cuda.device(self.device):
-            blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=self.device)
-            rc = self._lib.ttsdec_pack_weights(self._h, arr, n, blob.data_ptr(), _stream(self.device))
-        _lib.check(rc, "ttsdec_pack_weights", self._h)
-        self.blob = blob
-        self._fingerprint = weights_fingerprint(tensors)
-        del keep  # stream-ordered: the caching allocator keeps the memory valid for the enqueued copies
-        return blob
-
-    def ensure_packed(self, tensors: Sequence[Optional[Tensor]]) -> None:
-        if self.blob is None or self._fingerprint != weights_fingerprint(tensors):
-            self.pack(tensors)
-
     def bind(self, blob: Tensor) -> None:
         """Adopt a packed blob produced elsewhere (e.g. broadcast from rank 0)."""
         _require_device(blob, "blob")
@@ -199,18 +243,18 @@ class Engine:
             raise ValueError("blob size does not match this engine's dims")
         with torch.cuda.device(self.device):
             torch.cuda.current_stream(self.device).synchronize()  # the blob must be complete: its header is read back
-            _lib.check(self._lib.ttsdec_bind_weights(self._h, blob.data_ptr()), "ttsdec_bind_weights", self._h)
+            self._err(self._lib.ttsdec_bind_weights(self._h, blob.data_ptr()), "ttsdec_bind_weights")
         self.blob = blob
         self._fingerprint = None
 
     # ---- workspaces ----
-    def workspace(self, B: int, L: int) -> Tensor:
+    def step_workspace(self, B: int, L: int) -> Tensor:
         key = (B, L)
-        ws = self._ws.get(key)
+        ws = self._step_ws.get(key)
         if ws is None:
-            self._ws.clear()
+            self._step_ws.clear()
             ws = torch.empty(self.workspace_bytes(B, L), dtype=torch.uint8, device=self.device)
-            self._ws[key] = ws
+            self._step_ws[key] = ws
         return ws
 
     def postnet_workspace(self, B: int, T: int) -> Tensor:
@@ -245,7 +289,7 @@ class Engine:
         _require_device(memory, "memory")
         B, L, _ = memory.shape
         t_stride = w.shape[1]
-        ws = self.workspace(B, L)
+        ws = self.step_workspace(B, L)
         with torch.cuda.device(self.device):
             rc = self._lib.ttsdec_decode(
                 self._h, memory.data_ptr(), B, L, t_begin, n_steps, t_stride,
@@ -254,7 +298,7 @@ class Engine:
                 y.data_ptr(), s.data_ptr(), w.data_ptr(), t_out.data_ptr(),
                 ws.data_ptr(), ws.numel(), _stream(self.device),
             )
-        _lib.check(rc, "ttsdec_decode", self._h)
+        self._err(rc, "ttsdec_decode")
 
     def postnet(self, y: Tensor, precision: int = _lib.POSTNET_F32) -> Tensor:
         _require_device(y, "y")
@@ -265,21 +309,21 @@ class Engine:
             rc = self._lib.ttsdec_postnet(
                 self._h, y.data_ptr(), B, T, precision, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device)
             )
-        _lib.check(rc, "ttsdec_postnet", self._h)
+        self._err(rc, "ttsdec_postnet")
         return out
 
     def cell_step(self, x, memory, w, ctx, h_att, c_att, h_dec, c_dec, dropout_mode, masks, seed, step) -> Tensor:
         _require_device(memory, "memory")
         B, L, _ = memory.shape
         x_dec = torch.empty(B, self.dims.cell_output, dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, L)
+        ws = self.step_workspace(B, L)
         with torch.cuda.device(self.device):
             rc = self._lib.ttsdec_cell_step(
                 self._h, x.data_ptr(), memory.data_ptr(), B, L, w.data_ptr(), ctx.data_ptr(), h_att.data_ptr(),
                 c_att.data_ptr(), h_dec.data_ptr(), c_dec.data_ptr(), dropout_mode, _ptr(masks),
                 seed & 0xFFFFFFFFFFFFFFFF, step, x_dec.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device),
             )
-        _lib.check(rc, "ttsdec_cell_step", self._h)
+        self._err(rc, "ttsdec_cell_step")
         return x_dec
 
     def profile_step(self, memory: Tensor, iters: int, dropout_mode: int, masks: Optional[Tensor], seed: int):
@@ -289,7 +333,7 @@ class Engine:
         y = torch.empty(B, 2 * d.r, d.d_mel, device=self.device)  # (the profiled step is step 1 of 2)
         s = torch.empty(B, 2 * d.r, device=self.device)
         w = torch.empty(B, 2, L, device=self.device)
-        ws = self.workspace(B, L)
+        ws = self.step_workspace(B, L)
         ms = (C.c_float * 16)()
         names = (C.c_char_p * 16)()
         nk = C.c_int(0)
@@ -299,7 +343,7 @@ class Engine:
                 y.data_ptr(), s.data_ptr(), w.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device),
                 ms, names, 16, C.byref(nk),
             )
-        _lib.check(rc, "ttsdec_profile_step", self._h)
+        self._err(rc, "ttsdec_profile_step")
         return {names[i].decode(): float(ms[i]) for i in range(nk.value)}
 
 
@@ -312,7 +356,7 @@ class Engine:
         s = torch.empty(B, n_steps * d.r, device=self.device)
         w = torch.empty(B, n_steps, L, device=self.device)
         t_out = torch.zeros(2, dtype=torch.int32, device=self.device)
-        ws = self.workspace(B, L)
+        ws = self.step_workspace(B, L)
         ms = (C.c_float * 16)()
         names = (C.c_char_p * 16)()
         nk = C.c_int(0)
@@ -323,36 +367,39 @@ class Engine:
                 y.data_ptr(), s.data_ptr(), w.data_ptr(), t_out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device),
                 ms, names, 16, C.byref(nk), C.byref(step),
             )
-        _lib.check(rc, "ttsdec_profile_loop", self._h)
+        self._err(rc, "ttsdec_profile_loop")
         return {names[i].decode(): float(ms[i]) for i in range(nk.value)}, float(step.value)
 
 
 class EngineCache:
-    """Per-device engines of one module.  Lives in the module's __dict__ but is
-    dropped on pickling / deepcopy, and shared (keyed by device) by the replicas
-    nn.DataParallel makes (train_util.py:215 in the reference)."""
+    """Per-device engines of one module, made by ``engine_cls(dims, device)`` and rebuilt when the dims change.  Lives in the
+    module's __dict__ but is dropped on pickling / deepcopy, and shared (keyed by device) by the replicas nn.DataParallel
+    makes (train_util.py:215 in the reference)."""
 
-    def __init__(self):
-        self._by_dev: Dict[int, Engine] = {}
+    def __init__(self, engine_cls=Engine):
+        self.engine_cls = engine_cls
+        self._by_dev: Dict[int, Tuple[object, Handle]] = {}  # device index -> (dims it was built for, engine)
 
-    def get(self, dims: EngineDims, device: torch.device) -> Engine:
+    def get(self, dims, device: torch.device):
         idx = device.index if device.index is not None else torch.cuda.current_device()
-        e = self._by_dev.get(idx)
-        if e is None or e.dims != dims:
-            e = Engine(dims, torch.device("cuda", idx))
-            self._by_dev[idx] = e
-        return e
+        built = self._by_dev.get(idx)
+        if built is None or built[0] != dims:
+            built = self._by_dev[idx] = (copy.deepcopy(dims), self.engine_cls(dims, torch.device("cuda", idx)))
+        return built[1]
+
+    def engines(self) -> List[Handle]:
+        return [e for _, e in self._by_dev.values()]
 
     def clear(self) -> None:
-        for e in self._by_dev.values():
+        for e in self.engines():
             e.close()
         self._by_dev.clear()
 
     def __getstate__(self):
-        return {}
+        return {"engine_cls": self.engine_cls}
 
     def __setstate__(self, state):
-        self._by_dev = {}
+        self.engine_cls, self._by_dev = state["engine_cls"], {}
 
     def __deepcopy__(self, memo):
-        return EngineCache()
+        return EngineCache(self.engine_cls)

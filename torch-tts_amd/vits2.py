@@ -22,7 +22,6 @@ the [B, C, T] tensors of the reference API are transposed here.  Training (gradi
 conditioning are outside the path and raise."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, List, Optional
 
@@ -30,7 +29,36 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import PackedWeightsMixin, _require_device, _stream, weights_fingerprint
+from .engine import EngineCache, Handle, PackedWeightsMixin, _require_device, _stream
+
+
+def speaker_rows(g: Optional[torch.Tensor], B: int, gin_channels: int, owner: str) -> Optional[torch.Tensor]:
+    """g as the C ABI takes it: [B, gin] fp32 from the reference's [B, gin, 1] (models.py: g = emb_g(sid).unsqueeze(-1));
+    owner names the module in the messages ("a generator")."""
+    if g is None:
+        return None
+    if not gin_channels:
+        raise ValueError(f"g was given to {owner} built with gin_channels = 0")
+    _require_device(g, "g")
+    if g.dim() == 3:
+        if g.shape[2] != 1:
+            raise NotImplementedError("a time-varying g [B, gin, T] is outside the HIP path (the reference's callers pass [B, gin, 1])")
+        g = g[:, :, 0]
+    if tuple(g.shape) != (B, gin_channels):
+        raise ValueError(f"g must be [B, gin_channels(, 1)] = [{B}, {gin_channels}(, 1)], got {tuple(g.shape)}")
+    return g.to(torch.float32).contiguous()
+
+
+def inference_only(module: nn.Module, owner: str, x: Optional[torch.Tensor] = None, *, fp32: bool = False) -> None:
+    """The guard in front of a module's HIP path: no autograd through the parameters (or x); with x given, x and the parameters
+    on a ROCm device, and with fp32 also torch.float32.  owner names the module in the messages ("generator")."""
+    # (parameters() is walked only where a check needs it: under no_grad the text encoder's and the flow's guard costs nothing)
+    if x is not None and (not x.is_cuda or any(not p.is_cuda for p in module.parameters())):
+        raise NotImplementedError(f"the HIP {owner} runs on a ROCm device only: move the module and its input there")
+    if fp32 and (x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in module.parameters())):
+        raise NotImplementedError(f"the HIP {owner} is exact fp32: input and parameters must be torch.float32")
+    if torch.is_grad_enabled() and ((x is not None and x.requires_grad) or any(p.requires_grad for p in module.parameters())):
+        raise NotImplementedError(f"the HIP {owner} is inference-only: call under torch.no_grad()")
 
 
 class _LayerNorm(nn.Module):  # modules.LayerNorm: parameters gamma / beta
@@ -97,105 +125,20 @@ class Encoder(nn.Module):
         return out
 
 
-class VitsEngine:
+class VitsEngine(Handle):
     """One ttsvits handle on one device."""
 
+    PREFIX = "ttsvits"
+
     def __init__(self, dims: Dict[str, int], device: torch.device):
-        self._lib = _lib.load()
-        self.device = device
-        self.dims = dict(gin_channels=0, cond_layer_idx=0)
-        self.dims.update(dims)
-        dims = self.dims
-        h = C.c_void_p()
-        d = _lib.VitsDims(*[int(dims[n]) for n, _ in _lib.VitsDims._fields_])
-        with torch.cuda.device(device):  # the handle binds to the device current at create
-            _lib.check(self._lib.ttsvits_create(C.byref(d), C.byref(h)), "ttsvits_create")
-        self._h = h
-        self.blob: Optional[torch.Tensor] = None
-        self._fingerprint = None
-        self._ws: Dict = {}
+        dims = dict(dict(gin_channels=0, cond_layer_idx=0), **dims)
+        super().__init__(dims, _lib.VitsDims(*[int(dims[n]) for n, _ in _lib.VitsDims._fields_]), device)
         self.status = torch.zeros(1, dtype=torch.int32, device=device)  # bit 0: an id outside the table (ttsvits_text_encoder)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ttsvits_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _err(self, rc, what):
-        if rc != _lib.OK:
-            raise _lib.TtsdecError(rc, what, self._lib.ttsvits_last_hip_error(self._h).decode())
-
-    def num_weight_tensors(self) -> int:
-        return int(self._lib.ttsvits_num_weight_tensors(self._h))
-
-    def set_precision(self, mode: str) -> None:
-        """"f32" (exact, the modules' default) or "split_f16": arithmetic of every GEMM (include/ttsdec.h ttsvits_set_precision)."""
-        self._err(self._lib.ttsvits_set_precision(self._h, {"f32": _lib.PREC_F32, "split_f16": _lib.PREC_SPLIT_F16}[mode]), "ttsvits_set_precision")
-
-    def precision(self) -> str:
-        return {_lib.PREC_F32: "f32", _lib.PREC_SPLIT_F16: "split_f16"}[int(self._lib.ttsvits_get_precision(self._h))]
-
-    def ensure_packed(self, tensors, key_tensors=None) -> None:
-        """tensors: the list the C ABI expects, or a callable producing it (called only when a repack is
-        needed); key_tensors: the parameters whose identity / version decide that (default: the list itself -
-        derived tensors such as weight-normed weights are new objects on every call and must not be the key)."""
-        fp = weights_fingerprint([t for t in (key_tensors if key_tensors is not None else tensors) if t is not None])
-        if self.blob is not None and fp == self._fingerprint:
-            return
-        if callable(tensors):
-            tensors = tensors()
-        n = len(tensors)
-        assert n == self.num_weight_tensors(), (n, self.num_weight_tensors())
-        arr = (C.c_void_p * n)()
-        keep = []
-        for i, t in enumerate(tensors):
-            if t is None:
-                arr[i] = None
-                continue
-            _require_device(t, "vits2 weights")
-            tc = t.detach().to(torch.float32).contiguous()
-            keep.append(tc)
-            arr[i] = tc.data_ptr()
-        with torch.cuda.device(self.device):
-            blob = torch.empty(self._lib.ttsvits_packed_bytes(self._h), dtype=torch.uint8, device=self.device)
-            rc = self._lib.ttsvits_pack_weights(self._h, arr, n, blob.data_ptr(), _stream(self.device))
-            torch.cuda.current_stream(self.device).synchronize()  # `keep` must outlive the packing kernels
-        self._err(rc, "ttsvits_pack_weights")
-        self.blob, self._fingerprint = blob, fp
-
-    def _workspace(self, kind: str, nbytes: int) -> torch.Tensor:
-        ws = self._ws.get(kind)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._ws[kind] = ws
-        return ws
-
-    def _speaker(self, g: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
-        """g as the C ABI takes it: [B, gin] fp32 from the reference's [B, gin, 1] (models.py: g = emb_g(sid).unsqueeze(-1))."""
-        if g is None:
-            return None
-        gin = self.dims["gin_channels"]
-        if not gin:
-            raise ValueError("g was given to a module built with gin_channels = 0")
-        _require_device(g, "g")
-        if g.dim() == 3:
-            if g.shape[2] != 1:
-                raise NotImplementedError("a time-varying g [B, gin, T] is outside the HIP path (the reference's callers pass [B, gin, 1])")
-            g = g[:, :, 0]
-        if tuple(g.shape) != (B, gin):
-            raise ValueError(f"g must be [B, gin_channels(, 1)] = [{B}, {gin}(, 1)], got {tuple(g.shape)}")
-        return g.to(torch.float32).contiguous()
 
     def text_encoder(self, ids: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor] = None):
         _require_device(ids, "ids")
         B, T = ids.shape
-        g = self._speaker(g, B)
+        g = speaker_rows(g, B, self.dims["gin_channels"], "a module")
         ids = ids.to(torch.int64).contiguous()
         self.status.zero_()
         lens = lengths.to(device=self.device, dtype=torch.int32).contiguous()
@@ -203,7 +146,7 @@ class VitsEngine:
         x = torch.empty(B, T, H, device=self.device)
         m = torch.empty(B, T, I, device=self.device)
         logs = torch.empty(B, T, I, device=self.device)
-        ws = self._workspace("te", self._lib.ttsvits_text_encoder_workspace_bytes(self._h, B, T))
+        ws = self.workspace("te", self._lib.ttsvits_text_encoder_workspace_bytes(self._h, B, T))
         with torch.cuda.device(self.device):
             rc = self._lib.ttsvits_text_encoder(self._h, ids.data_ptr(), lens.data_ptr(), g.data_ptr() if g is not None else None, B, T,
                                                 x.data_ptr(), m.data_ptr(), logs.data_ptr(),
@@ -219,11 +162,11 @@ class VitsEngine:
         """z_cl [B, T, inter] channel-last."""
         _require_device(z_cl, "z")
         B, T, _ = z_cl.shape
-        g = self._speaker(g, B)
+        g = speaker_rows(g, B, self.dims["gin_channels"], "a module")
         z_cl = z_cl.to(torch.float32).contiguous()
         lens = lengths.to(device=self.device, dtype=torch.int32).contiguous()
         out = torch.empty_like(z_cl)
-        ws = self._workspace("flow", self._lib.ttsvits_flow_workspace_bytes(self._h, B, T))
+        ws = self.workspace("flow", self._lib.ttsvits_flow_workspace_bytes(self._h, B, T))
         with torch.cuda.device(self.device):
             rc = self._lib.ttsvits_flow_reverse(self._h, z_cl.data_ptr(), lens.data_ptr(), g.data_ptr() if g is not None else None, B, T,
                                                 out.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -235,38 +178,16 @@ class VitsEngine:
         """The forward direction (ttsvits_flow_forward) on z_cl [B, T, inter] channel-last; same workspace as flow_reverse."""
         _require_device(z_cl, "z")
         B, T, _ = z_cl.shape
-        g = self._speaker(g, B)
+        g = speaker_rows(g, B, self.dims["gin_channels"], "a module")
         z_cl = z_cl.to(torch.float32).contiguous()
         lens = lengths.to(device=self.device, dtype=torch.int32).contiguous()
         out = torch.empty_like(z_cl)
-        ws = self._workspace("flow", self._lib.ttsvits_flow_workspace_bytes(self._h, B, T))
+        ws = self.workspace("flow", self._lib.ttsvits_flow_workspace_bytes(self._h, B, T))
         with torch.cuda.device(self.device):
             rc = self._lib.ttsvits_flow_forward(self._h, z_cl.data_ptr(), lens.data_ptr(), g.data_ptr() if g is not None else None, B, T,
                                                 out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
         self._err(rc, "ttsvits_flow_forward")
         return out
-
-
-class _EngCache:
-    def __init__(self):
-        self.by_dev: Dict[int, VitsEngine] = {}
-
-    def __getstate__(self):
-        return {}
-
-    def __setstate__(self, st):
-        self.by_dev = {}
-
-    def __deepcopy__(self, memo):
-        return _EngCache()
-
-    def get(self, dims, device) -> VitsEngine:
-        key = device.index if device.index is not None else torch.cuda.current_device()
-        eng = self.by_dev.get(key)
-        if eng is None:
-            eng = VitsEngine(dims, torch.device("cuda", key))
-            self.by_dev[key] = eng
-        return eng
 
 
 _DEFAULT_FLOW = dict(flow_hidden=4, flow_kernel=1, flow_wn_layers=1, n_flows=0, flow_tf_layers=0, flow_tf_heads=1, flow_tf_kernel=1)
@@ -283,7 +204,7 @@ class TextEncoder(PackedWeightsMixin, nn.Module):
         self.encoder = Encoder(hidden_channels, filter_channels, n_heads, n_layers, kernel_size, p_dropout, gin_channels=gin_channels)  # models.py:358-366
         self.proj = nn.Conv1d(hidden_channels, out_channels * 2, 1)
         self.precision = "f32"  # arithmetic of the GEMMs: "f32" (the reference's own: exact fp32, default) or "split_f16" (two fp16 planes, opt-in: ~1.8x faster)
-        self._engines = _EngCache()
+        self._engines = EngineCache(VitsEngine)
 
     def _dims(self):
         d = dict(n_vocab=self.n_vocab, inter_channels=self.out_channels, hidden_channels=self.hidden_channels, filter_channels=self.filter_channels,
@@ -300,8 +221,7 @@ class TextEncoder(PackedWeightsMixin, nn.Module):
 
     def forward_cl(self, x, x_lengths, g=None):
         """forward's x, m, logs channel-last [B, T, C] (the library's own layout; ``infer`` chains it)."""
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("the HIP text encoder is inference-only: call under torch.no_grad()")
+        inference_only(self, "text encoder")
         eng = self._engines.get(self._dims(), x.device)
         eng.set_precision(self.precision)
         spk = [self.encoder.spk_emb_linear.weight, self.encoder.spk_emb_linear.bias] if self.gin_channels else []
@@ -376,7 +296,7 @@ class ResidualCouplingTransformersBlock(PackedWeightsMixin, nn.Module):
                                                                 gin_channels=gin_channels, mean_only=True))
             self.flows.append(_Flip())
         self.precision = "f32"  # arithmetic of the GEMMs: "f32" (the reference's own: exact fp32, default) or "split_f16" (two fp16 planes, opt-in: ~1.8x faster)
-        self._engines = _EngCache()
+        self._engines = EngineCache(VitsEngine)
 
     def _dims(self):
         return dict(n_vocab=1, inter_channels=self.channels, hidden_channels=4, filter_channels=4, n_heads=1, n_layers=0, kernel_size=1, window_size=0,
@@ -403,8 +323,7 @@ class ResidualCouplingTransformersBlock(PackedWeightsMixin, nn.Module):
         return self._engine(x_cl).flow_forward(x_cl, lengths, g)
 
     def _engine(self, z_cl) -> VitsEngine:
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("the HIP flow is inference-only: call under torch.no_grad()")
+        inference_only(self, "flow")
         eng = self._engines.get(self._dims(), z_cl.device)
         eng.set_precision(self.precision)
 
@@ -463,13 +382,12 @@ class ResBlock1(nn.Module):
         return out
 
 
-class GenEngine:
+class GenEngine(Handle):
     """One ttsgen handle on one device."""
 
+    PREFIX = "ttsgen"
+
     def __init__(self, dims: Dict, device: torch.device):
-        self._lib = _lib.load()
-        self.device = device
-        self.dims = dims
         d = _lib.GenDims()
         d.initial_channel, d.upsample_initial_channel = dims["initial_channel"], dims["upsample_initial_channel"]
         d.n_up, d.n_res = len(dims["upsample_rates"]), len(dims["resblock_kernel_sizes"])
@@ -485,68 +403,17 @@ class GenEngine:
                 d.res_dilations[j][l] = dl
         d.resblock = 1 if str(dims["resblock"]) == "1" else 2
         d.gin_channels = dims["gin_channels"]
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            rc = self._lib.ttsgen_create(C.byref(d), C.byref(h))
-        if rc == _lib.ERR_DIMS:
-            raise NotImplementedError(f"these generator dimensions are not built in the HIP library (include/ttsdec.h ttsgen_dims): {dims}")
-        _lib.check(rc, "ttsgen_create")
-        self._h = h
-        self.blob: Optional[torch.Tensor] = None
-        self._fingerprint = None
-        self._ws: Optional[torch.Tensor] = None
+        super().__init__(dims, d, device)
         self.up_total = math.prod(dims["upsample_rates"])
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ttsgen_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _err(self, rc, what):
-        if rc != _lib.OK:
-            raise _lib.TtsdecError(rc, what, self._lib.ttsgen_last_hip_error(self._h).decode())
-
-    def ensure_packed(self, tensors, key_tensors) -> None:
-        fp = weights_fingerprint(list(key_tensors))
-        if self.blob is not None and fp == self._fingerprint:
-            return
-        tensors = tensors()
-        n = len(tensors)
-        assert n == int(self._lib.ttsgen_num_weight_tensors(self._h)), (n, int(self._lib.ttsgen_num_weight_tensors(self._h)))
-        arr = (C.c_void_p * n)()
-        keep = []
-        for i, t in enumerate(tensors):
-            _require_device(t, "generator weights")
-            tc = t.detach().to(torch.float32).contiguous()
-            keep.append(tc)
-            arr[i] = tc.data_ptr()
-        with torch.cuda.device(self.device):
-            blob = torch.empty(self._lib.ttsgen_packed_bytes(self._h), dtype=torch.uint8, device=self.device)
-            rc = self._lib.ttsgen_pack_weights(self._h, arr, n, blob.data_ptr(), _stream(self.device))
-            torch.cuda.current_stream(self.device).synchronize()  # `keep` must outlive the packing kernels
-        self._err(rc, "ttsgen_pack_weights")
-        self.blob, self._fingerprint = blob, fp
-
-    def workspace(self, B: int, T: int) -> torch.Tensor:
-        nbytes = int(self._lib.ttsgen_workspace_bytes(self._h, B, T))
-        if nbytes == 0:
-            raise NotImplementedError(f"one utterance of {T} frames exceeds the generator's 2-GiB group bound")
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
 
     def forward(self, z_cl: torch.Tensor, g: Optional[torch.Tensor], n_stages: Optional[int] = None) -> torch.Tensor:
         """z_cl [B, T, C] channel-last fp32 -> [B, T * prod(u)]; n_stages (test aid): the activated output of that many stages,
         [B * T_s, C_s], read from the workspace (ttsgen_forward_stages)."""
         B, T, _ = z_cl.shape
-        ws = self.workspace(B, T)
+        nbytes = int(self._lib.ttsgen_workspace_bytes(self._h, B, T))
+        if nbytes == 0:
+            raise NotImplementedError(f"one utterance of {T} frames exceeds the generator's 2-GiB group bound")
+        ws = self.workspace("forward", nbytes)
         gp = g.data_ptr() if g is not None else None
         with torch.cuda.device(self.device):
             if n_stages is None:
@@ -560,19 +427,6 @@ class GenEngine:
         Ts = T * math.prod(rates)
         Cs = self.dims["upsample_initial_channel"] >> n_stages
         return ws[: B * Ts * Cs * 4].view(torch.float32).view(B, Ts, Cs).clone()
-
-
-class _GenEngCache(_EngCache):
-    def get(self, dims, device) -> GenEngine:
-        key = device.index if device.index is not None else torch.cuda.current_device()
-        eng = self.by_dev.get(key)
-        if eng is None:
-            eng = GenEngine(dims, torch.device("cuda", key))
-            self.by_dev[key] = eng
-        return eng
-
-    def __deepcopy__(self, memo):
-        return _GenEngCache()
 
 
 class Generator(PackedWeightsMixin, nn.Module):
@@ -609,7 +463,7 @@ class Generator(PackedWeightsMixin, nn.Module):
         self.gin_channels = gin_channels
         if gin_channels != 0:
             self.cond = nn.Conv1d(gin_channels, upsample_initial_channel, 1)
-        self._engines = _GenEngCache()
+        self._engines = EngineCache(GenEngine)
 
     def remove_weight_norm(self):
         for l in self.ups:
@@ -631,29 +485,13 @@ class Generator(PackedWeightsMixin, nn.Module):
         return out
 
     def _engine(self, x: torch.Tensor) -> GenEngine:
-        if not x.is_cuda or any(not p.is_cuda for p in self.parameters()):
-            raise NotImplementedError("the HIP generator runs on a ROCm device only: move the module and its input there")
-        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
-            raise NotImplementedError("the HIP generator is exact fp32: input and parameters must be torch.float32")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("the HIP generator is inference-only: call under torch.no_grad()")
+        inference_only(self, "generator", x, fp32=True)
         eng = self._engines.get(self._cfg, x.device)
         eng.ensure_packed(self.weight_tensors, key_tensors=list(self.parameters()))
         return eng
 
     def _speaker(self, g: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
-        if g is None:
-            return None
-        if not self.gin_channels:
-            raise ValueError("g was given to a generator built with gin_channels = 0")
-        _require_device(g, "g")
-        if g.dim() == 3:
-            if g.shape[2] != 1:
-                raise NotImplementedError("a time-varying g [B, gin, T] is outside the HIP path (the reference's callers pass [B, gin, 1])")
-            g = g[:, :, 0]
-        if tuple(g.shape) != (B, self.gin_channels):
-            raise ValueError(f"g must be [B, gin_channels(, 1)] = [{B}, {self.gin_channels}(, 1)], got {tuple(g.shape)}")
-        return g.to(torch.float32).contiguous()
+        return speaker_rows(g, B, self.gin_channels, "a generator")
 
     def forward(self, x, g=None):
         eng = self._engine(x)
@@ -731,72 +569,19 @@ class _Log(nn.Module):  # modules.Log: no parameters (training direction only)
     pass
 
 
-class DurEngine:
+class DurEngine(Handle):
     """One ttsdur handle on one device."""
 
+    PREFIX = "ttsdur"
+
     def __init__(self, dims: Dict, device: torch.device):
-        self._lib = _lib.load()
-        self.device = device
-        self.dims = dims
-        d = _lib.DurDims(*[int(dims[n]) for n, _ in _lib.DurDims._fields_])
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            rc = self._lib.ttsdur_create(C.byref(d), C.byref(h))
-        if rc == _lib.ERR_DIMS:
-            raise NotImplementedError(f"these duration-predictor dimensions are not built in the HIP library (include/ttsdec.h ttsdur_dims): {dims}")
-        _lib.check(rc, "ttsdur_create")
-        self._h = h
-        self.blob: Optional[torch.Tensor] = None
-        self._fingerprint = None
-        self._ws: Optional[torch.Tensor] = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ttsdur_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _err(self, rc, what):
-        if rc != _lib.OK:
-            raise _lib.TtsdecError(rc, what, self._lib.ttsdur_last_hip_error(self._h).decode())
-
-    def ensure_packed(self, tensors: List[torch.Tensor]) -> None:
-        fp = weights_fingerprint(tensors)
-        if self.blob is not None and fp == self._fingerprint:
-            return
-        n = len(tensors)
-        assert n == int(self._lib.ttsdur_num_weight_tensors(self._h)), (n, int(self._lib.ttsdur_num_weight_tensors(self._h)))
-        arr = (C.c_void_p * n)()
-        keep = []
-        for i, t in enumerate(tensors):
-            _require_device(t, "duration predictor weights")
-            tc = t.detach().to(torch.float32).contiguous()
-            keep.append(tc)
-            arr[i] = tc.data_ptr()
-        with torch.cuda.device(self.device):
-            blob = torch.empty(self._lib.ttsdur_packed_bytes(self._h), dtype=torch.uint8, device=self.device)
-            rc = self._lib.ttsdur_pack_weights(self._h, arr, n, blob.data_ptr(), _stream(self.device))
-            torch.cuda.current_stream(self.device).synchronize()  # `keep` must outlive the packing kernels
-        self._err(rc, "ttsdur_pack_weights")
-        self.blob, self._fingerprint = blob, fp
-
-    def workspace(self, B: int, T: int) -> torch.Tensor:
-        nbytes = int(self._lib.ttsdur_workspace_bytes(self._h, B, T))
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
+        super().__init__(dims, _lib.DurDims(*[int(dims[n]) for n, _ in _lib.DurDims._fields_]), device)
 
     def logw(self, x_cl: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor], noise: Optional[torch.Tensor] = None,
              noise_scale: float = 1.0) -> torch.Tensor:
         """x_cl [B, T, C] contiguous fp32, lengths [B] int32 (device), g [B, gin] or None; noise [B, 2, T] (SDP) -> logw [B, T]."""
         B, T, _ = x_cl.shape
-        ws = self.workspace(B, T)
+        ws = self.workspace("logw", int(self._lib.ttsdur_workspace_bytes(self._h, B, T)))
         out = torch.empty(B, T, device=self.device)
         gp = g.data_ptr() if g is not None else None
         with torch.cuda.device(self.device):
@@ -844,41 +629,12 @@ class DurEngine:
         return z_p, m_p, logs_p, attn
 
 
-class _DurEngCache(_EngCache):
-    def get(self, dims, device) -> DurEngine:
-        key = device.index if device.index is not None else torch.cuda.current_device()
-        eng = self.by_dev.get(key)
-        if eng is None:
-            eng = DurEngine(dims, torch.device("cuda", key))
-            self.by_dev[key] = eng
-        return eng
-
-    def __deepcopy__(self, memo):
-        return _DurEngCache()
-
-
 class _DurationBase(PackedWeightsMixin, nn.Module):
     def _check(self, x: torch.Tensor) -> None:
-        if not x.is_cuda or any(not p.is_cuda for p in self.parameters()):
-            raise NotImplementedError("the HIP duration predictor runs on a ROCm device only: move the module and its input there")
-        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
-            raise NotImplementedError("the HIP duration predictor is exact fp32: input and parameters must be torch.float32")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("the HIP duration predictor is inference-only: call under torch.no_grad()")
+        inference_only(self, "duration predictor", x, fp32=True)
 
     def _speaker(self, g: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
-        if g is None:
-            return None
-        if not self.gin_channels:
-            raise ValueError("g was given to a duration predictor built with gin_channels = 0")
-        _require_device(g, "g")
-        if g.dim() == 3:
-            if g.shape[2] != 1:
-                raise NotImplementedError("a time-varying g [B, gin, T] is outside the HIP path (the reference's callers pass [B, gin, 1])")
-            g = g[:, :, 0]
-        if tuple(g.shape) != (B, self.gin_channels):
-            raise ValueError(f"g must be [B, gin_channels(, 1)] = [{B}, {self.gin_channels}(, 1)], got {tuple(g.shape)}")
-        return g.to(torch.float32).contiguous()
+        return speaker_rows(g, B, self.gin_channels, "a duration predictor")
 
     def _engine(self, device) -> DurEngine:
         eng = self._engines.get(self._cfg, device)
@@ -929,7 +685,7 @@ class StochasticDurationPredictor(_DurationBase):
             self.cond = nn.Conv1d(gin_channels, filter_channels, 1)
         self._cfg = dict(kind=_lib.DUR_SDP, in_channels=in_channels, filter_channels=filter_channels, kernel_size=kernel_size, n_flows=n_flows,
                          gin_channels=gin_channels)
-        self._engines = _DurEngCache()
+        self._engines = EngineCache(DurEngine)
 
     def weight_tensors(self) -> List[torch.Tensor]:
         """ttsdur_pack_weights' order (include/ttsdec.h): the reverse path's parameters; flows.1 and post_* are not read."""
@@ -980,7 +736,7 @@ class DurationPredictor(_DurationBase):
             self.cond = nn.Conv1d(gin_channels, in_channels, 1)
         self._cfg = dict(kind=_lib.DUR_DP, in_channels=in_channels, filter_channels=filter_channels, kernel_size=kernel_size, n_flows=0,
                          gin_channels=gin_channels)
-        self._engines = _DurEngCache()
+        self._engines = EngineCache(DurEngine)
 
     def weight_tensors(self) -> List[torch.Tensor]:
         out = [self.conv_1.weight, self.conv_1.bias, self.norm_1.gamma, self.norm_1.beta, self.conv_2.weight, self.conv_2.bias,
@@ -1037,77 +793,20 @@ def infer(net_g, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_sc
 # ---------------------------------------------------------------------------------------------------------------------------
 # Posterior encoder (models.py:858-897) through ttspost_* and voice conversion (SynthesizerTrn.voice_conversion, models.py:1328-1336)
 # ---------------------------------------------------------------------------------------------------------------------------
-class PostEngine:
+class PostEngine(Handle):
     """One ttspost handle on one device."""
 
+    PREFIX = "ttspost"
+
     def __init__(self, dims: Dict, device: torch.device):
-        self._lib = _lib.load()
-        self.device = device
-        self.dims = dims
-        d = _lib.PostDims(*[int(dims[n]) for n, _ in _lib.PostDims._fields_])
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            rc = self._lib.ttspost_create(C.byref(d), C.byref(h))
-        if rc == _lib.ERR_DIMS:
-            raise NotImplementedError(f"these posterior-encoder dimensions are not built in the HIP library (include/ttsdec.h ttspost_dims): {dims}")
-        _lib.check(rc, "ttspost_create")
-        self._h = h
-        self.blob: Optional[torch.Tensor] = None
-        self._fingerprint = None
-        self._ws: Optional[torch.Tensor] = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ttspost_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _err(self, rc, what):
-        if rc != _lib.OK:
-            raise _lib.TtsdecError(rc, what, self._lib.ttspost_last_hip_error(self._h).decode())
-
-    def set_precision(self, mode: str) -> None:
-        self._err(self._lib.ttspost_set_precision(self._h, {"f32": _lib.PREC_F32, "split_f16": _lib.PREC_SPLIT_F16}[mode]), "ttspost_set_precision")
-
-    def ensure_packed(self, tensors, key_tensors) -> None:
-        fp = weights_fingerprint(list(key_tensors))
-        if self.blob is not None and fp == self._fingerprint:
-            return
-        tensors = tensors()
-        n = len(tensors)
-        assert n == int(self._lib.ttspost_num_weight_tensors(self._h)), (n, int(self._lib.ttspost_num_weight_tensors(self._h)))
-        arr = (C.c_void_p * n)()
-        keep = []
-        for i, t in enumerate(tensors):
-            _require_device(t, "posterior encoder weights")
-            tc = t.detach().to(torch.float32).contiguous()
-            keep.append(tc)
-            arr[i] = tc.data_ptr()
-        with torch.cuda.device(self.device):
-            blob = torch.empty(self._lib.ttspost_packed_bytes(self._h), dtype=torch.uint8, device=self.device)
-            rc = self._lib.ttspost_pack_weights(self._h, arr, n, blob.data_ptr(), _stream(self.device))
-            torch.cuda.current_stream(self.device).synchronize()  # `keep` must outlive the packing kernels
-        self._err(rc, "ttspost_pack_weights")
-        self.blob, self._fingerprint = blob, fp
-
-    def workspace(self, B: int, T: int) -> torch.Tensor:
-        nbytes = int(self._lib.ttspost_workspace_bytes(self._h, B, T))
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
+        super().__init__(dims, _lib.PostDims(*[int(dims[n]) for n, _ in _lib.PostDims._fields_]), device)
 
     def forward(self, y: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor], eps: torch.Tensor):
         """y [B, spec, T] contiguous fp32, lengths [B] int32 (device), g [B, gin] or None, eps [B, inter, >= T] -> z, m, logs
         [B, T, inter] channel-last."""
         B, _, T = y.shape
         I = self.dims["inter_channels"]
-        ws = self.workspace(B, T)
+        ws = self.workspace("forward", int(self._lib.ttspost_workspace_bytes(self._h, B, T)))
         z = torch.empty(B, T, I, device=self.device)
         m = torch.empty_like(z)
         logs = torch.empty_like(z)
@@ -1117,19 +816,6 @@ class PostEngine:
                                            _stream(self.device))
         self._err(rc, "ttspost_forward")
         return z, m, logs
-
-
-class _PostEngCache(_EngCache):
-    def get(self, dims, device) -> PostEngine:
-        key = device.index if device.index is not None else torch.cuda.current_device()
-        eng = self.by_dev.get(key)
-        if eng is None:
-            eng = PostEngine(dims, torch.device("cuda", key))
-            self.by_dev[key] = eng
-        return eng
-
-    def __deepcopy__(self, memo):
-        return _PostEngCache()
 
 
 class PosteriorEncoder(PackedWeightsMixin, nn.Module):
@@ -1150,32 +836,15 @@ class PosteriorEncoder(PackedWeightsMixin, nn.Module):
         self.precision = "f32"  # arithmetic of the GEMMs: "f32" (the reference's own: exact fp32, default) or "split_f16" (two fp16 planes, opt-in)
         self._cfg = dict(spec_channels=in_channels, inter_channels=out_channels, hidden_channels=hidden_channels, kernel_size=kernel_size,
                          n_layers=n_layers, gin_channels=gin_channels)
-        self._engines = _PostEngCache()
+        self._engines = EngineCache(PostEngine)
 
     def weight_tensors(self) -> List[torch.Tensor]:
         """ttspost_pack_weights' order (include/ttsdec.h), weight-normed convs as their effective weights."""
         return [self.pre.weight, self.pre.bias] + self.enc.weight_tensors() + [self.proj.weight, self.proj.bias]
 
-    def _speaker(self, g: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
-        if g is None:
-            return None
-        if not self.gin_channels:
-            raise ValueError("g was given to a posterior encoder built with gin_channels = 0")
-        _require_device(g, "g")
-        if g.dim() == 3:
-            if g.shape[2] != 1:
-                raise NotImplementedError("a time-varying g [B, gin, T] is outside the HIP path (the reference's callers pass [B, gin, 1])")
-            g = g[:, :, 0]
-        if tuple(g.shape) != (B, self.gin_channels):
-            raise ValueError(f"g must be [B, gin_channels(, 1)] = [{B}, {self.gin_channels}(, 1)], got {tuple(g.shape)}")
-        return g.to(torch.float32).contiguous()
-
     def forward_cl(self, x, x_lengths, g=None, *, noise=None):
         """forward on the reference's x [B, spec, T] -> z, m, logs channel-last [B, T, out_channels] (``voice_conversion`` chains it)."""
-        if not x.is_cuda or any(not p.is_cuda for p in self.parameters()):
-            raise NotImplementedError("the HIP posterior encoder runs on a ROCm device only: move the module and its input there")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("the HIP posterior encoder is inference-only: call under torch.no_grad()")
+        inference_only(self, "posterior encoder", x)
         B, S, T = x.shape
         if S != self.in_channels:
             raise ValueError(f"x must be [B, in_channels, T] with in_channels = {self.in_channels}, got {tuple(x.shape)}")
@@ -1184,7 +853,7 @@ class PosteriorEncoder(PackedWeightsMixin, nn.Module):
             noise = torch.randn(B, self.out_channels, T, device=dev)  # torch.randn_like(m), models.py:894
         if noise.dim() != 3 or noise.shape[0] != B or noise.shape[1] != self.out_channels or noise.shape[2] < T:
             raise ValueError(f"noise must be [B, out_channels, >= T] = [{B}, {self.out_channels}, >= {T}], got {tuple(noise.shape)}")
-        g = self._speaker(g, B)
+        g = speaker_rows(g, B, self.gin_channels, "a posterior encoder")
         eng = self._engines.get(self._cfg, dev)
         eng.set_precision(self.precision)
         eng.ensure_packed(self.weight_tensors, key_tensors=list(self.parameters()))
