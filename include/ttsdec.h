@@ -42,7 +42,8 @@ extern "C" {
 /* (The ttsgen_ family below - the HiFi-GAN generator - was added later without a bump: it adds entry points and a struct of its
  * own and changes none that existed, so a version-2 binding still binds every entry point it knows.) */
 /* (So was the ttsdur_ family at the end - the duration predictors and the length regulator - for the same reason.) */
-/* (And ttsvits_flow_forward and the ttspost_ family - the posterior encoder - for voice conversion.) */
+/* (And ttsvits_flow_forward and the ttspost_ family - the posterior encoder - for voice conversion; then ttsvits_neg_cent,
+ * ttsvits_maximum_path and ttsvits_align for monotonic alignment search.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -460,6 +461,37 @@ int ttsvits_flow_reverse(ttsvits_handle* h, const float* z, const int32_t* lengt
  * training forward is not computed (mean-only: it is 0). */
 int ttsvits_flow_forward(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* Monotonic alignment search between the text encoder's prior and the flow's z_p (the inverse of the length regulation,
+ * ttsdur_lengths / ttsdur_expand): the `with torch.no_grad():` block of SynthesizerTrn.forward (models.py:1224-1254) and
+ * monotonic_align/core.pyx:7-33.  Weightless: like ttsdur_lengths / ttsdur_expand these calls use the handle (of any dims, bound
+ * or not) for its device and its error text only.  They enqueue only.
+ *   t_y, t_x [B] int32 (device): frames and tokens of each utterance (the reference's mask.sum(1)[:, 0] / mask.sum(2)[:, 0]).
+ *   T_x <= 1024 (any T_y); more is refused with TTSDEC_ERR_DIMS. */
+enum { TTSVITS_PATH_F32 = 0, TTSVITS_PATH_F16 = 1, TTSVITS_PATH_BF16 = 2 }; /* element type of the dense path */
+/* Scratch of one ttsvits_maximum_path / ttsvits_align call: one decision bit per cell of the search (256-byte aligned). */
+size_t ttsvits_align_workspace_bytes(const ttsvits_handle* h, int B, int T_y, int T_x);
+/* neg_cent [B, T_y, T_x] (models.py:1226-1239) from z_p [B, T_y, C], m_p / logs_p [B, T_x, C], channel-last fp32, 16-byte aligned,
+ * C a multiple of 4 up to 4096:  sum_d(-0.5 log 2pi - logs_p) + sum_d(-0.5 z_p^2 s) + sum_d(z_p m_p s) + sum_d(-0.5 m_p^2 s) with
+ * s = exp(-2 logs_p); the two middle terms are one 2C-deep contraction in exact fp32 on the matrix pipe.  Cells at or beyond
+ * t_y[b] x t_x[b] are written as zeros; t_y / t_x NULL: every utterance is T_y x T_x. */
+int ttsvits_neg_cent(ttsvits_handle* h, const float* z_p, const float* m_p, const float* logs_p, const int32_t* t_y, const int32_t* t_x, int B,
+                    int T_y, int T_x, int C, float* neg_cent, void* stream);
+/* monotonic_align.maximum_path on any neg_cent [B, T_y, T_x] fp32 (not modified): the reference's path, bit for bit (fp32 `+` and
+ * max in its order, its edge rules, a tie stays on the token).
+ *   path        NULL, or [B, T_y, T_x] of path_dtype: 1 on the path, 0 elsewhere (zeros outside t_y x t_x)
+ *   frame_token [B, T_y] int32: the token of every frame, -1 at frames >= t_y[b]
+ *   dur         [B, T_x] int32: frames per token (path.sum over frames), 0 at tokens >= t_x[b]
+ *   status      [1] int32: 0, or flags of the utterances that were refused because the reference reads out of bounds there:
+ *               1 = t_y < 1 or t_x < 1, 2 = t_y < t_x, 4 = t_y > T_y or t_x > T_x.  Such an utterance gets frame_token -1, dur 0 and a
+ *               zero path; the caller reads status once and discards the call's outputs when it is not 0. */
+int ttsvits_maximum_path(ttsvits_handle* h, const float* neg_cent, const int32_t* t_y, const int32_t* t_x, int B, int T_y, int T_x, void* path,
+                        int path_dtype, int32_t* frame_token, int32_t* dur, int32_t* status, void* workspace, size_t workspace_bytes,
+                        void* stream);
+/* ttsvits_neg_cent into neg_cent [B, T_y, T_x] (kept: the caller's buffer), then ttsvits_maximum_path on it. */
+int ttsvits_align(ttsvits_handle* h, const float* z_p, const float* m_p, const float* logs_p, const int32_t* t_y, const int32_t* t_x, int B, int T_y,
+                 int T_x, int C, float* neg_cent, void* path, int path_dtype, int32_t* frame_token, int32_t* dur, int32_t* status,
+                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * VITS2 HiFi-GAN generator (latent z -> waveform): Generator.forward, vits2/models.py:900-974, with ResBlock1.forward

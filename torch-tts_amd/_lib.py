@@ -85,6 +85,8 @@ class GenDims(C.Structure):  # include/ttsdec.h ttsgen_dims
 
 
 DUR_SDP, DUR_DP = 0, 1  # include/ttsdec.h ttsdur_dims.kind
+PATH_F32, PATH_F16, PATH_BF16 = 0, 1, 2  # include/ttsdec.h TTSVITS_PATH_*
+ALIGN_MAX_TX = 1024  # tokens per utterance ttsvits_maximum_path is built for
 
 
 class DurDims(C.Structure):  # include/ttsdec.h ttsdur_dims
@@ -152,6 +154,10 @@ FAMILIES = (
         "flow_workspace_bytes": _ws_bytes,
         "flow_reverse": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
         "flow_forward": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
+        "align_workspace_bytes": (sz, [vp, i32, i32, i32]),  # (h, B, T_y, T_x)
+        "neg_cent": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+        "maximum_path": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
+        "align": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
     }),
     Family("ttsgen", GenDims, False, {
         "workspace_bytes": _ws_bytes,

@@ -15,6 +15,9 @@
                                              ``ttspost_*``)
 * ``voice_conversion(net_g, y, ...)``     - SynthesizerTrn.voice_conversion (models.py:1328-1336) over enc_q, flow (both
                                              directions) and dec
+* ``maximum_path(neg_cent, mask)``        - monotonic_align.maximum_path (monotonic_align/__init__.py:6-19) on the device
+* ``align(z_p, m_p, logs_p, ...)``        - the no_grad block of SynthesizerTrn.forward (models.py:1224-1254): neg_cent and the search
+* ``forced_alignment(net_g, x, ..., y, ...)`` - token durations of an utterance: enc_p, enc_q, flow forward, align
 
 All hold the reference's parameters (so checkpoints load) and run inference through the HIP library
 (``ttsvits_*`` / ``ttsgen_*`` / ``ttsdur_*`` / ``ttspost_*`` in include/ttsdec.h).  The library works on channel-last activations;
@@ -188,6 +191,55 @@ class VitsEngine(Handle):
                                                 out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
         self._err(rc, "ttsvits_flow_forward")
         return out
+
+    # ---- monotonic alignment search (weightless: a handle of any dims serves, bound or not) ----
+    _PATH_DTYPES = {torch.float32: _lib.PATH_F32, torch.float16: _lib.PATH_F16, torch.bfloat16: _lib.PATH_BF16}
+
+    def neg_cent(self, z_p, m_p, logs_p, t_y: Optional[torch.Tensor], t_x: Optional[torch.Tensor]) -> torch.Tensor:
+        """z_p [B, T_y, C], m_p / logs_p [B, T_x, C] contiguous fp32, t_y / t_x [B] int32 (device) or None -> neg_cent [B, T_y, T_x]
+        (include/ttsdec.h ttsvits_neg_cent)."""
+        B, T_y, Cc = z_p.shape
+        T_x = m_p.shape[1]
+        out = torch.empty(B, T_y, T_x, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsvits_neg_cent(self._h, z_p.data_ptr(), m_p.data_ptr(), logs_p.data_ptr(), t_y.data_ptr() if t_y is not None else None,
+                                           t_x.data_ptr() if t_x is not None else None, B, T_y, T_x, Cc, out.data_ptr(), _stream(self.device))
+        self._err(rc, "ttsvits_neg_cent")
+        return out
+
+    def maximum_path(self, neg_cent: torch.Tensor, t_y: torch.Tensor, t_x: torch.Tensor, dtype: Optional[torch.dtype] = torch.float32,
+                     z_p=None, m_p=None, logs_p=None):
+        """neg_cent [B, T_y, T_x] contiguous fp32, t_y / t_x [B] int32 (device) -> path [B, T_y, T_x] of ``dtype`` (None: not
+        written), frame_token [B, T_y] int32, dur [B, T_x] int32 (include/ttsdec.h ttsvits_maximum_path).  With z_p, m_p, logs_p given,
+        neg_cent is an output buffer and the call is ttsvits_align.  Reads the status word back: the call's one host sync."""
+        B, T_y, T_x = neg_cent.shape
+        if T_x > _lib.ALIGN_MAX_TX:
+            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsvits_maximum_path", f"T_x = {T_x} tokens: the search is built for up to {_lib.ALIGN_MAX_TX}")
+        ws = self.workspace("align", int(self._lib.ttsvits_align_workspace_bytes(self._h, B, T_y, T_x)))
+        # (a dtype the kernel does not store - fp64, integers - is written as fp32 and converted)
+        kdt = dtype if dtype in self._PATH_DTYPES else torch.float32
+        path = torch.empty(B, T_y, T_x, dtype=kdt, device=self.device) if dtype is not None else None
+        ft = torch.empty(B, T_y, dtype=torch.int32, device=self.device)
+        dur = torch.empty(B, T_x, dtype=torch.int32, device=self.device)
+        status = torch.empty(1, dtype=torch.int32, device=self.device)
+        tail = (B, T_y, T_x) if z_p is None else (B, T_y, T_x, z_p.shape[2], neg_cent.data_ptr())
+        head = (neg_cent.data_ptr(),) if z_p is None else (z_p.data_ptr(), m_p.data_ptr(), logs_p.data_ptr())
+        name = "ttsvits_maximum_path" if z_p is None else "ttsvits_align"
+        with torch.cuda.device(self.device):
+            rc = getattr(self._lib, name)(self._h, *head, t_y.data_ptr(), t_x.data_ptr(), *tail, path.data_ptr() if path is not None else None,
+                                          self._PATH_DTYPES[kdt], ft.data_ptr(), dur.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          _stream(self.device))
+        self._err(rc, name)
+        flags = int(status.item())
+        if flags & 4:
+            raise ValueError(f"an utterance's length from the mask exceeds the tensor [T_y, T_x] = [{T_y}, {T_x}]")
+        if flags & 1:
+            raise ValueError("an utterance has no frames or no tokens (t_y < 1 or t_x < 1): monotonic alignment search is undefined")
+        if flags & 2:
+            raise ValueError("an utterance has fewer frames than tokens (t_y < t_x): no monotonic path gives every token a frame")
+        if path is not None and path.dtype != dtype:
+            path = path.to(dtype)
+        return path, ft, dur
 
 
 _DEFAULT_FLOW = dict(flow_hidden=4, flow_kernel=1, flow_wn_layers=1, n_flows=0, flow_tf_layers=0, flow_tf_heads=1, flow_tf_kernel=1)
@@ -629,6 +681,8 @@ class DurEngine(Handle):
         return z_p, m_p, logs_p, attn
 
 
+
+
 class _DurationBase(PackedWeightsMixin, nn.Module):
     def _check(self, x: torch.Tensor) -> None:
         inference_only(self, "duration predictor", x, fp32=True)
@@ -896,3 +950,101 @@ def voice_conversion(net_g, y, y_lengths, sid_src, sid_tgt, *, noise=None):
     y_mask = (torch.arange(T, device=dev)[None, :] < lengths[:, None]).unsqueeze(1).to(torch.float32)
     o_hat = dec.forward_cl(z_hat * y_mask.transpose(1, 2), g_tgt).unsqueeze(1)
     return o_hat, y_mask, (z.transpose(1, 2), z_p.transpose(1, 2), z_hat.transpose(1, 2))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Monotonic alignment search (models.py:1224-1254, monotonic_align/) through ttsvits_neg_cent / ttsvits_maximum_path, forced alignment
+# ---------------------------------------------------------------------------------------------------------------------------
+_ALIGN_ENGINES = EngineCache(VitsEngine)  # weightless handles of the stand-alone calls, one per device
+_ALIGN_DIMS = dict(n_vocab=1, inter_channels=8, hidden_channels=4, filter_channels=4, n_heads=1, n_layers=0, kernel_size=1, window_size=0,
+                   **_DEFAULT_FLOW)  # (any valid dims)
+
+
+def _align_engine(device: torch.device, eng: Optional[VitsEngine] = None) -> VitsEngine:
+    return eng if eng is not None else _ALIGN_ENGINES.get(_ALIGN_DIMS, device)
+
+
+def _mask_lengths(mask: torch.Tensor):
+    """t_y, t_x [B] int32 of a [B, T_y, T_x] mask, as the reference's wrapper takes them (monotonic_align/__init__.py:16-17)."""
+    return (mask.sum(1)[:, 0].to(torch.int32).contiguous(), mask.sum(2)[:, 0].to(torch.int32).contiguous())
+
+
+def maximum_path(neg_cent, mask):
+    """monotonic_align.maximum_path (monotonic_align/__init__.py:6-19) on the device: neg_cent, mask [b, t_t, t_s] -> path [b, t_t, t_s]
+    in neg_cent's dtype and on its device, equal to the reference's.  The lengths are mask.sum(1)[:, 0] / mask.sum(2)[:, 0], computed
+    on the device; the one host read is the status word (ValueError where the reference would read out of bounds: an utterance
+    with t_t < t_s, or an empty one)."""
+    if not neg_cent.is_cuda or not mask.is_cuda:
+        raise NotImplementedError("vits2.maximum_path runs on a ROCm device only: there is no CPU fallback")
+    if neg_cent.dim() != 3 or tuple(mask.shape) != tuple(neg_cent.shape):
+        raise ValueError(f"neg_cent and mask must both be [b, t_t, t_s], got {tuple(neg_cent.shape)} and {tuple(mask.shape)}")
+    t_y, t_x = _mask_lengths(mask)
+    eng = _align_engine(neg_cent.device)
+    return eng.maximum_path(neg_cent.detach().to(torch.float32).contiguous(), t_y, t_x, neg_cent.dtype)[0]
+
+
+def _align_cl(eng: VitsEngine, z_cl, m_cl, logs_cl, t_y, t_x, mas_noise_scale=None, noise=None):
+    """neg_cent and the search on channel-last operands -> (path [B, T_y, T_x] fp32, frame_token, dur, neg_cent)."""
+    z_cl, m_cl, logs_cl = (t.detach().to(torch.float32).contiguous() for t in (z_cl, m_cl, logs_cl))
+    if mas_noise_scale is None:
+        B, T_y, _ = z_cl.shape
+        nc = torch.empty(B, T_y, m_cl.shape[1], device=z_cl.device)
+        path, ft, dur = eng.maximum_path(nc, t_y, t_x, torch.float32, z_cl, m_cl, logs_cl)
+        return path, ft, dur, nc
+    # models.py:1241-1247 on the unmasked cost matrix, as the reference computes it
+    nc = eng.neg_cent(z_cl, m_cl, logs_cl, None, None)
+    if noise is None:
+        noise = torch.randn_like(nc)
+    if tuple(noise.shape) != tuple(nc.shape):
+        raise ValueError(f"noise must be [B, T_y, T_x] = {tuple(nc.shape)}, got {tuple(noise.shape)}")
+    nc = (nc + torch.std(nc) * noise.to(device=nc.device, dtype=torch.float32) * mas_noise_scale).contiguous()
+    path, ft, dur = eng.maximum_path(nc, t_y, t_x, torch.float32)
+    return path, ft, dur, nc
+
+
+def align(z_p, m_p, logs_p, x_mask, y_mask, mas_noise_scale=None, *, noise=None):
+    """The ``with torch.no_grad():`` block of SynthesizerTrn.forward (models.py:1224-1254): z_p [B, C, T_y], m_p / logs_p [B, C, T_x],
+    x_mask [B, 1, T_x], y_mask [B, 1, T_y] -> attn [B, 1, T_y, T_x].  neg_cent and the search run in the HIP library; with
+    ``mas_noise_scale`` the std(neg_cent) * randn * scale term is added by torch ops between the two (``noise`` [B, T_y, T_x], test
+    hook, replaces the draw).  The one host read is the status word."""
+    for name, t in dict(z_p=z_p, m_p=m_p, logs_p=logs_p, x_mask=x_mask, y_mask=y_mask).items():
+        if not t.is_cuda:
+            raise NotImplementedError(f"vits2.align runs on a ROCm device only ({name} is on {t.device}): there is no CPU fallback")
+    if z_p.dim() != 3 or m_p.shape != logs_p.shape or m_p.shape[:2] != z_p.shape[:2] or z_p.shape[1] % 4:
+        raise ValueError(f"z_p [B, C, T_y] and m_p / logs_p [B, C, T_x] with C a multiple of 4 expected, got {tuple(z_p.shape)}, "
+                         f"{tuple(m_p.shape)}, {tuple(logs_p.shape)}")
+    t_x = x_mask[:, 0, :].sum(1).to(torch.int32).contiguous()
+    t_y = y_mask[:, 0, :].sum(1).to(torch.int32).contiguous()
+    cl = _DurationBase._channel_last
+    path, _, _, _ = _align_cl(_align_engine(z_p.device), cl(z_p), cl(m_p), cl(logs_p), t_y, t_x, mas_noise_scale, noise)
+    return path.unsqueeze(1)
+
+
+def forced_alignment(net_g, x, x_lengths, y, y_lengths, sid=None, *, mas_noise_scale=None, noise=None):
+    """Token durations of a given utterance: SynthesizerTrn.forward up to ``logw_`` (models.py:1214-1263) for a model whose enc_p /
+    enc_q / flow are this module's drop-ins - x [B, T_x] ids and y [B, spec, T_y] -> (attn [B, 1, T_y, T_x], w = attn.sum(2)
+    [B, 1, T_x], logw_ = log(w + 1e-6) * x_mask [B, 1, T_x], (z, z_p, m_p, logs_p) as the reference's [B, inter, T]).  Channel-last
+    from the encoders to the search; the one host read is the search's status word.  ``noise`` (test hook): the posterior's draw
+    [B, inter, >= T_y], or a pair (posterior draw, MAS draw [B, T_y, T_x]) with ``mas_noise_scale``."""
+    parts = {"enc_p": TextEncoder, "enc_q": PosteriorEncoder, "flow": ResidualCouplingTransformersBlock}
+    for name, cls in parts.items():
+        mod = getattr(net_g, name, None)
+        if not isinstance(mod, cls):
+            raise TypeError(f"net_g.{name} is {type(mod).__name__}, not the HIP drop-in: swap it in (INTEGRATION.md) - there is no fallback")
+    if not x.is_cuda or not y.is_cuda:
+        raise NotImplementedError("vits2.forced_alignment runs on a ROCm device only: move the model, the ids and the spectrogram there")
+    enc_p, enc_q, flow = net_g.enc_p, net_g.enc_q, net_g.flow
+    e_q, e_mas = noise if isinstance(noise, (tuple, list)) else (noise, None)
+    g = None if sid is None else net_g.emb_g(sid).unsqueeze(-1)  # [b, h, 1]
+    dev = x.device
+    t_x = x_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    t_y = y_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    _, m_cl, logs_cl = enc_p.forward_cl(x, t_x, g=g if enc_p.gin_channels else None)
+    z_cl, _, _ = enc_q.forward_cl(y, t_y, g=g, noise=e_q)
+    zp_cl = flow.forward_cl(z_cl, t_y, g)
+    eng = flow._engines.get(flow._dims(), dev)  # (the flow's own handle: the calls are weightless)
+    path, _, dur, _ = _align_cl(eng, zp_cl, m_cl, logs_cl, t_y, t_x, mas_noise_scale, e_mas)
+    w = dur.to(torch.float32).unsqueeze(1)
+    x_mask = (torch.arange(x.shape[1], device=dev)[None, :] < t_x[:, None]).unsqueeze(1).to(torch.float32)
+    logw_ = torch.log(w + 1e-6) * x_mask
+    return path.unsqueeze(1), w, logw_, (z_cl.transpose(1, 2), zp_cl.transpose(1, 2), m_cl.transpose(1, 2), logs_cl.transpose(1, 2))
