@@ -43,7 +43,8 @@ extern "C" {
  * own and changes none that existed, so a version-2 binding still binds every entry point it knows.) */
 /* (So was the ttsdur_ family at the end - the duration predictors and the length regulator - for the same reason.) */
 /* (And ttsvits_flow_forward and the ttspost_ family - the posterior encoder - for voice conversion; then ttsvits_neg_cent,
- * ttsvits_maximum_path and ttsvits_align for monotonic alignment search.) */
+ * ttsvits_maximum_path and ttsvits_align for monotonic alignment search; then ttsvits_spectrogram, ttsvits_spec_to_mel and
+ * ttsvits_mel_spectrogram, the spectrogram front-end.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -492,6 +493,36 @@ int ttsvits_maximum_path(ttsvits_handle* h, const float* neg_cent, const int32_t
 int ttsvits_align(ttsvits_handle* h, const float* z_p, const float* m_p, const float* logs_p, const int32_t* t_y, const int32_t* t_x, int B, int T_y,
                  int T_x, int C, float* neg_cent, void* path, int path_dtype, int32_t* frame_token, int32_t* dur, int32_t* status,
                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* Spectrogram front-end: the reference's vits2/mel_processing.py:58-187 (spectrogram_torch, spec_to_mel_torch, mel_spectrogram_torch,
+ * center=False), from waveforms to what ttspost_forward reads.  Weightless like the alignment calls above: the handle (of any dims,
+ * bound or not) gives its device and its error text.  The calls enqueue only.
+ *   wav      [B, N] fp32, one utterance per row; lengths [B] int32 samples of each (device), or NULL: every row is N samples
+ *   window   [win_size] fp32 (the reference's torch.hann_window(win_size)), centred in the n_fft-point frame with zeros around it
+ *   n_fft    256, 512, 1024 or 2048 (else TTSDEC_ERR_DIMS); win_size <= n_fft; any hop_size >= 1; bins = n_fft / 2 + 1
+ *   An utterance of len samples is reflect-padded by pad = (n_fft - hop_size) / 2 (C division) at its own two ends and has
+ *   1 + (len + 2 pad - n_fft) / hop_size frames; frame t, bin k is sqrt(re^2 + im^2 + 1e-6) of the windowed n_fft-point DFT of the
+ *   padded samples from t * hop_size (an FFT in fp32, twiddles evaluated in fp64 and rounded once).
+ *   T        frames of the output tensors; frames at or past an utterance's count are written as exact zeros
+ *   status   NULL, or [1] int32 (device): 0, or flags of refused utterances, whose frames are all zeros: 1 = len <= pad (the
+ *            reflection is undefined), 2 = no frame (len + 2 pad < n_fft), 4 = len > N or more frames than T (clamped)
+ *   mel_basis [n_mels, bins] fp32 row-major, n_mels <= 256: mel = log(max(mel_basis @ spec, 1e-5)) with fp32 sums over each row's
+ *            run of non-zero entries, in bin order
+ *   workspace ttsvits_spec_workspace_bytes(h, n_fft, n_mels) bytes (n_mels = 0 for ttsvits_spectrogram), 256-byte aligned; every call
+ *            rebuilds its tables there (twiddles; the non-zero run of each basis row) with one small launch of its own.
+ * Sizes are checked before any pointer: TTSDEC_ERR_INVALID_ARG for a size <= 0, TTSDEC_ERR_DIMS as above, then NULL pointers,
+ * then TTSDEC_ERR_WORKSPACE. */
+size_t ttsvits_spec_workspace_bytes(const ttsvits_handle* h, int n_fft, int n_mels); /* 0: n_fft or n_mels outside the ranges above */
+/* spec [B, bins, T] */
+int ttsvits_spectrogram(ttsvits_handle* h, const float* wav, const int32_t* lengths, int B, int N, const float* window, int n_fft, int hop_size,
+                        int win_size, float* spec, int T, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* mel [B, n_mels, T] from spec [B, bins, T] (bins = n_fft / 2 + 1); frames [B] int32 (device) or NULL: zeros at frames >= frames[b] */
+int ttsvits_spec_to_mel(ttsvits_handle* h, const float* spec, const int32_t* frames, int B, int n_fft, int T, const float* mel_basis, int n_mels,
+                        float* mel, void* workspace, size_t workspace_bytes, void* stream);
+/* mel [B, n_mels, T] from the waveforms: ttsvits_spectrogram and ttsvits_spec_to_mel in one kernel, the magnitudes staying in LDS */
+int ttsvits_mel_spectrogram(ttsvits_handle* h, const float* wav, const int32_t* lengths, int B, int N, const float* window, int n_fft, int hop_size,
+                            int win_size, const float* mel_basis, int n_mels, float* mel, int T, int32_t* status, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * VITS2 HiFi-GAN generator (latent z -> waveform): Generator.forward, vits2/models.py:900-974, with ResBlock1.forward

@@ -12,6 +12,7 @@ from . import vits2  # noqa: F401  (TextEncoder, ResidualCouplingTransformersBlo
 #                             PosteriorEncoder, voice_conversion)
 from .vits2 import DurationPredictor, Generator, PosteriorEncoder, StochasticDurationPredictor
 from . import audio  # noqa: F401  (AudioFrontend.mel_inv / decode, m_rev, synth_audio)
+from . import mel_processing  # noqa: F401  (spectrogram_torch, spec_to_mel_torch, mel_spectrogram_torch: the VITS2 audio front-end)
 from . import train_util  # noqa: F401  (load_state_dict: the reference's partial checkpoint loader + blob invalidation)
 
 __all__ = [

@@ -158,6 +158,10 @@ FAMILIES = (
         "neg_cent": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "maximum_path": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
         "align": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+        "spec_workspace_bytes": (sz, [vp, i32, i32]),  # (h, n_fft, n_mels)
+        "spectrogram": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
+        "spec_to_mel": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
+        "mel_spectrogram": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, sz, vp]),
     }),
     Family("ttsgen", GenDims, False, {
         "workspace_bytes": _ws_bytes,

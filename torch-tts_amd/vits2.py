@@ -18,6 +18,8 @@
 * ``maximum_path(neg_cent, mask)``        - monotonic_align.maximum_path (monotonic_align/__init__.py:6-19) on the device
 * ``align(z_p, m_p, logs_p, ...)``        - the no_grad block of SynthesizerTrn.forward (models.py:1224-1254): neg_cent and the search
 * ``forced_alignment(net_g, x, ..., y, ...)`` - token durations of an utterance: enc_p, enc_q, flow forward, align
+* ``spectrogram_torch`` / ``spec_to_mel_torch`` / ``mel_spectrogram_torch`` - mel_processing.py:58-187 (re-exported from
+                                             ``mel_processing``), and ``voice_conversion_from_audio`` / ``forced_alignment_from_audio``
 
 All hold the reference's parameters (so checkpoints load) and run inference through the HIP library
 (``ttsvits_*`` / ``ttsgen_*`` / ``ttsdur_*`` / ``ttspost_*`` in include/ttsdec.h).  The library works on channel-last activations;
@@ -240,6 +242,51 @@ class VitsEngine(Handle):
         if path is not None and path.dtype != dtype:
             path = path.to(dtype)
         return path, ft, dur
+
+    # ---- spectrogram front-end (weightless too; mel_processing.py holds the reference-named entry points) ----
+    def _spec_workspace(self, n_fft: int, n_mels: int, name: str) -> torch.Tensor:
+        nbytes = int(self._lib.ttsvits_spec_workspace_bytes(self._h, n_fft, n_mels))
+        if not nbytes:
+            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, name, f"n_fft = {n_fft}, n_mels = {n_mels}: built for n_fft 256 / 512 / 1024 / 2048, n_mels <= 256")
+        return self.workspace("spec", nbytes)
+
+    def spectrogram(self, wav: torch.Tensor, lengths: Optional[torch.Tensor], window: torch.Tensor, n_fft: int, hop_size: int, T: int,
+                    mel_basis: Optional[torch.Tensor] = None, *, check: bool = False) -> torch.Tensor:
+        """wav [B, N] contiguous fp32, lengths [B] int32 (device) or None, window [win_size] -> spec [B, n_fft / 2 + 1, T], or with
+        mel_basis [n_mels, bins] the log-mel [B, n_mels, T] (ttsvits_spectrogram / ttsvits_mel_spectrogram).  check: read the status
+        word back (one host sync) and raise for an utterance the kernel refused - for lengths the host has not seen."""
+        B, N = wav.shape
+        n_mels = 0 if mel_basis is None else int(mel_basis.shape[0])
+        name = "ttsvits_mel_spectrogram" if n_mels else "ttsvits_spectrogram"
+        ws = self._spec_workspace(n_fft, n_mels, name)
+        out = torch.empty(B, n_mels or n_fft // 2 + 1, T, device=self.device)
+        status = torch.empty(1, dtype=torch.int32, device=self.device) if check else None
+        mel_args = (mel_basis.data_ptr(), n_mels) if n_mels else ()
+        with torch.cuda.device(self.device):
+            rc = getattr(self._lib, name)(self._h, wav.data_ptr(), lengths.data_ptr() if lengths is not None else None, B, N, window.data_ptr(),
+                                          n_fft, hop_size, window.numel(), *mel_args, out.data_ptr(), T,
+                                          status.data_ptr() if check else None, ws.data_ptr(), ws.numel(), _stream(self.device))
+        self._err(rc, name)
+        if check:
+            flags = int(status.item())
+            if flags & 4:
+                raise ValueError(f"an utterance's length exceeds the waveform tensor's {N} samples")
+            if flags & 3:
+                raise ValueError(f"an utterance is no longer than the reflect padding ({int((n_fft - hop_size) / 2)} samples) or too short for "
+                                 f"one frame of n_fft = {n_fft}: its spectrogram is undefined")
+        return out
+
+    def spec_to_mel(self, spec: torch.Tensor, frames: Optional[torch.Tensor], n_fft: int, mel_basis: torch.Tensor) -> torch.Tensor:
+        """spec [B, n_fft / 2 + 1, T] contiguous fp32, frames [B] int32 (device) or None -> log-mel [B, n_mels, T] (ttsvits_spec_to_mel)."""
+        B, _, T = spec.shape
+        n_mels = int(mel_basis.shape[0])
+        ws = self._spec_workspace(n_fft, n_mels, "ttsvits_spec_to_mel")
+        mel = torch.empty(B, n_mels, T, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsvits_spec_to_mel(self._h, spec.data_ptr(), frames.data_ptr() if frames is not None else None, B, n_fft, T,
+                                               mel_basis.data_ptr(), n_mels, mel.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
+        self._err(rc, "ttsvits_spec_to_mel")
+        return mel
 
 
 _DEFAULT_FLOW = dict(flow_hidden=4, flow_kernel=1, flow_wn_layers=1, n_flows=0, flow_tf_layers=0, flow_tf_heads=1, flow_tf_kernel=1)
@@ -1048,3 +1095,40 @@ def forced_alignment(net_g, x, x_lengths, y, y_lengths, sid=None, *, mas_noise_s
     x_mask = (torch.arange(x.shape[1], device=dev)[None, :] < t_x[:, None]).unsqueeze(1).to(torch.float32)
     logw_ = torch.log(w + 1e-6) * x_mask
     return path.unsqueeze(1), w, logw_, (z_cl.transpose(1, 2), zp_cl.transpose(1, 2), m_cl.transpose(1, 2), logs_cl.transpose(1, 2))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Audio front-end (mel_processing.py, csrc/spec.hip) in front of voice conversion and forced alignment
+# ---------------------------------------------------------------------------------------------------------------------------
+from .mel_processing import mel_spectrogram_torch, spec_to_mel_torch, spectrogram_torch  # noqa: E402  (re-exported)
+
+
+def _spec_from_audio(net_g, wav, wav_lengths, n_fft, hop_size, win_size, sampling_rate, n_mels, fmin, fmax, mel_basis):
+    """What net_g.enc_q reads, from waveforms: the linear spectrogram when enc_q.in_channels is n_fft / 2 + 1, the log-mel when it is
+    n_mels (the reference's use_mel_posterior_encoder, the ModelConfig default) -> (y [B, in_channels, T], y_lengths [B])."""
+    enc_q = getattr(net_g, "enc_q", None)
+    if not isinstance(enc_q, PosteriorEncoder):
+        raise TypeError(f"net_g.enc_q is {type(enc_q).__name__}, not the HIP drop-in: swap it in (INTEGRATION.md) - there is no fallback")
+    if n_mels is None and mel_basis is not None:
+        n_mels = int(mel_basis.shape[0])
+    if enc_q.in_channels == n_fft // 2 + 1:
+        return spectrogram_torch(wav, n_fft, sampling_rate, hop_size, win_size, lengths=wav_lengths)
+    if n_mels is not None and enc_q.in_channels == n_mels:
+        return mel_spectrogram_torch(wav, n_fft, n_mels, sampling_rate, hop_size, win_size, fmin, fmax, mel_basis=mel_basis, lengths=wav_lengths)
+    raise ValueError(f"net_g.enc_q reads {enc_q.in_channels} channels: neither the linear spectrogram's n_fft / 2 + 1 = {n_fft // 2 + 1} nor "
+                     f"n_mels = {n_mels}")
+
+
+def voice_conversion_from_audio(net_g, wav, wav_lengths, sid_src, sid_tgt, *, n_fft, hop_size, win_size, sampling_rate, n_mels=None, fmin=0.0,
+                                fmax=None, mel_basis=None, noise=None):
+    """``voice_conversion`` from waveforms: wav [B, samples] fp32, wav_lengths [B] samples -> what voice_conversion returns for the
+    spectrogram the reference's data loader would have made of each utterance (mel_processing.py); no host round trip between."""
+    y, y_lengths = _spec_from_audio(net_g, wav, wav_lengths, n_fft, hop_size, win_size, sampling_rate, n_mels, fmin, fmax, mel_basis)
+    return voice_conversion(net_g, y, y_lengths, sid_src, sid_tgt, noise=noise)
+
+
+def forced_alignment_from_audio(net_g, x, x_lengths, wav, wav_lengths, sid=None, *, n_fft, hop_size, win_size, sampling_rate, n_mels=None,
+                                fmin=0.0, fmax=None, mel_basis=None, mas_noise_scale=None, noise=None):
+    """``forced_alignment`` from waveforms (see voice_conversion_from_audio)."""
+    y, y_lengths = _spec_from_audio(net_g, wav, wav_lengths, n_fft, hop_size, win_size, sampling_rate, n_mels, fmin, fmax, mel_basis)
+    return forced_alignment(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale=mas_noise_scale, noise=noise)
