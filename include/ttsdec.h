@@ -44,7 +44,8 @@ extern "C" {
 /* (So was the ttsdur_ family at the end - the duration predictors and the length regulator - for the same reason.) */
 /* (And ttsvits_flow_forward and the ttspost_ family - the posterior encoder - for voice conversion; then ttsvits_neg_cent,
  * ttsvits_maximum_path and ttsvits_align for monotonic alignment search; then ttsvits_spectrogram, ttsvits_spec_to_mel and
- * ttsvits_mel_spectrogram, the spectrogram front-end.) */
+ * ttsvits_mel_spectrogram, the spectrogram front-end; then ttsdec_griffinlim_workspace_bytes, ttsdec_mel_to_magnitude and
+ * ttsdec_griffinlim, mel -> waveform for the Tacotron path.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -523,6 +524,50 @@ int ttsvits_spec_to_mel(ttsvits_handle* h, const float* spec, const int32_t* fra
 int ttsvits_mel_spectrogram(ttsvits_handle* h, const float* wav, const int32_t* lengths, int B, int N, const float* window, int n_fft, int hop_size,
                             int win_size, const float* mel_basis, int n_mels, float* mel, int T, int32_t* status, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* Mel -> waveform for the Tacotron path: the reference's tacotron/inference.py:13-22 (synth_audio) with AudioFrontend.mel_inv /
+ * .decode (tacotron/data/audio.py:69-76) and m_rev (tacotron/data/dataset.py:183-184) - torchaudio's InverseMelScale,
+ * amplitude_to_DB, DB_to_amplitude and GriffinLim - on a padded batch.  Weightless: the ttsdec handle (of any dims, bound or not)
+ * gives its device and its error text.  The calls enqueue only.  Exact fp32.
+ *   frames   [B] int32 mel frames of each utterance (device), or NULL: every row has T.  An utterance of T_b frames gives
+ *            hop_length * (T_b - 1) samples (torch.istft(center=True)); frames at or past T_b and samples at or past that count are
+ *            written as exact zeros.  T >= 2.
+ *   n_fft    256, 512, 1024 or 2048 (else TTSDEC_ERR_DIMS), win_length == n_fft; hop_length <= n_fft / 2 (else TTSDEC_ERR_DIMS: the
+ *            overlap-added squared window must have no zero); bins = n_fft / 2 + 1
+ *   status   NULL, or [1] int32 (device): 0, or flags: 1 = an utterance of fewer than 2 frames (its row is zeros), 4 = frames[b] > T
+ *            (clamped)
+ * Sizes are checked before any pointer: TTSDEC_ERR_INVALID_ARG for a size <= 0, TTSDEC_ERR_DIMS as above, then NULL pointers,
+ * then TTSDEC_ERR_WORKSPACE. */
+size_t ttsdec_griffinlim_workspace_bytes(const ttsdec_handle* h, int B, int T, int n_fft); /* 0: a size outside the ranges above */
+/* y [B, T, n_mels] (the model's normalised mel, n_mels <= 256) -> mag [B, bins, T], the magnitude Griffin-Lim starts from:
+ *   M = 10^(0.1 (100 y - 100))                      m_rev, then db_to_amplitude (audio.py:74, dataset.py:183-184)
+ *   D = relu(P M)                                   InverseMelScale (audio.py:75): P [bins, n_mels] fp32 row-major is the minimum-norm
+ *                                                   solution operator fb (fb^T fb)^-1 of fb^T D = M - what lstsq(driver="gels")
+ *                                                   solves per utterance in the reference - for the filterbank fb [bins, n_mels]
+ *   mag = sqrt(10^(0.1 * 10 log10(max(D, 1e-12))))  amplitude_to_db (audio.py:76), db_to_amplitude (audio.py:70), and the
+ *                                                   root GriffinLim(power=2) takes first; a zero of D gives 1e-6
+ * with fp32 sums over the n_mels terms in order. */
+int ttsdec_mel_to_magnitude(ttsdec_handle* h, const float* y, const float* P, const int32_t* frames, int B, int T, int n_mels, int n_fft, float* mag,
+                            int32_t* status, void* stream);
+/* mag [B, bins, T] -> wave [B, hop_length * (T - 1)] by n_iter iterations of fast Griffin-Lim (audio.py:59-65, :71; torchaudio
+ * functional.griffinlim on the magnitude, i.e. after its pow(1 / power)):
+ *   repeat n_iter times:  inverse = istft(mag * angles);  rebuilt = stft(inverse, center=True, pad_mode="reflect");
+ *                         angles = rebuilt - tprev * momentum / (1 + momentum);  angles /= |angles| + 1e-16;  tprev = rebuilt
+ *   wave = istft(mag * angles), and with normalize != 0 wave / max |wave| per utterance (inference.py:21)
+ *   window   [n_fft] fp32 (the reference's torch.hann_window(n_fft))
+ *   angles   NULL (all ones: rand_init=False), or the initial phase factors [B, bins, T] complex64 (interleaved re, im) - torchaudio
+ *            starts from complex(rand, rand), which is not of unit modulus; the caller draws it
+ *   tprev    NULL (zeros), or [B, bins, T] complex64: with angles, the state of an iteration to go on from
+ *   0 <= momentum < 1;  n_iter >= 0 (0: the inverse STFT alone)
+ *   rebuilt_out, angles_out  NULL, or [B, bins, T] complex64 (n_iter >= 1 only): the last rebuilt spectrum (the next tprev) and the
+ *            phase factors the waveform was made from
+ *   An utterance of no more than n_fft / 2 samples is reflected as often as the padding needs (torch.stft refuses it).
+ *   workspace ttsdec_griffinlim_workspace_bytes(h, B, T, n_fft) bytes, 256-byte aligned; holds the twiddles (rebuilt by every call),
+ *            the frame-major magnitude, two spectra and the windowed inverse frames [B, T, n_fft].
+ * Deterministic: no atomics in the overlap-add; every utterance gets bit for bit what it gets alone. */
+int ttsdec_griffinlim(ttsdec_handle* h, const float* mag, const int32_t* frames, int B, int T, const float* window, int n_fft, int hop_length,
+                      const float* angles, const float* tprev, int n_iter, float momentum, int normalize, float* wave, float* rebuilt_out,
+                      float* angles_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * VITS2 HiFi-GAN generator (latent z -> waveform): Generator.forward, vits2/models.py:900-974, with ResBlock1.forward

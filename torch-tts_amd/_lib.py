@@ -143,6 +143,13 @@ FAMILIES = (
             vp, vp, vp, vp, vp, sz, vp,                 # y, s, w, T_out, workspace, workspace_bytes, stream
             C.POINTER(f32), C.POINTER(C.c_char_p), i32, C.POINTER(i32), C.POINTER(f32),
         ]),
+        "griffinlim_workspace_bytes": (sz, [vp, i32, i32, i32]),  # (h, B, T, n_fft)
+        "mel_to_magnitude": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "griffinlim": (i32, [
+            vp, vp, vp, i32, i32, vp, i32, i32,  # h, mag, frames, B, T, window, n_fft, hop_length
+            vp, vp, i32, f32, i32,               # angles, tprev, n_iter, momentum, normalize
+            vp, vp, vp, vp, vp, sz, vp,          # wave, rebuilt_out, angles_out, status, workspace, workspace_bytes, stream
+        ]),
     }),
     Family("ttsenc", EncDims, True, {
         "workspace_bytes": _ws_bytes,

@@ -6,15 +6,22 @@ The reference builds these from torchaudio (``InverseMelScale``, ``GriffinLim``,
 ``amplitude_to_DB``; torchaudio >= 2.2.1 per tacotron/requirements.txt), which is not installed here, so the
 published algorithms are restated on plain torch ops and run on whatever device the tensors live on (FFTs go
 to rocFFT through ``torch.stft`` / ``torch.istft``): this step is I/O + FFT, there is no hand-written kernel
-in it.  PARITY UNPINNED: without torchaudio no reference vectors can be produced, and the reference's
-Griffin-Lim starts from a random phase (``rand_init=True``); tests check the algebraic properties instead."""
+in those.  PARITY UNPINNED against torchaudio itself: without it no reference vectors can be produced, and the
+reference's Griffin-Lim starts from a random phase (``rand_init=True``); tests check the algebraic properties instead.
+
+The same step as HIP kernels, batched and length-aware (include/ttsdec.h ttsdec_mel_to_magnitude / ttsdec_griffinlim,
+csrc/griffinlim.hip): ``AudioFrontend.mel_to_magnitude``, ``griffinlim_native`` and ``synth_audio_native``.  ROCm-only,
+exact fp32, no fallback.  With the initial phase an explicit input the algorithm is deterministic, and what is pinned
+(tests/test_griffinlim_hip.py) is parity with the published algorithm as the functions above state it, run in fp64."""
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Optional
+from typing import Dict, Optional
 
 import torch
+
+from . import _lib
 
 
 @dataclass
@@ -116,6 +123,7 @@ class AudioFrontend:
         self.fb = melscale_fbanks(self.n_freqs, float(config.fmin), float(config.fmax), config.num_mels, config.sample_rate)
         if device is not None:
             self.fb = self.fb.to(device)
+        self._P: Dict[str, torch.Tensor] = {}  # inverse_basis() per device
 
     def stft_to_mels(self, D: torch.Tensor) -> torch.Tensor:  # MelScale: [..., n_freqs, T] -> [..., n_mels, T]
         return torch.matmul(D.transpose(-1, -2), self.fb.to(D.device)).transpose(-1, -2)
@@ -129,6 +137,32 @@ class AudioFrontend:
         # (gelsy) returns nothing useful here because the filterbank has all-zero rows above f_max
         sol = torch.linalg.lstsq(fbT.unsqueeze(0).expand(m2.shape[0], -1, -1).contiguous(), m2, driver="gels").solution
         return torch.relu(sol).reshape(lead + sol.shape[-2:])
+
+    def inverse_basis(self, device=None) -> torch.Tensor:
+        """P = fb (fb^T fb)^-1 [n_freqs, n_mels]: ``P @ M`` is the minimum-norm solution of fb^T D = M, which is what
+        ``lstsq(driver="gels")`` returns in ``mels_to_stft`` (fb^T has full row rank).  Made once in fp64 on the host and
+        rounded once to fp32."""
+        key = str(torch.device(device) if device is not None else "cpu")
+        if "cpu" not in self._P:
+            fb = self.fb.detach().to("cpu", torch.float64)
+            self._P["cpu"] = torch.linalg.solve(fb.T @ fb, fb.T).T.contiguous().to(torch.float32)
+        if key not in self._P:
+            self._P[key] = self._P["cpu"].to(device)
+        return self._P[key]
+
+    def mel_to_magnitude(self, y: torch.Tensor, lengths=None) -> torch.Tensor:
+        """y [B, T, n_mels] (or [T, n_mels]), the model's normalised mel -> the magnitude [B, n_freqs, T] Griffin-Lim starts
+        from: ``db_to_amplitude(mel_inv(m_rev(y)), 1, 1).sqrt()`` of every utterance in one kernel.  ``lengths`` ([B] mel
+        frames, host or device): frames past them are zeros."""
+        who = "AudioFrontend.mel_to_magnitude"
+        _check_native(y, self.n_fft, self.config.hop_length, self.n_fft, who)
+        y3 = y.unsqueeze(0) if y.dim() == 2 else y
+        if y3.dim() != 3 or y3.shape[2] != self.config.num_mels:
+            raise ValueError(f"{who}: y must be [B, T, n_mels = {self.config.num_mels}], got {tuple(y.shape)}")
+        B, T, _ = y3.shape
+        frames, on_device = _frames_arg(lengths, B, T, y.device, who)
+        mag = _engine(y.device).mel_to_magnitude(y3.detach().contiguous(), self.inverse_basis(y.device), frames, self.n_fft, check=on_device)
+        return mag[0] if y.dim() == 2 else mag
 
     def mel_inv(self, M_db: torch.Tensor) -> torch.Tensor:  # data/audio.py:73-76
         M = db_to_amplitude(M_db.mT, 1, 1)
@@ -148,3 +182,126 @@ def synth_audio(y: torch.Tensor, audio_frontend: AudioFrontend, generator: Optio
         w = audio_frontend.decode(D_db, generator=generator)
         wave.append(w / w.abs().max())
     return torch.stack(wave)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The same step through the HIP kernels (csrc/griffinlim.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+N_FFTS = (256, 512, 1024, 2048)  # what csrc/fft_lds.h has radix plans for
+_ENGINES = None
+_windows: Dict[tuple, torch.Tensor] = {}
+
+
+def _engine(device: torch.device):
+    """The weightless ttsdec handle of the stand-alone calls, one per device."""
+    global _ENGINES
+    from .engine import EngineCache, EngineDims
+
+    if _ENGINES is None:
+        _ENGINES = EngineCache()
+    return _ENGINES.get(EngineDims(), device)
+
+
+def wave_samples(frames: int, hop_length: int) -> int:
+    """Samples of an utterance of ``frames`` mel frames: torch.istft(center=True) gives hop_length * (frames - 1)."""
+    return hop_length * (frames - 1)
+
+
+def _check_native(t: torch.Tensor, n_fft: int, hop_length: int, win_length: int, who: str) -> None:
+    """The refusals of the native path, all before any device work."""
+    if n_fft not in N_FFTS:
+        raise _lib.DimsNotBuilt(_lib.ERR_DIMS, who, f"n_fft = {n_fft}: built for {N_FFTS} (768, the dataclass default, needs a radix-3 pass)")
+    if win_length != n_fft:
+        raise _lib.DimsNotBuilt(_lib.ERR_DIMS, who, f"win_length = {win_length}: built for win_length == n_fft = {n_fft}")
+    if not 1 <= hop_length <= n_fft // 2:
+        raise _lib.DimsNotBuilt(_lib.ERR_DIMS, who, f"hop_length = {hop_length}: needs 1 <= hop_length <= n_fft / 2 = {n_fft // 2} (the overlap-added "
+                                "squared window must have no zero)")
+    if t.dtype != torch.float32:
+        raise NotImplementedError(f"{who} is exact fp32: got {t.dtype}")
+    if not t.is_cuda:
+        raise NotImplementedError(f"{who} runs on a ROCm device only: there is no CPU fallback")
+
+
+def _frames_arg(lengths, B: int, T: int, device: torch.device, who: str):
+    """lengths (None, a sequence, a host or a device tensor of mel frames) -> ([B] int32 on the device or None, whether the host
+    has not seen the values)."""
+    if T < 2:
+        raise ValueError(f"{who}: {T} frame(s): an utterance needs at least 2 frames to have samples")
+    if lengths is None:
+        return None, False
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if tuple(lengths.shape) != (B,):
+            raise ValueError(f"{who}: lengths must be [B] = [{B}], got {tuple(lengths.shape)}")
+        return lengths.to(device=device, dtype=torch.int32).contiguous(), True
+    host = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+    if len(host) != B or any(v < 2 or v > T for v in host):
+        raise ValueError(f"{who}: lengths must be [B] = [{B}] frame counts in [2, {T}], got {host}")
+    return torch.tensor(host, dtype=torch.int32).to(device), False
+
+
+def griffinlim_native(mag: torch.Tensor, n_fft: int, hop_length: int, win_length: int, n_iter: int = 32, momentum: float = 0.99,
+                      rand_init: bool = True, generator: Optional[torch.Generator] = None, *, lengths=None, angles: Optional[torch.Tensor] = None,
+                      tprev: Optional[torch.Tensor] = None, normalize: bool = False, return_state: bool = False):
+    """``griffinlim`` through ttsdec_griffinlim, on the magnitude itself (no ``power``): mag [B, n_freqs, T] (or [n_freqs, T]) fp32
+    on a ROCm device -> waveform [B, hop_length * (T - 1)].
+
+    The start is ``angles`` ([B, n_freqs, T] complex) when given; else with ``rand_init`` it is drawn by the same two
+    ``torch.rand`` calls as ``griffinlim`` makes for a tensor of mag's shape, so one seed gives both paths one start - complex(re, im)
+    with re, im in [0, 1), not of unit modulus, as torchaudio has it; else all ones.  ``tprev`` (with ``angles``) continues a
+    run from its state.  ``lengths`` ([B] mel frames, host or device): every utterance is inverted alone, reflected at its own end,
+    and is zero past its hop_length * (frames - 1) samples.  ``normalize``: w / max |w| per utterance.  ``return_state``:
+    (wave, rebuilt, angles) - the last rebuilt spectrum (the next ``tprev``) and the phase factors of the final inverse."""
+    who = "griffinlim_native"
+    _check_native(mag, n_fft, hop_length, win_length, who)
+    if not 0 <= momentum < 1:
+        raise ValueError(f"{who}: momentum must be in [0, 1), got {momentum}")
+    if n_iter < 0:
+        raise ValueError(f"{who}: n_iter must be >= 0, got {n_iter}")
+    m3 = mag.unsqueeze(0) if mag.dim() == 2 else mag
+    if m3.dim() != 3 or m3.shape[1] != n_fft // 2 + 1:
+        raise ValueError(f"{who}: mag must be [B, n_fft / 2 + 1 = {n_fft // 2 + 1}, T], got {tuple(mag.shape)}")
+    dev = mag.device
+    B, bins, T = m3.shape
+    frames, on_device = _frames_arg(lengths, B, T, dev, who)
+
+    def state(t, name):
+        t = t.unsqueeze(0) if t.dim() == 2 else t
+        if tuple(t.shape) != (B, bins, T) or not t.is_complex():
+            raise ValueError(f"{who}: {name} must be complex [B, n_freqs, T] = [{B}, {bins}, {T}], got {t.dtype} {tuple(t.shape)}")
+        return t.to(device=dev, dtype=torch.complex64).contiguous()
+
+    if tprev is not None and angles is None:
+        raise ValueError(f"{who}: tprev continues a run and needs its angles")
+    if angles is not None:
+        angles = state(angles, "angles")
+    elif rand_init:
+        re = torch.rand(m3.shape, generator=generator, device=dev if generator is None or generator.device.type != "cpu" else "cpu")
+        im = torch.rand(m3.shape, generator=generator, device=re.device)
+        angles = torch.complex(re, im).to(dev)
+    tprev = state(tprev, "tprev") if tprev is not None else None
+    key = (n_fft, str(dev))
+    if key not in _windows:
+        _windows[key] = torch.hann_window(n_fft).to(dtype=torch.float32, device=dev)
+    keep = return_state and n_iter > 0
+    out = _engine(dev).griffinlim(m3.detach().contiguous(), frames, _windows[key], n_fft, hop_length,
+                                  torch.view_as_real(angles) if angles is not None else None,
+                                  torch.view_as_real(tprev) if tprev is not None else None, n_iter, float(momentum), normalize, keep, check=on_device)
+    if not return_state:
+        return out[0] if mag.dim() == 2 else out
+    if keep:
+        wave, rebuilt, ang = out
+    else:  # no iteration: the state is the one that came in
+        wave = out
+        ang = angles if angles is not None else torch.ones(B, bins, T, dtype=torch.complex64, device=dev)
+        rebuilt = tprev if tprev is not None else torch.zeros_like(ang)
+    return (wave[0], rebuilt[0], ang[0]) if mag.dim() == 2 else (wave, rebuilt, ang)
+
+
+def synth_audio_native(y: torch.Tensor, audio_frontend: AudioFrontend, lengths=None, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """``synth_audio`` for a padded batch on the device: y [B, T, n_mels] -> waves [B, hop_length * (T - 1)], each utterance
+    peak-normalised over its own samples and zero past them; ``lengths`` [B] in mel frames, on the host or the device.  (The two
+    ``torch.rand`` calls cover the whole batch, so for B > 1 the start differs from the one ``synth_audio`` draws utterance by
+    utterance from the same generator.)"""
+    fe = audio_frontend
+    mag = fe.mel_to_magnitude(y, lengths)
+    return griffinlim_native(mag, fe.n_fft, fe.config.hop_length, fe.n_fft, generator=generator, lengths=lengths, normalize=True)

@@ -8,95 +8,28 @@
 //   stft_kernel<MEL>   one workgroup per run of F consecutive frames of one utterance, F * n_fft = kTile.  The samples the run
 //                      covers are loaded once ((F - 1) * hop + n_fft of them, reflected by index), each frame is the real FFT of
 //                      n_fft points as a complex FFT of M = n_fft / 2 points z[n] = x[2n] + i x[2n + 1] plus the split step
-//                      X[k] = (Z[k] + conj Z[M - k]) / 2 - i W^k (Z[k] - conj Z[M - k]) / 2.  The complex FFT is a Stockham
-//                      autosort of radix-8 / radix-4 passes (M = 128: 8 4 4, 256: 8 8 4, 512: 8 8 8, 1024: 8 8 4 4) ping-ponging
-//                      between two LDS images; the first pass reads the window-weighted samples.  Complex element i of a frame
-//                      sits at i ^ (((i >> 3) ^ (i >> 6)) & 7): a pass's reads (lanes on consecutive i) and the stride-8 writes of
-//                      the first pass then touch every LDS bank once per lane group; the stride-64 writes of the second pass are
-//                      2-way.  The magnitudes go to LDS as [bin][F + 1] and leave as [B, bins, T] with the run's frames contiguous,
+//                      X[k] = (Z[k] + conj Z[M - k]) / 2 - i W^k (Z[k] - conj Z[M - k]) / 2.  The complex FFT is the Stockham
+//                      autosort of fft_lds.h (shared with griffinlim.hip); the first pass reads the window-weighted samples.
+//                      The magnitudes go to LDS as [bin][F + 1] and leave as [B, bins, T] with the run's frames contiguous,
 //                      or - MEL - through the basis to [B, n_mels, T] without reaching memory.
 //   mel_kernel         the same epilogue on a spec tile read from memory (ttsvits_spec_to_mel).
 // Frames at or past an utterance's count are exact zeros.  No sum depends on the batch or on the position of a frame in its run.
 #include <math.h>
 #include <stdint.h>
 
+#include "fft_lds.h"
 #include "kernels.h"
 
 using namespace ttsdec;
 
 namespace {
-constexpr int kThreads = 256;
+constexpr int kThreads = kFftThreads;
 constexpr int kTile = 4096;      // floats of one LDS image of a run: F frames x n_fft / 2 complex points
 constexpr int kMelFrames = 16;   // frames per workgroup of mel_kernel (bins <= 513), half of it above
 constexpr int kMaxMels = 256;
 enum { FLAG_REFLECT = 1, FLAG_EMPTY = 2, FLAG_RANGE = 4 };  // status word: len <= pad; no frame; a length beyond the row / frames beyond T
 
 inline HandleBase* base(ttsvits_handle* h) { return reinterpret_cast<HandleBase*>(h); }
-
-struct cf { float x, y; };
-__device__ inline cf cadd(cf a, cf b) { return {a.x + b.x, a.y + b.y}; }
-__device__ inline cf csub(cf a, cf b) { return {a.x - b.x, a.y - b.y}; }
-__device__ inline cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ inline cf mul_mi(cf a) { return {a.y, -a.x}; }  // a * -i
-__device__ inline int swz(int i) { return i ^ (((i >> 3) ^ (i >> 6)) & 7); }
-
-// natural-order DFTs of 4 and 8 points in registers
-__device__ inline void dft4(cf& v0, cf& v1, cf& v2, cf& v3) {
-  const cf a = cadd(v0, v2), b = csub(v0, v2), c = cadd(v1, v3), d = mul_mi(csub(v1, v3));
-  v0 = cadd(a, c);
-  v1 = cadd(b, d);
-  v2 = csub(a, c);
-  v3 = csub(b, d);
-}
-template <int R> __device__ inline void dft(cf* v);
-template <> __device__ inline void dft<4>(cf* v) { dft4(v[0], v[1], v[2], v[3]); }
-template <> __device__ inline void dft<8>(cf* v) {
-  constexpr float h = 0.70710678118654752440f;
-  cf e0 = cadd(v[0], v[4]), e1 = cadd(v[1], v[5]), e2 = cadd(v[2], v[6]), e3 = cadd(v[3], v[7]);
-  cf o0 = csub(v[0], v[4]), o1 = csub(v[1], v[5]), o2 = csub(v[2], v[6]), o3 = csub(v[3], v[7]);
-  o1 = {(o1.x + o1.y) * h, (o1.y - o1.x) * h};   // * (1 - i) / sqrt 2
-  o2 = mul_mi(o2);
-  o3 = {(o3.y - o3.x) * h, -(o3.x + o3.y) * h};  // * (-1 - i) / sqrt 2
-  dft4(e0, e1, e2, e3);
-  dft4(o0, o1, o2, o3);
-  v[0] = e0; v[2] = e1; v[4] = e2; v[6] = e3;
-  v[1] = o0; v[3] = o1; v[5] = o2; v[7] = o3;
-}
-
-// One Stockham pass of radix R over the F frames of the run: butterfly j of a frame reads elements j + r M / R, multiplies by
-// W_M^(r (j mod Ns) M / (Ns R)) = tw[r (j mod Ns) n_fft / (Ns R)], and writes the DFT to (j / Ns) Ns R + j mod Ns + r Ns.
-// FIRST: the elements are the window-weighted samples (samp: frame stride fs; win: the n_fft-point window).
-template <int R, bool FIRST>
-__device__ inline void fft_pass(const cf* __restrict__ src, cf* __restrict__ dst, const cf* __restrict__ tw, const float* __restrict__ samp,
-                                const float* __restrict__ win, int fs, int M, int lgM, int Ns, int F) {
-  constexpr int lgR = R == 8 ? 3 : 2;
-  const int lgPer = lgM - lgR, per = 1 << lgPer;
-  const int twq = (2 * M) / (Ns * R);
-  for (int w = threadIdx.x; w < (F << lgPer); w += kThreads) {
-    const int f = w >> lgPer, j = w & (per - 1);
-    cf v[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int i = j + (r << lgPer);
-      if (FIRST) {
-        const float* s = samp + f * fs + 2 * i;
-        v[r] = {s[0] * win[2 * i], s[1] * win[2 * i + 1]};
-      } else {
-        v[r] = src[(f << lgM) + swz(i)];
-      }
-    }
-    const int jl = j & (Ns - 1);
-    if (!FIRST) {
-      const int q = jl * twq;
-#pragma unroll
-      for (int r = 1; r < R; ++r) v[r] = cmul(v[r], tw[q * r]);
-    }
-    dft<R>(v);
-    const int o = ((j - jl) << lgR) + jl;
-#pragma unroll
-    for (int r = 0; r < R; ++r) dst[(f << lgM) + swz(o + r * Ns)] = v[r];
-  }
-}
 
 // log(max(basis @ S, 1e-5)) of the tile S [bins][ss] (frames t0 .. t0 + F - 1 of utterance b) -> mel [n_mels, T] of that utterance
 __device__ inline void mel_epilogue(const float* __restrict__ S, int ss, int bins, int F, int lgF, const float* __restrict__ basis,
@@ -194,25 +127,8 @@ __global__ __launch_bounds__(kThreads) void stft_kernel(const StftArgs a) {
   const int lgM = a.lgM;
   fft_pass<8, true>(nullptr, bufA, tw, samp, win, fs, M, lgM, 1, F);
   __syncthreads();
-  if (M == 128) {
-    fft_pass<4, false>(bufA, bufB, tw, nullptr, nullptr, 0, M, lgM, 8, F);
-    __syncthreads();
-    fft_pass<4, false>(bufB, bufA, tw, nullptr, nullptr, 0, M, lgM, 32, F);
-  } else {
-    fft_pass<8, false>(bufA, bufB, tw, nullptr, nullptr, 0, M, lgM, 8, F);
-    __syncthreads();
-    if (M == 512) fft_pass<8, false>(bufB, bufA, tw, nullptr, nullptr, 0, M, lgM, 64, F);
-    else fft_pass<4, false>(bufB, bufA, tw, nullptr, nullptr, 0, M, lgM, 64, F);
-  }
-  __syncthreads();
-  const cf* Z = bufA;
-  float* S = reinterpret_cast<float*>(bufB);
-  if (M == 1024) {
-    fft_pass<4, false>(bufA, bufB, tw, nullptr, nullptr, 0, M, lgM, 256, F);
-    __syncthreads();
-    Z = bufB;
-    S = reinterpret_cast<float*>(bufA);
-  }
+  const cf* Z = fft_rest(bufA, bufB, tw, M, lgM, F);
+  float* S = reinterpret_cast<float*>(Z == bufA ? bufB : bufA);
   // ---- split step and magnitude: S[k][f], k <= M ----
   const int ss = F + 1;
   for (int idx = tid; idx < bins * F; idx += kThreads) {

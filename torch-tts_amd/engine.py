@@ -209,6 +209,14 @@ class Handle:
         self._ws = None
 
 
+def _raise_frame_flags(flags: int, T: int) -> None:
+    """The status word of ttsdec_mel_to_magnitude / ttsdec_griffinlim (include/ttsdec.h)."""
+    if flags & 4:
+        raise ValueError(f"an utterance's length exceeds the tensor's {T} frames")
+    if flags & 1:
+        raise ValueError("an utterance has fewer than 2 frames: it has no samples (hop_length * (frames - 1))")
+
+
 class Engine(Handle):
     """One ttsdec handle bound to one device."""
 
@@ -246,6 +254,46 @@ class Engine(Handle):
             self._err(self._lib.ttsdec_bind_weights(self._h, blob.data_ptr()), "ttsdec_bind_weights")
         self.blob = blob
         self._fingerprint = None
+
+    # ---- mel -> waveform (weightless: a handle of any dims serves, bound or not; audio.py holds the entry points) ----
+    def mel_to_magnitude(self, y: Tensor, P: Tensor, frames: Optional[Tensor], n_fft: int, *, check: bool = False) -> Tensor:
+        """y [B, T, n_mels], P [n_fft / 2 + 1, n_mels] contiguous fp32, frames [B] int32 (device) or None -> mag [B, bins, T]
+        (ttsdec_mel_to_magnitude).  check: read the status word back (one host sync) and raise for a refused utterance."""
+        B, T, n_mels = y.shape
+        mag = torch.empty(B, n_fft // 2 + 1, T, device=self.device)
+        status = torch.empty(1, dtype=torch.int32, device=self.device) if check else None
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsdec_mel_to_magnitude(self._h, y.data_ptr(), P.data_ptr(), _ptr(frames), B, T, n_mels, n_fft, mag.data_ptr(),
+                                                   _ptr(status), _stream(self.device))
+        self._err(rc, "ttsdec_mel_to_magnitude")
+        if check:
+            _raise_frame_flags(int(status.item()), T)
+        return mag
+
+    def griffinlim(self, mag: Tensor, frames: Optional[Tensor], window: Tensor, n_fft: int, hop_length: int, angles: Optional[Tensor],
+                   tprev: Optional[Tensor], n_iter: int, momentum: float, normalize: bool, return_state: bool, *, check: bool = False):
+        """mag [B, n_fft / 2 + 1, T] contiguous fp32, angles / tprev [B, bins, T] contiguous complex64 or None -> wave
+        [B, hop_length * (T - 1)], and with return_state (n_iter >= 1) the last rebuilt spectrum and the final phase factors
+        (ttsdec_griffinlim)."""
+        B, bins, T = mag.shape
+        nbytes = int(self._lib.ttsdec_griffinlim_workspace_bytes(self._h, B, T, n_fft))
+        if not nbytes:
+            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsdec_griffinlim", f"B = {B}, T = {T}, n_fft = {n_fft}: built for n_fft 256 / 512 / 1024 / 2048, "
+                                    "T >= 2, B <= 65535")
+        ws = self.workspace("griffinlim", nbytes)
+        wave = torch.empty(B, hop_length * (T - 1), device=self.device)
+        state = [torch.empty(B, bins, T, dtype=torch.complex64, device=self.device) for _ in range(2)] if return_state else [None, None]
+        status = torch.empty(1, dtype=torch.int32, device=self.device) if check else None
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsdec_griffinlim(self._h, mag.data_ptr(), _ptr(frames), B, T, window.data_ptr(), n_fft, hop_length, _ptr(angles),
+                                             _ptr(tprev), n_iter, momentum, int(normalize), wave.data_ptr(), _ptr(state[0]), _ptr(state[1]),
+                                             _ptr(status), ws.data_ptr(), ws.numel(), _stream(self.device))
+        if rc == _lib.ERR_DIMS:
+            raise _lib.DimsNotBuilt(rc, "ttsdec_griffinlim", f"n_fft = {n_fft}, hop_length = {hop_length}: needs hop_length <= n_fft / 2")
+        self._err(rc, "ttsdec_griffinlim")
+        if check:
+            _raise_frame_flags(int(status.item()), T)
+        return (wave, state[0], state[1]) if return_state else wave
 
     # ---- workspaces ----
     def step_workspace(self, B: int, L: int) -> Tensor:
