@@ -249,3 +249,137 @@ def test_refusals():
     assert lib.ttspost_forward(*args(g.data_ptr(), nbytes)) == _lib.ERR_INVALID_ARG  # g on a gin-0 handle
     assert lib.ttspost_forward(*args(None, nbytes - 256)) == _lib.ERR_WORKSPACE  # short workspace
     torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 7. the one-element (W = 1) kernels of the flow: a z / out that is only 4-byte aligned; 8. the reported workspace size is the layout
+# ---------------------------------------------------------------------------------------------------------------------------
+SMALL_B, SMALL_T, SMALL_LENGTHS = 2, 37, [37, 5]
+PATTERN = 0xA5
+
+
+def _small_flow(prec):
+    """The flow of the golden fixture (four couplings, gin 8) with its inputs at B = 2, T = 37: -> module, z [B, T, C], lengths, g."""
+    sd, meta = load_golden()
+    f = meta["flow"]
+    fl = _T().vits2.ResidualCouplingTransformersBlock(f["channels"], f["hidden"], f["kernel"], 1, f["n_layers"], f["n_flows"], gin_channels=f["gin"],
+                                                      use_transformer_flows=True)
+    fl.load_state_dict(weights(sd, "flow"), strict=False)
+    fl = fl.cuda().eval()
+    fl.precision = prec
+    assert fl.n_flows >= 2
+    gen = torch.Generator().manual_seed(31)
+    z = torch.randn(SMALL_B, SMALL_T, f["channels"], generator=gen).cuda()
+    g = torch.randn(SMALL_B, f["gin"], generator=gen).cuda()
+    return fl, z, torch.tensor(SMALL_LENGTHS, dtype=torch.int32).cuda(), g
+
+
+def _one_float_in(t, tail=4):
+    """t's values in a contiguous view one float into a larger buffer (4-byte, not 16-byte aligned); -> view, the floats behind it."""
+    buf = torch.empty(t.numel() + 1 + tail, device=t.device).view(torch.uint8).fill_(PATTERN).view(torch.float32)
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v, buf[1 + t.numel():]
+
+
+@pytest.mark.parametrize("prec", ["f32", "split_f16"])
+def test_flow_misaligned_input_equals_aligned(prec):
+    fl, z, lens, g = _small_flow(prec)
+    zm, _ = _one_float_in(z)
+    assert z.data_ptr() % 16 == 0 and torch.equal(zm, z)
+    with torch.no_grad():
+        for run in (fl.forward_cl, fl.reverse_cl):  # the first coupling takes the W = 1 split, residual and coupling, the later ones W = 4
+            want, got = run(z, lens, g), run(zm, lens, g)
+            assert torch.equal(got, want), (prec, run.__name__, float((got - want).abs().max()))
+            assert float(want.abs().max()) > 0
+
+
+@pytest.mark.parametrize("prec", ["f32", "split_f16"])
+def test_flow_forward_misaligned_output_equals_aligned(prec):
+    from torch_tts_amd import _lib
+
+    fl, z, lens, g = _small_flow(prec)
+    with torch.no_grad():
+        want = fl.forward_cl(z, lens, g)
+        eng = fl._engine(z)
+    nbytes = int(eng._lib.ttsvits_flow_workspace_bytes(eng._h, SMALL_B, SMALL_T))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    out, behind = _one_float_in(torch.zeros_like(z))  # (only a direct call reaches the W = 1 flip copy-out: the wrapper allocates out)
+    rc = eng._lib.ttsvits_flow_forward(eng._h, z.data_ptr(), lens.data_ptr(), g.data_ptr(), SMALL_B, SMALL_T, out.data_ptr(), ws.data_ptr(), nbytes,
+                                       None)
+    torch.cuda.synchronize()
+    assert rc == _lib.OK
+    assert torch.equal(out, want)
+    assert behind.numel() == 4 and bool((behind.view(torch.uint8) == PATTERN).all())
+
+
+def _size_is_the_layout(nbytes, run):
+    """run(workspace pointer, bytes) -> rc, outputs: with exactly the reported bytes the call succeeds, computes what it computes in a
+    much larger workspace and leaves the bytes behind them alone; with one byte less it is refused."""
+    from torch_tts_amd import _lib
+
+    big = torch.zeros(4 * nbytes + (1 << 20), dtype=torch.uint8, device="cuda")
+    rc, want = run(big.data_ptr(), big.numel())
+    assert rc == _lib.OK
+    buf = torch.full((nbytes + 4096,), PATTERN, dtype=torch.uint8, device="cuda")
+    assert buf.data_ptr() % 256 == 0
+    rc, got = run(buf.data_ptr(), nbytes)
+    torch.cuda.synchronize()
+    assert rc == _lib.OK
+    for a, b in zip(got, want):
+        assert torch.equal(a, b) and float(b.abs().max()) > 0
+    assert bool((buf[nbytes:] == PATTERN).all())
+    rc, _ = run(buf.data_ptr(), nbytes - 1)
+    assert rc == _lib.ERR_WORKSPACE
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("prec", ["f32", "split_f16"])
+def test_reported_workspace_size_is_the_layout(prec):
+    B, T = SMALL_B, SMALL_T
+    gen = torch.Generator().manual_seed(32)
+    # the flow (g given: cond, the last buffer, is in use)
+    fl, z, lens, g = _small_flow(prec)
+    with torch.no_grad():
+        eng = fl._engine(z)  # packs the blob
+    lib = eng._lib
+
+    def run_flow(ws, n):
+        out = torch.empty_like(z)
+        return lib.ttsvits_flow_forward(eng._h, z.data_ptr(), lens.data_ptr(), g.data_ptr(), B, T, out.data_ptr(), ws, n, None), (out,)
+
+    _size_is_the_layout(int(lib.ttsvits_flow_workspace_bytes(eng._h, B, T)), run_flow)
+    # the text encoder (g given: the projected speaker embedding is its last buffer)
+    te = randomize(_T().vits2.TextEncoder(23, 16, 32, 48, 2, 3, 3, 0.1, gin_channels=8), 33).cuda().eval()
+    te.precision = prec
+    ids = torch.randint(0, 23, (B, T), generator=gen).cuda()
+    with torch.no_grad():
+        te.forward_cl(ids, lens, g)  # packs the blob
+    et = te._engines.get(te._dims(), ids.device)
+    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+    def run_text(ws, n):
+        x, m, logs = torch.empty(B, T, 32, device="cuda"), torch.empty(B, T, 16, device="cuda"), torch.empty(B, T, 16, device="cuda")
+        rc = lib.ttsvits_text_encoder(et._h, ids.data_ptr(), lens.data_ptr(), g.data_ptr(), B, T, x.data_ptr(), m.data_ptr(), logs.data_ptr(), ws, n,
+                                      None, status.data_ptr())
+        return rc, (x, m, logs)
+
+    _size_is_the_layout(int(lib.ttsvits_text_encoder_workspace_bytes(et._h, B, T)), run_text)
+    assert int(status) == 0
+    # the posterior encoder (13 spectrogram channels: padded to 16)
+    pe = _post(13, 8, 34, n_layers=3, inter=8, hidden=16)
+    pe.precision = prec
+    y = torch.randn(B, 13, T, generator=gen).cuda()
+    eps = torch.randn(B, 8, T, generator=gen).cuda()
+    with torch.no_grad():
+        pe.forward_cl(y, lens, g, noise=eps)  # packs the blob
+    ep = pe._engines.get(pe._cfg, y.device)
+
+    def run_post(ws, n):
+        zml = [torch.empty(B, T, 8, device="cuda") for _ in range(3)]
+        rc = lib.ttspost_forward(ep._h, y.data_ptr(), lens.data_ptr(), g.data_ptr(), eps.data_ptr(), T, B, T, zml[0].data_ptr(), zml[1].data_ptr(),
+                                 zml[2].data_ptr(), ws, n, None)
+        return rc, zml
+
+    _size_is_the_layout(int(lib.ttspost_workspace_bytes(ep._h, B, T)), run_post)

@@ -250,6 +250,55 @@ def test_ttspost_symbols_exported_and_tensor_count_matches_header():
         assert lib.ttspost_create(C.byref(_lib.PostDims(**kw)), C.byref(h)) == _lib.ERR_DIMS, bad
 
 
+# (name, B, T) -> bytes of ttsvits_text_encoder / ttsvits_flow / ttspost workspaces, as the library reported them before the size
+# functions became the carve routines' totals: the layouts may be rewritten, the reported sizes may not change
+WORKSPACE_BYTES = [
+    ("small", 1, 1, 5952, 7840, 3840),
+    ("small", 2, 37, 150912, 127040, 68864),
+    ("small", 3, 200, 1196800, 986880, 541440),
+    ("small_g", 1, 1, 5952, 7840, 3840),
+    ("small_g", 2, 37, 150912, 127040, 68864),
+    ("small_g", 3, 200, 1196800, 986880, 541440),
+    ("modelconfig", 1, 1, 22784, 25216, 40960),
+    ("modelconfig", 2, 37, 1369344, 1152768, 1193984),
+    ("modelconfig", 3, 200, 11067392, 9240320, 9349888),
+    ("modelconfig_g", 1, 1, 22784, 25216, 40960),
+    ("modelconfig_g", 2, 37, 1369344, 1152768, 1193984),
+    ("modelconfig_g", 3, 200, 11067392, 9240320, 9349888),
+]
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    import dataclasses
+
+    from torch_tts_amd import _lib
+
+    lib = _lib.load()
+    vm = json.load(open(os.path.join(HERE, "golden", "vits2_meta.json")))
+    vits = {"small": vm["dims"], "small_g": vm["dims_g"], "modelconfig": dataclasses.asdict(V.Vits2Dims()),
+            "modelconfig_g": dataclasses.asdict(V.Vits2Dims(gin_channels=256))}
+    small_post = dict(inter_channels=8, hidden_channels=16, kernel_size=5, n_layers=3)  # vc_meta.json "post"
+    full_post = dict(spec_channels=513, inter_channels=192, hidden_channels=192, kernel_size=5, n_layers=16)
+    post = {"small": dict(small_post, spec_channels=13, gin_channels=0), "small_g": dict(small_post, spec_channels=16, gin_channels=8),
+            "modelconfig": dict(full_post, gin_channels=0), "modelconfig_g": dict(full_post, gin_channels=256)}
+    handles = {}
+    for name in vits:
+        d = dict(dict(gin_channels=0, cond_layer_idx=0), **vits[name])
+        hv, hp = C.c_void_p(), C.c_void_p()
+        assert lib.ttsvits_create(C.byref(_lib.VitsDims(*[int(d[n]) for n, _ in _lib.VitsDims._fields_])), C.byref(hv)) == _lib.OK
+        assert lib.ttspost_create(C.byref(_lib.PostDims(**post[name])), C.byref(hp)) == _lib.OK
+        handles[name] = (hv, hp)
+    for name, B, T, te, fl, po in WORKSPACE_BYTES:
+        hv, hp = handles[name]
+        got = (lib.ttsvits_text_encoder_workspace_bytes(hv, B, T), lib.ttsvits_flow_workspace_bytes(hv, B, T), lib.ttspost_workspace_bytes(hp, B, T))
+        assert got == (te, fl, po), (name, B, T, got)
+    for hv, hp in handles.values():
+        assert lib.ttsvits_text_encoder_workspace_bytes(hv, 0, 5) == 0 and lib.ttsvits_flow_workspace_bytes(hv, 2, 0) == 0
+        assert lib.ttspost_workspace_bytes(hp, -1, 5) == 0
+        lib.ttsvits_destroy(hv)
+        lib.ttspost_destroy(hp)
+
+
 def test_voice_conversion_refuses_what_is_not_on_the_path():
     import torch_tts_amd as T
 

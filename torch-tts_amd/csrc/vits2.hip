@@ -906,252 +906,181 @@ __global__ void add_spk_kernel(float* x, f16* x_p, const float* gvec, const floa
   if (x_p) split_f16(v, x_p[i], x_p[(size_t)M * C + i]);
 }
 
-// commons.fused_add_tanh_sigmoid_multiply with g = None (commons.py:102-109): [M, 2H] -> [M, H]
-__global__ void wn_gate_kernel(const float* xin, float* acts, f16* acts_p, int M, int H, const float* gl, int T, int ldg) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)M * H) return;
-  const size_t m = i / H, c = i % H;
-  float a = xin[m * 2 * H + c], s = xin[m * 2 * H + H + c];
-  if (gl != nullptr) { a = add_rn(a, gl[(m / T) * ldg + c]); s = add_rn(s, gl[(m / T) * ldg + H + c]); }
-  const float v = mul_rn(tanhf(a), sigmoid_f(s));
-  if (acts != nullptr) acts[i] = v;  // (nullptr: the consumer - the res/skip GEMM in split-fp16 mode - reads the planes only)
-  if (acts_p) split_f16(v, acts_p[i], acts_p[(size_t)M * H + i]);
-}
-// modules.WN.forward:201-208: not last: x = (x + rs[:, :H]) * mask; output += rs[:, H:]
-//                             last:     output = (output + rs) * mask   (the final `output * x_mask` folded in)
-__global__ void wn_update_kernel(float* x, float* output, const float* rs, const float* mask, f16* x_p, f16* out_p, int M, int H, int last,
-                                 int first) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)M * H) return;
-  const size_t m = i / H, c = i % H;
-  const float o = first ? 0.f : output[i];
-  const size_t n = (size_t)M * H;
-  if (last) {
-    const float v = mul_rn(add_rn(o, rs[m * H + c]), mask[m]);
-    output[i] = v;
-    if (out_p) split_f16(v, out_p[i], out_p[n + i]);
-  } else {
-    const float v = mul_rn(add_rn(x[i], rs[m * 2 * H + c]), mask[m]);
-    x[i] = v;
-    if (x_p) split_f16(v, x_p[i], x_p[n + i]);
-    output[i] = add_rn(o, rs[m * 2 * H + H + c]);
-  }
-}
-// The same two kernels, four channels per thread (H % 4 == 0, fewer than 2^32 elements): 16-byte loads and stores, 8-byte
-// plane stores, one 32-bit division per four elements instead of a 64-bit one per element.  As one-element kernels they
-// were bound by their instruction streams (the division; tanhf + expf + an exact division per gate: ~100 instructions per
-// element), not by the 59 / 103 MB they stream.  kFast (the split-fp16 mode, whose GEMMs round these values to 22 bits
-// anyway): the gate on the hardware exp / rcp like the decoder's LSTM cell (common.h tanh_fast / sigmoid_fast); the
-// exact-fp32 mode keeps the library functions.
+// The elementwise steps of the WN and flow path, each one kernel templated on W, the channels a thread handles.
+// W = 4 (the channel count a multiple of 4 - of 8 where a row is split in halves -, fewer than 2^32 elements, every caller's
+// pointer 16-byte aligned: four_wide below): 16-byte loads and stores, 8-byte plane stores, 32-bit indices with one division per
+// four elements instead of a 64-bit one per element.  As one-element kernels they were bound by their instruction streams (the
+// division; tanhf + expf + an exact division per gate: ~100 instructions per element), not by the 59 / 103 MB they stream.
+// W = 1 covers the rest: size_t indices, one element per thread.  A kernel's channel counts arrive divided by W.
+typedef float f32x1 __attribute__((ext_vector_type(1)));
+typedef _Float16 f16x1v __attribute__((ext_vector_type(1)));
 typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split4_store(const f32x4& v, f16* planes, size_t n, size_t i4) {
-  f16x4v hi, lo;
+template <int W> using ew_idx = std::conditional_t<W == 4, uint32_t, size_t>;  // element and row indices
+template <int W> using ew_dim = std::conditional_t<W == 4, uint32_t, int>;     // the sizes as the kernel takes them
+template <int W> using ew_vec = std::conditional_t<W == 4, f32x4, f32x1>;
+template <int W> using ew_hvec = std::conditional_t<W == 4, f16x4v, f16x1v>;
+// the split-fp16 planes of v, W elements at element W * i: hi at planes, lo n halfs later
+template <int W>
+__device__ __forceinline__ void split_store(const ew_vec<W>& v, f16* planes, size_t n, size_t i) {
+  ew_hvec<W> hi, lo;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
+  for (int e = 0; e < W; ++e) {
     f16 h, l;
     split_f16(v[e], h, l);
     hi[e] = h;
     lo[e] = l;
   }
-  *reinterpret_cast<f16x4v*>(planes + 4 * i4) = hi;
-  *reinterpret_cast<f16x4v*>(planes + n + 4 * i4) = lo;
+  *reinterpret_cast<ew_hvec<W>*>(planes + W * i) = hi;
+  *reinterpret_cast<ew_hvec<W>*>(planes + n + W * i) = lo;
 }
+// commons.fused_add_tanh_sigmoid_multiply (commons.py:102-109): [M, 2H] -> [M, H]
 // (gl != nullptr: g_l of modules.py:193-199, the speaker conditioning of this WN layer - constant over an utterance's frames, so a
 // [B, ldg] matrix whose row is the frame's utterance; the reference adds it to x_in before the two activations, commons.py:102-109)
-template <bool kFast>
-__global__ void wn_gate4_kernel(const float* xin, float* acts, f16* acts_p, uint32_t M, uint32_t H4, const float* gl, uint32_t T, uint32_t ldg) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M * H4) return;
-  const uint32_t m = i / H4, c4 = i - m * H4;
-  const f32x4* row = reinterpret_cast<const f32x4*>(xin) + (size_t)m * 2 * H4;
-  f32x4 a = row[c4], s = row[H4 + c4];
+// kFast (the split-fp16 mode, whose GEMMs round these values to 22 bits anyway): the gate on the hardware exp / rcp like the
+// decoder's LSTM cell (common.h tanh_fast / sigmoid_fast); the exact-fp32 mode keeps the library functions.
+template <int W, bool kFast>
+__global__ void wn_gate_kernel(const float* xin, float* acts, f16* acts_p, ew_dim<W> M, ew_dim<W> H, const float* gl,
+                               ew_dim<W> T, ew_dim<W> ldg) {
+  using idx = ew_idx<W>;
+  using vec = ew_vec<W>;
+  const idx i = (idx)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (idx)M * H) return;
+  const idx m = i / H, c = i - m * H;
+  const vec* row = reinterpret_cast<const vec*>(xin) + (size_t)m * 2 * H;
+  vec a = row[c], s = row[H + c];
   if (gl != nullptr) {
-    const f32x4* grow = reinterpret_cast<const f32x4*>(gl + (size_t)(m / T) * ldg);
-    const f32x4 ga = grow[c4], gs = grow[H4 + c4];
+    const vec* grow = reinterpret_cast<const vec*>(gl + (size_t)(m / T) * ldg);
+    const vec ga = grow[c], gs = grow[H + c];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { a[e] = add_rn(a[e], ga[e]); s[e] = add_rn(s[e], gs[e]); }
+    for (int e = 0; e < W; ++e) { a[e] = add_rn(a[e], ga[e]); s[e] = add_rn(s[e], gs[e]); }
   }
-  f32x4 v;
+  vec v;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = kFast ? mul_rn(tanh_fast(a[e]), sigmoid_fast(s[e])) : mul_rn(tanhf(a[e]), sigmoid_f(s[e]));
-  if (acts != nullptr) reinterpret_cast<f32x4*>(acts)[i] = v;  // (nullptr: see wn_gate_kernel)
-  if (acts_p) split4_store(v, acts_p, (size_t)M * H4 * 4, i);
+  for (int e = 0; e < W; ++e) v[e] = kFast ? mul_rn(tanh_fast(a[e]), sigmoid_fast(s[e])) : mul_rn(tanhf(a[e]), sigmoid_f(s[e]));
+  if (acts != nullptr) reinterpret_cast<vec*>(acts)[i] = v;  // (nullptr: the consumer - the res/skip GEMM in split-fp16 mode - reads the planes only)
+  if (acts_p) split_store<W>(v, acts_p, (size_t)M * H * W, i);
 }
-__global__ void wn_update4_kernel(float* x, float* output, const float* rs, const float* mask, f16* x_p, f16* out_p, uint32_t M, uint32_t H4,
-                                  int last, int first) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M * H4) return;
-  const uint32_t m = i / H4, c4 = i - m * H4;
-  const size_t n = (size_t)M * H4 * 4;
+// modules.WN.forward:201-208: not last: x = (x + rs[:, :H]) * mask; output += rs[:, H:]
+//                             last:     output = (output + rs) * mask   (the final `output * x_mask` folded in)
+template <int W>
+__global__ void wn_update_kernel(float* x, float* output, const float* rs, const float* mask, f16* x_p, f16* out_p, ew_dim<W> M,
+                                 ew_dim<W> H, int last, int first) {
+  using idx = ew_idx<W>;
+  using vec = ew_vec<W>;
+  const idx i = (idx)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (idx)M * H) return;
+  const idx m = i / H, c = i - m * H;
+  const size_t n = (size_t)M * H * W;
   const float mk = mask[m];
-  f32x4 o = {0.f, 0.f, 0.f, 0.f};
-  if (!first) o = reinterpret_cast<const f32x4*>(output)[i];
-  f32x4 v;
+  vec o = {};
+  if (!first) o = reinterpret_cast<const vec*>(output)[i];
+  vec v;
   if (last) {
-    const f32x4 r = reinterpret_cast<const f32x4*>(rs)[(size_t)m * H4 + c4];
+    const vec r = reinterpret_cast<const vec*>(rs)[(size_t)m * H + c];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = mul_rn(add_rn(o[e], r[e]), mk);
-    reinterpret_cast<f32x4*>(output)[i] = v;
-    if (out_p) split4_store(v, out_p, n, i);
+    for (int e = 0; e < W; ++e) v[e] = mul_rn(add_rn(o[e], r[e]), mk);
+    reinterpret_cast<vec*>(output)[i] = v;
+    if (out_p) split_store<W>(v, out_p, n, i);
   } else {
-    const f32x4* row = reinterpret_cast<const f32x4*>(rs) + (size_t)m * 2 * H4;
-    const f32x4 r0 = row[c4], r1 = row[H4 + c4], xv = reinterpret_cast<const f32x4*>(x)[i];
-    f32x4 on;
+    const vec* row = reinterpret_cast<const vec*>(rs) + (size_t)m * 2 * H;
+    const vec r0 = row[c], r1 = row[H + c], xv = reinterpret_cast<const vec*>(x)[i];
+    vec on;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
+    for (int e = 0; e < W; ++e) {
       v[e] = mul_rn(add_rn(xv[e], r0[e]), mk);
       on[e] = add_rn(o[e], r1[e]);
     }
-    reinterpret_cast<f32x4*>(x)[i] = v;
-    if (x_p) split4_store(v, x_p, n, i);
-    reinterpret_cast<f32x4*>(output)[i] = on;
+    reinterpret_cast<vec*>(x)[i] = v;
+    if (x_p) split_store<W>(v, x_p, n, i);
+    reinterpret_cast<vec*>(output)[i] = on;
   }
 }
-// modules.Flip (modules.py:374-381) + split: xf = flip(x); x0m = xf[:, :half] * mask
-__global__ void flip_split_kernel(const float* x, const float* mask, float* xf, float* x0m, f16* x0m_p, int M, int I) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)M * I) return;
-  const size_t m = i / I, c = i % I;
-  const float v = x[m * I + (I - 1 - c)];
-  xf[i] = v;
-  const int half = I / 2;
-  if ((int)c < half) {
-    const float vm = mul_rn(v, mask[m]);
-    const size_t o = m * half + c;
-    x0m[o] = vm;
-    if (x0m_p) split_f16(vm, x0m_p[o], x0m_p[(size_t)M * half + o]);
+// The split in front of a coupling: xf = x, or flip(x) where a modules.Flip (modules.py:374-381) precedes it; x0m = xf[:, :half] * mask.
+// The reverse direction (models.py:807-809) runs Flip, layer_{n-1}, ..., Flip, layer_0: every split flips.  The forward direction
+// (models.py:506-526, 803-806) runs layer_0, Flip, layer_1, Flip, ...: no Flip in front of the first coupling, so its split copies x
+// as it stands, and the last Flip is folded into the copy-out (copy_out_kernel).  (W = 4: the flip reverses the four-channel groups
+// and the lanes of each.)
+template <int W, bool kFlip>
+__global__ void split_kernel(const float* x, const float* mask, float* xf, float* x0m, f16* x0m_p, ew_dim<W> M, ew_dim<W> I) {
+  using idx = ew_idx<W>;
+  using dim = ew_dim<W>;
+  using vec = ew_vec<W>;
+  const idx i = (idx)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (idx)M * I) return;
+  const idx m = i / I, c = i - m * I;
+  const dim half = I / 2;
+  vec v;
+  if (kFlip) {
+    const vec s = reinterpret_cast<const vec*>(x)[(size_t)m * I + (I - 1 - c)];
+#pragma unroll
+    for (int e = 0; e < W; ++e) v[e] = s[W - 1 - e];
+  } else {
+    v = reinterpret_cast<const vec*>(x)[i];
+  }
+  reinterpret_cast<vec*>(xf)[i] = v;
+  if ((dim)c < half) {
+    const float mk = mask[m];
+    vec vm;
+#pragma unroll
+    for (int e = 0; e < W; ++e) vm[e] = mul_rn(v[e], mk);
+    const size_t o = (size_t)m * half + c;
+    reinterpret_cast<vec*>(x0m)[o] = vm;
+    if (x0m_p) split_store<W>(vm, x0m_p, (size_t)M * half * W, o);
   }
 }
 // x0_ = pre_transformer(...) + x0 (models.py:509): enc [M, half] += xf[:, :half]
-__global__ void add_x0_kernel(float* enc, f16* enc_p, const float* xf, int M, int I) {
-  const int half = I / 2;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)M * half) return;
-  const size_t m = i / half, c = i % half;
-  const float v = add_rn(enc[i], xf[m * I + c]);
-  enc[i] = v;
-  if (enc_p) split_f16(v, enc_p[i], enc_p[(size_t)M * half + i]);
-}
-// x1 = (x1 - m) * exp(-0) * mask (models.py:529): xf[:, half:] updated in place; mm is post(h) * mask
-__global__ void couple_kernel(float* xf, const float* mm, const float* mask, int M, int I) {
-  const int half = I / 2;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)M * half) return;
-  const size_t m = i / half, c = i % half;
-  float* p = xf + m * I + half + c;
-  *p = mul_rn(mul_rn(sub_rn(*p, mm[i]), 1.0f), mask[m]);
-}
-// flip+split, x0 residual and the coupling update, four channels per thread (I % 8 == 0, fewer than 2^32 elements)
-__global__ void flip_split4_kernel(const float* x, const float* mask, float* xf, float* x0m, f16* x0m_p, uint32_t M, uint32_t I4) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M * I4) return;
-  const uint32_t m = i / I4, c4 = i - m * I4, half4 = I4 / 2;
-  const f32x4 s = reinterpret_cast<const f32x4*>(x)[(size_t)m * I4 + (I4 - 1 - c4)];
-  const f32x4 v = {s[3], s[2], s[1], s[0]};
-  reinterpret_cast<f32x4*>(xf)[i] = v;
-  if (c4 < half4) {
-    const float mk = mask[m];
-    f32x4 vm;
+template <int W>
+__global__ void add_x0_kernel(float* enc, f16* enc_p, const float* xf, ew_dim<W> M, ew_dim<W> I) {
+  using idx = ew_idx<W>;
+  using vec = ew_vec<W>;
+  const ew_dim<W> half = I / 2;
+  const idx i = (idx)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (idx)M * half) return;
+  const idx m = i / half, c = i - m * half;
+  const vec a = reinterpret_cast<const vec*>(enc)[i], b = reinterpret_cast<const vec*>(xf)[(size_t)m * I + c];
+  vec v;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) vm[e] = mul_rn(v[e], mk);
-    const size_t o = (size_t)m * half4 + c4;
-    reinterpret_cast<f32x4*>(x0m)[o] = vm;
-    if (x0m_p) split4_store(vm, x0m_p, (size_t)M * half4 * 4, o);
-  }
+  for (int e = 0; e < W; ++e) v[e] = add_rn(a[e], b[e]);
+  reinterpret_cast<vec*>(enc)[i] = v;
+  if (enc_p) split_store<W>(v, enc_p, (size_t)M * half * W, i);
 }
-__global__ void add_x04_kernel(float* enc, f16* enc_p, const float* xf, uint32_t M, uint32_t I4) {
-  const uint32_t half4 = I4 / 2;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M * half4) return;
-  const uint32_t m = i / half4, c4 = i - m * half4;
-  const f32x4 a = reinterpret_cast<const f32x4*>(enc)[i], b = reinterpret_cast<const f32x4*>(xf)[(size_t)m * I4 + c4];
-  f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = add_rn(a[e], b[e]);
-  reinterpret_cast<f32x4*>(enc)[i] = v;
-  if (enc_p) split4_store(v, enc_p, (size_t)M * half4 * 4, i);
-}
-__global__ void couple4_kernel(float* xf, const float* mm, const float* mask, uint32_t M, uint32_t I4) {
-  const uint32_t half4 = I4 / 2;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M * half4) return;
-  const uint32_t m = i / half4, c4 = i - m * half4;
-  f32x4* p = reinterpret_cast<f32x4*>(xf) + (size_t)m * I4 + half4 + c4;
-  const f32x4 a = *p, b = reinterpret_cast<const f32x4*>(mm)[i];
+// The coupling, mean-only (logs = 0): xf[:, half:] updated in place; mm is post(h) * mask.
+//   reverse (models.py:529):  x1 = (x1 - m) * exp(-0) * mask
+//   kForward (models.py:522): x1 = m + x1 * exp(0) * mask
+template <int W, bool kForward>
+__global__ void couple_kernel(float* xf, const float* mm, const float* mask, ew_dim<W> M, ew_dim<W> I) {
+  using idx = ew_idx<W>;
+  using vec = ew_vec<W>;
+  const ew_dim<W> half = I / 2;
+  const idx i = (idx)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (idx)M * half) return;
+  const idx m = i / half, c = i - m * half;
+  vec* p = reinterpret_cast<vec*>(xf) + (size_t)m * I + half + c;
+  const vec a = *p, b = reinterpret_cast<const vec*>(mm)[i];
   const float mk = mask[m];
-  f32x4 v;
+  vec v;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = mul_rn(mul_rn(sub_rn(a[e], b[e]), 1.0f), mk);
+  for (int e = 0; e < W; ++e)
+    v[e] = kForward ? add_rn(b[e], mul_rn(mul_rn(a[e], 1.0f), mk)) : mul_rn(mul_rn(sub_rn(a[e], b[e]), 1.0f), mk);
   *p = v;
 }
-// The forward direction (models.py:506-526, 803-806): flows run layer_0, Flip, layer_1, Flip, ... - no Flip in front of the first
-// coupling, so its split copies x as it stands (the Flips between couplings are the flip_split kernels above, the last one is
-// folded into the copy-out, flip_copy_kernel).  split: xf = x; x0m = x[:, :half] * mask
-__global__ void split_kernel(const float* x, const float* mask, float* xf, float* x0m, f16* x0m_p, int M, int I) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)M * I) return;
-  const size_t m = i / I, c = i % I;
-  const float v = x[i];
-  xf[i] = v;
-  const int half = I / 2;
-  if ((int)c < half) {
-    const float vm = mul_rn(v, mask[m]);
-    const size_t o = m * half + c;
-    x0m[o] = vm;
-    if (x0m_p) split_f16(vm, x0m_p[o], x0m_p[(size_t)M * half + o]);
+// The copy-out.  kFlip: with the last Flip of the forward direction (modules.py:374-381), out[m, c] = x[m, I - 1 - c]; else out = x.
+template <int W, bool kFlip>
+__global__ void copy_out_kernel(const float* x, float* out, ew_dim<W> M, ew_dim<W> I) {
+  using idx = ew_idx<W>;
+  using vec = ew_vec<W>;
+  const idx i = (idx)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (idx)M * I) return;
+  if (!kFlip) {
+    reinterpret_cast<vec*>(out)[i] = reinterpret_cast<const vec*>(x)[i];
+    return;
   }
-}
-__global__ void split4_kernel(const float* x, const float* mask, float* xf, float* x0m, f16* x0m_p, uint32_t M, uint32_t I4) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M * I4) return;
-  const uint32_t m = i / I4, c4 = i - m * I4, half4 = I4 / 2;
-  const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-  reinterpret_cast<f32x4*>(xf)[i] = v;
-  if (c4 < half4) {
-    const float mk = mask[m];
-    f32x4 vm;
+  const idx m = i / I, c = i - m * I;
+  const vec s = reinterpret_cast<const vec*>(x)[(size_t)m * I + (I - 1 - c)];
+  vec v;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) vm[e] = mul_rn(v[e], mk);
-    const size_t o = (size_t)m * half4 + c4;
-    reinterpret_cast<f32x4*>(x0m)[o] = vm;
-    if (x0m_p) split4_store(vm, x0m_p, (size_t)M * half4 * 4, o);
-  }
-}
-// x1 = m + x1 * exp(0) * mask (models.py:522, mean-only: logs = 0): xf[:, half:] updated in place; mm is post(h) * mask
-__global__ void couple_add_kernel(float* xf, const float* mm, const float* mask, int M, int I) {
-  const int half = I / 2;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)M * half) return;
-  const size_t m = i / half, c = i % half;
-  float* p = xf + m * I + half + c;
-  *p = add_rn(mm[i], mul_rn(mul_rn(*p, 1.0f), mask[m]));
-}
-__global__ void couple_add4_kernel(float* xf, const float* mm, const float* mask, uint32_t M, uint32_t I4) {
-  const uint32_t half4 = I4 / 2;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M * half4) return;
-  const uint32_t m = i / half4, c4 = i - m * half4;
-  f32x4* p = reinterpret_cast<f32x4*>(xf) + (size_t)m * I4 + half4 + c4;
-  const f32x4 a = *p, b = reinterpret_cast<const f32x4*>(mm)[i];
-  const float mk = mask[m];
-  f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = add_rn(b[e], mul_rn(mul_rn(a[e], 1.0f), mk));
-  *p = v;
-}
-// the last Flip of the forward direction (modules.py:374-381) as the copy-out: out[m, c] = x[m, I - 1 - c]
-__global__ void flip_copy_kernel(const float* x, float* out, int M, int I) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)M * I) return;
-  const size_t m = i / I, c = i % I;
-  out[i] = x[m * I + (I - 1 - c)];
-}
-__global__ void flip_copy4_kernel(const float* x, float* out, uint32_t M, uint32_t I4) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M * I4) return;
-  const uint32_t m = i / I4, c4 = i - m * I4;
-  const f32x4 s = reinterpret_cast<const f32x4*>(x)[(size_t)m * I4 + (I4 - 1 - c4)];
-  reinterpret_cast<f32x4*>(out)[i] = f32x4{s[3], s[2], s[1], s[0]};
+  for (int e = 0; e < W; ++e) v[e] = s[W - 1 - e];
+  reinterpret_cast<vec*>(out)[i] = v;
 }
 
 // PosteriorEncoder staging (models.py:890): the spectrogram y [B, S, T] as the reference takes it -> the channel-last operand of
@@ -1202,13 +1131,41 @@ __global__ __launch_bounds__(256) void post_sample_kernel(const float* stats, co
     }
   }
 }
-__global__ void copy_f_kernel(const float* a, float* b, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) b[i] = a[i];
-}
 // pack: rows of three [C, C] matrices stacked -> [3C, C]; conv weights via launch_conv_transpose
 
 inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+// One elementwise step over n elements: the W = 4 kernel on n / 4 threads or the W = 1 kernel on n.  Four-wide needs the channel
+// count C a multiple of `mult` (4; 8 where the kernel also works on half rows), fewer than 2^32 elements and the pointers that may
+// be a caller's 16-byte aligned (the workspace's own always are).  The arguments go in as the W = 1 kernel takes them; a Chan is a
+// channel count, which a kernel gets divided by its W.
+inline bool four_wide(size_t n, int C, int mult, const void* a = nullptr, const void* b = nullptr) {
+  return C % mult == 0 && n < ((size_t)1 << 32) && reinterpret_cast<uintptr_t>(a) % 16 == 0 && reinterpret_cast<uintptr_t>(b) % 16 == 0;
+}
+struct Chan { int c; };
+template <int W, typename T> T ew_arg(T v) { return v; }
+template <int W> int ew_arg(Chan v) { return v.c / W; }
+template <typename K4, typename K1, typename... A>
+void launch_ew(bool wide, K4 k4, K1 k1, size_t n, hipStream_t st, A... a) {
+  if (wide) hipLaunchKernelGGL(k4, grid1(n / 4), dim3(256), 0, st, ew_arg<4>(a)...);
+  else hipLaunchKernelGGL(k1, grid1(n), dim3(256), 0, st, ew_arg<1>(a)...);
+}
+
+// A workspace is walked once per call by a carve routine: with the caller's pointer it hands out the buffers, with none it only
+// counts - so the size a *_workspace_bytes function reports is the layout the call uses.  Buffers are kAlign floats apart.
+struct Carver {
+  float* base;  // nullptr: count only
+  size_t off = 0, slack = 0;  // floats handed out; floats reported on top of them (carve_stack)
+  float* take(size_t n) {
+    float* r = base ? base + off : nullptr;
+    off += up(n, kAlign);
+    return r;
+  }
+  f16* take_h(size_t n) { return reinterpret_cast<f16*>(take(n)); }  // n floats = the hi + lo planes of n elements
+  size_t bytes() const { return (off + slack) * sizeof(float); }
+};
+// row counts and offsets of the GEMM core are 32-bit: B * T frames of up to 4096 channels have to fit
+inline bool frames_fit(int B, int T) { return (size_t)B * T <= (size_t)INT32_MAX / 4096; }
 
 // ---------------------------------------------------------------------------
 // host-side building blocks
@@ -1346,18 +1303,18 @@ int run_stack(ttsvits_handle* h, const StackBlob& sb, const StackDims& sd, const
   return TTSDEC_OK;
 }
 
-size_t stack_ws_floats(const StackDims& sd, size_t M) {
-  return M * (size_t)(4 * sd.C + 3 * sd.C + sd.F + (sd.C > sd.F ? sd.C : sd.F) + 3 * sd.C + sd.F) + 13 * kAlign;
-}
-StackWs carve_stack(float*& p, const StackDims& sd, size_t M, bool split) {
-  auto take = [&](size_t n) { float* r = p; p += up(n, kAlign); return r; };
+StackWs carve_stack(Carver& cv, const StackDims& sd, size_t M, bool split) {
+  const size_t C = sd.C, F = sd.F, begin = cv.off;
   StackWs w;
-  w.x = take(M * sd.C); w.xm = take(M * sd.C); w.qkv = take(M * 3 * sd.C); w.att = take(M * sd.C); w.t = take(M * sd.C);
-  w.f = take(M * sd.F);
-  w.cx.planes = reinterpret_cast<f16*>(take(M * (sd.C > sd.F ? sd.C : sd.F)));  // hi + lo planes of one A operand (fallback)
-  w.x_p = reinterpret_cast<f16*>(take(M * sd.C)); w.xm_p = reinterpret_cast<f16*>(take(M * sd.C));
-  w.att_p = reinterpret_cast<f16*>(take(M * sd.C)); w.f_p = reinterpret_cast<f16*>(take(M * sd.F));
+  w.x = cv.take(M * C); w.xm = cv.take(M * C); w.qkv = cv.take(M * 3 * C); w.att = cv.take(M * C); w.t = cv.take(M * C);
+  w.f = cv.take(M * F);
+  w.cx.planes = cv.take_h(M * (C > F ? C : F));  // hi + lo planes of one A operand (fallback)
+  w.x_p = cv.take_h(M * C); w.xm_p = cv.take_h(M * C); w.att_p = cv.take_h(M * C); w.f_p = cv.take_h(M * F);
   w.cx.split = split;  // (ttsvits_set_precision: split-fp16 planes, or exact fp32 MFMAs for every GEMM)
+  // The stack has always been reported as its buffers' unrounded sum + 13 kAlign, which is more than the eleven rounded buffers
+  // above take (the buffers behind them start where these end, not behind the slack): the reported sizes are part of the C ABI's
+  // behaviour, so the difference stays in them.
+  cv.slack += M * (10 * C + 2 * F + (C > F ? C : F)) + 13 * kAlign - (cv.off - begin);
   return w;
 }
 
@@ -1408,34 +1365,46 @@ struct WnLayout {
   const size_t *in_w, *in_b, *rs_w, *rs_b;  // per layer: float offsets into the blob
   size_t cond_w, cond_b;                    // read when g != nullptr
 };
+template <typename Blob>  // FlowBlob or PostBlob
+WnLayout wn_layout(const Blob& b, int H, int kernel, int layers, int gin) {
+  return {H, kernel, layers, gin, b.in_w, b.in_b, b.rs_w, b.rs_b, b.cond_w, b.cond_b};
+}
 struct WnWs {
   float *hx, *ho, *acts, *xin, *rs, *cond;  // [M,H] [M,H] [M,H] [M,2H] [M,2H] [B, 2 H layers]
   f16 *hx_p, *acts_p, *ho_p;                // planes of hx / acts / ho, written by their producers
+  GemmCtx cx;                               // of the WN's GEMMs and of its caller's, whose widest A operand has K channels
 };
-void run_wn(const float* blob, const WnLayout& w, const WnWs& ws, const GemmCtx& fcx, const float* g, const float* mask, int B, int T,
-            hipStream_t st) {
+WnWs carve_wn(Carver& cv, size_t M, size_t B, size_t H, size_t layers, size_t K, bool split) {
+  WnWs w;
+  w.hx = cv.take(M * H); w.ho = cv.take(M * H); w.acts = cv.take(M * H); w.xin = cv.take(M * 2 * H); w.rs = cv.take(M * 2 * H);
+  w.cx.planes = cv.take_h(M * (H > K ? H : K));
+  w.cx.split = split;
+  w.hx_p = cv.take_h(M * H); w.acts_p = cv.take_h(M * H); w.ho_p = cv.take_h(M * H);
+  w.cond = cv.take(B * 2 * H * layers);
+  return w;
+}
+const GemmCtx kExact{nullptr, false};  // (the [B, gin] projections of g are a few KFLOP: always the exact fp32 instruction)
+void run_wn(const float* blob, const WnLayout& w, const WnWs& ws, const float* g, const float* mask, int B, int T, hipStream_t st) {
   const int M = B * T, Fh = w.H;
   const int ncond = 2 * Fh * w.layers;
-  GemmCtx exact;
-  exact.planes = nullptr; exact.split = false;
-  float *hx = ws.hx, *ho = ws.ho, *acts = ws.acts, *xin = ws.xin, *rs = ws.rs, *cond = ws.cond;
-  f16 *hx_p = ws.hx_p, *acts_p = ws.acts_p, *ho_p = ws.ho_p;
+  const size_t n = (size_t)M * Fh;
+  const bool vec4 = four_wide(n, Fh, 4), fast = vec4 && ws.cx.split;
   if (g != nullptr)  // g = cond_layer(g)  (modules.py:189-190; a 1x1 conv of [B, gin, 1]: one small GEMM per WN)
-    gemm_generic(exact, g, nullptr, w.gin, w.gin, blob + w.cond_w, (size_t)ncond * w.gin, blob + w.cond_b, B, ncond,
-                 cond, nullptr, ncond, 0, nullptr, nullptr, 1, 1, st);
+    gemm_generic(kExact, g, nullptr, w.gin, w.gin, blob + w.cond_w, (size_t)ncond * w.gin, blob + w.cond_b, B, ncond,
+                 ws.cond, nullptr, ncond, 0, nullptr, nullptr, 1, 1, st);
   for (int j = 0; j < w.layers; ++j) {
-    const float* gl = g != nullptr ? cond + (size_t)j * 2 * Fh : nullptr;  // g_l = g[:, 2 Fh j : 2 Fh (j + 1)]      modules.py:194-196
+    const float* gl = g != nullptr ? ws.cond + (size_t)j * 2 * Fh : nullptr;  // g_l = g[:, 2 Fh j : 2 Fh (j + 1)]      modules.py:194-196
     const bool last = j == w.layers - 1;
-    gemm_generic(fcx, hx, hx_p, Fh, Fh, blob + w.in_w[j], (size_t)2 * Fh * w.kernel * Fh, blob + w.in_b[j], M, 2 * Fh, xin, nullptr, 2 * Fh, 0,
-                 nullptr, nullptr, w.kernel, T, st);
-    const bool vec4 = Fh % 4 == 0 && (size_t)M * Fh < ((size_t)1 << 32);
-    if (vec4 && fcx.split) hipLaunchKernelGGL(wn_gate4_kernel<true>, grid1((size_t)M * Fh / 4), dim3(256), 0, st, xin, (Fh & 7) ? acts : (float*)nullptr, acts_p, (uint32_t)M, (uint32_t)Fh / 4, gl, (uint32_t)T, (uint32_t)ncond);
-    else if (vec4) hipLaunchKernelGGL(wn_gate4_kernel<false>, grid1((size_t)M * Fh / 4), dim3(256), 0, st, xin, acts, acts_p, (uint32_t)M, (uint32_t)Fh / 4, gl, (uint32_t)T, (uint32_t)ncond);
-    else hipLaunchKernelGGL(wn_gate_kernel, grid1((size_t)M * Fh), dim3(256), 0, st, xin, acts, acts_p, M, Fh, gl, T, ncond);
+    gemm_generic(ws.cx, ws.hx, ws.hx_p, Fh, Fh, blob + w.in_w[j], (size_t)2 * Fh * w.kernel * Fh, blob + w.in_b[j], M, 2 * Fh, ws.xin, nullptr,
+                 2 * Fh, 0, nullptr, nullptr, w.kernel, T, st);
+    // (the fast gate with Fh % 8 == 0 writes the planes only: the res/skip GEMM then reads nothing else)
+    launch_ew(vec4, fast ? wn_gate_kernel<4, true> : wn_gate_kernel<4, false>, wn_gate_kernel<1, false>, n, st, ws.xin,
+              fast && !(Fh & 7) ? (float*)nullptr : ws.acts, ws.acts_p, M, Chan{Fh}, gl, T, ncond);
     const int cr = last ? Fh : 2 * Fh;
-    gemm_generic(fcx, acts, acts_p, Fh, Fh, blob + w.rs_w[j], (size_t)cr * Fh, blob + w.rs_b[j], M, cr, rs, nullptr, cr, 0, nullptr, nullptr, 1, T, st);
-    if (vec4) hipLaunchKernelGGL(wn_update4_kernel, grid1((size_t)M * Fh / 4), dim3(256), 0, st, hx, ho, rs, mask, hx_p, ho_p, (uint32_t)M, (uint32_t)Fh / 4, last ? 1 : 0, j == 0 ? 1 : 0);
-    else hipLaunchKernelGGL(wn_update_kernel, grid1((size_t)M * Fh), dim3(256), 0, st, hx, ho, rs, mask, hx_p, ho_p, M, Fh, last ? 1 : 0, j == 0 ? 1 : 0);
+    gemm_generic(ws.cx, ws.acts, ws.acts_p, Fh, Fh, blob + w.rs_w[j], (size_t)cr * Fh, blob + w.rs_b[j], M, cr, ws.rs, nullptr, cr, 0, nullptr,
+                 nullptr, 1, T, st);
+    launch_ew(vec4, wn_update_kernel<4>, wn_update_kernel<1>, n, st, ws.hx, ws.ho, ws.rs, mask, ws.hx_p, ws.ho_p, M, Chan{Fh}, last ? 1 : 0,
+              j == 0 ? 1 : 0);
   }
 }
 
@@ -1460,9 +1429,35 @@ bool dims_ok(const ttsvits_dims& d) {
 }  // namespace
 
 namespace {
+// The workspaces of the two ttsvits calls (carved as the Carver comment says)
+struct TextWs {
+  StackWs sw;
+  float *mask, *stats, *gvec;  // [M] [M, 2I] [B, H]
+};
+TextWs carve_text(Carver& cv, const ttsvits_dims& d, size_t B, size_t T, bool split) {
+  const size_t M = B * T;
+  TextWs w;
+  w.sw = carve_stack(cv, enc_dims(d), M, split);
+  w.mask = cv.take(M); w.stats = cv.take(M * 2 * d.inter_channels); w.gvec = cv.take(B * d.hidden_channels);
+  return w;
+}
+struct FlowWs {
+  StackWs sw;
+  float *mask, *xa, *xb, *mm;  // [M]; current x (ping) and flipped x (pong) [M, I]; post(h) * mask [M, I / 2]
+  WnWs wn;                     // (wn.cond: WN.cond_layer(g) of the current coupling layer)
+};
+FlowWs carve_flow(Carver& cv, const ttsvits_dims& d, size_t B, size_t T, bool split) {
+  const size_t M = B * T, I = d.inter_channels;
+  FlowWs w;
+  w.sw = carve_stack(cv, tf_dims(d), M, split);
+  w.mask = cv.take(M); w.xa = cv.take(M * I); w.xb = cv.take(M * I); w.mm = cv.take(M * (I / 2));
+  w.wn = carve_wn(cv, M, B, d.flow_hidden, d.flow_wn_layers, I / 2, split);
+  return w;
+}
+
 // ResidualCouplingTransformersBlock.forward (models.py:803-810) in either direction.  Reverse: Flip, layer_{n-1}, ..., Flip,
 // layer_0 with x1 = (x1 - m) * mask; forward: layer_0, Flip, ..., layer_{n-1}, Flip with x1 = m + x1 * mask.  The Flip in front
-// of a coupling rides in its split (flip_split), the forward direction's last Flip in the copy-out (flip_copy; no flows: a plain copy).
+// of a coupling rides in its split, the forward direction's last Flip in the copy-out (no flows: a plain copy).
 int run_flow(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out, void* workspace,
              size_t workspace_bytes, void* stream, bool forward) {
   if (!h || !z || !lengths || !out || !workspace || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
@@ -1470,73 +1465,47 @@ int run_flow(ttsvits_handle* h, const float* z, const int32_t* lengths, const fl
   if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
   if (workspace_bytes < ttsvits_flow_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
   if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  if (!frames_fit(B, T)) return TTSDEC_ERR_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ttsvits_dims& d = h->d;
-  const VitsBlob& L = h->bl;
   const float* blob = h->blob;
   const int M = B * T, I = d.inter_channels, half = I / 2, Fh = d.flow_hidden;
-  float* p = static_cast<float*>(workspace);
-  const StackDims sd = tf_dims(d);
-  StackWs sw = carve_stack(p, sd, (size_t)M, h->precision == TTSDEC_PREC_SPLIT_F16);
-  auto take = [&](size_t n) { float* r = p; p += up(n, kAlign); return r; };
-  float* mask = take(M);
-  float* xa = take((size_t)M * I);   // current x (ping)
-  float* xb = take((size_t)M * I);   // flipped x (pong)
-  float* mm = take((size_t)M * half);
-  float* hx = take((size_t)M * Fh);   // WN running x
-  float* ho = take((size_t)M * Fh);   // WN output accumulator
-  float* acts = take((size_t)M * Fh);
-  float* xin = take((size_t)M * 2 * Fh);
-  float* rs = take((size_t)M * 2 * Fh);
-  GemmCtx fcx;
-  fcx.planes = reinterpret_cast<f16*>(take((size_t)M * (Fh > half ? Fh : half)));
-  fcx.split = h->precision == TTSDEC_PREC_SPLIT_F16;
-  f16* hx_p = reinterpret_cast<f16*>(take((size_t)M * Fh));  // planes of hx / acts / ho, written by their producers
-  f16* acts_p = reinterpret_cast<f16*>(take((size_t)M * Fh));
-  f16* ho_p = reinterpret_cast<f16*>(take((size_t)M * Fh));
-  const int ncond = 2 * Fh * d.flow_wn_layers;
-  float* cond = take((size_t)B * ncond);  // WN.cond_layer(g) of the current coupling layer, [B, 2 Fh n_layers]
+  const size_t n = (size_t)M * I;
+  Carver cv{static_cast<float*>(workspace)};
+  const FlowWs w = carve_flow(cv, d, B, T, h->precision == TTSDEC_PREC_SPLIT_F16);
+  const StackWs& sw = w.sw;
+  const WnWs& ws = w.wn;
+  float *xa = w.xa, *xb = w.xb, *mask = w.mask;
   hipLaunchKernelGGL(frame_mask_kernel, grid1(M), dim3(256), 0, st, lengths, T, mask, M);
   const float* cur = z;
-  WnWs wws;
-  wws.hx = hx; wws.ho = ho; wws.acts = acts; wws.xin = xin; wws.rs = rs; wws.cond = cond;
-  wws.hx_p = hx_p; wws.acts_p = acts_p; wws.ho_p = ho_p;
-  for (int n = 0; n < d.n_flows; ++n) {
+  for (int k = 0; k < d.n_flows; ++k) {
     // models.py:804-805: flows = layer_0, Flip, layer_1, Flip, ...;  807-809: reversed(flows) = Flip, layer_{n-1}, ..., Flip, layer_0
-    const int f = forward ? n : d.n_flows - 1 - n;
-    const FlowBlob& fb = L.flow[f];
-    const bool i4 = I % 8 == 0 && (size_t)M * I < ((size_t)1 << 32) && reinterpret_cast<uintptr_t>(cur) % 16 == 0;  // (cur may be the caller's z)
-    const bool flip = !forward || n > 0;  // (forward: no Flip in front of the first coupling)
-    if (i4 && flip) hipLaunchKernelGGL(flip_split4_kernel, grid1((size_t)M * I / 4), dim3(256), 0, st, cur, mask, xb, sw.xm, sw.xm_p, (uint32_t)M, (uint32_t)I / 4);
-    else if (flip) hipLaunchKernelGGL(flip_split_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, mask, xb, sw.xm, sw.xm_p, M, I);
-    else if (i4) hipLaunchKernelGGL(split4_kernel, grid1((size_t)M * I / 4), dim3(256), 0, st, cur, mask, xb, sw.xm, sw.xm_p, (uint32_t)M, (uint32_t)I / 4);
-    else hipLaunchKernelGGL(split_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, mask, xb, sw.xm, sw.xm_p, M, I);
+    const FlowBlob& fb = h->bl.flow[forward ? k : d.n_flows - 1 - k];
+    const bool i4 = four_wide(n, I, 8, cur);   // (cur may be the caller's z)
+    const bool flip = !forward || k > 0;       // (forward: no Flip in front of the first coupling)
+    launch_ew(i4, flip ? split_kernel<4, true> : split_kernel<4, false>, flip ? split_kernel<1, true> : split_kernel<1, false>, n, st, cur, mask,
+              xb, sw.xm, sw.xm_p, M, Chan{I});
     // x0_ = pre_transformer(x0 * mask, mask) + x0                                   models.py:508-509
-    int rc = run_stack(h, fb.tf, sd, sw, mask, B, T, st);
+    int rc = run_stack(h, fb.tf, tf_dims(d), sw, mask, B, T, st);
     if (rc != TTSDEC_OK) return rc;
-    if (i4) hipLaunchKernelGGL(add_x04_kernel, grid1((size_t)M * half / 4), dim3(256), 0, st, sw.xm, sw.xm_p, xb, (uint32_t)M, (uint32_t)I / 4);
-    else hipLaunchKernelGGL(add_x0_kernel, grid1((size_t)M * half), dim3(256), 0, st, sw.xm, sw.xm_p, xb, M, I);
+    launch_ew(i4, add_x0_kernel<4>, add_x0_kernel<1>, n / 2, st, sw.xm, sw.xm_p, xb, M, Chan{I});
     // h = pre(x0_) * mask                                                           :510
-    gemm_generic(fcx, sw.xm, sw.xm_p, half, half, blob + fb.pre_w, (size_t)Fh * half, blob + fb.pre_b, M, Fh, hx, hx_p, Fh, 0, mask, nullptr, 1, T, st);
+    gemm_generic(ws.cx, sw.xm, sw.xm_p, half, half, blob + fb.pre_w, (size_t)Fh * half, blob + fb.pre_b, M, Fh, ws.hx, ws.hx_p, Fh, 0, mask,
+                 nullptr, 1, T, st);
     // h = WN(h, mask, g)                                                            :511, modules.py:185-210
-    WnLayout wl;
-    wl.H = Fh; wl.kernel = d.flow_kernel; wl.layers = d.flow_wn_layers; wl.gin = d.gin_channels;
-    wl.in_w = fb.in_w; wl.in_b = fb.in_b; wl.rs_w = fb.rs_w; wl.rs_b = fb.rs_b; wl.cond_w = fb.cond_w; wl.cond_b = fb.cond_b;
-    run_wn(blob, wl, wws, fcx, g, mask, B, T, st);
+    run_wn(blob, wn_layout(fb, Fh, d.flow_kernel, d.flow_wn_layers, d.gin_channels), ws, g, mask, B, T, st);
     // m = post(h) * mask ; reverse: x1 = (x1 - m) * mask, forward: x1 = m + x1 * mask   :517, 522, 529
-    gemm_generic(fcx, ho, ho_p, Fh, Fh, blob + fb.post_w, (size_t)half * Fh, blob + fb.post_b, M, half, mm, nullptr, half, 0, mask, nullptr, 1, T, st);
-    if (i4 && forward) hipLaunchKernelGGL(couple_add4_kernel, grid1((size_t)M * half / 4), dim3(256), 0, st, xb, mm, mask, (uint32_t)M, (uint32_t)I / 4);
-    else if (forward) hipLaunchKernelGGL(couple_add_kernel, grid1((size_t)M * half), dim3(256), 0, st, xb, mm, mask, M, I);
-    else if (i4) hipLaunchKernelGGL(couple4_kernel, grid1((size_t)M * half / 4), dim3(256), 0, st, xb, mm, mask, (uint32_t)M, (uint32_t)I / 4);
-    else hipLaunchKernelGGL(couple_kernel, grid1((size_t)M * half), dim3(256), 0, st, xb, mm, mask, M, I);
+    gemm_generic(ws.cx, ws.ho, ws.ho_p, Fh, Fh, blob + fb.post_w, (size_t)half * Fh, blob + fb.post_b, M, half, w.mm, nullptr, half, 0, mask,
+                 nullptr, 1, T, st);
+    launch_ew(i4, forward ? couple_kernel<4, true> : couple_kernel<4, false>, forward ? couple_kernel<1, true> : couple_kernel<1, false>, n / 2,
+              st, xb, w.mm, mask, M, Chan{I});
     float* t = xa; xa = xb; xb = t;  // the coupled tensor becomes the next layer's input
     cur = xa;
   }
-  const bool o4 = I % 4 == 0 && (size_t)M * I < ((size_t)1 << 32) && reinterpret_cast<uintptr_t>(out) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(cur) % 16 == 0;
-  if (!forward || d.n_flows == 0) hipLaunchKernelGGL(copy_f_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, out, (size_t)M * I);
-  else if (o4) hipLaunchKernelGGL(flip_copy4_kernel, grid1((size_t)M * I / 4), dim3(256), 0, st, cur, out, (uint32_t)M, (uint32_t)I / 4);
-  else hipLaunchKernelGGL(flip_copy_kernel, grid1((size_t)M * I), dim3(256), 0, st, cur, out, M, I);
+  // (the plain copy - the reverse direction, or no flows - is the W = 1 kernel whatever the alignment)
+  const bool flip_out = forward && d.n_flows > 0;
+  launch_ew(flip_out && four_wide(n, I, 4, cur, out), copy_out_kernel<4, true>, flip_out ? copy_out_kernel<1, true> : copy_out_kernel<1, false>, n,
+            st, cur, out, M, Chan{I});
   return record_hip_error(h, forward ? "flow_forward" : "flow_reverse");
 }
 }  // namespace
@@ -1619,9 +1588,9 @@ int ttsvits_bind_weights(ttsvits_handle* h, const void* blob) { return bind_blob
 
 size_t ttsvits_text_encoder_workspace_bytes(const ttsvits_handle* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
-  const size_t M = (size_t)B * T;
-  return (stack_ws_floats(enc_dims(h->d), M) + up(M, kAlign) + up(M * 2 * h->d.inter_channels, kAlign) +
-          up((size_t)B * h->d.hidden_channels, kAlign)) * sizeof(float);
+  Carver cv{nullptr};
+  carve_text(cv, h->d, B, T, false);
+  return cv.bytes();
 }
 
 int ttsvits_text_encoder(ttsvits_handle* h, const int64_t* ids, const int32_t* lengths, const float* g, int B, int T, float* x, float* m,
@@ -1632,25 +1601,22 @@ int ttsvits_text_encoder(ttsvits_handle* h, const int64_t* ids, const int32_t* l
   if (workspace_bytes < ttsvits_text_encoder_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255))
     return TTSDEC_ERR_WORKSPACE;
   if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  if (!frames_fit(B, T)) return TTSDEC_ERR_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ttsvits_dims& d = h->d;
   const VitsBlob& L = h->bl;
   const int M = B * T, H = d.hidden_channels, I = d.inter_channels;
-  float* p = static_cast<float*>(workspace);
-  const StackDims sd = enc_dims(d);
-  StackWs sw = carve_stack(p, sd, (size_t)M, h->precision == TTSDEC_PREC_SPLIT_F16);
-  float* mask = p; p += up((size_t)M, kAlign);
-  float* stats = p; p += up((size_t)M * 2 * I, kAlign);
-  float* gvec = p;
-  GemmCtx exact;  // (the [B, gin] projections of g are a few KFLOP: always the exact fp32 instruction)
-  exact.planes = nullptr; exact.split = false;
+  Carver cv{static_cast<float*>(workspace)};
+  const TextWs w = carve_text(cv, d, B, T, h->precision == TTSDEC_PREC_SPLIT_F16);
+  const StackWs& sw = w.sw;
+  float *mask = w.mask, *stats = w.stats, *gvec = w.gvec;
   if (g != nullptr)  // attentions.py:81: spk_emb_linear(g)
-    gemm_generic(exact, g, nullptr, d.gin_channels, d.gin_channels, h->blob + L.spk_w, (size_t)H * d.gin_channels, h->blob + L.spk_b, B, H, gvec,
+    gemm_generic(kExact, g, nullptr, d.gin_channels, d.gin_channels, h->blob + L.spk_w, (size_t)H * d.gin_channels, h->blob + L.spk_b, B, H, gvec,
                  nullptr, H, 0, nullptr, nullptr, 1, 1, st);
   // models.py:370-376
   hipLaunchKernelGGL(embed_scale_kernel, grid1((size_t)M * H), dim3(256), 0, st, reinterpret_cast<const long long*>(ids), lengths,
                      h->blob + L.emb, d.n_vocab, T, H, sqrtf((float)H), sw.xm, sw.xm_p, mask, M, status);
-  int rc = run_stack(h, L.enc, sd, sw, mask, B, T, st, g != nullptr ? gvec : nullptr, d.cond_layer_idx);
+  int rc = run_stack(h, L.enc, enc_dims(d), sw, mask, B, T, st, g != nullptr ? gvec : nullptr, d.cond_layer_idx);
   if (rc != TTSDEC_OK) return rc;
   // models.py:377-379: stats = proj(x) * x_mask; m, logs = split(stats)
   gemm_generic(sw.cx, sw.xm, sw.xm_p, H, H, h->blob + L.proj_w, (size_t)2 * I * H, h->blob + L.proj_b, M, 2 * I, stats, nullptr, 2 * I, 0, mask,
@@ -1667,11 +1633,9 @@ int ttsvits_text_encoder(ttsvits_handle* h, const int64_t* ids, const int32_t* l
 
 size_t ttsvits_flow_workspace_bytes(const ttsvits_handle* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
-  const size_t M = (size_t)B * T, I = h->d.inter_channels, Fh = h->d.flow_hidden;
-  const size_t fl = up(M, kAlign) + 2 * up(M * I, kAlign) + up(M * (I / 2), kAlign) + 2 * up(M * Fh, kAlign) + up(M * Fh, kAlign) +
-                    2 * up(M * 2 * Fh, kAlign) + up(M * (Fh > I / 2 ? Fh : I / 2), kAlign) + 3 * up(M * Fh, kAlign) +
-                    up((size_t)B * 2 * Fh * h->d.flow_wn_layers, kAlign);
-  return (stack_ws_floats(tf_dims(h->d), M) + fl) * sizeof(float);
+  Carver cv{nullptr};
+  carve_flow(cv, h->d, B, T, false);
+  return cv.bytes();
 }
 
 int ttsvits_flow_reverse(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out,
@@ -1723,6 +1687,19 @@ PostBlob make_post_layout(const ttspost_dims& d, int spec_pad) {
   L.proj_w = take_w(2 * I * H); L.proj_b = take(2 * I);
   L.total = off;
   return L;
+}
+struct PostWs {
+  float *mask, *xs, *stats;  // [M]; the staged spectrogram [M, Sp]; proj(x) * mask [M, 2I]
+  f16* xs_p;                 // planes of xs
+  WnWs wn;
+};
+PostWs carve_post(Carver& cv, const ttspost_dims& d, size_t Sp, size_t B, size_t T, bool split) {
+  const size_t M = B * T;
+  PostWs w;
+  w.mask = cv.take(M); w.xs = cv.take(M * Sp); w.xs_p = cv.take_h(M * Sp);
+  w.wn = carve_wn(cv, M, B, d.hidden_channels, d.n_layers, Sp, split);
+  w.stats = cv.take(M * 2 * d.inter_channels);
+  return w;
 }
 bool post_dims_ok(const ttspost_dims& d) {
   if (d.spec_channels < 1 || d.spec_channels > 4096) return false;
@@ -1802,11 +1779,9 @@ int ttspost_bind_weights(ttspost_handle* h, const void* blob) { return bind_blob
 
 size_t ttspost_workspace_bytes(const ttspost_handle* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
-  const size_t M = (size_t)B * T, H = h->d.hidden_channels, I = h->d.inter_channels, Sp = h->spec_pad;
-  const size_t f = up(M, kAlign) + 2 * up(M * Sp, kAlign) + 3 * up(M * H, kAlign) + 2 * up(M * 2 * H, kAlign) +
-                   up(M * (H > Sp ? H : Sp), kAlign) + 3 * up(M * H, kAlign) + up((size_t)B * 2 * H * h->d.n_layers, kAlign) +
-                   up(M * 2 * I, kAlign);
-  return f * sizeof(float);
+  Carver cv{nullptr};
+  carve_post(cv, h->d, h->spec_pad, B, T, false);
+  return cv.bytes();
 }
 
 int ttspost_forward(ttspost_handle* h, const float* y, const int32_t* lengths, const float* g, const float* eps, int eps_T, int B, int T,
@@ -1816,41 +1791,28 @@ int ttspost_forward(ttspost_handle* h, const float* y, const int32_t* lengths, c
   if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
   if (workspace_bytes < ttspost_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
   if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
-  if ((size_t)B * T > (size_t)INT32_MAX / 4096) return TTSDEC_ERR_DIMS;  // (row counts and offsets of the GEMM core are 32-bit)
+  if (!frames_fit(B, T)) return TTSDEC_ERR_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ttspost_dims& d = h->d;
   const PostBlob& L = h->bl;
   const float* blob = h->blob;
   const int M = B * T, H = d.hidden_channels, I = d.inter_channels, S = d.spec_channels, Sp = h->spec_pad;
   const bool split = h->precision == TTSDEC_PREC_SPLIT_F16;
-  float* p = static_cast<float*>(workspace);
-  auto take = [&](size_t n) { float* r = p; p += up(n, kAlign); return r; };
-  float* mask = take(M);
-  float* xs = take((size_t)M * Sp);
-  f16* xs_p = reinterpret_cast<f16*>(take((size_t)M * Sp));
-  WnWs ws;
-  ws.hx = take((size_t)M * H); ws.ho = take((size_t)M * H); ws.acts = take((size_t)M * H);
-  ws.xin = take((size_t)M * 2 * H); ws.rs = take((size_t)M * 2 * H);
-  GemmCtx fcx;
-  fcx.planes = reinterpret_cast<f16*>(take((size_t)M * (H > Sp ? H : Sp)));
-  fcx.split = split;
-  ws.hx_p = reinterpret_cast<f16*>(take((size_t)M * H)); ws.acts_p = reinterpret_cast<f16*>(take((size_t)M * H));
-  ws.ho_p = reinterpret_cast<f16*>(take((size_t)M * H));
-  ws.cond = take((size_t)B * 2 * H * d.n_layers);
-  float* stats = take((size_t)M * 2 * I);
+  Carver cv{static_cast<float*>(workspace)};
+  const PostWs w = carve_post(cv, d, Sp, B, T, split);
+  const WnWs& ws = w.wn;
+  float *mask = w.mask, *xs = w.xs, *stats = w.stats;
+  f16* xs_p = w.xs_p;
   hipLaunchKernelGGL(frame_mask_kernel, grid1(M), dim3(256), 0, st, lengths, T, mask, M);
   // x = pre(y) * x_mask                                                             models.py:890
   const dim3 tgrid((T + kTr - 1) / kTr, (Sp + kTr - 1) / kTr, B);
   hipLaunchKernelGGL(post_stage_kernel, tgrid, dim3(256), 0, st, y, xs, split ? xs_p : (f16*)nullptr, S, Sp, T, M);
-  gemm_generic(fcx, xs, split ? xs_p : nullptr, Sp, Sp, blob + L.pre_w, (size_t)H * Sp, blob + L.pre_b, M, H, ws.hx, ws.hx_p, H, 0, mask, nullptr, 1,
+  gemm_generic(ws.cx, xs, split ? xs_p : nullptr, Sp, Sp, blob + L.pre_w, (size_t)H * Sp, blob + L.pre_b, M, H, ws.hx, ws.hx_p, H, 0, mask, nullptr, 1,
                T, st);
   // x = enc(x, x_mask, g=g)                                                         :891
-  WnLayout wl;
-  wl.H = H; wl.kernel = d.kernel_size; wl.layers = d.n_layers; wl.gin = d.gin_channels;
-  wl.in_w = L.in_w; wl.in_b = L.in_b; wl.rs_w = L.rs_w; wl.rs_b = L.rs_b; wl.cond_w = L.cond_w; wl.cond_b = L.cond_b;
-  run_wn(blob, wl, ws, fcx, g, mask, B, T, st);
+  run_wn(blob, wn_layout(L, H, d.kernel_size, d.n_layers, d.gin_channels), ws, g, mask, B, T, st);
   // stats = proj(x) * x_mask                                                        :892
-  gemm_generic(fcx, ws.ho, ws.ho_p, H, H, blob + L.proj_w, (size_t)2 * I * H, blob + L.proj_b, M, 2 * I, stats, nullptr, 2 * I, 0, mask, nullptr,
+  gemm_generic(ws.cx, ws.ho, ws.ho_p, H, H, blob + L.proj_w, (size_t)2 * I * H, blob + L.proj_b, M, 2 * I, stats, nullptr, 2 * I, 0, mask, nullptr,
                1, T, st);
   // m, logs = split(stats); z = (m + eps * exp(logs)) * x_mask                      :893-894
   const dim3 sgrid((T + kTr - 1) / kTr, (I + kTr - 1) / kTr, B);

@@ -163,8 +163,10 @@ class VitsEngine(Handle):
             raise IndexError(f"token id out of range [0, {self.dims['n_vocab']}) in the text encoder's input")
         return x, m, logs
 
-    def flow_reverse(self, z_cl: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """z_cl [B, T, inter] channel-last."""
+    def _flow(self, fn: str, z_cl: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor]) -> torch.Tensor:
+        """One direction of the flow (the C function fn) on z_cl [B, T, inter] channel-last.  A contiguous fp32 z_cl is passed as it
+        is, without a copy, whatever its alignment (a view into a larger buffer may be only 4-byte aligned: the library then takes
+        its one-element kernels for the first coupling)."""
         _require_device(z_cl, "z")
         B, T, _ = z_cl.shape
         g = speaker_rows(g, B, self.dims["gin_channels"], "a module")
@@ -173,26 +175,18 @@ class VitsEngine(Handle):
         out = torch.empty_like(z_cl)
         ws = self.workspace("flow", self._lib.ttsvits_flow_workspace_bytes(self._h, B, T))
         with torch.cuda.device(self.device):
-            rc = self._lib.ttsvits_flow_reverse(self._h, z_cl.data_ptr(), lens.data_ptr(), g.data_ptr() if g is not None else None, B, T,
-                                                out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                _stream(self.device))
-        self._err(rc, "ttsvits_flow_reverse")
+            rc = getattr(self._lib, fn)(self._h, z_cl.data_ptr(), lens.data_ptr(), g.data_ptr() if g is not None else None, B, T,
+                                        out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
+        self._err(rc, fn)
         return out
+
+    def flow_reverse(self, z_cl: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """z_cl [B, T, inter] channel-last."""
+        return self._flow("ttsvits_flow_reverse", z_cl, lengths, g)
 
     def flow_forward(self, z_cl: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The forward direction (ttsvits_flow_forward) on z_cl [B, T, inter] channel-last; same workspace as flow_reverse."""
-        _require_device(z_cl, "z")
-        B, T, _ = z_cl.shape
-        g = speaker_rows(g, B, self.dims["gin_channels"], "a module")
-        z_cl = z_cl.to(torch.float32).contiguous()
-        lens = lengths.to(device=self.device, dtype=torch.int32).contiguous()
-        out = torch.empty_like(z_cl)
-        ws = self.workspace("flow", self._lib.ttsvits_flow_workspace_bytes(self._h, B, T))
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsvits_flow_forward(self._h, z_cl.data_ptr(), lens.data_ptr(), g.data_ptr() if g is not None else None, B, T,
-                                                out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
-        self._err(rc, "ttsvits_flow_forward")
-        return out
+        return self._flow("ttsvits_flow_forward", z_cl, lengths, g)
 
     # ---- monotonic alignment search (weightless: a handle of any dims serves, bound or not) ----
     _PATH_DTYPES = {torch.float32: _lib.PATH_F32, torch.float16: _lib.PATH_F16, torch.bfloat16: _lib.PATH_BF16}
