@@ -448,19 +448,21 @@ size_t ttsvits_text_encoder_workspace_bytes(const ttsvits_handle* h, int B, int 
 /* ids [B, T] int64, lengths [B] int32 (device).  x [B, T, hidden], m and logs [B, T, inter]; padded frames are zero.
  * g: NULL, or the speaker embedding [B, gin_channels] fp32 (device) - the reference's g [B, gin, 1] (models.py:369, 376;
  * attentions.py:80-84); TTSDEC_ERR_INVALID_ARG when g is given and the handle has gin_channels == 0.
- * status: as for ttsenc_forward (bit 0: an id outside [0, n_vocab), models.py:370). */
+ * status: as for ttsenc_forward (bit 0: an id outside [0, n_vocab), models.py:370).
+ * TTSDEC_ERR_DIMS for B * T > INT32_MAX / 4096 frames: the GEMM core counts rows and offsets in 32 bits. */
 int ttsvits_text_encoder(ttsvits_handle* h, const int64_t* ids, const int32_t* lengths, const float* g, int B, int T, float* x,
                          float* m, float* logs, void* workspace, size_t workspace_bytes, void* stream, int32_t* status);
 size_t ttsvits_flow_workspace_bytes(const ttsvits_handle* h, int B, int T);
 /* z [B, T, inter] -> out [B, T, inter]; lengths [B] int32 (device) give y_mask.  g: NULL or the speaker embedding
- * [B, gin_channels] (the reference's g [B, gin, 1], models.py:506, 511; modules.py:185-199), as above. */
+ * [B, gin_channels] (the reference's g [B, gin, 1], models.py:506, 511; modules.py:185-199), as above.
+ * TTSDEC_ERR_DIMS for B * T > INT32_MAX / 4096 frames, as ttsvits_text_encoder. */
 int ttsvits_flow_reverse(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out,
                          void* workspace, size_t workspace_bytes, void* stream);
 /* The forward direction, ResidualCouplingTransformersBlock.forward(reverse=False) (models.py:803-806) over
  * ResidualCouplingTransformersLayer.forward (models.py:506-526, mean-only: x1 = m + x1 * exp(0) * x_mask) - the `self.flow(z, y_mask,
  * g=g_src)` of SynthesizerTrn.voice_conversion, models.py:1334.  Flows run layer_0, Flip, layer_1, Flip, ..., layer_{n-1}, Flip.
- * Same tensors, workspace (ttsvits_flow_workspace_bytes), precisions and errors as ttsvits_flow_reverse; the logdet of the
- * training forward is not computed (mean-only: it is 0). */
+ * Same tensors, workspace (ttsvits_flow_workspace_bytes), precisions and errors (TTSDEC_ERR_DIMS for B * T > INT32_MAX / 4096 frames
+ * among them) as ttsvits_flow_reverse; the logdet of the training forward is not computed (mean-only: it is 0). */
 int ttsvits_flow_forward(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out,
                          void* workspace, size_t workspace_bytes, void* stream);
 

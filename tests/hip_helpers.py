@@ -193,3 +193,35 @@ def postnet_bf16_emulation(y, pw, num_layers=3):
         beta = pw[f"conv.{i}.1.bias"] - pw[f"conv.{i}.1.running_mean"] * alpha
         xc = rb(O.isru(xc * alpha[None, :, None] + beta[None, :, None]))
     return y + torch.nn.functional.linear(xc.transpose(1, 2), rb(pw["fc_out.weight"]))
+
+
+WS_GUARD = 4096  # bytes on each side of a guarded workspace
+
+
+def assert_workspace_fits(monkeypatch, cls, method, nbytes_of, run):
+    """run() (-> a tensor) twice with `cls.method`, the engine's workspace getter, replaced: once on exactly the reported bytes -
+    nbytes_of(engine, *the getter's arguments) - cut from the middle of a tensor whose WS_GUARD bytes on either side hold a fixed
+    pattern, once on a generously oversized one.  The guards must come back untouched (an overrun is a changed byte of the test's
+    own memory, not a fault) and the two results must be bit-equal."""
+    bufs = []
+
+    def guarded(self, *a):
+        n = int(nbytes_of(self, *a))
+        buf = torch.full((2 * WS_GUARD + n,), 0xA5, dtype=torch.uint8, device=self.device)
+        assert n > 0 and buf.data_ptr() % 256 == 0
+        bufs.append(buf)
+        return buf[WS_GUARD:WS_GUARD + n]
+
+    def roomy(self, *a):
+        return torch.empty(4 * int(nbytes_of(self, *a)) + (1 << 20), dtype=torch.uint8, device=self.device)
+
+    with monkeypatch.context() as mp:
+        mp.setattr(cls, method, guarded)
+        got = run()
+        mp.setattr(cls, method, roomy)
+        want = run()
+    torch.cuda.synchronize()
+    assert bufs, "the call took no workspace"
+    for buf in bufs:
+        assert bool((buf[:WS_GUARD] == 0xA5).all()) and bool((buf[-WS_GUARD:] == 0xA5).all()), "a guard of the workspace was written"
+    assert torch.equal(got, want)

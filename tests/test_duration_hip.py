@@ -58,6 +58,29 @@ def test_golden_small_dims():
         assert float(lw[2, 0, 1:].abs().max()) == 0.0 and float(ld[1, 0, 5:].abs().max()) == 0.0  # padded frames
 
 
+@pytest.mark.parametrize("kind", ["sdp", "dp"])
+def test_carved_workspace_fits_the_reported_bytes(kind, monkeypatch):
+    """ttsdur_sdp_reverse / ttsdur_dp_forward at the golden small dims, (B, T) = (2, 37), with g: nothing is written outside
+    ttsdur_workspace_bytes, and the result is that of a roomy workspace bit for bit."""
+    from hip_helpers import assert_workspace_fits
+    from torch_tts_amd.engine import Handle
+
+    sd, meta = load_golden()
+    T = _T()
+    m = T.StochasticDurationPredictor(32, 192, 3, 0.5, 4, gin_channels=4) if kind == "sdp" else T.DurationPredictor(32, 48, 3, 0.5, gin_channels=4)
+    m.load_state_dict(weights(sd, f"{kind}4"), strict=True)
+    m = m.cuda().eval()
+    gen = torch.Generator().manual_seed(3)
+    x, g, noise = torch.randn(2, 32, 37, generator=gen).cuda(), torch.randn(2, 4, 1, generator=gen).cuda(), torch.randn(2, 2, 37, generator=gen).cuda()
+    x_mask = _mask([37, 20], 37).cuda()
+
+    def run():
+        with torch.no_grad():
+            return m(x, x_mask, g=g, reverse=True, noise_scale=1.0, noise=noise) if kind == "sdp" else m(x, x_mask, g=g)
+
+    assert_workspace_fits(monkeypatch, Handle, "workspace", lambda eng, name, nbytes: nbytes, run)
+
+
 def _fulldims_case(B=64, T=200, seed=0):
     g = torch.Generator().manual_seed(seed)
     lengths = torch.randint(1, T + 1, (B,), generator=g)

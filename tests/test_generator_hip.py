@@ -58,6 +58,28 @@ def test_golden_small_dims():
         _close(y, gsd[f"y{gin}/T9"], f"gin={gin} after remove_weight_norm")
 
 
+def test_carved_workspace_fits_the_reported_bytes(monkeypatch):
+    """ttsgen_forward at the golden small dims, B = 3 x T = 37 in groups of two (a full group, then a short last one whose buffers
+    lie closer together than the reported size's): nothing is written outside ttsgen_workspace_bytes, and the waveform is that of a
+    roomy workspace bit for bit."""
+    from hip_helpers import assert_workspace_fits
+    from torch_tts_amd.engine import Handle
+
+    gsd, meta = load_golden()
+    gen = make_generator(meta["dims"], 4)
+    gen.load_state_dict(weights(gsd, 4), strict=True)
+    gen = gen.cuda().eval()
+    rng = torch.Generator().manual_seed(4)
+    x, g = torch.randn(3, meta["dims"]["initial_channel"], 37, generator=rng).cuda(), torch.randn(3, 4, 1, generator=rng).cuda()
+    monkeypatch.setenv("TTSGEN_GROUP_FORCE", "2")
+
+    def run():
+        with torch.no_grad():
+            return gen(x, g)
+
+    assert_workspace_fits(monkeypatch, Handle, "workspace", lambda eng, name, nbytes: nbytes, run)
+
+
 def test_fulldims_b64_x_600(full_gen):
     gen, sd = full_gen
     B, T = 64, 600

@@ -493,6 +493,29 @@ def test_melpostnet2_golden_and_template_dims(golden_taco2, H):
         H.assert_close(out, ref, rt, at, f"postnet2 {mode}")
 
 
+# (the small MelPostnet's 20 mel channels keep it in fp32 in every mode; MelPostnet2's 24 / 64 reach the 16-bit planes)
+@pytest.mark.parametrize("kind,mode", [("mel", "f32"), ("mel2", "f32"), ("mel2", "split_f16"), ("mel2", "bf16")])
+def test_postnet_carved_workspace_fits_the_reported_bytes(kind, mode, golden, golden_taco2, H, monkeypatch):
+    """ttsdec_postnet (MelPostnet / MelPostnet2) at the golden small dims, (B, T) = (2, 37): nothing is written outside
+    ttsdec_postnet_workspace_bytes, and the result is that of a roomy workspace bit for bit."""
+    from torch_tts_amd.engine import Engine
+
+    if kind == "mel":
+        d = golden["meta"]["small_dims"]
+        pn = H.make_postnet(d["d_mel"], d["postnet_hidden"], d["postnet_layers"], golden["post"])
+    else:
+        d = golden_taco2["meta"]["dims"]
+        pn = H.make_postnet2(d["d_mel"], d["postnet_hidden"], d["postnet_layers"], golden_taco2["post"])
+    pn.precision = mode
+    y = torch.randn(2, 37, d["d_mel"], generator=torch.Generator().manual_seed(8)).cuda()
+
+    def run():
+        with torch.no_grad():
+            return pn(y)
+
+    H.assert_workspace_fits(monkeypatch, Engine, "postnet_workspace", lambda eng, B, T: eng.postnet_workspace_bytes(B, T), run)
+
+
 def test_postnet_ljspeech_dims_vs_oracle(H):
     pw = O.random_postnet_weights(80, 512, 3, seed=9)
     g = torch.Generator().manual_seed(2)

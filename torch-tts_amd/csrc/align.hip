@@ -230,7 +230,7 @@ extern "C" {
 
 size_t ttsvits_align_workspace_bytes(const ttsvits_handle* h, int B, int T_y, int T_x) {
   if (check_sizes(h, B, T_y, T_x) != TTSDEC_OK) return 0;
-  return ((size_t)B * T_y * row_bytes(T_x) + 255) / 256 * 256;
+  return up((size_t)B * T_y * row_bytes(T_x), 256);
 }
 
 int ttsvits_neg_cent(ttsvits_handle* h, const float* z_p, const float* m_p, const float* logs_p, const int32_t* t_y, const int32_t* t_x, int B,

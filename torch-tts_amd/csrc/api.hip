@@ -65,9 +65,6 @@ const char* last_hip_error(const HandleBase* h) { return h ? h->hip_err.c_str() 
 namespace {
 
 constexpr int kMaxPostnetLayers = 8;
-constexpr size_t kAlignFloats = 64;  // 256 B
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct BlobLayout {  // offsets in floats
   size_t pre0_w, pre0_b, pre1_w, pre1_b, wq;
@@ -87,16 +84,6 @@ struct BlobLayout {  // offsets in floats
   size_t p2_w[kMaxPostnetLayers][3], p2_wb[kMaxPostnetLayers][3], p2_wh[kMaxPostnetLayers][3], p2_wl[kMaxPostnetLayers][3];
   size_t p2_alpha[kMaxPostnetLayers][2], p2_beta[kMaxPostnetLayers][2];
   size_t wmax;  // [0] max |w| over the decoder matrices that have split-fp16 planes, [1] the same over the Postnet's
-  size_t total;
-};
-
-struct WsLayout {  // offsets in bytes
-  size_t ctrl, xpre0, xpre, ctx, h_att[2], c_att, h_dec[2], c_dec, q, ynext, w[2];
-  size_t xpre_h, xpre_l, ctx_h, ctx_l, h_att_h[2], h_att_l[2], h_dec_h[2], h_dec_l[2];  // split-fp16 planes
-  size_t jparts;  // split-K partial sums of the mel/stop projection [kProjSplit][B, proj_ldp]
-  size_t pa, pd;  // fp32 partial gate sums [B, 4H] of the two LSTMs' early parts (two-role step)
-  size_t loop_stamps;     // measurement only: launch start times of one graph replay [kLoopStampSlots][kLoopStampNodes] (common.h)
-  size_t dep, dep_bytes;  // arrival counters of the two-role launches: [DEP_KINDS][32-row blocks][kDepLine] (common.h)
   size_t total;
 };
 
@@ -195,49 +182,44 @@ inline int proj_parts(const ttsdec_handle* h, int prec, int B) {
 BlobLayout make_blob_layout(const ttsdec_dims& d) {
   BlobLayout L;
   memset(&L, 0, sizeof(L));
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    const size_t o = off;
-    off = align_up(off + n, kAlignFloats);
-    return o;
-  };
-  L.wmax = take(2);
+  Carver cv{nullptr};
+  L.wmax = cv.take_off(2);
   const size_t Ha = d.h_att, Hd = d.h_dec, D = d.d_ctx, P = d.d_pre, Mel = d.d_mel, R = d.r, Ph = pre_hidden(d);
-  L.pre0_w = take(Ph * Mel);
-  L.pre0_b = take(Ph);
-  L.pre1_w = take(P * Ph);
-  L.pre1_b = take(P);
-  L.wq = take(D * (size_t)query_ld(d));
-  L.att_ih = take(4 * Ha * (P + D));
-  L.att_hh = take(4 * Ha * Ha);
-  L.att_b = take(4 * Ha);
-  L.dec_ih = take(4 * Hd * (Ha + D));
-  L.dec_hh = take(4 * Hd * Hd);
-  L.dec_b = take(4 * Hd);
+  L.pre0_w = cv.take_off(Ph * Mel);
+  L.pre0_b = cv.take_off(Ph);
+  L.pre1_w = cv.take_off(P * Ph);
+  L.pre1_b = cv.take_off(P);
+  L.wq = cv.take_off(D * (size_t)query_ld(d));
+  L.att_ih = cv.take_off(4 * Ha * (P + D));
+  L.att_hh = cv.take_off(4 * Ha * Ha);
+  L.att_b = cv.take_off(4 * Ha);
+  L.dec_ih = cv.take_off(4 * Hd * (Ha + D));
+  L.dec_hh = cv.take_off(4 * Hd * Hd);
+  L.dec_b = cv.take_off(4 * Hd);
   // fp16 planes occupy half a float per element
-  L.pre0_h = take((Ph * Mel + 1) / 2); L.pre0_l = take((Ph * Mel + 1) / 2);
-  L.pre1_h = take((P * Ph + 1) / 2); L.pre1_l = take((P * Ph + 1) / 2);
-  L.pre0_ph = take((Ph * Mel + 1) / 2); L.pre0_pl = take((Ph * Mel + 1) / 2);
+  L.pre0_h = cv.take_off((Ph * Mel + 1) / 2); L.pre0_l = cv.take_off((Ph * Mel + 1) / 2);
+  L.pre1_h = cv.take_off((P * Ph + 1) / 2); L.pre1_l = cv.take_off((P * Ph + 1) / 2);
+  L.pre0_ph = cv.take_off((Ph * Mel + 1) / 2); L.pre0_pl = cv.take_off((Ph * Mel + 1) / 2);
   const size_t p64 = (P + 63) / 64 * 64;
-  L.pre1_ph = take((p64 * Ph + 1) / 2); L.pre1_pl = take((p64 * Ph + 1) / 2);
-  L.att_ih_h = take(2 * Ha * (P + D)); L.att_ih_l = take(2 * Ha * (P + D));
-  L.att_hh_h = take(2 * Ha * Ha);      L.att_hh_l = take(2 * Ha * Ha);
-  L.dec_ih_h = take(2 * Hd * (Ha + D)); L.dec_ih_l = take(2 * Hd * (Ha + D));
-  L.dec_hh_h = take(2 * Hd * Hd);      L.dec_hh_l = take(2 * Hd * Hd);
+  L.pre1_ph = cv.take_off((p64 * Ph + 1) / 2); L.pre1_pl = cv.take_off((p64 * Ph + 1) / 2);
+  L.att_ih_h = cv.take_off(2 * Ha * (P + D)); L.att_ih_l = cv.take_off(2 * Ha * (P + D));
+  L.att_hh_h = cv.take_off(2 * Ha * Ha);      L.att_hh_l = cv.take_off(2 * Ha * Ha);
+  L.dec_ih_h = cv.take_off(2 * Hd * (Ha + D)); L.dec_ih_l = cv.take_off(2 * Hd * (Ha + D));
+  L.dec_hh_h = cv.take_off(2 * Hd * Hd);      L.dec_hh_l = cv.take_off(2 * Hd * Hd);
   if (chunk_ok(d)) {
-    L.att_ih_ch = take(2 * Ha * (P + D)); L.att_ih_cl = take(2 * Ha * (P + D));
-    L.att_hh_ch = take(2 * Ha * Ha);      L.att_hh_cl = take(2 * Ha * Ha);
-    L.dec_ih_ch = take(2 * Hd * (Ha + D)); L.dec_ih_cl = take(2 * Hd * (Ha + D));
-    L.dec_hh_ch = take(2 * Hd * Hd);      L.dec_hh_cl = take(2 * Hd * Hd);
+    L.att_ih_ch = cv.take_off(2 * Ha * (P + D)); L.att_ih_cl = cv.take_off(2 * Ha * (P + D));
+    L.att_hh_ch = cv.take_off(2 * Ha * Ha);      L.att_hh_cl = cv.take_off(2 * Ha * Ha);
+    L.dec_ih_ch = cv.take_off(2 * Hd * (Ha + D)); L.dec_ih_cl = cv.take_off(2 * Hd * (Ha + D));
+    L.dec_hh_ch = cv.take_off(2 * Hd * Hd);      L.dec_hh_cl = cv.take_off(2 * Hd * Hd);
   }
-  L.h0a = take(Ha);
-  L.c0a = take(Ha);
-  L.h0d = take(Hd);
-  L.c0d = take(Hd);
-  L.proj_w = take((R * Mel + R) * (size_t)proj_ld(d));
-  L.proj_b = take(R * Mel + R);
-  L.wq_h = take((D * (size_t)query_ld(d) + 1) / 2); L.wq_l = take((D * (size_t)query_ld(d) + 1) / 2);
-  L.proj_h = take(((R * Mel + R) * (size_t)proj_ld(d) + 1) / 2); L.proj_l = take(((R * Mel + R) * (size_t)proj_ld(d) + 1) / 2);
+  L.h0a = cv.take_off(Ha);
+  L.c0a = cv.take_off(Ha);
+  L.h0d = cv.take_off(Hd);
+  L.c0d = cv.take_off(Hd);
+  L.proj_w = cv.take_off((R * Mel + R) * (size_t)proj_ld(d));
+  L.proj_b = cv.take_off(R * Mel + R);
+  L.wq_h = cv.take_off((D * (size_t)query_ld(d) + 1) / 2); L.wq_l = cv.take_off((D * (size_t)query_ld(d) + 1) / 2);
+  L.proj_h = cv.take_off(((R * Mel + R) * (size_t)proj_ld(d) + 1) / 2); L.proj_l = cv.take_off(((R * Mel + R) * (size_t)proj_ld(d) + 1) / 2);
   size_t cin = Mel;
   if (d.postnet_type == TTSDEC_POSTNET_TYPE_MEL2) {
     const size_t Hh = d.postnet_hidden, k = d.postnet_kernel;
@@ -245,71 +227,29 @@ BlobLayout make_blob_layout(const ttsdec_dims& d) {
     for (int i = 0; i < d.postnet_layers; ++i) {
       for (int c = 0; c < 3; ++c) {
         const size_t n = shapes[c][0] * shapes[c][1] * k;
-        L.p2_w[i][c] = take(n);
-        L.p2_wb[i][c] = take((n + 1) / 2); L.p2_wh[i][c] = take((n + 1) / 2); L.p2_wl[i][c] = take((n + 1) / 2);
+        L.p2_w[i][c] = cv.take_off(n);
+        L.p2_wb[i][c] = cv.take_off((n + 1) / 2); L.p2_wh[i][c] = cv.take_off((n + 1) / 2); L.p2_wl[i][c] = cv.take_off((n + 1) / 2);
       }
-      for (int c = 0; c < 2; ++c) { L.p2_alpha[i][c] = take(Hh); L.p2_beta[i][c] = take(Hh); }
+      for (int c = 0; c < 2; ++c) { L.p2_alpha[i][c] = cv.take_off(Hh); L.p2_beta[i][c] = cv.take_off(Hh); }
     }
-    L.total = off;
+    L.total = cv.off;
     return L;
   }
   for (int i = 0; i < d.postnet_layers; ++i) {
-    L.conv_w[i] = take((size_t)d.postnet_hidden * d.postnet_kernel * cin);
-    L.conv_alpha[i] = take(d.postnet_hidden);
-    L.conv_beta[i] = take(d.postnet_hidden);
+    L.conv_w[i] = cv.take_off((size_t)d.postnet_hidden * d.postnet_kernel * cin);
+    L.conv_alpha[i] = cv.take_off(d.postnet_hidden);
+    L.conv_beta[i] = cv.take_off(d.postnet_hidden);
     const size_t nh = ((size_t)d.postnet_hidden * d.postnet_kernel * cin + 1) / 2;  // 16-bit plane, in floats
-    L.conv_wb[i] = take(nh); L.conv_wh[i] = take(nh); L.conv_wl[i] = take(nh);
+    L.conv_wb[i] = cv.take_off(nh); L.conv_wh[i] = cv.take_off(nh); L.conv_wl[i] = cv.take_off(nh);
     cin = d.postnet_hidden;
   }
   if (d.postnet_layers > 0) {
-    L.fc_w = take(Mel * (size_t)d.postnet_hidden);
+    L.fc_w = cv.take_off(Mel * (size_t)d.postnet_hidden);
     const size_t nh = (Mel * (size_t)d.postnet_hidden + 1) / 2;
-    L.fc_wb = take(nh); L.fc_wh = take(nh); L.fc_wl = take(nh);
+    L.fc_wb = cv.take_off(nh); L.fc_wh = cv.take_off(nh); L.fc_wl = cv.take_off(nh);
   }
-  L.total = off;
+  L.total = cv.off;
   return L;
-}
-
-WsLayout make_ws_layout(const ttsdec_dims& d, int B, int Lm) {
-  WsLayout W;
-  size_t off = 0;
-  auto take = [&](size_t nfloats) {
-    const size_t o = off;
-    off = align_up(off + nfloats * sizeof(float), 256);
-    return o;
-  };
-  W.ctrl = off;
-  off += align_up(sizeof(Ctrl), 256);
-  const size_t b = (size_t)B;
-  W.xpre0 = take(b * pre_hidden(d));
-  W.xpre = take(b * d.d_pre);
-  W.ctx = take(b * d.d_ctx);
-  W.h_att[0] = take(b * d.h_att);
-  W.h_att[1] = take(b * d.h_att);
-  W.c_att = take(b * d.h_att);
-  W.h_dec[0] = take(b * d.h_dec);
-  W.h_dec[1] = take(b * d.h_dec);
-  W.c_dec = take(b * d.h_dec);
-  W.q = take((size_t)kQuerySplit * b * d.d_ctx);
-  W.ynext = take(b * d.d_mel);
-  W.w[0] = take(b * Lm);
-  W.w[1] = take(b * Lm);
-  auto takeh = [&](size_t nhalfs) { return take((nhalfs + 1) / 2); };
-  const size_t bp = (size_t)rows_pad(B);  // (the chunked layout pads the rows of a plane to whole 64-row blocks)
-  W.xpre_h = takeh(bp * d.d_pre); W.xpre_l = takeh(bp * d.d_pre);
-  W.ctx_h = takeh(bp * d.d_ctx); W.ctx_l = takeh(bp * d.d_ctx);
-  for (int i = 0; i < 2; ++i) {
-    W.h_att_h[i] = takeh(bp * d.h_att); W.h_att_l[i] = takeh(bp * d.h_att);
-    W.h_dec_h[i] = takeh(bp * d.h_dec); W.h_dec_l[i] = takeh(bp * d.h_dec);
-  }
-  W.jparts = take((size_t)kProjSplit * b * proj_ldp(d));
-  W.pa = take(b * 4 * d.h_att);
-  W.pd = take(b * 4 * d.h_dec);
-  W.loop_stamps = take(kLoopStampSlots * kLoopStampNodes * 2);
-  W.dep_bytes = (size_t)DEP_KINDS * ((B + 31) / 32) * kDepLine * sizeof(unsigned int);
-  W.dep = take(W.dep_bytes / sizeof(float));
-  W.total = off;
-  return W;
 }
 
 int check_dims(const ttsdec_dims& d) {
@@ -342,33 +282,38 @@ struct StepBufs {
   Ctrl* ctrl;
   float *xpre0, *xpre, *ctx, *h_att[2], *c_att, *h_dec[2], *c_dec, *q, *ynext, *w[2];
   f16 *xpre_h, *xpre_l, *ctx_h, *ctx_l, *h_att_h[2], *h_att_l[2], *h_dec_h[2], *h_dec_l[2];
-  float* jparts;
-  float *pa, *pd;
-  unsigned long long* loop_stamps;
-  unsigned int* dep;
+  float* jparts;  // split-K partial sums of the mel/stop projection [kProjSplit][B, proj_ldp]
+  float *pa, *pd;  // fp32 partial gate sums [B, 4H] of the two LSTMs' early parts (two-role step)
+  unsigned long long* loop_stamps;  // measurement only: launch start times of one graph replay [kLoopStampSlots][kLoopStampNodes] (common.h)
+  unsigned int* dep;  // arrival counters of the two-role launches: [DEP_KINDS][32-row blocks][kDepLine] (common.h), dep_bytes in all
+  size_t dep_bytes;
   int dep_blocks;  // 32-row blocks of the batch: dep + kind * dep_blocks * kDepLine is a hand-off kind's counter array
 };
 
-StepBufs carve(const WsLayout& W, void* ws) {
-  char* p = static_cast<char*>(ws);
+// The decode workspace (carved as layout.h's Carver comment says)
+StepBufs carve(Carver& cv, const ttsdec_dims& d, int B, int Lm) {
   StepBufs s;
-  s.ctrl = reinterpret_cast<Ctrl*>(p + W.ctrl);
-  auto f = [&](size_t off) { return reinterpret_cast<float*>(p + off); };
-  s.xpre0 = f(W.xpre0); s.xpre = f(W.xpre); s.ctx = f(W.ctx);
-  s.h_att[0] = f(W.h_att[0]); s.h_att[1] = f(W.h_att[1]); s.c_att = f(W.c_att);
-  s.h_dec[0] = f(W.h_dec[0]); s.h_dec[1] = f(W.h_dec[1]); s.c_dec = f(W.c_dec);
-  s.q = f(W.q); s.ynext = f(W.ynext); s.w[0] = f(W.w[0]); s.w[1] = f(W.w[1]);
-  auto hf = [&](size_t off) { return reinterpret_cast<f16*>(p + off); };
-  s.xpre_h = hf(W.xpre_h); s.xpre_l = hf(W.xpre_l); s.ctx_h = hf(W.ctx_h); s.ctx_l = hf(W.ctx_l);
+  s.ctrl = reinterpret_cast<Ctrl*>(cv.take((sizeof(Ctrl) + sizeof(float) - 1) / sizeof(float)));
+  const size_t b = (size_t)B;
+  s.xpre0 = cv.take(b * pre_hidden(d)); s.xpre = cv.take(b * d.d_pre); s.ctx = cv.take(b * d.d_ctx);
+  s.h_att[0] = cv.take(b * d.h_att); s.h_att[1] = cv.take(b * d.h_att); s.c_att = cv.take(b * d.h_att);
+  s.h_dec[0] = cv.take(b * d.h_dec); s.h_dec[1] = cv.take(b * d.h_dec); s.c_dec = cv.take(b * d.h_dec);
+  s.q = cv.take((size_t)kQuerySplit * b * d.d_ctx);
+  s.ynext = cv.take(b * d.d_mel); s.w[0] = cv.take(b * Lm); s.w[1] = cv.take(b * Lm);
+  auto takeh = [&](size_t nhalfs) { return cv.take_h((nhalfs + 1) / 2); };
+  const size_t bp = (size_t)rows_pad(B);  // (the chunked layout pads the rows of a plane to whole 64-row blocks)
+  s.xpre_h = takeh(bp * d.d_pre); s.xpre_l = takeh(bp * d.d_pre);
+  s.ctx_h = takeh(bp * d.d_ctx); s.ctx_l = takeh(bp * d.d_ctx);
   for (int i = 0; i < 2; ++i) {
-    s.h_att_h[i] = hf(W.h_att_h[i]); s.h_att_l[i] = hf(W.h_att_l[i]);
-    s.h_dec_h[i] = hf(W.h_dec_h[i]); s.h_dec_l[i] = hf(W.h_dec_l[i]);
+    s.h_att_h[i] = takeh(bp * d.h_att); s.h_att_l[i] = takeh(bp * d.h_att);
+    s.h_dec_h[i] = takeh(bp * d.h_dec); s.h_dec_l[i] = takeh(bp * d.h_dec);
   }
-  s.jparts = f(W.jparts);
-  s.pa = f(W.pa); s.pd = f(W.pd);
-  s.loop_stamps = reinterpret_cast<unsigned long long*>(p + W.loop_stamps);
-  s.dep = reinterpret_cast<unsigned int*>(p + W.dep);
-  s.dep_blocks = (int)(W.dep_bytes / (DEP_KINDS * kDepLine * sizeof(unsigned int)));
+  s.jparts = cv.take((size_t)kProjSplit * b * proj_ldp(d));
+  s.pa = cv.take(b * 4 * d.h_att); s.pd = cv.take(b * 4 * d.h_dec);
+  s.loop_stamps = reinterpret_cast<unsigned long long*>(cv.take(kLoopStampSlots * kLoopStampNodes * 2));
+  s.dep_blocks = (B + 31) / 32;
+  s.dep_bytes = (size_t)DEP_KINDS * s.dep_blocks * kDepLine * sizeof(unsigned int);
+  s.dep = reinterpret_cast<unsigned int*>(cv.take(s.dep_bytes / sizeof(float)));
   return s;
 }
 
@@ -1175,7 +1120,9 @@ int ttsdec_bind_weights(ttsdec_handle* h, const void* blob) {
 
 size_t ttsdec_workspace_bytes(const ttsdec_handle* h, int B, int L) {
   if (!h || B <= 0 || L <= 0) return 0;
-  return make_ws_layout(h->d, B, L).total;
+  Carver cv{nullptr};
+  carve(cv, h->d, B, L);
+  return cv.bytes();
 }
 
 // stamp_loop (ttsdec_profile_loop): every step kernel records its start time (common.h loop_stamp) in the workspace
@@ -1192,10 +1139,10 @@ static int decode_impl(ttsdec_handle* h, const float* memory, int B, int L, int 
   if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
   int rc = check_device(h);
   if (rc != TTSDEC_OK) return rc;
-  const WsLayout W = make_ws_layout(h->d, B, L);
-  if (workspace_bytes < W.total || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  Carver cv{static_cast<float*>(workspace)};
+  const StepBufs sb = carve(cv, h->d, B, L);
+  if (workspace_bytes < cv.bytes() || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const StepBufs sb = carve(W, workspace);
   const ttsdec_dims& d = h->d;
 
   if (t_begin & 1) return TTSDEC_ERR_INVALID_ARG;  // buffer parity is tied to the step index
@@ -1234,7 +1181,7 @@ static int decode_impl(ttsdec_handle* h, const float* memory, int B, int L, int 
     ca.stamps = h->stamps_buf;
   }
   launch_set_call(sb.ctrl, ca, st);
-  HIP_TRY(h, hipMemsetAsync(sb.dep, 0, W.dep_bytes, st));  // arrival counters count from the call's first step
+  HIP_TRY(h, hipMemsetAsync(sb.dep, 0, sb.dep_bytes, st));  // arrival counters count from the call's first step
 
   StepIo io;
   memset(&io, 0, sizeof(io));
@@ -1281,15 +1228,16 @@ int ttsdec_profile_loop(ttsdec_handle* h, const float* memory, int B, int L, int
   const StepOrder& order = step_order(h, B);
   if (n_kernels) *n_kernels = order.n;
   if (n_out < order.n || order.n >= kLoopStampNodes) return TTSDEC_ERR_INVALID_ARG;
-  const WsLayout W = make_ws_layout(h->d, B, L);
-  if (workspace_bytes < W.total) return TTSDEC_ERR_WORKSPACE;
+  Carver cv{static_cast<float*>(workspace)};
+  const StepBufs sb = carve(cv, h->d, B, L);
+  if (workspace_bytes < cv.bytes()) return TTSDEC_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   int rc = decode_impl(h, memory, B, L, 0, n_steps, n_steps, -1e30f, 0, dropout_mode, masks, seed, nullptr, 0, nullptr, y, s, w, T_out, workspace,
                        workspace_bytes, stream, true);
   if (rc != TTSDEC_OK) return rc;
   unsigned long long t[kLoopStampSlots * kLoopStampNodes];
   HIP_TRY(h, hipStreamSynchronize(st));
-  HIP_TRY(h, hipMemcpy(t, static_cast<char*>(workspace) + W.loop_stamps, sizeof(t), hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(t, sb.loop_stamps, sizeof(t), hipMemcpyDeviceToHost));
   // the LAST replay's start times: slots 0 .. kGraphSlots-1; a launch's span = the next launch's start - its own
   // (s_memrealtime ticks of 10 ns); the last launch of the last slot has no successor inside the replay and is left out
   double total = 0.0;
@@ -1312,13 +1260,30 @@ int ttsdec_profile_loop(ttsdec_handle* h, const float* memory, int B, int L, int
   return TTSDEC_OK;
 }
 
+// The Postnet's workspace (carved as layout.h's Carver comment says): two activation buffers (fp32, or hi + lo fp16 planes, or one
+// bf16 plane), then MelPostnet: the 16-bit planes of the input; MelPostnet2: the fp32 residual stream and its 16-bit planes, both
+// ping-pong
+struct PostnetWs {
+  char *act[2], *yin, *xbuf[2], *xpl[2];
+};
+static PostnetWs carve_postnet(Carver& cv, const ttsdec_dims& d, size_t M) {
+  auto take = [&](size_t nfloats) { return reinterpret_cast<char*>(cv.take(nfloats)); };
+  PostnetWs w = {};
+  for (char*& a : w.act) a = take(M * d.postnet_hidden);
+  if (d.postnet_type != TTSDEC_POSTNET_TYPE_MEL2) {
+    w.yin = take(M * d.d_mel);
+    return w;
+  }
+  for (char*& x : w.xbuf) x = take(M * d.d_mel);
+  for (char*& x : w.xpl) x = take(M * d.d_mel);
+  return w;
+}
+
 size_t ttsdec_postnet_workspace_bytes(const ttsdec_handle* h, int B, int T) {
   if (!h || B <= 0 || T <= 0 || h->d.postnet_layers <= 0) return 0;
-  // two activation buffers (fp32, or hi+lo fp16 planes, or one bf16 plane) + 16-bit planes of the input
-  // (+ for MelPostnet2: two fp32 residual-stream buffers and a second plane buffer)
-  const size_t act = align_up((size_t)B * T * h->d.postnet_hidden * sizeof(float), 256);
-  const size_t xin = align_up((size_t)B * T * h->d.d_mel * sizeof(float), 256);
-  return 2 * act + (h->d.postnet_type == TTSDEC_POSTNET_TYPE_MEL2 ? 4 * xin : xin);
+  Carver cv{nullptr};
+  carve_postnet(cv, h->d, (size_t)B * T);
+  return cv.bytes();
 }
 
 int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision, float* y_post, void* workspace,
@@ -1342,17 +1307,16 @@ int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision
     if (precision == TTSDEC_POSTNET_SPLIT_F16 && h->wmax_post < kSplitMax) prec = PREC_F16S;
   }
   const size_t M = (size_t)B * T;
-  const size_t act_bytes = align_up(M * d.postnet_hidden * sizeof(float), 256);
-  char* wsb = static_cast<char*>(workspace);
-  char* act[2] = {wsb, wsb + act_bytes};
-  char* yin = wsb + 2 * act_bytes;
+  Carver cv{static_cast<float*>(workspace)};
+  const PostnetWs pw = carve_postnet(cv, d, M);
+  char* const* act = pw.act;
+  char* yin = pw.yin;
   auto plane = [&](size_t float_off) { return reinterpret_cast<const void*>(h->blob + float_off); };
 
   if (d.postnet_type == TTSDEC_POSTNET_TYPE_MEL2) {
     // MelPostnet2.forward (modules.py:213-216): x = x + conv3(lrelu(BN(conv2(lrelu(BN(conv1(x))))))) per layer
-    const size_t xin_bytes = align_up(M * d.d_mel * sizeof(float), 256);
-    char* xbuf[2] = {yin, yin + xin_bytes};             // fp32 residual stream, ping-pong
-    char* xpl[2] = {yin + 2 * xin_bytes, yin + 3 * xin_bytes};  // its 16-bit planes, ping-pong
+    char* const* xbuf = pw.xbuf;  // fp32 residual stream, ping-pong
+    char* const* xpl = pw.xpl;    // its 16-bit planes, ping-pong
     const int Hh = d.postnet_hidden, kk = d.postnet_kernel;
     const float* xcur = y;
     const void *x0 = y, *x1 = y;
@@ -1493,10 +1457,10 @@ int ttsdec_cell_step(ttsdec_handle* h, const float* x, const float* memory, int 
   if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
   int rc = check_device(h);
   if (rc != TTSDEC_OK) return rc;
-  const WsLayout W = make_ws_layout(h->d, B, L);
-  if (workspace_bytes < W.total || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  Carver cv{static_cast<float*>(workspace)};
+  const StepBufs sb = carve(cv, h->d, B, L);
+  if (workspace_bytes < cv.bytes() || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const StepBufs sb = carve(W, workspace);
   const ttsdec_dims& d = h->d;
   const size_t b = (size_t)B;
   const int p = step & 1;
@@ -1586,10 +1550,10 @@ int ttsdec_profile_step(ttsdec_handle* h, const float* memory, int B, int L, int
   if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
   int rc = check_device(h);
   if (rc != TTSDEC_OK) return rc;
-  const WsLayout W = make_ws_layout(h->d, B, L);
-  if (workspace_bytes < W.total || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  Carver cv{static_cast<float*>(workspace)};
+  const StepBufs sb = carve(cv, h->d, B, L);
+  if (workspace_bytes < cv.bytes() || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const StepBufs sb = carve(W, workspace);
   StepIo io;
   memset(&io, 0, sizeof(io));
   io.memory = memory; io.B = B; io.L = L; io.t = 0; io.t_rel = 0; io.t_stride = 1;

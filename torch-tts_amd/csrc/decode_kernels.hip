@@ -700,6 +700,19 @@ void launch_copy(const float* src, float* dst, size_t n, hipStream_t st) {
   hipLaunchKernelGGL(copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst, n);
 }
 
+// cond(g) (a 1x1 conv on [B, K, 1]): out[b, n] = bias[n] + sum_k W[n, k] g[b, k], k in order
+__global__ void cond_kernel(const float* g, const float* W, const float* bias, float* out, int B, int N, int K) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * N) return;
+  const int b = i / N, n = i % N;
+  float acc = 0.f;
+  for (int k = 0; k < K; ++k) acc = fmaf(W[(size_t)n * K + k], g[(size_t)b * K + k], acc);
+  out[i] = __fadd_rn(acc, bias[n]);
+}
+void launch_cond(const float* g, const float* W, const float* bias, float* out, int B, int N, int K, hipStream_t st) {
+  hipLaunchKernelGGL(cond_kernel, dim3((unsigned)(((size_t)B * N + 255) / 256)), dim3(256), 0, st, g, W, bias, out, B, N, K);
+}
+
 __global__ void split_kernel(const float* src, f16* hi, f16* lo, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) split_f16(src[i], hi[i], lo[i]);

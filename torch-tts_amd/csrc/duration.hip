@@ -24,15 +24,12 @@
 using namespace ttsdec;
 
 namespace {
-constexpr size_t kAlign = 64;  // floats
 constexpr int kRows = 16;      // frames per workgroup tile
 constexpr int kThreads = 256;
 constexpr int kMaxC = 256;     // LDS: 3 x kRows x C floats (DDSConv), kRows x (3 C_in + N) floats (pw_conv) <= 64 KiB
 constexpr int kBins = 10;      // ConvFlow num_bins
 constexpr int kProj = 3 * kBins - 1;
 constexpr float kTail = 5.f;   // ConvFlow tail_bound
-inline size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 struct DdsW {  // one DDSConv (3 layers), offsets in floats
   size_t dw_w[3], dw_b[3];     // [3][C] tap-major, [C]
@@ -75,54 +72,53 @@ bool dims_ok(const ttsdur_dims& d) {
 DurBlob make_layout(const ttsdur_dims& d) {
   DurBlob L;
   memset(&L, 0, sizeof(L));
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off = up(off + n, kAlign); return o; };
+  Carver cv{nullptr};
   const size_t C = d.in_channels;
   auto dds = [&](DdsW& w) {
     for (int i = 0; i < 3; ++i) {
-      w.dw_w[i] = take(3 * C);
-      w.dw_b[i] = take(C);
-      w.pw_w[i] = take(C * C);
-      w.pw_b[i] = take(C);
-      w.n1g[i] = take(C);
-      w.n1b[i] = take(C);
-      w.n2g[i] = take(C);
-      w.n2b[i] = take(C);
+      w.dw_w[i] = cv.take_off(3 * C);
+      w.dw_b[i] = cv.take_off(C);
+      w.pw_w[i] = cv.take_off(C * C);
+      w.pw_b[i] = cv.take_off(C);
+      w.n1g[i] = cv.take_off(C);
+      w.n1b[i] = cv.take_off(C);
+      w.n2g[i] = cv.take_off(C);
+      w.n2b[i] = cv.take_off(C);
     }
   };
   if (d.kind == 0) {
-    L.pre_w = take(C * C);
-    L.pre_b = take(C);
+    L.pre_w = cv.take_off(C * C);
+    L.pre_b = cv.take_off(C);
     dds(L.convs);
-    L.proj_w = take(C * C);
-    L.proj_b = take(C);
-    L.ea_m = take(2);
-    L.ea_logs = take(2);
+    L.proj_w = cv.take_off(C * C);
+    L.proj_b = cv.take_off(C);
+    L.ea_m = cv.take_off(2);
+    L.ea_logs = cv.take_off(2);
     for (int k = 0; k < d.n_flows - 1; ++k) {
-      L.f_pre_w[k] = take(C);
-      L.f_pre_b[k] = take(C);
+      L.f_pre_w[k] = cv.take_off(C);
+      L.f_pre_b[k] = cv.take_off(C);
       dds(L.f_convs[k]);
-      L.f_proj_w[k] = take(C * kProj);
-      L.f_proj_b[k] = take(kProj);
+      L.f_proj_w[k] = cv.take_off(C * kProj);
+      L.f_proj_b[k] = cv.take_off(kProj);
     }
   } else {
     const size_t F = d.filter_channels;
-    L.c1_w = take(3 * C * F);
-    L.c1_b = take(F);
-    L.n1g = take(F);
-    L.n1b = take(F);
-    L.c2_w = take(3 * F * F);
-    L.c2_b = take(F);
-    L.n2g = take(F);
-    L.n2b = take(F);
-    L.p_w = take(F);
-    L.p_b = take(1);
+    L.c1_w = cv.take_off(3 * C * F);
+    L.c1_b = cv.take_off(F);
+    L.n1g = cv.take_off(F);
+    L.n1b = cv.take_off(F);
+    L.c2_w = cv.take_off(3 * F * F);
+    L.c2_b = cv.take_off(F);
+    L.n2g = cv.take_off(F);
+    L.n2b = cv.take_off(F);
+    L.p_w = cv.take_off(F);
+    L.p_b = cv.take_off(1);
   }
   if (d.gin_channels > 0) {
-    L.cond_w = take(C * d.gin_channels);
-    L.cond_b = take(C);
+    L.cond_w = cv.take_off(C * d.gin_channels);
+    L.cond_b = cv.take_off(C);
   }
-  L.total = off;
+  L.total = cv.off;
   return L;
 }
 
@@ -131,11 +127,26 @@ int n_tensors(const ttsdur_dims& d) {
   return d.kind == 0 ? 2 + 24 + 2 + 2 + (d.n_flows - 1) * 28 + g : 10 + g;
 }
 
-size_t ws_floats(const ttsdur_dims& d, int B, int T) {
-  const size_t M = (size_t)B * T, C = d.in_channels;
-  const size_t cond = up((size_t)B * C, kAlign);
-  if (d.kind == 0) return 4 * up(M * C, kAlign) + up(2 * M, kAlign) + cond;
-  return up(M * d.filter_channels, kAlign) + cond;
+// The workspaces of the two predictors (carved as layout.h's Carver comment says)
+struct SdpWs { float *XP, *XA, *XB, *XC, *Z, *condv; };  // four [M, C] activations; [B, 2, T] the flows' state; [B, C] cond(g)
+SdpWs carve_sdp(Carver& cv, const ttsdur_dims& d, size_t B, size_t T) {
+  const size_t MC = B * T * d.in_channels;
+  SdpWs w;
+  w.XP = cv.take(MC); w.XA = cv.take(MC); w.XB = cv.take(MC); w.XC = cv.take(MC);
+  w.Z = cv.take(2 * B * T); w.condv = cv.take(B * d.in_channels);
+  return w;
+}
+struct DpWs { float *H1, *condv; };  // [M, F] conv_1's output; [B, C] cond(g)
+DpWs carve_dp(Carver& cv, const ttsdur_dims& d, size_t B, size_t T) {
+  DpWs w;
+  w.H1 = cv.take(B * T * d.filter_channels); w.condv = cv.take(B * d.in_channels);
+  return w;
+}
+size_t carved_bytes(const ttsdur_dims& d, int B, int T) {
+  Carver cv{nullptr};
+  if (d.kind == 0) carve_sdp(cv, d, B, T);
+  else carve_dp(cv, d, B, T);
+  return cv.bytes();
 }
 
 // ===========================================================================
@@ -251,16 +262,6 @@ __device__ float spline_inverse(float x, const float* h, float sqrt_c) {
 // ===========================================================================
 // kernels
 // ===========================================================================
-// cond(g): out[b, n] = bias[n] + sum_k W[n, k] g[b, k]
-__global__ void dur_cond_kernel(const float* g, const float* W, const float* bias, float* out, int B, int N, int K) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * N) return;
-  const int b = i / N, n = i % N;
-  float acc = 0.f;
-  for (int k = 0; k < K; ++k) acc = fmaf(W[(size_t)n * K + k], g[(size_t)b * K + k], acc);
-  out[i] = acc + bias[n];
-}
-
 // src [N, Cin, taps] (a Conv1d weight) -> dst [taps * Cin][N] (K-major: row tap * Cin + ci)
 __global__ void pack_kmajor_kernel(const float* src, float* dst, int N, int Cin, int taps) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -573,7 +574,7 @@ int check_call(ttsdur_handle* h, int kind, const float* x, const int* lengths, c
   if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
   if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
   if ((size_t)B * T > (size_t)1 << 30) return TTSDEC_ERR_DIMS;
-  if (ws_bytes < ws_floats(h->d, B, T) * sizeof(float) || (reinterpret_cast<uintptr_t>(ws) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (ws_bytes < carved_bytes(h->d, B, T) || (reinterpret_cast<uintptr_t>(ws) & 255)) return TTSDEC_ERR_WORKSPACE;
   if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   return TTSDEC_OK;
 }
@@ -666,7 +667,7 @@ int ttsdur_bind_weights(ttsdur_handle* h, const void* blob) { return bind_blob(h
 
 size_t ttsdur_workspace_bytes(const ttsdur_handle* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
-  return ws_floats(h->d, B, T) * sizeof(float);
+  return carved_bytes(h->d, B, T);
 }
 
 int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths, const float* g, const float* noise, float noise_scale, int B,
@@ -679,13 +680,11 @@ int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths,
   const DurBlob& L = h->bl;
   const float* b = h->blob;
   const int C = d.in_channels, M = B * T;
-  const size_t F = up((size_t)M * C, kAlign);
-  float* ws = static_cast<float*>(workspace);
-  float *XP = ws, *XA = ws + F, *XB = ws + 2 * F, *XC = ws + 3 * F;
-  float* Z = ws + 4 * F;                       // [B, 2, T]
-  float* condv = Z + up((size_t)2 * M, kAlign);  // [B, C]
+  Carver cv{static_cast<float*>(workspace)};
+  const SdpWs w = carve_sdp(cv, d, B, T);
+  float *XP = w.XP, *XA = w.XA, *XB = w.XB, *XC = w.XC, *Z = w.Z, *condv = w.condv;
   const unsigned nblk = (unsigned)((M + kRows - 1) / kRows);
-  if (g) hipLaunchKernelGGL(dur_cond_kernel, grid1((size_t)B * C), dim3(256), 0, st, g, b + L.cond_w, b + L.cond_b, condv, B, C, d.gin_channels);
+  if (g) launch_cond(g, b + L.cond_w, b + L.cond_b, condv, B, C, d.gin_channels, st);
   {  // models.py:80-84: x = pre(x) (+ cond(g))
     PwArgs p;
     memset(&p, 0, sizeof(p));
@@ -732,11 +731,11 @@ int ttsdur_dp_forward(ttsdur_handle* h, const float* x, const int32_t* lengths, 
   const DurBlob& L = h->bl;
   const float* b = h->blob;
   const int C = d.in_channels, Fc = d.filter_channels, M = B * T;
-  float* ws = static_cast<float*>(workspace);
-  float* H1 = ws;
-  float* condv = ws + up((size_t)M * Fc, kAlign);
+  Carver cv{static_cast<float*>(workspace)};
+  const DpWs w = carve_dp(cv, d, B, T);
+  float *H1 = w.H1, *condv = w.condv;
   const unsigned nblk = (unsigned)((M + kRows - 1) / kRows);
-  if (g) hipLaunchKernelGGL(dur_cond_kernel, grid1((size_t)B * C), dim3(256), 0, st, g, b + L.cond_w, b + L.cond_b, condv, B, C, d.gin_channels);
+  if (g) launch_cond(g, b + L.cond_w, b + L.cond_b, condv, B, C, d.gin_channels, st);
   PwArgs p;
   memset(&p, 0, sizeof(p));
   p.lengths = lengths; p.T = T; p.M = M; p.taps = 3; p.in_mask = 1; p.relu_ln = 1;

@@ -15,9 +15,6 @@
 using namespace ttsdec;
 
 namespace {
-constexpr size_t kAlign = 64;  // floats
-inline size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 struct EncBlob {  // offsets in floats
   size_t emb, conv_w[3], alpha[3], beta[3], w_ih, w_hh[2], h0, c0, total;
 };
@@ -35,24 +32,23 @@ namespace {
 EncBlob make_layout(const ttsenc_dims& d) {
   EncBlob L;
   memset(&L, 0, sizeof(L));
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off = up(off + n, kAlign); return o; };
+  Carver cv{nullptr};
   const size_t E = d.d_emb, H = d.d_out / 2, k = d.conv_kernel;
-  L.emb = take((size_t)d.alphabet_size * E);
+  L.emb = cv.take_off((size_t)d.alphabet_size * E);
   // (GEMM weights of n elements take 2n floats: fp32 | fp16 hi plane | fp16 lo plane)
-  for (int i = 0; i < 3; ++i) { L.conv_w[i] = take(2 * E * k * E); L.alpha[i] = take(E); L.beta[i] = take(E); }
-  L.w_ih = take(2 * 8 * H * 2 * E);  // [fwd i,f,g,o ; rev i,f,g,o] x [conv | emb]
-  L.w_hh[0] = take(4 * H * H);
-  L.w_hh[1] = take(4 * H * H);
-  L.h0 = take(2 * H);
-  L.c0 = take(2 * H);
-  L.total = off;
+  for (int i = 0; i < 3; ++i) { L.conv_w[i] = cv.take_off(2 * E * k * E); L.alpha[i] = cv.take_off(E); L.beta[i] = cv.take_off(E); }
+  L.w_ih = cv.take_off(2 * 8 * H * 2 * E);  // [fwd i,f,g,o ; rev i,f,g,o] x [conv | emb]
+  L.w_hh[0] = cv.take_off(4 * H * H);
+  L.w_hh[1] = cv.take_off(4 * H * H);
+  L.h0 = cv.take_off(2 * H);
+  L.c0 = cv.take_off(2 * H);
+  L.total = cv.off;
   return L;
 }
 EncWs make_ws(const ttsenc_dims& d, int B, int Lm) {
   EncWs W;
-  size_t off = 0;
-  auto take = [&](size_t nfloats) { const size_t o = off; off = up(off + nfloats * sizeof(float), 256); return o; };
+  Carver cv{nullptr};
+  auto take = [&](size_t nfloats) { return cv.take_off(nfloats) * sizeof(float); };
   const size_t M = (size_t)B * Lm, E = d.d_emb, H = d.d_out / 2;
   W.x = take(M * E);
   W.act[0] = take(M * E);
@@ -65,7 +61,7 @@ EncWs make_ws(const ttsenc_dims& d, int B, int Lm) {
     W.c[dir] = take((size_t)B * H);
   }
   W.planes = take(M * 2 * E);  // hi + lo fp16 planes of one GEMM's A operand
-  W.total = off;
+  W.total = cv.bytes();
   return W;
 }
 }  // namespace

@@ -10,12 +10,21 @@ namespace ttsdec {
 
 constexpr int kFftThreads = 256;
 
+inline int lg2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+inline bool fft_ok(int n_fft) { return n_fft == 256 || n_fft == 512 || n_fft == 1024 || n_fft == 2048; }  // the sizes the passes below cover
+
 struct cf { float x, y; };
 __device__ inline cf cadd(cf a, cf b) { return {a.x + b.x, a.y + b.y}; }
 __device__ inline cf csub(cf a, cf b) { return {a.x - b.x, a.y - b.y}; }
 __device__ inline cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 __device__ inline cf mul_mi(cf a) { return {a.y, -a.x}; }  // a * -i
 __device__ inline int swz(int i) { return i ^ (((i >> 3) ^ (i >> 6)) & 7); }
+// exp(-2 pi i k / n_fft), evaluated in fp64 and rounded once
+__device__ inline cf twiddle(int k, int n_fft) {
+  double s, c;
+  sincospi(-2.0 * (double)k / (double)n_fft, &s, &c);
+  return {(float)c, (float)s};
+}
 
 // natural-order DFTs of 4 and 8 points in registers
 __device__ inline void dft4(cf& v0, cf& v1, cf& v2, cf& v3) {

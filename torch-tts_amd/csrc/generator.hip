@@ -26,9 +26,6 @@
 using namespace ttsdec;
 
 namespace {
-constexpr size_t kAlign = 64;  // floats
-inline size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 constexpr float kLrelu = 0.1f;       // modules.LRELU_SLOPE
 constexpr float kLreluLast = 0.01f;  // F.leaky_relu's default, models.py:963
 
@@ -80,30 +77,29 @@ bool dims_ok(const ttsgen_dims& d) {
 GenBlob make_layout(const ttsgen_dims& d) {
   GenBlob L;
   memset(&L, 0, sizeof(L));
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off = up(off + n, kAlign); return o; };
+  Carver cv{nullptr};
   const size_t C0 = d.upsample_initial_channel;
-  L.pre_w = take(C0 * 7 * d.initial_channel);
-  L.pre_b = take(C0);
+  L.pre_w = cv.take_off(C0 * 7 * d.initial_channel);
+  L.pre_b = cv.take_off(C0);
   for (int i = 0; i < d.n_up; ++i) {
     const size_t Ci = i == 0 ? C0 : chan(d, i - 1), Co = chan(d, i), u = d.up_rates[i];
-    L.up_w[i] = take(u * Co * 3 * Ci);
-    L.up_b[i] = take(u * Co);
+    L.up_w[i] = cv.take_off(u * Co * 3 * Ci);
+    L.up_b[i] = cv.take_off(u * Co);
   }
   for (int i = 0; i < d.n_up; ++i) {
     const size_t C = chan(d, i);
     for (int j = 0; j < d.n_res; ++j)
       for (int c = 0; c < 6; ++c) {
-        L.rw[i][j][c] = take(C * d.res_kernels[j] * C);
-        L.rb[i][j][c] = take(C);
+        L.rw[i][j][c] = cv.take_off(C * d.res_kernels[j] * C);
+        L.rb[i][j][c] = cv.take_off(C);
       }
   }
-  L.post_w = take(7 * (size_t)chan(d, d.n_up - 1));
+  L.post_w = cv.take_off(7 * (size_t)chan(d, d.n_up - 1));
   if (d.gin_channels > 0) {
-    L.cond_w = take(C0 * d.gin_channels);
-    L.cond_b = take(C0);
+    L.cond_w = cv.take_off(C0 * d.gin_channels);
+    L.cond_b = cv.take_off(C0);
   }
-  L.total = off;
+  L.total = cv.off;
   return L;
 }
 
@@ -137,8 +133,16 @@ int group_size(const ttsgen_dims& d, int B, int T) {
   return G;
 }
 
-size_t ws_floats(const ttsgen_dims& d, int G, int T) {
-  return 6 * up((size_t)G * utt_floats(d, T), kAlign) + up((size_t)G * d.upsample_initial_channel, kAlign);
+// The workspace of one group of G utterances (carved as layout.h's Carver comment says).  Y: a stage's activated input (conv_pre's
+// output, then each stage's result; kept first: ttsgen_forward_stages reads it); X / LX: the upsampled x and lrelu(x); H: c1's
+// output; R / LR: the branch's running x' and lrelu(x'); condv: [G, C0] cond(g)
+struct GenWs { float *Y, *X, *LX, *H, *R, *LR, *condv; };
+GenWs carve_gen(Carver& cv, const ttsgen_dims& d, size_t G, int T) {
+  const size_t F = G * utt_floats(d, T);
+  GenWs w;
+  w.Y = cv.take(F); w.X = cv.take(F); w.LX = cv.take(F); w.H = cv.take(F); w.R = cv.take(F); w.LR = cv.take(F);
+  w.condv = cv.take(G * d.upsample_initial_channel);
+  return w;
 }
 
 // ===========================================================================
@@ -159,16 +163,6 @@ __global__ void pack_up_kernel(const float* w, float* out, int Cin, int Cout, in
 __global__ void rep_bias_kernel(const float* b, float* out, int Cout, int u) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < u * Cout) out[i] = b[i % Cout];
-}
-
-// cond(g) (models.py:944-945, 1x1 conv on [B, gin, 1]): out[b, n] = bias[n] + sum_k W[n, k] g[b, k], k in order
-__global__ void cond_kernel(const float* g, const float* W, const float* bias, float* out, int B, int N, int K) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * N) return;
-  const int b = i / N, n = i % N;
-  float acc = 0.f;
-  for (int k = 0; k < K; ++k) acc = fmaf(W[(size_t)n * K + k], g[(size_t)b * K + k], acc);
-  out[i] = __fadd_rn(acc, bias[n]);
 }
 
 // conv_post (Conv1d(C, 1, 7, padding 3, bias=False)) + tanh, models.py:964-965: one output sample per lane; x [M = G*T, C]
@@ -215,13 +209,11 @@ void run_group(const ttsgen_handle* h, const float* z, const float* g, int G, in
   const ttsgen_dims& d = h->d;
   const GenBlob& L = h->bl;
   const float* b = h->blob;
-  const size_t F = up((size_t)G * utt_floats(d, T), kAlign);
-  // Y: a stage's activated input (conv_pre's output, then each stage's result; kept first: ttsgen_forward_stages reads it);
-  // X / LX: the upsampled x and lrelu(x); H: c1's output; R / LR: the branch's running x' and lrelu(x'); S: the stage sum
-  float *Y = ws, *X = ws + F, *LX = ws + 2 * F, *H = ws + 3 * F, *R = ws + 4 * F, *LR = ws + 5 * F;
-  float* condv = ws + 6 * F;  // [G, C0] cond(g)
+  Carver cv{ws};  // (the layout of THIS group: the last one may hold fewer utterances than the reported size is for)
+  const GenWs w = carve_gen(cv, d, G, T);
+  float *Y = w.Y, *X = w.X, *LX = w.LX, *H = w.H, *R = w.R, *LR = w.LR, *condv = w.condv;
   const int C0 = d.upsample_initial_channel;
-  if (g != nullptr) hipLaunchKernelGGL(cond_kernel, grid1((size_t)G * C0), dim3(256), 0, st, g, b + L.cond_w, b + L.cond_b, condv, G, C0, d.gin_channels);
+  if (g != nullptr) launch_cond(g, b + L.cond_w, b + L.cond_b, condv, G, C0, d.gin_channels, st);
   // models.py:948-950: x = conv_pre(x) (+ cond(g)); the first stage reads lrelu(x, 0.1) (:953)
   {
     GemmArgs a = conv_args(z, G * T, T, d.initial_channel, 7, 1, b + L.pre_w, b + L.pre_b, C0);
@@ -340,7 +332,9 @@ size_t ttsgen_workspace_bytes(const ttsgen_handle* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
   const int G = group_size(h->d, B, T);
   if (G < 1) return 0;
-  return ws_floats(h->d, G, T) * sizeof(float);
+  Carver cv{nullptr};
+  carve_gen(cv, h->d, G, T);
+  return cv.bytes();
 }
 
 static int gen_call(ttsgen_handle* h, const float* z, const float* g, int B, int T, int n_stages, float* out, void* workspace,

@@ -346,28 +346,23 @@ __global__ __launch_bounds__(kThreads) void peak_kernel(float* __restrict__ wave
   for (int j = tid; j < L; j += kThreads) w[j] = w[j] / m;
 }
 
-// exp(-2 pi i k / n_fft), k < n_fft, evaluated in fp64 and rounded once.  grid n_fft / 256
+// the twiddles (fft_lds.h) for k < n_fft.  grid n_fft / 256
 __global__ __launch_bounds__(kThreads) void twiddle_kernel(cf* __restrict__ tw, int n_fft) {
   const int k = blockIdx.x * kThreads + threadIdx.x;
-  double s, c;
-  sincospi(-2.0 * (double)k / (double)n_fft, &s, &c);
-  tw[k] = {(float)c, (float)s};
+  tw[k] = twiddle(k, n_fft);
 }
 
-int lg2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-bool fft_ok(int n_fft) { return n_fft == 256 || n_fft == 512 || n_fft == 1024 || n_fft == 2048; }
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 struct WsLayout { size_t tw, mag, ra, rb, fr, total; };
 WsLayout ws_layout(int B, int T, int n_fft) {
   const size_t bt = (size_t)B * T, bins = n_fft / 2 + 1;
   WsLayout l;
   l.tw = 0;
-  l.mag = l.tw + up256((size_t)n_fft * sizeof(cf));
-  l.ra = l.mag + up256(bt * bins * sizeof(float));
-  l.rb = l.ra + up256(bt * bins * sizeof(cf));
-  l.fr = l.rb + up256(bt * bins * sizeof(cf));
-  l.total = l.fr + up256(bt * n_fft * sizeof(float));
+  l.mag = l.tw + up((size_t)n_fft * sizeof(cf), 256);
+  l.ra = l.mag + up(bt * bins * sizeof(float), 256);
+  l.rb = l.ra + up(bt * bins * sizeof(cf), 256);
+  l.fr = l.rb + up(bt * bins * sizeof(cf), 256);
+  l.total = l.fr + up(bt * n_fft * sizeof(float), 256);
   return l;
 }
 

@@ -3,6 +3,7 @@
 #include <string>
 
 #include "common.h"
+#include "layout.h"
 
 namespace ttsdec {
 
@@ -292,6 +293,8 @@ void launch_advance(Ctrl* ctrl, int n_slots, hipStream_t st);
 // ---- weight packing ----
 void launch_add_vec(const float* a, const float* b, float* out, int n, hipStream_t st);
 void launch_copy(const float* src, float* dst, size_t n, hipStream_t st);
+// the speaker conditioning cond(g) of the VITS2 generator and duration predictors: out [B, N] = g [B, K] . W [N, K]^T + bias
+void launch_cond(const float* g, const float* W, const float* bias, float* out, int B, int N, int K, hipStream_t st);
 void launch_split(const float* src, f16* hi, f16* lo, size_t n, hipStream_t st);
 // src [M, K] row-major -> split-fp16 planes in the chunked layout [K / 32][mpad][32] (common.h Seg3)
 void launch_split_frame_order(const float* src, f16* hi, f16* lo, int N, int K, int layer, hipStream_t st);  // PreNet planes, frame kernel's lane order

@@ -175,9 +175,7 @@ __global__ __launch_bounds__(kThreads) void spec_prep_kernel(cf* __restrict__ tw
   const int nb = n_fft / kThreads;
   if ((int)blockIdx.x < nb) {
     const int k = blockIdx.x * kThreads + threadIdx.x;
-    double s, c;
-    sincospi(-2.0 * (double)k / (double)n_fft, &s, &c);
-    tw[k] = {(float)c, (float)s};
+    tw[k] = twiddle(k, n_fft);
     return;
   }
   __shared__ int lo, hi;
@@ -192,10 +190,8 @@ __global__ __launch_bounds__(kThreads) void spec_prep_kernel(cf* __restrict__ tw
   if (threadIdx.x == 0) band[m] = hi > lo ? make_int2(lo, hi) : make_int2(0, 0);
 }
 
-int lg2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-bool fft_ok(int n_fft) { return n_fft == 256 || n_fft == 512 || n_fft == 1024 || n_fft == 2048; }
-size_t tw_bytes(int n_fft) { return ((size_t)n_fft * sizeof(cf) + 255) / 256 * 256; }
-size_t ws_bytes_of(int n_fft, int n_mels) { return tw_bytes(n_fft) + ((size_t)n_mels * sizeof(int2) + 255) / 256 * 256; }
+size_t tw_bytes(int n_fft) { return up((size_t)n_fft * sizeof(cf), 256); }
+size_t ws_bytes_of(int n_fft, int n_mels) { return tw_bytes(n_fft) + up((size_t)n_mels * sizeof(int2), 256); }
 
 int check_wave(const ttsvits_handle* h, int B, int N, int n_fft, int hop, int win, int T) {
   if (!h || B <= 0 || N <= 0 || hop <= 0 || win <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;

@@ -22,9 +22,7 @@
 using namespace ttsdec;
 
 namespace {
-constexpr size_t kAlign = 64;  // floats
 constexpr int kMaxLayers = 12, kMaxFlows = 8, kMaxWn = 8;
-inline size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // one attentions.Encoder stack (attentions.py:14-93)
 struct StackBlob {
@@ -65,38 +63,37 @@ StackDims tf_dims(const ttsvits_dims& d) {
 VitsBlob make_layout(const ttsvits_dims& d) {
   VitsBlob L;
   memset(&L, 0, sizeof(L));
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off = up(off + n, kAlign); return o; };
+  Carver cv{nullptr};
   // a GEMM weight of n elements occupies 2n floats: fp32 | fp16 hi plane | fp16 lo plane (w_hi / w_lo below)
-  auto take_w = [&](size_t n) { return take(2 * n); };
+  auto take_w = [&](size_t n) { return cv.take_off(2 * n); };
   auto stack = [&](StackBlob& s, const StackDims& sd) {
     const size_t C = sd.C, F = sd.F, k = sd.kernel, dk = sd.C / sd.heads;
     for (int i = 0; i < sd.layers; ++i) {
-      s.wqkv[i] = take_w(3 * C * C); s.bqkv[i] = take(3 * C); s.wo[i] = take_w(C * C); s.bo[i] = take(C);
-      if (sd.window >= 0) { s.ek[i] = take((2 * sd.window + 1) * dk); s.ev[i] = take((2 * sd.window + 1) * dk); }
-      s.g1[i] = take(C); s.b1[i] = take(C);
-      s.w1[i] = take_w(F * k * C); s.c1[i] = take(F); s.w2[i] = take_w(C * k * F); s.c2[i] = take(C);
-      s.g2[i] = take(C); s.b2[i] = take(C);
+      s.wqkv[i] = take_w(3 * C * C); s.bqkv[i] = cv.take_off(3 * C); s.wo[i] = take_w(C * C); s.bo[i] = cv.take_off(C);
+      if (sd.window >= 0) { s.ek[i] = cv.take_off((2 * sd.window + 1) * dk); s.ev[i] = cv.take_off((2 * sd.window + 1) * dk); }
+      s.g1[i] = cv.take_off(C); s.b1[i] = cv.take_off(C);
+      s.w1[i] = take_w(F * k * C); s.c1[i] = cv.take_off(F); s.w2[i] = take_w(C * k * F); s.c2[i] = cv.take_off(C);
+      s.g2[i] = cv.take_off(C); s.b2[i] = cv.take_off(C);
     }
   };
   const size_t H = d.hidden_channels, I = d.inter_channels, half = I / 2, Fh = d.flow_hidden;
-  L.emb = take((size_t)d.n_vocab * H);
-  if (d.gin_channels > 0) { L.spk_w = take_w(H * d.gin_channels); L.spk_b = take(H); }
+  L.emb = cv.take_off((size_t)d.n_vocab * H);
+  if (d.gin_channels > 0) { L.spk_w = take_w(H * d.gin_channels); L.spk_b = cv.take_off(H); }
   stack(L.enc, enc_dims(d));
-  L.proj_w = take_w(2 * I * H); L.proj_b = take(2 * I);
+  L.proj_w = take_w(2 * I * H); L.proj_b = cv.take_off(2 * I);
   for (int f = 0; f < d.n_flows; ++f) {
     FlowBlob& fb = L.flow[f];
     stack(fb.tf, tf_dims(d));
-    fb.pre_w = take_w(Fh * half); fb.pre_b = take(Fh);
-    if (d.gin_channels > 0) { fb.cond_w = take_w(2 * Fh * d.flow_wn_layers * d.gin_channels); fb.cond_b = take(2 * Fh * d.flow_wn_layers); }
+    fb.pre_w = take_w(Fh * half); fb.pre_b = cv.take_off(Fh);
+    if (d.gin_channels > 0) { fb.cond_w = take_w(2 * Fh * d.flow_wn_layers * d.gin_channels); fb.cond_b = cv.take_off(2 * Fh * d.flow_wn_layers); }
     for (int j = 0; j < d.flow_wn_layers; ++j) {
       const size_t cr = j < d.flow_wn_layers - 1 ? 2 * Fh : Fh;
-      fb.in_w[j] = take_w(2 * Fh * d.flow_kernel * Fh); fb.in_b[j] = take(2 * Fh);
-      fb.rs_w[j] = take_w(cr * Fh); fb.rs_b[j] = take(cr);
+      fb.in_w[j] = take_w(2 * Fh * d.flow_kernel * Fh); fb.in_b[j] = cv.take_off(2 * Fh);
+      fb.rs_w[j] = take_w(cr * Fh); fb.rs_b[j] = cv.take_off(cr);
     }
-    fb.post_w = take_w(half * Fh); fb.post_b = take(half);
+    fb.post_w = take_w(half * Fh); fb.post_b = cv.take_off(half);
   }
-  L.total = off;
+  L.total = cv.off;
   return L;
 }
 
@@ -1133,8 +1130,6 @@ __global__ __launch_bounds__(256) void post_sample_kernel(const float* stats, co
 }
 // pack: rows of three [C, C] matrices stacked -> [3C, C]; conv weights via launch_conv_transpose
 
-inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 // One elementwise step over n elements: the W = 4 kernel on n / 4 threads or the W = 1 kernel on n.  Four-wide needs the channel
 // count C a multiple of `mult` (4; 8 where the kernel also works on half rows), fewer than 2^32 elements and the pointers that may
 // be a caller's 16-byte aligned (the workspace's own always are).  The arguments go in as the W = 1 kernel takes them; a Chan is a
@@ -1151,19 +1146,6 @@ void launch_ew(bool wide, K4 k4, K1 k1, size_t n, hipStream_t st, A... a) {
   else hipLaunchKernelGGL(k1, grid1(n), dim3(256), 0, st, ew_arg<1>(a)...);
 }
 
-// A workspace is walked once per call by a carve routine: with the caller's pointer it hands out the buffers, with none it only
-// counts - so the size a *_workspace_bytes function reports is the layout the call uses.  Buffers are kAlign floats apart.
-struct Carver {
-  float* base;  // nullptr: count only
-  size_t off = 0, slack = 0;  // floats handed out; floats reported on top of them (carve_stack)
-  float* take(size_t n) {
-    float* r = base ? base + off : nullptr;
-    off += up(n, kAlign);
-    return r;
-  }
-  f16* take_h(size_t n) { return reinterpret_cast<f16*>(take(n)); }  // n floats = the hi + lo planes of n elements
-  size_t bytes() const { return (off + slack) * sizeof(float); }
-};
 // row counts and offsets of the GEMM core are 32-bit: B * T frames of up to 4096 channels have to fit
 inline bool frames_fit(int B, int T) { return (size_t)B * T <= (size_t)INT32_MAX / 4096; }
 
@@ -1673,19 +1655,18 @@ namespace {
 PostBlob make_post_layout(const ttspost_dims& d, int spec_pad) {
   PostBlob L;
   memset(&L, 0, sizeof(L));
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off = up(off + n, kAlign); return o; };
-  auto take_w = [&](size_t n) { return take(2 * n); };
+  Carver cv{nullptr};
+  auto take_w = [&](size_t n) { return cv.take_off(2 * n); };
   const size_t H = d.hidden_channels, I = d.inter_channels, nl = d.n_layers;
-  L.pre_w = take_w(H * spec_pad); L.pre_b = take(H);  // [H, spec_pad]: columns spec .. spec_pad-1 stay zero
-  if (d.gin_channels > 0) { L.cond_w = take_w(2 * H * nl * d.gin_channels); L.cond_b = take(2 * H * nl); }
+  L.pre_w = take_w(H * spec_pad); L.pre_b = cv.take_off(H);  // [H, spec_pad]: columns spec .. spec_pad-1 stay zero
+  if (d.gin_channels > 0) { L.cond_w = take_w(2 * H * nl * d.gin_channels); L.cond_b = cv.take_off(2 * H * nl); }
   for (int j = 0; j < d.n_layers; ++j) {
     const size_t cr = j < d.n_layers - 1 ? 2 * H : H;
-    L.in_w[j] = take_w(2 * H * d.kernel_size * H); L.in_b[j] = take(2 * H);
-    L.rs_w[j] = take_w(cr * H); L.rs_b[j] = take(cr);
+    L.in_w[j] = take_w(2 * H * d.kernel_size * H); L.in_b[j] = cv.take_off(2 * H);
+    L.rs_w[j] = take_w(cr * H); L.rs_b[j] = cv.take_off(cr);
   }
-  L.proj_w = take_w(2 * I * H); L.proj_b = take(2 * I);
-  L.total = off;
+  L.proj_w = take_w(2 * I * H); L.proj_b = cv.take_off(2 * I);
+  L.total = cv.off;
   return L;
 }
 struct PostWs {
