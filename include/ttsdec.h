@@ -45,7 +45,8 @@ extern "C" {
 /* (And ttsvits_flow_forward and the ttspost_ family - the posterior encoder - for voice conversion; then ttsvits_neg_cent,
  * ttsvits_maximum_path and ttsvits_align for monotonic alignment search; then ttsvits_spectrogram, ttsvits_spec_to_mel and
  * ttsvits_mel_spectrogram, the spectrogram front-end; then ttsdec_griffinlim_workspace_bytes, ttsdec_mel_to_magnitude and
- * ttsdec_griffinlim, mel -> waveform for the Tacotron path.) */
+ * ttsdec_griffinlim, mel -> waveform for the Tacotron path; then ttsdec_mel_analysis_workspace_bytes and ttsdec_mel_analysis,
+ * waveform -> dB spectrogram and mel for it.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -570,6 +571,35 @@ int ttsdec_mel_to_magnitude(ttsdec_handle* h, const float* y, const float* P, co
 int ttsdec_griffinlim(ttsdec_handle* h, const float* mag, const int32_t* frames, int B, int T, const float* window, int n_fft, int hop_length,
                       const float* angles, const float* tprev, int n_iter, float momentum, int normalize, float* wave, float* rebuilt_out,
                       float* angles_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Waveform -> dB spectrogram and dB mel for the Tacotron path: the reference's AudioFrontend.encode (tacotron/data/audio.py:55-67)
+ * after its resampling - wave / max |wave|, torchaudio's Spectrogram(power=2, normalized=True, center=True), MelScale and
+ * amplitude_to_DB(10, 1e-12, 0) - on a padded batch.  Weightless like the calls above; enqueues only.  Exact fp32.
+ *   wave     [B, n_samples] fp32, one utterance per row; lengths [B] int32 samples of each (device), or NULL: every row is n_samples
+ *   window   [n_fft] fp32 (the reference's torch.hann_window(n_fft)); fb [bins, n_mels] fp32 row-major, the mel filterbank
+ *   n_fft    256, 512, 1024 or 2048, win_length == n_fft; 1 <= hop_length <= n_fft / 2 (the range of ttsdec_griffinlim, its
+ *            inverse); n_mels <= 256; B <= 65535; 1 <= T <= 2^22; n_samples <= 2^30 (else TTSDEC_ERR_DIMS); bins = n_fft / 2 + 1
+ *   An utterance of len samples is divided by its own max |x|, reflect-padded by n_fft / 2 at its own two ends and has
+ *   1 + len / hop_length frames (C division).  Frame t:
+ *     D[k] = |X[k]|^2 / sum w^2                 X the windowed n_fft-point DFT of the padded samples from t * hop_length (an FFT in
+ *                                               fp32, twiddles and 1 / sum w^2 evaluated in fp64 and rounded once)
+ *     M[m] = sum_k fb[k, m] D[k]                fp32 sums over each filter's run of non-zero entries, in bin order
+ *     spec_db = 10 log10(max(D, 1e-12)),  mel_db = 10 log10(max(M, 1e-12))
+ *   D itself never reaches memory.
+ *   T        frames of the output tensors; frames at or past an utterance's count are written as exact zeros
+ *   spec_db  NULL (not computed), or [B, T, bins];  mel_db [B, T, n_mels];  frames_out NULL, or [B] int32: every utterance's frames
+ *   status   NULL, or [1] int32 (device): 0, or flags of refused utterances, whose frames are all zeros and whose count is 0:
+ *            1 = len <= n_fft / 2 (the reflection is undefined), 2 = max |x| is 0 (the reference divides by it); and
+ *            4 = len > n_samples or more frames than T (clamped)
+ *   workspace ttsdec_mel_analysis_workspace_bytes(h, B, n_fft, n_mels) bytes, 256-byte aligned; every call rebuilds its tables there
+ *            (twiddles, the bands of the filterbank, 1 / sum w^2) and keeps the peaks there.
+ * Sizes are checked before any pointer: TTSDEC_ERR_INVALID_ARG for B, n_samples or n_mels <= 0, TTSDEC_ERR_DIMS as above, then NULL
+ * pointers, then TTSDEC_ERR_WORKSPACE.  Deterministic (the peak is an integer maximum); every utterance gets bit for bit what it
+ * gets alone. */
+size_t ttsdec_mel_analysis_workspace_bytes(const ttsdec_handle* h, int B, int n_fft, int n_mels); /* 0: a size outside the ranges above */
+int ttsdec_mel_analysis(ttsdec_handle* h, const float* wave, const int32_t* lengths, int B, int n_samples, const float* window, const float* fb,
+                        int n_mels, int n_fft, int hop_length, int T, float* spec_db, float* mel_db, int32_t* frames_out, int32_t* status,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * VITS2 HiFi-GAN generator (latent z -> waveform): Generator.forward, vits2/models.py:900-974, with ResBlock1.forward

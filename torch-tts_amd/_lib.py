@@ -150,6 +150,12 @@ FAMILIES = (
             vp, vp, i32, f32, i32,               # angles, tprev, n_iter, momentum, normalize
             vp, vp, vp, vp, vp, sz, vp,          # wave, rebuilt_out, angles_out, status, workspace, workspace_bytes, stream
         ]),
+        "mel_analysis_workspace_bytes": (sz, [vp, i32, i32, i32]),  # (h, B, n_fft, n_mels)
+        "mel_analysis": (i32, [
+            vp, vp, vp, i32, i32, vp, vp,        # h, wave, lengths, B, n_samples, window, fb
+            i32, i32, i32, i32,                  # n_mels, n_fft, hop_length, T
+            vp, vp, vp, vp, vp, sz, vp,          # spec_db, mel_db, frames_out, status, workspace, workspace_bytes, stream
+        ]),
     }),
     Family("ttsenc", EncDims, True, {
         "workspace_bytes": _ws_bytes,

@@ -12,7 +12,11 @@ reference's Griffin-Lim starts from a random phase (``rand_init=True``); tests c
 The same step as HIP kernels, batched and length-aware (include/ttsdec.h ttsdec_mel_to_magnitude / ttsdec_griffinlim,
 csrc/griffinlim.hip): ``AudioFrontend.mel_to_magnitude``, ``griffinlim_native`` and ``synth_audio_native``.  ROCm-only,
 exact fp32, no fallback.  With the initial phase an explicit input the algorithm is deterministic, and what is pinned
-(tests/test_griffinlim_hip.py) is parity with the published algorithm as the functions above state it, run in fp64."""
+(tests/test_griffinlim_hip.py) is parity with the published algorithm as the functions above state it, run in fp64.
+
+The analysis half, ``AudioFrontend.encode`` (data/audio.py:55-67: peak normalisation, ``Spectrogram(power=2, normalized=True)``,
+``MelScale``, ``amplitude_to_DB``), is restated on torch ops in the same way (no resampling), and runs as HIP kernels on a padded
+batch through ``AudioFrontend.encode_native`` (ttsdec_mel_analysis, csrc/analysis.hip; tests/test_analysis_hip.py)."""
 from __future__ import annotations
 
 import math
@@ -113,7 +117,7 @@ def griffinlim(specgram: torch.Tensor, n_fft: int, hop_length: int, win_length: 
 
 
 class AudioFrontend:
-    """Inference half of data/audio.py's AudioFrontend: ``mel_inv`` (mel dB -> linear dB) and ``decode``
+    """data/audio.py's AudioFrontend: ``encode`` (waveform -> linear dB and mel dB), ``mel_inv`` (mel dB -> linear dB) and ``decode``
     (linear dB -> waveform by Griffin-Lim)."""
 
     def __init__(self, config: AudioFrontendConfig, device: Optional[torch.device] = None):
@@ -163,6 +167,64 @@ class AudioFrontend:
         frames, on_device = _frames_arg(lengths, B, T, y.device, who)
         mag = _engine(y.device).mel_to_magnitude(y3.detach().contiguous(), self.inverse_basis(y.device), frames, self.n_fft, check=on_device)
         return mag[0] if y.dim() == 2 else mag
+
+    def spectrogram(self, wave: torch.Tensor) -> torch.Tensor:
+        """Spectrogram(power=2, normalized=True, center=True) (data/audio.py:50-52): [..., time] -> [..., n_freqs, 1 + time // hop],
+        the "window" normalisation (by sqrt(sum w^2)) applied before the power."""
+        window = torch.hann_window(self.n_fft, device=wave.device, dtype=wave.dtype)
+        X = torch.stft(wave, n_fft=self.n_fft, hop_length=self.config.hop_length, win_length=self.n_fft, window=window, center=True,
+                       pad_mode="reflect", normalized=False, onesided=True, return_complex=True)
+        X = X / window.pow(2.0).sum().sqrt()
+        return X.abs().pow(2.0)
+
+    def encode(self, wave: torch.Tensor, sr: int):  # data/audio.py:55-67
+        """wave [time] (or [..., time], normalised by the one peak of the whole tensor, as the reference has it) -> (D_db [T, n_freqs],
+        M_db [T, n_mels]) in wave's dtype on its device, T = 1 + time // hop_length."""
+        if sr != self.config.sample_rate:
+            raise NotImplementedError(f"AudioFrontend.encode: resampling ({sr} -> {self.config.sample_rate} Hz) is not built: resample the "
+                                      "waveform first")
+        wave = wave / wave.abs().max()
+        D = self.spectrogram(wave)
+        M = torch.matmul(D.mT, self.fb.to(device=D.device, dtype=D.dtype)).mT  # stft_to_mels, in wave's dtype
+        D_db = amplitude_to_db(D, 10, 1e-12, 0)
+        M_db = amplitude_to_db(M, 10, 1e-12, 0)
+        return D_db.mT, M_db.mT
+
+    def encode_native(self, wave: torch.Tensor, lengths=None, *, spectrogram: bool = True):
+        """``encode`` of every utterance of a padded batch in one call (ttsdec_mel_analysis, csrc/analysis.hip): wave [B, N] (or [N])
+        fp32 on a ROCm device at the configured sample rate -> (D_db [B, T, n_freqs], M_db [B, T, n_mels], frames [B] int32),
+        T = 1 + N // hop_length; for 1-D input the reference's 2-D shapes and a scalar count.  ``lengths`` ([B] samples, host or
+        device): every utterance is normalised by its own peak and reflected at its own end, has 1 + length // hop_length frames and
+        exact zeros past them.  ``spectrogram=False`` leaves D_db out (None): it is 87 % of the bytes the call writes."""
+        who = "AudioFrontend.encode_native"
+        _check_native(wave, self.n_fft, self.config.hop_length, self.n_fft, who)
+        w2 = wave.unsqueeze(0) if wave.dim() == 1 else wave
+        if w2.dim() != 2:
+            raise ValueError(f"{who}: wave must be [B, N] or [N], got {tuple(wave.shape)}")
+        dev = wave.device
+        B, N = w2.shape
+        half = self.n_fft // 2
+        if N <= half:
+            raise ValueError(f"{who}: {N} samples: an utterance needs more than n_fft / 2 = {half} to be reflect-padded")
+        if lengths is None:
+            lens = None
+        elif isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+            if tuple(lengths.shape) != (B,):
+                raise ValueError(f"{who}: lengths must be [B] = [{B}], got {tuple(lengths.shape)}")
+            lens = lengths.to(device=dev, dtype=torch.int32).contiguous()
+        else:
+            host = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+            if len(host) != B or any(v <= half or v > N for v in host):
+                raise ValueError(f"{who}: lengths must be [B] = [{B}] sample counts in [{half + 1}, {N}], got {host}")
+            lens = torch.tensor(host, dtype=torch.int32).to(dev)
+        key = (self.n_fft, str(dev))
+        if key not in _windows:
+            _windows[key] = torch.hann_window(self.n_fft).to(dtype=torch.float32, device=dev)
+        fb = self.fb.detach().to(device=dev, dtype=torch.float32).contiguous()
+        D_db, M_db, frames = _engine(dev).mel_analysis(w2.detach().contiguous(), lens, _windows[key], fb, self.config.hop_length, spectrogram)
+        if wave.dim() == 1:
+            return (D_db[0] if spectrogram else None), M_db[0], frames[0]
+        return D_db, M_db, frames
 
     def mel_inv(self, M_db: torch.Tensor) -> torch.Tensor:  # data/audio.py:73-76
         M = db_to_amplitude(M_db.mT, 1, 1)

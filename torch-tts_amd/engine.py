@@ -295,6 +295,40 @@ class Engine(Handle):
             _raise_frame_flags(int(status.item()), T)
         return (wave, state[0], state[1]) if return_state else wave
 
+    # ---- waveform -> dB spectrogram and mel (weightless; audio.py holds the entry point) ----
+    def mel_analysis(self, wave: Tensor, lengths: Optional[Tensor], window: Tensor, fb: Tensor, hop_length: int, spectrogram: bool):
+        """wave [B, N] contiguous fp32, lengths [B] int32 (device) or None, window [n_fft], fb [n_fft / 2 + 1, n_mels] contiguous fp32
+        -> (spec_db [B, T, bins] or None, mel_db [B, T, n_mels], frames [B] int32), T = 1 + N // hop_length (ttsdec_mel_analysis).
+        The status word is always read back (one host sync): a silent utterance is only known on the device."""
+        B, N = wave.shape
+        n_fft, (bins, n_mels) = window.numel(), fb.shape
+        T = 1 + N // hop_length
+        nbytes = int(self._lib.ttsdec_mel_analysis_workspace_bytes(self._h, B, n_fft, n_mels))
+        if not nbytes:
+            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsdec_mel_analysis", f"B = {B}, n_fft = {n_fft}, n_mels = {n_mels}: built for n_fft 256 / 512 / "
+                                    "1024 / 2048, n_mels <= 256, B <= 65535")
+        ws = self.workspace("mel_analysis", nbytes)
+        spec = torch.empty(B, T, bins, device=self.device) if spectrogram else None
+        mel = torch.empty(B, T, n_mels, device=self.device)
+        frames = torch.empty(B, dtype=torch.int32, device=self.device)
+        status = torch.empty(1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsdec_mel_analysis(self._h, wave.data_ptr(), _ptr(lengths), B, N, window.data_ptr(), fb.data_ptr(), n_mels, n_fft,
+                                               hop_length, T, _ptr(spec), mel.data_ptr(), frames.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), _stream(self.device))
+        if rc == _lib.ERR_DIMS:
+            raise _lib.DimsNotBuilt(rc, "ttsdec_mel_analysis", f"n_fft = {n_fft}, hop_length = {hop_length}, {N} samples: needs 1 <= hop_length "
+                                    "<= n_fft / 2, at most 2^30 samples and 2^22 frames")
+        self._err(rc, "ttsdec_mel_analysis")
+        flags = int(status.item())
+        if flags & 4:
+            raise ValueError(f"an utterance's length exceeds the row's {N} samples")
+        if flags & 1:
+            raise ValueError(f"an utterance has no more than n_fft / 2 = {n_fft // 2} samples: it cannot be reflect-padded")
+        if flags & 2:
+            raise ValueError("an utterance is all zeros: it has no peak to normalise by")
+        return spec, mel, frames
+
     # ---- workspaces ----
     def step_workspace(self, B: int, L: int) -> Tensor:
         key = (B, L)
