@@ -16,6 +16,9 @@ pytestmark = pytest.mark.gpu
 A = T.audio
 DEV = torch.device("cuda:0")
 CONFIGS = ((1024, 256, 120), (1024, 256, 600), (512, 128, 90), (2048, 512, 70))  # n_fft, hop, frames
+# ... and an odd hop - the forward kernel's scalar first pass; the pairs need an even frame stride - whose 11 frames leave the
+# 16-frame run partly filled (the one-pass tests only: the 32-iteration ones would add nothing on that branch)
+ONE_PASS_CONFIGS = CONFIGS + ((256, 63, 11),)
 
 
 def rel(w, w64):
@@ -59,7 +62,7 @@ def test_mel_to_magnitude_against_the_fp64_chain():
     assert torch.equal(feg.mel_to_magnitude(y.to(DEV), torch.tensor(lens, device=DEV)), mag)
 
 
-@pytest.mark.parametrize("n_fft,hop,frames", CONFIGS)
+@pytest.mark.parametrize("n_fft,hop,frames", ONE_PASS_CONFIGS)
 def test_inverse_stft_alone(n_fft, hop, frames):
     mag = spec_input(n_fft, hop, frames)
     ang = random_start(mag.shape, 5)
@@ -72,7 +75,7 @@ def test_inverse_stft_alone(n_fft, hop, frames):
     assert e <= 4 * e32
 
 
-@pytest.mark.parametrize("n_fft,hop,frames", CONFIGS)
+@pytest.mark.parametrize("n_fft,hop,frames", ONE_PASS_CONFIGS)
 def test_one_iteration_from_the_fp64_runs_own_state(n_fft, hop, frames):
     mags = {"spectrogram": spec_input(n_fft, hop, frames)}
     if n_fft == 1024:

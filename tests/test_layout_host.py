@@ -84,6 +84,7 @@ def reported_sizes(lib, _lib):
     for n_fft in N_FFT:
         rows[f"griffinlim_ws/{n_fft}"] = [lib.ttsdec_griffinlim_workspace_bytes(hd, B, T, n_fft) for B, T in BT]  # (T < 2: refused)
         rows[f"spec_ws/{n_fft}"] = [lib.ttsvits_spec_workspace_bytes(hv, n_fft, n_mels) for n_mels in (0, 80, 128)]
+        rows[f"mel_analysis_ws/{n_fft}"] = [lib.ttsdec_mel_analysis_workspace_bytes(hd, B, n_fft, n_mels) for B in (1, 2, 3) for n_mels in (80, 128)]
     rows["align_ws"] = [lib.ttsvits_align_workspace_bytes(hv, B, T, Tx) for B, T in BT for Tx in (1, 9, 150)]
     os.environ["TTSGEN_GROUP_FORCE"] = "2"  # (read at every call: groups of two utterances, so B = 3 reports what B = 2 needs)
     try:
@@ -103,7 +104,9 @@ def reported_sizes(lib, _lib):
               lib.ttsdec_griffinlim_workspace_bytes(hd, 2, 1, 512), lib.ttsdec_griffinlim_workspace_bytes(None, 2, 37, 512),
               lib.ttsvits_spec_workspace_bytes(hv, 300, 80), lib.ttsvits_spec_workspace_bytes(hv, 512, -1), lib.ttsvits_spec_workspace_bytes(None, 512, 80),
               lib.ttsvits_align_workspace_bytes(hv, 0, 37, 9), lib.ttsvits_align_workspace_bytes(hv, 2, 37, 0), lib.ttsvits_align_workspace_bytes(hv, 2, 37, 1025),
-              lib.ttsvits_align_workspace_bytes(None, 2, 37, 9)]
+              lib.ttsvits_align_workspace_bytes(None, 2, 37, 9),
+              lib.ttsdec_mel_analysis_workspace_bytes(hd, 2, 300, 80), lib.ttsdec_mel_analysis_workspace_bytes(hd, 2, 512, 257),
+              lib.ttsdec_mel_analysis_workspace_bytes(hd, 0, 512, 80), lib.ttsdec_mel_analysis_workspace_bytes(None, 2, 512, 80)]
     rows["refused"] = [sum(1 for z in zeros if z != 0), len(zeros)]
     for fam, h in handles.values():
         getattr(lib, fam + "_destroy")(h)
@@ -111,7 +114,8 @@ def reported_sizes(lib, _lib):
 
 
 # As the library of commit e178cdf ("VITS2 flow path: one templated kernel per step, one layout per workspace") reported them, before
-# the size functions of these families became their carve routines' totals.  Bytes.
+# the size functions of these families became their carve routines' totals; the mel_analysis_ws rows as the library of commit 3e4a5ff
+# ("Add Tacotron audio analysis on HIP") reported them.  Bytes.
 RECORDED = {
     "dec_small_mel/packed": [1472256],
     "dec_small_mel/decode_ws": [112896, 118784, 129280],
@@ -167,16 +171,20 @@ RECORDED = {
     "post_model_g/ws": [40960, 1193984, 9349888],
     "griffinlim_ws/256": [0, 269312, 2164736],
     "spec_ws/256": [2048, 2816, 3072],
+    "mel_analysis_ws/256": [3328, 3584, 3328, 3584, 3328, 3584],
     "griffinlim_ws/512": [0, 536576, 4317184],
     "spec_ws/512": [4096, 4864, 5120],
+    "mel_analysis_ws/512": [5376, 5632, 5376, 5632, 5376, 5632],
     "griffinlim_ws/1024": [0, 1071104, 8622080],
     "spec_ws/1024": [8192, 8960, 9216],
+    "mel_analysis_ws/1024": [9472, 9728, 9472, 9728, 9472, 9728],
     "griffinlim_ws/2048": [0, 2140160, 17231872],
     "spec_ws/2048": [16384, 17152, 17408],
+    "mel_analysis_ws/2048": [17664, 17920, 17664, 17920, 17664, 17920],
     "align_ws": [256, 256, 256, 4864, 4864, 4864, 38400, 38400, 38400],
     "gen_small_g/ws_group2": [1792, 113920, 614656],
     "gen_model/ws_group2": [198656, 14553088, 78647296],
-    "refused": [0, 173],
+    "refused": [0, 177],
 }
 
 

@@ -154,6 +154,24 @@ def test_analytic_cases():
     assert ok
 
 
+def test_hop_longer_than_the_frame():
+    """hop > n_fft: the frames do not overlap, the run's samples are loaded frame by frame and the negative padding crops both ends."""
+    _, meta = load_golden()
+    n_fft, hop, win = 256, 300, 200
+    bar = 4 * meta["configs"][1]["spec_frame_err"]  # the n_fft = 256 configuration
+    g = torch.Generator().manual_seed(13)
+    y = torch.rand(2, 2500, generator=g) * 1.6 - 0.8
+    lens = [2500, 1700]
+    spec, sl = MP().spectrogram_torch(y.to(dev()), n_fft, SR, hop, win, lengths=lens)
+    ref, counts = spectrogram_batch(y.double(), lens, n_fft, hop, win)
+    assert counts == sl.tolist() == [8, 5] and spec.shape == ref.shape
+    for b in range(2):
+        e = frame_err(spec[b, :, : counts[b]].cpu(), ref[b, :, : counts[b]])
+        print(f"n_fft {n_fft}, hop {hop}, win {win}, utterance {b}: frame err {e:.3e}, bar {bar:.3e}")
+        assert e <= bar
+        assert not spec[b, :, counts[b] :].any()
+
+
 def test_benchmarked_shape():
     _, meta = load_golden()
     B, N, n_fft, hop = 64, 153600, 1024, 256

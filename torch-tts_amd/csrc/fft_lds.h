@@ -1,4 +1,4 @@
-// The in-LDS complex FFT shared by the spectrogram front-end (spec.hip) and Griffin-Lim (griffinlim.hip): a Stockham autosort of
+// The in-LDS complex FFT under every frame run (stft_run.h; spec.hip, griffinlim.hip, analysis.hip): a Stockham autosort of
 // radix-8 / radix-4 passes over the F frames of a workgroup's run (M = 128: 8 4 4, 256: 8 8 4, 512: 8 8 8, 1024: 8 8 4 4),
 // ping-ponging between two LDS images of F * M complex points.  Complex element i of a frame sits at swz(i): a pass's reads (lanes
 // on consecutive i) and the stride-8 writes of the first pass then touch every LDS bank once per lane group; the stride-64 writes
@@ -81,6 +81,28 @@ __device__ inline void fft_pass(const cf* __restrict__ src, cf* __restrict__ dst
     const int o = ((j - jl) << lgR) + jl;
 #pragma unroll
     for (int r = 0; r < R; ++r) dst[(f << lgM) + swz(o + r * Ns)] = v[r];
+  }
+}
+
+// fft_pass<8, true> with the samples and the window read as 8-byte pairs: lanes on consecutive pairs touch every bank once per
+// 32-lane group, where the 4-byte reads at stride 2 above are 2-way.  Needs an even frame stride fs.  The same products, the same DFT.
+__device__ inline void fft_pass8_first_paired(cf* __restrict__ dst, const float* __restrict__ samp, const float* __restrict__ win, int fs, int M,
+                                              int lgM, int F) {
+  const float2* s2 = reinterpret_cast<const float2*>(samp);
+  const float2* w2 = reinterpret_cast<const float2*>(win);
+  const int lgPer = lgM - 3, per = 1 << lgPer, fs2 = fs >> 1;
+  for (int w = threadIdx.x; w < (F << lgPer); w += kFftThreads) {
+    const int f = w >> lgPer, j = w & (per - 1);
+    cf v[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int i = j + (r << lgPer);
+      const float2 s = s2[f * fs2 + i], ww = w2[i];
+      v[r] = {s.x * ww.x, s.y * ww.y};
+    }
+    dft<8>(v);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) dst[(f << lgM) + swz((j << 3) + r)] = v[r];
   }
 }
 

@@ -10,35 +10,33 @@
 //                      3 GFLOP at 64 x 600 frames leave nothing for the matrix pipe to win.
 //   transpose_kernel   [B, bins, T] <-> [B, T, bins] (fp32 or complex): the iteration works frame-major, where a frame's spectrum is
 //                      one contiguous row; the caller's tensors keep torch's [B, bins, T].  Writes zeros at frames >= frames[b].
-//   istft_kernel       one workgroup per run of F frames (F * n_fft = kTile): phase factors (given; or, from the second iteration
-//                      on, (R_k - mom R_k-1) / (|R_k - mom R_k-1| + 1e-16) of the last two rebuilt spectra - `angles` and `tprev` of
-//                      the reference are never stored) -> mag * phase -> inverse real FFT of n_fft points as one complex FFT of
-//                      M = n_fft / 2 points (Z[k] = E[k] + i O[k], E = (X[k] + conj X[M-k]) / 2, O = (X[k] - conj X[M-k]) / 2 *
-//                      conj W^k; ifft = conj fft conj / M; fft_lds.h) -> times the window -> frames [B, T, n_fft].
+//   istft_kernel       one workgroup per run of F frames (F * n_fft = kTile; the RunLds of stft_run.h without samples): phase
+//                      factors (given; or, from the second iteration on, (R_k - mom R_k-1) / (|R_k - mom R_k-1| + 1e-16) of the
+//                      last two rebuilt spectra - `angles` and `tprev` of the reference are never stored) -> mag * phase -> inverse
+//                      real FFT of n_fft points as one complex FFT of M = n_fft / 2 points (Z[k] = E[k] + i O[k], E = (X[k] +
+//                      conj X[M-k]) / 2, O = (X[k] - conj X[M-k]) / 2 * conj W^k; ifft = conj fft conj / M; fft_lds.h) -> times
+//                      the window -> frames [B, T, n_fft].
 //   stft_kernel        the same run of frames forward (torch.stft(center=True, pad_mode="reflect")): its (F - 1) hop + n_fft
 //                      samples are gathered from the inverse frames - each sample the sum, in frame order, of the <= n_fft / hop
 //                      frames that cover it, divided by the same sum of the squared window (torch.istft's overlap-add, with no
-//                      atomics and no waveform in memory) - reflected at the utterance's own two ends, windowed, transformed and
-//                      split to X[k], k <= M -> rebuilt [B, T, bins].
+//                      atomics and no waveform in memory) - reflected at the utterance's own two ends; then stft_run.h's
+//                      forward_run, whose emit stores X[k], k <= M -> rebuilt [B, T, bins].
 //   ola_kernel         that gather once more for the waveform itself, after the last inverse; peak_kernel: w / max |w| per utterance.
-// LDS: the samples and the window are read as 8-byte pairs (lanes on consecutive pairs: every bank once per 32-lane group; the
-// 4-byte reads at stride 2 of spec.hip's first pass are 2-way), spectra are read and written in bin order through swz().
+// The twiddles come from stft_run.h's launch_stft_tables.  LDS: with an even hop the samples and the window are read as 8-byte pairs
+// (fft_lds.h fft_pass8_first_paired), spectra are read and written in bin order through swz().
 // Nothing depends on the batch or on where a frame falls in its run: a ragged batch gives each utterance what it gets alone.
 #include <math.h>
 #include <stdint.h>
 
-#include "fft_lds.h"
 #include "kernels.h"
+#include "stft_run.h"
 
 using namespace ttsdec;
 
 namespace {
 constexpr int kThreads = kFftThreads;
-constexpr int kTile = 4096;       // floats of one LDS image of a run: F frames x n_fft / 2 complex points
-constexpr int kMaxMels = 256;
 constexpr int kMelFrames = 64;    // frames per workgroup of mel_to_mag_kernel (one per lane)
 constexpr int kMelBins = 4;       // bins per thread and step
-constexpr int kMaxFrames = 1 << 22;
 enum { FLAG_SHORT = 1, FLAG_RANGE = 4 };  // status word: fewer than 2 frames (the row is zeros); frames[b] beyond T (clamped)
 enum { PH_ONES = 0, PH_GIVEN = 1, PH_UPDATE = 2 };
 
@@ -180,23 +178,18 @@ __device__ inline float ola_sample(const float* __restrict__ fr, const float* wi
   return acc / env;
 }
 
-// grid (ceil(T / F), B); dynamic LDS 3 n_fft + 2 kTile floats
+// grid (ceil(T / F), B); dynamic LDS run_lds_floats(n_fft, 0)
 __global__ __launch_bounds__(kThreads) void istft_kernel(const GlArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int N = a.n_fft, M = N >> 1, bins = M + 1, F = a.F, T = a.T, lgM = a.lgM;
-  cf* tw = reinterpret_cast<cf*>(lds);            // [N]
-  float* win = lds + 2 * N;                       // [N]
-  cf* bufA = reinterpret_cast<cf*>(lds + 3 * N);  // [F * M]
-  cf* bufB = bufA + kTile / 2;
+  const RunLds l = run_lds(lds, N);
+  cf *tw = l.tw, *bufA = l.bufA, *bufB = l.bufB;
   const int b = blockIdx.y, t0 = blockIdx.x * F, tid = threadIdx.x;
   int flags;
   const int tb = frames_of(a.frames, b, T, &flags);
   if (flags && a.status && blockIdx.x == 0 && tid == 0) atomicOr(a.status, flags);
   if (t0 >= tb) return;  // (workgroup-uniform)
-  for (int i = tid; i < N; i += kThreads) {
-    tw[i] = a.tw[i];
-    win[i] = a.window[i];
-  }
+  load_tables(l, N, a.tw, a.window, N);
   __syncthreads();
   // ---- mag * phase -> conj Z, bins k and M - k by one thread ----
   const int half = M / 2 + 1;
@@ -231,7 +224,7 @@ __global__ __launch_bounds__(kThreads) void istft_kernel(const GlArgs a) {
   const cf* Z = fft_rest(bufB, bufA, tw, M, lgM, F);
   // ---- x[2n] + i x[2n + 1] = conj Z[n] / M, times the window ----
   const float sc = 1.f / (float)M;
-  const float2* win2 = reinterpret_cast<const float2*>(win);
+  const float2* win2 = reinterpret_cast<const float2*>(l.win);
   for (int idx = tid; idx < (F << lgM); idx += kThreads) {
     const int f = idx >> lgM, n = idx & (M - 1), t = t0 + f;
     if (t >= tb) continue;
@@ -241,24 +234,17 @@ __global__ __launch_bounds__(kThreads) void istft_kernel(const GlArgs a) {
   }
 }
 
-// grid (ceil(T / F), B); dynamic LDS 3 n_fft + 2 kTile + scount floats
+// grid (ceil(T / F), B); dynamic LDS run_lds_floats(n_fft, scount)
 __global__ __launch_bounds__(kThreads) void stft_kernel(const GlArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int N = a.n_fft, M = N >> 1, bins = M + 1, F = a.F, T = a.T, lgM = a.lgM, hop = a.hop;
-  cf* tw = reinterpret_cast<cf*>(lds);
-  float* win = lds + 2 * N;
-  cf* bufA = reinterpret_cast<cf*>(lds + 3 * N);
-  cf* bufB = bufA + kTile / 2;
-  float* samp = lds + 3 * N + 2 * kTile;  // [scount]
+  const int N = a.n_fft, M = N >> 1, bins = M + 1, F = a.F, T = a.T, hop = a.hop;
+  const RunLds l = run_lds(lds, N);
   const int b = blockIdx.y, t0 = blockIdx.x * F, tid = threadIdx.x;
   int flags;
   const int tb = frames_of(a.frames, b, T, &flags);
   if (t0 >= tb) return;  // (workgroup-uniform)
-  for (int i = tid; i < N; i += kThreads) {
-    tw[i] = a.tw[i];
-    win[i] = a.window[i];
-  }
-  __syncthreads();
+  load_tables(l, N, a.tw, a.window, N);
+  __syncthreads();  // (ola_sample reads the window from LDS)
   // ---- the run's samples: overlap-add of the inverse frames, reflected at the utterance's own ends ----
   const float* frb = a.fr + (size_t)b * T * N;
   const int L = hop * (tb - 1), period = 2 * (L - 1);
@@ -275,43 +261,17 @@ __global__ __launch_bounds__(kThreads) void stft_kernel(const GlArgs a) {
         if (j < 0) j += period;
         if (j >= L) j = period - j;
       }
-      v = ola_sample(frb, win, tb, N, hop, j);
+      v = ola_sample(frb, l.win, tb, N, hop, j);
     }
-    samp[s] = v;
+    l.samp[s] = v;
   }
   __syncthreads();
-  // ---- first radix-8 pass on the window-weighted samples, read as pairs ----
-  if (hop & 1) {
-    fft_pass<8, true>(nullptr, bufA, tw, samp, win, hop, M, lgM, 1, F);
-  } else {
-    const float2* s2 = reinterpret_cast<const float2*>(samp);
-    const float2* w2 = reinterpret_cast<const float2*>(win);
-    const int lgPer = lgM - 3, per = 1 << lgPer, fs2 = hop >> 1;
-    for (int w = tid; w < (F << lgPer); w += kThreads) {
-      const int f = w >> lgPer, j = w & (per - 1);
-      cf v[8];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int i = j + (r << lgPer);
-        const float2 s = s2[f * fs2 + i], ww = w2[i];
-        v[r] = {s.x * ww.x, s.y * ww.y};
-      }
-      dft<8>(v);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) bufA[(f << lgM) + swz((j << 3) + r)] = v[r];
-    }
-  }
-  __syncthreads();
-  const cf* Z = fft_rest(bufA, bufB, tw, M, lgM, F);
-  // ---- split step: X[k] = E[k] + W^k O[k], k <= M ----
-  for (int idx = tid; idx < bins * F; idx += kThreads) {
-    const int f = idx / bins, k = idx - f * bins, t = t0 + f;
-    if (t >= tb) continue;
-    const cf zk = Z[(f << lgM) + swz(k & (M - 1))], zm = Z[(f << lgM) + swz((M - k) & (M - 1))];
-    const cf xe = {0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y)};
-    const cf xo = {0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x)};
-    a.reb[((size_t)b * T + t) * bins + k] = cadd(xe, cmul(tw[k], xo));
-  }
+  // ---- transform and split step: X[k], k <= M, of the frames that exist ----
+  cf* reb = a.reb + ((size_t)b * T + t0) * bins;
+  forward_run(l, hop, !(hop & 1), M, a.lgM, F, [=](int f, int k, cf x, float*) {
+    if (t0 + f >= tb) return;
+    reb[(size_t)f * bins + k] = x;
+  });
 }
 
 // grid (ceil(hop (T - 1) / 256), B)
@@ -346,24 +306,17 @@ __global__ __launch_bounds__(kThreads) void peak_kernel(float* __restrict__ wave
   for (int j = tid; j < L; j += kThreads) w[j] = w[j] / m;
 }
 
-// the twiddles (fft_lds.h) for k < n_fft.  grid n_fft / 256
-__global__ __launch_bounds__(kThreads) void twiddle_kernel(cf* __restrict__ tw, int n_fft) {
-  const int k = blockIdx.x * kThreads + threadIdx.x;
-  tw[k] = twiddle(k, n_fft);
-}
-
-
-struct WsLayout { size_t tw, mag, ra, rb, fr, total; };
-WsLayout ws_layout(int B, int T, int n_fft) {
-  const size_t bt = (size_t)B * T, bins = n_fft / 2 + 1;
-  WsLayout l;
-  l.tw = 0;
-  l.mag = l.tw + up((size_t)n_fft * sizeof(cf), 256);
-  l.ra = l.mag + up(bt * bins * sizeof(float), 256);
-  l.rb = l.ra + up(bt * bins * sizeof(cf), 256);
-  l.fr = l.rb + up(bt * bins * sizeof(cf), 256);
-  l.total = l.fr + up(bt * n_fft * sizeof(float), 256);
-  return l;
+// [n_fft] twiddles; [B, T, bins] the magnitudes frame-major; two rebuilt spectra [B, T, bins]; [B, T, n_fft] windowed inverse frames
+struct GlWs { cf* tw; float* mag; cf *ra, *rb; float* fr; };
+GlWs carve_griffinlim(Carver& cv, size_t B, size_t T, size_t n_fft) {
+  const size_t bt = B * T, bins = n_fft / 2 + 1;
+  GlWs w;
+  w.tw = reinterpret_cast<cf*>(cv.take(2 * n_fft));
+  w.mag = cv.take(bt * bins);
+  w.ra = reinterpret_cast<cf*>(cv.take(2 * bt * bins));
+  w.rb = reinterpret_cast<cf*>(cv.take(2 * bt * bins));
+  w.fr = cv.take(bt * n_fft);
+  return w;
 }
 
 int check_sizes(const ttsdec_handle* h, int B, int T, int n_fft, int hop) {
@@ -385,7 +338,9 @@ extern "C" {
 
 size_t ttsdec_griffinlim_workspace_bytes(const ttsdec_handle* h, int B, int T, int n_fft) {
   if (!h || B <= 0 || B > 65535 || T < 2 || T > kMaxFrames || !fft_ok(n_fft)) return 0;
-  return ws_layout(B, T, n_fft).total;
+  Carver cv{nullptr};
+  carve_griffinlim(cv, B, T, n_fft);
+  return cv.bytes();
 }
 
 int ttsdec_mel_to_magnitude(ttsdec_handle* h, const float* y, const float* P, const int32_t* frames, int B, int T, int n_mels, int n_fft, float* mag,
@@ -414,30 +369,27 @@ int ttsdec_griffinlim(ttsdec_handle* h, const float* mag, const int32_t* frames,
   if (rc != TTSDEC_OK) return rc;
   if (n_iter < 0 || !(momentum >= 0.f && momentum < 1.f)) return TTSDEC_ERR_INVALID_ARG;
   if (!mag || !window || !wave || ((rebuilt_out || angles_out) && n_iter == 0)) return TTSDEC_ERR_INVALID_ARG;
-  const WsLayout l = ws_layout(B, T, n_fft);
-  if (!workspace || workspace_bytes < l.total || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  Carver cv{static_cast<float*>(workspace)};
+  const GlWs ws = carve_griffinlim(cv, B, T, n_fft);
+  if (!workspace || workspace_bytes < cv.bytes() || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
   if (!device_is_current(base(h)->device)) return TTSDEC_ERR_DEVICE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* ws = static_cast<char*>(workspace);
   const int bins = n_fft / 2 + 1;
-  cf* tw = reinterpret_cast<cf*>(ws + l.tw);
-  float* magT = reinterpret_cast<float*>(ws + l.mag);
-  cf* cur = reinterpret_cast<cf*>(ws + l.ra);
-  cf* prev = reinterpret_cast<cf*>(ws + l.rb);
+  cf *cur = ws.ra, *prev = ws.rb;
   hipError_t e = hipSuccess;
   if (status) e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
   if (e == hipSuccess && n_iter > 0 && !tprev) e = hipMemsetAsync(prev, 0, (size_t)B * T * bins * sizeof(cf), st);
   if (e != hipSuccess) return hip_fail(base(h), e, "griffinlim");
-  hipLaunchKernelGGL(twiddle_kernel, dim3((unsigned)(n_fft / kThreads)), dim3(kThreads), 0, st, tw, n_fft);
-  transpose<float>(mag, magT, frames, B, T, bins, T, 1, st);
+  launch_stft_tables(ws.tw, n_fft, nullptr, nullptr, nullptr, 0, 0, bins, 0, nullptr, st);
+  transpose<float>(mag, ws.mag, frames, B, T, bins, T, 1, st);
   if (angles) transpose<cf>(reinterpret_cast<const cf*>(angles), cur, frames, B, T, bins, T, 1, st);
   if (tprev && n_iter > 0) transpose<cf>(reinterpret_cast<const cf*>(tprev), prev, frames, B, T, bins, T, 1, st);
 
   GlArgs a;
-  a.mag = magT; a.ang_out = nullptr; a.fr = reinterpret_cast<float*>(ws + l.fr); a.wave = wave; a.frames = frames; a.window = window; a.tw = tw;
+  a.mag = ws.mag; a.ang_out = nullptr; a.fr = ws.fr; a.wave = wave; a.frames = frames; a.window = window; a.tw = ws.tw;
   a.status = status; a.mom = momentum / (1.f + momentum); a.T = T; a.n_fft = n_fft; a.lgM = lg2(n_fft / 2); a.hop = hop_length;
-  a.F = kTile / n_fft; a.scount = (a.F - 1) * hop_length + n_fft;
-  const size_t lds_i = sizeof(float) * ((size_t)3 * n_fft + 2 * kTile), lds_f = lds_i + sizeof(float) * (size_t)a.scount;
+  a.F = run_frames(n_fft); a.scount = run_samples(n_fft, hop_length);
+  const size_t lds_i = sizeof(float) * run_lds_floats(n_fft, 0), lds_f = sizeof(float) * run_lds_floats(n_fft, a.scount);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_i) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f) != hipSuccess)
     return record_hip_error(base(h), "hipFuncSetAttribute(griffinlim kernels)");

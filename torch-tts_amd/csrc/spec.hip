@@ -2,14 +2,10 @@
 // vits2/mel_processing.py:58-187 - reflect pad by (n_fft - hop) / 2 at each utterance's own ends, Hann-windowed STFT (center=False),
 // sqrt(re^2 + im^2 + 1e-6), and for the mel forms log(clamp(mel_basis @ spec, 1e-5)).
 //
-//   spec_prep_kernel   the per-call tables in the workspace: exp(-2 pi i k / n_fft), k < n_fft, evaluated in fp64 and rounded once; and
-//                      per mel row the run [lo, hi) of bins outside which the basis row is exactly zero (a triangular filterbank
-//                      has ~2 * bins non-zeros in n_mels * bins entries; a dense basis just gets [0, bins)).
-//   stft_kernel<MEL>   one workgroup per run of F consecutive frames of one utterance, F * n_fft = kTile.  The samples the run
-//                      covers are loaded once ((F - 1) * hop + n_fft of them, reflected by index), each frame is the real FFT of
-//                      n_fft points as a complex FFT of M = n_fft / 2 points z[n] = x[2n] + i x[2n + 1] plus the split step
-//                      X[k] = (Z[k] + conj Z[M - k]) / 2 - i W^k (Z[k] - conj Z[M - k]) / 2.  The complex FFT is the Stockham
-//                      autosort of fft_lds.h (shared with griffinlim.hip); the first pass reads the window-weighted samples.
+//   (tables)           twiddles and, per mel row, the band of its non-zero bins, in the workspace: stft_run.h launch_stft_tables.
+//   stft_kernel<MEL>   one workgroup per run of F consecutive frames of one utterance, F * n_fft = kTile: the frame run of
+//                      stft_run.h - the samples the run covers loaded once ((F - 1) * hop + n_fft of them, reflected by index; frame
+//                      by frame when hop > n_fft), the window centred, forward_run - with sqrt(|X|^2 + 1e-6) as its emit.
 //                      The magnitudes go to LDS as [bin][F + 1] and leave as [B, bins, T] with the run's frames contiguous,
 //                      or - MEL - through the basis to [B, n_mels, T] without reaching memory.
 //   mel_kernel         the same epilogue on a spec tile read from memory (ttsvits_spec_to_mel).
@@ -17,16 +13,14 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "fft_lds.h"
 #include "kernels.h"
+#include "stft_run.h"
 
 using namespace ttsdec;
 
 namespace {
 constexpr int kThreads = kFftThreads;
-constexpr int kTile = 4096;      // floats of one LDS image of a run: F frames x n_fft / 2 complex points
 constexpr int kMelFrames = 16;   // frames per workgroup of mel_kernel (bins <= 513), half of it above
-constexpr int kMaxMels = 256;
 enum { FLAG_REFLECT = 1, FLAG_EMPTY = 2, FLAG_RANGE = 4 };  // status word: len <= pad; no frame; a length beyond the row / frames beyond T
 
 inline HandleBase* base(ttsvits_handle* h) { return reinterpret_cast<HandleBase*>(h); }
@@ -39,11 +33,7 @@ __device__ inline void mel_epilogue(const float* __restrict__ S, int ss, int bin
     if (t >= T) continue;
     float val = 0.f;
     if (t < tb) {
-      const int2 r = band[m];
-      const float* row = basis + (size_t)m * bins;
-      float acc = 0.f;
-      for (int k = r.x; k < r.y; ++k) acc += row[k] * S[k * ss + f];
-      val = logf(fmaxf(acc, 1e-5f));
+      val = logf(fmaxf(band_dot(basis + (size_t)m * bins, 1, band[m], S, ss, f), 1e-5f));
     }
     melb[(size_t)m * T + t] = val;
   }
@@ -78,11 +68,7 @@ template <bool MEL>
 __global__ __launch_bounds__(kThreads) void stft_kernel(const StftArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int N = a.n_fft, M = N >> 1, bins = M + 1, F = a.F, T = a.T;
-  cf* tw = reinterpret_cast<cf*>(lds);              // [N]
-  float* win = lds + 2 * N;                         // [N]
-  cf* bufA = reinterpret_cast<cf*>(lds + 3 * N);    // [F * M]
-  cf* bufB = bufA + kTile / 2;                      // [F * M]
-  float* samp = lds + 3 * N + 2 * kTile;            // [scount]
+  const RunLds l = run_lds(lds, N);
   const int b = blockIdx.y, t0 = blockIdx.x * F, tid = threadIdx.x;
   const int pad = (N - a.hop) / 2;
   int flags;
@@ -100,45 +86,14 @@ __global__ __launch_bounds__(kThreads) void stft_kernel(const StftArgs a) {
     return;
   }
   // ---- tables and the run's samples ----
-  for (int i = tid; i < N; i += kThreads) {
-    tw[i] = a.tw[i];
-    const int wl = (N - a.win) / 2, j = i - wl;
-    win[i] = (j >= 0 && j < a.win) ? a.window[j] : 0.f;
-  }
-  const float* wb = a.wav + (size_t)b * a.Nsamp;
+  load_tables(l, N, a.tw, a.window, a.win);
   const bool overlap = a.hop <= N;
-  const int fs = overlap ? a.hop : N;
-  const long long plen = (long long)len + 2 * pad;  // samples of the padded utterance
-  for (int s = tid; s < a.scount; s += kThreads) {
-    long long p;
-    if (overlap) p = (long long)t0 * a.hop + s;
-    else p = (long long)(t0 + s / N) * a.hop + s % N;
-    float v = 0.f;
-    if (p < plen) {
-      long long j = p - pad;
-      if (j < 0) j = -j;
-      if (j >= len) j = 2 * ((long long)len - 1) - j;
-      v = wb[j];
-    }
-    samp[s] = v;
-  }
+  load_reflected(l.samp, a.scount, a.wav + (size_t)b * a.Nsamp, len, pad, t0, a.hop, N, overlap, [](float v) { return v; });
   __syncthreads();
-  // ---- complex FFT of M points per frame ----
-  const int lgM = a.lgM;
-  fft_pass<8, true>(nullptr, bufA, tw, samp, win, fs, M, lgM, 1, F);
-  __syncthreads();
-  const cf* Z = fft_rest(bufA, bufB, tw, M, lgM, F);
-  float* S = reinterpret_cast<float*>(Z == bufA ? bufB : bufA);
-  // ---- split step and magnitude: S[k][f], k <= M ----
+  // ---- transform, split step and magnitude: S[k][f], k <= M ----
   const int ss = F + 1;
-  for (int idx = tid; idx < bins * F; idx += kThreads) {
-    const int f = idx / bins, k = idx - f * bins;
-    const cf zk = Z[(f << lgM) + swz(k & (M - 1))], zm = Z[(f << lgM) + swz((M - k) & (M - 1))];
-    const cf xe = {0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y)};
-    const cf xo = {0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x)};
-    const cf x = cadd(xe, cmul(tw[k], xo));
-    S[k * ss + f] = sqrtf((x.x * x.x + x.y * x.y) + 1e-6f);
-  }
+  const float* S = forward_run(l, overlap ? a.hop : N, false, M, a.lgM, F,
+                               [ss](int f, int k, cf x, float* S) { S[k * ss + f] = sqrtf((x.x * x.x + x.y * x.y) + 1e-6f); });
   __syncthreads();
   if (MEL) {
     mel_epilogue(S, ss, bins, F, a.lgF, a.basis, a.band, a.n_mels, outb, T, t0, tb);
@@ -169,29 +124,13 @@ __global__ __launch_bounds__(kThreads) void mel_kernel(const float* __restrict__
   mel_epilogue(lds, ss, bins, F, lgF, basis, band, n_mels, mel + (size_t)b * n_mels * T, T, t0, tb);
 }
 
-// blocks [0, n_fft / 256): the twiddles; then one block per mel row: its band
-__global__ __launch_bounds__(kThreads) void spec_prep_kernel(cf* __restrict__ tw, int n_fft, const float* __restrict__ basis, int bins, int n_mels,
-                                                             int2* __restrict__ band) {
-  const int nb = n_fft / kThreads;
-  if ((int)blockIdx.x < nb) {
-    const int k = blockIdx.x * kThreads + threadIdx.x;
-    tw[k] = twiddle(k, n_fft);
-    return;
-  }
-  __shared__ int lo, hi;
-  const int m = blockIdx.x - nb;
-  if (threadIdx.x == 0) { lo = bins; hi = 0; }
-  __syncthreads();
-  int l = bins, h = 0;
-  for (int k = threadIdx.x; k < bins; k += kThreads)
-    if (basis[(size_t)m * bins + k] != 0.f) { l = l < k ? l : k; h = k + 1; }
-  if (h) { atomicMin(&lo, l); atomicMax(&hi, h); }
-  __syncthreads();
-  if (threadIdx.x == 0) band[m] = hi > lo ? make_int2(lo, hi) : make_int2(0, 0);
+struct SpecWs { cf* tw; int2* band; };  // [n_fft] twiddles; [n_mels] bands
+SpecWs carve_spec(Carver& cv, int n_fft, int n_mels) {
+  SpecWs w;
+  w.tw = reinterpret_cast<cf*>(cv.take((size_t)2 * n_fft));
+  w.band = reinterpret_cast<int2*>(cv.take((size_t)2 * n_mels));
+  return w;
 }
-
-size_t tw_bytes(int n_fft) { return up((size_t)n_fft * sizeof(cf), 256); }
-size_t ws_bytes_of(int n_fft, int n_mels) { return tw_bytes(n_fft) + up((size_t)n_mels * sizeof(int2), 256); }
 
 int check_wave(const ttsvits_handle* h, int B, int N, int n_fft, int hop, int win, int T) {
   if (!h || B <= 0 || N <= 0 || hop <= 0 || win <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
@@ -199,27 +138,27 @@ int check_wave(const ttsvits_handle* h, int B, int N, int n_fft, int hop, int wi
   return TTSDEC_OK;
 }
 
-int check_ws(const void* ws, size_t bytes, int n_fft, int n_mels) {
-  return (!ws || bytes < ws_bytes_of(n_fft, n_mels) || (reinterpret_cast<uintptr_t>(ws) & 255)) ? TTSDEC_ERR_WORKSPACE : TTSDEC_OK;
+// the caller's workspace carved into w, or refused
+int check_ws(void* ws, size_t bytes, int n_fft, int n_mels, SpecWs* w) {
+  Carver cv{static_cast<float*>(ws)};
+  *w = carve_spec(cv, n_fft, n_mels);
+  return (!ws || bytes < cv.bytes() || (reinterpret_cast<uintptr_t>(ws) & 255)) ? TTSDEC_ERR_WORKSPACE : TTSDEC_OK;
 }
 
 int run_stft(ttsvits_handle* h, const float* wav, const int32_t* lengths, int B, int N, const float* window, int n_fft, int hop, int win,
-             const float* basis, int n_mels, float* out, int T, int32_t* status, void* ws, hipStream_t st, const char* what) {
+             const float* basis, int n_mels, float* out, int T, int32_t* status, const SpecWs& w, hipStream_t st, const char* what) {
   if (!device_is_current(base(h)->device)) return TTSDEC_ERR_DEVICE;
   const int bins = n_fft / 2 + 1;
-  cf* tw = static_cast<cf*>(ws);
-  int2* band = reinterpret_cast<int2*>(static_cast<char*>(ws) + tw_bytes(n_fft));
   if (status) {
     hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
     if (e != hipSuccess) return hip_fail(base(h), e, what);
   }
-  hipLaunchKernelGGL(spec_prep_kernel, dim3((unsigned)(n_fft / kThreads + n_mels)), dim3(kThreads), 0, st, tw, n_fft, basis, bins, n_mels, band);
+  launch_stft_tables(w.tw, n_fft, nullptr, nullptr, basis, bins, 1, bins, n_mels, w.band, st);
   StftArgs a;
-  a.wav = wav; a.lengths = lengths; a.window = window; a.tw = tw; a.basis = basis; a.band = band; a.out = out; a.status = status;
+  a.wav = wav; a.lengths = lengths; a.window = window; a.tw = w.tw; a.basis = basis; a.band = w.band; a.out = out; a.status = status;
   a.Nsamp = N; a.n_fft = n_fft; a.lgM = lg2(n_fft / 2); a.hop = hop; a.win = win; a.n_mels = n_mels; a.T = T;
-  a.F = kTile / n_fft; a.lgF = lg2(a.F);
-  a.scount = hop <= n_fft ? (a.F - 1) * hop + n_fft : a.F * n_fft;
-  const size_t lds = sizeof(float) * ((size_t)3 * n_fft + 2 * kTile + a.scount);
+  a.F = run_frames(n_fft); a.lgF = lg2(a.F); a.scount = run_samples(n_fft, hop);
+  const size_t lds = sizeof(float) * run_lds_floats(n_fft, a.scount);
   const dim3 grid((unsigned)((T + a.F - 1) / a.F), (unsigned)B);
   auto kfn = n_mels ? stft_kernel<true> : stft_kernel<false>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -234,7 +173,9 @@ extern "C" {
 
 size_t ttsvits_spec_workspace_bytes(const ttsvits_handle* h, int n_fft, int n_mels) {
   if (!h || !fft_ok(n_fft) || n_mels < 0 || n_mels > kMaxMels) return 0;
-  return ws_bytes_of(n_fft, n_mels);
+  Carver cv{nullptr};
+  carve_spec(cv, n_fft, n_mels);
+  return cv.bytes();
 }
 
 int ttsvits_spectrogram(ttsvits_handle* h, const float* wav, const int32_t* lengths, int B, int N, const float* window, int n_fft, int hop_size,
@@ -242,8 +183,9 @@ int ttsvits_spectrogram(ttsvits_handle* h, const float* wav, const int32_t* leng
   int rc = check_wave(h, B, N, n_fft, hop_size, win_size, T);
   if (rc != TTSDEC_OK) return rc;
   if (!wav || !window || !spec) return TTSDEC_ERR_INVALID_ARG;
-  if ((rc = check_ws(workspace, workspace_bytes, n_fft, 0)) != TTSDEC_OK) return rc;
-  return run_stft(h, wav, lengths, B, N, window, n_fft, hop_size, win_size, nullptr, 0, spec, T, status, workspace,
+  SpecWs w;
+  if ((rc = check_ws(workspace, workspace_bytes, n_fft, 0, &w)) != TTSDEC_OK) return rc;
+  return run_stft(h, wav, lengths, B, N, window, n_fft, hop_size, win_size, nullptr, 0, spec, T, status, w,
                   static_cast<hipStream_t>(stream), "spectrogram");
 }
 
@@ -255,8 +197,9 @@ int ttsvits_mel_spectrogram(ttsvits_handle* h, const float* wav, const int32_t* 
   if (n_mels <= 0) return TTSDEC_ERR_INVALID_ARG;
   if (n_mels > kMaxMels) return TTSDEC_ERR_DIMS;
   if (!wav || !window || !mel_basis || !mel) return TTSDEC_ERR_INVALID_ARG;
-  if ((rc = check_ws(workspace, workspace_bytes, n_fft, n_mels)) != TTSDEC_OK) return rc;
-  return run_stft(h, wav, lengths, B, N, window, n_fft, hop_size, win_size, mel_basis, n_mels, mel, T, status, workspace,
+  SpecWs w;
+  if ((rc = check_ws(workspace, workspace_bytes, n_fft, n_mels, &w)) != TTSDEC_OK) return rc;
+  return run_stft(h, wav, lengths, B, N, window, n_fft, hop_size, win_size, mel_basis, n_mels, mel, T, status, w,
                   static_cast<hipStream_t>(stream), "mel_spectrogram");
 }
 
@@ -265,17 +208,17 @@ int ttsvits_spec_to_mel(ttsvits_handle* h, const float* spec, const int32_t* fra
   if (!h || B <= 0 || T <= 0 || n_mels <= 0) return TTSDEC_ERR_INVALID_ARG;
   if (!fft_ok(n_fft) || n_mels > kMaxMels || B > 65535) return TTSDEC_ERR_DIMS;
   if (!spec || !mel_basis || !mel) return TTSDEC_ERR_INVALID_ARG;
-  const int rc = check_ws(workspace, workspace_bytes, n_fft, n_mels);
+  SpecWs w;
+  const int rc = check_ws(workspace, workspace_bytes, n_fft, n_mels, &w);
   if (rc != TTSDEC_OK) return rc;
   if (!device_is_current(base(h)->device)) return TTSDEC_ERR_DEVICE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int bins = n_fft / 2 + 1;
-  int2* band = reinterpret_cast<int2*>(static_cast<char*>(workspace) + tw_bytes(n_fft));
-  hipLaunchKernelGGL(spec_prep_kernel, dim3((unsigned)n_mels), dim3(kThreads), 0, st, nullptr, 0, mel_basis, bins, n_mels, band);
+  launch_stft_tables(nullptr, 0, nullptr, nullptr, mel_basis, bins, 1, bins, n_mels, w.band, st);
   const int F = bins <= 513 ? kMelFrames : kMelFrames / 2;
   const size_t lds = sizeof(float) * (size_t)bins * (F + 1);
   hipLaunchKernelGGL(mel_kernel, dim3((unsigned)((T + F - 1) / F), (unsigned)B), dim3(kThreads), lds, st, spec, frames, bins, T, F, lg2(F), mel_basis,
-                     band, n_mels, mel);
+                     w.band, n_mels, mel);
   return record_hip_error(base(h), "spec_to_mel");
 }
 
