@@ -386,6 +386,80 @@ int ttsenc_set_precision(ttsenc_handle* h, int precision);
 int ttsenc_get_precision(const ttsenc_handle* h);
 
 /* ---------------------------------------------------------------------------------------
+ * Style encoder (tacotron/modules/style.py, modules/attention.py:129-186), a second handle of the ttsenc_ family: the
+ * ReferenceEncoder (n_convs x [Conv2d 3x3 stride 2 pad 1 + bias -> BatchNorm2d (running statistics) -> ReLU], then a one-layer
+ * LSTM over the packed sequence, last hidden state) and what VAE / GST / GST_VAE put behind it.  Eval mode, exact fp32
+ * throughout (no precision switch).  Activations are channels-last, [B, T_l, F_l, C_l], sizes L -> (L - 1) / 2 + 1 per stage
+ * on both axes.
+ * ------------------------------------------------------------------------------------- */
+#define TTSENC_STYLE_MAX_CONVS 8
+enum { TTSENC_STYLE_ENCODER = 0, TTSENC_STYLE_VAE = 1, TTSENC_STYLE_GST = 2, TTSENC_STYLE_GST_VAE = 3 };
+typedef struct ttsenc_style_dims {
+  int32_t n_mels;                            /* audio.num_mels: the input's feature axis                              */
+  int32_t n_convs;                           /* len(ref_enc_filters) (6), 1 .. TTSENC_STYLE_MAX_CONVS                  */
+  int32_t filters[TTSENC_STYLE_MAX_CONVS];   /* ref_enc_filters (32, 32, 64, 64, 128, 128): multiples of 4             */
+  int32_t d_enc;                             /* ReferenceEncoder dim_out (128): LSTM hidden size, a multiple of 4      */
+  int32_t kind;                              /* TTSENC_STYLE_*                                                         */
+  int32_t d_emb;                             /* dim_emb (256): the style embedding added to `memory` (kinds 1 - 3)     */
+  int32_t d_vae;                             /* dim_vae (kinds 1, 3)                                                   */
+  int32_t n_tokens;                          /* num_tokens (kinds 2, 3), <= 64                                         */
+  int32_t n_heads;                           /* num_heads (kinds 2, 3), <= 16, divides d_emb                           */
+  float bn_eps;                              /* 1e-5                                                                   */
+} ttsenc_style_dims;
+typedef struct ttsenc_style_handle ttsenc_style_handle;
+
+/* Source tensors for ttsenc_style_pack_weights: the head in this order, then six per conv stage i at
+ * TTSENC_STYLE_W_STAGES + 6 * i + TTSENC_STYLE_W_CONV_W ... (ttsenc_style_num_weight_tensors = TTSENC_STYLE_W_STAGES +
+ * 6 * n_convs).  Tensors that the handle's kind does not have are NULL. */
+enum {
+  TTSENC_STYLE_W_LSTM_IH = 0, /* encoder.gru.weight_ih_l0 [4 d_enc, C_last * F_last], columns c * F_last + f       */
+  TTSENC_STYLE_W_LSTM_HH,     /* encoder.gru.weight_hh_l0 [4 d_enc, d_enc]                                          */
+  TTSENC_STYLE_W_LSTM_BIH,    /* encoder.gru.bias_ih_l0 [4 d_enc]                                                   */
+  TTSENC_STYLE_W_LSTM_BHH,    /* encoder.gru.bias_hh_l0 [4 d_enc]                                                   */
+  TTSENC_STYLE_W_MEAN_W,      /* mean_linear.weight [d_vae, d_enc (VAE) or d_emb (GST_VAE)]                         */
+  TTSENC_STYLE_W_MEAN_B,      /* mean_linear.bias [d_vae]                                                           */
+  TTSENC_STYLE_W_LOGVAR_W,    /* logvar_linear.weight                                                               */
+  TTSENC_STYLE_W_LOGVAR_B,    /* logvar_linear.bias                                                                 */
+  TTSENC_STYLE_W_FC_OUT,      /* fc_out.weight [d_emb, d_vae]                                                       */
+  TTSENC_STYLE_W_EMBED,       /* stl.embed [n_tokens, d_emb / n_heads]                                              */
+  TTSENC_STYLE_W_QUERY,       /* stl.attention.W_query.weight [d_emb, d_enc]                                        */
+  TTSENC_STYLE_W_KEY,         /* stl.attention.W_key.weight [d_emb, d_emb / n_heads]                                */
+  TTSENC_STYLE_W_VALUE,       /* stl.attention.W_value.weight [d_emb, d_emb / n_heads]                              */
+  TTSENC_STYLE_W_STAGES       /* first tensor of conv stage 0                                                       */
+};
+enum {
+  TTSENC_STYLE_W_CONV_W = 0,  /* encoder.convs.i.weight [C_i, C_{i-1}, 3, 3]                                        */
+  TTSENC_STYLE_W_CONV_B,      /* encoder.convs.i.bias [C_i]                                                         */
+  TTSENC_STYLE_W_BN_W,        /* encoder.bns.i.weight                                                               */
+  TTSENC_STYLE_W_BN_B,        /* encoder.bns.i.bias                                                                 */
+  TTSENC_STYLE_W_BN_MEAN,     /* encoder.bns.i.running_mean                                                         */
+  TTSENC_STYLE_W_BN_VAR,      /* encoder.bns.i.running_var                                                          */
+  TTSENC_STYLE_W_PER_STAGE
+};
+
+/* TTSDEC_ERR_DIMS: a filter count that is no multiple of 4, d_enc no multiple of 4 (the LSTM kernel's K segments are 16-byte
+ * columns), d_emb % n_heads != 0, or a size beyond the limits above. */
+int ttsenc_style_create(const ttsenc_style_dims* dims, ttsenc_style_handle** out);
+int ttsenc_style_destroy(ttsenc_style_handle* h);
+const char* ttsenc_style_last_hip_error(const ttsenc_style_handle* h);
+int ttsenc_style_num_weight_tensors(const ttsenc_style_handle* h);
+size_t ttsenc_style_packed_bytes(const ttsenc_style_handle* h);
+/* Besides the copies: conv weights to [C_out][ky][kx][C_in], BatchNorm folded to (alpha, beta), W_ih's columns permuted to the
+ * channels-last order f * C + c, b_ih + b_hh, and the token keys / values tanh(embed) . W_key^T, . W_value^T (input-independent). */
+int ttsenc_style_pack_weights(ttsenc_style_handle* h, const float* const* src, int n_src, void* blob, void* stream);
+int ttsenc_style_bind_weights(ttsenc_style_handle* h, const void* blob);
+size_t ttsenc_style_workspace_bytes(const ttsenc_style_handle* h, int B, int T);
+/* x: frame (b, t) at x + (b * T + t) * ldx, n_mels floats (ldx >= n_mels, a multiple of 4 is not required).
+ * lengths [B] int32 on the device or NULL (every row runs all T' = T after n_convs stages steps); a row's LSTM runs
+ * min(max(lengths[b] >> n_convs, 1), T') steps - a length above T is clamped here, the caller checks host-side lengths.
+ * The convs are not masked: they see whatever the padded frames hold, as the reference's do.
+ * eps [B, d_vae] (kinds 1, 3; NULL otherwise): the caller's standard-normal draw.
+ * enc_out [B, d_enc] (always); x_out [B, d_emb] and kl_out [B, d_vae] (kinds 1, 3; x_out alone for kind 2; NULL otherwise).
+ * No host synchronisation; every reduction runs in a fixed order. */
+int ttsenc_style_forward(ttsenc_style_handle* h, const float* x, int ldx, const int32_t* lengths, const float* eps, int B, int T,
+                         float* enc_out, float* x_out, float* kl_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * VITS2 second hot path (BASELINE.json configs[4]):
  *   ttsvits_text_encoder  = TextEncoder.forward, vits2/models.py:369-380
  *       (attentions.Encoder :76-93, MultiHeadAttention.attention :246-295 with the relative-position

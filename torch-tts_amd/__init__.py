@@ -7,6 +7,7 @@ from .decoder import Decoder
 from .decoder_cell import LSTMZoneoutCell, PreNet, StepwiseMonotonicAttention, Taco2DecoderCell, Taco2ProdDecoderCell
 from .engine import Engine, EngineDims
 from .postnet import Conv1dFix, MelPostnet, MelPostnet2
+from .style import GST, GST_VAE, STL, VAE, MultiHeadAttention, ReferenceEncoder, StyleEngine
 from .tacotron import Encoder2, Tacotron, build_tacotron, lengths_to_mask
 from . import vits2  # noqa: F401  (TextEncoder, ResidualCouplingTransformersBlock, Generator, StochasticDurationPredictor, DurationPredictor, infer,
 #                             PosteriorEncoder, voice_conversion)
@@ -19,4 +20,5 @@ __all__ = [
     "Decoder", "Taco2ProdDecoderCell", "Taco2DecoderCell", "PreNet", "LSTMZoneoutCell", "StepwiseMonotonicAttention", "MelPostnet", "MelPostnet2",
     "Tacotron", "Encoder2", "build_tacotron", "lengths_to_mask", "Engine", "EngineDims",
     "Generator", "StochasticDurationPredictor", "DurationPredictor", "PosteriorEncoder",
+    "ReferenceEncoder", "STL", "GST", "VAE", "GST_VAE", "MultiHeadAttention", "StyleEngine",
 ]

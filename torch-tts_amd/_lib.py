@@ -68,6 +68,17 @@ class EncDims(C.Structure):
     ]
 
 
+STYLE_MAX_CONVS = 8  # include/ttsdec.h TTSENC_STYLE_MAX_CONVS
+STYLE_ENCODER, STYLE_VAE, STYLE_GST, STYLE_GST_VAE = 0, 1, 2, 3  # ttsenc_style_dims.kind
+STYLE_W_STAGES, STYLE_W_PER_STAGE = 13, 6  # TTSENC_STYLE_W_STAGES / _PER_STAGE
+
+
+class StyleDims(C.Structure):  # include/ttsdec.h ttsenc_style_dims
+    _fields_ = [("n_mels", C.c_int32), ("n_convs", C.c_int32), ("filters", C.c_int32 * STYLE_MAX_CONVS), ("d_enc", C.c_int32),
+                ("kind", C.c_int32), ("d_emb", C.c_int32), ("d_vae", C.c_int32), ("n_tokens", C.c_int32), ("n_heads", C.c_int32),
+                ("bn_eps", C.c_float)]
+
+
 class VitsDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_vocab", "inter_channels", "hidden_channels", "filter_channels", "n_heads", "n_layers", "kernel_size", "window_size",
@@ -101,6 +112,17 @@ class PostDims(C.Structure):  # include/ttsdec.h ttspost_dims
 # _get_precision, and (restype, argtypes) of its own entry points.  Every family also has the shared ones of SHARED below.
 vp, i32, u64, sz, f32 = C.c_void_p, C.c_int, C.c_uint64, C.c_size_t, C.c_float
 _ws_bytes = (sz, [vp, i32, i32])  # <prefix>_*workspace_bytes(h, B, T)
+
+
+# entry points every handle has besides its create
+_SHARED_SIGS = {
+    "destroy": (i32, [vp]),
+    "last_hip_error": (C.c_char_p, [vp]),
+    "num_weight_tensors": (i32, [vp]),
+    "packed_bytes": (sz, [vp]),
+    "pack_weights": (i32, [vp, C.POINTER(vp), i32, vp, vp]),
+    "bind_weights": (i32, [vp, vp]),
+}
 
 
 class Family(NamedTuple):
@@ -160,6 +182,11 @@ FAMILIES = (
     Family("ttsenc", EncDims, True, {
         "workspace_bytes": _ws_bytes,
         "forward": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, sz, vp, vp]),
+        # the style encoder: a second handle of this family (engine.Handle builds its names with PREFIX = "ttsenc_style")
+        "style_create": (i32, [C.POINTER(StyleDims), C.POINTER(vp)]),
+        **{f"style_{n}": sig for n, sig in _SHARED_SIGS.items()},
+        "style_workspace_bytes": _ws_bytes,
+        "style_forward": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]),  # h, x, ldx, lengths, eps, B, T, enc_out, x_out, kl_out, ws, bytes, stream
     }),
     Family("ttsvits", VitsDims, True, {
         "text_encoder_workspace_bytes": _ws_bytes,
@@ -193,14 +220,7 @@ FAMILIES = (
         "forward": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     }),
 )
-SHARED = {
-    "destroy": (i32, [vp]),
-    "last_hip_error": (C.c_char_p, [vp]),
-    "num_weight_tensors": (i32, [vp]),
-    "packed_bytes": (sz, [vp]),
-    "pack_weights": (i32, [vp, C.POINTER(vp), i32, vp, vp]),
-    "bind_weights": (i32, [vp, vp]),
-}
+SHARED = _SHARED_SIGS
 PRECISION = {"set_precision": (i32, [vp, i32]), "get_precision": (i32, [vp])}
 
 

@@ -1,8 +1,9 @@
 """Model assembly with the reference's API (tacotron/tacotron.py:20-56,165-224):
 ``Tacotron(encoder, decoder, postnet, refencoder).forward(...) -> (y, y_post, s,
 {"w", "kl_loss"})`` and ``build_tacotron(config)``.  The decoder and postnet are the
-HIP-backed drop-ins of this package; so is the encoder in eval mode (torch-tts_amd/encoder.py;
-it runs once per batch, before the hot path)."""
+HIP-backed drop-ins of this package; so are the encoder (torch-tts_amd/encoder.py) and the style
+encoder (torch-tts_amd/style.py) in eval mode; both run once per batch, before the hot path.
+``fast_inference()`` leaves the style encoder in exact fp32: it has no other arithmetic."""
 from __future__ import annotations
 
 import torch
@@ -13,6 +14,7 @@ from .engine import PackedWeightsMixin
 from .decoder_cell import Taco2DecoderCell, Taco2ProdDecoderCell
 from .encoder import Encoder2
 from .postnet import MelPostnet, MelPostnet2
+from .style import VAE
 
 
 def lengths_to_mask(lengths):
@@ -110,6 +112,8 @@ def build_tacotron(config):
             postnet = MelPostnet(audio_config["num_mels"], dim_hidden=postnet_config["dim_hidden"], num_layers=postnet_config["num_layers"])
         else:
             postnet = MelPostnet2(audio_config["num_mels"], dim_hidden=postnet_config["dim_hidden"], num_layers=postnet_config["num_layers"])
-    if config["model"].get("style_encoder"):
-        raise NotImplementedError("style encoder (VAE) is outside the hot path and not provided")
-    return Tacotron(encoder, decoder, postnet=postnet, refencoder=None)
+    style_encoder_config = config["model"].get("style_encoder")
+    refencoder = None
+    if style_encoder_config:  # tacotron.py:216-220
+        refencoder = VAE(num_mels=audio_config["num_mels"], dim_vae=style_encoder_config["dim_vae"])
+    return Tacotron(encoder, decoder, postnet=postnet, refencoder=refencoder)
