@@ -46,7 +46,8 @@ extern "C" {
  * ttsvits_maximum_path and ttsvits_align for monotonic alignment search; then ttsvits_spectrogram, ttsvits_spec_to_mel and
  * ttsvits_mel_spectrogram, the spectrogram front-end; then ttsdec_griffinlim_workspace_bytes, ttsdec_mel_to_magnitude and
  * ttsdec_griffinlim, mel -> waveform for the Tacotron path; then ttsdec_mel_analysis_workspace_bytes and ttsdec_mel_analysis,
- * waveform -> dB spectrogram and mel for it.) */
+ * waveform -> dB spectrogram and mel for it; then ttsvits_generator_planes_bytes, _pack_planes, _workspace_bytes and _forward,
+ * the generator with its arithmetic as a call argument.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -678,7 +679,8 @@ int ttsdec_mel_analysis(ttsdec_handle* h, const float* wave, const int32_t* leng
 /* ---------------------------------------------------------------------------------------
  * VITS2 HiFi-GAN generator (latent z -> waveform): Generator.forward, vits2/models.py:900-974, with ResBlock1.forward
  * modules.py:221-315 called without x_mask - the `self.dec(...)` of SynthesizerTrn.infer, models.py:1322.  Eval mode, exact fp32
- * (the fp32-input matrix instruction for every conv, fp32 vector ALU elsewhere).  Activations are CHANNEL-LAST: z [B, T, C].
+ * (the fp32-input matrix instruction for every conv, fp32 vector ALU elsewhere; split-fp16 is opt-in per call through
+ * ttsvits_generator_forward, at the end of this block).  Activations are CHANNEL-LAST: z [B, T, C].
  *   conv_pre (7 taps) [+ cond(g)]; per upsampling stage i: leaky_relu(0.1), ConvTranspose1d(k = 2u, stride u) as a 3-tap conv
  *   producing u output phases per input frame, then the mean of n_res ResBlock1 (three (dilated conv, conv) pairs each);
  *   leaky_relu(0.01) (models.py:963: the default slope), conv_post (7 taps, no bias), tanh.
@@ -739,6 +741,39 @@ int ttsgen_forward(ttsgen_handle* h, const float* z, const float* g, int B, int 
  * [B * T_s, C_s] fp32 (T_s = T * u_0 * ... * u_{n_stages-1}, C_s its channels; conv_pre: [B * T, C0]); nothing is written to out. */
 int ttsgen_forward_stages(ttsgen_handle* h, const float* z, const float* g, int B, int T, int n_stages, void* workspace, size_t workspace_bytes,
                           void* stream);
+
+/* The same forward with the arithmetic of its conv GEMMs as a call argument (as ttsdec_postnet has it): `precision` is
+ * TTSDEC_PREC_F32 - then the call IS ttsgen_forward / ttsgen_forward_stages, the same code and the same bits, and `planes` is
+ * ignored - or TTSDEC_PREC_SPLIT_F16 (opt-in: two fp16 planes per GEMM operand, three products, fp32 accumulate; held to the
+ * exact path's parity bar); anything else is TTSDEC_ERR_INVALID_ARG.  These take a ttsgen_handle under the ttsvits_ prefix, as
+ * ttsenc_style_* puts a second handle type under ttsenc_.
+ *   Only GEMM operands are split.  x, the resblocks' running x', the branch sum and the bias / cond(g) / residual / sum /
+ * division chain of the epilogues stay fp32, in the exact path's order; conv_post + tanh reads fp32.  Every conv input - z, and
+ * the leaky-ReLU outputs between the convs - is held as planes (hi = fp16(x), lo = fp16((x - hi) * 2^11)); the split SATURATES:
+ * an activation beyond +-65504 enters the next conv as +-65504, and there is no status word that says so (finite weights of a
+ * trained generator keep activations orders of magnitude below it).
+ *   A layer runs in split-fp16 when its input channels are a multiple of 8 and, where it is dilated, divide 64 or are a multiple
+ * of 64 (the K tile of the split tiles); the resblocks of one stage switch together.  Any other layer keeps the exact fp32 tiles
+ * inside a split-fp16 call (reading an fp32 copy of its input).  ModelConfig dims: every conv qualifies.  (ups[0] always does:
+ * upsample_initial_channel is twice a multiple of 4.  So planes_bytes is never 0.)
+ *   ttsvits_generator_planes_bytes: size of the second blob, the planes of the weights of every layer that runs in split-fp16 (per
+ * weight of n elements: hi plane, lo plane, 4 n bytes rounded up to 256); 62.6 MB at the ModelConfig dims.  An fp32-only caller
+ * allocates nothing.
+ *   ttsvits_generator_pack_planes: builds them (256-byte aligned device memory) from the fp32 blob that is bound - a split of the
+ * packed blob, in its layout (conv weights tap-major, ups as the polyphase 3-tap weight), not a second packing - on `stream`;
+ * TTSDEC_ERR_NOT_BOUND when nothing is bound.  Call it again whenever the fp32 blob is repacked.
+ *   ttsvits_generator_workspace_bytes(gen, TTSDEC_PREC_F32, B, T) == ttsgen_workspace_bytes(gen, B, T); split-fp16 adds the planes
+ * of z ([G * T, initial_channel]) and, for a handle with both kinds of layer, one more activation buffer.  0 for a bad precision.
+ *   ttsvits_generator_forward: z, g, B, T, out, workspace as ttsgen_forward; groups as there.  n_stages == n_up with out != NULL
+ * is the full forward; 0 <= n_stages < n_up (out ignored), or n_stages == n_up with out == NULL, is ttsgen_forward_stages (B
+ * must fit one group): whatever the precision, that stage's activated output is left as fp32 [B * T_s, C_s] at the start of
+ * the workspace.  Any other n_stages is TTSDEC_ERR_INVALID_ARG.  Split-fp16 with
+ * planes == NULL is TTSDEC_ERR_INVALID_ARG. */
+size_t ttsvits_generator_planes_bytes(const ttsgen_handle* gen);
+int ttsvits_generator_pack_planes(ttsgen_handle* gen, void* planes, void* stream);
+size_t ttsvits_generator_workspace_bytes(const ttsgen_handle* gen, int precision, int B, int T);
+int ttsvits_generator_forward(ttsgen_handle* gen, int precision, const void* planes, const float* z, const float* g, int B, int T,
+                              int n_stages, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * VITS2 duration predictors and length regulation: the `self.dp(...)` and the prior expansion of SynthesizerTrn.infer,

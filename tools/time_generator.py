@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""Times the VITS2 HiFi-GAN generator (models.py:900-974) at the ModelConfig dims: the HIP library (torch_tts_amd.Generator, exact
-fp32) and the same module written with F.conv1d / F.conv_transpose1d on the same GPU in fp32 (what a user runs today).
-Reports ms per call, mel-frames/s, audio-seconds/s at 22.05 kHz and the fraction of the fp32 matrix pipe (157.3 TFLOP/s) the
-algorithmic FLOPs reach.  Usage: python tools/time_generator.py [--batch 64] [--frames 600] [--min-seconds 1.0] [--skip-torch]"""
+"""Times the VITS2 HiFi-GAN generator (models.py:900-974) at the ModelConfig dims: the HIP library (torch_tts_amd.Generator) in exact
+fp32 and in split-fp16 - the two modes in one process, alternating in rounds - and the same module written with F.conv1d /
+F.conv_transpose1d on the same GPU in fp32 (what a user runs today).  Reports ms per call (the median of the rounds) and the
+spread between the rounds of one mode, mel-frames/s, audio-seconds/s at 22.05 kHz and the share of the matrix pipe: for f32 the
+algorithmic FLOPs against the fp32 matrix peak (157.3 TFLOP/s), for split_f16 the three fp16 products it issues per algorithmic
+product against the fp16 matrix peak (2516.8 TFLOP/s dense).
+Usage: python tools/time_generator.py [--batch 64] [--frames 600] [--precision f32 split_f16] [--rounds 5] [--min-seconds 1.0] [--skip-torch]"""
 import argparse
 import json
 import os
+import statistics
 import sys
 import warnings
 
@@ -18,6 +22,7 @@ warnings.filterwarnings("ignore", category=FutureWarning)
 import torch_tts_amd as T  # noqa: E402
 
 FP32_MATRIX_TFLOPS = 157.3  # MI355X, fp32-input MFMA
+FP16_MATRIX_TFLOPS = 16 * FP32_MATRIX_TFLOPS  # fp16 MFMA, dense: 16 x the fp32-input rate (~2.5 PFLOP/s)
 SAMPLE_RATE = 22050
 DIMS = dict(initial_channel=192, resblock="1", resblock_kernel_sizes=[3, 7, 11], resblock_dilation_sizes=[[1, 3, 5]] * 3,
             upsample_rates=[8, 8, 2, 2], upsample_initial_channel=512, upsample_kernel_sizes=[16, 16, 4, 4], gin_channels=0)
@@ -81,6 +86,8 @@ def main():
     ap.add_argument("--frames", type=int, default=600)
     ap.add_argument("--min-seconds", type=float, default=1.0)
     ap.add_argument("--skip-torch", action="store_true")
+    ap.add_argument("--precision", nargs="+", choices=["f32", "split_f16"], default=["f32", "split_f16"])
+    ap.add_argument("--rounds", type=int, default=5, help="timed windows per mode, the modes alternating (--min-seconds is one mode's total)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.backends.cudnn.allow_tf32 = False
@@ -102,16 +109,34 @@ def main():
     for B in args.batch:
         z = torch.randn(B, DIMS["initial_channel"], Tn, device=dev)
         rows = {}
+        def hip(mode):
+            gen.precision = mode
+            return gen(z)
+
+        def rates(ms):
+            return dict(mel_frames_per_s=round(B * Tn / ms * 1e3, 1), audio_s_per_s=round(B * Tn * up / SAMPLE_RATE / ms * 1e3, 1))
+
         with torch.no_grad():
-            impls = [("hip", lambda: gen(z))] + ([] if args.skip_torch else [("torch_ops", lambda: torch_forward(gen, z))])
-            for name, fn in impls:
-                ms, n = time_call(fn, args.min_seconds)
-                rows[name] = dict(ms_per_call=round(ms, 3), calls=n, mel_frames_per_s=round(B * Tn / ms * 1e3, 1),
-                                  audio_s_per_s=round(B * Tn * up / SAMPLE_RATE / ms * 1e3, 1),
-                                  fp32_pipe_fraction=round(B * flop / (ms * 1e-3) / (FP32_MATRIX_TFLOPS * 1e12), 4))
+            per = {m: [] for m in args.precision}
+            for _ in range(args.rounds):  # f32, split_f16, f32, ...: drift of the clocks lands on both modes alike
+                for m in args.precision:
+                    per[m].append(time_call(lambda: hip(m), args.min_seconds / args.rounds))
+            for m, windows in per.items():
+                ms = statistics.median(w[0] for w in windows)
+                rows["hip" if m == "f32" else "hip_split_f16"] = dict(
+                    ms_per_call=round(ms, 3), ms_rounds=[round(w[0], 3) for w in windows], spread_ms=round(max(w[0] for w in windows) - min(w[0] for w in windows), 3),
+                    calls=sum(w[1] for w in windows), **rates(ms),
+                    **(dict(fp32_pipe_fraction=round(B * flop / (ms * 1e-3) / (FP32_MATRIX_TFLOPS * 1e12), 4)) if m == "f32" else
+                       dict(fp16_pipe_fraction=round(3 * B * flop / (ms * 1e-3) / (FP16_MATRIX_TFLOPS * 1e12), 4))))
+            if len(per) == 2:
+                rows["f32_over_split_f16"] = round(rows["hip"]["ms_per_call"] / rows["hip_split_f16"]["ms_per_call"], 3)
+                rows["max_abs_diff_split_f16_vs_f32"] = (hip("split_f16") - hip("f32")).abs().max().item()
             if not args.skip_torch:
-                d = (gen(z) - torch_forward(gen, z)).abs().max().item()
-                rows["max_abs_diff_hip_vs_torch"] = d
+                ms, n = time_call(lambda: torch_forward(gen, z), args.min_seconds)
+                rows["torch_ops"] = dict(ms_per_call=round(ms, 3), calls=n, **rates(ms),
+                                         fp32_pipe_fraction=round(B * flop / (ms * 1e-3) / (FP32_MATRIX_TFLOPS * 1e12), 4))
+                rows["max_abs_diff_hip_vs_torch"] = (hip("f32") - torch_forward(gen, z)).abs().max().item()
+            gen.precision = "f32"
         print(json.dumps(dict(B=B, T=Tn, gflop_per_utterance=round(flop / 1e9, 2), **rows)), flush=True)
 
 

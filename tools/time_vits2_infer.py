@@ -184,6 +184,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--only", choices=["sdp-hip"], default=None)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--split-f16", action="store_true", help='also time infer with precision = "split_f16" on enc_p, flow and dec together')
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.backends.cudnn.allow_tf32 = False
@@ -209,8 +210,16 @@ def main():
             sdp = rounds({"hip": lambda: net.dp(x, x_mask, reverse=True, noise_scale=0.8, noise=noise_w),
                           "torch_ops": lambda: torch_sdp_reverse(net.dp, x, x_mask, noise_w, 0.8)}, args.rounds)
             o_hip = V.infer(net, ids, lengths_d, noise_scale=0.667, length_scale=1.0, noise_scale_w=0.8, noise=(noise_w, None))[0]
-            inf = rounds({"hip": lambda: V.infer(net, ids, lengths_d, noise_scale=0.667, length_scale=1.0, noise_scale_w=0.8, noise=(noise_w, None)),
-                          "torch_dp_dense_path": lambda: torch_dp_infer(net, ids, lengths_d, noise_w)}, args.rounds)
+            def hip_infer(mode):
+                net.enc_p.precision = net.flow.precision = net.dec.precision = mode
+                return V.infer(net, ids, lengths_d, noise_scale=0.667, length_scale=1.0, noise_scale_w=0.8, noise=(noise_w, None))
+
+            def torch_dp_path():  # (its enc_p / flow / dec are the HIP ones: in exact fp32, whatever the variant before it set)
+                net.enc_p.precision = net.flow.precision = net.dec.precision = "f32"
+                return torch_dp_infer(net, ids, lengths_d, noise_w)
+
+            inf = rounds({"hip": lambda: hip_infer("f32"), **({"hip_split_f16": lambda: hip_infer("split_f16")} if args.split_f16 else {}),
+                          "torch_dp_dense_path": torch_dp_path}, args.rounds)
         row = dict(B=B, tokens=Tx, mean_tokens=float(lengths.float().mean()), frames=int(o_hip.shape[2] // 256),
                    sdp_logw_max_abs_diff_hip_vs_torch=float((lw_hip - lw_torch).abs().max()))
         for tag, res in (("sdp", sdp), ("infer", inf)):

@@ -202,6 +202,11 @@ FAMILIES = (
         "spectrogram": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
         "spec_to_mel": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
         "mel_spectrogram": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, sz, vp]),
+        # the generator with its arithmetic as a call argument: these take a ttsgen handle (vits2.GenEngine)
+        "generator_planes_bytes": (sz, [vp]),
+        "generator_pack_planes": (i32, [vp, vp, vp]),  # gen, planes, stream
+        "generator_workspace_bytes": (sz, [vp, i32, i32, i32]),  # (gen, precision, B, T)
+        "generator_forward": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]),  # gen, precision, planes, z, g, B, T, n_stages, out, ws, bytes, stream
     }),
     Family("ttsgen", GenDims, False, {
         "workspace_bytes": _ws_bytes,

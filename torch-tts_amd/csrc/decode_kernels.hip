@@ -48,20 +48,21 @@ struct LoaderConv {
   __device__ __forceinline__ unsigned row_off(int r, int) const { return (unsigned)r * (unsigned)Cin * EB; }
 };
 
-// ... and with dilation d (GemmArgs A_CONV_DIL; buffer-descriptor loads only): tap j of frame m reads frame m + (j - taps/2)*d, so
+// ... and with dilation d (GemmArgs A_CONV_DIL; buffer-descriptor loads only; xp: x, and for 16-bit elements the split-fp16 lo plane laid out like
+// it - no second member in the exact-fp32 form, whose kernels keep the code they had before the planes came): tap j of frame m reads frame m + (j - taps/2)*d, so
 // k = j*Cin + c sits at byte (k + j*(d-1)*Cin)*EB from the window's base.  When Cin is a multiple of the K tile KT, a tile lies in
 // one tap and the walk jumps (d-1)*Cin*EB every Cin/KT tiles (gemm_tile kTapJump); when Cin divides KT, a tile holds KT/Cin whole
 // taps: each tile advances KT*d elements and a lane adds its own column's tap offset once (col_off).
 template <int EB>
 struct LoaderConvDil {
-  const void* x;
+  const void* xp[EB == 2 ? 2 : 1];
   int m0, M, T, Cin, taps, K, d;  // d >= 1
   static constexpr bool kRange = true, kTapJump = true;
   __device__ __forceinline__ int nseg() const { return 1; }
   __device__ __forceinline__ int seglen(int i) const { return i == 0 ? K : 0; }
   __device__ __forceinline__ bool row_ok(int r) const { return m0 + r < M; }
-  __device__ __forceinline__ gbyte* row_ptr(int r, int, int) const {
-    return as_global(x) + (((long)(m0 + r) - (taps >> 1) * d) * Cin) * EB;
+  __device__ __forceinline__ gbyte* row_ptr(int r, int, int plane) const {
+    return as_global(xp[EB == 2 ? plane : 0]) + (((long)(m0 + r) - (taps >> 1) * d) * Cin) * EB;
   }
   // valid taps of frame t: 0 <= t + (j - taps/2)*d < T
   __device__ __forceinline__ int k_lo(int r) const {
@@ -78,8 +79,8 @@ struct LoaderConvDil {
   __device__ __forceinline__ long tile_inc(int rowb) const { return Cin < rowb / EB ? (long)rowb * d : rowb; }
   __device__ __forceinline__ int tap_tiles(int kt) const { return Cin >= kt ? Cin / kt : 0x7fffffff; }
   __device__ __forceinline__ unsigned tap_jump(int) const { return (unsigned)((d - 1) * Cin * EB); }
-  __device__ __forceinline__ const void* seg_base(int, int) const {
-    return static_cast<const char*>(x) + ((long)m0 - (taps >> 1) * d) * Cin * EB;
+  __device__ __forceinline__ const void* seg_base(int, int plane) const {
+    return static_cast<const char*>(xp[EB == 2 ? plane : 0]) + ((long)m0 - (taps >> 1) * d) * Cin * EB;
   }
   __device__ __forceinline__ unsigned row_off(int r, int) const { return (unsigned)r * (unsigned)Cin * EB; }
 };
@@ -211,7 +212,8 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void gemm_rows_ke
 
   constexpr int EB = Cfg::EB;
   if constexpr (AK == A_CONV_DIL) {
-    const LoaderConvDil<EB> la{g.a.p0, m0, g.M, g.T, g.Cin, g.taps, g.K, g.dil > 1 ? g.dil : 1};
+    LoaderConvDil<EB> la{{g.a.p0}, m0, g.M, g.T, g.Cin, g.taps, g.K, g.dil > 1 ? g.dil : 1};
+    if constexpr (EB == 2) la.xp[1] = g.a_lo.p0;
     const LoaderW<EB> lb{make_seg1(g.W, g.ldw, g.K), make_seg1(g.W_lo, g.ldw, g.K), n0, g.N};
     gemm_tile<Cfg, LoaderConvDil<EB>, LoaderW<EB>, NoGate, 2>(la, lb, smem, live);
   } else if (AK == A_CONV) {
@@ -357,6 +359,9 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void gemm_rows_ke
       if (g.div != 0.f) v = div_rn(v, g.div);
       if (g.out != nullptr) g.out[o] = v;
       if (g.out2 != nullptr) g.out2[o] = v > 0.f ? v : mul_rn(v, g.slope2);
+      // (split-fp16 tiles only: the activated value as planes for the next conv - out_kind 1, below; the exact-fp32 tiles of
+      // the generator never write planes)
+      if constexpr (Cfg::kPrec != PREC_F32) store16(v > 0.f ? v : mul_rn(v, g.slope2));
     }
   }
   // the 16-bit copies in a loop of their own per kind: the kind is the same for every output, and tested per output it cut
@@ -451,6 +456,26 @@ static void launch_gemm_dil(const GemmArgs& a, hipStream_t st) {
   }
 }
 
+// ... and in split-fp16 (ttsvits_generator_forward): the 128 x 128 tile with full-depth stages (64 k) of launch_gemm_cfg for
+// N >= 128 and M >= 2048; below that the lean tiles, whose half-depth stages (32 k) let two workgroups share a CU - 64 x 64
+// (64 KiB), and 128 x 32 with three stages where N is 32 (20 KiB each: 64 KiB with the loaders' dummy slots, where four stages
+// would be 84).  These layers have short K (3 to 11 taps of 32 or 64 channels) and write up to three values per output, so one
+// workgroup's stores run beside the other's loads; on the full-depth 64 x 64 tile (128 KiB, one workgroup per CU) the 64- and
+// 32-channel stages were slower than in exact fp32.  TTSGEN_SPLIT_NO_LEAN=1 puts that tile back (measurement).
+static void launch_gemm_dil_f16s(const GemmArgs& a, hipStream_t st) {
+  constexpr int AK = A_CONV_DIL, EK = EPI_LRELU2;
+  static const bool lean = getenv("TTSGEN_SPLIT_NO_LEAN") == nullptr;
+  auto go = [&](auto cfg) {
+    using Cfg = decltype(cfg);
+    dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM);
+    hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
+  };
+  if (a.N >= 128 && a.M >= 2048) go(TileCfg<2, 2, 1, 2, PREC_F16S, 0, 2, 2, 0>{});
+  else if (!lean) go(TileCfg<2, 2, 1, 4, PREC_F16S>{});
+  else if (a.N <= 32) go(TileCfg<4, 1, 1, 3, PREC_F16S, 0, 1, 1, 1>{});
+  else go(TileCfg<2, 2, 1, 4, PREC_F16S, 0, 1, 1, 1>{});
+}
+
 template <int AK, int EK>
 static void launch_gemm_prec(const GemmArgs& a, hipStream_t st) {
   if (a.prec == PREC_F16S) return launch_gemm_cfg<AK, EK, PREC_F16S>(a, st);
@@ -462,6 +487,7 @@ void launch_gemm(const GemmArgs& a, AKind ak, EpiKind ek, hipStream_t st) {
   if (a.M <= 0 || a.N <= 0) return;
   if (ak == A_CONV_DIL) {
     if (ek == EPI_LRELU2 && a.prec == PREC_F32) launch_gemm_dil(a, st);
+    else if (ek == EPI_LRELU2 && a.prec == PREC_F16S) launch_gemm_dil_f16s(a, st);
     return;
   }
   if (ak == A_CONV && ek == EPI_BN_ISRU) return launch_gemm_prec<A_CONV, EPI_BN_ISRU>(a, st);

@@ -14,6 +14,12 @@
 //                    lrelu(x, 0.1), or lrelu(x, 0.01) after the last stage (models.py:963 has no slope argument)
 //   conv_post + tanh a streaming kernel, one output sample per lane, fixed summation order.
 // Utterances go in groups whose largest activation stays below 2 GiB (include/ttsdec.h): the workspace holds one group.
+//
+// Split-fp16 (ttsvits_generator_*, opt-in): the same launches with PREC_F16S tiles.  Only GEMM operands are split - the weights
+// once (ttsvits_generator_pack_planes: a split of the packed blob), every conv input by the epilogue that produces it (the
+// activated buffers Y / LX / H / LR then hold hi / lo fp16 planes instead of fp32; z by launch_split).  x, the branch's x', the
+// branch sum and the bias / cond / residual / sum / division chain stay fp32, in the exact path's order.  A layer the split tiles
+// do not cover (split_ok) keeps the exact tiles inside such a call and reads its input as fp32.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -37,11 +43,21 @@ struct GenBlob {  // offsets in floats
   size_t cond_w, cond_b;                    // [C0, gin], [C0]
   size_t total;
 };
+
+// the second blob (ttsvits_generator_pack_planes): the fp16 planes of the conv weights that run in split-fp16.  Offsets in floats;
+// a weight of n elements takes n floats - its hi plane, then its lo plane - in the packed (tap-major / polyphase) layout
+struct GenPlanes {
+  bool pre, up[TTSGEN_MAX_UP], res[TTSGEN_MAX_UP];  // conv_pre / ups[i] / the resblocks of stage i run in split-fp16
+  bool all;  // (never none: ups[0] reads upsample_initial_channel = 2 C_0 channels, a multiple of 8 whenever the dims are built)
+  size_t pre_w, up_w[TTSGEN_MAX_UP], rw[TTSGEN_MAX_UP][TTSGEN_MAX_RES][6];
+  size_t total;
+};
 }  // namespace
 
 struct ttsgen_handle : HandleBase {
   ttsgen_dims d;
   GenBlob bl;
+  GenPlanes pl;
 };
 
 namespace {
@@ -103,6 +119,36 @@ GenBlob make_layout(const ttsgen_dims& d) {
   return L;
 }
 
+// A conv runs in split-fp16 when its rows are whole 16-byte columns of fp16 (Cin % 8) and, dilated, when its taps line up with the
+// 64-k tiles of launch_gemm_dil_f16s (Cin | 64 or 64 | Cin; its 32-k tiles then line up too).  The resblocks of a stage
+// share their buffers, so they switch together: one dilation that fails keeps the whole stage exact.
+bool split_ok(int Cin, int dil) { return Cin % 8 == 0 && (dil == 1 || Cin % 64 == 0 || 64 % Cin == 0); }
+
+GenPlanes make_planes(const ttsgen_dims& d) {
+  GenPlanes P;
+  memset(&P, 0, sizeof(P));
+  Carver cv{nullptr};
+  const size_t C0 = d.upsample_initial_channel;
+  P.all = true;
+  auto note = [&](bool ok) { P.all = P.all && ok; return ok; };
+  if ((P.pre = note(split_ok(d.initial_channel, 1)))) P.pre_w = cv.take_off(C0 * 7 * d.initial_channel);
+  for (int i = 0; i < d.n_up; ++i) {
+    const size_t Ci = i == 0 ? C0 : chan(d, i - 1), Co = chan(d, i), u = d.up_rates[i];
+    if ((P.up[i] = note(split_ok((int)Ci, 1)))) P.up_w[i] = cv.take_off(u * Co * 3 * Ci);
+  }
+  for (int i = 0; i < d.n_up; ++i) {
+    const size_t C = chan(d, i);
+    bool ok = true;
+    for (int j = 0; j < d.n_res; ++j)
+      for (int l = 0; l < 3; ++l) ok = ok && split_ok((int)C, d.res_dilations[j][l]);
+    if (!(P.res[i] = note(ok))) continue;
+    for (int j = 0; j < d.n_res; ++j)
+      for (int c = 0; c < 6; ++c) P.rw[i][j][c] = cv.take_off(C * d.res_kernels[j] * C);
+  }
+  P.total = cv.off;
+  return P;
+}
+
 int n_tensors(const ttsgen_dims& d) { return 2 + 2 * d.n_up + 12 * d.n_up * d.n_res + 1 + (d.gin_channels > 0 ? 2 : 0); }
 
 // largest activation of one utterance, in floats (include/ttsdec.h)
@@ -136,12 +182,23 @@ int group_size(const ttsgen_dims& d, int B, int T) {
 // The workspace of one group of G utterances (carved as layout.h's Carver comment says).  Y: a stage's activated input (conv_pre's
 // output, then each stage's result; kept first: ttsgen_forward_stages reads it); X / LX: the upsampled x and lrelu(x); H: c1's
 // output; R / LR: the branch's running x' and lrelu(x'); condv: [G, C0] cond(g)
-struct GenWs { float *Y, *X, *LX, *H, *R, *LR, *condv; };
-GenWs carve_gen(Carver& cv, const ttsgen_dims& d, size_t G, int T) {
+//
+// Split-fp16 (pl != nullptr: the handle's GenPlanes): the same six buffers - the two fp16 planes of an
+// [M, N] activation take the bytes of its fp32 form, hi plane first - plus zp, the planes of z, and, when some layer stays exact,
+// tmp: an exact layer cannot write planes, so where a split layer reads its result the fp32 form goes to tmp and launch_split
+// makes the planes.  Planes do not sit at their fp32 element's bytes, so the last conv of a stage cannot turn the branch sum into
+// the next stage's input in place as the exact path does (there each element is read and written by one thread): the planes go
+// to LX, which no launch reads after the last branch's first conv, and Y and LX swap roles for the next stage.  A stage output
+// that is wanted as fp32 (the last stage, for conv_post; a ttsgen_forward_stages read-back; an exact next layer) is written in
+// place when Y is the first buffer and into LX, then the first buffer, otherwise: it always ends up at the start of the workspace.
+struct GenWs { float *Y, *X, *LX, *H, *R, *LR, *condv, *zp, *tmp; };
+GenWs carve_gen(Carver& cv, const ttsgen_dims& d, size_t G, int T, const GenPlanes* pl = nullptr) {
   const size_t F = G * utt_floats(d, T);
   GenWs w;
   w.Y = cv.take(F); w.X = cv.take(F); w.LX = cv.take(F); w.H = cv.take(F); w.R = cv.take(F); w.LR = cv.take(F);
   w.condv = cv.take(G * d.upsample_initial_channel);
+  w.zp = pl != nullptr && pl->pre ? cv.take(G * T * d.initial_channel) : nullptr;
+  w.tmp = pl != nullptr && !pl->all ? cv.take(F) : nullptr;
   return w;
 }
 
@@ -204,23 +261,59 @@ GemmArgs conv_args(const float* x, int M, int T, int Cin, int taps, int dil, con
   return g;
 }
 
-// the forward pass over one group of G utterances; n_stages < n_up stops early (ttsgen_forward_stages)
-void run_group(const ttsgen_handle* h, const float* z, const float* g, int G, int T, int n_stages, float* out, float* ws, hipStream_t st) {
+// the planes of an n-element tensor held in n floats: hi, then lo
+f16* plane_hi(const float* p) { return reinterpret_cast<f16*>(const_cast<float*>(p)); }
+f16* plane_lo(const float* p, size_t n) { return plane_hi(p) + n; }
+
+// the forward pass over one group of G utterances; n_stages < n_up stops early (ttsgen_forward_stages).  planes == nullptr: exact
+// fp32; else the handle's split layers (GenPlanes) take their weights from it and their inputs as planes
+void run_group(const ttsgen_handle* h, const float* planes, const float* z, const float* g, int G, int T, int n_stages, float* out, float* ws,
+               hipStream_t st) {
   const ttsgen_dims& d = h->d;
   const GenBlob& L = h->bl;
+  const GenPlanes none{};
+  const GenPlanes& P = planes != nullptr ? h->pl : none;
   const float* b = h->blob;
   Carver cv{ws};  // (the layout of THIS group: the last one may hold fewer utterances than the reported size is for)
-  const GenWs w = carve_gen(cv, d, G, T);
+  const GenWs w = carve_gen(cv, d, G, T, planes != nullptr ? &h->pl : nullptr);
   float *Y = w.Y, *X = w.X, *LX = w.LX, *H = w.H, *R = w.R, *LR = w.LR, *condv = w.condv;
   const int C0 = d.upsample_initial_channel;
+  // one conv: x as fp32, or (sp: a split layer) as the planes its producer left, with the weight planes at wp
+  auto conv = [&](bool sp, const float* x, int M, int Tx, int Cin, int taps, int dil, size_t w_off, size_t wp, size_t b_off, int N) {
+    GemmArgs a = conv_args(x, M, Tx, Cin, taps, dil, b + w_off, b + b_off, N);
+    if (sp) {
+      a.a = make_seg1(plane_hi(x), Cin, taps * Cin);
+      a.a_lo = make_seg1(plane_lo(x, (size_t)M * Cin), Cin, taps * Cin);
+      a.W = plane_hi(planes + wp);
+      a.W_lo = plane_lo(planes + wp, (size_t)N * taps * Cin);
+      a.prec = PREC_F16S;
+    }
+    return a;
+  };
+  // launches it with its activated output in dst: fp32, or the planes a split consumer reads (as_planes)
+  auto launch = [&](GemmArgs& a, float* dst, bool as_planes) {
+    const size_t n = (size_t)a.M * a.N;
+    if (!as_planes) {
+      a.out2 = dst;
+    } else if (a.prec == PREC_F16S) {
+      a.out_kind = 1;
+      a.out_h = plane_hi(dst);
+      a.out_l = plane_lo(dst, n);
+    } else {
+      a.out2 = w.tmp;  // (an exact layer in front of a split one)
+    }
+    launch_gemm(a, A_CONV_DIL, EPI_LRELU2, st);
+    if (as_planes && a.prec != PREC_F16S) launch_split(w.tmp, plane_hi(dst), plane_lo(dst, n), n, st);
+  };
   if (g != nullptr) launch_cond(g, b + L.cond_w, b + L.cond_b, condv, G, C0, d.gin_channels, st);
   // models.py:948-950: x = conv_pre(x) (+ cond(g)); the first stage reads lrelu(x, 0.1) (:953)
   {
-    GemmArgs a = conv_args(z, G * T, T, d.initial_channel, 7, 1, b + L.pre_w, b + L.pre_b, C0);
+    const size_t nz = (size_t)G * T * d.initial_channel;
+    if (P.pre) launch_split(z, plane_hi(w.zp), plane_lo(w.zp, nz), nz, st);
+    GemmArgs a = conv(P.pre, P.pre ? w.zp : z, G * T, T, d.initial_channel, 7, 1, L.pre_w, P.pre_w, L.pre_b, C0);
     a.rowvec = g != nullptr ? condv : nullptr;
-    a.out2 = Y;
     a.slope2 = n_stages == 0 && d.n_up == 0 ? kLreluLast : kLrelu;
-    launch_gemm(a, A_CONV_DIL, EPI_LRELU2, st);
+    launch(a, Y, n_stages > 0 && P.up[0]);
   }
   int Ts = T, Cin = C0;
   for (int i = 0; i < n_stages; ++i) {
@@ -228,40 +321,47 @@ void run_group(const ttsgen_handle* h, const float* z, const float* g, int G, in
     Ts *= u;
     const int M = G * Ts;
     const float slope_out = i == d.n_up - 1 ? kLreluLast : kLrelu;
+    const bool rs = P.res[i];
     // :954 x = ups[i](x): [G*Tin, u*C] = [G*Ts, C]; x and lrelu(x, 0.1) (the first layer of every branch, modules.py:298)
     {
-      GemmArgs a = conv_args(Y, G * Tin, Tin, Cin, 3, 1, b + L.up_w[i], b + L.up_b[i], u * C);
+      GemmArgs a = conv(P.up[i], Y, G * Tin, Tin, Cin, 3, 1, L.up_w[i], P.up_w[i], L.up_b[i], u * C);
       a.out = X;
-      a.out2 = LX;
-      launch_gemm(a, A_CONV_DIL, EPI_LRELU2, st);
+      launch(a, LX, rs);
     }
     // :955-962 xs = sum_j resblocks[i * n_res + j](x); x = xs / n_res.  The sum lives in Y (the stage input, dead once ups[i] has
-    // read it); the last branch turns it into the stage's activated output in place
+    // read it); the last branch turns it into the stage's activated output: in place, or - planes, and fp32 when Y is not the
+    // first buffer - into LX, which then becomes Y (carve_gen)
     float* Ssum = Y;
     for (int j = 0; j < d.n_res; ++j) {
       const int k = d.res_kernels[j];
       for (int l = 0; l < 3; ++l) {
         // modules.py:298-301: xt = c1(lrelu(x)); xt = lrelu(xt)
-        GemmArgs c1 = conv_args(l == 0 ? LX : LR, M, Ts, C, k, d.res_dilations[j][l], b + L.rw[i][j][l], b + L.rb[i][j][l], C);
-        c1.out2 = H;
-        launch_gemm(c1, A_CONV_DIL, EPI_LRELU2, st);
+        GemmArgs c1 = conv(rs, l == 0 ? LX : LR, M, Ts, C, k, d.res_dilations[j][l], L.rw[i][j][l], P.rw[i][j][l], L.rb[i][j][l], C);
+        launch(c1, H, rs);
         // :304-305: x = c2(xt) + x
-        GemmArgs c2 = conv_args(H, M, Ts, C, k, 1, b + L.rw[i][j][3 + l], b + L.rb[i][j][3 + l], C);
+        GemmArgs c2 = conv(rs, H, M, Ts, C, k, 1, L.rw[i][j][3 + l], P.rw[i][j][3 + l], L.rb[i][j][3 + l], C);
         c2.resid = l == 0 ? X : R;
         if (l < 2) {
           c2.out = R;
-          c2.out2 = LR;
+          launch(c2, LR, rs);
         } else {
           if (j > 0) c2.sum = Ssum;  // xs += rb_j(x)
           if (j == d.n_res - 1) {
             c2.div = (float)d.n_res;  // x = xs / num_kernels; then lrelu for the next stage / conv_post
-            c2.out2 = Ssum;
             c2.slope2 = slope_out;
+            const bool as_planes = i + 1 < n_stages && P.up[i + 1];
+            float* dst = !as_planes && Y == w.Y ? Ssum : LX;
+            launch(c2, dst, as_planes);
+            if (dst != Y) {
+              LX = Y;
+              Y = dst;
+            }
           } else {
             c2.out = Ssum;
+            c2.out2 = nullptr;
+            launch_gemm(c2, A_CONV_DIL, EPI_LRELU2, st);
           }
         }
-        launch_gemm(c2, A_CONV_DIL, EPI_LRELU2, st);
       }
     }
     Cin = C;
@@ -282,6 +382,7 @@ int ttsgen_create(const ttsgen_dims* dims, ttsgen_handle** out) {
   if (!h) return TTSDEC_ERR_INVALID_ARG;
   h->d = *dims;
   h->bl = make_layout(*dims);
+  h->pl = make_planes(*dims);
   h->device = current_device_or_minus1();
   *out = h;
   return TTSDEC_OK;
@@ -328,31 +429,36 @@ int ttsgen_pack_weights(ttsgen_handle* h, const float* const* src, int n_src, vo
 
 int ttsgen_bind_weights(ttsgen_handle* h, const void* blob) { return bind_blob(h, blob); }
 
-size_t ttsgen_workspace_bytes(const ttsgen_handle* h, int B, int T) {
+// the workspace of a call: exact fp32 (pl = nullptr), or split-fp16 with the handle's planes
+static size_t gen_ws_bytes(const ttsgen_handle* h, const GenPlanes* pl, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
   const int G = group_size(h->d, B, T);
   if (G < 1) return 0;
   Carver cv{nullptr};
-  carve_gen(cv, h->d, G, T);
+  carve_gen(cv, h->d, G, T, pl);
   return cv.bytes();
 }
 
-static int gen_call(ttsgen_handle* h, const float* z, const float* g, int B, int T, int n_stages, float* out, void* workspace,
-                    size_t workspace_bytes, void* stream) {
+// planes != nullptr: split-fp16 (the handle has split layers)
+size_t ttsgen_workspace_bytes(const ttsgen_handle* h, int B, int T) { return gen_ws_bytes(h, nullptr, B, T); }
+
+static int gen_call(ttsgen_handle* h, const float* planes, const float* z, const float* g, int B, int T, int n_stages, float* out,
+                    void* workspace, size_t workspace_bytes, void* stream) {
   if (!h || !z || !workspace || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
   if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
   if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
   const int G = group_size(h->d, B, T);
   if (G < 1) return TTSDEC_ERR_DIMS;
   if (n_stages < h->d.n_up && G < B) return TTSDEC_ERR_INVALID_ARG;  // (the stage read-back holds one group)
-  if (workspace_bytes < ttsgen_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (workspace_bytes < gen_ws_bytes(h, planes != nullptr ? &h->pl : nullptr, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255))
+    return TTSDEC_ERR_WORKSPACE;
   if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   size_t up_all = 1;
   for (int i = 0; i < h->d.n_up; ++i) up_all *= h->d.up_rates[i];
   for (int b0 = 0; b0 < B; b0 += G) {
     const int n = B - b0 < G ? B - b0 : G;
-    run_group(h, z + (size_t)b0 * T * h->d.initial_channel, g != nullptr ? g + (size_t)b0 * h->d.gin_channels : nullptr, n, T, n_stages,
+    run_group(h, planes, z + (size_t)b0 * T * h->d.initial_channel, g != nullptr ? g + (size_t)b0 * h->d.gin_channels : nullptr, n, T, n_stages,
               out != nullptr ? out + (size_t)b0 * T * up_all : nullptr, static_cast<float*>(workspace), st);
   }
   return record_hip_error(h, "forward");
@@ -361,13 +467,57 @@ static int gen_call(ttsgen_handle* h, const float* z, const float* g, int B, int
 int ttsgen_forward(ttsgen_handle* h, const float* z, const float* g, int B, int T, float* out, void* workspace, size_t workspace_bytes,
                    void* stream) {
   if (!out) return TTSDEC_ERR_INVALID_ARG;
-  return gen_call(h, z, g, B, T, h ? h->d.n_up : 0, out, workspace, workspace_bytes, stream);
+  return gen_call(h, nullptr, z, g, B, T, h ? h->d.n_up : 0, out, workspace, workspace_bytes, stream);
 }
 
 int ttsgen_forward_stages(ttsgen_handle* h, const float* z, const float* g, int B, int T, int n_stages, void* workspace, size_t workspace_bytes,
                           void* stream) {
   if (!h || n_stages < 0 || n_stages > h->d.n_up) return TTSDEC_ERR_INVALID_ARG;
-  return gen_call(h, z, g, B, T, n_stages, nullptr, workspace, workspace_bytes, stream);
+  return gen_call(h, nullptr, z, g, B, T, n_stages, nullptr, workspace, workspace_bytes, stream);
+}
+
+// ---- the same forward with the arithmetic as a call argument (include/ttsdec.h) ----
+size_t ttsvits_generator_planes_bytes(const ttsgen_handle* h) { return h ? h->pl.total * sizeof(float) : 0; }
+
+int ttsvits_generator_pack_planes(ttsgen_handle* h, void* planes, void* stream) {
+  if (!h) return TTSDEC_ERR_INVALID_ARG;
+  if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
+  if (!planes) return TTSDEC_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(planes) & 255) return TTSDEC_ERR_WORKSPACE;
+  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ttsgen_dims& d = h->d;
+  const GenBlob& L = h->bl;
+  const GenPlanes& P = h->pl;
+  const float* b = h->blob;
+  float* p = static_cast<float*>(planes);
+  auto split = [&](size_t src, size_t dst, size_t n) { launch_split(b + src, plane_hi(p + dst), plane_lo(p + dst, n), n, st); };
+  const size_t C0 = d.upsample_initial_channel;
+  if (P.pre) split(L.pre_w, P.pre_w, C0 * 7 * d.initial_channel);
+  for (int i = 0; i < d.n_up; ++i) {
+    const size_t Ci = i == 0 ? C0 : chan(d, i - 1), C = chan(d, i), u = d.up_rates[i];
+    if (P.up[i]) split(L.up_w[i], P.up_w[i], u * C * 3 * Ci);
+    for (int j = 0; j < d.n_res && P.res[i]; ++j)
+      for (int c = 0; c < 6; ++c) split(L.rw[i][j][c], P.rw[i][j][c], C * d.res_kernels[j] * C);
+  }
+  return record_hip_error(h, "pack_planes");
+}
+
+size_t ttsvits_generator_workspace_bytes(const ttsgen_handle* h, int precision, int B, int T) {
+  if (!h || (precision != TTSDEC_PREC_F32 && precision != TTSDEC_PREC_SPLIT_F16)) return 0;
+  return gen_ws_bytes(h, precision == TTSDEC_PREC_SPLIT_F16 ? &h->pl : nullptr, B, T);
+}
+
+int ttsvits_generator_forward(ttsgen_handle* h, int precision, const void* planes, const float* z, const float* g, int B, int T, int n_stages,
+                              float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!h || (precision != TTSDEC_PREC_F32 && precision != TTSDEC_PREC_SPLIT_F16)) return TTSDEC_ERR_INVALID_ARG;
+  if (n_stages < 0 || n_stages > h->d.n_up) return TTSDEC_ERR_INVALID_ARG;
+  const bool split = precision == TTSDEC_PREC_SPLIT_F16;
+  if (split && !planes) return TTSDEC_ERR_INVALID_ARG;
+  if (split && (reinterpret_cast<uintptr_t>(planes) & 255)) return TTSDEC_ERR_WORKSPACE;
+  // (out is only looked at by the full forward: with fewer stages, or with out == NULL, the call is the stage read-back)
+  return gen_call(h, split ? static_cast<const float*>(planes) : nullptr, z, g, B, T, n_stages, n_stages == h->d.n_up ? out : nullptr, workspace,
+                  workspace_bytes, stream);
 }
 
 }  // extern "C"

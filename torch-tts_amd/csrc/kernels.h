@@ -8,7 +8,7 @@
 namespace ttsdec {
 
 // ---- generic row-GEMM (PreNet layers, query projection, mel/stop projection, postnet) ----
-// A_CONV_DIL: A_CONV with dilation `dil` (exact fp32, EPI_LRELU2 only; the HiFi-GAN generator, generator.hip)
+// A_CONV_DIL: A_CONV with dilation `dil` (exact fp32 or split-fp16, EPI_LRELU2 only; the HiFi-GAN generator, generator.hip)
 enum AKind { A_PLAIN = 0, A_CONV = 1, A_CONV_DIL = 2 };
 enum EpiKind { EPI_PLAIN = 0, EPI_RELU_DROPOUT = 1, EPI_PROJ = 2, EPI_BN_ISRU = 3, EPI_RESIDUAL = 4, EPI_BN_LRELU = 5, EPI_BN_ISRLU = 6, EPI_GENERIC = 7,
                EPI_LRELU2 = 8 };
@@ -18,7 +18,8 @@ struct GemmArgs {
   // A_CONV: implicit im2col of x [Bc*T, Cin] with `taps` taps centred on the row's frame:
   //         A[m][tap*Cin + c] = x[b, t + tap - taps/2, c] (zero outside [0, T)).
   // A_CONV_DIL: A[m][tap*Cin + c] = x[b, t + (tap - taps/2)*d, c], d = max(dil, 1) (below; padding get_padding(k, d) =
-  //         d(k-1)/2 keeps the conv centred); needs Cin % 4 == 0 and, for d > 1, Cin | 32 or 32 | Cin (the K tile of its tiles).
+  //         d(k-1)/2 keeps the conv centred); needs Cin % 4 == 0 and, for d > 1, Cin | 32 or 32 | Cin (the K tile of its tiles); in
+  //         split-fp16 Cin % 8 == 0 and, for d > 1, Cin | 64 or 64 | Cin.
   Seg3 a;
   Seg3 a_lo;            // second plane of A (split-fp16 lo), same shape; 16-bit modes only
   int T, Cin, taps;
@@ -77,7 +78,7 @@ struct GemmArgs {
   int t;  // absolute step index when ctrl == nullptr
   // A_CONV_DIL: the dilation (0 and 1 both mean none, so a zero-initialised GemmArgs stays an undilated conv)
   int dil;
-  // EPI_LRELU2 (exact fp32; the HiFi-GAN generator's layers, generator.hip):
+  // EPI_LRELU2 (the HiFi-GAN generator's layers, generator.hip; split-fp16 tiles also store out2's value as planes, out_kind 1):
   //   v = acc + bias[n];  v = v + rowvec[(m / T) * N + n]  (rowvec: one row per utterance, e.g. cond(g));
   //   v = v + resid[m, n];  v = sum[m, n] + v;  v = v / div  (a true division; div = 0: none);
   //   out[m, n] = v;  out2[m, n] = leaky_relu(v, slope2) = v > 0 ? v : v * slope2.

@@ -34,7 +34,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import EngineCache, Handle, PackedWeightsMixin, _require_device, _stream
+from .engine import EngineCache, Handle, PackedWeightsMixin, _ptr, _require_device, _stream
 
 
 def speaker_rows(g: Optional[torch.Tensor], B: int, gin_channels: int, owner: str) -> Optional[torch.Tensor]:
@@ -475,6 +475,14 @@ class ResBlock1(nn.Module):
         return out
 
 
+def _precision_code(mode: str) -> int:
+    """"f32" / "split_f16" -> TTSDEC_PREC_*; anything else is a ValueError."""
+    try:
+        return {"f32": _lib.PREC_F32, "split_f16": _lib.PREC_SPLIT_F16}[mode]
+    except (KeyError, TypeError):
+        raise ValueError(f'precision must be "f32" or "split_f16", got {mode!r}') from None
+
+
 class GenEngine(Handle):
     """One ttsgen handle on one device."""
 
@@ -498,24 +506,40 @@ class GenEngine(Handle):
         d.gin_channels = dims["gin_channels"]
         super().__init__(dims, d, device)
         self.up_total = math.prod(dims["upsample_rates"])
+        self._planes: Optional[torch.Tensor] = None  # the split-fp16 weight planes (ttsvits_generator_pack_planes) ...
+        self._planes_of = None                       # ... and the fp32 blob they were split from
 
-    def forward(self, z_cl: torch.Tensor, g: Optional[torch.Tensor], n_stages: Optional[int] = None) -> torch.Tensor:
+    def planes(self) -> torch.Tensor:
+        """The fp16 planes of the bound fp32 blob: built on the first split-fp16 call, rebuilt after every repack (a repack makes
+        a new blob tensor)."""
+        nbytes = int(self._lib.ttsvits_generator_planes_bytes(self._h))
+        if self._planes is None or self._planes_of is not self.blob:
+            with torch.cuda.device(self.device):
+                planes = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                rc = self._lib.ttsvits_generator_pack_planes(self._h, planes.data_ptr(), _stream(self.device))
+            self._err(rc, "ttsvits_generator_pack_planes")
+            self._planes, self._planes_of = planes, self.blob
+        return self._planes
+
+    def forward(self, z_cl: torch.Tensor, g: Optional[torch.Tensor], n_stages: Optional[int] = None, precision: str = "f32") -> torch.Tensor:
         """z_cl [B, T, C] channel-last fp32 -> [B, T * prod(u)]; n_stages (test aid): the activated output of that many stages,
-        [B * T_s, C_s], read from the workspace (ttsgen_forward_stages)."""
+        [B * T_s, C_s], read from the workspace; precision "f32" or "split_f16" (ttsvits_generator_forward)."""
         B, T, _ = z_cl.shape
-        nbytes = int(self._lib.ttsgen_workspace_bytes(self._h, B, T))
+        prec = _precision_code(precision)
+        planes = self.planes() if prec == _lib.PREC_SPLIT_F16 else None
+        nbytes = int(self._lib.ttsvits_generator_workspace_bytes(self._h, prec, B, T))
         if nbytes == 0:
             raise NotImplementedError(f"one utterance of {T} frames exceeds the generator's 2-GiB group bound")
         ws = self.workspace("forward", nbytes)
         gp = g.data_ptr() if g is not None else None
+        n_up = len(self.dims["upsample_rates"])
         with torch.cuda.device(self.device):
-            if n_stages is None:
-                out = torch.empty(B, T * self.up_total, device=self.device)
-                rc = self._lib.ttsgen_forward(self._h, z_cl.data_ptr(), gp, B, T, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
-                self._err(rc, "ttsgen_forward")
-                return out
-            rc = self._lib.ttsgen_forward_stages(self._h, z_cl.data_ptr(), gp, B, T, n_stages, ws.data_ptr(), ws.numel(), _stream(self.device))
-        self._err(rc, "ttsgen_forward_stages")
+            out = torch.empty(B, T * self.up_total, device=self.device) if n_stages is None else None
+            rc = self._lib.ttsvits_generator_forward(self._h, prec, _ptr(planes), z_cl.data_ptr(), gp, B, T, n_up if n_stages is None else n_stages,
+                                                     _ptr(out), ws.data_ptr(), ws.numel(), _stream(self.device))
+        self._err(rc, "ttsvits_generator_forward")
+        if n_stages is None:
+            return out
         rates = self.dims["upsample_rates"][:n_stages]
         Ts = T * math.prod(rates)
         Cs = self.dims["upsample_initial_channel"] >> n_stages
@@ -525,7 +549,8 @@ class GenEngine(Handle):
 class Generator(PackedWeightsMixin, nn.Module):
     """models.Generator (models.py:900-974): same constructor, parameters and state-dict keys (weight-normalised ``ups`` and
     ``resblocks``; ``remove_weight_norm()`` turns them into plain ``weight``s, and both forms load and run).  ``forward(x
-    [B, C, T], g=None) -> [B, 1, T * prod(upsample_rates)]`` runs in the HIP library in exact fp32; inference only."""
+    [B, C, T], g=None) -> [B, 1, T * prod(upsample_rates)]`` runs in the HIP library, in exact fp32 unless ``precision`` is set to
+    "split_f16"; inference only."""
 
     def __init__(self, initial_channel, resblock, resblock_kernel_sizes, resblock_dilation_sizes, upsample_rates, upsample_initial_channel,
                  upsample_kernel_sizes, gin_channels=0):
@@ -557,6 +582,7 @@ class Generator(PackedWeightsMixin, nn.Module):
         if gin_channels != 0:
             self.cond = nn.Conv1d(gin_channels, upsample_initial_channel, 1)
         self._engines = EngineCache(GenEngine)
+        self.precision = "f32"  # arithmetic of the GEMMs: "f32" (the reference's own: exact fp32, default) or "split_f16" (two fp16 planes, opt-in)
 
     def remove_weight_norm(self):
         for l in self.ups:
@@ -578,6 +604,7 @@ class Generator(PackedWeightsMixin, nn.Module):
         return out
 
     def _engine(self, x: torch.Tensor) -> GenEngine:
+        _precision_code(self.precision)
         inference_only(self, "generator", x, fp32=True)
         eng = self._engines.get(self._cfg, x.device)
         eng.ensure_packed(self.weight_tensors, key_tensors=list(self.parameters()))
@@ -589,19 +616,19 @@ class Generator(PackedWeightsMixin, nn.Module):
     def forward(self, x, g=None):
         eng = self._engine(x)
         B = x.shape[0]
-        out = eng.forward(x.transpose(1, 2).contiguous(), self._speaker(g, B))  # (a copy also makes infer's sliced z contiguous)
+        out = eng.forward(x.transpose(1, 2).contiguous(), self._speaker(g, B), precision=self.precision)  # (a copy also makes infer's sliced z contiguous)
         return out.unsqueeze(1)
 
     def forward_cl(self, z_cl, g=None):
         """forward on channel-last z [B, T, C] -> [B, T * prod(upsample_rates)] (``infer`` chains it)."""
         eng = self._engine(z_cl)
-        return eng.forward(z_cl.contiguous(), self._speaker(g, z_cl.shape[0]))
+        return eng.forward(z_cl.contiguous(), self._speaker(g, z_cl.shape[0]), precision=self.precision)
 
     def stage_outputs(self, x, g=None, n_stages=0) -> torch.Tensor:
         """Test aid: the activated output of the first ``n_stages`` upsampling stages (0: conv_pre's), channel-last
         [B, T_s, C_s] - leaky_relu(x, 0.1), or 0.01 after the last stage."""
         eng = self._engine(x)
-        return eng.forward(x.transpose(1, 2).contiguous(), self._speaker(g, x.shape[0]), n_stages=n_stages)
+        return eng.forward(x.transpose(1, 2).contiguous(), self._speaker(g, x.shape[0]), n_stages=n_stages, precision=self.precision)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
