@@ -47,7 +47,8 @@ extern "C" {
  * ttsvits_mel_spectrogram, the spectrogram front-end; then ttsdec_griffinlim_workspace_bytes, ttsdec_mel_to_magnitude and
  * ttsdec_griffinlim, mel -> waveform for the Tacotron path; then ttsdec_mel_analysis_workspace_bytes and ttsdec_mel_analysis,
  * waveform -> dB spectrogram and mel for it; then ttsvits_generator_planes_bytes, _pack_planes, _workspace_bytes and _forward,
- * the generator with its arithmetic as a call argument.) */
+ * the generator with its arithmetic as a call argument; then ttsdec_resample_workspace_bytes and ttsdec_resample, sample-rate
+ * conversion in front of ttsdec_mel_analysis.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -675,6 +676,33 @@ size_t ttsdec_mel_analysis_workspace_bytes(const ttsdec_handle* h, int B, int n_
 int ttsdec_mel_analysis(ttsdec_handle* h, const float* wave, const int32_t* lengths, int B, int n_samples, const float* window, const float* fb,
                         int n_mels, int n_fft, int hop_length, int T, float* spec_db, float* mel_db, int32_t* frames_out, int32_t* status,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* Sample-rate conversion of a padded batch: torchaudio's functional.resample with its defaults (sinc_interp_hann), the first line of
+ * the reference's AudioFrontend.encode (tacotron/data/audio.py:55-58).  Weightless like the calls above; enqueues only.  Exact fp32.
+ * With g = gcd(orig_freq, new_freq), o = orig_freq / g, n = new_freq / g and lpw = lowpass_filter_width:
+ *     base  = min(o, n) * rolloff,   width = ceil(lpw * o / base),   taps = 2 * width + o
+ *     t     = clamp(base * ((k - width) / o - p / n), -lpw, +lpw)                          phase p < n, tap k < taps
+ *     K[p, k] = (base / o) * cos(t * pi / lpw / 2)^2 * (t == 0 ? 1 : sin(pi t) / (pi t))   in fp64, rounded once
+ *     y[blk * n + p] = sum_k K[p, k] * xp[blk * o + k]         xp: the utterance with width zeros in front of it and zeros after it
+ *   wave     [B, n_samples] fp32, one utterance per row; lengths [B] int32 samples of each (device), or NULL: every row is n_samples.
+ *            Samples at or past lengths[b] count as zero whatever the row holds there (they are never read).
+ *   out      [B, n_out] fp32: utterance b has ceil(n * len_b / o) samples (64-bit integers), exact zeros after them up to n_out;
+ *            lengths_out NULL, or [B] int32: those counts
+ *   status   NULL, or [1] int32 (device): 0, or 4 = lengths[b] > n_samples or more output than n_out (clamped)
+ *   workspace ttsdec_resample_workspace_bytes(...) = align256(4 * n * taps) bytes, 256-byte aligned: the table alone, which every call
+ *            rebuilds there in fp64 with one launch.  Where t is clamped the rounded K is an exact zero (cos(pi / 2)^2 ~ 4e-33), so the
+ *            table keeps, per phase, only the run of taps around width + o p / n that can be non-zero, and a sum runs over that run.
+ *   rolloff  is read as the 7-digit decimal that gives this float (0.99f as 0.99), in fp64 like everything else of the table
+ *   orig_freq != new_freq, both > 0; lowpass_filter_width >= 1; 0 < rolloff <= 1 (else TTSDEC_ERR_INVALID_ARG, as for B, n_samples or
+ *   n_out <= 0); o <= 1024, n <= 1024, taps <= 16384, B <= 65535, n_samples <= 2^30, n_out <= 2^30 (else TTSDEC_ERR_DIMS: 16001 ->
+ *   16000 would need a 1 GB table).  Sizes are checked before any pointer, then NULL pointers, then TTSDEC_ERR_WORKSPACE.
+ * Every output is one fp32 fma chain over its taps in tap order: deterministic, and every utterance gets bit for bit what it gets
+ * alone.  No atomics but the status word; no host synchronisation. */
+size_t ttsdec_resample_workspace_bytes(const ttsdec_handle* h, int orig_freq, int new_freq, int lowpass_filter_width, float rolloff);
+        /* 0: refused */
+int ttsdec_resample(ttsdec_handle* h, const float* wave, const int32_t* lengths, int B, int n_samples, int orig_freq, int new_freq,
+                    int lowpass_filter_width, float rolloff, float* out, int n_out, int32_t* lengths_out, int32_t* status,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * VITS2 HiFi-GAN generator (latent z -> waveform): Generator.forward, vits2/models.py:900-974, with ResBlock1.forward

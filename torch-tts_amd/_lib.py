@@ -178,6 +178,11 @@ FAMILIES = (
             i32, i32, i32, i32,                  # n_mels, n_fft, hop_length, T
             vp, vp, vp, vp, vp, sz, vp,          # spec_db, mel_db, frames_out, status, workspace, workspace_bytes, stream
         ]),
+        "resample_workspace_bytes": (sz, [vp, i32, i32, i32, f32]),  # (h, orig_freq, new_freq, lowpass_filter_width, rolloff)
+        "resample": (i32, [
+            vp, vp, vp, i32, i32, i32, i32, i32, f32,  # h, wave, lengths, B, n_samples, orig_freq, new_freq, lowpass_filter_width, rolloff
+            vp, i32, vp, vp, vp, sz, vp,               # out, n_out, lengths_out, status, workspace, workspace_bytes, stream
+        ]),
     }),
     Family("ttsenc", EncDims, True, {
         "workspace_bytes": _ws_bytes,

@@ -16,7 +16,12 @@ exact fp32, no fallback.  With the initial phase an explicit input the algorithm
 
 The analysis half, ``AudioFrontend.encode`` (data/audio.py:55-67: peak normalisation, ``Spectrogram(power=2, normalized=True)``,
 ``MelScale``, ``amplitude_to_DB``), is restated on torch ops in the same way (no resampling), and runs as HIP kernels on a padded
-batch through ``AudioFrontend.encode_native`` (ttsdec_mel_analysis, csrc/analysis.hip; tests/test_analysis_hip.py)."""
+batch through ``AudioFrontend.encode_native`` (ttsdec_mel_analysis, csrc/analysis.hip; tests/test_analysis_hip.py).
+
+Its first line, ``resample(wave, orig_freq=sr, new_freq=config.sample_rate)`` (data/audio.py:55-58), is ``resample`` here (torchaudio's
+``functional.resample`` with its defaults, restated on torch ops: the oracle when run in fp64) and ``resample_native`` on HIP
+(ttsdec_resample, csrc/resample.hip; tests/test_resample_hip.py); ``encode_native(..., sr=...)`` chains the two calls on the device,
+and ``xref_native`` gives the ``xref`` / ``xref_lengths`` pair of ``Tacotron.forward`` from a reference waveform at any rate."""
 from __future__ import annotations
 
 import math
@@ -116,6 +121,47 @@ def griffinlim(specgram: torch.Tensor, n_fft: int, hop_length: int, win_length: 
     return wave.reshape(shape[:-2] + wave.shape[-1:])
 
 
+def _resample_plan(orig_freq: int, new_freq: int, lowpass_filter_width: int, rolloff: float, who: str):
+    """(o, n, base, width, taps) of a rate pair: o / n the rates over their gcd, base = min(o, n) * rolloff the cutoff, width =
+    ceil(lowpass_filter_width * o / base), taps = 2 * width + o."""
+    if int(orig_freq) != orig_freq or int(new_freq) != new_freq or orig_freq <= 0 or new_freq <= 0:
+        raise ValueError(f"{who}: the rates must be positive integers, got {orig_freq} -> {new_freq}")
+    if int(lowpass_filter_width) != lowpass_filter_width or lowpass_filter_width < 1:
+        raise ValueError(f"{who}: lowpass_filter_width must be an integer >= 1, got {lowpass_filter_width}")
+    if not 0.0 < rolloff <= 1.0:
+        raise ValueError(f"{who}: rolloff must be in (0, 1], got {rolloff}")
+    g = math.gcd(int(orig_freq), int(new_freq))
+    o, n = int(orig_freq) // g, int(new_freq) // g
+    base = min(o, n) * rolloff
+    width = math.ceil(lowpass_filter_width * o / base)
+    return o, n, base, width, 2 * width + o
+
+
+def resample(wave: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> torch.Tensor:
+    """torchaudio.functional.resample with its defaults (``sinc_interp_hann``): wave [..., time] -> [..., ceil(n * time / o)], on
+    wave's device in wave's dtype.  The polyphase kernel [n, taps] is evaluated in fp64 and rounded once to that dtype; the filter is a
+    conv1d of stride o with n output channels, interleaved.  Equal rates return the input as it is."""
+    o, n, base, width, taps = _resample_plan(orig_freq, new_freq, lowpass_filter_width, rolloff, "resample")
+    if o == n:
+        return wave
+    if not wave.is_floating_point():
+        raise TypeError(f"resample: wave must be floating point, got {wave.dtype}")
+    lpw = lowpass_filter_width
+    idx = torch.arange(-width, width + o, dtype=torch.float64, device=wave.device)[None, None] / o
+    t = torch.arange(0, -n, -1, dtype=torch.float64, device=wave.device)[:, None, None] / n + idx
+    t = (t * base).clamp(-lpw, lpw)
+    window = torch.cos(t * math.pi / lpw / 2) ** 2
+    t = t * math.pi
+    kernel = torch.where(t == 0, torch.ones_like(t), torch.sin(t) / t) * (window * (base / o))
+    kernel = kernel.to(wave.dtype)
+    shape = wave.shape
+    x = wave.reshape(-1, shape[-1])
+    x = torch.nn.functional.pad(x, (width, width + o))
+    y = torch.nn.functional.conv1d(x[:, None], kernel, stride=o)  # [rows, n, blocks]
+    y = y.transpose(1, 2).reshape(x.shape[0], -1)[..., : -(-n * shape[-1] // o)]
+    return y.reshape(shape[:-1] + y.shape[-1:])
+
+
 class AudioFrontend:
     """data/audio.py's AudioFrontend: ``encode`` (waveform -> linear dB and mel dB), ``mel_inv`` (mel dB -> linear dB) and ``decode``
     (linear dB -> waveform by Griffin-Lim)."""
@@ -190,13 +236,21 @@ class AudioFrontend:
         M_db = amplitude_to_db(M, 10, 1e-12, 0)
         return D_db.mT, M_db.mT
 
-    def encode_native(self, wave: torch.Tensor, lengths=None, *, spectrogram: bool = True):
+    def encode_native(self, wave: torch.Tensor, lengths=None, *, spectrogram: bool = True, sr: Optional[int] = None):
         """``encode`` of every utterance of a padded batch in one call (ttsdec_mel_analysis, csrc/analysis.hip): wave [B, N] (or [N])
         fp32 on a ROCm device at the configured sample rate -> (D_db [B, T, n_freqs], M_db [B, T, n_mels], frames [B] int32),
         T = 1 + N // hop_length; for 1-D input the reference's 2-D shapes and a scalar count.  ``lengths`` ([B] samples, host or
         device): every utterance is normalised by its own peak and reflected at its own end, has 1 + length // hop_length frames and
-        exact zeros past them.  ``spectrogram=False`` leaves D_db out (None): it is 87 % of the bytes the call writes."""
+        exact zeros past them.  ``spectrogram=False`` leaves D_db out (None): it is 87 % of the bytes the call writes.  ``sr``: the
+        rate of ``wave`` and ``lengths``; one that differs from the configured rate sends the batch through ``resample_native`` first
+        (the two calls chain on the device, the analysis reads the resampled lengths, and every peak is taken after resampling, as the
+        reference has it); None or the configured rate is the call without it."""
         who = "AudioFrontend.encode_native"
+        if sr is not None and sr != self.config.sample_rate:
+            _check_native(wave, self.n_fft, self.config.hop_length, self.n_fft, who)
+            wave, lengths = resample_native(wave, sr, self.config.sample_rate, lengths)
+            if wave.dim() == 1:
+                lengths = None  # (the row is the utterance)
         _check_native(wave, self.n_fft, self.config.hop_length, self.n_fft, who)
         w2 = wave.unsqueeze(0) if wave.dim() == 1 else wave
         if w2.dim() != 2:
@@ -367,3 +421,56 @@ def synth_audio_native(y: torch.Tensor, audio_frontend: AudioFrontend, lengths=N
     fe = audio_frontend
     mag = fe.mel_to_magnitude(y, lengths)
     return griffinlim_native(mag, fe.n_fft, fe.config.hop_length, fe.n_fft, generator=generator, lengths=lengths, normalize=True)
+
+
+def resample_native(wave: torch.Tensor, orig_freq: int, new_freq: int, lengths=None, *, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """``resample`` of every utterance of a padded batch in one call (ttsdec_resample, csrc/resample.hip): wave [B, N] (or [N]) fp32 on
+    a ROCm device -> (out [B, n_out], lengths_out [B] int32), n_out = ceil(n * N / o); for 1-D input the 1-D wave and a scalar count.
+    ``lengths`` ([B] samples, a sequence, a host or a device tensor): samples at or past them are never read, utterance b has
+    ceil(n * lengths[b] / o) samples and exact zeros after them.  Equal rates return the input and its lengths."""
+    who = "resample_native"
+    o, n, _, _, taps = _resample_plan(orig_freq, new_freq, lowpass_filter_width, rolloff, who)
+    if o > 1024 or n > 1024 or taps > 16384:
+        raise _lib.DimsNotBuilt(_lib.ERR_DIMS, who, f"{orig_freq} -> {new_freq} Hz is {o} / {n} with {taps} taps: built for reduced rates <= 1024 "
+                                "and <= 16384 taps (the table has n * taps words)")
+    if wave.dtype != torch.float32:
+        raise NotImplementedError(f"{who} is exact fp32: got {wave.dtype}")
+    if not wave.is_cuda:
+        raise NotImplementedError(f"{who} runs on a ROCm device only: there is no CPU fallback")
+    w2 = wave.unsqueeze(0) if wave.dim() == 1 else wave
+    if w2.dim() != 2 or w2.shape[1] < 1:
+        raise ValueError(f"{who}: wave must be [B, N] or [N] with N >= 1, got {tuple(wave.shape)}")
+    dev = wave.device
+    B, N = w2.shape
+    if N > 1 << 30 or -(-n * N // o) > 1 << 30 or B > 65535:
+        raise _lib.DimsNotBuilt(_lib.ERR_DIMS, who, f"B = {B}, {N} samples: built for B <= 65535 and at most 2^30 samples in and out")
+    on_device = False
+    if lengths is None:
+        lens = None
+    elif isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if tuple(lengths.shape) != (B,):
+            raise ValueError(f"{who}: lengths must be [B] = [{B}], got {tuple(lengths.shape)}")
+        lens, on_device = lengths.to(device=dev, dtype=torch.int32).contiguous(), True
+    else:
+        host = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        if len(host) != B or any(v < 0 or v > N for v in host):
+            raise ValueError(f"{who}: lengths must be [B] = [{B}] sample counts in [0, {N}], got {host}")
+        lens = torch.tensor(host, dtype=torch.int32).to(dev)
+    if o == n:
+        counts = lens if lens is not None else torch.full((B,), N, dtype=torch.int32, device=dev)
+        return (wave, counts[0]) if wave.dim() == 1 else (wave, counts)
+    out, counts = _engine(dev).resample(w2.detach().contiguous(), lens, int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff),
+                                        -(-n * N // o), check=on_device)
+    return (out[0], counts[0]) if wave.dim() == 1 else (out, counts)
+
+
+def xref_native(frontend: AudioFrontend, wave: torch.Tensor, lengths=None, sr: Optional[int] = None):
+    """The reference-audio input of ``Tacotron.forward`` and the style encoders (inference.py ``--ref``): ``m_fwd`` of
+    ``encode_native(wave, lengths, spectrogram=False, sr=sr)`` -> (xref [B, T, n_mels], frames [B] int32), exact zeros at the frames
+    at or past each utterance's count (``m_fwd(0)`` is 1, so they are masked)."""
+    _, M_db, frames = frontend.encode_native(wave, lengths, spectrogram=False, sr=sr)
+    xref = m_fwd(M_db)
+    if M_db.dim() == 3:
+        live = torch.arange(M_db.shape[1], device=M_db.device)[None, :] < frames[:, None]
+        xref = torch.where(live[:, :, None], xref, torch.zeros_like(xref))
+    return xref, frames

@@ -329,6 +329,31 @@ class Engine(Handle):
             raise ValueError("an utterance is all zeros: it has no peak to normalise by")
         return spec, mel, frames
 
+    # ---- sample-rate conversion (weightless; audio.py holds the entry point) ----
+    def resample(self, wave: Tensor, lengths: Optional[Tensor], orig_freq: int, new_freq: int, lowpass_filter_width: int, rolloff: float,
+                 n_out: int, *, check: bool = False):
+        """wave [B, N] contiguous fp32, lengths [B] int32 (device) or None -> (out [B, n_out], lengths_out [B] int32)
+        (ttsdec_resample).  Enqueues only; check: read the status word back (one host sync) and raise for a length beyond the row."""
+        B, N = wave.shape
+        nbytes = int(self._lib.ttsdec_resample_workspace_bytes(self._h, orig_freq, new_freq, lowpass_filter_width, rolloff))
+        if not nbytes:
+            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsdec_resample", f"{orig_freq} -> {new_freq} Hz, lowpass_filter_width = {lowpass_filter_width}, "
+                                    f"rolloff = {rolloff}: built for reduced rates <= 1024 and <= 16384 taps")
+        ws = self.workspace("resample", nbytes)
+        out = torch.empty(B, n_out, device=self.device)
+        lengths_out = torch.empty(B, dtype=torch.int32, device=self.device)
+        status = torch.empty(1, dtype=torch.int32, device=self.device) if check else None
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsdec_resample(self._h, wave.data_ptr(), _ptr(lengths), B, N, orig_freq, new_freq, lowpass_filter_width, rolloff,
+                                           out.data_ptr(), n_out, lengths_out.data_ptr(), _ptr(status), ws.data_ptr(), ws.numel(),
+                                           _stream(self.device))
+        if rc == _lib.ERR_DIMS:
+            raise _lib.DimsNotBuilt(rc, "ttsdec_resample", f"B = {B}, {N} -> {n_out} samples: needs B <= 65535 and at most 2^30 samples")
+        self._err(rc, "ttsdec_resample")
+        if check and int(status.item()) & 4:
+            raise ValueError(f"an utterance's length exceeds the row's {N} samples")
+        return out, lengths_out
+
     # ---- workspaces ----
     def step_workspace(self, B: int, L: int) -> Tensor:
         key = (B, L)
