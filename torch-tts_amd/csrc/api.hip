@@ -66,23 +66,29 @@ namespace {
 
 constexpr int kMaxPostnetLayers = 8;
 
+constexpr size_t kAbsent = ~(size_t)0;  // offset of a form the blob does not hold of a matrix
+
+// One weight matrix [rows, cols] in every form the blob holds.  Offsets in floats; a 16-bit plane takes half a float per element.
+struct Mat {
+  size_t rows, cols;
+  int src;        // the tensor (TTSDEC_W_*) its planes and the range guard are made from, or -1: the blob's own fp32 copy (a repack)
+  size_t w;       // fp32
+  size_t h, l;    // split-fp16 hi / lo planes
+  size_t b;       // bf16 plane (the Postnet's matrices)
+  size_t ch, cl;  // hi / lo planes in the chunked layout (common.h Seg3 / launch_pack_lstm_chunked): the LSTMs' when chunk_ok(dims)
+  size_t n() const { return rows * cols; }
+  size_t plane() const { return (n() + 1) / 2; }  // floats of one 16-bit plane
+};
+
 struct BlobLayout {  // offsets in floats
-  size_t pre0_w, pre0_b, pre1_w, pre1_b, wq;
-  size_t pre0_h, pre0_l, pre1_h, pre1_l;  // split-fp16 planes of the PreNet weights
-  size_t pre0_ph, pre0_pl, pre1_ph, pre1_pl;  // the same in the frame kernel's lane order (launch_split_frame_order; layer 1 padded to 64 rows)
-  size_t wq_h, wq_l, proj_h, proj_l;      // ... of the query and mel/stop projection weights
-  size_t att_ih, att_hh, att_b, dec_ih, dec_hh, dec_b;
-  size_t att_ih_h, att_ih_l, att_hh_h, att_hh_l, dec_ih_h, dec_ih_l, dec_hh_h, dec_hh_l;  // split-fp16 planes
-  // the same planes in the chunked layout (common.h Seg3 / launch_pack_lstm_chunked), used when chunk_ok(dims)
-  size_t att_ih_ch, att_ih_cl, att_hh_ch, att_hh_cl, dec_ih_ch, dec_ih_cl, dec_hh_ch, dec_hh_cl;
+  Mat pre0, pre1, wq, att_ih, att_hh, dec_ih, dec_hh, proj;  // proj: [fc_mel ; fc_stop] stacked on the output axis (decoder.py:13-14)
+  Mat conv[kMaxPostnetLayers], fc;                           // MelPostnet
+  Mat p2[kMaxPostnetLayers][3];                              // MelPostnet2: per layer three Conv1dFix weights ...
+  size_t p2_alpha[kMaxPostnetLayers][2], p2_beta[kMaxPostnetLayers][2];  // ... and two folded BatchNorms
+  size_t conv_alpha[kMaxPostnetLayers], conv_beta[kMaxPostnetLayers];
+  size_t pre0_b, pre1_b, att_b, dec_b, proj_b;
+  size_t pre0_ph, pre0_pl, pre1_ph, pre1_pl;  // the PreNet planes in the frame kernel's lane order (launch_split_frame_order; layer 1 padded to 64 rows)
   size_t h0a, c0a, h0d, c0d;
-  size_t proj_w, proj_b;
-  size_t conv_w[kMaxPostnetLayers], conv_alpha[kMaxPostnetLayers], conv_beta[kMaxPostnetLayers];
-  size_t conv_wb[kMaxPostnetLayers], conv_wh[kMaxPostnetLayers], conv_wl[kMaxPostnetLayers];  // bf16 / split-fp16 planes
-  size_t fc_w, fc_wb, fc_wh, fc_wl;
-  // MelPostnet2: per layer three Conv1dFix weights (+ 16-bit planes) and two folded BatchNorms
-  size_t p2_w[kMaxPostnetLayers][3], p2_wb[kMaxPostnetLayers][3], p2_wh[kMaxPostnetLayers][3], p2_wl[kMaxPostnetLayers][3];
-  size_t p2_alpha[kMaxPostnetLayers][2], p2_beta[kMaxPostnetLayers][2];
   size_t wmax;  // [0] max |w| over the decoder matrices that have split-fp16 planes, [1] the same over the Postnet's
   size_t total;
 };
@@ -171,83 +177,72 @@ inline bool proj_regw_shapes(const ttsdec_handle* h) {
   const ttsdec_dims& d = h->d;
   return h->proj_regw && use_frame(d) && !((d.h_att | d.h_dec | d.d_ctx) & 7) && proj_split(proj_k(d)) > 0 && proj_n(d) <= 192;
 }
-inline bool proj_regw(const ttsdec_handle* h, int prec, int B) {
-  (void)B;
+inline bool proj_regw(const ttsdec_handle* h, int prec) {
   return proj_regw_shapes(h) && (prec || h->head_proj != 0);  // (exact fp32: as a head role - head_proj() - only)
 }
-inline int proj_parts(const ttsdec_handle* h, int prec, int B) {
-  return proj_regw(h, prec, B) ? proj_split(proj_k(h->d)) : split_of(proj_k(h->d), kProjSplit);
+inline int proj_parts(const ttsdec_handle* h, int prec) {
+  return proj_regw(h, prec) ? proj_split(proj_k(h->d)) : split_of(proj_k(h->d), kProjSplit);
 }
 
+// Every matrix's shape is stated here, once; the walk below is the blob: its order must not change.
 BlobLayout make_blob_layout(const ttsdec_dims& d) {
   BlobLayout L;
   memset(&L, 0, sizeof(L));
   Carver cv{nullptr};
-  L.wmax = cv.take_off(2);
   const size_t Ha = d.h_att, Hd = d.h_dec, D = d.d_ctx, P = d.d_pre, Mel = d.d_mel, R = d.r, Ph = pre_hidden(d);
-  L.pre0_w = cv.take_off(Ph * Mel);
-  L.pre0_b = cv.take_off(Ph);
-  L.pre1_w = cv.take_off(P * Ph);
-  L.pre1_b = cv.take_off(P);
-  L.wq = cv.take_off(D * (size_t)query_ld(d));
-  L.att_ih = cv.take_off(4 * Ha * (P + D));
-  L.att_hh = cv.take_off(4 * Ha * Ha);
-  L.att_b = cv.take_off(4 * Ha);
-  L.dec_ih = cv.take_off(4 * Hd * (Ha + D));
-  L.dec_hh = cv.take_off(4 * Hd * Hd);
-  L.dec_b = cv.take_off(4 * Hd);
-  // fp16 planes occupy half a float per element
-  L.pre0_h = cv.take_off((Ph * Mel + 1) / 2); L.pre0_l = cv.take_off((Ph * Mel + 1) / 2);
-  L.pre1_h = cv.take_off((P * Ph + 1) / 2); L.pre1_l = cv.take_off((P * Ph + 1) / 2);
-  L.pre0_ph = cv.take_off((Ph * Mel + 1) / 2); L.pre0_pl = cv.take_off((Ph * Mel + 1) / 2);
+  const size_t Hh = d.postnet_hidden, k = d.postnet_kernel;
+  auto mat = [](size_t rows, size_t cols, int src) { return Mat{rows, cols, src, kAbsent, kAbsent, kAbsent, kAbsent, kAbsent, kAbsent}; };
+  auto take_w = [&](Mat& m) { m.w = cv.take_off(m.n()); };
+  auto take_split = [&](Mat& m) { m.h = cv.take_off(m.plane()); m.l = cv.take_off(m.plane()); };
+  auto take_w16 = [&](Mat& m) { take_w(m); m.b = cv.take_off(m.plane()); take_split(m); };  // a Postnet matrix: w, wb, wh, wl
+  L.pre0 = mat(Ph, Mel, TTSDEC_W_PRE0_W);
+  L.pre1 = mat(P, Ph, TTSDEC_W_PRE1_W);
+  L.wq = mat(D, query_ld(d), TTSDEC_W_QUERY_W);
+  L.att_ih = mat(4 * Ha, P + D, TTSDEC_W_ATT_IH);
+  L.att_hh = mat(4 * Ha, Ha, TTSDEC_W_ATT_HH);
+  L.dec_ih = mat(4 * Hd, Ha + D, TTSDEC_W_DEC_IH);
+  L.dec_hh = mat(4 * Hd, Hd, TTSDEC_W_DEC_HH);
+  L.proj = mat(R * Mel + R, proj_ld(d), -1);
+  Mat* const lstm[4] = {&L.att_ih, &L.att_hh, &L.dec_ih, &L.dec_hh};
+
+  L.wmax = cv.take_off(2);
+  take_w(L.pre0); L.pre0_b = cv.take_off(Ph);
+  take_w(L.pre1); L.pre1_b = cv.take_off(P);
+  take_w(L.wq);
+  take_w(L.att_ih); take_w(L.att_hh); L.att_b = cv.take_off(4 * Ha);
+  take_w(L.dec_ih); take_w(L.dec_hh); L.dec_b = cv.take_off(4 * Hd);
+  take_split(L.pre0); take_split(L.pre1);
+  L.pre0_ph = cv.take_off(L.pre0.plane()); L.pre0_pl = cv.take_off(L.pre0.plane());
   const size_t p64 = (P + 63) / 64 * 64;
   L.pre1_ph = cv.take_off((p64 * Ph + 1) / 2); L.pre1_pl = cv.take_off((p64 * Ph + 1) / 2);
-  L.att_ih_h = cv.take_off(2 * Ha * (P + D)); L.att_ih_l = cv.take_off(2 * Ha * (P + D));
-  L.att_hh_h = cv.take_off(2 * Ha * Ha);      L.att_hh_l = cv.take_off(2 * Ha * Ha);
-  L.dec_ih_h = cv.take_off(2 * Hd * (Ha + D)); L.dec_ih_l = cv.take_off(2 * Hd * (Ha + D));
-  L.dec_hh_h = cv.take_off(2 * Hd * Hd);      L.dec_hh_l = cv.take_off(2 * Hd * Hd);
-  if (chunk_ok(d)) {
-    L.att_ih_ch = cv.take_off(2 * Ha * (P + D)); L.att_ih_cl = cv.take_off(2 * Ha * (P + D));
-    L.att_hh_ch = cv.take_off(2 * Ha * Ha);      L.att_hh_cl = cv.take_off(2 * Ha * Ha);
-    L.dec_ih_ch = cv.take_off(2 * Hd * (Ha + D)); L.dec_ih_cl = cv.take_off(2 * Hd * (Ha + D));
-    L.dec_hh_ch = cv.take_off(2 * Hd * Hd);      L.dec_hh_cl = cv.take_off(2 * Hd * Hd);
-  }
+  for (Mat* m : lstm) take_split(*m);
+  if (chunk_ok(d))
+    for (Mat* m : lstm) { m->ch = cv.take_off(m->plane()); m->cl = cv.take_off(m->plane()); }
   L.h0a = cv.take_off(Ha);
   L.c0a = cv.take_off(Ha);
   L.h0d = cv.take_off(Hd);
   L.c0d = cv.take_off(Hd);
-  L.proj_w = cv.take_off((R * Mel + R) * (size_t)proj_ld(d));
-  L.proj_b = cv.take_off(R * Mel + R);
-  L.wq_h = cv.take_off((D * (size_t)query_ld(d) + 1) / 2); L.wq_l = cv.take_off((D * (size_t)query_ld(d) + 1) / 2);
-  L.proj_h = cv.take_off(((R * Mel + R) * (size_t)proj_ld(d) + 1) / 2); L.proj_l = cv.take_off(((R * Mel + R) * (size_t)proj_ld(d) + 1) / 2);
-  size_t cin = Mel;
+  take_w(L.proj); L.proj_b = cv.take_off(R * Mel + R);
+  take_split(L.wq);
+  take_split(L.proj);
   if (d.postnet_type == TTSDEC_POSTNET_TYPE_MEL2) {
-    const size_t Hh = d.postnet_hidden, k = d.postnet_kernel;
     const size_t shapes[3][2] = {{Hh, Mel}, {Hh, Hh}, {Mel, Hh}};  // [C_out, C_in] of the three convs
     for (int i = 0; i < d.postnet_layers; ++i) {
-      for (int c = 0; c < 3; ++c) {
-        const size_t n = shapes[c][0] * shapes[c][1] * k;
-        L.p2_w[i][c] = cv.take_off(n);
-        L.p2_wb[i][c] = cv.take_off((n + 1) / 2); L.p2_wh[i][c] = cv.take_off((n + 1) / 2); L.p2_wl[i][c] = cv.take_off((n + 1) / 2);
-      }
+      for (int c = 0; c < 3; ++c) take_w16(L.p2[i][c] = mat(shapes[c][0], shapes[c][1] * k, -1));
       for (int c = 0; c < 2; ++c) { L.p2_alpha[i][c] = cv.take_off(Hh); L.p2_beta[i][c] = cv.take_off(Hh); }
     }
     L.total = cv.off;
     return L;
   }
   for (int i = 0; i < d.postnet_layers; ++i) {
-    L.conv_w[i] = cv.take_off((size_t)d.postnet_hidden * d.postnet_kernel * cin);
-    L.conv_alpha[i] = cv.take_off(d.postnet_hidden);
-    L.conv_beta[i] = cv.take_off(d.postnet_hidden);
-    const size_t nh = ((size_t)d.postnet_hidden * d.postnet_kernel * cin + 1) / 2;  // 16-bit plane, in floats
-    L.conv_wb[i] = cv.take_off(nh); L.conv_wh[i] = cv.take_off(nh); L.conv_wl[i] = cv.take_off(nh);
-    cin = d.postnet_hidden;
+    Mat& m = L.conv[i] = mat(Hh, k * (i ? Hh : Mel), -1);
+    take_w(m);
+    L.conv_alpha[i] = cv.take_off(Hh);
+    L.conv_beta[i] = cv.take_off(Hh);
+    m.b = cv.take_off(m.plane());
+    take_split(m);
   }
-  if (d.postnet_layers > 0) {
-    L.fc_w = cv.take_off(Mel * (size_t)d.postnet_hidden);
-    const size_t nh = (Mel * (size_t)d.postnet_hidden + 1) / 2;
-    L.fc_wb = cv.take_off(nh); L.fc_wh = cv.take_off(nh); L.fc_wl = cv.take_off(nh);
-  }
+  if (d.postnet_layers > 0) take_w16(L.fc = mat(Mel, Hh, TTSDEC_W_DECODER_COUNT + TTSDEC_W_POSTNET_PER_LAYER * d.postnet_layers));
   L.total = cv.off;
   return L;
 }
@@ -358,13 +353,41 @@ struct StepOrder {
 bool split_ok(const ttsdec_dims& d) { return !((d.d_pre | d.d_ctx | d.h_att | d.h_dec) & 7); }
 // launch order of one step: the Prod cell attends between its two LSTMs, the Taco2 cell after both
 const StepOrder& step_order(const ttsdec_handle* h, int B);
-bool head_proj(const ttsdec_handle* h, int B);
+bool head_proj(const ttsdec_handle* h);
 bool query_role(const ttsdec_handle* h, int B);
 int& option_ref(ttsdec_handle* h, int o);
 void apply_env_options(ttsdec_handle* h);
 void drop_graph(ttsdec_handle* h);
 int lstm_prec(const ttsdec_handle* h) {
   return (h->precision == TTSDEC_PREC_SPLIT_F16 && split_ok(h->d) && h->wmax_dec < kSplitMax) ? 1 : 0;
+}
+// rows per chunk of the activation planes when they are in the chunked layout (common.h Seg3), 0 = row-major
+int act_mpad(const ttsdec_handle* h, int B) { return (lstm_prec(h) && chunk_ok(h->d) && h->chunk_a) ? rows_pad(B) : 0; }
+
+// ---- GEMM operands by precision: fp32 | split-fp16 hi + lo planes | one bf16 plane ----
+struct Planes {  // what a GEMM reads as a / a_lo (fp32 and bf16: the same pointer twice)
+  const void *p0, *p1;
+};
+template <class Args>  // GemmArgs / ProjArgs
+void set_weight(Args& g, const Mat& m, const float* blob, int prec) {
+  g.W = blob + (prec == PREC_F16S ? m.h : (prec == PREC_BF16 ? m.b : m.w));
+  g.W_lo = prec == PREC_F16S ? blob + m.l : g.W;
+}
+// x [n] fp32 as a first layer reads it: x itself, or its 16-bit form made in buf
+Planes act_input(int prec, const float* x, char* buf, size_t n, hipStream_t st) {
+  if (prec == PREC_F32) return {x, x};
+  f16* p = reinterpret_cast<f16*>(buf);
+  if (prec == PREC_BF16) { launch_to_bf16(x, buf, n, st); return {p, p}; }
+  launch_split(x, p, p + n, n, st);
+  return {p, p + n};
+}
+// the result [n = M * N] of g goes to buf in the form of `prec`: -> as the next layer reads it.  (16-bit modes leave g.out alone.)
+Planes set_output(GemmArgs& g, int prec, char* buf, size_t n) {
+  if (prec == PREC_F32) { g.out = reinterpret_cast<float*>(buf); return {buf, buf}; }
+  g.out_kind = prec == PREC_F16S ? 1 : 2;
+  g.out_h = reinterpret_cast<f16*>(buf);
+  if (prec == PREC_F16S) g.out_l = g.out_h + n;
+  return {g.out_h, prec == PREC_F16S ? g.out_l : g.out_h};
 }
 
 // reads the two weight maxima back from the blob header (one small synchronous copy)
@@ -389,16 +412,36 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
   const float keep_scale = 1.0f / (1.0f - d.p_dropout);
   const int prec = lstm_prec(h);
   auto plane = [&](size_t float_off) { return reinterpret_cast<const f16*>(blob + float_off); };
-  // chunked operand layout of the split-fp16 planes (0 = row-major)
-  const int mpad = (prec && chunk_ok(d) && h->chunk_a) ? rows_pad(B) : 0;
+  const int mpad = act_mpad(h, B);
   auto act = [&](Seg3 s) { return chunked(s, mpad); };  // an activation-plane segment list in the layout in use
   auto dep = [&](int kind) { return sb.dep + (size_t)kind * sb.dep_blocks * kDepLine; };  // a hand-off kind's arrival counters
+  // An activation as a GEMM's a / a_lo: its (hi, lo) planes in the layout in use, or fp32 (twice).
+  struct Act {
+    Seg3 a, a_lo;
+  };
+  auto pick = [&](bool planes, Seg3 f32, Seg3 hi, Seg3 lo) { return planes ? Act{act(hi), act(lo)} : Act{f32, f32}; };
+  // cat[h_att, h_dec] of buffer parity q: the Taco2 cell's query and projection input, cat[h0, h1, zeros] (decoder_cell.py:126, :136)
+  auto h01_in = [&](int q, bool planes) {
+    return pick(planes, make_seg2(sb.h_att[q], Ha, Ha, sb.h_dec[q], Hd, Hd), make_seg2(sb.h_att_h[q], Ha, Ha, sb.h_dec_h[q], Hd, Hd),
+                make_seg2(sb.h_att_l[q], Ha, Ha, sb.h_dec_l[q], Hd, Hd));
+  };
+  // query_layer input: h_att (Prod, decoder_cell.py:188)
+  auto query_in = [&](int q, bool planes) {
+    if (is_taco2(d)) return h01_in(q, planes);
+    return pick(planes, make_seg1(sb.h_att[q], Ha, Ha), make_seg1(sb.h_att_h[q], Ha, Ha), make_seg1(sb.h_att_l[q], Ha, Ha));
+  };
+  // projection input: cat[h_dec, ctx] (Prod, decoder_cell.py:192)
+  auto proj_in = [&](int q, bool planes) {
+    if (is_taco2(d)) return h01_in(q, planes);
+    return pick(planes, make_seg2(sb.h_dec[q], Hd, Hd, sb.ctx, D, D), make_seg2(sb.h_dec_h[q], Hd, Hd, sb.ctx_h, D, D),
+                make_seg2(sb.h_dec_l[q], Hd, Hd, sb.ctx_l, D, D));
+  };
 
   auto frame_args = [&](bool fin_only) {
     FrameArgs f;
     memset(&f, 0, sizeof(f));
     const int Ph = pre_hidden(d);
-    f.parts = sb.jparts; f.n_parts = proj_parts(h, prec, B); f.ldp = proj_ldp(d);
+    f.parts = sb.jparts; f.n_parts = proj_parts(h, prec); f.ldp = proj_ldp(d);
     f.part_stride = (size_t)B * proj_ldp(d);
     f.proj_bias = blob + bl.proj_b;
     f.y_out = io.y; f.s_out = io.s; f.ynext = sb.ynext;
@@ -407,7 +450,7 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
     f.dbg = io.dbg;
     if (io.dbg & 1) f.finalize = 0;       // measurement ablations (profile_step only)
     if (io.dbg & 8) f.only_finalize = 1;
-    f.W0 = blob + bl.pre0_w; f.b0 = blob + bl.pre0_b; f.W1 = blob + bl.pre1_w; f.b1 = blob + bl.pre1_b;
+    f.W0 = blob + bl.pre0.w; f.b0 = blob + bl.pre0_b; f.W1 = blob + bl.pre1.w; f.b1 = blob + bl.pre1_b;
     f.W0h = plane(bl.pre0_ph); f.W0l = plane(bl.pre0_pl); f.W1h = plane(bl.pre1_ph); f.W1l = plane(bl.pre1_pl);  // (lane order)
     f.prec = prec ? PREC_F16S : PREC_F32;
     f.Ph = Ph; f.P = P;
@@ -439,12 +482,9 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
     }
     x1 = prec ? (const void*)sb.ctx_h : sb.ctx; x1l = prec ? (const void*)sb.ctx_l : sb.ctx;
     const bool ck = prec && chunk_ok(d) && h->chunk_b;
-    const size_t o_ih_h = which ? (ck ? bl.dec_ih_ch : bl.dec_ih_h) : (ck ? bl.att_ih_ch : bl.att_ih_h);
-    const size_t o_ih_l = which ? (ck ? bl.dec_ih_cl : bl.dec_ih_l) : (ck ? bl.att_ih_cl : bl.att_ih_l);
-    const size_t o_hh_h = which ? (ck ? bl.dec_hh_ch : bl.dec_hh_h) : (ck ? bl.att_hh_ch : bl.att_hh_h);
-    const size_t o_hh_l = which ? (ck ? bl.dec_hh_cl : bl.dec_hh_l) : (ck ? bl.att_hh_cl : bl.att_hh_l);
-    const f16 *wih_h = plane(o_ih_h), *wih_l = plane(o_ih_l), *whh_h = plane(o_hh_h), *whh_l = plane(o_hh_l);
-    const float *wih = blob + (which ? bl.dec_ih : bl.att_ih), *whh = blob + (which ? bl.dec_hh : bl.att_hh);
+    const Mat &ih = which ? bl.dec_ih : bl.att_ih, &hh = which ? bl.dec_hh : bl.att_hh;
+    const f16 *wih_h = plane(ck ? ih.ch : ih.h), *wih_l = plane(ck ? ih.cl : ih.l), *whh_h = plane(ck ? hh.ch : hh.h), *whh_l = plane(ck ? hh.cl : hh.l);
+    const float *wih = blob + ih.w, *whh = blob + hh.w;
     // column k0 of W_ih: row-major + k0 elements; chunked: chunk k0 / 32 of unit block 0 = k0 / 32 * (64 rows * 32) elements
     const size_t w1_off = ck ? (size_t)k0 * 64 : (size_t)k0;
     auto W0 = [&](bool lo) { return prec ? (const void*)(lo ? wih_l : wih_h) : (const void*)wih; };
@@ -515,13 +555,9 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
     ProjArgs pq;
     memset(&pq, 0, sizeof(pq));
     pq.prec = prec ? PREC_F16S : PREC_F32;
-    if (prec) {
-      pq.a = act(make_seg1(sb.h_att_h[1 - p], Ha, Ha)); pq.a_lo = act(make_seg1(sb.h_att_l[1 - p], Ha, Ha));
-      pq.W = plane(bl.wq_h); pq.W_lo = plane(bl.wq_l);
-    } else {
-      pq.a = make_seg1(sb.h_att[1 - p], Ha, Ha);
-      pq.W = blob + bl.wq;
-    }
+    const Act in = query_in(1 - p, prec != 0);
+    pq.a = in.a; pq.a_lo = in.a_lo;
+    set_weight(pq, bl.wq, blob, pq.prec);
     pq.ldw = query_ld(d); pq.M = B; pq.N = D; pq.K = query_k(d); pq.ksplit = proj_split(pq.K);
     pq.split_stride = (size_t)B * D; pq.out = sb.q; pq.ldo = D; pq.ctrl = ctrl; pq.slot = io.slot; pq.mode = PROJ_QUERY;
     pq.dep_cnt = dep(DEP_QUERY);
@@ -534,19 +570,6 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
     a.q_tiles = proj_grid_size(B, D, pq.ksplit); a.q_wait_n = proj_grid_size(32, D, pq.ksplit); a.q_cnt = pq.dep_cnt;
     return a;
   };
-  // the mel/stop projection on the register-weight kernel, split-fp16 Prod cell: cat[h_dec, ctx] of buffer parity 1 - pp
-  auto head_proj_args = [&](int pp, int mode) {
-    ProjArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.a = act(make_seg2(sb.h_dec_h[1 - pp], Hd, Hd, sb.ctx_h, D, D));
-    pa.a_lo = act(make_seg2(sb.h_dec_l[1 - pp], Hd, Hd, sb.ctx_l, D, D));
-    pa.W = plane(bl.proj_h); pa.W_lo = plane(bl.proj_l); pa.ldw = proj_ld(d); pa.prec = PREC_F16S;
-    pa.M = B; pa.N = proj_n(d); pa.K = proj_k(d); pa.ksplit = proj_parts(h, prec, B); pa.split_stride = (size_t)B * proj_ldp(d);
-    pa.out = sb.jparts; pa.ldo = proj_ldp(d); pa.ctrl = ctrl; pa.slot = io.slot; pa.node = io.node_pos;
-    pa.mode = mode;
-    return pa;
-  };
-
   const int attn_variant = h->attn_form > 0 ? h->attn_form : 0;  // (measurement: fused_kernels.hip attn_lstm_f32_wide)
   switch (node) {
     case N_F:
@@ -588,11 +611,11 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
       const int Ph = pre_hidden(d);
       if (layer == 0) {
         g.a = make_seg1(sb.ynext, d.d_mel, d.d_mel);
-        g.W = blob + bl.pre0_w; g.ldw = d.d_mel; g.K = d.d_mel; g.bias = blob + bl.pre0_b;
+        g.W = blob + bl.pre0.w; g.ldw = d.d_mel; g.K = d.d_mel; g.bias = blob + bl.pre0_b;
         g.out = sb.xpre0; g.N = Ph; g.ldo = Ph;
       } else {
         g.a = make_seg1(sb.xpre0, Ph, Ph);
-        g.W = blob + bl.pre1_w; g.ldw = Ph; g.K = Ph; g.bias = blob + bl.pre1_b;
+        g.W = blob + bl.pre1.w; g.ldw = Ph; g.K = Ph; g.bias = blob + bl.pre1_b;
         g.out = sb.xpre; g.N = P; g.ldo = P;
         if (prec) { g.out_h = sb.xpre_h; g.out_l = sb.xpre_l; g.out_kind = 1; }
       }
@@ -611,21 +634,11 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
     case N_Q: {
       GemmArgs g;
       memset(&g, 0, sizeof(g));
-      // query_layer input: h_att (Prod, decoder_cell.py:188) or cat[h0, h1, zeros] (Taco2, :126)
-      if (is_taco2(d)) g.a = make_seg2(sb.h_att[1 - p], Ha, Ha, sb.h_dec[1 - p], Hd, Hd);
-      else g.a = make_seg1(sb.h_att[1 - p], Ha, Ha);
-      g.W = blob + bl.wq; g.ldw = query_ld(d); g.K = query_k(d); g.M = B; g.N = D; g.out = sb.q; g.ldo = D;
-      if (prec) {  // split-fp16 planes: the LSTM epilogues emitted them for h, the pack step for the weights
-        g.prec = PREC_F16S;
-        g.W = plane(bl.wq_h); g.W_lo = plane(bl.wq_l);
-        if (is_taco2(d)) {
-          g.a = act(make_seg2(sb.h_att_h[1 - p], Ha, Ha, sb.h_dec_h[1 - p], Hd, Hd));
-          g.a_lo = act(make_seg2(sb.h_att_l[1 - p], Ha, Ha, sb.h_dec_l[1 - p], Hd, Hd));
-        } else {
-          g.a = act(make_seg1(sb.h_att_h[1 - p], Ha, Ha));
-          g.a_lo = act(make_seg1(sb.h_att_l[1 - p], Ha, Ha));
-        }
-      }
+      // (split-fp16 planes: the LSTM epilogues emitted them for h, the pack step for the weights)
+      const Act in = query_in(1 - p, prec != 0);
+      g.a = in.a; g.a_lo = in.a_lo; g.prec = prec ? PREC_F16S : PREC_F32;
+      set_weight(g, bl.wq, blob, g.prec);
+      g.ldw = query_ld(d); g.K = query_k(d); g.M = B; g.N = D; g.out = sb.q; g.ldo = D;
       g.ksplit = query_split(d); g.kchunk = g.K / g.ksplit; g.split_stride = (size_t)B * D;
       g.ctrl = ctrl; g.slot = io.slot; g.node = io.node_pos; g.t = io.t;
       launch_gemm(g, A_PLAIN, EPI_PLAIN, st);
@@ -639,29 +652,14 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
       // step t-1's outputs are this step's "previous" buffers.  N_JFIN: io.slot carries the last step's parity.
       const bool head = node == N_JFA || node == N_JF;
       const int p = head ? 1 - ((io.use_ctrl ? io.slot : io.t) & 1) : ((io.use_ctrl ? io.slot : io.t) & 1);
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      // projection input: cat[h_dec, ctx] (Prod, decoder_cell.py:192) or cat[h0, h1, zeros] (Taco2, :136)
-      if (is_taco2(d)) g.a = make_seg2(sb.h_att[1 - p], Ha, Ha, sb.h_dec[1 - p], Hd, Hd);
-      else g.a = make_seg2(sb.h_dec[1 - p], Hd, Hd, sb.ctx, D, D);
-      g.W = blob + bl.proj_w; g.ldw = proj_ld(d); g.K = proj_k(d); g.M = B; g.N = proj_n(d);
-      g.ctrl = ctrl; g.slot = io.slot; g.node = io.node_pos; g.t = io.t;
-      if (prec && use_frame(d)) {
-        g.prec = PREC_F16S;
-        g.W = plane(bl.proj_h); g.W_lo = plane(bl.proj_l);
-        if (is_taco2(d)) {
-          g.a = act(make_seg2(sb.h_att_h[1 - p], Ha, Ha, sb.h_dec_h[1 - p], Hd, Hd));
-          g.a_lo = act(make_seg2(sb.h_att_l[1 - p], Ha, Ha, sb.h_dec_l[1 - p], Hd, Hd));
-        } else {
-          g.a = act(make_seg2(sb.h_dec_h[1 - p], Hd, Hd, sb.ctx_h, D, D));
-          g.a_lo = act(make_seg2(sb.h_dec_l[1 - p], Hd, Hd, sb.ctx_l, D, D));
-        }
-      }
-      if (proj_regw(h, prec, B)) {  // (same slabs, from the kernel that keeps its weight fragments in registers)
+      const int jprec = (prec && use_frame(d)) ? PREC_F16S : PREC_F32;  // (the three-launch form keeps the projection on fp32)
+      const Act in = proj_in(1 - p, jprec != PREC_F32);
+      if (proj_regw(h, prec)) {  // (same slabs, from the kernel that keeps its weight fragments in registers)
         ProjArgs pa;
         memset(&pa, 0, sizeof(pa));
-        pa.a = g.a; pa.a_lo = g.a_lo; pa.W = g.W; pa.W_lo = g.W_lo; pa.ldw = g.ldw; pa.prec = g.prec;
-        pa.M = B; pa.N = g.N; pa.K = g.K; pa.ksplit = proj_parts(h, prec, B); pa.split_stride = (size_t)B * proj_ldp(d);
+        pa.a = in.a; pa.a_lo = in.a_lo; pa.ldw = proj_ld(d); pa.prec = jprec;
+        set_weight(pa, bl.proj, blob, jprec);
+        pa.M = B; pa.N = proj_n(d); pa.K = proj_k(d); pa.ksplit = proj_parts(h, prec); pa.split_stride = (size_t)B * proj_ldp(d);
         pa.out = sb.jparts; pa.ldo = proj_ldp(d); pa.ctrl = ctrl; pa.slot = io.slot; pa.node = io.node_pos;
         pa.mode = head ? PROJ_HEAD : (node == N_JFIN ? PROJ_FINAL : PROJ_STEP);
         if (head) {
@@ -680,6 +678,12 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
         }
         break;
       }
+      GemmArgs g;
+      memset(&g, 0, sizeof(g));
+      g.a = in.a; g.a_lo = in.a_lo; g.prec = jprec;
+      set_weight(g, bl.proj, blob, jprec);
+      g.ldw = proj_ld(d); g.K = proj_k(d); g.M = B; g.N = proj_n(d);
+      g.ctrl = ctrl; g.slot = io.slot; g.node = io.node_pos; g.t = io.t;
       if (use_frame(d)) {
         // raw split-K partial sums; bias, leaky-ReLU, y / s / stop rule happen in the next frame kernel
         g.out = sb.jparts; g.ldo = proj_ldp(d);
@@ -748,8 +752,7 @@ int overlap_level(const ttsdec_handle* h, int B) {
 // Round 3: also where the step runs one role per launch (N_JF: [proj | frame]) - us per step without / with it
 // (profiles/r03_w_head_proj_level0.txt): exact fp32 B = 64 76.5 / 74.7, B = 128 103.0 / 100.9; sandra config (two frames per
 // step) 63.4 / 63.3, B = 1 44.3 / 44.1 - the hop costs there what the launch did.
-bool head_proj(const ttsdec_handle* h, int B) {
-  (void)B;
+bool head_proj(const ttsdec_handle* h) {
   return proj_regw_shapes(h) && h->head_proj != 0;  // (-1 = default = on)
 }
 // The query as a job of the attention role (fused_kernels.hip attn_lstm_kernel): needs every attention-role workgroup resident
@@ -778,14 +781,20 @@ bool query_role(const ttsdec_handle* h, int B) {
 const StepOrder& step_order(const ttsdec_handle* h, int B) {
   const ttsdec_dims& d = h->d;
   if (const int lv = overlap_level(h, B)) {
-    if (is_taco2(d)) return head_proj(h, B) ? kOrderTaco2H : kOrderTaco2O;
-    if (lv >= 2 && query_role(h, B)) return head_proj(h, B) ? kOrderProdH2Q : kOrderProdO2Q;
-    if (head_proj(h, B)) return lv >= 2 ? kOrderProdH2 : kOrderProdH;
+    if (is_taco2(d)) return head_proj(h) ? kOrderTaco2H : kOrderTaco2O;
+    if (lv >= 2 && query_role(h, B)) return head_proj(h) ? kOrderProdH2Q : kOrderProdO2Q;
+    if (head_proj(h)) return lv >= 2 ? kOrderProdH2 : kOrderProdH;
     return lv >= 2 ? kOrderProdO2 : kOrderProdO;
   }
-  if (use_frame(d) && head_proj(h, B)) return is_taco2(d) ? kOrderTaco2HF : kOrderProdHF;
+  if (use_frame(d) && head_proj(h)) return is_taco2(d) ? kOrderTaco2HF : kOrderProdHF;
   if (use_frame(d)) return is_taco2(d) ? kOrderTaco2F : kOrderProdF;
   return is_taco2(d) ? kOrderTaco2 : kOrderProd;
+}
+
+bool has_two_role_node(const StepOrder& order) {
+  for (int i = 0; i < order.n; ++i)
+    if (order.nodes[i] == N_FA || order.nodes[i] == N_JFA || order.nodes[i] == N_TD || order.nodes[i] == N_QTD) return true;
+  return false;
 }
 
 // One step on a single stream, in the reference's order.  (For the Taco2 cell the attention
@@ -994,64 +1003,55 @@ int ttsdec_pack_weights(ttsdec_handle* h, const float* const* src, int n_src, vo
   const ttsdec_dims& d = h->d;
   const BlobLayout& L = h->bl;
   float* b = static_cast<float*>(blob);
-  const size_t Ha = d.h_att, Hd = d.h_dec, D = d.d_ctx, P = d.d_pre, Mel = d.d_mel, R = d.r, Ph = pre_hidden(d);
-  const size_t Dp = proj_ld(d);
-  launch_copy(src[TTSDEC_W_PRE0_W], b + L.pre0_w, Ph * Mel, st);
-  launch_copy(src[TTSDEC_W_PRE0_B], b + L.pre0_b, Ph, st);
-  launch_copy(src[TTSDEC_W_PRE1_W], b + L.pre1_w, P * Ph, st);
-  launch_copy(src[TTSDEC_W_PRE1_B], b + L.pre1_b, P, st);
-  launch_copy(src[TTSDEC_W_QUERY_W], b + L.wq, D * (size_t)query_ld(d), st);
-  launch_copy(src[TTSDEC_W_ATT_IH], b + L.att_ih, 4 * Ha * (P + D), st);
-  launch_copy(src[TTSDEC_W_ATT_HH], b + L.att_hh, 4 * Ha * Ha, st);
+  const size_t Ha = d.h_att, Hd = d.h_dec, Mel = d.d_mel, R = d.r, Dp = proj_ld(d);
+  auto hp = [&](size_t float_off) { return reinterpret_cast<f16*>(b + float_off); };
+  auto from = [&](const Mat& m) { return m.src < 0 ? b + m.w : src[m.src]; };
+  // every 16-bit form the record holds (a NULL source: none, like launch_copy) ...
+  auto planes = [&](const Mat& m) {
+    launch_split(from(m), hp(m.h), hp(m.l), m.n(), st);
+    if (m.b != kAbsent) launch_to_bf16(from(m), b + m.b, m.n(), st);
+    if (m.ch != kAbsent) launch_pack_lstm_chunked(from(m), hp(m.ch), hp(m.cl), (int)(m.rows / 4), (int)m.cols, st);
+  };
+  // ... and the range guard of the split-fp16 planes: max |w| of every matrix that has them, the decoder's into wmax[0], the Postnet's into [1]
+  auto guard = [&](const Mat& m, int which) { launch_absmax(from(m), m.n(), b + L.wmax + which, st); };
+  const Mat* const dec[7] = {&L.pre0, &L.pre1, &L.wq, &L.att_ih, &L.att_hh, &L.dec_ih, &L.dec_hh};
+  for (const Mat* m : dec) {
+    launch_copy(src[m->src], b + m->w, m->n(), st);
+    planes(*m);
+    guard(*m, 0);
+  }
+  launch_copy(src[TTSDEC_W_PRE0_B], b + L.pre0_b, L.pre0.rows, st);
+  launch_copy(src[TTSDEC_W_PRE1_B], b + L.pre1_b, L.pre1.rows, st);
   if (src[TTSDEC_W_ATT_BIH] && src[TTSDEC_W_ATT_BHH])
     launch_add_vec(src[TTSDEC_W_ATT_BIH], src[TTSDEC_W_ATT_BHH], b + L.att_b, (int)(4 * Ha), st);
-  launch_copy(src[TTSDEC_W_DEC_IH], b + L.dec_ih, 4 * Hd * (Ha + D), st);
-  launch_copy(src[TTSDEC_W_DEC_HH], b + L.dec_hh, 4 * Hd * Hd, st);
   if (src[TTSDEC_W_DEC_BIH] && src[TTSDEC_W_DEC_BHH])
     launch_add_vec(src[TTSDEC_W_DEC_BIH], src[TTSDEC_W_DEC_BHH], b + L.dec_b, (int)(4 * Hd), st);
-  auto hp = [&](size_t float_off) { return reinterpret_cast<f16*>(b + float_off); };
-  launch_split(src[TTSDEC_W_PRE0_W], hp(L.pre0_h), hp(L.pre0_l), Ph * Mel, st);
-  launch_split(src[TTSDEC_W_PRE1_W], hp(L.pre1_h), hp(L.pre1_l), P * Ph, st);
   if (use_frame(d)) {  // (the frame kernel's shapes: frame_supported - d_mel = 80, Ph = 128 or 256)
-    launch_split_frame_order(src[TTSDEC_W_PRE0_W], hp(L.pre0_ph), hp(L.pre0_pl), (int)Ph, (int)Mel, 0, st);
-    launch_split_frame_order(src[TTSDEC_W_PRE1_W], hp(L.pre1_ph), hp(L.pre1_pl), (int)P, (int)Ph, 1, st);
-  }
-  launch_split(src[TTSDEC_W_ATT_IH], hp(L.att_ih_h), hp(L.att_ih_l), 4 * Ha * (P + D), st);
-  launch_split(src[TTSDEC_W_ATT_HH], hp(L.att_hh_h), hp(L.att_hh_l), 4 * Ha * Ha, st);
-  launch_split(src[TTSDEC_W_DEC_IH], hp(L.dec_ih_h), hp(L.dec_ih_l), 4 * Hd * (Ha + D), st);
-  launch_split(src[TTSDEC_W_DEC_HH], hp(L.dec_hh_h), hp(L.dec_hh_l), 4 * Hd * Hd, st);
-  if (chunk_ok(d)) {
-    launch_pack_lstm_chunked(src[TTSDEC_W_ATT_IH], hp(L.att_ih_ch), hp(L.att_ih_cl), (int)Ha, (int)(P + D), st);
-    launch_pack_lstm_chunked(src[TTSDEC_W_ATT_HH], hp(L.att_hh_ch), hp(L.att_hh_cl), (int)Ha, (int)Ha, st);
-    launch_pack_lstm_chunked(src[TTSDEC_W_DEC_IH], hp(L.dec_ih_ch), hp(L.dec_ih_cl), (int)Hd, (int)(Ha + D), st);
-    launch_pack_lstm_chunked(src[TTSDEC_W_DEC_HH], hp(L.dec_hh_ch), hp(L.dec_hh_cl), (int)Hd, (int)Hd, st);
+    launch_split_frame_order(src[TTSDEC_W_PRE0_W], hp(L.pre0_ph), hp(L.pre0_pl), (int)L.pre0.rows, (int)L.pre0.cols, 0, st);
+    launch_split_frame_order(src[TTSDEC_W_PRE1_W], hp(L.pre1_ph), hp(L.pre1_pl), (int)L.pre1.rows, (int)L.pre1.cols, 1, st);
   }
   launch_copy(src[TTSDEC_W_INIT_H0], b + L.h0a, Ha, st);
   launch_copy(src[TTSDEC_W_INIT_C0], b + L.c0a, Ha, st);
   launch_copy(src[TTSDEC_W_INIT_H1], b + L.h0d, Hd, st);
   launch_copy(src[TTSDEC_W_INIT_C1], b + L.c0d, Hd, st);
-  // [fc_mel ; fc_stop] stacked on the output axis (decoder.py:13-14)
-  launch_copy(src[TTSDEC_W_MEL_W], b + L.proj_w, R * Mel * Dp, st);
-  launch_copy(src[TTSDEC_W_STOP_W], b + L.proj_w + R * Mel * Dp, R * Dp, st);
+  // [fc_mel ; fc_stop] stacked on the output axis; the planes need both, the guard reads whatever was stacked
+  launch_copy(src[TTSDEC_W_MEL_W], b + L.proj.w, R * Mel * Dp, st);
+  launch_copy(src[TTSDEC_W_STOP_W], b + L.proj.w + R * Mel * Dp, R * Dp, st);
   launch_copy(src[TTSDEC_W_MEL_B], b + L.proj_b, R * Mel, st);
   launch_copy(src[TTSDEC_W_STOP_B], b + L.proj_b + R * Mel, R, st);
-  launch_split(src[TTSDEC_W_QUERY_W], hp(L.wq_h), hp(L.wq_l), D * (size_t)query_ld(d), st);
-  if (src[TTSDEC_W_MEL_W] && src[TTSDEC_W_STOP_W])
-    launch_split(b + L.proj_w, hp(L.proj_h), hp(L.proj_l), (R * Mel + R) * Dp, st);
-  int cin = d.d_mel;
+  if (src[TTSDEC_W_MEL_W] && src[TTSDEC_W_STOP_W]) planes(L.proj);
+  guard(L.proj, 0);
+  const int Hh = d.postnet_hidden, k = d.postnet_kernel;
   if (d.postnet_type == TTSDEC_POSTNET_TYPE_MEL2) {
-    const int Hh = d.postnet_hidden, k = d.postnet_kernel;
-    const int shapes[3][2] = {{Hh, (int)Mel}, {Hh, Hh}, {(int)Mel, Hh}};
     for (int i = 0; i < d.postnet_layers; ++i) {
       // per layer: conv1.w, bn1.{w,b,mean,var}, conv2.w, bn2.{w,b,mean,var}, conv3.w
       const float* const* ps = src + TTSDEC_W_DECODER_COUNT + TTSDEC_W_POSTNET2_PER_LAYER * i;
-      const int conv_idx[3] = {0, 5, 10};
       for (int c = 0; c < 3; ++c) {
-        if (!ps[conv_idx[c]]) return TTSDEC_ERR_INVALID_ARG;
-        const size_t n = (size_t)shapes[c][0] * shapes[c][1] * k;
-        launch_conv1dfix_pack(ps[conv_idx[c]], b + L.p2_w[i][c], shapes[c][0], shapes[c][1], k, st);
-        launch_split(b + L.p2_w[i][c], hp(L.p2_wh[i][c]), hp(L.p2_wl[i][c]), n, st);
-        launch_to_bf16(b + L.p2_w[i][c], b + L.p2_wb[i][c], n, st);
+        const Mat& m = L.p2[i][c];
+        if (!ps[5 * c]) return TTSDEC_ERR_INVALID_ARG;
+        launch_conv1dfix_pack(ps[5 * c], b + m.w, (int)m.rows, (int)m.cols / k, k, st);
+        planes(m);
+        guard(m, 1);
       }
       for (int c = 0; c < 2; ++c) {
         const float* const* bn = ps + 1 + 5 * c;
@@ -1059,50 +1059,19 @@ int ttsdec_pack_weights(ttsdec_handle* h, const float* const* src, int n_src, vo
         launch_bn_fold(bn[0], bn[1], bn[2], bn[3], d.bn_eps, b + L.p2_alpha[i][c], b + L.p2_beta[i][c], Hh, st);
       }
     }
-  } else
-  for (int i = 0; i < d.postnet_layers; ++i) {
-    const float* const* ps = src + TTSDEC_W_DECODER_COUNT + TTSDEC_W_POSTNET_PER_LAYER * i;
-    if (!ps[0] || !ps[1] || !ps[2] || !ps[3] || !ps[4]) return TTSDEC_ERR_INVALID_ARG;
-    launch_conv_transpose(ps[0], b + L.conv_w[i], d.postnet_hidden, cin, d.postnet_kernel, st);
-    {
-      const size_t n = (size_t)d.postnet_hidden * d.postnet_kernel * cin;
-      launch_split(b + L.conv_w[i], hp(L.conv_wh[i]), hp(L.conv_wl[i]), n, st);
-      launch_to_bf16(b + L.conv_w[i], b + L.conv_wb[i], n, st);
+  } else if (d.postnet_layers > 0) {
+    for (int i = 0; i < d.postnet_layers; ++i) {
+      const float* const* ps = src + TTSDEC_W_DECODER_COUNT + TTSDEC_W_POSTNET_PER_LAYER * i;
+      const Mat& m = L.conv[i];
+      if (!ps[0] || !ps[1] || !ps[2] || !ps[3] || !ps[4]) return TTSDEC_ERR_INVALID_ARG;
+      launch_conv_transpose(ps[0], b + m.w, Hh, (int)m.cols / k, k, st);
+      planes(m);
+      guard(m, 1);
+      launch_bn_fold(ps[1], ps[2], ps[3], ps[4], d.bn_eps, b + L.conv_alpha[i], b + L.conv_beta[i], Hh, st);
     }
-    launch_bn_fold(ps[1], ps[2], ps[3], ps[4], d.bn_eps, b + L.conv_alpha[i], b + L.conv_beta[i], d.postnet_hidden, st);
-    cin = d.postnet_hidden;
-  }
-  if (d.postnet_layers > 0 && d.postnet_type == TTSDEC_POSTNET_TYPE_MEL) {
-    const float* fc = src[TTSDEC_W_DECODER_COUNT + TTSDEC_W_POSTNET_PER_LAYER * d.postnet_layers];
-    const size_t n = Mel * (size_t)d.postnet_hidden;
-    launch_copy(fc, b + L.fc_w, n, st);
-    launch_split(fc, hp(L.fc_wh), hp(L.fc_wl), n, st);
-    launch_to_bf16(fc, b + L.fc_wb, n, st);
-  }
-  // range guard of the split-fp16 planes: max |w| of every matrix that has them
-  {
-    float* wm = b + L.wmax;
-    launch_absmax(src[TTSDEC_W_PRE0_W], Ph * Mel, wm, st);
-    launch_absmax(src[TTSDEC_W_PRE1_W], P * Ph, wm, st);
-    launch_absmax(src[TTSDEC_W_ATT_IH], 4 * Ha * (P + D), wm, st);
-    launch_absmax(src[TTSDEC_W_ATT_HH], 4 * Ha * Ha, wm, st);
-    launch_absmax(src[TTSDEC_W_DEC_IH], 4 * Hd * (Ha + D), wm, st);
-    launch_absmax(src[TTSDEC_W_DEC_HH], 4 * Hd * Hd, wm, st);
-    launch_absmax(src[TTSDEC_W_QUERY_W], D * (size_t)query_ld(d), wm, st);
-    launch_absmax(b + L.proj_w, (R * Mel + R) * Dp, wm, st);
-    if (d.postnet_type == TTSDEC_POSTNET_TYPE_MEL2) {
-      const size_t Hh = d.postnet_hidden, k = d.postnet_kernel;
-      const size_t n3[3] = {Hh * Mel * k, Hh * Hh * k, Mel * Hh * k};
-      for (int i = 0; i < d.postnet_layers; ++i)
-        for (int c = 0; c < 3; ++c) launch_absmax(b + L.p2_w[i][c], n3[c], wm + 1, st);
-    } else {
-      size_t ci = Mel;
-      for (int i = 0; i < d.postnet_layers; ++i) {
-        launch_absmax(b + L.conv_w[i], (size_t)d.postnet_hidden * d.postnet_kernel * ci, wm + 1, st);
-        ci = d.postnet_hidden;
-      }
-      if (d.postnet_layers > 0) launch_absmax(b + L.fc_w, Mel * (size_t)d.postnet_hidden, wm + 1, st);
-    }
+    launch_copy(src[L.fc.src], b + L.fc.w, L.fc.n(), st);
+    planes(L.fc);
+    guard(L.fc, 1);
   }
   rc = pack_end(h, b);
   if (rc != TTSDEC_OK) return rc;
@@ -1158,7 +1127,7 @@ static int decode_impl(ttsdec_handle* h, const float* memory, int B, int L, int 
     ia.ctx = sb.ctx; ia.w = sb.w[0]; ia.ynext = sb.ynext;
     ia.h_att_h = sb.h_att_h[0]; ia.h_att_l = sb.h_att_l[0]; ia.h_dec_h = sb.h_dec_h[0]; ia.h_dec_l = sb.h_dec_l[0];
     ia.ctx_h = sb.ctx_h; ia.ctx_l = sb.ctx_l;
-    ia.out_mpad = (lstm_prec(h) && chunk_ok(d) && h->chunk_a) ? rows_pad(B) : 0;
+    ia.out_mpad = act_mpad(h, B);
     ia.memory = is_taco2(d) ? memory : nullptr;
     ia.B = B; ia.L = L; ia.D = d.d_ctx; ia.Ha = d.h_att; ia.Hd = d.h_dec; ia.d_mel = d.d_mel;
     launch_init(ia, st);
@@ -1197,7 +1166,7 @@ static int decode_impl(ttsdec_handle* h, const float* memory, int B, int L, int 
     }
   }
   io.node_pos = kLoopStampNodes - 1;     // (the end-of-call launches below stamp a node index no step launch uses)
-  if (head_proj(h, B) && n_steps > 0) {  // (that step order leaves each step's projection to the NEXT step's launch)
+  if (head_proj(h) && n_steps > 0) {  // (that step order leaves each step's projection to the NEXT step's launch)
     io.slot = (n_steps - 1) & 1;        // buffer parity of the call's last step (t_begin is even)
     launch_node(h, sb, io, N_JFIN, st);
   }
@@ -1309,139 +1278,61 @@ int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision
   const size_t M = (size_t)B * T;
   Carver cv{static_cast<float*>(workspace)};
   const PostnetWs pw = carve_postnet(cv, d, M);
-  char* const* act = pw.act;
-  char* yin = pw.yin;
-  auto plane = [&](size_t float_off) { return reinterpret_cast<const void*>(h->blob + float_off); };
+  const int Hh = d.postnet_hidden;
+  // one layer on input a [M, cin]: a conv over `taps` frames (A_CONV), or taps = 0: a plain GEMM
+  auto layer = [&](Planes a, int cin, int taps, const Mat& w) {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.prec = prec;
+    g.a = make_seg1(a.p0, cin, cin); g.a_lo = make_seg1(a.p1, cin, cin);
+    if (taps) { g.T = T; g.Cin = cin; g.taps = taps; }
+    set_weight(g, w, h->blob, prec);
+    g.ldw = g.K = (int)w.cols; g.M = (int)M; g.N = g.ldo = (int)w.rows;
+    return g;
+  };
 
   if (d.postnet_type == TTSDEC_POSTNET_TYPE_MEL2) {
-    // MelPostnet2.forward (modules.py:213-216): x = x + conv3(lrelu(BN(conv2(lrelu(BN(conv1(x))))))) per layer
-    char* const* xbuf = pw.xbuf;  // fp32 residual stream, ping-pong
-    char* const* xpl = pw.xpl;    // its 16-bit planes, ping-pong
-    const int Hh = d.postnet_hidden, kk = d.postnet_kernel;
+    // MelPostnet2.forward (modules.py:213-216): x = x + conv3(lrelu(BN(conv2(lrelu(BN(conv1(x))))))) per layer;
+    // the fp32 residual stream and its 16-bit planes ping-pong in xbuf / xpl
     const float* xcur = y;
-    const void *x0 = y, *x1 = y;
-    if (prec == PREC_F16S) {
-      f16* xh = reinterpret_cast<f16*>(xpl[1]);
-      launch_split(y, xh, xh + M * d.d_mel, M * d.d_mel, st);
-      x0 = xh; x1 = xh + M * d.d_mel;
-    } else if (prec == PREC_BF16) {
-      launch_to_bf16(y, xpl[1], M * d.d_mel, st);
-      x0 = x1 = xpl[1];
-    }
-    auto wsel = [&](int i, int c, bool lo) -> const void* {
-      if (prec == PREC_F32) return h->blob + L.p2_w[i][c];
-      if (prec == PREC_BF16) return plane(L.p2_wb[i][c]);
-      return plane(lo ? L.p2_wl[i][c] : L.p2_wh[i][c]);
-    };
+    Planes x = act_input(prec, y, pw.xpl[1], M * d.d_mel, st);
     for (int i = 0; i < d.postnet_layers; ++i) {
-      const void *a0 = x0, *a1 = x1;
-      int cin2 = d.d_mel;
+      Planes a = x;
       for (int c = 0; c < 2; ++c) {  // conv1 / conv2 + BN + LeakyReLU
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.prec = prec;
-        g.a = make_seg1(a0, cin2, cin2); g.a_lo = make_seg1(a1, cin2, cin2);
-        g.T = T; g.Cin = cin2; g.taps = kk; g.ldw = kk * cin2; g.K = kk * cin2;
-        g.W = wsel(i, c, false); g.W_lo = wsel(i, c, true);
-        g.M = (int)M; g.N = Hh; g.ldo = Hh;
+        GemmArgs g = layer(a, c ? Hh : d.d_mel, d.postnet_kernel, L.p2[i][c]);
         g.alpha = h->blob + L.p2_alpha[i][c]; g.beta = h->blob + L.p2_beta[i][c];
-        char* o = act[c];
-        if (prec == PREC_F32) { g.out = reinterpret_cast<float*>(o); a0 = a1 = o; }
-        else if (prec == PREC_F16S) {
-          g.out_kind = 1; g.out_h = reinterpret_cast<f16*>(o); g.out_l = g.out_h + M * Hh; a0 = g.out_h; a1 = g.out_l;
-        } else { g.out_kind = 2; g.out_h = reinterpret_cast<f16*>(o); a0 = a1 = o; }
+        a = set_output(g, prec, pw.act[c], M * Hh);
         launch_gemm(g, A_CONV, EPI_BN_LRELU, st);
-        cin2 = Hh;
       }
-      GemmArgs g;  // conv3 + residual
-      memset(&g, 0, sizeof(g));
-      g.prec = prec;
-      g.a = make_seg1(a0, Hh, Hh); g.a_lo = make_seg1(a1, Hh, Hh);
-      g.T = T; g.Cin = Hh; g.taps = kk; g.ldw = kk * Hh; g.K = kk * Hh;
-      g.W = wsel(i, 2, false); g.W_lo = wsel(i, 2, true);
-      g.M = (int)M; g.N = d.d_mel; g.ldo = d.d_mel;
+      GemmArgs g = layer(a, Hh, d.postnet_kernel, L.p2[i][2]);  // conv3 + residual
       g.resid = xcur;
       const bool last = (i == d.postnet_layers - 1);
-      float* xnew = last ? y_post : reinterpret_cast<float*>(xbuf[i & 1]);
-      g.out = xnew;
-      if (!last && prec == PREC_F16S) {
-        g.out_kind = 1; g.out_h = reinterpret_cast<f16*>(xpl[i & 1]); g.out_l = g.out_h + M * d.d_mel; x0 = g.out_h; x1 = g.out_l;
-      } else if (!last && prec == PREC_BF16) {
-        g.out_kind = 2; g.out_h = reinterpret_cast<f16*>(xpl[i & 1]); x0 = x1 = xpl[i & 1];
-      } else if (!last) {
-        x0 = x1 = xnew;
-      }
+      float* xnew = last ? y_post : reinterpret_cast<float*>(pw.xbuf[i & 1]);
+      if (!last) x = set_output(g, prec, prec == PREC_F32 ? reinterpret_cast<char*>(xnew) : pw.xpl[i & 1], M * d.d_mel);
+      g.out = xnew;  // (the 16-bit modes keep the fp32 stream beside the planes: the next layer's residual)
       launch_gemm(g, A_CONV, EPI_RESIDUAL, st);
       xcur = xnew;
     }
     return record_hip_error(h, "postnet2");
   }
 
-  // current layer input as (plane 0, plane 1)
-  const void *in0 = y, *in1 = y;
-  if (prec == PREC_F16S) {
-    f16* yh = reinterpret_cast<f16*>(yin);
-    f16* yl = yh + M * d.d_mel;
-    launch_split(y, yh, yl, M * d.d_mel, st);
-    in0 = yh; in1 = yl;
-  } else if (prec == PREC_BF16) {
-    launch_to_bf16(y, yin, M * d.d_mel, st);
-    in0 = in1 = yin;
-  }
-  int cin = d.d_mel;
+  Planes in = act_input(prec, y, pw.yin, M * d.d_mel, st);
   for (int i = 0; i < d.postnet_layers; ++i) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.prec = prec;
-    g.a = make_seg1(in0, cin, cin);
-    g.a_lo = make_seg1(in1, cin, cin);
-    g.T = T; g.Cin = cin; g.taps = d.postnet_kernel;
-    g.ldw = d.postnet_kernel * cin; g.K = d.postnet_kernel * cin;
-    g.M = (int)M; g.N = d.postnet_hidden;
+    GemmArgs g = layer(in, i ? Hh : d.d_mel, d.postnet_kernel, L.conv[i]);
     g.alpha = h->blob + L.conv_alpha[i]; g.beta = h->blob + L.conv_beta[i];
-    g.ldo = d.postnet_hidden;
-    char* o = act[i & 1];
+    char* o = pw.act[i & 1];
+    in = set_output(g, prec, o, M * Hh);
     // the wide hidden -> hidden layers on the 256 x 256 schedule (conv256.hip) where the shape is that kernel's - exact fp32 and
     // bf16; TTSDEC_CONV256=0 keeps the shared tile (measurement)
     static const bool use256 = [] { const char* e = getenv("TTSDEC_CONV256"); return !(e && e[0] == '0'); }();
-    if (prec == PREC_F32) {
-      g.W = g.W_lo = h->blob + L.conv_w[i];
-      g.out = reinterpret_cast<float*>(o);
-      in0 = in1 = o;
-      if (use256 && launch_conv256_f32(static_cast<const float*>(g.a.p0), static_cast<const float*>(g.W), g.alpha, g.beta, g.out, (int)M, T, cin,
-                                       d.postnet_kernel, d.postnet_hidden, st)) {
-        cin = d.postnet_hidden;
-        continue;
-      }
-    } else if (prec == PREC_F16S) {
-      g.W = plane(L.conv_wh[i]); g.W_lo = plane(L.conv_wl[i]);
-      g.out_kind = 1;
-      g.out_h = reinterpret_cast<f16*>(o);
-      g.out_l = g.out_h + M * d.postnet_hidden;
-      in0 = g.out_h; in1 = g.out_l;
-    } else {
-      g.W = g.W_lo = plane(L.conv_wb[i]);
-      g.out_kind = 2;
-      g.out_h = reinterpret_cast<f16*>(o);
-      in0 = in1 = o;
-      if (use256 && launch_conv256_bf16(g.a.p0, g.W, g.alpha, g.beta, o, (int)M, T, cin, d.postnet_kernel, d.postnet_hidden, st)) {
-        cin = d.postnet_hidden;
-        continue;
-      }
-    }
+    if (use256 && prec == PREC_F32 &&
+        launch_conv256_f32(static_cast<const float*>(g.a.p0), static_cast<const float*>(g.W), g.alpha, g.beta, g.out, (int)M, T, g.Cin, g.taps, Hh, st))
+      continue;
+    if (use256 && prec == PREC_BF16 && launch_conv256_bf16(g.a.p0, g.W, g.alpha, g.beta, o, (int)M, T, g.Cin, g.taps, Hh, st)) continue;
     launch_gemm(g, A_CONV, EPI_BN_ISRU, st);
-    cin = d.postnet_hidden;
   }
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.prec = prec;
-  g.a = make_seg1(in0, cin, cin);
-  g.a_lo = make_seg1(in1, cin, cin);
-  if (prec == PREC_F32) g.W = g.W_lo = h->blob + L.fc_w;
-  else if (prec == PREC_F16S) { g.W = plane(L.fc_wh); g.W_lo = plane(L.fc_wl); }
-  else g.W = g.W_lo = plane(L.fc_wb);
-  g.ldw = cin; g.K = cin; g.M = (int)M; g.N = d.d_mel;
-  g.resid = y; g.out = y_post; g.ldo = d.d_mel;
+  GemmArgs g = layer(in, Hh, 0, L.fc);
+  g.resid = y; g.out = y_post;
   launch_gemm(g, A_PLAIN, EPI_RESIDUAL, st);
   return record_hip_error(h, "postnet");
 }
@@ -1474,8 +1365,8 @@ int ttsdec_cell_step(ttsdec_handle* h, const float* x, const float* memory, int 
   launch_copy(h_dec, sb.h_dec[p], b * d.h_dec, st);
   launch_copy(c_dec, sb.c_dec, b * d.h_dec, st);
   const int prec = lstm_prec(h);
-  if (prec && chunk_ok(d) && h->chunk_a) {
-    const int mp = rows_pad(B);
+  const int mp = act_mpad(h, B);
+  if (mp) {
     if (!t2) launch_split_chunked(ctx, sb.ctx_h, sb.ctx_l, B, d.d_ctx, mp, st);
     launch_split_chunked(h_att, sb.h_att_h[p], sb.h_att_l[p], B, d.h_att, mp, st);
     launch_split_chunked(h_dec, sb.h_dec_h[p], sb.h_dec_l[p], B, d.h_dec, mp, st);
@@ -1495,7 +1386,7 @@ int ttsdec_cell_step(ttsdec_handle* h, const float* x, const float* memory, int 
     AttnArgs a;
     memset(&a, 0, sizeof(a));
     a.memory = memory; a.w_prev = sb.w[p]; a.w_new = sb.w[1 - p]; a.ctx = sb.ctx; a.ctx_only = 1;
-    if (prec) { a.ctx_h = sb.ctx_h; a.ctx_l = sb.ctx_l; a.out_mpad = (chunk_ok(d) && h->chunk_a) ? rows_pad(B) : 0; }
+    if (prec) { a.ctx_h = sb.ctx_h; a.ctx_l = sb.ctx_l; a.out_mpad = mp; }
     a.B = B; a.L = L; a.D = d.d_ctx; a.t_stride = 1;
     launch_attn(a, st);
     if (use_frame(d)) launch_node(h, sb, io, N_F, st);  // (io.finalize = 0: the input frame is x itself)
@@ -1570,8 +1461,7 @@ int ttsdec_profile_step(ttsdec_handle* h, const float* memory, int B, int L, int
   const char* names[kMaxKernelsPerStep + 4];
   int nn = 0;
   for (int k = 0; k < order.n; ++k) { nodes[nn] = order.nodes[k]; names[nn++] = order.names[k]; }
-  if ((&order == &kOrderProdO || &order == &kOrderProdO2 || &order == &kOrderProdH || &order == &kOrderProdH2 || &order == &kOrderProdO2Q ||
-       &order == &kOrderProdH2Q) && n_out >= order.n + 4) {
+  if (!is_taco2(h->d) && has_two_role_node(order) && n_out >= order.n + 4) {
     const Node extra[4] = {N_F, N_AG, N_T, N_DG};
     const char* extra_names[4] = {"prenet(alone)", "lstm_att_lean(alone)", "attention(alone)", "lstm_dec_lean(alone)"};
     for (int k = 0; k < 4; ++k) { nodes[nn] = extra[k]; names[nn++] = extra_names[k]; }

@@ -167,14 +167,13 @@ int ttsenc_forward(ttsenc_handle* h, const int64_t* ids, const int32_t* lengths,
     memset(&g, 0, sizeof(g));
     g.a = make_seg1(in, E, E); g.a_lo = g.a;
     g.T = L; g.Cin = E; g.taps = d.conv_kernel;
-    g.W = g.W_lo = blob + bl.conv_w[i]; g.ldw = d.conv_kernel * E; g.K = d.conv_kernel * E;
+    set_weight_contiguous(g, blob + bl.conv_w[i], (size_t)E * d.conv_kernel * E, split);
+    g.ldw = d.conv_kernel * E; g.K = d.conv_kernel * E;
     if (split) {
-      const size_t n = (size_t)M * E, nw = (size_t)E * d.conv_kernel * E;
+      const size_t n = (size_t)M * E;
       launch_split(in, ph, ph + n, n, st);
       g.a = make_seg1(ph, E, E); g.a_lo = make_seg1(ph + n, E, E);
       g.prec = PREC_F16S;
-      g.W = reinterpret_cast<const f16*>(blob + bl.conv_w[i] + nw);
-      g.W_lo = reinterpret_cast<const f16*>(blob + bl.conv_w[i] + nw) + nw;
     }
     g.M = M; g.N = E;
     g.alpha = blob + bl.alpha[i]; g.beta = blob + bl.beta[i];
@@ -187,14 +186,13 @@ int ttsenc_forward(ttsenc_handle* h, const int64_t* ids, const int32_t* lengths,
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.a = make_seg1(cat, 2 * E, 2 * E); g.a_lo = g.a;
-    g.W = g.W_lo = blob + bl.w_ih; g.ldw = 2 * E; g.K = 2 * E; g.M = M; g.N = 8 * H; g.out = gx; g.ldo = 8 * H;
+    set_weight_contiguous(g, blob + bl.w_ih, (size_t)8 * H * 2 * E, split);
+    g.ldw = 2 * E; g.K = 2 * E; g.M = M; g.N = 8 * H; g.out = gx; g.ldo = 8 * H;
     if (split) {
-      const size_t n = (size_t)M * 2 * E, nw = (size_t)8 * H * 2 * E;
+      const size_t n = (size_t)M * 2 * E;
       launch_split(cat, ph, ph + n, n, st);
       g.a = make_seg1(ph, 2 * E, 2 * E); g.a_lo = make_seg1(ph + n, 2 * E, 2 * E);
       g.prec = PREC_F16S;
-      g.W = reinterpret_cast<const f16*>(blob + bl.w_ih + nw);
-      g.W_lo = reinterpret_cast<const f16*>(blob + bl.w_ih + nw) + nw;
       launch_gemm(g, A_PLAIN, EPI_GENERIC, st);  // (the precision-aware plain epilogue: no bias / mask / residual here)
     } else {
       launch_gemm(g, A_PLAIN, EPI_PLAIN, st);

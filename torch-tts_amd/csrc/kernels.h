@@ -91,6 +91,13 @@ struct GemmArgs {
 };
 
 void launch_gemm(const GemmArgs& a, AKind ak, EpiKind ek, hipStream_t st);
+// The packed-weight convention of the encoder and VITS2 blobs: fp32 [n_w] | split-fp16 hi [n_w] | lo [n_w], back to back.
+// Points g at the fp32 copy at W, or (split) at the two planes behind it.
+inline void set_weight_contiguous(GemmArgs& g, const float* W, size_t n_w, bool split) {
+  const f16* hi = reinterpret_cast<const f16*>(W + n_w);
+  g.W = split ? static_cast<const void*>(hi) : W;
+  g.W_lo = split ? static_cast<const void*>(hi + n_w) : W;
+}
 
 // ---- LSTM zoneout cell: gates GEMM + cell update fused ----
 struct LstmArgs {

@@ -1168,8 +1168,8 @@ void gemm_generic(const GemmCtx& cx, const float* a, const f16* a_pl, int lda, i
   memset(&g, 0, sizeof(g));
   g.M = M; g.N = N; g.bias = bias; g.out = out; g.ldo = ldo; g.act = act; g.row_mask = row_mask; g.resid = resid;
   const void *a0 = a, *a1 = a;
-  g.W = g.W_lo = W;
   const bool split = cx.split && lda == K && !(K & 7);
+  set_weight_contiguous(g, W, n_w, split);
   if (out_pl != nullptr && ldo == N) { g.out_kind = 1; g.out_h = out_pl; g.out_l = out_pl + (size_t)M * N; }
   if (split) {
     const f16* ph = a_pl;
@@ -1179,8 +1179,6 @@ void gemm_generic(const GemmCtx& cx, const float* a, const f16* a_pl, int lda, i
     }
     a0 = ph; a1 = ph + (size_t)M * K;
     g.prec = PREC_F16S;
-    g.W = reinterpret_cast<const f16*>(W + n_w);
-    g.W_lo = reinterpret_cast<const f16*>(W + n_w) + n_w;
   }
   if (taps > 1) {
     g.a = make_seg1(a0, K, K); g.a_lo = make_seg1(a1, K, K);
