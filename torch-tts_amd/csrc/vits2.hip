@@ -22,28 +22,61 @@
 using namespace ttsdec;
 
 namespace {
-constexpr int kMaxLayers = 12, kMaxFlows = 8, kMaxWn = 8;
+constexpr int kMaxLayers = 12, kMaxFlows = 8, kMaxWn = 8, kMaxPostWn = 32;
+
+// One linear or conv weight [N, taps, K] (tap-major, as the GEMM core reads it) with its bias [N].  Offsets in floats.  The weight
+// takes 2 n() floats: fp32 | fp16 hi plane | fp16 lo plane back to back (set_weight_contiguous).  src: its weight among the pack
+// call's source tensors, the bias right behind it.
+struct Lin {
+  size_t w, b;
+  int N, K, taps, src;
+  size_t n() const { return (size_t)N * taps * K; }
+};
+struct Vec {  // a tensor no GEMM reads (LayerNorm gamma / beta, the relative-position tables, the embedding table): plain fp32
+  size_t off, n;
+  int src;
+};
+// The one walk over a blob (at *_create): it hands out the offsets in blob order and the source indices in the order
+// include/ttsdec.h documents - the two orders are the same - so src, at its end, is the family's tensor count.
+struct Walk {
+  Carver cv{nullptr};
+  int src = 0;
+  Vec vec(size_t n) { return {cv.take_off(n), n, src++}; }
+  Lin lin(int N, int K, int taps = 1, int n_src = 2) {  // (n_src: 6 for q / k / v stacked into one weight)
+    Lin l{0, 0, N, K, taps, src};
+    l.w = cv.take_off(2 * l.n());
+    l.b = cv.take_off(N);
+    src += n_src;
+    return l;
+  }
+};
 
 // one attentions.Encoder stack (attentions.py:14-93)
 struct StackBlob {
-  size_t wqkv[kMaxLayers], bqkv[kMaxLayers], wo[kMaxLayers], bo[kMaxLayers], ek[kMaxLayers], ev[kMaxLayers];
-  size_t g1[kMaxLayers], b1[kMaxLayers], w1[kMaxLayers], c1[kMaxLayers], w2[kMaxLayers], c2[kMaxLayers], g2[kMaxLayers], b2[kMaxLayers];
+  Lin wqkv[kMaxLayers], wo[kMaxLayers], w1[kMaxLayers], w2[kMaxLayers];  // conv_q / conv_k / conv_v stacked on the output axis
+  Vec ek[kMaxLayers], ev[kMaxLayers], g1[kMaxLayers], b1[kMaxLayers], g2[kMaxLayers], b2[kMaxLayers];  // (ek / ev: n = 0 without a window)
 };
 struct StackDims {
   int C, F, heads, layers, kernel, window;  // window < 0: no relative-position terms
 };
+struct WnBlob {  // modules.WN (modules.py:133-183): H = in[0].K channels, in[0].taps taps
+  int layers;
+  Lin cond;  // cond_layer (gin_channels > 0): [2 H layers, gin]
+  Lin in[kMaxPostWn], rs[kMaxPostWn];
+};
 struct FlowBlob {
   StackBlob tf;
-  size_t pre_w, pre_b, in_w[kMaxWn], in_b[kMaxWn], rs_w[kMaxWn], rs_b[kMaxWn], post_w, post_b;
-  size_t cond_w, cond_b;  // WN.cond_layer (gin_channels > 0): [2 Fh n_layers, gin], [2 Fh n_layers]
+  Lin pre, post;
+  WnBlob wn;
 };
-struct VitsBlob {  // offsets in floats
-  size_t emb;
-  size_t spk_w, spk_b;  // encoder.spk_emb_linear (gin_channels > 0): [hidden, gin], [hidden]
+struct VitsBlob {
+  Vec emb;
+  Lin spk;  // encoder.spk_emb_linear (gin_channels > 0): [hidden, gin]
   StackBlob enc;
-  size_t proj_w, proj_b;
+  Lin proj;
   FlowBlob flow[kMaxFlows];
-  size_t total;
+  size_t total;  // floats
+  int n_src;     // source tensors of ttsvits_pack_weights
 };
 }  // namespace
 
@@ -60,48 +93,44 @@ StackDims tf_dims(const ttsvits_dims& d) {
   return {half, half, d.flow_tf_heads, d.flow_tf_layers, d.flow_tf_kernel, -1};
 }
 
+void walk_stack(Walk& wk, StackBlob& s, const StackDims& sd) {
+  const int C = sd.C, F = sd.F;
+  const size_t nrel = (size_t)(2 * sd.window + 1) * (C / sd.heads);
+  for (int i = 0; i < sd.layers; ++i) {
+    s.wqkv[i] = wk.lin(3 * C, C, 1, 6); s.wo[i] = wk.lin(C, C);
+    if (sd.window >= 0) { s.ek[i] = wk.vec(nrel); s.ev[i] = wk.vec(nrel); }
+    s.g1[i] = wk.vec(C); s.b1[i] = wk.vec(C);
+    s.w1[i] = wk.lin(F, C, sd.kernel); s.w2[i] = wk.lin(C, F, sd.kernel);
+    s.g2[i] = wk.vec(C); s.b2[i] = wk.vec(C);
+  }
+}
+void walk_wn(Walk& wk, WnBlob& w, int H, int kernel, int layers, int gin) {
+  w.layers = layers;
+  if (gin > 0) w.cond = wk.lin(2 * H * layers, gin);
+  for (int j = 0; j < layers; ++j) {
+    w.in[j] = wk.lin(2 * H, H, kernel);
+    w.rs[j] = wk.lin(j < layers - 1 ? 2 * H : H, H);  // (the last layer has no residual half: modules.py:176-179)
+  }
+}
 VitsBlob make_layout(const ttsvits_dims& d) {
   VitsBlob L;
   memset(&L, 0, sizeof(L));
-  Carver cv{nullptr};
-  // a GEMM weight of n elements occupies 2n floats: fp32 | fp16 hi plane | fp16 lo plane (w_hi / w_lo below)
-  auto take_w = [&](size_t n) { return cv.take_off(2 * n); };
-  auto stack = [&](StackBlob& s, const StackDims& sd) {
-    const size_t C = sd.C, F = sd.F, k = sd.kernel, dk = sd.C / sd.heads;
-    for (int i = 0; i < sd.layers; ++i) {
-      s.wqkv[i] = take_w(3 * C * C); s.bqkv[i] = cv.take_off(3 * C); s.wo[i] = take_w(C * C); s.bo[i] = cv.take_off(C);
-      if (sd.window >= 0) { s.ek[i] = cv.take_off((2 * sd.window + 1) * dk); s.ev[i] = cv.take_off((2 * sd.window + 1) * dk); }
-      s.g1[i] = cv.take_off(C); s.b1[i] = cv.take_off(C);
-      s.w1[i] = take_w(F * k * C); s.c1[i] = cv.take_off(F); s.w2[i] = take_w(C * k * F); s.c2[i] = cv.take_off(C);
-      s.g2[i] = cv.take_off(C); s.b2[i] = cv.take_off(C);
-    }
-  };
-  const size_t H = d.hidden_channels, I = d.inter_channels, half = I / 2, Fh = d.flow_hidden;
-  L.emb = cv.take_off((size_t)d.n_vocab * H);
-  if (d.gin_channels > 0) { L.spk_w = take_w(H * d.gin_channels); L.spk_b = cv.take_off(H); }
-  stack(L.enc, enc_dims(d));
-  L.proj_w = take_w(2 * I * H); L.proj_b = cv.take_off(2 * I);
+  Walk wk;
+  const int H = d.hidden_channels, I = d.inter_channels, half = I / 2, Fh = d.flow_hidden;
+  L.emb = wk.vec((size_t)d.n_vocab * H);
+  if (d.gin_channels > 0) L.spk = wk.lin(H, d.gin_channels);
+  walk_stack(wk, L.enc, enc_dims(d));
+  L.proj = wk.lin(2 * I, H);
   for (int f = 0; f < d.n_flows; ++f) {
     FlowBlob& fb = L.flow[f];
-    stack(fb.tf, tf_dims(d));
-    fb.pre_w = take_w(Fh * half); fb.pre_b = cv.take_off(Fh);
-    if (d.gin_channels > 0) { fb.cond_w = take_w(2 * Fh * d.flow_wn_layers * d.gin_channels); fb.cond_b = cv.take_off(2 * Fh * d.flow_wn_layers); }
-    for (int j = 0; j < d.flow_wn_layers; ++j) {
-      const size_t cr = j < d.flow_wn_layers - 1 ? 2 * Fh : Fh;
-      fb.in_w[j] = take_w(2 * Fh * d.flow_kernel * Fh); fb.in_b[j] = cv.take_off(2 * Fh);
-      fb.rs_w[j] = take_w(cr * Fh); fb.rs_b[j] = cv.take_off(cr);
-    }
-    fb.post_w = take_w(half * Fh); fb.post_b = cv.take_off(half);
+    walk_stack(wk, fb.tf, tf_dims(d));
+    fb.pre = wk.lin(Fh, half);
+    walk_wn(wk, fb.wn, Fh, d.flow_kernel, d.flow_wn_layers, d.gin_channels);
+    fb.post = wk.lin(half, Fh);
   }
-  L.total = cv.off;
+  L.total = wk.cv.off;
+  L.n_src = wk.src;
   return L;
-}
-
-int n_stack_tensors(const StackDims& sd) { return sd.layers * (sd.window >= 0 ? 18 : 16); }
-int n_cond_tensors(const ttsvits_dims& d) { return d.gin_channels > 0 ? 2 : 0; }
-int n_text_tensors(const ttsvits_dims& d) { return 1 + n_cond_tensors(d) + n_stack_tensors(enc_dims(d)) + 2; }
-int n_flow_tensors(const ttsvits_dims& d) {
-  return d.n_flows * (n_stack_tensors(tf_dims(d)) + 2 + n_cond_tensors(d) + 4 * d.flow_wn_layers + 2);
 }
 
 // ===========================================================================
@@ -1128,8 +1157,6 @@ __global__ __launch_bounds__(256) void post_sample_kernel(const float* stats, co
     }
   }
 }
-// pack: rows of three [C, C] matrices stacked -> [3C, C]; conv weights via launch_conv_transpose
-
 // One elementwise step over n elements: the W = 4 kernel on n / 4 threads or the W = 1 kernel on n.  Four-wide needs the channel
 // count C a multiple of `mult` (4; 8 where the kernel also works on half rows), fewer than 2^32 elements and the pointers that may
 // be a caller's 16-byte aligned (the workspace's own always are).  The arguments go in as the W = 1 kernel takes them; a Chan is a
@@ -1148,29 +1175,46 @@ void launch_ew(bool wide, K4 k4, K1 k1, size_t n, hipStream_t st, A... a) {
 
 // row counts and offsets of the GEMM core are 32-bit: B * T frames of up to 4096 channels have to fit
 inline bool frames_fit(int B, int T) { return (size_t)B * T <= (size_t)INT32_MAX / 4096; }
+// The guards in front of every forward call, in the order their codes take precedence.  args_ok: the call's own pointers and
+// sizes; need: what its *_workspace_bytes reports (0 for a NULL handle).
+template <typename Handle>
+int check_call(const Handle* h, bool args_ok, const float* g, const void* workspace, size_t workspace_bytes, size_t need, int B, int T) {
+  if (!h || !args_ok || !workspace || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
+  if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  if (!frames_fit(B, T)) return TTSDEC_ERR_DIMS;
+  return TTSDEC_OK;
+}
 
 // ---------------------------------------------------------------------------
 // host-side building blocks
 // ---------------------------------------------------------------------------
-// One GEMM of the path.  W points at the packed weight (fp32 | hi | lo, see make_layout) of n_w elements.
+// One GEMM of the path: out [M, l.N] = epilogue(a [M, l.K] (M = B * T frames, l.taps taps along T) . weight l of the blob + bias).
 // Split-fp16 arithmetic (3 f16 MFMA products, fp32 accumulate - the same accuracy class as fp32, see
 // gemm_tile.h): the A operand's planes are produced by one elementwise pass into `planes`.
 struct GemmCtx {
   f16* planes;  // scratch for the A operand's hi / lo planes: 2 * max(M * K) halfs
   bool split;   // false: exact fp32 MFMAs
 };
-// a_pl: the A operand's planes if its producer already wrote them (else they are made here);
-// out_pl: where to put the planes of the result for the next GEMM (needs ldo == N), or nullptr.
-void gemm_generic(const GemmCtx& cx, const float* a, const f16* a_pl, int lda, int K, const float* W, size_t n_w, const float* bias, int M,
-                  int N, float* out, f16* out_pl, int ldo, int act, const float* row_mask, const float* resid, int taps, int T,
-                  hipStream_t st) {
+struct Epi {  // what a call chooses besides its weight, input and output
+  int act = 0;                      // 1: ReLU
+  const float* row_mask = nullptr;  // the frame mask [M]
+  const float* resid = nullptr;     // [M, N] added to the result
+  f16* out_pl = nullptr;            // where to put the planes of the result for the next GEMM
+};
+// a_pl: the A operand's planes if its producer already wrote them (else they are made here)
+void gemm_generic(const GemmCtx& cx, const float* blob, const Lin& l, const float* a, const f16* a_pl, float* out, int M, int T, hipStream_t st,
+                  const Epi& e = {}) {
+  const int K = l.K;
   GemmArgs g;
   memset(&g, 0, sizeof(g));
-  g.M = M; g.N = N; g.bias = bias; g.out = out; g.ldo = ldo; g.act = act; g.row_mask = row_mask; g.resid = resid;
+  g.M = M; g.N = l.N; g.bias = blob + l.b; g.out = out; g.ldo = l.N; g.act = e.act; g.row_mask = e.row_mask; g.resid = e.resid;
   const void *a0 = a, *a1 = a;
-  const bool split = cx.split && lda == K && !(K & 7);
-  set_weight_contiguous(g, W, n_w, split);
-  if (out_pl != nullptr && ldo == N) { g.out_kind = 1; g.out_h = out_pl; g.out_l = out_pl + (size_t)M * N; }
+  const bool split = cx.split && !(K & 7);
+  set_weight_contiguous(g, blob + l.w, l.n(), split);
+  if (e.out_pl != nullptr) { g.out_kind = 1; g.out_h = e.out_pl; g.out_l = e.out_pl + (size_t)M * l.N; }
   if (split) {
     const f16* ph = a_pl;
     if (ph == nullptr) {
@@ -1180,13 +1224,12 @@ void gemm_generic(const GemmCtx& cx, const float* a, const f16* a_pl, int lda, i
     a0 = ph; a1 = ph + (size_t)M * K;
     g.prec = PREC_F16S;
   }
-  if (taps > 1) {
-    g.a = make_seg1(a0, K, K); g.a_lo = make_seg1(a1, K, K);
-    g.T = T; g.Cin = K; g.taps = taps; g.ldw = taps * K; g.K = taps * K;
+  g.a = make_seg1(a0, K, K); g.a_lo = make_seg1(a1, K, K);
+  g.ldw = l.taps * K; g.K = l.taps * K;
+  if (l.taps > 1) {
+    g.T = T; g.Cin = K; g.taps = l.taps;
     launch_gemm(g, A_CONV, EPI_GENERIC, st);
   } else {
-    g.a = make_seg1(a0, lda, K); g.a_lo = make_seg1(a1, lda, K);
-    g.ldw = K; g.K = K;
     launch_gemm(g, A_PLAIN, EPI_GENERIC, st);
   }
 }
@@ -1201,6 +1244,13 @@ size_t mha_lds_bytes(int T, int dk, int window) {
   return ((size_t)kMhaRows * dk + (size_t)kMhaChunk * (dk + 1) + 2 * (size_t)nrel * dk + (size_t)kMhaRows * T) * sizeof(float);
 }
 constexpr size_t kMhaMaxLds = 150 * 1024;
+struct MhaLaunch {  // an attention kernel (each takes an MhaArgs) as run_stack launches it
+  void (*fn)(MhaArgs);
+  dim3 grid, block;
+  size_t lds;  // dynamic LDS bytes
+};
+template <int DK>
+MhaLaunch flash_launch(unsigned blocks) { return {mha_flash_kernel<DK>, dim3(blocks), dim3(kFaThreads), (size_t)2 * FaLds<DK>::BUF}; }
 
 void launch_layernorm(const float* in, const float* gamma, const float* beta, const float* mask, float* out, float* out_m, f16* out_p,
                       f16* outm_p, int M, int C, hipStream_t st) {
@@ -1226,60 +1276,46 @@ int run_stack(ttsvits_handle* h, const StackBlob& sb, const StackDims& sd, const
   // no relative window, split-fp16 arithmetic, a head width the flash kernel is built for: one pass over the keys on the f16
   // matrix instruction (the exact-fp32 mode keeps the exact-fp32 kernels)
   const bool use_flash = sd.window < 0 && h->precision == TTSDEC_PREC_SPLIT_F16 && (dk == 48 || dk == 32 || dk == 64 || dk == 16) && !(C & 3);
-  const void* kfn = !use_mfma ? (const void*)mha_kernel
-                   : dk == 96 ? (const void*)mha_mfma_kernel<48>
-                   : dk == 48 ? (const void*)mha_mfma_kernel<24>
-                   : dk == 16 ? (const void*)mha_mfma_kernel<8> : (const void*)mha_mfma_kernel<4>;
-  if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  // the one choice of this call's attention kernel, launched in the layer loop
+  MhaLaunch mha{mha_kernel, dim3((T + kMhaRows - 1) / kMhaRows, sd.heads, B), dim3(kMhaThreads), lds};
+  if (use_flash) {
+    const unsigned nb = ((T + kFaQ - 1) / kFaQ) * sd.heads * B;
+    mha = dk == 48 ? flash_launch<48>(nb) : dk == 32 ? flash_launch<32>(nb) : dk == 64 ? flash_launch<64>(nb) : flash_launch<16>(nb);
+  } else if (use_mfma) {
+    mha.fn = dk == 96 ? mha_mfma_kernel<48> : dk == 48 ? mha_mfma_kernel<24> : dk == 16 ? mha_mfma_kernel<8> : mha_mfma_kernel<4>;
+    mha.grid = dim3((T + kMhaMRows - 1) / kMhaMRows, sd.heads, B), mha.block = dim3(kMhaMThreads);
+  }
+  if (hipFuncSetAttribute((const void*)mha.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mha.lds) != hipSuccess)
     return record_hip_error(h, "hipFuncSetAttribute(mha kernel)");
-  const float* xin = sw.xm;  // layer 0 attends over x * mask; later layers over the unmasked LayerNorm output
   for (int i = 0; i < sd.layers; ++i) {
-    float* xa = i == 0 ? sw.xm : sw.x;
+    float* xa = i == 0 ? sw.xm : sw.x;  // layer 0 attends over x * mask; later layers over the unmasked LayerNorm output
     f16* xa_p = i == 0 ? sw.xm_p : sw.x_p;
     if (gvec != nullptr && i == cond_idx)
       hipLaunchKernelGGL(add_spk_kernel, grid1((size_t)M * C), dim3(256), 0, st, xa, sw.cx.split ? xa_p : nullptr, gvec, mask, M, C, T);
-    gemm_generic(sw.cx, xa, xa_p, C, C, blob + sb.wqkv[i], (size_t)3 * C * C, blob + sb.bqkv[i], M, 3 * C, sw.qkv, nullptr, 3 * C, 0, nullptr,
-                 nullptr, 1, T, st);
+    gemm_generic(sw.cx, blob, sb.wqkv[i], xa, xa_p, sw.qkv, M, T, st);
     MhaArgs a;
     a.qkv = sw.qkv; a.mask = mask; a.out = sw.att; a.out_p = sw.att_p; a.n_out = (size_t)M * C;
     a.planes_only = (use_flash && sw.cx.split && sw.att_p != nullptr && !(C & 7)) ? 1 : 0;
     a.T = T; a.C = C; a.dk = dk; a.window = sd.window;
-    a.ek = sd.window >= 0 ? blob + sb.ek[i] : nullptr; a.ev = sd.window >= 0 ? blob + sb.ev[i] : nullptr;
+    a.ek = sd.window >= 0 ? blob + sb.ek[i].off : nullptr; a.ev = sd.window >= 0 ? blob + sb.ev[i].off : nullptr;
     a.qscale = sqrtf((float)dk);
-    if (use_flash) {
-      const dim3 grid(((T + kFaQ - 1) / kFaQ) * sd.heads * B), block(kFaThreads);
-      if (dk == 48) hipLaunchKernelGGL(mha_flash_kernel<48>, grid, block, 2 * FaLds<48>::BUF, st, a);
-      else if (dk == 32) hipLaunchKernelGGL(mha_flash_kernel<32>, grid, block, 2 * FaLds<32>::BUF, st, a);
-      else if (dk == 64) hipLaunchKernelGGL(mha_flash_kernel<64>, grid, block, 2 * FaLds<64>::BUF, st, a);
-      else hipLaunchKernelGGL(mha_flash_kernel<16>, grid, block, 2 * FaLds<16>::BUF, st, a);
-    } else if (use_mfma) {
-      const dim3 grid((T + kMhaMRows - 1) / kMhaMRows, sd.heads, B), block(kMhaMThreads);
-      if (dk == 96) hipLaunchKernelGGL(mha_mfma_kernel<48>, grid, block, lds, st, a);
-      else if (dk == 48) hipLaunchKernelGGL(mha_mfma_kernel<24>, grid, block, lds, st, a);
-      else if (dk == 16) hipLaunchKernelGGL(mha_mfma_kernel<8>, grid, block, lds, st, a);
-      else hipLaunchKernelGGL(mha_mfma_kernel<4>, grid, block, lds, st, a);
-    } else {
-      hipLaunchKernelGGL(mha_kernel, dim3((T + kMhaRows - 1) / kMhaRows, sd.heads, B), dim3(kMhaThreads), lds, st, a);
-    }
+    hipLaunchKernelGGL(mha.fn, mha.grid, mha.block, mha.lds, st, a);
     // x = LayerNorm(x + conv_o(att))
-    gemm_generic(sw.cx, sw.att, sw.att_p, C, C, blob + sb.wo[i], (size_t)C * C, blob + sb.bo[i], M, C, sw.t, nullptr, C, 0, nullptr, xa, 1, T, st);
+    gemm_generic(sw.cx, blob, sb.wo[i], sw.att, sw.att_p, sw.t, M, T, st, {0, nullptr, xa});
     // (only the outputs somebody reads: x for the FFN's residual; x * mask as the FFN's input - its planes where conv_1 runs on
     // planes (gemm_generic: split mode and C % 8 == 0), the fp32 form otherwise)
     const bool pl = sw.cx.split && !(C & 7) && sw.xm_p != nullptr;
-    launch_layernorm(sw.t, blob + sb.g1[i], blob + sb.b1[i], mask, sw.x, pl ? (float*)nullptr : sw.xm, (f16*)nullptr,
+    launch_layernorm(sw.t, blob + sb.g1[i].off, blob + sb.b1[i].off, mask, sw.x, pl ? (float*)nullptr : sw.xm, (f16*)nullptr,
                      pl ? sw.xm_p : (f16*)nullptr, M, C, st);
     // FFN (attentions.py:411-419): conv_2(relu(conv_1(x * mask)) * mask) * mask, then x = LayerNorm(x + y)
-    gemm_generic(sw.cx, sw.xm, sw.xm_p, C, C, blob + sb.w1[i], (size_t)sd.F * sd.kernel * C, blob + sb.c1[i], M, sd.F, sw.f, sw.f_p, sd.F, 1, mask,
-                 nullptr, sd.kernel, T, st);
-    gemm_generic(sw.cx, sw.f, sw.f_p, sd.F, sd.F, blob + sb.w2[i], (size_t)C * sd.kernel * sd.F, blob + sb.c2[i], M, C, sw.t, nullptr, C, 0, mask,
-                 sw.x, sd.kernel, T, st);
+    gemm_generic(sw.cx, blob, sb.w1[i], sw.xm, sw.xm_p, sw.f, M, T, st, {1, mask, nullptr, sw.f_p});
+    gemm_generic(sw.cx, blob, sb.w2[i], sw.f, sw.f_p, sw.t, M, T, st, {0, mask, sw.x});
     // (a layer in the middle hands the next one x and, where its QKV GEMM runs on planes, x's planes; the last layer hands the
     // caller x * mask in both forms)
     const bool last_layer = i == sd.layers - 1;
-    launch_layernorm(sw.t, blob + sb.g2[i], blob + sb.b2[i], mask, last_layer ? (float*)nullptr : sw.x, last_layer ? sw.xm : (float*)nullptr,
+    launch_layernorm(sw.t, blob + sb.g2[i].off, blob + sb.b2[i].off, mask, last_layer ? (float*)nullptr : sw.x, last_layer ? sw.xm : (float*)nullptr,
                      (!last_layer && pl) ? sw.x_p : (f16*)nullptr, last_layer ? sw.xm_p : (f16*)nullptr, M, C, st);
   }
-  (void)xin;
   return TTSDEC_OK;
 }
 
@@ -1298,57 +1334,45 @@ StackWs carve_stack(Carver& cv, const StackDims& sd, size_t M, bool split) {
   return w;
 }
 
-// fp32 weight at float offset `off` (n elements) -> its fp16 hi / lo planes right behind it
-void pack_planes(float* b, size_t off, size_t n, hipStream_t st) {
-  f16* hi = reinterpret_cast<f16*>(b + off + n);
-  launch_split(b + off, hi, hi + n, n, st);
+// The pack steps.  src: the pack call's source tensors, b: the zeroed blob.  A NULL source is skipped (the ttsvits family allows
+// them: a module that owns only the text encoder or only the flow packs what it has); its planes are split from the zeros.
+void pack_vec(const float* const* src, float* b, const Vec& v, hipStream_t st) { launch_copy(src[v.src], b + v.off, v.n, st); }
+void pack_planes(float* b, const Lin& l, hipStream_t st) {  // the fp32 weight -> its fp16 hi / lo planes right behind it
+  f16* hi = reinterpret_cast<f16*>(b + l.w + l.n());
+  launch_split(b + l.w, hi, hi + l.n(), l.n(), st);
 }
-
-int pack_stack(const float* const* src, int& k, float* b, const StackBlob& s, const StackDims& sd, hipStream_t st) {
-  const size_t C = sd.C, F = sd.F, dk = sd.C / sd.heads;
+void pack_lin(const float* const* src, float* b, const Lin& l, hipStream_t st) {
+  if (l.taps == 1) launch_copy(src[l.src], b + l.w, l.n(), st);
+  else if (src[l.src]) launch_conv_transpose(src[l.src], b + l.w, l.N, l.K, l.taps, st);  // [N, K, taps] -> [N, taps, K]
+  launch_copy(src[l.src + 1], b + l.b, l.N, st);
+  pack_planes(b, l, st);
+}
+void pack_stack(const float* const* src, float* b, const StackBlob& s, const StackDims& sd, hipStream_t st) {
   for (int i = 0; i < sd.layers; ++i) {
-    for (int j = 0; j < 3; ++j) {  // conv_q / conv_k / conv_v stacked on the output axis
-      launch_copy(src[k + 2 * j], b + s.wqkv[i] + j * C * C, C * C, st);
-      launch_copy(src[k + 2 * j + 1], b + s.bqkv[i] + j * C, C, st);
+    const Lin& q = s.wqkv[i];
+    for (int j = 0; j < 3; ++j) {  // conv_q / conv_k / conv_v (weight, bias each) stacked on the output axis
+      launch_copy(src[q.src + 2 * j], b + q.w + j * (q.n() / 3), q.n() / 3, st);
+      launch_copy(src[q.src + 2 * j + 1], b + q.b + j * (q.N / 3), q.N / 3, st);
     }
-    launch_copy(src[k + 6], b + s.wo[i], C * C, st);
-    launch_copy(src[k + 7], b + s.bo[i], C, st);
-    pack_planes(b, s.wqkv[i], 3 * C * C, st);
-    pack_planes(b, s.wo[i], C * C, st);
-    k += 8;
-    if (sd.window >= 0) {
-      launch_copy(src[k], b + s.ek[i], (2 * sd.window + 1) * dk, st);
-      launch_copy(src[k + 1], b + s.ev[i], (2 * sd.window + 1) * dk, st);
-      k += 2;
-    }
-    launch_copy(src[k], b + s.g1[i], C, st);
-    launch_copy(src[k + 1], b + s.b1[i], C, st);
-    if (src[k + 2]) launch_conv_transpose(src[k + 2], b + s.w1[i], (int)F, (int)C, sd.kernel, st);
-    launch_copy(src[k + 3], b + s.c1[i], F, st);
-    if (src[k + 4]) launch_conv_transpose(src[k + 4], b + s.w2[i], (int)C, (int)F, sd.kernel, st);
-    launch_copy(src[k + 5], b + s.c2[i], C, st);
-    launch_copy(src[k + 6], b + s.g2[i], C, st);
-    launch_copy(src[k + 7], b + s.b2[i], C, st);
-    pack_planes(b, s.w1[i], F * sd.kernel * C, st);
-    pack_planes(b, s.w2[i], C * sd.kernel * F, st);
-    k += 8;
+    pack_planes(b, q, st);
+    pack_lin(src, b, s.wo[i], st);
+    for (const Vec* v : {&s.ek[i], &s.ev[i], &s.g1[i], &s.b1[i], &s.g2[i], &s.b2[i]}) pack_vec(src, b, *v, st);  // (no window: ek / ev are empty)
+    pack_lin(src, b, s.w1[i], st);
+    pack_lin(src, b, s.w2[i], st);
   }
-  return TTSDEC_OK;
+}
+void pack_wn(const float* const* src, float* b, const WnBlob& w, hipStream_t st) {
+  if (w.cond.N) pack_lin(src, b, w.cond, st);
+  for (int j = 0; j < w.layers; ++j) {
+    pack_lin(src, b, w.in[j], st);
+    pack_lin(src, b, w.rs[j], st);
+  }
 }
 
 // modules.WN.forward (modules.py:185-210), dilation_rate 1, eval mode, shared by the flow's coupling layers and the posterior
 // encoder: ws.hx [M, H] (and its planes ws.hx_p, when the GEMMs run on planes) in - overwritten - and ws.ho [M, H] = WN(hx) * mask
 // (and its planes ws.ho_p) out.  Per layer j: in_layers.j (kernel taps) -> the gate [+ g_l] -> res_skip_layers.j -> the update.
 // g: NULL or [B, gin]: cond_layer(g) (a 1x1 conv of [B, gin, 1]) first, one small exact-fp32 GEMM into ws.cond [B, 2 H layers].
-struct WnLayout {
-  int H, kernel, layers, gin;
-  const size_t *in_w, *in_b, *rs_w, *rs_b;  // per layer: float offsets into the blob
-  size_t cond_w, cond_b;                    // read when g != nullptr
-};
-template <typename Blob>  // FlowBlob or PostBlob
-WnLayout wn_layout(const Blob& b, int H, int kernel, int layers, int gin) {
-  return {H, kernel, layers, gin, b.in_w, b.in_b, b.rs_w, b.rs_b, b.cond_w, b.cond_b};
-}
 struct WnWs {
   float *hx, *ho, *acts, *xin, *rs, *cond;  // [M,H] [M,H] [M,H] [M,2H] [M,2H] [B, 2 H layers]
   f16 *hx_p, *acts_p, *ho_p;                // planes of hx / acts / ho, written by their producers
@@ -1364,25 +1388,21 @@ WnWs carve_wn(Carver& cv, size_t M, size_t B, size_t H, size_t layers, size_t K,
   return w;
 }
 const GemmCtx kExact{nullptr, false};  // (the [B, gin] projections of g are a few KFLOP: always the exact fp32 instruction)
-void run_wn(const float* blob, const WnLayout& w, const WnWs& ws, const float* g, const float* mask, int B, int T, hipStream_t st) {
-  const int M = B * T, Fh = w.H;
+void run_wn(const float* blob, const WnBlob& w, const WnWs& ws, const float* g, const float* mask, int B, int T, hipStream_t st) {
+  const int M = B * T, Fh = w.in[0].K;
   const int ncond = 2 * Fh * w.layers;
   const size_t n = (size_t)M * Fh;
   const bool vec4 = four_wide(n, Fh, 4), fast = vec4 && ws.cx.split;
   if (g != nullptr)  // g = cond_layer(g)  (modules.py:189-190; a 1x1 conv of [B, gin, 1]: one small GEMM per WN)
-    gemm_generic(kExact, g, nullptr, w.gin, w.gin, blob + w.cond_w, (size_t)ncond * w.gin, blob + w.cond_b, B, ncond,
-                 ws.cond, nullptr, ncond, 0, nullptr, nullptr, 1, 1, st);
+    gemm_generic(kExact, blob, w.cond, g, nullptr, ws.cond, B, 1, st);
   for (int j = 0; j < w.layers; ++j) {
     const float* gl = g != nullptr ? ws.cond + (size_t)j * 2 * Fh : nullptr;  // g_l = g[:, 2 Fh j : 2 Fh (j + 1)]      modules.py:194-196
     const bool last = j == w.layers - 1;
-    gemm_generic(ws.cx, ws.hx, ws.hx_p, Fh, Fh, blob + w.in_w[j], (size_t)2 * Fh * w.kernel * Fh, blob + w.in_b[j], M, 2 * Fh, ws.xin, nullptr,
-                 2 * Fh, 0, nullptr, nullptr, w.kernel, T, st);
+    gemm_generic(ws.cx, blob, w.in[j], ws.hx, ws.hx_p, ws.xin, M, T, st);
     // (the fast gate with Fh % 8 == 0 writes the planes only: the res/skip GEMM then reads nothing else)
     launch_ew(vec4, fast ? wn_gate_kernel<4, true> : wn_gate_kernel<4, false>, wn_gate_kernel<1, false>, n, st, ws.xin,
               fast && !(Fh & 7) ? (float*)nullptr : ws.acts, ws.acts_p, M, Chan{Fh}, gl, T, ncond);
-    const int cr = last ? Fh : 2 * Fh;
-    gemm_generic(ws.cx, ws.acts, ws.acts_p, Fh, Fh, blob + w.rs_w[j], (size_t)cr * Fh, blob + w.rs_b[j], M, cr, ws.rs, nullptr, cr, 0, nullptr,
-                 nullptr, 1, T, st);
+    gemm_generic(ws.cx, blob, w.rs[j], ws.acts, ws.acts_p, ws.rs, M, T, st);  // (2 Fh columns; Fh in the last layer)
     launch_ew(vec4, wn_update_kernel<4>, wn_update_kernel<1>, n, st, ws.hx, ws.ho, ws.rs, mask, ws.hx_p, ws.ho_p, M, Chan{Fh}, last ? 1 : 0,
               j == 0 ? 1 : 0);
   }
@@ -1440,16 +1460,12 @@ FlowWs carve_flow(Carver& cv, const ttsvits_dims& d, size_t B, size_t T, bool sp
 // of a coupling rides in its split, the forward direction's last Flip in the copy-out (no flows: a plain copy).
 int run_flow(ttsvits_handle* h, const float* z, const int32_t* lengths, const float* g, int B, int T, float* out, void* workspace,
              size_t workspace_bytes, void* stream, bool forward) {
-  if (!h || !z || !lengths || !out || !workspace || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
-  if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
-  if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
-  if (workspace_bytes < ttsvits_flow_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
-  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
-  if (!frames_fit(B, T)) return TTSDEC_ERR_DIMS;
+  int rc = check_call(h, z && lengths && out, g, workspace, workspace_bytes, ttsvits_flow_workspace_bytes(h, B, T), B, T);
+  if (rc != TTSDEC_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ttsvits_dims& d = h->d;
   const float* blob = h->blob;
-  const int M = B * T, I = d.inter_channels, half = I / 2, Fh = d.flow_hidden;
+  const int M = B * T, I = d.inter_channels;
   const size_t n = (size_t)M * I;
   Carver cv{static_cast<float*>(workspace)};
   const FlowWs w = carve_flow(cv, d, B, T, h->precision == TTSDEC_PREC_SPLIT_F16);
@@ -1466,17 +1482,15 @@ int run_flow(ttsvits_handle* h, const float* z, const int32_t* lengths, const fl
     launch_ew(i4, flip ? split_kernel<4, true> : split_kernel<4, false>, flip ? split_kernel<1, true> : split_kernel<1, false>, n, st, cur, mask,
               xb, sw.xm, sw.xm_p, M, Chan{I});
     // x0_ = pre_transformer(x0 * mask, mask) + x0                                   models.py:508-509
-    int rc = run_stack(h, fb.tf, tf_dims(d), sw, mask, B, T, st);
+    rc = run_stack(h, fb.tf, tf_dims(d), sw, mask, B, T, st);
     if (rc != TTSDEC_OK) return rc;
     launch_ew(i4, add_x0_kernel<4>, add_x0_kernel<1>, n / 2, st, sw.xm, sw.xm_p, xb, M, Chan{I});
     // h = pre(x0_) * mask                                                           :510
-    gemm_generic(ws.cx, sw.xm, sw.xm_p, half, half, blob + fb.pre_w, (size_t)Fh * half, blob + fb.pre_b, M, Fh, ws.hx, ws.hx_p, Fh, 0, mask,
-                 nullptr, 1, T, st);
+    gemm_generic(ws.cx, blob, fb.pre, sw.xm, sw.xm_p, ws.hx, M, T, st, {0, mask, nullptr, ws.hx_p});
     // h = WN(h, mask, g)                                                            :511, modules.py:185-210
-    run_wn(blob, wn_layout(fb, Fh, d.flow_kernel, d.flow_wn_layers, d.gin_channels), ws, g, mask, B, T, st);
+    run_wn(blob, fb.wn, ws, g, mask, B, T, st);
     // m = post(h) * mask ; reverse: x1 = (x1 - m) * mask, forward: x1 = m + x1 * mask   :517, 522, 529
-    gemm_generic(ws.cx, ws.ho, ws.ho_p, Fh, Fh, blob + fb.post_w, (size_t)half * Fh, blob + fb.post_b, M, half, w.mm, nullptr, half, 0, mask,
-                 nullptr, 1, T, st);
+    gemm_generic(ws.cx, blob, fb.post, ws.ho, ws.ho_p, w.mm, M, T, st, {0, mask});
     launch_ew(i4, forward ? couple_kernel<4, true> : couple_kernel<4, false>, forward ? couple_kernel<1, true> : couple_kernel<1, false>, n / 2,
               st, xb, w.mm, mask, M, Chan{I});
     float* t = xa; xa = xb; xb = t;  // the coupled tensor becomes the next layer's input
@@ -1511,7 +1525,7 @@ int ttsvits_destroy(ttsvits_handle* h) {
   return TTSDEC_OK;
 }
 const char* ttsvits_last_hip_error(const ttsvits_handle* h) { return last_hip_error(h); }
-int ttsvits_num_weight_tensors(const ttsvits_handle* h) { return h ? n_text_tensors(h->d) + n_flow_tensors(h->d) : TTSDEC_ERR_INVALID_ARG; }
+int ttsvits_num_weight_tensors(const ttsvits_handle* h) { return h ? h->bl.n_src : TTSDEC_ERR_INVALID_ARG; }
 size_t ttsvits_packed_bytes(const ttsvits_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
 
 int ttsvits_pack_weights(ttsvits_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
@@ -1521,45 +1535,16 @@ int ttsvits_pack_weights(ttsvits_handle* h, const float* const* src, int n_src, 
   const ttsvits_dims& d = h->d;
   const VitsBlob& L = h->bl;
   float* b = static_cast<float*>(blob);
-  const size_t H = d.hidden_channels, I = d.inter_channels, half = I / 2, Fh = d.flow_hidden;
-  int k = 0;
-  // (launch_copy / launch_conv_transpose skip NULL sources: a module that owns only the text encoder
-  // or only the flow packs what it has)
-  launch_copy(src[k++], b + L.emb, (size_t)d.n_vocab * H, st);
-  if (d.gin_channels > 0) {
-    launch_copy(src[k++], b + L.spk_w, H * d.gin_channels, st);
-    launch_copy(src[k++], b + L.spk_b, H, st);
-    pack_planes(b, L.spk_w, H * d.gin_channels, st);
-  }
-  pack_stack(src, k, b, L.enc, enc_dims(d), st);
-  launch_copy(src[k++], b + L.proj_w, 2 * I * H, st);
-  launch_copy(src[k++], b + L.proj_b, 2 * I, st);
-  pack_planes(b, L.proj_w, 2 * I * H, st);
+  pack_vec(src, b, L.emb, st);
+  if (d.gin_channels > 0) pack_lin(src, b, L.spk, st);
+  pack_stack(src, b, L.enc, enc_dims(d), st);
+  pack_lin(src, b, L.proj, st);
   for (int f = 0; f < d.n_flows; ++f) {
     const FlowBlob& fb = L.flow[f];
-    pack_stack(src, k, b, fb.tf, tf_dims(d), st);
-    launch_copy(src[k++], b + fb.pre_w, Fh * half, st);
-    launch_copy(src[k++], b + fb.pre_b, Fh, st);
-    pack_planes(b, fb.pre_w, Fh * half, st);
-    if (d.gin_channels > 0) {
-      const size_t nc = 2 * Fh * d.flow_wn_layers;
-      launch_copy(src[k++], b + fb.cond_w, nc * d.gin_channels, st);
-      launch_copy(src[k++], b + fb.cond_b, nc, st);
-      pack_planes(b, fb.cond_w, nc * d.gin_channels, st);
-    }
-    for (int j = 0; j < d.flow_wn_layers; ++j) {
-      const size_t cr = j < d.flow_wn_layers - 1 ? 2 * Fh : Fh;
-      if (src[k]) launch_conv_transpose(src[k], b + fb.in_w[j], (int)(2 * Fh), (int)Fh, d.flow_kernel, st);
-      launch_copy(src[k + 1], b + fb.in_b[j], 2 * Fh, st);
-      launch_copy(src[k + 2], b + fb.rs_w[j], cr * Fh, st);
-      launch_copy(src[k + 3], b + fb.rs_b[j], cr, st);
-      pack_planes(b, fb.in_w[j], 2 * Fh * d.flow_kernel * Fh, st);
-      pack_planes(b, fb.rs_w[j], cr * Fh, st);
-      k += 4;
-    }
-    launch_copy(src[k++], b + fb.post_w, half * Fh, st);
-    launch_copy(src[k++], b + fb.post_b, half, st);
-    pack_planes(b, fb.post_w, half * Fh, st);
+    pack_stack(src, b, fb.tf, tf_dims(d), st);
+    pack_lin(src, b, fb.pre, st);
+    pack_wn(src, b, fb.wn, st);
+    pack_lin(src, b, fb.post, st);
   }
   return pack_end(h, b);
 }
@@ -1575,13 +1560,8 @@ size_t ttsvits_text_encoder_workspace_bytes(const ttsvits_handle* h, int B, int 
 
 int ttsvits_text_encoder(ttsvits_handle* h, const int64_t* ids, const int32_t* lengths, const float* g, int B, int T, float* x, float* m,
                          float* logs, void* workspace, size_t workspace_bytes, void* stream, int32_t* status) {
-  if (!h || !ids || !lengths || !x || !m || !logs || !workspace || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
-  if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
-  if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
-  if (workspace_bytes < ttsvits_text_encoder_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255))
-    return TTSDEC_ERR_WORKSPACE;
-  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
-  if (!frames_fit(B, T)) return TTSDEC_ERR_DIMS;
+  int rc = check_call(h, ids && lengths && x && m && logs, g, workspace, workspace_bytes, ttsvits_text_encoder_workspace_bytes(h, B, T), B, T);
+  if (rc != TTSDEC_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ttsvits_dims& d = h->d;
   const VitsBlob& L = h->bl;
@@ -1591,16 +1571,14 @@ int ttsvits_text_encoder(ttsvits_handle* h, const int64_t* ids, const int32_t* l
   const StackWs& sw = w.sw;
   float *mask = w.mask, *stats = w.stats, *gvec = w.gvec;
   if (g != nullptr)  // attentions.py:81: spk_emb_linear(g)
-    gemm_generic(kExact, g, nullptr, d.gin_channels, d.gin_channels, h->blob + L.spk_w, (size_t)H * d.gin_channels, h->blob + L.spk_b, B, H, gvec,
-                 nullptr, H, 0, nullptr, nullptr, 1, 1, st);
+    gemm_generic(kExact, h->blob, L.spk, g, nullptr, gvec, B, 1, st);
   // models.py:370-376
   hipLaunchKernelGGL(embed_scale_kernel, grid1((size_t)M * H), dim3(256), 0, st, reinterpret_cast<const long long*>(ids), lengths,
-                     h->blob + L.emb, d.n_vocab, T, H, sqrtf((float)H), sw.xm, sw.xm_p, mask, M, status);
-  int rc = run_stack(h, L.enc, enc_dims(d), sw, mask, B, T, st, g != nullptr ? gvec : nullptr, d.cond_layer_idx);
+                     h->blob + L.emb.off, d.n_vocab, T, H, sqrtf((float)H), sw.xm, sw.xm_p, mask, M, status);
+  rc = run_stack(h, L.enc, enc_dims(d), sw, mask, B, T, st, g != nullptr ? gvec : nullptr, d.cond_layer_idx);
   if (rc != TTSDEC_OK) return rc;
   // models.py:377-379: stats = proj(x) * x_mask; m, logs = split(stats)
-  gemm_generic(sw.cx, sw.xm, sw.xm_p, H, H, h->blob + L.proj_w, (size_t)2 * I * H, h->blob + L.proj_b, M, 2 * I, stats, nullptr, 2 * I, 0, mask,
-               nullptr, 1, T, st);
+  gemm_generic(sw.cx, h->blob, L.proj, sw.xm, sw.xm_p, stats, M, T, st, {0, mask});
   if (hipMemcpyAsync(x, sw.xm, (size_t)M * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return record_hip_error(h, "copy x");
   if (hipMemcpy2DAsync(m, (size_t)I * sizeof(float), stats, (size_t)2 * I * sizeof(float), (size_t)I * sizeof(float), M,
                        hipMemcpyDeviceToDevice, st) != hipSuccess)
@@ -1634,12 +1612,11 @@ int ttsvits_flow_forward(ttsvits_handle* h, const float* z, const int32_t* lengt
 // PosteriorEncoder (models.py:858-897): ttspost_*
 // ===========================================================================
 namespace {
-constexpr int kMaxPostWn = 32;
-struct PostBlob {  // offsets in floats; GEMM weights take 2n floats (fp32 | hi | lo), as in make_layout
-  size_t pre_w, pre_b, cond_w, cond_b;
-  size_t in_w[kMaxPostWn], in_b[kMaxPostWn], rs_w[kMaxPostWn], rs_b[kMaxPostWn];
-  size_t proj_w, proj_b;
-  size_t total;
+struct PostBlob {
+  Lin pre, proj;  // pre: [hidden, spec_pad], columns spec .. spec_pad-1 stay zero
+  WnBlob wn;
+  size_t total;  // floats
+  int n_src;     // source tensors of ttspost_pack_weights
 };
 }  // namespace
 
@@ -1653,18 +1630,12 @@ namespace {
 PostBlob make_post_layout(const ttspost_dims& d, int spec_pad) {
   PostBlob L;
   memset(&L, 0, sizeof(L));
-  Carver cv{nullptr};
-  auto take_w = [&](size_t n) { return cv.take_off(2 * n); };
-  const size_t H = d.hidden_channels, I = d.inter_channels, nl = d.n_layers;
-  L.pre_w = take_w(H * spec_pad); L.pre_b = cv.take_off(H);  // [H, spec_pad]: columns spec .. spec_pad-1 stay zero
-  if (d.gin_channels > 0) { L.cond_w = take_w(2 * H * nl * d.gin_channels); L.cond_b = cv.take_off(2 * H * nl); }
-  for (int j = 0; j < d.n_layers; ++j) {
-    const size_t cr = j < d.n_layers - 1 ? 2 * H : H;
-    L.in_w[j] = take_w(2 * H * d.kernel_size * H); L.in_b[j] = cv.take_off(2 * H);
-    L.rs_w[j] = take_w(cr * H); L.rs_b[j] = cv.take_off(cr);
-  }
-  L.proj_w = take_w(2 * I * H); L.proj_b = cv.take_off(2 * I);
-  L.total = cv.off;
+  Walk wk;
+  L.pre = wk.lin(d.hidden_channels, spec_pad);
+  walk_wn(wk, L.wn, d.hidden_channels, d.kernel_size, d.n_layers, d.gin_channels);
+  L.proj = wk.lin(2 * d.inter_channels, d.hidden_channels);
+  L.total = wk.cv.off;
+  L.n_src = wk.src;
   return L;
 }
 struct PostWs {
@@ -1713,44 +1684,24 @@ int ttspost_destroy(ttspost_handle* h) {
 const char* ttspost_last_hip_error(const ttspost_handle* h) { return last_hip_error(h); }
 int ttspost_set_precision(ttspost_handle* h, int precision) { return set_precision(h, precision); }
 int ttspost_get_precision(const ttspost_handle* h) { return get_precision(h); }
-int ttspost_num_weight_tensors(const ttspost_handle* h) {
-  return h ? 4 + 4 * h->d.n_layers + (h->d.gin_channels > 0 ? 2 : 0) : TTSDEC_ERR_INVALID_ARG;
-}
+int ttspost_num_weight_tensors(const ttspost_handle* h) { return h ? h->bl.n_src : TTSDEC_ERR_INVALID_ARG; }
 size_t ttspost_packed_bytes(const ttspost_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
 
 int ttspost_pack_weights(ttspost_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int rc = pack_begin(h, src, n_src, ttspost_num_weight_tensors(h), false, blob, ttspost_packed_bytes(h), st);
   if (rc != TTSDEC_OK) return rc;
-  const ttspost_dims& d = h->d;
   const PostBlob& L = h->bl;
   float* b = static_cast<float*>(blob);
-  const size_t H = d.hidden_channels, I = d.inter_channels, S = d.spec_channels, Sp = h->spec_pad;
-  int k = 0;
-  // pre.weight [H, S, 1] -> rows of Sp floats (the padding columns stay zero)
-  if (hipMemcpy2DAsync(b + L.pre_w, Sp * sizeof(float), src[k++], S * sizeof(float), S * sizeof(float), H, hipMemcpyDeviceToDevice, st) != hipSuccess)
+  // pre.weight [H, S, 1] -> rows of spec_pad floats (the padding columns stay zero)
+  const size_t S = h->d.spec_channels;
+  if (hipMemcpy2DAsync(b + L.pre.w, L.pre.K * sizeof(float), src[L.pre.src], S * sizeof(float), S * sizeof(float), L.pre.N,
+                       hipMemcpyDeviceToDevice, st) != hipSuccess)
     return record_hip_error(h, "copy pre.weight");
-  launch_copy(src[k++], b + L.pre_b, H, st);
-  pack_planes(b, L.pre_w, H * Sp, st);
-  if (d.gin_channels > 0) {
-    const size_t nc = 2 * H * d.n_layers;
-    launch_copy(src[k++], b + L.cond_w, nc * d.gin_channels, st);
-    launch_copy(src[k++], b + L.cond_b, nc, st);
-    pack_planes(b, L.cond_w, nc * d.gin_channels, st);
-  }
-  for (int j = 0; j < d.n_layers; ++j) {
-    const size_t cr = j < d.n_layers - 1 ? 2 * H : H;
-    launch_conv_transpose(src[k], b + L.in_w[j], (int)(2 * H), (int)H, d.kernel_size, st);
-    launch_copy(src[k + 1], b + L.in_b[j], 2 * H, st);
-    launch_copy(src[k + 2], b + L.rs_w[j], cr * H, st);
-    launch_copy(src[k + 3], b + L.rs_b[j], cr, st);
-    pack_planes(b, L.in_w[j], 2 * H * d.kernel_size * H, st);
-    pack_planes(b, L.rs_w[j], cr * H, st);
-    k += 4;
-  }
-  launch_copy(src[k++], b + L.proj_w, 2 * I * H, st);
-  launch_copy(src[k++], b + L.proj_b, 2 * I, st);
-  pack_planes(b, L.proj_w, 2 * I * H, st);
+  launch_copy(src[L.pre.src + 1], b + L.pre.b, L.pre.N, st);
+  pack_planes(b, L.pre, st);
+  pack_wn(src, b, L.wn, st);
+  pack_lin(src, b, L.proj, st);
   return pack_end(h, b);
 }
 
@@ -1765,17 +1716,13 @@ size_t ttspost_workspace_bytes(const ttspost_handle* h, int B, int T) {
 
 int ttspost_forward(ttspost_handle* h, const float* y, const int32_t* lengths, const float* g, const float* eps, int eps_T, int B, int T,
                     float* z, float* m, float* logs, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!h || !y || !lengths || !eps || !z || !m || !logs || !workspace || B <= 0 || T <= 0 || eps_T < T) return TTSDEC_ERR_INVALID_ARG;
-  if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
-  if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
-  if (workspace_bytes < ttspost_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
-  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
-  if (!frames_fit(B, T)) return TTSDEC_ERR_DIMS;
+  const int rc = check_call(h, y && lengths && eps && z && m && logs && eps_T >= T, g, workspace, workspace_bytes, ttspost_workspace_bytes(h, B, T), B, T);
+  if (rc != TTSDEC_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ttspost_dims& d = h->d;
   const PostBlob& L = h->bl;
   const float* blob = h->blob;
-  const int M = B * T, H = d.hidden_channels, I = d.inter_channels, S = d.spec_channels, Sp = h->spec_pad;
+  const int M = B * T, I = d.inter_channels, S = d.spec_channels, Sp = h->spec_pad;
   const bool split = h->precision == TTSDEC_PREC_SPLIT_F16;
   Carver cv{static_cast<float*>(workspace)};
   const PostWs w = carve_post(cv, d, Sp, B, T, split);
@@ -1786,13 +1733,11 @@ int ttspost_forward(ttspost_handle* h, const float* y, const int32_t* lengths, c
   // x = pre(y) * x_mask                                                             models.py:890
   const dim3 tgrid((T + kTr - 1) / kTr, (Sp + kTr - 1) / kTr, B);
   hipLaunchKernelGGL(post_stage_kernel, tgrid, dim3(256), 0, st, y, xs, split ? xs_p : (f16*)nullptr, S, Sp, T, M);
-  gemm_generic(ws.cx, xs, split ? xs_p : nullptr, Sp, Sp, blob + L.pre_w, (size_t)H * Sp, blob + L.pre_b, M, H, ws.hx, ws.hx_p, H, 0, mask, nullptr, 1,
-               T, st);
+  gemm_generic(ws.cx, blob, L.pre, xs, split ? xs_p : nullptr, ws.hx, M, T, st, {0, mask, nullptr, ws.hx_p});
   // x = enc(x, x_mask, g=g)                                                         :891
-  run_wn(blob, wn_layout(L, H, d.kernel_size, d.n_layers, d.gin_channels), ws, g, mask, B, T, st);
+  run_wn(blob, L.wn, ws, g, mask, B, T, st);
   // stats = proj(x) * x_mask                                                        :892
-  gemm_generic(ws.cx, ws.ho, ws.ho_p, H, H, blob + L.proj_w, (size_t)2 * I * H, blob + L.proj_b, M, 2 * I, stats, nullptr, 2 * I, 0, mask, nullptr,
-               1, T, st);
+  gemm_generic(ws.cx, blob, L.proj, ws.ho, ws.ho_p, stats, M, T, st, {0, mask});
   // m, logs = split(stats); z = (m + eps * exp(logs)) * x_mask                      :893-894
   const dim3 sgrid((T + kTr - 1) / kTr, (I + kTr - 1) / kTr, B);
   hipLaunchKernelGGL(post_sample_kernel, sgrid, dim3(256), 0, st, stats, eps, eps_T, mask, z, m, logs, I, T);
