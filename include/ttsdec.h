@@ -48,7 +48,8 @@ extern "C" {
  * ttsdec_griffinlim, mel -> waveform for the Tacotron path; then ttsdec_mel_analysis_workspace_bytes and ttsdec_mel_analysis,
  * waveform -> dB spectrogram and mel for it; then ttsvits_generator_planes_bytes, _pack_planes, _workspace_bytes and _forward,
  * the generator with its arithmetic as a call argument; then ttsdec_resample_workspace_bytes and ttsdec_resample, sample-rate
- * conversion in front of ttsdec_mel_analysis.) */
+ * conversion in front of ttsdec_mel_analysis; then ttsvits_disc_*, the waveform discriminators, a second handle kind under
+ * ttsvits_ with a struct of its own.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -802,6 +803,55 @@ int ttsvits_generator_pack_planes(ttsgen_handle* gen, void* planes, void* stream
 size_t ttsvits_generator_workspace_bytes(const ttsgen_handle* gen, int precision, int B, int T);
 int ttsvits_generator_forward(ttsgen_handle* gen, int precision, const void* planes, const float* z, const float* g, int B, int T,
                               int n_stages, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * VITS2 waveform discriminators: DiscriminatorP.forward and DiscriminatorS.forward, vits2/models.py:977-1083 (the members of
+ * MultiPeriodDiscriminator, models.py:1086-1110).  Eval mode, exact fp32, inference only; weight norm only (spectral norm is not
+ * built).  A second handle kind of the ttsvits_ family, as ttsenc_style_* is one of ttsenc_; it has no set_precision.
+ *   period p > 0: DiscriminatorP(p, kernel_size, stride) - the waveform [B, T] reflect-padded on the right to a multiple of p and
+ *     folded to [B, 1, H, p], H = ceil(T / p) (pad and fold are an index computation of the first layer); five (k, 1) convs
+ *     1 -> 32 -> 128 -> 512 -> 1024 -> 1024 with strides (s, s, s, s, 1), padding (k - 1) / 2 and leaky_relu(0.1), then conv_post
+ *     1024 -> 1 with 3 taps.
+ *   period 0: DiscriminatorS - Conv1d 1 -> 16 (k 15), four grouped stride-4 k-41 convs 16 -> 64 -> 256 -> 1024 -> 1024 (4, 16, 64,
+ *     256 groups), Conv1d 1024 -> 1024 (k 5), each with leaky_relu(0.1), then conv_post 1024 -> 1 (k 3); kernel_size and stride
+ *     are ignored.
+ * Activations are CHANNELS-LAST and PERIOD-MAJOR: feature map i is [B, p, H_i, C_i] (DiscriminatorS: p = 1, [B, L_i, C_i]), the
+ * reference's [B, C_i, H_i, p] ([B, C_i, L_i]) permuted; H_{i+1} = (H_i + 2 pad - k) / stride + 1.  The dense convs (Ci >= 32, no
+ * groups) are implicit GEMMs of the exact-fp32 tile with one fixed tile shape; layer 0, the grouped convs and conv_post are
+ * direct kernels with a fixed summation order.  Nothing depends on B: a row gets the same bits alone and in any batch, and the
+ * same call twice gives the same bits.
+ * ------------------------------------------------------------------------------------- */
+#define TTSVITS_DISC_MAX_CONVS 6
+typedef struct ttsvits_disc_dims {
+  int32_t period;      /* 0 = DiscriminatorS; else DiscriminatorP's period (2, 3, 5, 7, 11), 1..4096        */
+  int32_t kernel_size; /* DiscriminatorP: 5; odd, 1..15                                                      */
+  int32_t stride;      /* DiscriminatorP: 3; 1..16                                                           */
+} ttsvits_disc_dims;
+typedef struct ttsvits_disc_handle ttsvits_disc_handle;
+
+/* Dimensions not built (an even or too large kernel_size, a stride or period out of range) are refused with TTSDEC_ERR_DIMS. */
+int ttsvits_disc_create(const ttsvits_disc_dims* dims, ttsvits_disc_handle** out);
+int ttsvits_disc_destroy(ttsvits_disc_handle* h);
+const char* ttsvits_disc_last_hip_error(const ttsvits_disc_handle* h);
+/* Source tensors for ttsvits_disc_pack_weights (device fp32, the reference's parameter shapes, EFFECTIVE weights - g * v / ||v||
+ * of weight_norm folded), in this order: convs.i.weight, convs.i.bias for every conv i, then conv_post.weight, conv_post.bias
+ * (12 tensors for DiscriminatorP, 14 for DiscriminatorS).  None may be NULL. */
+int ttsvits_disc_num_weight_tensors(const ttsvits_disc_handle* h);
+size_t ttsvits_disc_packed_bytes(const ttsvits_disc_handle* h);
+int ttsvits_disc_pack_weights(ttsvits_disc_handle* h, const float* const* src, int n_src, void* blob, void* stream);
+int ttsvits_disc_bind_weights(ttsvits_disc_handle* h, const void* blob);
+/* Scratch of a scores-only call (fmaps == NULL): two buffers that the layers' outputs alternate between.  0 when the call is
+ * refused: B or T <= 0; a T the reference's reflect pad itself refuses (T % p != 0 and p - T % p >= T); or B * T or an
+ * activation's element count beyond 2^31 - 1 (32-bit row and element indices; split the batch). */
+size_t ttsvits_disc_workspace_bytes(const ttsvits_disc_handle* h, int B, int T);
+/* forward (models.py:1034-1053 / 1072-1083): y [B, T] (the reference's [B, 1, T]) -> scores [B, H_last * p] in the reference's
+ * flatten order (index h * p + w) - the same memory as its last feature map [B, 1, H_last, p].
+ *   fmaps: NULL, or num_convs (5 / 6) device pointers, 16-byte aligned, that receive the activated output of every conv in the
+ * layout above; the workspace is then not used and may be NULL.  With fmaps == NULL the activations stay in the workspace
+ * (256-byte aligned, at least ttsvits_disc_workspace_bytes).
+ * TTSDEC_ERR_DIMS for a call the size function refuses.  Enqueues only - no synchronisation, no host reads. */
+int ttsvits_disc_forward(ttsvits_disc_handle* h, const float* y, int B, int T, float* scores, float* const* fmaps, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * VITS2 duration predictors and length regulation: the `self.dp(...)` and the prior expansion of SynthesizerTrn.infer,

@@ -95,6 +95,10 @@ class GenDims(C.Structure):  # include/ttsdec.h ttsgen_dims
                 ("resblock", C.c_int32), ("gin_channels", C.c_int32)]
 
 
+class DiscDims(C.Structure):  # include/ttsdec.h ttsvits_disc_dims
+    _fields_ = [(n, C.c_int32) for n in ("period", "kernel_size", "stride")]
+
+
 DUR_SDP, DUR_DP = 0, 1  # include/ttsdec.h ttsdur_dims.kind
 PATH_F32, PATH_F16, PATH_BF16 = 0, 1, 2  # include/ttsdec.h TTSVITS_PATH_*
 ALIGN_MAX_TX = 1024  # tokens per utterance ttsvits_maximum_path is built for
@@ -212,6 +216,11 @@ FAMILIES = (
         "generator_pack_planes": (i32, [vp, vp, vp]),  # gen, planes, stream
         "generator_workspace_bytes": (sz, [vp, i32, i32, i32]),  # (gen, precision, B, T)
         "generator_forward": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]),  # gen, precision, planes, z, g, B, T, n_stages, out, ws, bytes, stream
+        # the waveform discriminators: a second handle of this family (vits2.DiscEngine builds its names with PREFIX = "ttsvits_disc")
+        "disc_create": (i32, [C.POINTER(DiscDims), C.POINTER(vp)]),
+        **{f"disc_{n}": sig for n, sig in _SHARED_SIGS.items()},
+        "disc_workspace_bytes": _ws_bytes,
+        "disc_forward": (i32, [vp, vp, i32, i32, vp, C.POINTER(vp), vp, sz, vp]),  # h, y, B, T, scores, fmaps, ws, bytes, stream
     }),
     Family("ttsgen", GenDims, False, {
         "workspace_bytes": _ws_bytes,

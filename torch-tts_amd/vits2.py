@@ -20,6 +20,10 @@
 * ``forced_alignment(net_g, x, ..., y, ...)`` - token durations of an utterance: enc_p, enc_q, flow forward, align
 * ``spectrogram_torch`` / ``spec_to_mel_torch`` / ``mel_spectrogram_torch`` - mel_processing.py:58-187 (re-exported from
                                              ``mel_processing``), and ``voice_conversion_from_audio`` / ``forced_alignment_from_audio``
+* ``DiscriminatorS`` / ``DiscriminatorP`` / ``MultiPeriodDiscriminator`` - the waveform discriminators, vits2/models.py:977-1110
+                                             (``forward(x) -> (scores, fmap)``, ``forward(y, y_hat)`` -> the four lists;
+                                             ``ttsvits_disc_*``), with ``feature_loss`` / ``discriminator_loss`` / ``generator_loss``
+                                             (losses.py:7-34) as torch ops on the device
 
 All hold the reference's parameters (so checkpoints load) and run inference through the HIP library
 (``ttsvits_*`` / ``ttsgen_*`` / ``ttsdur_*`` / ``ttspost_*`` in include/ttsdec.h).  The library works on channel-last activations;
@@ -27,6 +31,7 @@ the [B, C, T] tensors of the reference API are transposed here.  Training (gradi
 conditioning are outside the path and raise."""
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict, List, Optional
 
@@ -629,6 +634,187 @@ class Generator(PackedWeightsMixin, nn.Module):
         [B, T_s, C_s] - leaky_relu(x, 0.1), or 0.01 after the last stage."""
         eng = self._engine(x)
         return eng.forward(x.transpose(1, 2).contiguous(), self._speaker(g, x.shape[0]), n_stages=n_stages, precision=self.precision)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Waveform discriminators (models.py:977-1110) through ttsvits_disc_* (include/ttsdec.h), and the three GAN terms of losses.py:7-34
+# ---------------------------------------------------------------------------------------------------------------------------
+class DiscEngine(Handle):
+    """One ttsvits_disc handle on one device: DiscriminatorP(period) or, with period 0, DiscriminatorS."""
+
+    PREFIX = "ttsvits_disc"
+
+    def __init__(self, dims: Dict, device: Optional[torch.device]):
+        super().__init__(dims, _lib.DiscDims(dims["period"], dims["kernel_size"], dims["stride"]), device)
+        self.p = dims["period"] or 1
+        if dims["period"]:  # (Co, kernel, stride) of every conv and of conv_post
+            k, s = dims["kernel_size"], dims["stride"]
+            self.layers = [(32, k, s), (128, k, s), (512, k, s), (1024, k, s), (1024, k, 1), (1, 3, 1)]
+        else:
+            self.layers = [(16, 15, 1), (64, 41, 4), (256, 41, 4), (1024, 41, 4), (1024, 41, 4), (1024, 5, 1), (1, 3, 1)]
+
+    def workspace_bytes(self, B: int, T: int) -> int:
+        return int(self._fn("workspace_bytes")(self._h, B, T))
+
+    def heights(self, T: int) -> List[int]:
+        """Rows per column after every conv and after conv_post (H = ceil(T / p) before them)."""
+        H, out = -(-T // self.p), []
+        for _, k, s in self.layers:
+            H = (H + 2 * ((k - 1) // 2) - k) // s + 1
+            out.append(H)
+        return out
+
+    def forward(self, y: torch.Tensor, with_fmaps: bool = True):
+        """y [B, T] contiguous fp32 -> (scores [B, H_last * p], the convs' activated outputs [B, p, H_i, C_i] channels-last, or None:
+        a scores-only call keeps them in the workspace)."""
+        B, T = y.shape
+        p = self.p
+        if T % p and p - T % p >= T:
+            raise ValueError(f"{T} samples cannot be reflect-padded to a multiple of the period {p}: the pad ({p - T % p}) must be smaller than T")
+        nbytes = self.workspace_bytes(B, T)
+        if nbytes == 0:
+            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsvits_disc_forward", f"B = {B}, T = {T}: an activation's indices leave 32 bits; split the batch")
+        Hs = self.heights(T)
+        with torch.cuda.device(self.device):
+            scores = torch.empty(B, Hs[-1] * p, device=self.device)
+            fm, arr, ws = None, None, None
+            if with_fmaps:
+                fm = [torch.empty(B, p, H, C, device=self.device) for H, (C, _, _) in zip(Hs[:-1], self.layers[:-1])]
+                arr = (ctypes.c_void_p * len(fm))(*[t.data_ptr() for t in fm])
+            else:
+                ws = self.workspace("forward", nbytes)
+            rc = self._fn("forward")(self._h, y.data_ptr(), B, T, scores.data_ptr(), arr, _ptr(ws), 0 if ws is None else ws.numel(), _stream(self.device))
+        self._err(rc, "ttsvits_disc_forward")
+        return scores, fm
+
+
+class _DiscriminatorBase(PackedWeightsMixin, nn.Module):
+    """What DiscriminatorP and DiscriminatorS share: ``convs`` and ``conv_post`` (weight-normalised, the reference's state-dict
+    keys), packed from their effective weights, and the call.  Inference only, exact fp32, eval mode."""
+
+    def _setup(self, dims: Dict, use_spectral_norm: bool) -> None:
+        if use_spectral_norm:
+            raise NotImplementedError("use_spectral_norm=True is not built in the HIP library (weight norm only)")
+        self.use_spectral_norm = False
+        self._watch_state_dict_loads()
+        self._cfg = dims
+        self._engines = EngineCache(DiscEngine)
+
+    def weight_tensors(self) -> List[torch.Tensor]:
+        """The effective fp32 weights in ttsvits_disc_pack_weights' order (include/ttsdec.h)."""
+        out = []
+        for c in list(self.convs) + [self.conv_post]:
+            out += [_effective_weight(c), c.bias]
+        return out
+
+    def _run(self, x: torch.Tensor, with_fmaps: bool):
+        if x.dim() != 3 or x.shape[1] != 1 or x.shape[0] < 1 or x.shape[2] < 1:
+            raise ValueError(f"x must be [B, 1, T], got {tuple(x.shape)}")
+        p = self._cfg["period"] or 1
+        T = x.shape[2]
+        if T % p and p - T % p >= T:  # (before any launch, the weight packing included)
+            raise ValueError(f"{T} samples cannot be reflect-padded to a multiple of the period {p}: the pad ({p - T % p}) must be smaller than T")
+        inference_only(self, "discriminator", x, fp32=True)
+        eng = self._engines.get(self._cfg, x.device)
+        eng.ensure_packed(self.weight_tensors, key_tensors=list(self.parameters()))
+        return eng.forward(x[:, 0].contiguous(), with_fmaps)
+
+    def forward(self, x):
+        """x [B, 1, T] -> (scores [B, L], fmap): the reference's shapes.  Every fmap but the last is a PERMUTED VIEW of the
+        library's channels-last buffer (same shape and values as the reference's, other strides; ``.contiguous()`` copies);
+        the last one is a view of the scores."""
+        scores, fm = self._run(x, True)
+        return scores, self._as_reference(scores, fm)
+
+    def scores(self, x) -> torch.Tensor:
+        """forward's scores alone: the feature maps stay in a workspace and are not returned."""
+        return self._run(x, False)[0]
+
+
+class DiscriminatorP(_DiscriminatorBase):
+    """models.DiscriminatorP (models.py:977-1053): same constructor, parameters and state-dict keys."""
+
+    def __init__(self, period, kernel_size=5, stride=3, use_spectral_norm=False):
+        super().__init__()
+        self._setup(dict(period=int(period), kernel_size=int(kernel_size), stride=int(stride)), use_spectral_norm)
+        self.period = period
+        wn, pad = nn.utils.weight_norm, (_get_padding(kernel_size, 1), 0)
+        ch = [1, 32, 128, 512, 1024, 1024]
+        self.convs = nn.ModuleList(wn(nn.Conv2d(ch[i], ch[i + 1], (kernel_size, 1), (stride if i < 4 else 1, 1), padding=pad)) for i in range(5))
+        self.conv_post = wn(nn.Conv2d(1024, 1, (3, 1), 1, padding=(1, 0)))
+
+    def _as_reference(self, scores, fm):
+        B = scores.shape[0]
+        return [t.permute(0, 3, 2, 1) for t in fm] + [scores.view(B, 1, -1, self.period)]  # [B, p, H, C] -> [B, C, H, p]
+
+
+class DiscriminatorS(_DiscriminatorBase):
+    """models.DiscriminatorS (models.py:1056-1083): same constructor, parameters and state-dict keys."""
+
+    def __init__(self, use_spectral_norm=False):
+        super().__init__()
+        self._setup(dict(period=0, kernel_size=0, stride=0), use_spectral_norm)
+        wn = nn.utils.weight_norm
+        self.convs = nn.ModuleList([
+            wn(nn.Conv1d(1, 16, 15, 1, padding=7)),
+            wn(nn.Conv1d(16, 64, 41, 4, groups=4, padding=20)),
+            wn(nn.Conv1d(64, 256, 41, 4, groups=16, padding=20)),
+            wn(nn.Conv1d(256, 1024, 41, 4, groups=64, padding=20)),
+            wn(nn.Conv1d(1024, 1024, 41, 4, groups=256, padding=20)),
+            wn(nn.Conv1d(1024, 1024, 5, 1, padding=2)),
+        ])
+        self.conv_post = wn(nn.Conv1d(1024, 1, 3, 1, padding=1))
+
+    def _as_reference(self, scores, fm):
+        return [t[:, 0].permute(0, 2, 1) for t in fm] + [scores.unsqueeze(1)]  # [B, 1, L, C] -> [B, C, L]
+
+
+class MultiPeriodDiscriminator(nn.Module):
+    """models.MultiPeriodDiscriminator (models.py:1086-1110): DiscriminatorS and DiscriminatorP(2, 3, 5, 7, 11) under
+    ``discriminators``; ``forward(y, y_hat)`` returns the reference's four lists.  Each member runs ONCE on the 2B rows of y and
+    y_hat together - no kernel's arithmetic depends on the batch, so that is bit-identical to two calls - and the results are
+    split by rows (views)."""
+
+    def __init__(self, use_spectral_norm=False):
+        super().__init__()
+        discs = [DiscriminatorS(use_spectral_norm=use_spectral_norm)]
+        discs += [DiscriminatorP(i, use_spectral_norm=use_spectral_norm) for i in [2, 3, 5, 7, 11]]
+        self.discriminators = nn.ModuleList(discs)
+
+    def forward(self, y, y_hat):
+        if y.shape != y_hat.shape:
+            raise ValueError(f"y and y_hat must have one shape, got {tuple(y.shape)} and {tuple(y_hat.shape)}")
+        B = y.shape[0]
+        both = torch.cat([y, y_hat], 0)
+        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
+        for d in self.discriminators:
+            s, fmap = d(both)
+            y_d_rs.append(s[:B])
+            y_d_gs.append(s[B:])
+            fmap_rs.append([f[:B] for f in fmap])
+            fmap_gs.append([f[B:] for f in fmap])
+        return y_d_rs, y_d_gs, fmap_rs, fmap_gs
+
+
+def feature_loss(fmap_r, fmap_g):
+    """losses.py:7-13: twice the summed mean absolute distance of the feature maps (torch ops on the device)."""
+    loss = 0
+    for dr, dg in zip(fmap_r, fmap_g):
+        for rl, gl in zip(dr, dg):
+            loss = loss + torch.mean(torch.abs(rl.detach() - gl))
+    return loss * 2
+
+
+def discriminator_loss(disc_real_outputs, disc_generated_outputs):
+    """losses.py:16-25: the least-squares terms per discriminator, (real [n], generated [n])."""
+    r_losses = [torch.mean((1 - dr) ** 2) for dr in disc_real_outputs]
+    g_losses = [torch.mean(dg**2) for dg in disc_generated_outputs]
+    return torch.stack(r_losses), torch.stack(g_losses)
+
+
+def generator_loss(disc_outputs):
+    """losses.py:28-34: mean((1 - D(G))^2) per discriminator, [n]."""
+    return torch.stack([torch.mean((1 - dg) ** 2) for dg in disc_outputs])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
