@@ -49,7 +49,7 @@ extern "C" {
  * waveform -> dB spectrogram and mel for it; then ttsvits_generator_planes_bytes, _pack_planes, _workspace_bytes and _forward,
  * the generator with its arithmetic as a call argument; then ttsdec_resample_workspace_bytes and ttsdec_resample, sample-rate
  * conversion in front of ttsdec_mel_analysis; then ttsvits_disc_*, the waveform discriminators, a second handle kind under
- * ttsvits_ with a struct of its own.) */
+ * ttsvits_ with a struct of its own; then ttsvits_durdisc_*, the duration discriminators, a third one.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -852,6 +852,64 @@ size_t ttsvits_disc_workspace_bytes(const ttsvits_disc_handle* h, int B, int T);
  * TTSDEC_ERR_DIMS for a call the size function refuses.  Enqueues only - no synchronisation, no host reads. */
 int ttsvits_disc_forward(ttsvits_disc_handle* h, const float* y, int B, int T, float* scores, float* const* fmaps, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * VITS2 duration discriminators: DurationDiscriminatorV1 and DurationDiscriminatorV2, vits2/models.py:183-329 (the net_dur_disc of
+ * the reference's train.py, its DUR_*.pth checkpoint).  Eval mode, exact fp32, inference only.  A third handle kind of the
+ * ttsvits_ family; it has no set_precision.  C = in_channels, F = filter_channels, every conv has 3 taps and padding 1; neither
+ * class uses gin_channels / g.  Activations are CHANNEL-LAST, one row per token: x [B, T, C] as ttsvits_text_encoder writes it.
+ *   trunk (once per call):          V2: h = norm_2(relu(conv_2(norm_1(relu(conv_1(x m))) m)));  V1: h = conv_2(conv_1(x m) m)
+ *   probability (per duration):     u = pre_out_conv_1(cat([h, dur_proj(dur)], 1) m)  [V2: u = pre_out_norm_1(relu(u))]
+ *                                   u = pre_out_conv_2(u m)                           [V2: u = pre_out_norm_2(relu(u))]
+ *                                   p = sigmoid(output_layer(u m))   - sigmoid(output_layer's bias) at a masked token
+ * m is the token mask t < lengths[b], applied as a SELECT: what x, hidden and dur hold at masked tokens is never read into a
+ * result.  The four wide convs (conv_1, conv_2, the h half of pre_out_conv_1, pre_out_conv_2) are implicit GEMMs of the exact-fp32
+ * tile with one fixed tile shape.  cat([h, d]) is never built: dur_proj is rank one, so its half of pre_out_conv_1 is folded at
+ * pack time into a slope and an offset table [3][F] (S[tap][n] = sum_c W[n, F + c, tap] w_dur[c], O with b_dur; c ascending), and
+ * the h half is computed once per call for all its durations.  Nothing depends on B: an utterance in a padded batch gets bit for
+ * bit what it gets alone at T = its own length, n_dur = 2 gives the bits of two n_dur = 1 calls, and the same call twice gives the
+ * same bits (no atomics).
+ * ------------------------------------------------------------------------------------- */
+#define TTSVITS_DURDISC_MAX_CHANNELS 1024
+typedef struct ttsvits_durdisc_dims {
+  int32_t version;         /* 1 = DurationDiscriminatorV1, 2 = DurationDiscriminatorV2                                  */
+  int32_t in_channels;     /* the text encoder's hidden_channels (192); a multiple of 4, <= TTSVITS_DURDISC_MAX_CHANNELS */
+  int32_t filter_channels; /* 192 or 256 in the reference's configurations; a multiple of 4, <= the same cap            */
+  int32_t kernel_size;     /* 3                                                                                        */
+} ttsvits_durdisc_dims;
+typedef struct ttsvits_durdisc_handle ttsvits_durdisc_handle;
+
+/* TTSDEC_ERR_DIMS - never another computation - for a version other than 1 or 2, a kernel_size other than 3, and channel counts
+ * that are not positive multiples of 4 or exceed the cap. */
+int ttsvits_durdisc_create(const ttsvits_durdisc_dims* dims, ttsvits_durdisc_handle** out);
+int ttsvits_durdisc_destroy(ttsvits_durdisc_handle* h);
+const char* ttsvits_durdisc_last_hip_error(const ttsvits_durdisc_handle* h);
+/* Source tensors for ttsvits_durdisc_pack_weights (device fp32, the reference's parameter shapes), in this order - the state
+ * dict's, the [V2] pairs only for version 2 and V1's unused pre_out_norm_* left out: conv_1.weight [F, C, 3], conv_1.bias,
+ * [V2: norm_1.gamma, norm_1.beta,] conv_2.weight [F, F, 3], conv_2.bias, [V2: norm_2.gamma, norm_2.beta,] dur_proj.weight [F, 1, 1],
+ * dur_proj.bias, pre_out_conv_1.weight [F, 2F, 3], pre_out_conv_1.bias, [V2: pre_out_norm_1.gamma, .beta,] pre_out_conv_2.weight
+ * [F, F, 3], pre_out_conv_2.bias, [V2: pre_out_norm_2.gamma, .beta,] output_layer.0.weight [1, F], output_layer.0.bias [1]:
+ * 12 tensors for V1, 20 for V2.  None may be NULL. */
+int ttsvits_durdisc_num_weight_tensors(const ttsvits_durdisc_handle* h);
+size_t ttsvits_durdisc_packed_bytes(const ttsvits_durdisc_handle* h);
+int ttsvits_durdisc_pack_weights(ttsvits_durdisc_handle* h, const float* const* src, int n_src, void* blob, void* stream);
+int ttsvits_durdisc_bind_weights(ttsvits_durdisc_handle* h, const void* blob);
+/* Scratch of either call with n_dur (1 or 2) durations (the trunk's is that of n_dur = 1): a multiple of 256, monotone in B, T
+ * and n_dur; 0 for a NULL handle, a size <= 0, n_dur outside {1, 2} or n_dur * B * T > INT32_MAX / 4096 rows (the GEMM core counts
+ * rows and offsets in 32 bits; split the batch). */
+size_t ttsvits_durdisc_workspace_bytes(const ttsvits_durdisc_handle* h, int B, int T, int n_dur);
+/* forward up to the loop over the durations (models.py:243-250 / 317-322): x [B, T, C], lengths [B] int32 (device) -> hidden_out
+ * [B, T, F] = h * m (zero at masked tokens, where the reference's own h is never read).  x and hidden_out 16-byte aligned.
+ * Both calls: TTSDEC_ERR_INVALID_ARG for a NULL or misaligned pointer, B or T <= 0, n_dur outside {1, 2}, or a workspace that is
+ * NULL, not 256-byte aligned or smaller than ttsvits_durdisc_workspace_bytes; TTSDEC_ERR_NOT_BOUND before bind_weights;
+ * TTSDEC_ERR_DIMS for a call the size function refuses.  Enqueue only - no synchronisation, no host reads. */
+int ttsvits_durdisc_trunk(ttsvits_durdisc_handle* h, const float* x, const int32_t* lengths, int B, int T, float* hidden_out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* forward_probability (models.py:222-236 / 298-310) for n_dur durations at once: hidden [B, T, F] (16-byte aligned; the trunk's
+ * output, or the reference's h - it is masked again here), dur [n_dur, B, T] -> prob_out [n_dur, B, T] (the reference's [B, T, 1]
+ * per duration) and, unless logit_out is NULL, the pre-sigmoid logits in the same shape. */
+int ttsvits_durdisc_prob(ttsvits_durdisc_handle* h, const float* hidden, const int32_t* lengths, const float* dur, int n_dur, int B, int T,
+                         float* prob_out, float* logit_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * VITS2 duration predictors and length regulation: the `self.dp(...)` and the prior expansion of SynthesizerTrn.infer,

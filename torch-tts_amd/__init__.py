@@ -11,8 +11,8 @@ from .style import GST, GST_VAE, STL, VAE, MultiHeadAttention, ReferenceEncoder,
 from .tacotron import Encoder2, Tacotron, build_tacotron, lengths_to_mask
 from . import vits2  # noqa: F401  (TextEncoder, ResidualCouplingTransformersBlock, Generator, StochasticDurationPredictor, DurationPredictor, infer,
 #                             PosteriorEncoder, voice_conversion)
-from .vits2 import (DiscriminatorP, DiscriminatorS, DurationPredictor, Generator, MultiPeriodDiscriminator, PosteriorEncoder,
-                    StochasticDurationPredictor)
+from .vits2 import (DiscriminatorP, DiscriminatorS, DurationDiscriminatorV1, DurationDiscriminatorV2, DurationPredictor, Generator,
+                    MultiPeriodDiscriminator, PosteriorEncoder, StochasticDurationPredictor)
 from . import audio  # noqa: F401  (AudioFrontend.mel_inv / decode, m_rev, synth_audio)
 from . import mel_processing  # noqa: F401  (spectrogram_torch, spec_to_mel_torch, mel_spectrogram_torch: the VITS2 audio front-end)
 from . import train_util  # noqa: F401  (load_state_dict: the reference's partial checkpoint loader + blob invalidation)
@@ -21,6 +21,6 @@ __all__ = [
     "Decoder", "Taco2ProdDecoderCell", "Taco2DecoderCell", "PreNet", "LSTMZoneoutCell", "StepwiseMonotonicAttention", "MelPostnet", "MelPostnet2",
     "Tacotron", "Encoder2", "build_tacotron", "lengths_to_mask", "Engine", "EngineDims",
     "Generator", "StochasticDurationPredictor", "DurationPredictor", "PosteriorEncoder",
-    "DiscriminatorS", "DiscriminatorP", "MultiPeriodDiscriminator",
+    "DiscriminatorS", "DiscriminatorP", "MultiPeriodDiscriminator", "DurationDiscriminatorV1", "DurationDiscriminatorV2",
     "ReferenceEncoder", "STL", "GST", "VAE", "GST_VAE", "MultiHeadAttention", "StyleEngine",
 ]

@@ -99,6 +99,10 @@ class DiscDims(C.Structure):  # include/ttsdec.h ttsvits_disc_dims
     _fields_ = [(n, C.c_int32) for n in ("period", "kernel_size", "stride")]
 
 
+class DurDiscDims(C.Structure):  # include/ttsdec.h ttsvits_durdisc_dims
+    _fields_ = [(n, C.c_int32) for n in ("version", "in_channels", "filter_channels", "kernel_size")]
+
+
 DUR_SDP, DUR_DP = 0, 1  # include/ttsdec.h ttsdur_dims.kind
 PATH_F32, PATH_F16, PATH_BF16 = 0, 1, 2  # include/ttsdec.h TTSVITS_PATH_*
 ALIGN_MAX_TX = 1024  # tokens per utterance ttsvits_maximum_path is built for
@@ -221,6 +225,12 @@ FAMILIES = (
         **{f"disc_{n}": sig for n, sig in _SHARED_SIGS.items()},
         "disc_workspace_bytes": _ws_bytes,
         "disc_forward": (i32, [vp, vp, i32, i32, vp, C.POINTER(vp), vp, sz, vp]),  # h, y, B, T, scores, fmaps, ws, bytes, stream
+        # the duration discriminators: a third handle of this family (vits2.DurDiscEngine, PREFIX = "ttsvits_durdisc")
+        "durdisc_create": (i32, [C.POINTER(DurDiscDims), C.POINTER(vp)]),
+        **{f"durdisc_{n}": sig for n, sig in _SHARED_SIGS.items()},
+        "durdisc_workspace_bytes": (sz, [vp, i32, i32, i32]),  # (h, B, T, n_dur)
+        "durdisc_trunk": (i32, [vp, vp, vp, i32, i32, vp, vp, sz, vp]),  # h, x, lengths, B, T, hidden_out, ws, bytes, stream
+        "durdisc_prob": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),  # h, hidden, lengths, dur, n_dur, B, T, prob, logit, ws, bytes, stream
     }),
     Family("ttsgen", GenDims, False, {
         "workspace_bytes": _ws_bytes,

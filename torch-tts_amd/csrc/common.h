@@ -418,6 +418,29 @@ __device__ __forceinline__ float wave_max(float v) {
   return fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
 }
 
+// modules.LayerNorm (vits2/modules.py:24-27: F.layer_norm over the channels) of one row spread over a wave: every lane holds N of
+// the row's C channels in v (ok[i]: v[i] is a channel of the row; otherwise v[i] = 0).  -> the mean and 1 / sqrt(var + eps), the
+// same in every lane; layernorm_value is one channel's result.  Shared by the row kernels of vits2.hip and durdisc.hip.
+template <int N>
+__device__ __forceinline__ void wave_layernorm_stats(const float (&v)[N], const bool (&ok)[N], int C, float eps, float& mean, float& rstd) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < N; ++i) s += v[i];
+  s = wave_sum(s);
+  mean = s / (float)C;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const float dlt = ok[i] ? v[i] - mean : 0.f;
+    q += dlt * dlt;
+  }
+  q = wave_sum(q);
+  rstd = 1.0f / sqrt_rn(add_rn(q / (float)C, eps));
+}
+__device__ __forceinline__ float layernorm_value(float v, float mean, float rstd, float gamma, float beta) {
+  return add_rn(mul_rn(mul_rn(v - mean, rstd), gamma), beta);
+}
+
 template <int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (N > 0) {

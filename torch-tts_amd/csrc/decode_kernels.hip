@@ -429,7 +429,7 @@ static void launch_gemm_cfg(const GemmArgs& a, hipStream_t st) {
       return;
     }
   }
-  if (PREC != PREC_F32 || (a.M >= 64 && tiles_big >= 512)) {
+  if (PREC != PREC_F32 || (a.fixed_tile != 1 && a.M >= 64 && tiles_big >= 512)) {  // (fixed_tile: kernels.h)
     // 64x64 tiles; ring: fp32 4 x 16 KiB, bf16 5 x 16 KiB, split-fp16 4 x 32 KiB
     using Cfg = TileCfg<2, 2, 1, (PREC == PREC_BF16 ? 5 : 4), PREC>;
     dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM, (EK == EPI_PLAIN && a.ksplit > 1) ? a.ksplit : 1);
@@ -866,19 +866,20 @@ void launch_to_bf16(const float* src, void* dst, size_t n, hipStream_t st) {
   hipLaunchKernelGGL(to_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, static_cast<bf16*>(dst), n);
 }
 
-__global__ void conv_transpose_kernel(const float* w, float* out, int Co, int Ci, int k) {
+__global__ void conv_transpose_kernel(const float* w, float* out, int Co, int Ci, int k, size_t src_row) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t n = (size_t)Co * Ci * k;
   if (i >= n) return;
-  // out[co][tap][ci] = w[co][ci][tap]
+  // out[co][tap][ci] = w[co][ci][tap]  (output channel co of w starts at w + co * src_row)
   const int ci = (int)(i % Ci);
   const int tap = (int)((i / Ci) % k);
   const int co = (int)(i / ((size_t)Ci * k));
-  out[i] = w[((size_t)co * Ci + ci) * k + tap];
+  out[i] = w[(size_t)co * src_row + (size_t)ci * k + tap];
 }
-void launch_conv_transpose(const float* w, float* out, int Co, int Ci, int k, hipStream_t st) {
+void launch_conv_transpose(const float* w, float* out, int Co, int Ci, int k, hipStream_t st, size_t src_row) {
   const size_t n = (size_t)Co * Ci * k;
-  hipLaunchKernelGGL(conv_transpose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, out, Co, Ci, k);
+  hipLaunchKernelGGL(conv_transpose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, out, Co, Ci, k,
+                     src_row ? src_row : (size_t)Ci * k);
 }
 
 __global__ void conv1dfix_pack_kernel(const float* w, float* out, int Co, int Ci, int k) {

@@ -88,6 +88,10 @@ struct GemmArgs {
   float slope2, div;
   const float* sum;
   const float* rowvec;
+  // Exact fp32 only.  0: the tile is chosen by the size of the GEMM (decode_kernels.hip launch_gemm_cfg) - an output's summation
+  // order then depends on M.  1: always the 32 x 32 tile with K split over the four MFMA waves, so a row gets the same bits
+  // whatever M is (the duration discriminators, durdisc.hip: an utterance alone and in any batch).
+  int fixed_tile;
 };
 
 void launch_gemm(const GemmArgs& a, AKind ak, EpiKind ek, hipStream_t st);
@@ -345,7 +349,13 @@ int set_precision(HandleBase* h, int precision);
 int get_precision(const HandleBase* h);
 const char* last_hip_error(const HandleBase* h);
 void launch_fill_rows(float* dst, const float* row, int n_rows, int n_cols, hipStream_t st);  // dst[m, :] = row[:]
-void launch_conv_transpose(const float* w /*[Co,Ci,k]*/, float* out /*[Co,k,Ci]*/, int Co, int Ci, int k, hipStream_t st);
+// src_row: floats from one output channel of w to the next (0: Ci * k, w is dense) - more when only the first Ci of a wider
+// conv's input channels are wanted (durdisc.hip: the x half of pre_out_conv_1)
+void launch_conv_transpose(const float* w /*[Co,Ci,k]*/, float* out /*[Co,k,Ci]*/, int Co, int Ci, int k, hipStream_t st, size_t src_row = 0);
+// modules.LayerNorm over the C <= 1024 channels of each of M rows, one wave per row (vits2.hip): out = LN(in), out_m = LN(in) *
+// mask[row]; out_p / outm_p: their split-fp16 planes (hi, lo M * C halfs later).  Every output may be nullptr; mask too (= 1).
+void launch_layernorm(const float* in, const float* gamma, const float* beta, const float* mask, float* out, float* out_m, f16* out_p,
+                      f16* outm_p, int M, int C, hipStream_t st);
 // Conv1dFix (mps_fixes.py:22-29) pairs flat-weight column n*Ci + c with x[c, t + pad - n]:
 // out[co][tap][ci] = wflat[co][(k-1-tap)*Ci + ci]
 void launch_conv1dfix_pack(const float* w, float* out, int Co, int Ci, int k, hipStream_t st);

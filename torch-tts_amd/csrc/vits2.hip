@@ -172,30 +172,21 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* in, co
   if (row >= M) return;
   const float* x = in + (size_t)row * C;
   float v[NJ];  // C <= 64 NJ
-  float s = 0.f;
+  bool ok[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int c = lane + 64 * j;
-    v[j] = c < C ? x[c] : 0.f;
-    s += v[j];
+    ok[j] = c < C;
+    v[j] = ok[j] ? x[c] : 0.f;
   }
-  s = wave_sum(s);
-  const float mean = s / (float)C;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int c = lane + 64 * j;
-    const float dlt = c < C ? v[j] - mean : 0.f;
-    q += dlt * dlt;
-  }
-  q = wave_sum(q);
-  const float rstd = 1.0f / sqrt_rn(add_rn(q / (float)C, eps));
+  float mean, rstd;
+  wave_layernorm_stats(v, ok, C, eps, mean, rstd);
   const float mk = mask ? mask[row] : 1.0f;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int c = lane + 64 * j;
     if (c < C) {
-      const float y = add_rn(mul_rn(mul_rn(v[j] - mean, rstd), gamma[c]), beta[c]);
+      const float y = layernorm_value(v[j], mean, rstd, gamma[c], beta[c]);
       const size_t o = (size_t)row * C + c, n = (size_t)M * C;
       if (out) out[o] = y;
       if (out_m) out_m[o] = mul_rn(y, mk);
@@ -1252,13 +1243,18 @@ struct MhaLaunch {  // an attention kernel (each takes an MhaArgs) as run_stack 
 template <int DK>
 MhaLaunch flash_launch(unsigned blocks) { return {mha_flash_kernel<DK>, dim3(blocks), dim3(kFaThreads), (size_t)2 * FaLds<DK>::BUF}; }
 
-void launch_layernorm(const float* in, const float* gamma, const float* beta, const float* mask, float* out, float* out_m, f16* out_p,
-                      f16* outm_p, int M, int C, hipStream_t st) {
+}  // namespace
+
+// (kernels.h: also the trunk norms of the duration discriminators, durdisc.hip)
+void ttsdec::launch_layernorm(const float* in, const float* gamma, const float* beta, const float* mask, float* out, float* out_m, f16* out_p,
+                              f16* outm_p, int M, int C, hipStream_t st) {
   const dim3 grid((M + 3) / 4), block(256);
   if (C <= 128) hipLaunchKernelGGL(layernorm_rows_kernel<2>, grid, block, 0, st, in, gamma, beta, mask, out, out_m, out_p, outm_p, M, C, 1e-5f);
   else if (C <= 256) hipLaunchKernelGGL(layernorm_rows_kernel<4>, grid, block, 0, st, in, gamma, beta, mask, out, out_m, out_p, outm_p, M, C, 1e-5f);
   else hipLaunchKernelGGL(layernorm_rows_kernel<16>, grid, block, 0, st, in, gamma, beta, mask, out, out_m, out_p, outm_p, M, C, 1e-5f);
 }
+
+namespace {
 
 // attentions.Encoder.forward (attentions.py:76-93), eval mode.  Input: sw.x = sw.xm = x * mask.
 // Result: sw.xm (= x * mask of the last layer).

@@ -24,6 +24,11 @@
                                              (``forward(x) -> (scores, fmap)``, ``forward(y, y_hat)`` -> the four lists;
                                              ``ttsvits_disc_*``), with ``feature_loss`` / ``discriminator_loss`` / ``generator_loss``
                                              (losses.py:7-34) as torch ops on the device
+* ``DurationDiscriminatorV1`` / ``DurationDiscriminatorV2`` - the duration discriminators, vits2/models.py:183-329
+                                             (``forward(x, x_mask, dur_r, dur_hat, g=None)`` -> ``[p_r, p_hat]`` / ``[[p_r], [p_hat]]``,
+                                             ``forward_probability``; ``ttsvits_durdisc_*``), and
+                                             ``duration_discriminator_scores(net_g, net_dur_disc, x, ..., y, ...)`` - what train.py:414
+                                             feeds and gets from them
 
 All hold the reference's parameters (so checkpoints load) and run inference through the HIP library
 (``ttsvits_*`` / ``ttsgen_*`` / ``ttsdur_*`` / ``ttspost_*`` in include/ttsdec.h).  The library works on channel-last activations;
@@ -937,17 +942,8 @@ class DurEngine(Handle):
 
 
 
-class _DurationBase(PackedWeightsMixin, nn.Module):
-    def _check(self, x: torch.Tensor) -> None:
-        inference_only(self, "duration predictor", x, fp32=True)
-
-    def _speaker(self, g: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
-        return speaker_rows(g, B, self.gin_channels, "a duration predictor")
-
-    def _engine(self, device) -> DurEngine:
-        eng = self._engines.get(self._cfg, device)
-        eng.ensure_packed(self.weight_tensors())
-        return eng
+class _TokenOperandsMixin:
+    """The reference's [B, C, T] / [B, 1, T] operands as the token-row kernels take them (duration predictors and discriminators)."""
 
     @staticmethod
     def _channel_last(x: torch.Tensor) -> torch.Tensor:
@@ -958,6 +954,19 @@ class _DurationBase(PackedWeightsMixin, nn.Module):
     @staticmethod
     def _lengths(x_mask: torch.Tensor) -> torch.Tensor:
         return x_mask[:, 0, :].sum(dim=1).round().to(torch.int32)  # sequence_mask is a prefix mask
+
+
+class _DurationBase(_TokenOperandsMixin, PackedWeightsMixin, nn.Module):
+    def _check(self, x: torch.Tensor) -> None:
+        inference_only(self, "duration predictor", x, fp32=True)
+
+    def _speaker(self, g: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
+        return speaker_rows(g, B, self.gin_channels, "a duration predictor")
+
+    def _engine(self, device) -> DurEngine:
+        eng = self._engines.get(self._cfg, device)
+        eng.ensure_packed(self.weight_tensors())
+        return eng
 
 
 class StochasticDurationPredictor(_DurationBase):
@@ -1063,6 +1072,158 @@ class DurationPredictor(_DurationBase):
     def forward(self, x, x_mask, g=None):
         self._check(x)
         return self.logw_cl(self._channel_last(x), self._lengths(x_mask), g).unsqueeze(1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Duration discriminators (models.py:183-329) through ttsvits_durdisc_* (include/ttsdec.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+class DurDiscEngine(Handle):
+    """One ttsvits_durdisc handle on one device: DurationDiscriminatorV1 or V2 (dims["version"])."""
+
+    PREFIX = "ttsvits_durdisc"
+
+    def __init__(self, dims: Dict, device: Optional[torch.device]):
+        super().__init__(dims, _lib.DurDiscDims(*[int(dims[n]) for n, _ in _lib.DurDiscDims._fields_]), device)
+
+    def workspace_bytes(self, B: int, T: int, n_dur: int = 2) -> int:
+        return int(self._fn("workspace_bytes")(self._h, B, T, n_dur))
+
+    def _workspace(self, B: int, T: int, n_dur: int, what: str) -> torch.Tensor:
+        nbytes = self.workspace_bytes(B, T, n_dur)
+        if nbytes == 0:
+            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, what, f"B = {B}, T = {T}: the row indices leave 32 bits; split the batch")
+        return self.workspace("call", nbytes)
+
+    def trunk(self, x_cl: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+        """x_cl [B, T, C] contiguous fp32, lengths [B] int32 (device) -> hidden [B, T, F], zero at masked tokens."""
+        B, T, _ = x_cl.shape
+        ws = self._workspace(B, T, 1, "ttsvits_durdisc_trunk")
+        with torch.cuda.device(self.device):
+            out = torch.empty(B, T, self.dims["filter_channels"], device=self.device)
+            rc = self._fn("trunk")(self._h, x_cl.data_ptr(), lengths.data_ptr(), B, T, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
+        self._err(rc, "ttsvits_durdisc_trunk")
+        return out
+
+    def prob(self, hidden_cl: torch.Tensor, lengths: torch.Tensor, dur: torch.Tensor, with_logits: bool = False):
+        """hidden_cl [B, T, F], dur [n_dur, B, T] (n_dur 1 or 2), both contiguous fp32 -> (prob [n_dur, B, T], logits or None)."""
+        n_dur, B, T = dur.shape
+        ws = self._workspace(B, T, n_dur, "ttsvits_durdisc_prob")
+        with torch.cuda.device(self.device):
+            prob = torch.empty(n_dur, B, T, device=self.device)
+            logit = torch.empty_like(prob) if with_logits else None
+            rc = self._fn("prob")(self._h, hidden_cl.data_ptr(), lengths.data_ptr(), dur.data_ptr(), n_dur, B, T, prob.data_ptr(), _ptr(logit),
+                                  ws.data_ptr(), ws.numel(), _stream(self.device))
+        self._err(rc, "ttsvits_durdisc_prob")
+        return prob, logit
+
+
+class _DurationDiscriminatorBase(_TokenOperandsMixin, PackedWeightsMixin, nn.Module):
+    """What DurationDiscriminatorV1 and V2 share: the reference's constructor, parameters and state-dict keys, and the two calls.
+    Inference only, exact fp32, eval mode; ``gin_channels`` and ``g`` are accepted and ignored, as the reference does."""
+
+    VERSION = 0
+
+    def __init__(self, in_channels, filter_channels, kernel_size, p_dropout, gin_channels=0):
+        super().__init__()
+        self._watch_state_dict_loads()
+        self.in_channels, self.filter_channels, self.kernel_size, self.p_dropout, self.gin_channels = (
+            in_channels, filter_channels, kernel_size, p_dropout, gin_channels)
+        pad = kernel_size // 2
+        if self.VERSION == 1:
+            self.drop = nn.Dropout(p_dropout)
+        self.conv_1 = nn.Conv1d(in_channels, filter_channels, kernel_size, padding=pad)
+        if self.VERSION == 2:
+            self.norm_1 = _LayerNorm(filter_channels)
+        self.conv_2 = nn.Conv1d(filter_channels, filter_channels, kernel_size, padding=pad)
+        if self.VERSION == 2:
+            self.norm_2 = _LayerNorm(filter_channels)
+        self.dur_proj = nn.Conv1d(1, filter_channels, 1)
+        self.pre_out_conv_1 = nn.Conv1d(2 * filter_channels, filter_channels, kernel_size, padding=pad)
+        self.pre_out_norm_1 = _LayerNorm(filter_channels)  # (V1 owns both pre_out norms and never uses them: models.py:211-215)
+        self.pre_out_conv_2 = nn.Conv1d(filter_channels, filter_channels, kernel_size, padding=pad)
+        self.pre_out_norm_2 = _LayerNorm(filter_channels)
+        self.output_layer = nn.Sequential(nn.Linear(filter_channels, 1), nn.Sigmoid())
+        self._cfg = dict(version=self.VERSION, in_channels=in_channels, filter_channels=filter_channels, kernel_size=kernel_size)
+        self._engines = EngineCache(DurDiscEngine)
+
+    def weight_tensors(self) -> List[torch.Tensor]:
+        """ttsvits_durdisc_pack_weights' order (include/ttsdec.h): the state dict's, without V1's unused norms."""
+        def norm(name):  # (V2 only: V1 has no trunk norms and does not use its pre_out ones)
+            return [getattr(self, name).gamma, getattr(self, name).beta] if self.VERSION == 2 else []
+
+        out = [self.conv_1.weight, self.conv_1.bias] + norm("norm_1") + [self.conv_2.weight, self.conv_2.bias] + norm("norm_2")
+        out += [self.dur_proj.weight, self.dur_proj.bias, self.pre_out_conv_1.weight, self.pre_out_conv_1.bias] + norm("pre_out_norm_1")
+        out += [self.pre_out_conv_2.weight, self.pre_out_conv_2.bias] + norm("pre_out_norm_2")
+        return out + [self.output_layer[0].weight, self.output_layer[0].bias]
+
+    def _engine(self, device) -> DurDiscEngine:
+        eng = self._engines.get(self._cfg, device)
+        eng.ensure_packed(self.weight_tensors())
+        return eng
+
+    def _operands(self, x, x_mask, channels: int, durs):
+        """The checks both calls share -> (x channel-last, lengths [B] int32, dur [n_dur, B, T] contiguous)."""
+        if x.dim() != 3 or x.shape[1] != channels or x.shape[0] < 1 or x.shape[2] < 1:
+            raise ValueError(f"x must be [B, {channels}, T], got {tuple(x.shape)}")
+        B, _, T = x.shape
+        if x_mask.dim() != 3 or tuple(x_mask.shape) != (B, 1, T):
+            raise ValueError(f"x_mask must be [B, 1, T] = [{B}, 1, {T}], got {tuple(x_mask.shape)}")
+        for d in durs:
+            if d.dim() != 3 or tuple(d.shape) != (B, 1, T):
+                raise ValueError(f"a duration tensor must be [B, 1, T] = [{B}, 1, {T}], got {tuple(d.shape)}")
+        inference_only(self, "duration discriminator", x, fp32=True)
+        # (the kernels read the lengths and the durations through raw device pointers: every operand on x's device, or no launch)
+        if x_mask.device != x.device:
+            raise NotImplementedError(f"the HIP duration discriminator takes x_mask on x's ROCm device ({x.device}), got {x_mask.device}")
+        for d in durs:
+            if d.device != x.device or d.dtype != torch.float32:
+                raise NotImplementedError(f"the HIP duration discriminator takes fp32 durations on x's ROCm device ({x.device}), got "
+                                          f"{d.dtype} on {d.device}")
+        dur = torch.stack([d.detach()[:, 0] for d in durs]).contiguous() if durs else None
+        lengths = self._lengths(x_mask.detach()).to(device=x.device, dtype=torch.int32).contiguous()
+        return self._channel_last(x.detach()), lengths, dur
+
+    def trunk(self, x, x_mask) -> torch.Tensor:
+        """forward up to its loop over the durations: x [B, C, T] -> h * x_mask [B, F, T] (a transposed view of the library's
+        channel-last buffer) - what ``forward_probability`` takes."""
+        x_cl, lengths, _ = self._operands(x, x_mask, self.in_channels, [])
+        return self._engine(x.device).trunk(x_cl, lengths).transpose(1, 2)
+
+    def probabilities(self, x, x_mask, durs, with_logits: bool = False):
+        """forward_probability for one or two duration tensors [B, 1, T] in one call on the trunk's output x [B, F, T] ->
+        (prob [n_dur, B, T], the pre-sigmoid logits or None)."""
+        h_cl, lengths, dur = self._operands(x, x_mask, self.filter_channels, list(durs))
+        return self._engine(x.device).prob(h_cl, lengths, dur, with_logits)
+
+    def forward_probability(self, x, x_mask, dur, g=None):
+        """models.py:222-236 / 298-310: x [B, F, T] (the trunk's output), dur [B, 1, T] -> output_prob [B, T, 1]."""
+        return self.probabilities(x, x_mask, [dur])[0][0].unsqueeze(-1)
+
+    def _pair(self, x, x_mask, dur_r, dur_hat):
+        x_cl, lengths, dur = self._operands(x, x_mask, self.in_channels, [dur_r, dur_hat])
+        eng = self._engine(x.device)
+        prob, _ = eng.prob(eng.trunk(x_cl, lengths), lengths, dur)
+        return prob[0].unsqueeze(-1), prob[1].unsqueeze(-1)
+
+
+class DurationDiscriminatorV1(_DurationDiscriminatorBase):
+    """models.DurationDiscriminatorV1 (models.py:183-257): same constructor, parameters and state-dict keys (the pre_out norms it
+    never uses included); ``forward(x, x_mask, dur_r, dur_hat, g=None) -> [p_r, p_hat]``, each [B, T, 1]."""
+
+    VERSION = 1
+
+    def forward(self, x, x_mask, dur_r, dur_hat, g=None):
+        return list(self._pair(x, x_mask, dur_r, dur_hat))
+
+
+class DurationDiscriminatorV2(_DurationDiscriminatorBase):
+    """models.DurationDiscriminatorV2 (models.py:260-329): same constructor, parameters and state-dict keys;
+    ``forward(x, x_mask, dur_r, dur_hat, g=None) -> [[p_r], [p_hat]]``, each [B, T, 1]."""
+
+    VERSION = 2
+
+    def forward(self, x, x_mask, dur_r, dur_hat, g=None):
+        return [[p] for p in self._pair(x, x_mask, dur_r, dur_hat)]
 
 
 def infer(net_g, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1.0, max_len=None, *, noise=None):
@@ -1280,20 +1441,26 @@ def forced_alignment(net_g, x, x_lengths, y, y_lengths, sid=None, *, mas_noise_s
     [B, 1, T_x], logw_ = log(w + 1e-6) * x_mask [B, 1, T_x], (z, z_p, m_p, logs_p) as the reference's [B, inter, T]).  Channel-last
     from the encoders to the search; the one host read is the search's status word.  ``noise`` (test hook): the posterior's draw
     [B, inter, >= T_y], or a pair (posterior draw, MAS draw [B, T_y, T_x]) with ``mas_noise_scale``."""
-    parts = {"enc_p": TextEncoder, "enc_q": PosteriorEncoder, "flow": ResidualCouplingTransformersBlock}
+    return _forced_alignment(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, noise, {}, "vits2.forced_alignment")[:4]
+
+
+def _forced_alignment(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, noise, more_parts, caller):
+    """forced_alignment's body -> its four results, then what ``duration_discriminator_scores`` goes on with: the text encoder's
+    x channel-last [B, T_x, H], t_x [B] int32, x_mask [B, 1, T_x] and g.  more_parts: further drop-ins of net_g the caller needs."""
+    parts = {"enc_p": TextEncoder, "enc_q": PosteriorEncoder, "flow": ResidualCouplingTransformersBlock, **more_parts}
     for name, cls in parts.items():
         mod = getattr(net_g, name, None)
         if not isinstance(mod, cls):
             raise TypeError(f"net_g.{name} is {type(mod).__name__}, not the HIP drop-in: swap it in (INTEGRATION.md) - there is no fallback")
     if not x.is_cuda or not y.is_cuda:
-        raise NotImplementedError("vits2.forced_alignment runs on a ROCm device only: move the model, the ids and the spectrogram there")
+        raise NotImplementedError(f"{caller} runs on a ROCm device only: move the model, the ids and the spectrogram there")
     enc_p, enc_q, flow = net_g.enc_p, net_g.enc_q, net_g.flow
     e_q, e_mas = noise if isinstance(noise, (tuple, list)) else (noise, None)
     g = None if sid is None else net_g.emb_g(sid).unsqueeze(-1)  # [b, h, 1]
     dev = x.device
     t_x = x_lengths.to(device=dev, dtype=torch.int32).contiguous()
     t_y = y_lengths.to(device=dev, dtype=torch.int32).contiguous()
-    _, m_cl, logs_cl = enc_p.forward_cl(x, t_x, g=g if enc_p.gin_channels else None)
+    xs, m_cl, logs_cl = enc_p.forward_cl(x, t_x, g=g if enc_p.gin_channels else None)
     z_cl, _, _ = enc_q.forward_cl(y, t_y, g=g, noise=e_q)
     zp_cl = flow.forward_cl(z_cl, t_y, g)
     eng = flow._engines.get(flow._dims(), dev)  # (the flow's own handle: the calls are weightless)
@@ -1301,7 +1468,31 @@ def forced_alignment(net_g, x, x_lengths, y, y_lengths, sid=None, *, mas_noise_s
     w = dur.to(torch.float32).unsqueeze(1)
     x_mask = (torch.arange(x.shape[1], device=dev)[None, :] < t_x[:, None]).unsqueeze(1).to(torch.float32)
     logw_ = torch.log(w + 1e-6) * x_mask
-    return path.unsqueeze(1), w, logw_, (z_cl.transpose(1, 2), zp_cl.transpose(1, 2), m_cl.transpose(1, 2), logs_cl.transpose(1, 2))
+    zs = (z_cl.transpose(1, 2), zp_cl.transpose(1, 2), m_cl.transpose(1, 2), logs_cl.transpose(1, 2))
+    return path.unsqueeze(1), w, logw_, zs, xs, t_x, x_mask, g
+
+
+def duration_discriminator_scores(net_g, net_dur_disc, x, x_lengths, y, y_lengths, sid=None, *, noise_scale_w=1.0, mas_noise_scale=None,
+                                  noise=None):
+    """What the reference's trainer feeds and gets from its duration discriminator, ``net_dur_disc(hidden_x, x_mask, logw_, logw)``
+    (train.py:385 / 414), in eval mode: SynthesizerTrn.forward up to ``(x, logw, logw_)`` (models.py:1214-1264) - the text encoder
+    once, ``forced_alignment``'s body for logw_, and the duration predictor for logw: ``dp(x, x_mask, g=g, reverse=True,
+    noise_scale=noise_scale_w)`` for a StochasticDurationPredictor, ``dp(x, x_mask, g=g)`` for a DurationPredictor - then the
+    discriminator.  -> (y_dur_hat_r, y_dur_hat_g, (hidden_x [B, H, T_x], x_mask [B, 1, T_x], logw_, logw [B, 1, T_x])); the two
+    outputs are what ``discriminator_loss`` / ``generator_loss`` take ([p] lists for V2, the tensors wrapped by the caller for
+    V1, as train.py does).  ``noise`` (test hook): the pair (forced_alignment's ``noise``, the SDP's draw [B, 2, T_x] or None)."""
+    if not isinstance(net_dur_disc, _DurationDiscriminatorBase):
+        raise TypeError(f"net_dur_disc is {type(net_dur_disc).__name__}, not the HIP drop-in: swap it in (INTEGRATION.md) - there is no fallback")
+    if noise is not None and not (isinstance(noise, (tuple, list)) and len(noise) == 2):
+        raise ValueError("noise must be a pair: (forced_alignment's noise, the stochastic duration predictor's draw [B, 2, T_x] or None)")
+    e_fa, e_w = noise if noise is not None else (None, None)
+    _, _, logw_, _, xs, t_x, x_mask, g = _forced_alignment(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, e_fa,
+                                                           {"dp": (StochasticDurationPredictor, DurationPredictor)},
+                                                           "vits2.duration_discriminator_scores")
+    logw = net_g.dp.logw_cl(xs, t_x, g, noise_scale_w, e_w).unsqueeze(1)
+    hidden_x = xs.transpose(1, 2)
+    y_dur_hat_r, y_dur_hat_g = net_dur_disc(hidden_x, x_mask, logw_, logw)
+    return y_dur_hat_r, y_dur_hat_g, (hidden_x, x_mask, logw_, logw)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
