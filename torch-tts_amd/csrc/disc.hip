@@ -42,9 +42,7 @@ struct DiscBlob {
   size_t total;
 };
 // the one walk over the blob: offsets in blob order, source indices in the order include/ttsdec.h documents
-struct Walk {
-  Carver cv{nullptr};
-  int src = 0;
+struct Walk : BlobWalk {
   Conv conv(int Ci, int Co, int k, int stride, int groups = 1) {
     Conv c{0, 0, Ci, Co, k, stride, (k - 1) / 2, groups, src};
     c.w = cv.take_off(c.n());

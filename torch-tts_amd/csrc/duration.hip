@@ -12,6 +12,8 @@
 //   lengths_kernel   w = exp(logw) * mask * length_scale, ceil, running sums, y_len, one workgroup
 //   expand_kernel    the frame-rate prior (m_p, logs_p, z_p channel-last; attn) from the running sums, no dense matmul
 // SDP reverse at n_flows = 4: 1 (cond(g)) + 1 (pre) + 3 (DDSConv) + 3 x 3 (ConvFlows) = 14 launches (13 without g).
+// Every weight has one record (KConv: a K-major conv weight with its bias; Vec, layout.h: a tensor copied as given), made by one
+// walk at ttsdur_create; ttsdur_pack_weights and the forward calls read offsets, shapes and source indices from the records.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -31,24 +33,52 @@ constexpr int kBins = 10;      // ConvFlow num_bins
 constexpr int kProj = 3 * kBins - 1;
 constexpr float kTail = 5.f;   // ConvFlow tail_bound
 
-struct DdsW {  // one DDSConv (3 layers), offsets in floats
-  size_t dw_w[3], dw_b[3];     // [3][C] tap-major, [C]
-  size_t pw_w[3], pw_b[3];     // [C][C] K-major, [C]
-  size_t n1g[3], n1b[3], n2g[3], n2b[3];
+struct KConv {  // a Conv1d weight [N, Cin, taps] packed K-major [taps * Cin][N] (pack_kmajor_kernel) and its bias [N]; float offsets
+  size_t w, b;
+  int N, Cin, taps;
+  int src;  // its first source tensor: the weight, then the bias
+  size_t n() const { return (size_t)N * Cin * taps; }
 };
+struct Pair { Vec w, b; };  // a weight and its bias, or a LayerNorm's gamma and beta, both copied as given
+struct DdsLayer {           // one DDSConv layer: convs_sep [C, 1, 3] -> [3][C] tap-major, convs_1x1 [C][C], norms_1, norms_2
+  KConv dw, pw;
+  Pair n1, n2;
+};
+typedef DdsLayer DdsW[3];   // one DDSConv
 struct DurBlob {
   // kind 0
-  size_t pre_w, pre_b;               // [C][C] K-major, [C]
+  KConv pre;                 // [C][C]
   DdsW convs;
-  size_t proj_w, proj_b;             // [C][C] K-major, [C]
-  size_t ea_m, ea_logs;              // [2], [2]
-  size_t f_pre_w[8], f_pre_b[8];     // [C], [C] (flows.{2k+1}, k = 1 .. n_flows-1)
+  KConv proj;                // [C][C]
+  Vec ea_m, ea_logs;         // [2], [2]
+  Pair f_pre[8];             // [C], [C] (flows.{2k+1}, k = 1 .. n_flows-1)
   DdsW f_convs[8];
-  size_t f_proj_w[8], f_proj_b[8];   // [C][29] K-major, [29]
+  KConv f_proj[8];           // [C][29]
   // kind 1
-  size_t c1_w, c1_b, n1g, n1b, c2_w, c2_b, n2g, n2b, p_w, p_b;  // [3C][F], [F], ..., [3F][F], ..., [F], [1]
-  size_t cond_w, cond_b;             // [C, gin] (as given), [C]
+  KConv c1, c2;              // [3C][F], [3F][F]
+  Pair n1, n2, p;            // [F], [F]; proj: [F], [1]
+  Pair cond;                 // [C, gin], [C]
   size_t total;
+  int n_src;                 // source tensors of ttsdur_pack_weights
+};
+// the one walk over the blob: offsets in blob order, source indices in the order include/ttsdec.h documents (src ends as their count)
+struct Walk : BlobWalk {
+  Pair pair(size_t nw, size_t nb) { return {vec(nw), vec(nb)}; }
+  KConv conv(int N, int Cin, int taps) {
+    KConv c{0, 0, N, Cin, taps, src};
+    c.w = cv.take_off(c.n());
+    c.b = cv.take_off(N);
+    src += 2;
+    return c;
+  }
+  void dds(DdsW& w, int C) {
+    for (DdsLayer& l : w) {
+      l.dw = conv(C, 1, 3);
+      l.pw = conv(C, C, 1);
+      l.n1 = pair(C, C);
+      l.n2 = pair(C, C);
+    }
+  }
 };
 }  // namespace
 
@@ -72,59 +102,31 @@ bool dims_ok(const ttsdur_dims& d) {
 DurBlob make_layout(const ttsdur_dims& d) {
   DurBlob L;
   memset(&L, 0, sizeof(L));
-  Carver cv{nullptr};
-  const size_t C = d.in_channels;
-  auto dds = [&](DdsW& w) {
-    for (int i = 0; i < 3; ++i) {
-      w.dw_w[i] = cv.take_off(3 * C);
-      w.dw_b[i] = cv.take_off(C);
-      w.pw_w[i] = cv.take_off(C * C);
-      w.pw_b[i] = cv.take_off(C);
-      w.n1g[i] = cv.take_off(C);
-      w.n1b[i] = cv.take_off(C);
-      w.n2g[i] = cv.take_off(C);
-      w.n2b[i] = cv.take_off(C);
-    }
-  };
+  Walk w;
+  const int C = d.in_channels;
   if (d.kind == 0) {
-    L.pre_w = cv.take_off(C * C);
-    L.pre_b = cv.take_off(C);
-    dds(L.convs);
-    L.proj_w = cv.take_off(C * C);
-    L.proj_b = cv.take_off(C);
-    L.ea_m = cv.take_off(2);
-    L.ea_logs = cv.take_off(2);
+    L.pre = w.conv(C, C, 1);
+    w.dds(L.convs, C);
+    L.proj = w.conv(C, C, 1);
+    L.ea_m = w.vec(2);
+    L.ea_logs = w.vec(2);
     for (int k = 0; k < d.n_flows - 1; ++k) {
-      L.f_pre_w[k] = cv.take_off(C);
-      L.f_pre_b[k] = cv.take_off(C);
-      dds(L.f_convs[k]);
-      L.f_proj_w[k] = cv.take_off(C * kProj);
-      L.f_proj_b[k] = cv.take_off(kProj);
+      L.f_pre[k] = w.pair(C, C);  // [C, 1, 1], [C]
+      w.dds(L.f_convs[k], C);
+      L.f_proj[k] = w.conv(kProj, C, 1);
     }
   } else {
-    const size_t F = d.filter_channels;
-    L.c1_w = cv.take_off(3 * C * F);
-    L.c1_b = cv.take_off(F);
-    L.n1g = cv.take_off(F);
-    L.n1b = cv.take_off(F);
-    L.c2_w = cv.take_off(3 * F * F);
-    L.c2_b = cv.take_off(F);
-    L.n2g = cv.take_off(F);
-    L.n2b = cv.take_off(F);
-    L.p_w = cv.take_off(F);
-    L.p_b = cv.take_off(1);
+    const int F = d.filter_channels;
+    L.c1 = w.conv(F, C, 3);
+    L.n1 = w.pair(F, F);
+    L.c2 = w.conv(F, F, 3);
+    L.n2 = w.pair(F, F);
+    L.p = w.pair(F, 1);
   }
-  if (d.gin_channels > 0) {
-    L.cond_w = cv.take_off(C * d.gin_channels);
-    L.cond_b = cv.take_off(C);
-  }
-  L.total = cv.off;
+  if (d.gin_channels > 0) L.cond = w.pair((size_t)C * d.gin_channels, C);
+  L.total = w.cv.off;
+  L.n_src = w.src;
   return L;
-}
-
-int n_tensors(const ttsdur_dims& d) {
-  const int g = d.gin_channels > 0 ? 2 : 0;
-  return d.kind == 0 ? 2 + 24 + 2 + 2 + (d.n_flows - 1) * 28 + g : 10 + g;
 }
 
 // The workspaces of the two predictors (carved as layout.h's Carver comment says)
@@ -548,6 +550,25 @@ __global__ __launch_bounds__(256) void expand_kernel(const int* cum, const float
 size_t dds_lds(int C) { return (size_t)3 * kRows * C * sizeof(float); }
 size_t pw_lds(int Cin, int taps, int N) { return (size_t)kRows * (taps * Cin + N) * sizeof(float); }
 
+// ttsdur_pack_weights' steps, one per record: from src into the blob b
+void pack_conv(const float* const* src, float* b, const KConv& c, hipStream_t st) {
+  hipLaunchKernelGGL(pack_kmajor_kernel, grid1(c.n()), dim3(256), 0, st, src[c.src], b + c.w, c.N, c.Cin, c.taps);
+  launch_copy(src[c.src + 1], b + c.b, c.N, st);
+}
+void pack_vec(const float* const* src, float* b, const Vec& v, hipStream_t st) { launch_copy(src[v.src], b + v.off, v.n, st); }
+void pack_pair(const float* const* src, float* b, const Pair& p, hipStream_t st) {
+  pack_vec(src, b, p.w, st);
+  pack_vec(src, b, p.b, st);
+}
+void pack_dds(const float* const* src, float* b, const DdsW& w, hipStream_t st) {
+  for (const DdsLayer& l : w) {
+    pack_conv(src, b, l.dw, st);
+    pack_conv(src, b, l.pw, st);
+    pack_pair(src, b, l.n1, st);
+    pack_pair(src, b, l.n2, st);
+  }
+}
+
 void run_dds(const ttsdur_handle* h, const DdsW& w, DdsArgs a, const float* x_first, float* bufA, float* bufB, int tail, hipStream_t st) {
   const float* b = h->blob;
   const unsigned nblk = (unsigned)((a.M + kRows - 1) / kRows);
@@ -555,8 +576,8 @@ void run_dds(const ttsdur_handle* h, const DdsW& w, DdsArgs a, const float* x_fi
   for (int i = 0; i < 3; ++i) {
     DdsArgs l = a;
     l.xin = i > 0 ? in : x_first;  // (zin stays: the head reads it in layer 0, the spline epilogue in layer 2)
-    l.dw_w = b + w.dw_w[i]; l.dw_b = b + w.dw_b[i]; l.pw_w = b + w.pw_w[i]; l.pw_b = b + w.pw_b[i];
-    l.n1g = b + w.n1g[i]; l.n1b = b + w.n1b[i]; l.n2g = b + w.n2g[i]; l.n2b = b + w.n2b[i];
+    l.dw_w = b + w[i].dw.w; l.dw_b = b + w[i].dw.b; l.pw_w = b + w[i].pw.w; l.pw_b = b + w[i].pw.b;
+    l.n1g = b + w[i].n1.w.off; l.n1b = b + w[i].n1.b.off; l.n2g = b + w[i].n2.w.off; l.n2b = b + w[i].n2.b.off;
     l.dil = i == 0 ? 1 : (i == 1 ? 3 : 9);  // kernel_size ** i
     l.last = i == 2;
     l.tail = i == 2 ? tail : TAIL_NONE;
@@ -600,7 +621,7 @@ int ttsdur_destroy(ttsdur_handle* h) {
   return TTSDEC_OK;
 }
 const char* ttsdur_last_hip_error(const ttsdur_handle* h) { return last_hip_error(h); }
-int ttsdur_num_weight_tensors(const ttsdur_handle* h) { return h ? n_tensors(h->d) : TTSDEC_ERR_INVALID_ARG; }
+int ttsdur_num_weight_tensors(const ttsdur_handle* h) { return h ? h->bl.n_src : TTSDEC_ERR_INVALID_ARG; }
 size_t ttsdur_packed_bytes(const ttsdur_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
 
 int ttsdur_pack_weights(ttsdur_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
@@ -610,56 +631,25 @@ int ttsdur_pack_weights(ttsdur_handle* h, const float* const* src, int n_src, vo
   const ttsdur_dims& d = h->d;
   const DurBlob& L = h->bl;
   float* b = static_cast<float*>(blob);
-  const int C = d.in_channels;
-  int k = 0;
-  auto kmajor = [&](size_t off, int N, int Cin, int taps) {
-    hipLaunchKernelGGL(pack_kmajor_kernel, grid1((size_t)N * Cin * taps), dim3(256), 0, st, src[k++], b + off, N, Cin, taps);
-  };
-  auto copy = [&](size_t off, size_t n) { launch_copy(src[k++], b + off, n, st); };
-  auto dds = [&](const DdsW& w) {
-    for (int i = 0; i < 3; ++i) {
-      kmajor(w.dw_w[i], C, 1, 3);  // [C, 1, 3] -> [3][C]
-      copy(w.dw_b[i], C);
-      kmajor(w.pw_w[i], C, C, 1);
-      copy(w.pw_b[i], C);
-      copy(w.n1g[i], C);
-      copy(w.n1b[i], C);
-      copy(w.n2g[i], C);
-      copy(w.n2b[i], C);
-    }
-  };
   if (d.kind == 0) {
-    kmajor(L.pre_w, C, C, 1);
-    copy(L.pre_b, C);
-    dds(L.convs);
-    kmajor(L.proj_w, C, C, 1);
-    copy(L.proj_b, C);
-    copy(L.ea_m, 2);
-    copy(L.ea_logs, 2);
+    pack_conv(src, b, L.pre, st);
+    pack_dds(src, b, L.convs, st);
+    pack_conv(src, b, L.proj, st);
+    pack_vec(src, b, L.ea_m, st);
+    pack_vec(src, b, L.ea_logs, st);
     for (int f = 0; f < d.n_flows - 1; ++f) {
-      copy(L.f_pre_w[f], C);  // [C, 1, 1]
-      copy(L.f_pre_b[f], C);
-      dds(L.f_convs[f]);
-      kmajor(L.f_proj_w[f], kProj, C, 1);
-      copy(L.f_proj_b[f], kProj);
+      pack_pair(src, b, L.f_pre[f], st);
+      pack_dds(src, b, L.f_convs[f], st);
+      pack_conv(src, b, L.f_proj[f], st);
     }
   } else {
-    const int F = d.filter_channels;
-    kmajor(L.c1_w, F, C, 3);
-    copy(L.c1_b, F);
-    copy(L.n1g, F);
-    copy(L.n1b, F);
-    kmajor(L.c2_w, F, F, 3);
-    copy(L.c2_b, F);
-    copy(L.n2g, F);
-    copy(L.n2b, F);
-    copy(L.p_w, F);
-    copy(L.p_b, 1);
+    pack_conv(src, b, L.c1, st);
+    pack_pair(src, b, L.n1, st);
+    pack_conv(src, b, L.c2, st);
+    pack_pair(src, b, L.n2, st);
+    pack_pair(src, b, L.p, st);
   }
-  if (d.gin_channels > 0) {
-    copy(L.cond_w, (size_t)C * d.gin_channels);
-    copy(L.cond_b, C);
-  }
+  if (d.gin_channels > 0) pack_pair(src, b, L.cond, st);
   return pack_end(h, b);
 }
 
@@ -684,11 +674,11 @@ int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths,
   const SdpWs w = carve_sdp(cv, d, B, T);
   float *XP = w.XP, *XA = w.XA, *XB = w.XB, *XC = w.XC, *Z = w.Z, *condv = w.condv;
   const unsigned nblk = (unsigned)((M + kRows - 1) / kRows);
-  if (g) launch_cond(g, b + L.cond_w, b + L.cond_b, condv, B, C, d.gin_channels, st);
+  if (g) launch_cond(g, b + L.cond.w.off, b + L.cond.b.off, condv, B, C, d.gin_channels, st);
   {  // models.py:80-84: x = pre(x) (+ cond(g))
     PwArgs p;
     memset(&p, 0, sizeof(p));
-    p.x = x; p.Cin = C; p.taps = 1; p.W = b + L.pre_w; p.bias = b + L.pre_b; p.N = C; p.out_rowvec = g ? condv : nullptr;
+    p.x = x; p.Cin = C; p.taps = 1; p.W = b + L.pre.w; p.bias = b + L.pre.b; p.N = C; p.out_rowvec = g ? condv : nullptr;
     p.out = XP; p.lengths = lengths; p.T = T; p.M = M;
     hipLaunchKernelGGL(pw_conv_kernel, dim3(nblk), dim3(kThreads), pw_lds(C, 1, C), st, p);
   }
@@ -697,7 +687,7 @@ int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths,
   a.lengths = lengths; a.C = C; a.T = T; a.M = M; a.zscale = 1.f; a.sqrt_c = sqrtf((float)C);
   {  // :85-86: x = proj(convs(x, x_mask)) * x_mask -> XC
     DdsArgs c = a;
-    c.tw = b + L.proj_w; c.tb = b + L.proj_b; c.xout = XC;
+    c.tw = b + L.proj.w; c.tb = b + L.proj.b; c.xout = XC;
     run_dds(h, L.convs, c, XP, XA, XB, TAIL_PROJ, st);
     // (run_dds hands layer 2 xout = XC through c.xout: the tail writes it)
   }
@@ -708,13 +698,13 @@ int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths,
     c.zin = f == d.n_flows - 2 ? noise : Z;
     c.zscale = f == d.n_flows - 2 ? noise_scale : 1.f;
     c.c0 = c0;
-    c.pre_w = b + L.f_pre_w[f]; c.pre_b = b + L.f_pre_b[f]; c.gadd = XC;
-    c.tw = b + L.f_proj_w[f]; c.tb = b + L.f_proj_b[f];
+    c.pre_w = b + L.f_pre[f].w.off; c.pre_b = b + L.f_pre[f].b.off; c.gadd = XC;
+    c.tw = b + L.f_proj[f].w; c.tb = b + L.f_proj[f].b;
     c.zout = Z;
     if (f == 0) {
       c.logw = logw;
-      c.ea_m = b + L.ea_m;
-      c.ea_logs = b + L.ea_logs;
+      c.ea_m = b + L.ea_m.off;
+      c.ea_logs = b + L.ea_logs.off;
     }
     run_dds(h, L.f_convs[f], c, nullptr, XA, XB, TAIL_FLOW, st);
     c0 ^= 1;  // the Flip after it
@@ -735,18 +725,18 @@ int ttsdur_dp_forward(ttsdur_handle* h, const float* x, const int32_t* lengths, 
   const DpWs w = carve_dp(cv, d, B, T);
   float *H1 = w.H1, *condv = w.condv;
   const unsigned nblk = (unsigned)((M + kRows - 1) / kRows);
-  if (g) launch_cond(g, b + L.cond_w, b + L.cond_b, condv, B, C, d.gin_channels, st);
+  if (g) launch_cond(g, b + L.cond.w.off, b + L.cond.b.off, condv, B, C, d.gin_channels, st);
   PwArgs p;
   memset(&p, 0, sizeof(p));
   p.lengths = lengths; p.T = T; p.M = M; p.taps = 3; p.in_mask = 1; p.relu_ln = 1;
   // models.py:171-174: x = norm_1(relu(conv_1((x + cond(g)) * x_mask)))
-  p.x = x; p.Cin = C; p.in_rowvec = g ? condv : nullptr; p.W = b + L.c1_w; p.bias = b + L.c1_b; p.N = Fc;
-  p.gamma = b + L.n1g; p.beta = b + L.n1b; p.out = H1;
+  p.x = x; p.Cin = C; p.in_rowvec = g ? condv : nullptr; p.W = b + L.c1.w; p.bias = b + L.c1.b; p.N = Fc;
+  p.gamma = b + L.n1.w.off; p.beta = b + L.n1.b.off; p.out = H1;
   hipLaunchKernelGGL(pw_conv_kernel, dim3(nblk), dim3(kThreads), pw_lds(C, 3, Fc), st, p);
   // :175-180: x = norm_2(relu(conv_2(x * x_mask))); proj(x * x_mask) * x_mask
-  p.x = H1; p.Cin = Fc; p.in_rowvec = nullptr; p.W = b + L.c2_w; p.bias = b + L.c2_b;
-  p.gamma = b + L.n2g; p.beta = b + L.n2b; p.out = nullptr;
-  p.proj_w = b + L.p_w; p.proj_b = b + L.p_b; p.proj_out = logw;
+  p.x = H1; p.Cin = Fc; p.in_rowvec = nullptr; p.W = b + L.c2.w; p.bias = b + L.c2.b;
+  p.gamma = b + L.n2.w.off; p.beta = b + L.n2.b.off; p.out = nullptr;
+  p.proj_w = b + L.p.w.off; p.proj_b = b + L.p.b.off; p.proj_out = logw;
   hipLaunchKernelGGL(pw_conv_kernel, dim3(nblk), dim3(kThreads), pw_lds(Fc, 3, Fc), st, p);
   return record_hip_error(h, "dp_forward");
 }

@@ -48,9 +48,7 @@ struct DurDiscBlob {
   size_t total;
 };
 // the one walk over the blob: offsets in blob order, source indices in the order include/ttsdec.h documents
-struct Walk {
-  Carver cv{nullptr};
-  int src = 0;
+struct Walk : BlobWalk {
   Conv conv(int N, int K, int n_src = 2) {
     Conv c{0, 0, N, K, src};
     c.w = cv.take_off((size_t)N * kTaps * K);

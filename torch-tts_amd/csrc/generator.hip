@@ -20,6 +20,8 @@
 // activated buffers Y / LX / H / LR then hold hi / lo fp16 planes instead of fp32; z by launch_split).  x, the branch's x', the
 // branch sum and the bias / cond / residual / sum / division chain stay fp32, in the exact path's order.  A layer the split tiles
 // do not cover (split_ok) keeps the exact tiles inside such a call and reads its input as fp32.
+// Every conv has one record (GConv: blob and planes offsets, whether it splits, N / Cin / taps, its source tensors, how it is
+// packed), made by one walk at ttsgen_create; the two pack steps and the forward loop over the records and state no shape.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -35,29 +37,34 @@ namespace {
 constexpr float kLrelu = 0.1f;       // modules.LRELU_SLOPE
 constexpr float kLreluLast = 0.01f;  // F.leaky_relu's default, models.py:963
 
-struct GenBlob {  // offsets in floats
-  size_t pre_w, pre_b;                      // [C0, 7 * Cin] tap-major, [C0]
-  size_t up_w[TTSGEN_MAX_UP], up_b[TTSGEN_MAX_UP];  // [u * Cout, 3 * Cin] polyphase, [u * Cout] (bias per phase)
-  size_t rw[TTSGEN_MAX_UP][TTSGEN_MAX_RES][6], rb[TTSGEN_MAX_UP][TTSGEN_MAX_RES][6];  // convs1.0-2, convs2.0-2: [C, k * C], [C]
-  size_t post_w;                            // [7, C_last]
-  size_t cond_w, cond_b;                    // [C0, gin], [C0]
-  size_t total;
+// One conv of the generator as the GEMM core reads it: packed weight [N, taps * Cin] and bias [N].  Made once by the walk at
+// ttsgen_create; layout, pack, the planes, the tensor count and the forward's GEMM calls all read it.  Offsets in floats.
+struct GConv {
+  size_t w, b;  // in the blob (conv_post has no bias)
+  size_t p;     // in the planes buffer (split): hi plane, then lo plane, n() floats in all, in the packed layout
+  bool split;   // runs in split-fp16 in a ttsvits_generator_forward call that asks for it
+  int N, Cin, taps;
+  int src;      // its first source tensor: the weight, then the bias
+  int u;        // ttsgen_pack_weights: 0, a Conv1d [N, Cin, taps] -> [N, taps, Cin]; else a ConvTranspose1d [Cin, N / u, 2u] packed
+  bool bias;    // as the polyphase 3-tap conv, its bias once per phase.  bias: false for conv_post
+  int K() const { return taps * Cin; }
+  size_t n() const { return (size_t)N * K(); }
 };
-
-// the second blob (ttsvits_generator_pack_planes): the fp16 planes of the conv weights that run in split-fp16.  Offsets in floats;
-// a weight of n elements takes n floats - its hi plane, then its lo plane - in the packed (tap-major / polyphase) layout
-struct GenPlanes {
-  bool pre, up[TTSGEN_MAX_UP], res[TTSGEN_MAX_UP];  // conv_pre / ups[i] / the resblocks of stage i run in split-fp16
-  bool all;  // (never none: ups[0] reads upsample_initial_channel = 2 C_0 channels, a multiple of 8 whenever the dims are built)
-  size_t pre_w, up_w[TTSGEN_MAX_UP], rw[TTSGEN_MAX_UP][TTSGEN_MAX_RES][6];
-  size_t total;
+struct GenBlob {
+  GConv pre;                                         // [C0, 7 * Cin] tap-major
+  GConv up[TTSGEN_MAX_UP];                           // [u * Cout, 3 * Cin] polyphase, bias [u * Cout]
+  GConv res[TTSGEN_MAX_UP][TTSGEN_MAX_RES][6];       // convs1.0-2, convs2.0-2: [C, k * C]
+  GConv post;                                        // [1, 7 * C_last]
+  Vec cond_w, cond_b;                                // [C0, gin], [C0], copied as given (no GEMM tile reads them)
+  bool all;  // every conv does (never none: ups[0] reads upsample_initial_channel = 2 C_0 channels, a multiple of 8)
+  size_t total, planes_total;  // floats: the blob; the second blob (ttsvits_generator_pack_planes)
+  int n_src;                   // source tensors of ttsgen_pack_weights
 };
 }  // namespace
 
 struct ttsgen_handle : HandleBase {
   ttsgen_dims d;
   GenBlob bl;
-  GenPlanes pl;
 };
 
 namespace {
@@ -90,66 +97,56 @@ bool dims_ok(const ttsgen_dims& d) {
   return true;
 }
 
-GenBlob make_layout(const ttsgen_dims& d) {
-  GenBlob L;
-  memset(&L, 0, sizeof(L));
-  Carver cv{nullptr};
-  const size_t C0 = d.upsample_initial_channel;
-  L.pre_w = cv.take_off(C0 * 7 * d.initial_channel);
-  L.pre_b = cv.take_off(C0);
-  for (int i = 0; i < d.n_up; ++i) {
-    const size_t Ci = i == 0 ? C0 : chan(d, i - 1), Co = chan(d, i), u = d.up_rates[i];
-    L.up_w[i] = cv.take_off(u * Co * 3 * Ci);
-    L.up_b[i] = cv.take_off(u * Co);
-  }
-  for (int i = 0; i < d.n_up; ++i) {
-    const size_t C = chan(d, i);
-    for (int j = 0; j < d.n_res; ++j)
-      for (int c = 0; c < 6; ++c) {
-        L.rw[i][j][c] = cv.take_off(C * d.res_kernels[j] * C);
-        L.rb[i][j][c] = cv.take_off(C);
-      }
-  }
-  L.post_w = cv.take_off(7 * (size_t)chan(d, d.n_up - 1));
-  if (d.gin_channels > 0) {
-    L.cond_w = cv.take_off(C0 * d.gin_channels);
-    L.cond_b = cv.take_off(C0);
-  }
-  L.total = cv.off;
-  return L;
-}
-
 // A conv runs in split-fp16 when its rows are whole 16-byte columns of fp16 (Cin % 8) and, dilated, when its taps line up with the
 // 64-k tiles of launch_gemm_dil_f16s (Cin | 64 or 64 | Cin; its 32-k tiles then line up too).  The resblocks of a stage
 // share their buffers, so they switch together: one dilation that fails keeps the whole stage exact.
 bool split_ok(int Cin, int dil) { return Cin % 8 == 0 && (dil == 1 || Cin % 64 == 0 || 64 % Cin == 0); }
 
-GenPlanes make_planes(const ttsgen_dims& d) {
-  GenPlanes P;
-  memset(&P, 0, sizeof(P));
-  Carver cv{nullptr};
-  const size_t C0 = d.upsample_initial_channel;
-  P.all = true;
-  auto note = [&](bool ok) { P.all = P.all && ok; return ok; };
-  if ((P.pre = note(split_ok(d.initial_channel, 1)))) P.pre_w = cv.take_off(C0 * 7 * d.initial_channel);
+// The one walk (at ttsgen_create): blob offsets in blob order, source indices in the order include/ttsdec.h documents (src ends as
+// their count) and, for the convs that run in split-fp16, planes offsets in that order too: pre, the ups, the resblocks of split stages
+struct Walk : BlobWalk {
+  Carver pv{nullptr};  // the planes buffer
+  GConv conv(int N, int Cin, int taps, bool split, int u = 0, bool bias = true) {
+    GConv c{0, 0, 0, split, N, Cin, taps, src, u, bias};
+    c.w = cv.take_off(c.n());
+    if (bias) c.b = cv.take_off(N);
+    if (split) c.p = pv.take_off(c.n());
+    src += bias ? 2 : 1;
+    return c;
+  }
+};
+
+GenBlob make_layout(const ttsgen_dims& d) {
+  GenBlob L;
+  memset(&L, 0, sizeof(L));
+  Walk w;
+  const int C0 = d.upsample_initial_channel;
+  L.pre = w.conv(C0, d.initial_channel, 7, split_ok(d.initial_channel, 1));
+  L.all = L.pre.split;
   for (int i = 0; i < d.n_up; ++i) {
-    const size_t Ci = i == 0 ? C0 : chan(d, i - 1), Co = chan(d, i), u = d.up_rates[i];
-    if ((P.up[i] = note(split_ok((int)Ci, 1)))) P.up_w[i] = cv.take_off(u * Co * 3 * Ci);
+    const int Ci = i == 0 ? C0 : chan(d, i - 1), u = d.up_rates[i];
+    L.up[i] = w.conv(u * chan(d, i), Ci, 3, split_ok(Ci, 1), u);
+    L.all = L.all && L.up[i].split;
   }
   for (int i = 0; i < d.n_up; ++i) {
-    const size_t C = chan(d, i);
+    const int C = chan(d, i);
     bool ok = true;
     for (int j = 0; j < d.n_res; ++j)
-      for (int l = 0; l < 3; ++l) ok = ok && split_ok((int)C, d.res_dilations[j][l]);
-    if (!(P.res[i] = note(ok))) continue;
+      for (int l = 0; l < 3; ++l) ok = ok && split_ok(C, d.res_dilations[j][l]);
+    L.all = L.all && ok;
     for (int j = 0; j < d.n_res; ++j)
-      for (int c = 0; c < 6; ++c) P.rw[i][j][c] = cv.take_off(C * d.res_kernels[j] * C);
+      for (int c = 0; c < 6; ++c) L.res[i][j][c] = w.conv(C, C, d.res_kernels[j], ok);
   }
-  P.total = cv.off;
-  return P;
+  L.post = w.conv(1, chan(d, d.n_up - 1), 7, false, 0, false);
+  if (d.gin_channels > 0) {
+    L.cond_w = w.vec((size_t)C0 * d.gin_channels);
+    L.cond_b = w.vec(C0);
+  }
+  L.total = w.cv.off;
+  L.planes_total = w.pv.off;
+  L.n_src = w.src;
+  return L;
 }
-
-int n_tensors(const ttsgen_dims& d) { return 2 + 2 * d.n_up + 12 * d.n_up * d.n_res + 1 + (d.gin_channels > 0 ? 2 : 0); }
 
 // largest activation of one utterance, in floats (include/ttsdec.h)
 size_t utt_floats(const ttsgen_dims& d, int T) {
@@ -183,7 +180,7 @@ int group_size(const ttsgen_dims& d, int B, int T) {
 // output, then each stage's result; kept first: ttsgen_forward_stages reads it); X / LX: the upsampled x and lrelu(x); H: c1's
 // output; R / LR: the branch's running x' and lrelu(x'); condv: [G, C0] cond(g)
 //
-// Split-fp16 (pl != nullptr: the handle's GenPlanes): the same six buffers - the two fp16 planes of an
+// Split-fp16 (pl != nullptr: the handle's records): the same six buffers - the two fp16 planes of an
 // [M, N] activation take the bytes of its fp32 form, hi plane first - plus zp, the planes of z, and, when some layer stays exact,
 // tmp: an exact layer cannot write planes, so where a split layer reads its result the fp32 form goes to tmp and launch_split
 // makes the planes.  Planes do not sit at their fp32 element's bytes, so the last conv of a stage cannot turn the branch sum into
@@ -192,12 +189,12 @@ int group_size(const ttsgen_dims& d, int B, int T) {
 // that is wanted as fp32 (the last stage, for conv_post; a ttsgen_forward_stages read-back; an exact next layer) is written in
 // place when Y is the first buffer and into LX, then the first buffer, otherwise: it always ends up at the start of the workspace.
 struct GenWs { float *Y, *X, *LX, *H, *R, *LR, *condv, *zp, *tmp; };
-GenWs carve_gen(Carver& cv, const ttsgen_dims& d, size_t G, int T, const GenPlanes* pl = nullptr) {
+GenWs carve_gen(Carver& cv, const ttsgen_dims& d, size_t G, int T, const GenBlob* pl = nullptr) {
   const size_t F = G * utt_floats(d, T);
   GenWs w;
   w.Y = cv.take(F); w.X = cv.take(F); w.LX = cv.take(F); w.H = cv.take(F); w.R = cv.take(F); w.LR = cv.take(F);
   w.condv = cv.take(G * d.upsample_initial_channel);
-  w.zp = pl != nullptr && pl->pre ? cv.take(G * T * d.initial_channel) : nullptr;
+  w.zp = pl != nullptr && pl->pre.split ? cv.take(G * T * d.initial_channel) : nullptr;
   w.tmp = pl != nullptr && !pl->all ? cv.take(F) : nullptr;
   return w;
 }
@@ -246,17 +243,17 @@ __global__ __launch_bounds__(256) void conv_post_tanh_kernel(const float* __rest
   out[m] = tanhf(acc);
 }
 
-// one conv of the generator: x [M, Cin] channel-last in utterances of T frames, W [N, taps * Cin]
-GemmArgs conv_args(const float* x, int M, int T, int Cin, int taps, int dil, const float* W, const float* bias, int N) {
+// one conv of the generator (its record c, weights in blob): x [M, Cin] channel-last in utterances of T frames, W [N, taps * Cin]
+GemmArgs conv_args(const GConv& c, const float* blob, const float* x, int M, int T, int dil) {
   GemmArgs g;
   memset(&g, 0, sizeof(g));
-  g.a = make_seg1(x, Cin, taps * Cin);
+  g.a = make_seg1(x, c.Cin, c.K());
   g.a_lo = g.a;
-  g.T = T; g.Cin = Cin; g.taps = taps; g.dil = dil;
-  g.W = W; g.W_lo = W; g.ldw = taps * Cin; g.prec = PREC_F32;
-  g.M = M; g.N = N; g.K = taps * Cin;
-  g.bias = bias;
-  g.ldo = N;
+  g.T = T; g.Cin = c.Cin; g.taps = c.taps; g.dil = dil;
+  g.W = blob + c.w; g.W_lo = g.W; g.ldw = c.K(); g.prec = PREC_F32;
+  g.M = M; g.N = c.N; g.K = c.K();
+  g.bias = blob + c.b;
+  g.ldo = c.N;
   g.slope2 = kLrelu;
   return g;
 }
@@ -265,27 +262,42 @@ GemmArgs conv_args(const float* x, int M, int T, int Cin, int taps, int dil, con
 f16* plane_hi(const float* p) { return reinterpret_cast<f16*>(const_cast<float*>(p)); }
 f16* plane_lo(const float* p, size_t n) { return plane_hi(p) + n; }
 
+// ttsgen_pack_weights' step for one conv: its weight and bias from src into the blob b
+void pack_conv(const float* const* src, float* b, const GConv& c, hipStream_t st) {
+  if (c.u > 0) {
+    const int Cout = c.N / c.u;
+    hipLaunchKernelGGL(pack_up_kernel, grid1(c.n()), dim3(256), 0, st, src[c.src], b + c.w, c.Cin, Cout, c.u);
+    hipLaunchKernelGGL(rep_bias_kernel, grid1((size_t)c.N), dim3(256), 0, st, src[c.src + 1], b + c.b, Cout, c.u);
+    return;
+  }
+  launch_conv_transpose(src[c.src], b + c.w, c.N, c.Cin, c.taps, st);  // [Co, Ci, k] -> [Co, k, Ci]
+  if (c.bias) launch_copy(src[c.src + 1], b + c.b, c.N, st);
+}
+// ttsvits_generator_pack_planes' step: the planes of a split conv's packed weight, from the blob b into the planes buffer p
+void split_conv(const float* b, float* p, const GConv& c, hipStream_t st) {
+  if (c.split) launch_split(b + c.w, plane_hi(p + c.p), plane_lo(p + c.p, c.n()), c.n(), st);
+}
+
 // the forward pass over one group of G utterances; n_stages < n_up stops early (ttsgen_forward_stages).  planes == nullptr: exact
-// fp32; else the handle's split layers (GenPlanes) take their weights from it and their inputs as planes
+// fp32; else the handle's split layers (GConv::split) take their weights from it and their inputs as planes
 void run_group(const ttsgen_handle* h, const float* planes, const float* z, const float* g, int G, int T, int n_stages, float* out, float* ws,
                hipStream_t st) {
   const ttsgen_dims& d = h->d;
   const GenBlob& L = h->bl;
-  const GenPlanes none{};
-  const GenPlanes& P = planes != nullptr ? h->pl : none;
   const float* b = h->blob;
   Carver cv{ws};  // (the layout of THIS group: the last one may hold fewer utterances than the reported size is for)
-  const GenWs w = carve_gen(cv, d, G, T, planes != nullptr ? &h->pl : nullptr);
+  const GenWs w = carve_gen(cv, d, G, T, planes != nullptr ? &L : nullptr);
   float *Y = w.Y, *X = w.X, *LX = w.LX, *H = w.H, *R = w.R, *LR = w.LR, *condv = w.condv;
   const int C0 = d.upsample_initial_channel;
-  // one conv: x as fp32, or (sp: a split layer) as the planes its producer left, with the weight planes at wp
-  auto conv = [&](bool sp, const float* x, int M, int Tx, int Cin, int taps, int dil, size_t w_off, size_t wp, size_t b_off, int N) {
-    GemmArgs a = conv_args(x, M, Tx, Cin, taps, dil, b + w_off, b + b_off, N);
-    if (sp) {
-      a.a = make_seg1(plane_hi(x), Cin, taps * Cin);
-      a.a_lo = make_seg1(plane_lo(x, (size_t)M * Cin), Cin, taps * Cin);
-      a.W = plane_hi(planes + wp);
-      a.W_lo = plane_lo(planes + wp, (size_t)N * taps * Cin);
+  auto split = [&](const GConv& c) { return planes != nullptr && c.split; };  // this call runs c in split-fp16
+  // one conv: x as fp32, or (a split layer) as the planes its producer left, with the weight planes at c.p
+  auto conv = [&](const GConv& c, const float* x, int M, int Tx, int dil) {
+    GemmArgs a = conv_args(c, b, x, M, Tx, dil);
+    if (split(c)) {
+      a.a = make_seg1(plane_hi(x), c.Cin, c.K());
+      a.a_lo = make_seg1(plane_lo(x, (size_t)M * c.Cin), c.Cin, c.K());
+      a.W = plane_hi(planes + c.p);
+      a.W_lo = plane_lo(planes + c.p, c.n());
       a.prec = PREC_F16S;
     }
     return a;
@@ -305,26 +317,26 @@ void run_group(const ttsgen_handle* h, const float* planes, const float* z, cons
     launch_gemm(a, A_CONV_DIL, EPI_LRELU2, st);
     if (as_planes && a.prec != PREC_F16S) launch_split(w.tmp, plane_hi(dst), plane_lo(dst, n), n, st);
   };
-  if (g != nullptr) launch_cond(g, b + L.cond_w, b + L.cond_b, condv, G, C0, d.gin_channels, st);
+  if (g != nullptr) launch_cond(g, b + L.cond_w.off, b + L.cond_b.off, condv, G, C0, d.gin_channels, st);
   // models.py:948-950: x = conv_pre(x) (+ cond(g)); the first stage reads lrelu(x, 0.1) (:953)
   {
     const size_t nz = (size_t)G * T * d.initial_channel;
-    if (P.pre) launch_split(z, plane_hi(w.zp), plane_lo(w.zp, nz), nz, st);
-    GemmArgs a = conv(P.pre, P.pre ? w.zp : z, G * T, T, d.initial_channel, 7, 1, L.pre_w, P.pre_w, L.pre_b, C0);
+    if (split(L.pre)) launch_split(z, plane_hi(w.zp), plane_lo(w.zp, nz), nz, st);
+    GemmArgs a = conv(L.pre, split(L.pre) ? w.zp : z, G * T, T, 1);
     a.rowvec = g != nullptr ? condv : nullptr;
     a.slope2 = n_stages == 0 && d.n_up == 0 ? kLreluLast : kLrelu;
-    launch(a, Y, n_stages > 0 && P.up[0]);
+    launch(a, Y, n_stages > 0 && split(L.up[0]));
   }
-  int Ts = T, Cin = C0;
+  int Ts = T;
   for (int i = 0; i < n_stages; ++i) {
-    const int u = d.up_rates[i], C = chan(d, i), Tin = Ts;
-    Ts *= u;
+    const int Tin = Ts;
+    Ts *= d.up_rates[i];
     const int M = G * Ts;
     const float slope_out = i == d.n_up - 1 ? kLreluLast : kLrelu;
-    const bool rs = P.res[i];
+    const bool rs = split(L.res[i][0][0]);  // (the resblocks of a stage switch together)
     // :954 x = ups[i](x): [G*Tin, u*C] = [G*Ts, C]; x and lrelu(x, 0.1) (the first layer of every branch, modules.py:298)
     {
-      GemmArgs a = conv(P.up[i], Y, G * Tin, Tin, Cin, 3, 1, L.up_w[i], P.up_w[i], L.up_b[i], u * C);
+      GemmArgs a = conv(L.up[i], Y, G * Tin, Tin, 1);
       a.out = X;
       launch(a, LX, rs);
     }
@@ -333,13 +345,12 @@ void run_group(const ttsgen_handle* h, const float* planes, const float* z, cons
     // first buffer - into LX, which then becomes Y (carve_gen)
     float* Ssum = Y;
     for (int j = 0; j < d.n_res; ++j) {
-      const int k = d.res_kernels[j];
       for (int l = 0; l < 3; ++l) {
         // modules.py:298-301: xt = c1(lrelu(x)); xt = lrelu(xt)
-        GemmArgs c1 = conv(rs, l == 0 ? LX : LR, M, Ts, C, k, d.res_dilations[j][l], L.rw[i][j][l], P.rw[i][j][l], L.rb[i][j][l], C);
+        GemmArgs c1 = conv(L.res[i][j][l], l == 0 ? LX : LR, M, Ts, d.res_dilations[j][l]);
         launch(c1, H, rs);
         // :304-305: x = c2(xt) + x
-        GemmArgs c2 = conv(rs, H, M, Ts, C, k, 1, L.rw[i][j][3 + l], P.rw[i][j][3 + l], L.rb[i][j][3 + l], C);
+        GemmArgs c2 = conv(L.res[i][j][3 + l], H, M, Ts, 1);
         c2.resid = l == 0 ? X : R;
         if (l < 2) {
           c2.out = R;
@@ -349,7 +360,7 @@ void run_group(const ttsgen_handle* h, const float* planes, const float* z, cons
           if (j == d.n_res - 1) {
             c2.div = (float)d.n_res;  // x = xs / num_kernels; then lrelu for the next stage / conv_post
             c2.slope2 = slope_out;
-            const bool as_planes = i + 1 < n_stages && P.up[i + 1];
+            const bool as_planes = i + 1 < n_stages && split(L.up[i + 1]);
             float* dst = !as_planes && Y == w.Y ? Ssum : LX;
             launch(c2, dst, as_planes);
             if (dst != Y) {
@@ -364,10 +375,9 @@ void run_group(const ttsgen_handle* h, const float* planes, const float* z, cons
         }
       }
     }
-    Cin = C;
   }
   if (n_stages == d.n_up && out != nullptr)  // :964-965
-    hipLaunchKernelGGL(conv_post_tanh_kernel, grid1((size_t)G * Ts), dim3(256), 0, st, Y, b + L.post_w, out, G * Ts, Ts, Cin);
+    hipLaunchKernelGGL(conv_post_tanh_kernel, grid1((size_t)G * Ts), dim3(256), 0, st, Y, b + L.post.w, out, G * Ts, Ts, L.post.Cin);
 }
 
 }  // namespace
@@ -382,7 +392,6 @@ int ttsgen_create(const ttsgen_dims* dims, ttsgen_handle** out) {
   if (!h) return TTSDEC_ERR_INVALID_ARG;
   h->d = *dims;
   h->bl = make_layout(*dims);
-  h->pl = make_planes(*dims);
   h->device = current_device_or_minus1();
   *out = h;
   return TTSDEC_OK;
@@ -392,7 +401,7 @@ int ttsgen_destroy(ttsgen_handle* h) {
   return TTSDEC_OK;
 }
 const char* ttsgen_last_hip_error(const ttsgen_handle* h) { return last_hip_error(h); }
-int ttsgen_num_weight_tensors(const ttsgen_handle* h) { return h ? n_tensors(h->d) : TTSDEC_ERR_INVALID_ARG; }
+int ttsgen_num_weight_tensors(const ttsgen_handle* h) { return h ? h->bl.n_src : TTSDEC_ERR_INVALID_ARG; }
 size_t ttsgen_packed_bytes(const ttsgen_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
 
 int ttsgen_pack_weights(ttsgen_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
@@ -402,45 +411,31 @@ int ttsgen_pack_weights(ttsgen_handle* h, const float* const* src, int n_src, vo
   const ttsgen_dims& d = h->d;
   const GenBlob& L = h->bl;
   float* b = static_cast<float*>(blob);
-  const int C0 = d.upsample_initial_channel;
-  int k = 0;
-  launch_conv_transpose(src[k++], b + L.pre_w, C0, d.initial_channel, 7, st);  // [Co, Ci, 7] -> [Co, 7, Ci]
-  launch_copy(src[k++], b + L.pre_b, C0, st);
-  for (int i = 0; i < d.n_up; ++i) {
-    const int Ci = i == 0 ? C0 : chan(d, i - 1), Co = chan(d, i), u = d.up_rates[i];
-    hipLaunchKernelGGL(pack_up_kernel, grid1((size_t)u * Co * 3 * Ci), dim3(256), 0, st, src[k++], b + L.up_w[i], Ci, Co, u);
-    hipLaunchKernelGGL(rep_bias_kernel, grid1((size_t)u * Co), dim3(256), 0, st, src[k++], b + L.up_b[i], Co, u);
-  }
-  for (int i = 0; i < d.n_up; ++i) {
-    const int C = chan(d, i);
+  pack_conv(src, b, L.pre, st);
+  for (int i = 0; i < d.n_up; ++i) pack_conv(src, b, L.up[i], st);
+  for (int i = 0; i < d.n_up; ++i)
     for (int j = 0; j < d.n_res; ++j)
-      for (int c = 0; c < 6; ++c) {
-        launch_conv_transpose(src[k++], b + L.rw[i][j][c], C, C, d.res_kernels[j], st);
-        launch_copy(src[k++], b + L.rb[i][j][c], C, st);
-      }
-  }
-  launch_conv_transpose(src[k++], b + L.post_w, 1, chan(d, d.n_up - 1), 7, st);  // [1, C, 7] -> [7, C]
-  if (d.gin_channels > 0) {
-    launch_copy(src[k++], b + L.cond_w, (size_t)C0 * d.gin_channels, st);
-    launch_copy(src[k++], b + L.cond_b, C0, st);
-  }
+      for (int c = 0; c < 6; ++c) pack_conv(src, b, L.res[i][j][c], st);
+  pack_conv(src, b, L.post, st);
+  if (d.gin_channels > 0)
+    for (const Vec& v : {L.cond_w, L.cond_b}) launch_copy(src[v.src], b + v.off, v.n, st);
   return pack_end(h, b);
 }
 
 int ttsgen_bind_weights(ttsgen_handle* h, const void* blob) { return bind_blob(h, blob); }
 
-// the workspace of a call: exact fp32 (pl = nullptr), or split-fp16 with the handle's planes
-static size_t gen_ws_bytes(const ttsgen_handle* h, const GenPlanes* pl, int B, int T) {
+// the workspace of a call: exact fp32, or split-fp16 with the handle's split layers
+static size_t gen_ws_bytes(const ttsgen_handle* h, bool split, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
   const int G = group_size(h->d, B, T);
   if (G < 1) return 0;
   Carver cv{nullptr};
-  carve_gen(cv, h->d, G, T, pl);
+  carve_gen(cv, h->d, G, T, split ? &h->bl : nullptr);
   return cv.bytes();
 }
 
 // planes != nullptr: split-fp16 (the handle has split layers)
-size_t ttsgen_workspace_bytes(const ttsgen_handle* h, int B, int T) { return gen_ws_bytes(h, nullptr, B, T); }
+size_t ttsgen_workspace_bytes(const ttsgen_handle* h, int B, int T) { return gen_ws_bytes(h, false, B, T); }
 
 static int gen_call(ttsgen_handle* h, const float* planes, const float* z, const float* g, int B, int T, int n_stages, float* out,
                     void* workspace, size_t workspace_bytes, void* stream) {
@@ -450,7 +445,7 @@ static int gen_call(ttsgen_handle* h, const float* planes, const float* z, const
   const int G = group_size(h->d, B, T);
   if (G < 1) return TTSDEC_ERR_DIMS;
   if (n_stages < h->d.n_up && G < B) return TTSDEC_ERR_INVALID_ARG;  // (the stage read-back holds one group)
-  if (workspace_bytes < gen_ws_bytes(h, planes != nullptr ? &h->pl : nullptr, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255))
+  if (workspace_bytes < gen_ws_bytes(h, planes != nullptr, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255))
     return TTSDEC_ERR_WORKSPACE;
   if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -477,7 +472,7 @@ int ttsgen_forward_stages(ttsgen_handle* h, const float* z, const float* g, int 
 }
 
 // ---- the same forward with the arithmetic as a call argument (include/ttsdec.h) ----
-size_t ttsvits_generator_planes_bytes(const ttsgen_handle* h) { return h ? h->pl.total * sizeof(float) : 0; }
+size_t ttsvits_generator_planes_bytes(const ttsgen_handle* h) { return h ? h->bl.planes_total * sizeof(float) : 0; }
 
 int ttsvits_generator_pack_planes(ttsgen_handle* h, void* planes, void* stream) {
   if (!h) return TTSDEC_ERR_INVALID_ARG;
@@ -488,24 +483,20 @@ int ttsvits_generator_pack_planes(ttsgen_handle* h, void* planes, void* stream) 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ttsgen_dims& d = h->d;
   const GenBlob& L = h->bl;
-  const GenPlanes& P = h->pl;
   const float* b = h->blob;
   float* p = static_cast<float*>(planes);
-  auto split = [&](size_t src, size_t dst, size_t n) { launch_split(b + src, plane_hi(p + dst), plane_lo(p + dst, n), n, st); };
-  const size_t C0 = d.upsample_initial_channel;
-  if (P.pre) split(L.pre_w, P.pre_w, C0 * 7 * d.initial_channel);
+  split_conv(b, p, L.pre, st);
   for (int i = 0; i < d.n_up; ++i) {
-    const size_t Ci = i == 0 ? C0 : chan(d, i - 1), C = chan(d, i), u = d.up_rates[i];
-    if (P.up[i]) split(L.up_w[i], P.up_w[i], u * C * 3 * Ci);
-    for (int j = 0; j < d.n_res && P.res[i]; ++j)
-      for (int c = 0; c < 6; ++c) split(L.rw[i][j][c], P.rw[i][j][c], C * d.res_kernels[j] * C);
+    split_conv(b, p, L.up[i], st);
+    for (int j = 0; j < d.n_res; ++j)
+      for (int c = 0; c < 6; ++c) split_conv(b, p, L.res[i][j][c], st);
   }
   return record_hip_error(h, "pack_planes");
 }
 
 size_t ttsvits_generator_workspace_bytes(const ttsgen_handle* h, int precision, int B, int T) {
   if (!h || (precision != TTSDEC_PREC_F32 && precision != TTSDEC_PREC_SPLIT_F16)) return 0;
-  return gen_ws_bytes(h, precision == TTSDEC_PREC_SPLIT_F16 ? &h->pl : nullptr, B, T);
+  return gen_ws_bytes(h, precision == TTSDEC_PREC_SPLIT_F16, B, T);
 }
 
 int ttsvits_generator_forward(ttsgen_handle* h, int precision, const void* planes, const float* z, const float* g, int B, int T, int n_stages,

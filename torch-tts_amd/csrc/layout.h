@@ -1,5 +1,5 @@
-// Host-side layout helpers shared by every C-ABI family: the alignment grid, the 1-D launch grid, and the Carver that walks a
-// workspace or a weight blob.
+// Host-side layout helpers shared by every C-ABI family: the alignment grid, the 1-D launch grid, the Carver that walks a
+// workspace or a weight blob, and what every blob walk starts from.
 #pragma once
 #include "common.h"
 
@@ -26,6 +26,19 @@ struct Carver {
   }
   f16* take_h(size_t n) { return reinterpret_cast<f16*>(take(n)); }  // n floats = the hi + lo planes of n elements
   size_t bytes() const { return (off + slack) * sizeof(float); }
+};
+
+// A weight blob is walked once, at *_create, into one record per weight; layout, pack, the tensor count and the forward calls read
+// the records.  BlobWalk is what every family's walk starts from: the carver hands out the offsets in blob order, src the source
+// indices in the order include/ttsdec.h documents - the two orders are the same - so src, at the end, is *_num_weight_tensors.
+struct Vec {  // a tensor kept as given, plain fp32 (a bias, LayerNorm gamma / beta, a table): offset and elements in floats
+  size_t off, n;
+  int src;
+};
+struct BlobWalk {
+  Carver cv{nullptr};
+  int src = 0;
+  Vec vec(size_t n) { return {cv.take_off(n), n, src++}; }
 };
 
 }  // namespace ttsdec

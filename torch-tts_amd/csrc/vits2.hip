@@ -32,16 +32,9 @@ struct Lin {
   int N, K, taps, src;
   size_t n() const { return (size_t)N * taps * K; }
 };
-struct Vec {  // a tensor no GEMM reads (LayerNorm gamma / beta, the relative-position tables, the embedding table): plain fp32
-  size_t off, n;
-  int src;
-};
-// The one walk over a blob (at *_create): it hands out the offsets in blob order and the source indices in the order
-// include/ttsdec.h documents - the two orders are the same - so src, at its end, is the family's tensor count.
-struct Walk {
-  Carver cv{nullptr};
-  int src = 0;
-  Vec vec(size_t n) { return {cv.take_off(n), n, src++}; }
+// The one walk over a blob (at *_create; layout.h): offsets in blob order, source indices in the order include/ttsdec.h documents.
+// Its Vec is a tensor no GEMM reads (LayerNorm gamma / beta, the relative-position tables, the embedding table).
+struct Walk : BlobWalk {
   Lin lin(int N, int K, int taps = 1, int n_src = 2) {  // (n_src: 6 for q / k / v stacked into one weight)
     Lin l{0, 0, N, K, taps, src};
     l.w = cv.take_off(2 * l.n());
