@@ -294,6 +294,39 @@ int ttsdec_decode(ttsdec_handle* h, const float* memory, int B, int L, int t_beg
                   const float* teacher, int teacher_T, const uint8_t* teacher_flags, float* y, float* s, float* w,
                   int32_t* T_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * ttsdec_decode, free-running, under the PER-UTTERANCE stop rule (batched synthesis): every argument ttsdec_decode takes but
+ * check_stop, and
+ *
+ *   stop_steps    device int32 [B].  Utterance b STOPS at the first step t_b at which any of its r stop logits is
+ *                 < stop_threshold; stop_steps[b] = t_b then, and later crossings of the same utterance change nothing.  An
+ *                 utterance that has not fired holds 0x7fffffff.  A call with t_begin = 0 resets the array (and the count of
+ *                 stopped utterances, which lives in the workspace) together with the recurrent state; calls with t_begin > 0
+ *                 continue it, so the chunks of one decode must pass the same array.
+ *   The CALL fires at t_all = max_b t_b, the step at which the last live utterance stops: from there on everything is as
+ *   after the batch-global rule fired at t_all - the outputs are final through step t_all inclusive, later steps of this and
+ *   following calls are skipped, the "State after a fired stop" note above applies.
+ *   An utterance that has stopped is still computed up to t_all (the tiles are fixed): its outputs at steps > t_b are
+ *   don't-care; ttsdec_zero_tail clears them.
+ *   T_out         [0] = t_all + 1 if the call has fired, else t_begin + n_steps; [1]: the flag bits of ttsdec_decode.  Bit 1,
+ *                 the split-fp16 range flag, may also be raised by an utterance past its own stop step, whose free-running
+ *                 frames nobody bounds.
+ *   teacher       must be NULL (TTSDEC_ERR_INVALID_ARG otherwise, as for stop_steps == NULL and an odd t_begin): the
+ *                 per-utterance rule is free-running only.  teacher_T and teacher_flags are ignored.
+ * For B = 1 this is ttsdec_decode with check_stop = 1, bit for bit; for any B the arithmetic of a step is ttsdec_decode's.
+ */
+int ttsdec_decode_each(ttsdec_handle* h, const float* memory, int B, int L, int t_begin, int n_steps, int t_stride,
+                       float stop_threshold, int dropout_mode, const uint8_t* masks, uint64_t seed, const float* teacher,
+                       int teacher_T, const uint8_t* teacher_flags, float* y, float* s, float* w, int32_t* stop_steps,
+                       int32_t* T_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Zeroes rows [lengths[b] / len_div, T) of every entry b of x [B, T, C] fp32, entries batch_stride floats apart (>= T * C): what
+ * a ragged batch holds past each utterance's end.  lengths: device int32 [B], clamped to [0, T * len_div]; B <= 65535.  Write-only,
+ * and only over the padding.  (After ttsdec_decode_each: y with C = d_mel, s with C = 1, w with C = L, T in steps and
+ * len_div = r for lengths in frames.) */
+int ttsdec_zero_tail(ttsdec_handle* h, float* x, const int32_t* lengths, int B, int T, int64_t batch_stride, int C, int len_div,
+                     void* stream);
+
 /* Postnet scratch for B*T frames. */
 size_t ttsdec_postnet_workspace_bytes(const ttsdec_handle* h, int B, int T);
 
@@ -302,6 +335,16 @@ size_t ttsdec_postnet_workspace_bytes(const ttsdec_handle* h, int B, int T);
  * TTSDEC_POSTNET_TYPE_MEL2, MelPostnet2.forward (modules.py:213-216). */
 int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision, float* y_post, void* workspace,
                    size_t workspace_bytes, void* stream);
+
+/* The Postnet on a ragged batch: row b of y_post, frames [0, lengths[b]), is what ttsdec_postnet gives for y[b, :lengths[b]]
+ * alone (B = 1, T = lengths[b]) - the input of every conv layer, y and each hidden activation, is zero at frames
+ * >= lengths[b], and so is y_post.  What y holds there is never used.
+ *   lengths       device int32 [B], frames, each in [0, T] (0: an all-zero row; values outside are clamped); B <= 65535.
+ *                 NULL = ttsdec_postnet: the same launches, the same bits.
+ * Same workspace (ttsdec_postnet_workspace_bytes).  The conv kernels are ttsdec_postnet's; between them a write-only pass zeroes
+ * each activation's padding. */
+int ttsdec_postnet_ragged(ttsdec_handle* h, const float* y, const int32_t* lengths, int B, int T, int precision, float* y_post,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* One decoder-cell step on caller-held state (Taco2ProdDecoderCell.forward,
  * tacotron/decoder_cell.py:180-195), for callers that drive the cell directly.

@@ -155,8 +155,17 @@ FAMILIES = (
             vp, vp, vp, vp,                   # y, s, w, T_out
             vp, sz, vp,                       # workspace, workspace_bytes, stream
         ]),
+        "decode_each": (i32, [
+            vp, vp, i32, i32, i32, i32, i32,  # h, memory, B, L, t_begin, n_steps, t_stride
+            f32, i32, vp, u64,                # stop_threshold, dropout_mode, masks, seed
+            vp, i32, vp,                      # teacher (NULL), teacher_T, teacher_flags
+            vp, vp, vp, vp, vp,               # y, s, w, stop_steps, T_out
+            vp, sz, vp,                       # workspace, workspace_bytes, stream
+        ]),
+        "zero_tail": (i32, [vp, vp, vp, i32, i32, C.c_int64, i32, i32, vp]),  # h, x, lengths, B, T, batch_stride, C, len_div, stream
         "postnet_workspace_bytes": _ws_bytes,
         "postnet": (i32, [vp, vp, i32, i32, i32, vp, vp, sz, vp]),
+        "postnet_ragged": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]),  # h, y, lengths, B, T, precision, y_post, ws, bytes, stream
         "cell_step": (i32, [
             vp, vp, vp, i32, i32,             # h, x, memory, B, L
             vp, vp, vp, vp, vp, vp,           # w, ctx, h_att, c_att, h_dec, c_dec

@@ -1098,8 +1098,10 @@ size_t ttsdec_workspace_bytes(const ttsdec_handle* h, int B, int L) {
 static int decode_impl(ttsdec_handle* h, const float* memory, int B, int L, int t_begin, int n_steps, int t_stride,
                        float stop_threshold, int check_stop, int dropout_mode, const uint8_t* masks, uint64_t seed,
                        const float* teacher, int teacher_T, const uint8_t* teacher_flags, float* y, float* s, float* w,
-                       int32_t* T_out, void* workspace, size_t workspace_bytes, void* stream, bool stamp_loop) {
+                       int32_t* T_out, void* workspace, size_t workspace_bytes, void* stream, bool stamp_loop,
+                       int32_t* stop_steps = nullptr) {
   if (!h || !memory || !y || !s || !w || !workspace) return TTSDEC_ERR_INVALID_ARG;
+  if ((check_stop == 2) != (stop_steps != nullptr)) return TTSDEC_ERR_INVALID_ARG;  // (2: ttsdec_decode_each only)
   if (B <= 0 || L <= 0 || t_begin < 0 || n_steps < 0 || t_stride < n_steps) return TTSDEC_ERR_INVALID_ARG;
   if (dropout_mode < TTSDEC_DROPOUT_OFF || dropout_mode > TTSDEC_DROPOUT_PHILOX) return TTSDEC_ERR_INVALID_ARG;
   if (dropout_mode == TTSDEC_DROPOUT_MASKS && !masks) return TTSDEC_ERR_INVALID_ARG;
@@ -1130,6 +1132,7 @@ static int decode_impl(ttsdec_handle* h, const float* memory, int B, int L, int 
     ia.out_mpad = act_mpad(h, B);
     ia.memory = is_taco2(d) ? memory : nullptr;
     ia.B = B; ia.L = L; ia.D = d.d_ctx; ia.Ha = d.h_att; ia.Hd = d.h_dec; ia.d_mel = d.d_mel;
+    ia.stop_steps = stop_steps;
     launch_init(ia, st);
   }
   CallArgs ca;
@@ -1140,6 +1143,7 @@ static int decode_impl(ttsdec_handle* h, const float* memory, int B, int L, int 
   ca.debug_flags = h->debug_flags > 0 ? h->debug_flags : 0;
   ca.spin_limit = h->spin_limit > 0 ? h->spin_limit : kRoleSpinLimit;
   ca.loop_stamps = stamp_loop ? sb.loop_stamps : nullptr;
+  ca.stop_steps = stop_steps; ca.stop_rows = B;
   // measurement only: TTSDEC_STAMPS=<file> collects per-workgroup time stamps of the two-role launches of the
   // call's last step and writes them to <file> (synchronises; never set in production)
   const char* stamp_file = getenv("TTSDEC_STAMPS");
@@ -1185,8 +1189,17 @@ int ttsdec_decode(ttsdec_handle* h, const float* memory, int B, int L, int t_beg
                   float stop_threshold, int check_stop, int dropout_mode, const uint8_t* masks, uint64_t seed,
                   const float* teacher, int teacher_T, const uint8_t* teacher_flags, float* y, float* s, float* w,
                   int32_t* T_out, void* workspace, size_t workspace_bytes, void* stream) {
-  return decode_impl(h, memory, B, L, t_begin, n_steps, t_stride, stop_threshold, check_stop, dropout_mode, masks, seed, teacher, teacher_T,
+  return decode_impl(h, memory, B, L, t_begin, n_steps, t_stride, stop_threshold, check_stop != 0, dropout_mode, masks, seed, teacher, teacher_T,
                      teacher_flags, y, s, w, T_out, workspace, workspace_bytes, stream, false);
+}
+
+int ttsdec_decode_each(ttsdec_handle* h, const float* memory, int B, int L, int t_begin, int n_steps, int t_stride,
+                       float stop_threshold, int dropout_mode, const uint8_t* masks, uint64_t seed, const float* teacher,
+                       int teacher_T, const uint8_t* teacher_flags, float* y, float* s, float* w, int32_t* stop_steps,
+                       int32_t* T_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (teacher || !stop_steps) return TTSDEC_ERR_INVALID_ARG;  // (free-running only: a teacher-forced decode has no stop rule)
+  return decode_impl(h, memory, B, L, t_begin, n_steps, t_stride, stop_threshold, 2, dropout_mode, masks, seed, nullptr, teacher_T,
+                     teacher_flags, y, s, w, T_out, workspace, workspace_bytes, stream, false, stop_steps);
 }
 
 int ttsdec_profile_loop(ttsdec_handle* h, const float* memory, int B, int L, int n_steps, int dropout_mode, const uint8_t* masks,
@@ -1255,9 +1268,14 @@ size_t ttsdec_postnet_workspace_bytes(const ttsdec_handle* h, int B, int T) {
   return cv.bytes();
 }
 
-int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision, float* y_post, void* workspace,
-                   size_t workspace_bytes, void* stream) {
+// lengths != nullptr (ttsdec_postnet_ragged): every conv layer's input - y and each hidden activation, in whatever form the
+// precision keeps it - is zeroed at frames >= lengths[b] by a write-only pass over the padding (launch_zero_tail), so each
+// utterance sees the zero padding it would see alone; the conv kernels, the 256-wide schedule included, are the same launches.
+// lengths == nullptr adds no launch and no copy: ttsdec_postnet as it always was.
+static int postnet_impl(ttsdec_handle* h, const float* y, const int32_t* lengths, int B, int T, int precision, float* y_post,
+                        void* workspace, size_t workspace_bytes, void* stream) {
   if (!h || !y || !y_post || !workspace || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (lengths && B > 65535) return TTSDEC_ERR_INVALID_ARG;  // (launch_zero_tail: one grid row per utterance)
   if (h->d.postnet_layers <= 0) return TTSDEC_ERR_DIMS;
   if (precision != TTSDEC_POSTNET_F32 && precision != TTSDEC_POSTNET_BF16 && precision != TTSDEC_POSTNET_SPLIT_F16)
     return TTSDEC_ERR_INVALID_ARG;
@@ -1290,12 +1308,31 @@ int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision
     g.ldw = g.K = (int)w.cols; g.M = (int)M; g.N = g.ldo = (int)w.rows;
     return g;
   };
+  // ragged batches: the tail of a [M, C] activation in the form of `prec` (fp32 rows, a bf16 plane, or a hi / lo fp16 plane pair)
+  const int ew = prec == PREC_F32 ? 1 : 2;  // elements per 32-bit word
+  auto mask = [&](Planes a, int C) {
+    if (!lengths) return;
+    launch_zero_tail(const_cast<void*>(a.p0), lengths, B, T, (size_t)T * C / ew, C / ew, 1, st);
+    if (a.p1 != a.p0) launch_zero_tail(const_cast<void*>(a.p1), lengths, B, T, (size_t)T * C / ew, C / ew, 1, st);
+  };
+  auto mask_f32 = [&](float* a) {
+    if (lengths) launch_zero_tail(a, lengths, B, T, (size_t)T * d.d_mel, d.d_mel, 1, st);
+  };
+  // y as the first layer reads it; ragged and exact fp32: a copy in `buf`, since y itself is the caller's
+  auto first_input = [&](char* buf) {
+    if (lengths && prec == PREC_F32) {
+      launch_copy(y, reinterpret_cast<float*>(buf), M * d.d_mel, st);
+      return Planes{buf, buf};
+    }
+    return act_input(prec, y, buf, M * d.d_mel, st);
+  };
 
   if (d.postnet_type == TTSDEC_POSTNET_TYPE_MEL2) {
     // MelPostnet2.forward (modules.py:213-216): x = x + conv3(lrelu(BN(conv2(lrelu(BN(conv1(x))))))) per layer;
     // the fp32 residual stream and its 16-bit planes ping-pong in xbuf / xpl
     const float* xcur = y;
-    Planes x = act_input(prec, y, pw.xpl[1], M * d.d_mel, st);
+    Planes x = first_input(pw.xpl[1]);
+    mask(x, d.d_mel);  // (the residual stream xcur may stay y: what it adds past an utterance's end is zeroed with the sum)
     for (int i = 0; i < d.postnet_layers; ++i) {
       Planes a = x;
       for (int c = 0; c < 2; ++c) {  // conv1 / conv2 + BN + LeakyReLU
@@ -1303,6 +1340,7 @@ int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision
         g.alpha = h->blob + L.p2_alpha[i][c]; g.beta = h->blob + L.p2_beta[i][c];
         a = set_output(g, prec, pw.act[c], M * Hh);
         launch_gemm(g, A_CONV, EPI_BN_LRELU, st);
+        mask(a, Hh);
       }
       GemmArgs g = layer(a, Hh, d.postnet_kernel, L.p2[i][2]);  // conv3 + residual
       g.resid = xcur;
@@ -1311,12 +1349,15 @@ int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision
       if (!last) x = set_output(g, prec, prec == PREC_F32 ? reinterpret_cast<char*>(xnew) : pw.xpl[i & 1], M * d.d_mel);
       g.out = xnew;  // (the 16-bit modes keep the fp32 stream beside the planes: the next layer's residual)
       launch_gemm(g, A_CONV, EPI_RESIDUAL, st);
+      mask_f32(xnew);
+      if (!last && prec != PREC_F32) mask(x, d.d_mel);
       xcur = xnew;
     }
     return record_hip_error(h, "postnet2");
   }
 
-  Planes in = act_input(prec, y, pw.yin, M * d.d_mel, st);
+  Planes in = first_input(pw.yin);
+  mask(in, d.d_mel);
   for (int i = 0; i < d.postnet_layers; ++i) {
     GemmArgs g = layer(in, i ? Hh : d.d_mel, d.postnet_kernel, L.conv[i]);
     g.alpha = h->blob + L.conv_alpha[i]; g.beta = h->blob + L.conv_beta[i];
@@ -1326,15 +1367,42 @@ int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision
     // bf16; TTSDEC_CONV256=0 keeps the shared tile (measurement)
     static const bool use256 = [] { const char* e = getenv("TTSDEC_CONV256"); return !(e && e[0] == '0'); }();
     if (use256 && prec == PREC_F32 &&
-        launch_conv256_f32(static_cast<const float*>(g.a.p0), static_cast<const float*>(g.W), g.alpha, g.beta, g.out, (int)M, T, g.Cin, g.taps, Hh, st))
+        launch_conv256_f32(static_cast<const float*>(g.a.p0), static_cast<const float*>(g.W), g.alpha, g.beta, g.out, (int)M, T, g.Cin, g.taps, Hh, st)) {
+      mask(in, Hh);
       continue;
-    if (use256 && prec == PREC_BF16 && launch_conv256_bf16(g.a.p0, g.W, g.alpha, g.beta, o, (int)M, T, g.Cin, g.taps, Hh, st)) continue;
+    }
+    if (use256 && prec == PREC_BF16 && launch_conv256_bf16(g.a.p0, g.W, g.alpha, g.beta, o, (int)M, T, g.Cin, g.taps, Hh, st)) {
+      mask(in, Hh);
+      continue;
+    }
     launch_gemm(g, A_CONV, EPI_BN_ISRU, st);
+    mask(in, Hh);
   }
   GemmArgs g = layer(in, Hh, 0, L.fc);
   g.resid = y; g.out = y_post;
   launch_gemm(g, A_PLAIN, EPI_RESIDUAL, st);
+  mask_f32(y_post);
   return record_hip_error(h, "postnet");
+}
+
+int ttsdec_postnet(ttsdec_handle* h, const float* y, int B, int T, int precision, float* y_post, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+  return postnet_impl(h, y, nullptr, B, T, precision, y_post, workspace, workspace_bytes, stream);
+}
+
+int ttsdec_postnet_ragged(ttsdec_handle* h, const float* y, const int32_t* lengths, int B, int T, int precision, float* y_post,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  return postnet_impl(h, y, lengths, B, T, precision, y_post, workspace, workspace_bytes, stream);
+}
+
+int ttsdec_zero_tail(ttsdec_handle* h, float* x, const int32_t* lengths, int B, int T, int64_t batch_stride, int C, int len_div,
+                     void* stream) {
+  if (!h || !x || !lengths || B <= 0 || B > 65535 || T <= 0 || C <= 0 || len_div <= 0 || batch_stride < (int64_t)T * C)
+    return TTSDEC_ERR_INVALID_ARG;
+  const int rc = check_device(h);
+  if (rc != TTSDEC_OK) return rc;
+  launch_zero_tail(x, lengths, B, T, (size_t)batch_stride, C, len_div, static_cast<hipStream_t>(stream));
+  return record_hip_error(h, "zero_tail");
 }
 
 int ttsdec_cell_step(ttsdec_handle* h, const float* x, const float* memory, int B, int L, float* w, float* ctx,

@@ -52,8 +52,30 @@ struct Ctrl {
   // loop_stamps[slot * kLoopStampNodes + position of the launch in the step order] - the launches' start times inside the
   // replayed graph, at the price of one 8-byte store per launch
   unsigned long long* loop_stamps;
-  int pad[22];
+  // per-utterance stop rule (check_stop = 2, ttsdec_decode_each; stop_fire below): the caller's [B] first-firing steps, how many
+  // rows have fired so far, and B.  Reset with the recurrent state (t_begin == 0), kept across the chunks of one decode.
+  int32_t* stop_steps;
+  int rows_stopped, stop_rows;
+  int pad[18];
 };
+static_assert(sizeof(Ctrl) == 232, "the control block's size is part of the workspace layout: take new words out of pad");
+
+// The stop rule at a firing logit (v < stop_thr) of row `row` at step `t`; mode = Ctrl::check_stop (1 or 2).
+//   1: decoder.py:68, batch-global - the call ends at the first step at which ANY row fires.
+//   2: per utterance - row b stops at its first firing step t_b (stop_steps[b]), the call ends at max_b t_b: the thread that
+//      records the last row's first firing lowers stop_t.  Steps are stream-ordered and every firing of one step carries the
+//      same t, so that thread's t is the maximum whatever the order inside the step.
+// Only ever reached from a firing logit of a real row (row < B), so steps that fire nothing run the same code as before.
+__device__ __forceinline__ void stop_fire(Ctrl* c, int mode, int row, int t) {
+  if (mode != 2) {
+    atomicMin(&c->stop_t, t);
+    return;
+  }
+  const int old = atomicMin(&c->stop_steps[row], t);
+  if (old != kStopNever) return;  // a later crossing of a row that has stopped, or the row's second logit of this step
+  const int n = atomicAdd(&c->rows_stopped, 1) + 1;
+  if (n == c->stop_rows) atomicMin(&c->stop_t, t);
+}
 constexpr int kLoopStampNodes = 8;   // >= launches per step
 constexpr int kLoopStampSlots = 32;  // >= steps per captured graph
 __device__ __forceinline__ void loop_stamp(const Ctrl* c, int slot, int node) {

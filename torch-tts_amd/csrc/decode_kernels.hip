@@ -317,10 +317,10 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void gemm_rows_ke
         as_g(g.y_out)[((size_t)m * g.t_stride * g.r + (size_t)g.t_rel * g.r + jf) * g.d_mel + c] = v;
         if (jf == g.r - 1) g.ynext[(size_t)m * g.d_mel + c] = v;  // decoder.py:48 y_t[:, -1, :]
       } else {
-        // decoder.py:52 stop logit; decoder.py:68 batch-global rule
+        // decoder.py:52 stop logit; decoder.py:68 batch-global rule, or the per-utterance one (common.h stop_fire; m < M = B here)
         const int jf = n - nm;
         as_g(g.s_out)[(size_t)m * g.t_stride * g.r + (size_t)g.t_rel * g.r + jf] = v;
-        if (g.check_stop && v < g.stop_thr) atomicMin(&g.ctrl->stop_t, g.t);
+        if (g.check_stop && v < g.stop_thr) stop_fire(g.ctrl, g.check_stop, m, g.t);
       }
     } else if (EK == EPI_BN_ISRU) {
       // modules.py:181 isru(BatchNorm1d(conv(x))) with eval-mode BN as x*alpha + beta
@@ -621,7 +621,9 @@ __global__ void init_state_kernel(InitArgs g) {
     g.ctrl->stop_t = kStopNever;
     g.ctrl->steps_done = 0;
     g.ctrl->range_err = 0;
+    g.ctrl->rows_stopped = 0;
   }
+  if (g.stop_steps != nullptr && i < (size_t)g.B) g.stop_steps[i] = kStopNever;  // per-utterance stop rule (common.h stop_fire)
   const size_t nHa = (size_t)g.B * g.Ha, nHd = (size_t)g.B * g.Hd;
   if (i < nHa) {
     g.h_att[i] = g.h0_att[i % g.Ha];
@@ -696,6 +698,8 @@ __global__ void set_call_kernel(Ctrl* c, CallArgs a) {
   c->debug_flags = a.debug_flags;
   c->spin_limit = a.spin_limit;
   c->loop_stamps = a.loop_stamps;
+  c->stop_steps = a.stop_steps;
+  c->stop_rows = a.stop_rows;
 }
 void launch_set_call(Ctrl* ctrl, const CallArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(set_call_kernel, dim3(1), dim3(1), 0, st, ctrl, a);
@@ -855,6 +859,30 @@ __global__ void fill_rows_kernel(float* dst, const float* row, int n_rows, int n
 void launch_fill_rows(float* dst, const float* row, int n_rows, int n_cols, hipStream_t st) {
   const size_t n = (size_t)n_rows * n_cols;
   hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dst, row, n_rows, n_cols);
+}
+
+// Ragged batches: zeroes rows [lengths[b] / len_div, T) of every batch entry b of a [B, T, row_words] array of 32-bit words (an
+// fp32 activation, or one 16-bit plane, two elements per word), entries batch_words apart.  Write-only: blocks whose rows all
+// lie before the entry's end leave at once, so the pass costs what the padding is, not what the array is.  Lengths are clamped to
+// [0, T]: nothing outside the array is ever written.
+__global__ void zero_tail_kernel(uint32_t* buf, const int32_t* lengths, int T, size_t batch_words, int row_words, int len_div,
+                                 int rows_per_block) {
+  const int b = blockIdx.y;
+  int len = lengths[b] / len_div;
+  len = len < 0 ? 0 : (len > T ? T : len);
+  const int t0 = blockIdx.x * rows_per_block;
+  const int lo = len > t0 ? len : t0, hi = t0 + rows_per_block < T ? t0 + rows_per_block : T;
+  if (lo >= hi) return;
+  uint32_t* p = buf + (size_t)b * batch_words + (size_t)lo * row_words;
+  const size_t n = (size_t)(hi - lo) * row_words;
+  for (size_t i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0u;
+}
+void launch_zero_tail(void* buf, const int32_t* lengths, int B, int T, size_t batch_words, int row_words, int len_div, hipStream_t st) {
+  if (B <= 0 || T <= 0 || row_words <= 0) return;
+  int rows = 4096 / row_words;  // ~16 KiB of stores per block
+  rows = rows < 1 ? 1 : rows;
+  hipLaunchKernelGGL(zero_tail_kernel, dim3((unsigned)((T + rows - 1) / rows), (unsigned)B), dim3(256), 0, st,
+                     static_cast<uint32_t*>(buf), lengths, T, batch_words, row_words, len_div, rows);
 }
 
 __global__ void to_bf16_kernel(const float* src, bf16* dst, size_t n) {

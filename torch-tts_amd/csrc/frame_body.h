@@ -317,7 +317,8 @@ __device__ __forceinline__ void frame_body(FrameArgs g, float* lds, int bx, int 
         }
       }
     }
-    if (fire && g.check_stop && g.ctrl != nullptr) atomicMin(&g.ctrl->stop_t, t - 1);  // decoder.py:68
+    // decoder.py:68, or the per-utterance rule (common.h stop_fire; `fire` implies fm < M: it is only set under `store`)
+    if (fire && g.check_stop && g.ctrl != nullptr) stop_fire(g.ctrl, g.check_stop, fm, t - 1);
   }
   if (g.only_finalize) {
     report_range(over, g.ctrl);

@@ -283,9 +283,12 @@ struct InitArgs {
   int out_mpad;  // > 0: chunked layout of those planes (common.h Seg3)
   const float* memory;  // != nullptr: ctx_0 = bmm(w_0, memory) = memory[:, 0, :] (Taco2DecoderCell, decoder_cell.py:118)
   int B, L, D, Ha, Hd, d_mel;
+  int32_t* stop_steps;  // [B] or nullptr: reset to kStopNever (per-utterance stop rule)
 };
 void launch_init(const InitArgs& a, hipStream_t st);
 void launch_finish(Ctrl* ctrl, int32_t* T_out, hipStream_t st);
+// zeroes rows [lengths[b] / len_div, T) of each of B entries of [T, row_words] 32-bit words, batch_words apart (B <= 65535)
+void launch_zero_tail(void* buf, const int32_t* lengths, int B, int T, size_t batch_words, int row_words, int len_div, hipStream_t st);
 struct CallArgs {  // copied into *ctrl by launch_set_call at the start of every ttsdec_decode
   int t_begin, n_steps, t_stride, check_stop, dropout_mode, teacher_T;
   float stop_thr;
@@ -298,6 +301,8 @@ struct CallArgs {  // copied into *ctrl by launch_set_call at the start of every
   unsigned long long* stamps;  // measurement only
   int debug_flags, spin_limit;  // test hooks (Ctrl)
   unsigned long long* loop_stamps;  // measurement only (Ctrl)
+  int32_t* stop_steps;              // check_stop = 2: the caller's [B] stop steps, and B (Ctrl)
+  int stop_rows;
 };
 void launch_set_call(Ctrl* ctrl, const CallArgs& a, hipStream_t st);
 void launch_advance(Ctrl* ctrl, int n_slots, hipStream_t st);

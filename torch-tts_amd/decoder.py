@@ -83,22 +83,40 @@ class Decoder(PackedWeightsMixin, nn.Module):
         cap = total_steps if total_steps is not None else (self.max_decoder_steps or None)
         check_stop = x is None
 
-        if self.dropout_source == "reference_rng":
-            mode = _lib.DROPOUT_MASKS
-            stream = MaskStream(B, self.decoder_cell.dim_pre, self.decoder_cell.pre_net.p_dropout,
-                                p_no_forcing=p_no_forcing if x is not None else None,
-                                teacher_steps=total_steps if x is not None else None,
-                                d_pre_hidden=getattr(self.decoder_cell, "dim_pre_hidden", None))
-        elif self.dropout_source == "philox":
-            mode, stream = _lib.DROPOUT_PHILOX, None
-        elif self.dropout_source == "off":
-            mode, stream = _lib.DROPOUT_OFF, None
-        else:
-            raise ValueError(f"unknown dropout_source {self.dropout_source!r}")
+        mode, stream = self._dropout(B, p_no_forcing=p_no_forcing if x is not None else None,
+                                     teacher_steps=total_steps if x is not None else None)
         if x is not None and p_no_forcing and stream is None:
             # teacher-forcing coin flips still come from the host generator, like the reference
             stream = MaskStream(B, self.decoder_cell.dim_pre, 0.0, p_no_forcing=p_no_forcing, teacher_steps=total_steps)
 
+        def launch(t, n, masks_dev, flags_dev, y, s, w, t_out):
+            eng.decode(
+                memory, t_begin=t, n_steps=n, stop_threshold=float(self.stop_threshold), check_stop=check_stop,
+                dropout_mode=mode, masks=masks_dev, seed=int(self.dropout_seed), teacher=teacher,
+                teacher_flags=flags_dev, y=y, s=s, w=w, t_out=t_out,
+            )
+
+        y, s, w, _ = self._chunked_decode(eng, memory, mode, stream, cap, total_steps, teacher, launch)
+        return y, s.unsqueeze(2), w  # B x T x D_mel, B x T x 1, B x T x L
+
+    def _dropout(self, B, **stream_args):
+        """(dropout mode, MaskStream or None) of ``dropout_source``; stream_args: the teacher-forcing draws of the stream."""
+        if self.dropout_source == "reference_rng":
+            return _lib.DROPOUT_MASKS, MaskStream(B, self.decoder_cell.dim_pre, self.decoder_cell.pre_net.p_dropout,
+                                                  d_pre_hidden=getattr(self.decoder_cell, "dim_pre_hidden", None), **stream_args)
+        if self.dropout_source == "philox":
+            return _lib.DROPOUT_PHILOX, None
+        if self.dropout_source == "off":
+            return _lib.DROPOUT_OFF, None
+        raise ValueError(f"unknown dropout_source {self.dropout_source!r}")
+
+    def _chunked_decode(self, eng, memory, mode, stream, cap, total_steps, teacher, launch):
+        """The step loop both stop rules share: chunks of ``chunk_steps`` (one call when total_steps is given) from step 0, one
+        host sync per chunk, the range-flag error, the role-timeout fallback.  ``launch(t, n, masks, teacher_flags, y, s, w,
+        t_out)`` enqueues steps [t, t + n) - ``ttsdec_decode`` or ``ttsdec_decode_each``.  Returns (y, s [B, T], w, steps produced)."""
+        device = memory.device
+        B, L, _ = memory.shape
+        r, dm = self.r, self.dim_mel
         chunk = max(2, int(self.chunk_steps) + (int(self.chunk_steps) & 1))  # even: ttsdec_decode ties buffer parity to t_begin
 
         def run():
@@ -106,7 +124,7 @@ class Decoder(PackedWeightsMixin, nn.Module):
             ys: List[torch.Tensor] = []
             ss: List[torch.Tensor] = []
             wsl: List[torch.Tensor] = []
-            flags_all = torch.ones(total_steps if x is not None else 0, dtype=torch.uint8)
+            flags_all = torch.ones(total_steps if teacher is not None else 0, dtype=torch.uint8)
             t_out = torch.zeros(2, dtype=torch.int32, device=device)
             t = 0
             produced = 0
@@ -119,17 +137,13 @@ class Decoder(PackedWeightsMixin, nn.Module):
                     masks, flags = stream.draw(n)
                     if mode == _lib.DROPOUT_MASKS:
                         masks_dev = masks.to(device, non_blocking=False)
-                    if x is not None:
+                    if teacher is not None:
                         flags_all[t : t + n] = flags
                 flags_dev = flags_all.to(device) if teacher is not None else None
                 y = torch.empty(B, n * r, dm, dtype=torch.float32, device=device)
                 s = torch.empty(B, n * r, dtype=torch.float32, device=device)
                 w = torch.empty(B, n, L, dtype=torch.float32, device=device)
-                eng.decode(
-                    memory, t_begin=t, n_steps=n, stop_threshold=float(self.stop_threshold), check_stop=check_stop,
-                    dropout_mode=mode, masks=masks_dev, seed=int(self.dropout_seed), teacher=teacher,
-                    teacher_flags=flags_dev, y=y, s=s, w=w, t_out=t_out,
-                )
+                launch(t, n, masks_dev, flags_dev, y, s, w, t_out)
                 done, flags = (int(v) for v in t_out.tolist())  # the one host sync of this chunk
                 fired = flags & 1
                 if flags & 4:
@@ -171,4 +185,42 @@ class Decoder(PackedWeightsMixin, nn.Module):
         y = ys[0] if len(ys) == 1 else torch.cat(ys, dim=1)
         s = ss[0] if len(ss) == 1 else torch.cat(ss, dim=1)
         w = wsl[0] if len(wsl) == 1 else torch.cat(wsl, dim=1)
-        return y, s.unsqueeze(2), w  # B x T x D_mel, B x T x 1, B x T x L
+        return y, s, w, produced
+
+    def forward_each(self, memory, mmask, max_steps: int = 0):
+        """Free-running batched decode in which EACH utterance ends at its own stop token (``ttsdec_decode_each``): row b stops
+        at the first step t_b at which one of its r stop logits is below ``stop_threshold``, and the call ends at the step at
+        which the last row stops - where ``forward`` ends the whole batch at the first row's.  Inference only (eval mode, no
+        autograd graph).  ``max_steps`` as in ``forward``: at most max_steps + 1 steps (0: unbounded, or ``max_decoder_steps``).
+
+        Returns ``(y, s, w, lengths, stopped)``: y [B, T, D_mel], s [B, T], w [B, T / r, L] with T = (last stop step + 1) * r;
+        ``lengths`` int64 [B] on the device, in frames: (t_b + 1) * r, or T for a row that never fired before the cap;
+        ``stopped`` bool [B].  y, s and w are ZERO past each row's length (a stopped row is still computed while others run;
+        what it produced there is cleared).  The arithmetic of every step is ``forward``'s: a row's frames up to its length are
+        bit-identical to those of ``forward(memory, mmask, max_steps=T / r - 1)``.  One host sync per chunk of steps."""
+        if not memory.is_cuda:
+            raise RuntimeError(
+                "Decoder runs on the HIP path only: move the model and its inputs to a ROCm device (no CPU fallback)"
+            )
+        if self.training or (torch.is_grad_enabled() and (memory.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            raise RuntimeError("Decoder.forward_each is inference only: call module.eval() and run it under torch.no_grad()")
+        device = memory.device
+        memory = memory.detach().to(torch.float32).contiguous()
+        B, r = memory.shape[0], self.r
+        if B > 65535:  # (ttsdec_zero_tail and ttsdec_postnet_ragged take one grid row per utterance: said before any step runs)
+            raise ValueError(f"forward_each: {B} utterances in one batch; at most 65535 (split the batch)")
+        eng = self.engine(device)
+        cap = int(max_steps) + 1 if max_steps else (self.max_decoder_steps or None)
+        mode, stream = self._dropout(B)
+        stop_steps = torch.empty(B, dtype=torch.int32, device=device)  # reset by the t_begin = 0 call, kept across chunks
+
+        def launch(t, n, masks_dev, flags_dev, y, s, w, t_out):
+            eng.decode_each(memory, t_begin=t, n_steps=n, stop_threshold=float(self.stop_threshold), dropout_mode=mode,
+                            masks=masks_dev, seed=int(self.dropout_seed), y=y, s=s, w=w, stop_steps=stop_steps, t_out=t_out)
+
+        y, s, w, produced = self._chunked_decode(eng, memory, mode, stream, cap, None, None, launch)
+        stopped = stop_steps < produced  # (a row that has not fired holds 0x7fffffff)
+        lengths32 = torch.where(stopped, (stop_steps + 1) * r, torch.full_like(stop_steps, produced * r))
+        for x, div in ((y, 1), (s, 1), (w, r)):
+            eng.zero_tail(x, lengths32, div)
+        return y, s, w, lengths32.to(torch.int64), stopped

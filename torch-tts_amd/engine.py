@@ -407,16 +407,56 @@ class Engine(Handle):
             )
         self._err(rc, "ttsdec_decode")
 
-    def postnet(self, y: Tensor, precision: int = _lib.POSTNET_F32) -> Tensor:
+    def decode_each(self, memory: Tensor, *, t_begin: int, n_steps: int, stop_threshold: float, dropout_mode: int,
+                    masks: Optional[Tensor], seed: int, y: Tensor, s: Tensor, w: Tensor, stop_steps: Tensor, t_out: Tensor) -> None:
+        """decode under the per-utterance stop rule (ttsdec_decode_each); stop_steps: int32 [B] on the device, the same tensor
+        for every chunk of one decode."""
+        _require_device(memory, "memory")
+        B, L, _ = memory.shape
+        if stop_steps.dtype != torch.int32 or stop_steps.numel() != B or not stop_steps.is_contiguous():
+            raise ValueError("stop_steps must be a contiguous int32 [B] tensor")
+        _require_device(stop_steps, "stop_steps")
+        ws = self.step_workspace(B, L)
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsdec_decode_each(
+                self._h, memory.data_ptr(), B, L, t_begin, n_steps, w.shape[1],
+                float(stop_threshold), dropout_mode, _ptr(masks), seed & 0xFFFFFFFFFFFFFFFF, None, 0, None,
+                y.data_ptr(), s.data_ptr(), w.data_ptr(), stop_steps.data_ptr(), t_out.data_ptr(),
+                ws.data_ptr(), ws.numel(), _stream(self.device),
+            )
+        self._err(rc, "ttsdec_decode_each")
+
+    def zero_tail(self, x: Tensor, lengths: Tensor, len_div: int = 1) -> None:
+        """Zeroes x[b, lengths[b] // len_div :] in place (ttsdec_zero_tail).  x: fp32 [B, T] or [B, T, C] whose entries x[b] are
+        contiguous (a slice along T of a contiguous tensor is fine); lengths: int32 [B] on the device."""
+        _require_device(x, "x")
+        B, T = x.shape[:2]
+        Cc = x.shape[2] if x.dim() == 3 else 1
+        if x.dtype != torch.float32 or x.dim() not in (2, 3) or not x[0].is_contiguous():
+            raise ValueError("zero_tail: x must be fp32 [B, T] or [B, T, C] with contiguous entries")
+        if T == 0:
+            return
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsdec_zero_tail(self._h, x.data_ptr(), lengths.data_ptr(), B, T, x.stride(0) if B > 1 else T * Cc, Cc,
+                                            len_div, _stream(self.device))
+        self._err(rc, "ttsdec_zero_tail")
+
+    def postnet(self, y: Tensor, precision: int = _lib.POSTNET_F32, lengths: Optional[Tensor] = None) -> Tensor:
         _require_device(y, "y")
         B, T, _ = y.shape
         out = torch.empty_like(y)
         ws = self.postnet_workspace(B, T)
         with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_postnet(
-                self._h, y.data_ptr(), B, T, precision, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device)
-            )
-        self._err(rc, "ttsdec_postnet")
+            if lengths is None:
+                rc = self._lib.ttsdec_postnet(
+                    self._h, y.data_ptr(), B, T, precision, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device)
+                )
+            else:  # int32 [B] on the device, frames
+                rc = self._lib.ttsdec_postnet_ragged(
+                    self._h, y.data_ptr(), lengths.data_ptr(), B, T, precision, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                    _stream(self.device)
+                )
+        self._err(rc, "ttsdec_postnet" if lengths is None else "ttsdec_postnet_ragged")
         return out
 
     def cell_step(self, x, memory, w, ctx, h_att, c_att, h_dec, c_dec, dropout_mode, masks, seed, step) -> Tensor:

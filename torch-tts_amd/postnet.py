@@ -12,6 +12,16 @@ from . import _lib
 from .engine import EngineCache, EngineDims, PackedWeightsMixin
 
 
+def frame_lengths(lengths, x):
+    """Per-utterance frame counts as ttsdec_postnet_ragged takes them: int32 [B] on x's device (no host sync), or None."""
+    if lengths is None:
+        return None
+    lengths = torch.as_tensor(lengths)
+    if lengths.dim() != 1 or lengths.numel() != x.shape[0] or lengths.is_floating_point():
+        raise ValueError(f"lengths must be {x.shape[0]} integer frame counts, one per utterance")
+    return lengths.to(device=x.device, dtype=torch.int32).contiguous()
+
+
 class MelPostnet(PackedWeightsMixin, nn.Module):
     def __init__(self, dim_mel, dim_hidden=512, kernel_size=5, num_layers=3):
         super().__init__()
@@ -54,16 +64,20 @@ class MelPostnet(PackedWeightsMixin, nn.Module):
         eng.ensure_packed(self.weight_tensors())
         return eng
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        """lengths: None, or per-utterance frame counts [B] (each in [0, T]) of a ragged batch: row b of the result is then what
+        this module gives for x[b, :lengths[b]] alone, and zero from lengths[b] on - whatever x holds there (eval mode only)."""
         if not x.is_cuda:
             raise RuntimeError("MelPostnet runs on the HIP path only: move the module and input to a ROCm device")
         if self.training or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
             from . import autograd_path  # training semantics (batch-statistics BatchNorm, dropout) or a graph: torch ops on the device
 
             autograd_path.warn_eval_on_autograd_path(self)
+            if lengths is not None:
+                raise NotImplementedError("MelPostnet: lengths are an inference feature of the HIP path (eval mode, no grad)")
             return autograd_path.mel_postnet(self, x)
         prec = {"f32": _lib.POSTNET_F32, "bf16": _lib.POSTNET_BF16, "split_f16": _lib.POSTNET_SPLIT_F16}[self.precision]
-        return self.engine(x.device).postnet(x.detach().to(torch.float32).contiguous(), prec)
+        return self.engine(x.device).postnet(x.detach().to(torch.float32).contiguous(), prec, frame_lengths(lengths, x))
 
 
 class Conv1dFix(nn.Module):
@@ -139,13 +153,17 @@ class MelPostnet2(PackedWeightsMixin, nn.Module):
         eng.ensure_packed(self.weight_tensors())
         return eng
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        """lengths: None, or per-utterance frame counts [B] (each in [0, T]) of a ragged batch: row b of the result is then what
+        this module gives for x[b, :lengths[b]] alone, and zero from lengths[b] on - whatever x holds there (eval mode only)."""
         if not x.is_cuda:
             raise RuntimeError("MelPostnet2 runs on the HIP path only: move the module and input to a ROCm device")
         if self.training or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
             from . import autograd_path
 
             autograd_path.warn_eval_on_autograd_path(self)
+            if lengths is not None:
+                raise NotImplementedError("MelPostnet2: lengths are an inference feature of the HIP path (eval mode, no grad)")
             return autograd_path.mel_postnet2(self, x)
         prec = {"f32": _lib.POSTNET_F32, "bf16": _lib.POSTNET_BF16, "split_f16": _lib.POSTNET_SPLIT_F16}[self.precision]
-        return self.engine(x.device).postnet(x.detach().to(torch.float32).contiguous(), prec)
+        return self.engine(x.device).postnet(x.detach().to(torch.float32).contiguous(), prec, frame_lengths(lengths, x))

@@ -86,6 +86,34 @@ class Tacotron(PackedWeightsMixin, nn.Module):
         y_post = self.postnet(y) if self.postnet else y
         return y, y_post, s, {"w": w, "kl_loss": kl_loss}
 
+    def synthesize(self, cond, cond_lengths, xref=None, xref_lengths=None, max_steps: int = 0):
+        """Batched synthesis: a batch of texts in, a ragged batch of spectrograms out, each utterance ending at its OWN stop
+        token (``Decoder.forward_each``) and post-processed as if alone (the Postnet with lengths).  Inference only.
+        Returns ``(y, y_post, s, {"w", "kl_loss", "lengths", "stopped"})``: y / y_post [B, T, D_mel], s [B, T, 1], w [B, T / r, L],
+        all zero past each utterance's ``lengths[b]`` frames (int64 [B], on the device); ``stopped[b]`` is False for an
+        utterance that reached the step cap without firing.  ``lengths`` is what ``synth_audio_native(y_post, frontend,
+        lengths=lengths)`` takes."""
+        defer = isinstance(self.encoder, Encoder2) and not self.training
+        if defer:  # (as in forward: the id range check rides on the decoder's sync)
+            prev, self.encoder.defer_id_check = self.encoder.defer_id_check, True
+        try:
+            memory = self.encoder(cond, cond_lengths)
+        finally:
+            if defer:
+                self.encoder.defer_id_check = prev
+        kl_loss = torch.scalar_tensor(0)
+        if xref is not None and self.refencoder is not None:
+            style_embed, style_loss_dict = self.refencoder(xref, xref_lengths)
+            memory = memory + style_embed
+            if "kl" in style_loss_dict:
+                kl_loss = style_loss_dict["kl"].mean()
+        mmask = lengths_to_mask(cond_lengths)
+        y, s, w, lengths, stopped = self.decoder.forward_each(memory, mmask, max_steps)
+        if defer:
+            self.encoder.check_ids()
+        y_post = self.postnet(y, lengths=lengths) if self.postnet else y
+        return y, y_post, s.unsqueeze(2), {"w": w, "kl_loss": kl_loss, "lengths": lengths, "stopped": stopped}
+
 
 def build_tacotron(config):
     """config dict -> Tacotron, as tacotron.py:165-224 for the LJSpeech-style configs
