@@ -49,7 +49,8 @@ extern "C" {
  * waveform -> dB spectrogram and mel for it; then ttsvits_generator_planes_bytes, _pack_planes, _workspace_bytes and _forward,
  * the generator with its arithmetic as a call argument; then ttsdec_resample_workspace_bytes and ttsdec_resample, sample-rate
  * conversion in front of ttsdec_mel_analysis; then ttsvits_disc_*, the waveform discriminators, a second handle kind under
- * ttsvits_ with a struct of its own; then ttsvits_durdisc_*, the duration discriminators, a third one.) */
+ * ttsvits_ with a struct of its own; then ttsvits_durdisc_*, the duration discriminators, a third one; then ttsvits_durnll_*, the
+ * stochastic duration predictor's likelihood, a fourth.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -953,6 +954,59 @@ int ttsvits_durdisc_trunk(ttsvits_durdisc_handle* h, const float* x, const int32
  * per duration) and, unless logit_out is NULL, the pre-sigmoid logits in the same shape. */
 int ttsvits_durdisc_prob(ttsvits_durdisc_handle* h, const float* hidden, const int32_t* lengths, const float* dur, int n_dur, int B, int T,
                          float* prob_out, float* logit_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * VITS2 duration likelihood: StochasticDurationPredictor.forward(x, x_mask, w, g=g), vits2/models.py:78-125 - the `l_length` of
+ * SynthesizerTrn.forward (:1258-1259) before its division, the VL/dur of the reference's validation.  Eval mode, exact fp32,
+ * inference only.  A fourth handle kind of the ttsvits_ family; it has no set_precision.  C = in_channels; activations are
+ * CHANNEL-LAST, x [B, T, C] as ttsvits_text_encoder writes it; m is the token mask t < lengths[b], applied as a select.
+ *   x' = proj(convs(pre(x) [+ cond(g)])) m;  g_q = x' + post_proj(post_convs(post_pre(w))) m
+ *   z_q = e_q m -> post_flows: ElementwiseAffine, 4 x (ConvFlow conditioned on g_q, Flip);  (z_u, z1) = z_q
+ *   u = sigmoid(z_u) m, z0 = (w - u) m;  logdet_tot_q = the posterior flows' log-dets + sum (logsigmoid(z_u) + logsigmoid(-z_u)) m
+ *   z = flows(cat([Log(z0), z1])): ElementwiseAffine, n_flows x (ConvFlow conditioned on x', Flip);  logdet_tot = Log's and theirs
+ *   nll = sum 0.5 (log 2pi + z^2) m - logdet_tot  +  sum -0.5 (log 2pi + e_q^2) m - logdet_tot_q
+ * The kernels are those of ttsdur_sdp_reverse (one launch per DDSConv layer over tiles of 16 tokens) with the spline's forward
+ * branch (transforms.py:100-209, searchsorted on cumwidths, linear tails) and the elementwise steps in their epilogues.  Every
+ * token row keeps its own log-det sums; one last launch sums an utterance's tokens in a fixed order and adds the Gaussian terms:
+ * no atomics, an utterance in a padded batch gets bit for bit what it gets alone at T = its own length, and the same call twice
+ * gives the same bits.
+ * ------------------------------------------------------------------------------------- */
+typedef struct ttsvits_durnll_dims {
+  int32_t in_channels;  /* hidden_channels (192): width of x and of the predictor (models.py:40); a multiple of 4, <= 256 */
+  int32_t kernel_size;  /* 3 (the only size built)                                                                       */
+  int32_t n_flows;      /* 4 (2..8)                                                                                      */
+  int32_t gin_channels; /* 0, or the width of the speaker vector g (cond, 1x1)                                           */
+} ttsvits_durnll_dims;
+typedef struct ttsvits_durnll_handle ttsvits_durnll_handle;
+
+/* TTSDEC_ERR_DIMS for what ttsdur_create refuses of a kind-0 predictor: kernel_size != 3, in_channels not a multiple of 4 or
+ * above 256, n_flows < 2 or > 8, gin_channels < 0. */
+int ttsvits_durnll_create(const ttsvits_durnll_dims* dims, ttsvits_durnll_handle** out);
+int ttsvits_durnll_destroy(ttsvits_durnll_handle* h);
+const char* ttsvits_durnll_last_hip_error(const ttsvits_durnll_handle* h);
+/* Source tensors for ttsvits_durnll_pack_weights (device fp32, the reference's parameter shapes), in this order - a blob of its
+ * own, every parameter of the module (a trunk is the 28 tensors pre.weight, pre.bias, the DDSConv's 24, proj.weight, proj.bias as
+ * ttsdur_pack_weights lists them; a ConvFlow the same 28 with pre [C, 1, 1] and proj [29, C, 1]):
+ *   pre, convs, proj (28);  flows.0.m, flows.0.logs [2, 1];  flows.{2k+1} for k = 0 .. n_flows-1 (28 each; flows.1 included);
+ *   post_pre [C, 1, 1], post_convs, post_proj (28);  post_flows.0.m, post_flows.0.logs;  post_flows.{1, 3, 5, 7} (28 each);
+ *   when gin_channels > 0: cond.weight [C, gin, 1], cond.bias [C].
+ * 172 + 28 n_flows tensors (284 at n_flows = 4), 2 more with g.  None may be NULL. */
+int ttsvits_durnll_num_weight_tensors(const ttsvits_durnll_handle* h);
+size_t ttsvits_durnll_packed_bytes(const ttsvits_durnll_handle* h);
+int ttsvits_durnll_pack_weights(ttsvits_durnll_handle* h, const float* const* src, int n_src, void* blob, void* stream);
+int ttsvits_durnll_bind_weights(ttsvits_durnll_handle* h, const void* blob);
+/* Scratch of one ttsvits_durnll_forward call of B utterances of T tokens; 0 for a NULL handle or a size <= 0. */
+size_t ttsvits_durnll_workspace_bytes(const ttsvits_durnll_handle* h, int B, int T);
+/* x [B, T, C], lengths [B] int32 (device), g NULL or [B, gin], w [B, T] the durations (the reference's [B, 1, T]), noise [B, 2, T]
+ * the reference's draw torch.randn(B, 2, T) (e_q before its mask) -> nll_out [B]; unless NULL, terms_out [B, 4] = { sum -0.5
+ * (log 2pi + e_q^2) m, logdet_tot_q, sum 0.5 (log 2pi + z^2) m, logdet_tot } with nll = (terms[2] - terms[3]) + (terms[0] -
+ * terms[1]), and z_out [B, 2, T] = z after the last flow (zero at masked tokens).  TTSDEC_ERR_INVALID_ARG for a NULL x, lengths, w,
+ * noise or nll_out, B or T <= 0, or g with gin_channels = 0; TTSDEC_ERR_NOT_BOUND before bind_weights; TTSDEC_ERR_DIMS for
+ * B * T > 2^30; TTSDEC_ERR_WORKSPACE for a workspace that is not 256-byte aligned or smaller than
+ * ttsvits_durnll_workspace_bytes.  Enqueue only - no synchronisation, no host reads. */
+int ttsvits_durnll_forward(ttsvits_durnll_handle* h, const float* x, const int32_t* lengths, const float* g, const float* w, const float* noise,
+                           int B, int T, float* nll_out, float* terms_out, float* z_out, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * VITS2 duration predictors and length regulation: the `self.dp(...)` and the prior expansion of SynthesizerTrn.infer,

@@ -103,6 +103,10 @@ class DurDiscDims(C.Structure):  # include/ttsdec.h ttsvits_durdisc_dims
     _fields_ = [(n, C.c_int32) for n in ("version", "in_channels", "filter_channels", "kernel_size")]
 
 
+class DurNllDims(C.Structure):  # include/ttsdec.h ttsvits_durnll_dims
+    _fields_ = [(n, C.c_int32) for n in ("in_channels", "kernel_size", "n_flows", "gin_channels")]
+
+
 DUR_SDP, DUR_DP = 0, 1  # include/ttsdec.h ttsdur_dims.kind
 PATH_F32, PATH_F16, PATH_BF16 = 0, 1, 2  # include/ttsdec.h TTSVITS_PATH_*
 ALIGN_MAX_TX = 1024  # tokens per utterance ttsvits_maximum_path is built for
@@ -240,6 +244,11 @@ FAMILIES = (
         "durdisc_workspace_bytes": (sz, [vp, i32, i32, i32]),  # (h, B, T, n_dur)
         "durdisc_trunk": (i32, [vp, vp, vp, i32, i32, vp, vp, sz, vp]),  # h, x, lengths, B, T, hidden_out, ws, bytes, stream
         "durdisc_prob": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),  # h, hidden, lengths, dur, n_dur, B, T, prob, logit, ws, bytes, stream
+        # the stochastic duration predictor's likelihood: a fourth handle of this family (vits2.DurNllEngine, PREFIX = "ttsvits_durnll")
+        "durnll_create": (i32, [C.POINTER(DurNllDims), C.POINTER(vp)]),
+        **{f"durnll_{n}": sig for n, sig in _SHARED_SIGS.items()},
+        "durnll_workspace_bytes": _ws_bytes,
+        "durnll_forward": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]),  # h, x, lengths, g, w, noise, B, T, nll, terms, z, ws, bytes, stream
     }),
     Family("ttsgen", GenDims, False, {
         "workspace_bytes": _ws_bytes,

@@ -12,6 +12,11 @@
 //   lengths_kernel   w = exp(logw) * mask * length_scale, ceil, running sums, y_len, one workgroup
 //   expand_kernel    the frame-rate prior (m_p, logs_p, z_p channel-last; attn) from the running sums, no dense matmul
 // SDP reverse at n_flows = 4: 1 (cond(g)) + 1 (pre) + 3 (DDSConv) + 3 x 3 (ConvFlows) = 14 launches (13 without g).
+// The SDP's forward direction, the duration likelihood (include/ttsdec.h ttsvits_durnll_*, models.py:87-125), runs on the same
+// kernels: dds_layer_kernel<true> adds post_pre in the load, `+ x` on the posterior conditioning's proj, the spline's forward
+// branch with its log-determinant, and the elementwise steps between the flows (ElementwiseAffine, the sigmoid split, Log) in
+// the epilogues; nll_reduce_kernel sums each utterance's tokens.  dds_layer_kernel<false> is the reverse path's kernel as it was.
+// At n_flows = 4: 1 (cond(g)) + 1 (pre) + 3 + 3 (post_convs) + 4 x 3 (post_flows) + 4 x 3 (flows) + 1 (sums) = 33 launches.
 // Every weight has one record (KConv: a K-major conv weight with its bias; Vec, layout.h: a tensor copied as given), made by one
 // walk at ttsdur_create; ttsdur_pack_weights and the forward calls read offsets, shapes and source indices from the records.
 #include <math.h>
@@ -61,6 +66,25 @@ struct DurBlob {
   size_t total;
   int n_src;                 // source tensors of ttsdur_pack_weights
 };
+struct NllBlob {             // ttsvits_durnll_*: every parameter of the SDP, in the order include/ttsdec.h documents
+  KConv pre;
+  DdsW convs;
+  KConv proj;
+  Vec ea_m, ea_logs;         // flows.0
+  Pair f_pre[8];             // flows.{2k+1}, k = 0 .. n_flows-1 (flows.1 included)
+  DdsW f_convs[8];
+  KConv f_proj[8];
+  Pair post_pre;             // [C, 1, 1], [C]
+  DdsW post_convs;
+  KConv post_proj;
+  Vec pea_m, pea_logs;       // post_flows.0
+  Pair pf_pre[4];            // post_flows.{1, 3, 5, 7}
+  DdsW pf_convs[4];
+  KConv pf_proj[4];
+  Pair cond;
+  size_t total;
+  int n_src;
+};
 // the one walk over the blob: offsets in blob order, source indices in the order include/ttsdec.h documents (src ends as their count)
 struct Walk : BlobWalk {
   Pair pair(size_t nw, size_t nb) { return {vec(nw), vec(nb)}; }
@@ -85,6 +109,10 @@ struct Walk : BlobWalk {
 struct ttsdur_handle : HandleBase {
   ttsdur_dims d;
   DurBlob bl;
+};
+struct ttsvits_durnll_handle : HandleBase {
+  ttsvits_durnll_dims d;
+  NllBlob bl;
 };
 
 namespace {
@@ -129,6 +157,38 @@ DurBlob make_layout(const ttsdur_dims& d) {
   return L;
 }
 
+bool nll_dims_ok(const ttsvits_durnll_dims& d) {  // what kind 0 above accepts
+  return dims_ok(ttsdur_dims{0, d.in_channels, d.in_channels, d.kernel_size, d.n_flows, d.gin_channels});
+}
+
+NllBlob make_nll_layout(const ttsvits_durnll_dims& d) {
+  NllBlob L;
+  memset(&L, 0, sizeof(L));
+  Walk w;
+  const int C = d.in_channels;
+  auto flow = [&](Pair& pre, DdsW& convs, KConv& proj) {
+    pre = w.pair(C, C);
+    w.dds(convs, C);
+    proj = w.conv(kProj, C, 1);
+  };
+  L.pre = w.conv(C, C, 1);
+  w.dds(L.convs, C);
+  L.proj = w.conv(C, C, 1);
+  L.ea_m = w.vec(2);
+  L.ea_logs = w.vec(2);
+  for (int k = 0; k < d.n_flows; ++k) flow(L.f_pre[k], L.f_convs[k], L.f_proj[k]);
+  L.post_pre = w.pair(C, C);
+  w.dds(L.post_convs, C);
+  L.post_proj = w.conv(C, C, 1);
+  L.pea_m = w.vec(2);
+  L.pea_logs = w.vec(2);
+  for (int k = 0; k < 4; ++k) flow(L.pf_pre[k], L.pf_convs[k], L.pf_proj[k]);
+  if (d.gin_channels > 0) L.cond = w.pair((size_t)C * d.gin_channels, C);
+  L.total = w.cv.off;
+  L.n_src = w.src;
+  return L;
+}
+
 // The workspaces of the two predictors (carved as layout.h's Carver comment says)
 struct SdpWs { float *XP, *XA, *XB, *XC, *Z, *condv; };  // four [M, C] activations; [B, 2, T] the flows' state; [B, C] cond(g)
 SdpWs carve_sdp(Carver& cv, const ttsdur_dims& d, size_t B, size_t T) {
@@ -142,6 +202,16 @@ struct DpWs { float *H1, *condv; };  // [M, F] conv_1's output; [B, C] cond(g)
 DpWs carve_dp(Carver& cv, const ttsdur_dims& d, size_t B, size_t T) {
   DpWs w;
   w.H1 = cv.take(B * T * d.filter_channels); w.condv = cv.take(B * d.in_channels);
+  return w;
+}
+// the likelihood's: the SDP's buffers (XP holds pre's output, then g_q = x + h_w) and the per-token log-det sums of the posterior
+// and the main flows [B, T]
+struct NllWs { float *XP, *XA, *XB, *XC, *Z, *LDQ, *LD, *condv; };
+NllWs carve_nll(Carver& cv, const ttsvits_durnll_dims& d, size_t B, size_t T) {
+  const size_t MC = B * T * d.in_channels;
+  NllWs w;
+  w.XP = cv.take(MC); w.XA = cv.take(MC); w.XB = cv.take(MC); w.XC = cv.take(MC);
+  w.Z = cv.take(2 * B * T); w.LDQ = cv.take(B * T); w.LD = cv.take(B * T); w.condv = cv.take(B * d.in_channels);
   return w;
 }
 size_t carved_bytes(const ttsdur_dims& d, int B, int T) {
@@ -261,6 +331,56 @@ __device__ float spline_inverse(float x, const float* h, float sqrt_c) {
   return root * ibw + icw;
 }
 
+// The forward branch of the same spline (transforms.py:100-209 with inverse=False) and its log |dy/dx|: the knots as above
+// (spline_inverse keeps its own copy of them: what it computes is pinned bit for bit), searchsorted on cumwidths.
+__device__ float spline_forward(float x, const float* h, float sqrt_c, float* logabsdet) {
+  *logabsdet = 0.f;
+  if (!(x >= -kTail && x <= kTail)) return x;  // linear tails: identity, log-det 0
+  const float kMin = 1e-3f;
+  float cw[kBins + 1], ch[kBins + 1], der[kBins + 1];
+  auto cum = [&](int base, float* cu) {
+    float mx = -INFINITY, e[kBins], s = 0.f;
+    for (int i = 0; i < kBins; ++i) mx = fmaxf(mx, h[base + i] / sqrt_c);
+    for (int i = 0; i < kBins; ++i) {
+      e[i] = expf(h[base + i] / sqrt_c - mx);
+      s += e[i];
+    }
+    float c = 0.f;
+    cu[0] = -kTail;
+    for (int i = 0; i < kBins; ++i) {
+      const float wv = kMin + (1.f - kMin * kBins) * (e[i] / s);
+      c += wv;
+      cu[i + 1] = (2.f * kTail) * c + (-kTail);
+    }
+    cu[kBins] = kTail;
+  };
+  cum(0, cw);
+  cum(kBins, ch);
+  const float edge = (float)0.5397424172369522;  // the same padding constant as the inverse (transforms.py:69-72)
+  der[0] = kMin + softplus(edge);
+  der[kBins] = der[0];
+  for (int i = 1; i < kBins; ++i) der[i] = kMin + softplus(h[2 * kBins + i - 1]);
+  int idx = -1;  // searchsorted(cumwidths, x) with the eps on the last edge (transforms.py:45-47, 147)
+  for (int i = 0; i <= kBins; ++i) {
+    const float e = i == kBins ? cw[kBins] + 1e-6f : cw[i];
+    idx += x >= e ? 1 : 0;
+  }
+  idx = idx < 0 ? 0 : (idx > kBins - 1 ? kBins - 1 : idx);
+  const float icw = cw[idx], ibw = cw[idx + 1] - cw[idx];
+  const float ich = ch[idx], ih = ch[idx + 1] - ch[idx];
+  const float delta = ih / ibw;
+  const float d0 = der[idx], d1 = der[idx + 1];
+  const float theta = (x - icw) / ibw;
+  const float tomt = theta * (1.f - theta);
+  const float num = ih * (delta * (theta * theta) + d0 * tomt);
+  const float den = delta + (d0 + d1 - 2.f * delta) * tomt;
+  const float dnum = (delta * delta) * (d1 * (theta * theta) + 2.f * delta * tomt + d0 * ((1.f - theta) * (1.f - theta)));
+  *logabsdet = logf(dnum) - 2.f * logf(den);
+  return ich + num / den;
+}
+// F.logsigmoid
+__device__ inline float logsigmoid(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
+
 // ===========================================================================
 // kernels
 // ===========================================================================
@@ -347,7 +467,7 @@ __global__ __launch_bounds__(kThreads) void pw_conv_kernel(PwArgs a) {
   }
 }
 
-enum { TAIL_NONE = 0, TAIL_PROJ = 1, TAIL_FLOW = 2 };
+enum { TAIL_NONE = 0, TAIL_PROJ = 1, TAIL_FLOW = 2, TAIL_FWD = 3 };
 
 struct DdsArgs {
   const float* xin;        // [M, C] the layer's input x (layer > 0, or the conditioning path's first layer)
@@ -366,15 +486,28 @@ struct DdsArgs {
   float sqrt_c;
   const int* lengths;
   int C, T, M;
+  // dds_layer_kernel<true> only (the likelihood, ttsvits_durnll_forward):
+  const float* w;          // [M] durations.  head with w set and zin null (post_convs): x[m, c] = pre_w[c] * w[m] + pre_b[c]
+  const float* tadd;       // TAIL_PROJ: xout = (proj(x) + b + tadd[m, :]) * mask  (g_q = x + h_w)
+  const float* eq;         // TAIL_PROJ: also zout = ElementwiseAffine(eq * mask) (ea_m, ea_logs) and ldinit = its log-det
+  // TAIL_FWD: [C][29] tw -> the spline's forward branch on x1, cat([x0, y1]) * mask -> zout, ldacc[m] += its log |det|.
+  // split (the last posterior flow): then u = sigmoid(z_u) * mask, z0 = (w - u) * mask, ldacc += logsigmoid(z_u) +
+  // logsigmoid(-z_u); y = Log(z0), zout = ElementwiseAffine(cat([y, z1])) (ea_m, ea_logs: the main flows'), ldinit = their log-dets
+  float *ldacc, *ldinit;   // [M] per-token log-det sums, each written by the lane that owns the row
+  int split;
 };
 
+template <bool kNll>
 __device__ inline float dds_input(const DdsArgs& a, int b, int t, int c) {
   const size_t m = (size_t)b * a.T + t;
   if (a.xin) return a.xin[m * a.C + c];
+  if constexpr (kNll)
+    if (!a.zin) return a.pre_w[c] * a.w[m] + a.pre_b[c];
   const float x0 = a.zin[((size_t)b * 2 + a.c0) * a.T + t] * a.zscale;
   return (a.pre_w[c] * x0 + a.pre_b[c]) + a.gadd[m * a.C + c];
 }
 
+template <bool kNll>
 __global__ __launch_bounds__(kThreads) void dds_layer_kernel(DdsArgs a) {
   extern __shared__ float lds[];
   const int C = a.C;
@@ -389,11 +522,11 @@ __global__ __launch_bounds__(kThreads) void dds_layer_kernel(DdsArgs a) {
     float xv = 0.f, y = 0.f;
     if (m < a.M) {
       const int b = m / a.T, t = m % a.T, len = min(a.lengths[b], a.T);
-      xv = dds_input(a, b, t, c);
+      xv = dds_input<kNll>(a, b, t, c);
       float acc = 0.f;
       for (int tap = 0; tap < 3; ++tap) {
         const int tt = t + (tap - 1) * a.dil;
-        const float v = tt == t ? (t < len ? xv : 0.f) : (tt >= 0 && tt < len ? dds_input(a, b, tt, c) : 0.f);
+        const float v = tt == t ? (t < len ? xv : 0.f) : (tt >= 0 && tt < len ? dds_input<kNll>(a, b, tt, c) : 0.f);
         acc = fmaf(a.dw_w[tap * C + c], v, acc);
       }
       y = acc + a.dw_b[c];
@@ -433,8 +566,22 @@ __global__ __launch_bounds__(kThreads) void dds_layer_kernel(DdsArgs a) {
     __syncthreads();
     for (int idx = threadIdx.x; idx < kRows * C; idx += kThreads) {
       const int m = m0 + idx / C;
-      if (m < a.M) a.xout[(size_t)m * C + idx % C] = (m % a.T) < a.lengths[m / a.T] ? Y[idx] : 0.f;
+      if constexpr (kNll) {
+        if (m < a.M) a.xout[(size_t)m * C + idx % C] = (m % a.T) < a.lengths[m / a.T] ? Y[idx] + (a.tadd ? a.tadd[(size_t)m * C + idx % C] : 0.f) : 0.f;
+      } else {
+        if (m < a.M) a.xout[(size_t)m * C + idx % C] = (m % a.T) < a.lengths[m / a.T] ? Y[idx] : 0.f;
+      }
     }
+    if constexpr (kNll)
+      if (a.eq && threadIdx.x < kRows && m0 + (int)threadIdx.x < a.M) {  // models.py:95-102: z_q = e_q * mask, then post_flows.0
+        const int m = m0 + threadIdx.x, b = m / a.T, t = m % a.T;
+        const bool on = t < a.lengths[b];
+        for (int ch = 0; ch < 2; ++ch) {
+          const size_t i = ((size_t)b * 2 + ch) * a.T + t;
+          a.zout[i] = on ? a.ea_m[ch] + expf(a.ea_logs[ch]) * a.eq[i] : 0.f;
+        }
+        a.ldinit[m] = on ? a.ea_logs[0] + a.ea_logs[1] : 0.f;
+      }
     return;
   }
   // TAIL_FLOW: h = proj(x) * mask [kRows][29]; x1 -> spline^-1; cat([x0, x1]) * mask
@@ -448,6 +595,26 @@ __global__ __launch_bounds__(kThreads) void dds_layer_kernel(DdsArgs a) {
       float h[kProj];
       for (int j = 0; j < kProj; ++j) h[j] = on ? Y[r * kProj + j] : 0.f;
       const size_t i0 = ((size_t)b * 2 + a.c0) * a.T + t, i1 = ((size_t)b * 2 + (1 - a.c0)) * a.T + t;
+      if constexpr (kNll) {  // TAIL_FWD (the only flow tail of the likelihood)
+        float lad = 0.f;
+        const float x0 = on ? a.zin[i0] : 0.f;
+        const float y1 = on ? spline_forward(a.zin[i1], h, a.sqrt_c, &lad) : 0.f;
+        float acc = on ? a.ldacc[m] + lad : 0.f;
+        if (!a.split) {
+          a.zout[i0] = x0;
+          a.zout[i1] = y1;
+        } else {  // models.py:103-117; the Flip after this flow is the posterior's fourth: channel 0 is z_u, channel 1 is z1
+          const float zu = a.c0 == 0 ? x0 : y1, z1 = a.c0 == 0 ? y1 : x0;
+          const float u = 1.f / (1.f + expf(-zu));
+          const float y = logf(fmaxf(a.w[m] - u, 1e-5f));
+          acc += logsigmoid(zu) + logsigmoid(-zu);
+          a.zout[((size_t)b * 2 + 0) * a.T + t] = on ? a.ea_m[0] + expf(a.ea_logs[0]) * y : 0.f;
+          a.zout[((size_t)b * 2 + 1) * a.T + t] = on ? a.ea_m[1] + expf(a.ea_logs[1]) * z1 : 0.f;
+          a.ldinit[m] = on ? -y + (a.ea_logs[0] + a.ea_logs[1]) : 0.f;
+        }
+        a.ldacc[m] = on ? acc : 0.f;
+        return;
+      }
       const float x0 = a.zin[i0] * a.zscale, x1 = a.zin[i1] * a.zscale;
       const float y1 = on ? spline_inverse(x1, h, a.sqrt_c) : 0.f;
       if (a.logw) {  // Flip, then ElementwiseAffine reverse on channel 0 (= this flow's x1)
@@ -547,7 +714,39 @@ __global__ __launch_bounds__(256) void expand_kernel(const int* cum, const float
     }
 }
 
+// models.py:109-112, 121-125 for one utterance per wave: lane l sums tokens l, l + 64, ... below the length, then the lanes are
+// summed by a fixed butterfly - the same bits whatever the batch around the utterance.  terms: { sum -0.5 (log 2pi + e_q^2),
+// logdet_tot_q, sum 0.5 (log 2pi + z^2), logdet_tot }; nll = (terms[2] - terms[3]) + (terms[0] - terms[1]).
+// z [B, 2, T] physical channels: flip = 1 when an odd number of Flips makes logical channel ch the physical 1 - ch.
+__global__ __launch_bounds__(64) void nll_reduce_kernel(const float* eq, const float* z, const float* ldq, const float* ld, const int* lengths,
+                                                         int T, int flip, float* nll, float* terms, float* z_out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int len = min(lengths[b], T);
+  const float kLog2Pi = 1.8378770664093453f;
+  const float *e0 = eq + (size_t)b * 2 * T, *e1 = e0 + T, *z0 = z + (size_t)b * 2 * T, *z1 = z0 + T;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int t = lane; t < len; t += 64) {
+    s[0] += -0.5f * (kLog2Pi + e0[t] * e0[t]) + -0.5f * (kLog2Pi + e1[t] * e1[t]);
+    s[1] += ldq[(size_t)b * T + t];
+    s[2] += 0.5f * (kLog2Pi + z0[t] * z0[t]) + 0.5f * (kLog2Pi + z1[t] * z1[t]);
+    s[3] += ld[(size_t)b * T + t];
+  }
+  for (int i = 0; i < 4; ++i) s[i] = wave_sum(s[i]);
+  if (lane == 0) {
+    nll[b] = (s[2] - s[3]) + (s[0] - s[1]);
+    if (terms)
+      for (int i = 0; i < 4; ++i) terms[(size_t)b * 4 + i] = s[i];
+  }
+  if (z_out)
+    for (int t = lane; t < T; t += 64) {
+      z_out[((size_t)b * 2 + flip) * T + t] = z0[t];
+      z_out[((size_t)b * 2 + (1 - flip)) * T + t] = z1[t];
+    }
+}
+
 size_t dds_lds(int C) { return (size_t)3 * kRows * C * sizeof(float); }
+// the likelihood's launches: dds_lds, and room for the 29 projected columns behind Y where C < 16 leaves less than that
+size_t nll_lds(int C) { return max(dds_lds(C), (size_t)kRows * (C + kProj) * sizeof(float)); }
 size_t pw_lds(int Cin, int taps, int N) { return (size_t)kRows * (taps * Cin + N) * sizeof(float); }
 
 // ttsdur_pack_weights' steps, one per record: from src into the blob b
@@ -569,8 +768,8 @@ void pack_dds(const float* const* src, float* b, const DdsW& w, hipStream_t st) 
   }
 }
 
-void run_dds(const ttsdur_handle* h, const DdsW& w, DdsArgs a, const float* x_first, float* bufA, float* bufB, int tail, hipStream_t st) {
-  const float* b = h->blob;
+template <bool kNll = false>
+void run_dds(const float* b, const DdsW& w, DdsArgs a, const float* x_first, float* bufA, float* bufB, int tail, hipStream_t st) {
   const unsigned nblk = (unsigned)((a.M + kRows - 1) / kRows);
   const float* in = x_first;
   for (int i = 0; i < 3; ++i) {
@@ -583,7 +782,7 @@ void run_dds(const ttsdur_handle* h, const DdsW& w, DdsArgs a, const float* x_fi
     l.tail = i == 2 ? tail : TAIL_NONE;
     float* out = (i % 2 == 0) ? bufA : bufB;
     if (i < 2) l.xout = out;
-    hipLaunchKernelGGL(dds_layer_kernel, dim3(nblk), dim3(kThreads), dds_lds(a.C), st, l);
+    hipLaunchKernelGGL(dds_layer_kernel<kNll>, dim3(nblk), dim3(kThreads), kNll ? nll_lds(a.C) : dds_lds(a.C), st, l);
     in = out;
   }
 }
@@ -688,7 +887,7 @@ int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths,
   {  // :85-86: x = proj(convs(x, x_mask)) * x_mask -> XC
     DdsArgs c = a;
     c.tw = b + L.proj.w; c.tb = b + L.proj.b; c.xout = XC;
-    run_dds(h, L.convs, c, XP, XA, XB, TAIL_PROJ, st);
+    run_dds(b, L.convs, c, XP, XA, XB, TAIL_PROJ, st);
     // (run_dds hands layer 2 xout = XC through c.xout: the tail writes it)
   }
   // :127-133: [Flip, ConvFlow_{n-1}, Flip, ..., ConvFlow_1, Flip, ElementwiseAffine]; z = noise * noise_scale
@@ -706,7 +905,7 @@ int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths,
       c.ea_m = b + L.ea_m.off;
       c.ea_logs = b + L.ea_logs.off;
     }
-    run_dds(h, L.f_convs[f], c, nullptr, XA, XB, TAIL_FLOW, st);
+    run_dds(b, L.f_convs[f], c, nullptr, XA, XB, TAIL_FLOW, st);
     c0 ^= 1;  // the Flip after it
   }
   return record_hip_error(h, "sdp_reverse");
@@ -759,6 +958,127 @@ int ttsdur_expand(ttsdur_handle* h, const int32_t* cum, const float* m, const fl
   hipLaunchKernelGGL(expand_kernel, dim3((unsigned)((T_y + kExpFrames - 1) / kExpFrames), (unsigned)B), dim3(256), lds,
                      static_cast<hipStream_t>(stream), cum, m, logs, eps, eps_T, noise_scale, T, inter, T_y, z_p, m_p, logs_p, attn);
   return record_hip_error(h, "expand");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// ttsvits_durnll_*: StochasticDurationPredictor.forward(x, x_mask, w, g) (models.py:78-125), the duration likelihood
+// ---------------------------------------------------------------------------------------------------------------------------
+int ttsvits_durnll_create(const ttsvits_durnll_dims* dims, ttsvits_durnll_handle** out) {
+  if (!dims || !out) return TTSDEC_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (!nll_dims_ok(*dims)) return TTSDEC_ERR_DIMS;
+  ttsvits_durnll_handle* h = new (std::nothrow) ttsvits_durnll_handle();
+  if (!h) return TTSDEC_ERR_INVALID_ARG;
+  h->d = *dims;
+  h->bl = make_nll_layout(*dims);
+  h->device = current_device_or_minus1();
+  *out = h;
+  return TTSDEC_OK;
+}
+int ttsvits_durnll_destroy(ttsvits_durnll_handle* h) {
+  delete h;
+  return TTSDEC_OK;
+}
+const char* ttsvits_durnll_last_hip_error(const ttsvits_durnll_handle* h) { return last_hip_error(h); }
+int ttsvits_durnll_num_weight_tensors(const ttsvits_durnll_handle* h) { return h ? h->bl.n_src : TTSDEC_ERR_INVALID_ARG; }
+size_t ttsvits_durnll_packed_bytes(const ttsvits_durnll_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
+
+int ttsvits_durnll_pack_weights(ttsvits_durnll_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = pack_begin(h, src, n_src, ttsvits_durnll_num_weight_tensors(h), false, blob, ttsvits_durnll_packed_bytes(h), st);
+  if (rc != TTSDEC_OK) return rc;
+  const NllBlob& L = h->bl;
+  float* b = static_cast<float*>(blob);
+  auto flow = [&](const Pair& pre, const DdsW& convs, const KConv& proj) {
+    pack_pair(src, b, pre, st);
+    pack_dds(src, b, convs, st);
+    pack_conv(src, b, proj, st);
+  };
+  pack_conv(src, b, L.pre, st);
+  pack_dds(src, b, L.convs, st);
+  pack_conv(src, b, L.proj, st);
+  pack_vec(src, b, L.ea_m, st);
+  pack_vec(src, b, L.ea_logs, st);
+  for (int f = 0; f < h->d.n_flows; ++f) flow(L.f_pre[f], L.f_convs[f], L.f_proj[f]);
+  pack_pair(src, b, L.post_pre, st);
+  pack_dds(src, b, L.post_convs, st);
+  pack_conv(src, b, L.post_proj, st);
+  pack_vec(src, b, L.pea_m, st);
+  pack_vec(src, b, L.pea_logs, st);
+  for (int f = 0; f < 4; ++f) flow(L.pf_pre[f], L.pf_convs[f], L.pf_proj[f]);
+  if (h->d.gin_channels > 0) pack_pair(src, b, L.cond, st);
+  return pack_end(h, b);
+}
+
+int ttsvits_durnll_bind_weights(ttsvits_durnll_handle* h, const void* blob) { return bind_blob(h, blob); }
+
+size_t ttsvits_durnll_workspace_bytes(const ttsvits_durnll_handle* h, int B, int T) {
+  if (!h || B <= 0 || T <= 0) return 0;
+  Carver cv{nullptr};
+  carve_nll(cv, h->d, B, T);
+  return cv.bytes();
+}
+
+int ttsvits_durnll_forward(ttsvits_durnll_handle* h, const float* x, const int32_t* lengths, const float* g, const float* w, const float* noise,
+                           int B, int T, float* nll_out, float* terms_out, float* z_out, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  if (!h || !x || !lengths || !w || !noise || !nll_out || !workspace || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
+  if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
+  if ((size_t)B * T > (size_t)1 << 30) return TTSDEC_ERR_DIMS;
+  if (workspace_bytes < ttsvits_durnll_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ttsvits_durnll_dims& d = h->d;
+  const NllBlob& L = h->bl;
+  const float* b = h->blob;
+  const int C = d.in_channels, M = B * T;
+  Carver cv{static_cast<float*>(workspace)};
+  const NllWs ws = carve_nll(cv, d, B, T);
+  const unsigned nblk = (unsigned)((M + kRows - 1) / kRows);
+  if (g) launch_cond(g, b + L.cond.w.off, b + L.cond.b.off, ws.condv, B, C, d.gin_channels, st);
+  {  // models.py:79-83: x = pre(x) (+ cond(g))
+    PwArgs p;
+    memset(&p, 0, sizeof(p));
+    p.x = x; p.Cin = C; p.taps = 1; p.W = b + L.pre.w; p.bias = b + L.pre.b; p.N = C; p.out_rowvec = g ? ws.condv : nullptr;
+    p.out = ws.XP; p.lengths = lengths; p.T = T; p.M = M;
+    hipLaunchKernelGGL(pw_conv_kernel, dim3(nblk), dim3(kThreads), pw_lds(C, 1, C), st, p);
+  }
+  DdsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.lengths = lengths; a.C = C; a.T = T; a.M = M; a.zscale = 1.f; a.sqrt_c = sqrtf((float)C); a.w = w;
+  {  // :84-85: x = proj(convs(x, x_mask)) * x_mask -> XC
+    DdsArgs c = a;
+    c.tw = b + L.proj.w; c.tb = b + L.proj.b; c.xout = ws.XC;
+    run_dds<true>(b, L.convs, c, ws.XP, ws.XA, ws.XB, TAIL_PROJ, st);
+  }
+  {  // :92-96: g_q = x + post_proj(post_convs(post_pre(w))) * x_mask -> XP; z_q = post_flows.0(e_q * x_mask) -> Z, LDQ
+    DdsArgs c = a;
+    c.pre_w = b + L.post_pre.w.off; c.pre_b = b + L.post_pre.b.off;
+    c.tw = b + L.post_proj.w; c.tb = b + L.post_proj.b; c.tadd = ws.XC; c.xout = ws.XP;
+    c.eq = noise; c.ea_m = b + L.pea_m.off; c.ea_logs = b + L.pea_logs.off; c.zout = ws.Z; c.ldinit = ws.LDQ;
+    run_dds<true>(b, L.post_convs, c, nullptr, ws.XA, ws.XB, TAIL_PROJ, st);
+  }
+  // a ConvFlow forward and the Flip after it (modules.py:486-514): x0 is the physical channel c0 of Z
+  int c0 = 0;
+  auto flow = [&](const Pair& pre, const DdsW& convs, const KConv& proj, const float* cond, float* ldacc, bool split) {
+    DdsArgs c = a;
+    c.zin = ws.Z; c.zout = ws.Z; c.c0 = c0;
+    c.pre_w = b + pre.w.off; c.pre_b = b + pre.b.off; c.gadd = cond;
+    c.tw = b + proj.w; c.tb = b + proj.b;
+    c.ldacc = ldacc;
+    if (split) {  // :103-117, and flows.0
+      c.split = 1;
+      c.ea_m = b + L.ea_m.off; c.ea_logs = b + L.ea_logs.off; c.ldinit = ws.LD;
+    }
+    run_dds<true>(b, convs, c, nullptr, ws.XA, ws.XB, TAIL_FWD, st);
+    c0 ^= 1;
+  };
+  for (int f = 0; f < 4; ++f) flow(L.pf_pre[f], L.pf_convs[f], L.pf_proj[f], ws.XP, ws.LDQ, f == 3);
+  // (four Flips: channel 0 is z_u again, and c0 == 0)
+  for (int f = 0; f < d.n_flows; ++f) flow(L.f_pre[f], L.f_convs[f], L.f_proj[f], ws.XC, ws.LD, false);
+  hipLaunchKernelGGL(nll_reduce_kernel, dim3((unsigned)B), dim3(64), 0, st, noise, ws.Z, ws.LDQ, ws.LD, lengths, T, c0, nll_out, terms_out, z_out);
+  return record_hip_error(h, "durnll_forward");
 }
 
 }  // extern "C"

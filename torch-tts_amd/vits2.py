@@ -6,8 +6,9 @@
                                              (``forward(x, x_mask, g=None, reverse=True)``)
 * ``Generator`` (+ ``ResBlock1``)         - the HiFi-GAN generator, vits2/models.py:900-974 and modules.py:221-315
                                              (``forward(x, g=None) -> [B, 1, T * prod(upsample_rates)]``; ``ttsgen_*``)
-* ``StochasticDurationPredictor``         - vits2/models.py:29-137, reverse only (``forward(x, x_mask, g=None, reverse=True,
-                                             noise_scale=1.0) -> logw [B, 1, T]``; ``ttsdur_*``)
+* ``StochasticDurationPredictor``         - vits2/models.py:29-137: ``forward(x, x_mask, g=None, reverse=True, noise_scale=1.0)
+                                             -> logw [B, 1, T]`` (``ttsdur_*``), and the other direction as ``nll(x, x_mask, w,
+                                             g=None) -> [B]``, the likelihood of given durations (``ttsvits_durnll_*``)
 * ``DurationPredictor``                   - vits2/models.py:140-180 (``forward(x, x_mask, g=None) -> logw [B, 1, T]``)
 * ``infer(net_g, x, x_lengths, ...)``     - SynthesizerTrn.infer (models.py:1288-1323) over the four drop-ins, channel-last
                                              from the ids to the waveform
@@ -29,10 +30,12 @@
                                              ``forward_probability``; ``ttsvits_durdisc_*``), and
                                              ``duration_discriminator_scores(net_g, net_dur_disc, x, ..., y, ...)`` - what train.py:414
                                              feeds and gets from them
+* ``duration_loss(net_g, x, ..., y, ...)`` - SynthesizerTrn.forward up to ``l_length`` (models.py:1214-1267), the VL/dur of the
+                                             reference's validation, and ``duration_loss_from_audio``
 
 All hold the reference's parameters (so checkpoints load) and run inference through the HIP library
 (``ttsvits_*`` / ``ttsgen_*`` / ``ttsdur_*`` / ``ttspost_*`` in include/ttsdec.h).  The library works on channel-last activations;
-the [B, C, T] tensors of the reference API are transposed here.  Training (gradients, logdet) and time-varying speaker
+the [B, C, T] tensors of the reference API are transposed here.  Training (gradients) and time-varying speaker
 conditioning are outside the path and raise."""
 from __future__ import annotations
 
@@ -940,6 +943,33 @@ class DurEngine(Handle):
         return z_p, m_p, logs_p, attn
 
 
+class DurNllEngine(Handle):
+    """One ttsvits_durnll handle on one device: the stochastic duration predictor's likelihood (its forward direction)."""
+
+    PREFIX = "ttsvits_durnll"
+
+    def __init__(self, dims: Dict, device: Optional[torch.device]):
+        super().__init__(dims, _lib.DurNllDims(*[int(dims[n]) for n, _ in _lib.DurNllDims._fields_]), device)
+
+    def workspace_bytes(self, B: int, T: int) -> int:
+        return int(self._fn("workspace_bytes")(self._h, B, T))
+
+    def forward(self, x_cl: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor], w: torch.Tensor, noise: torch.Tensor,
+                parts: bool = False):
+        """x_cl [B, T, C], w [B, T], noise [B, 2, T] contiguous fp32, lengths [B] int32 (device), g [B, gin] or None -> nll [B]
+        (, terms [B, 4], z [B, 2, T] with ``parts``)."""
+        B, T, _ = x_cl.shape
+        ws = self.workspace("call", self.workspace_bytes(B, T))
+        with torch.cuda.device(self.device):
+            nll = torch.empty(B, device=self.device)
+            terms = torch.empty(B, 4, device=self.device) if parts else None
+            z = torch.empty(B, 2, T, device=self.device) if parts else None
+            rc = self._fn("forward")(self._h, x_cl.data_ptr(), lengths.data_ptr(), _ptr(g), w.data_ptr(), noise.data_ptr(), B, T, nll.data_ptr(),
+                                     _ptr(terms), _ptr(z), ws.data_ptr(), ws.numel(), _stream(self.device))
+        self._err(rc, "ttsvits_durnll_forward")
+        return (nll, terms, z) if parts else nll
+
+
 
 
 class _TokenOperandsMixin:
@@ -971,9 +1001,11 @@ class _DurationBase(_TokenOperandsMixin, PackedWeightsMixin, nn.Module):
 
 class StochasticDurationPredictor(_DurationBase):
     """models.StochasticDurationPredictor (models.py:29-137): same constructor, parameters and state-dict keys (the training-only
-    post_* modules and flows.1 included, unused).  ``forward(x, x_mask, g=g, reverse=True, noise_scale=...) -> logw [B, 1, T]``
-    runs in the HIP library in exact fp32; the forward (training) direction raises.  ``noise=`` (keyword, test hook) replaces the
-    reference's draw torch.randn(B, 2, T) on the CPU generator."""
+    post_* modules and flows.1 included; the reverse pass does not read them).  ``forward(x, x_mask, g=g, reverse=True,
+    noise_scale=...) -> logw [B, 1, T]`` runs in the HIP library in exact fp32; ``forward`` in the other direction raises, and
+    what it would return in eval mode - the likelihood nll [B] of given durations - is ``nll(x, x_mask, w, g=g)``, a method of its
+    own with a handle and a blob of its own (every parameter of the module).  ``noise=`` (keyword, test hook) replaces the
+    reference's draw torch.randn(B, 2, T) on the CPU generator in either direction."""
 
     def __init__(self, in_channels, filter_channels, kernel_size, p_dropout, n_flows=4, gin_channels=0):
         super().__init__()
@@ -1003,6 +1035,50 @@ class StochasticDurationPredictor(_DurationBase):
         self._cfg = dict(kind=_lib.DUR_SDP, in_channels=in_channels, filter_channels=filter_channels, kernel_size=kernel_size, n_flows=n_flows,
                          gin_channels=gin_channels)
         self._engines = EngineCache(DurEngine)
+        self._nll_cfg = dict(in_channels=in_channels, kernel_size=kernel_size, n_flows=n_flows, gin_channels=gin_channels)
+        self._nll_engines = EngineCache(DurNllEngine)
+
+    def nll_weight_tensors(self) -> List[torch.Tensor]:
+        """ttsvits_durnll_pack_weights' order (include/ttsdec.h): every parameter of the module."""
+        def trunk(pre, convs, proj):
+            return [pre.weight, pre.bias] + convs.weight_tensors() + [proj.weight, proj.bias]
+
+        out = trunk(self.pre, self.convs, self.proj) + [self.flows[0].m, self.flows[0].logs]
+        for k in range(self.n_flows):
+            out += self.flows[2 * k + 1].weight_tensors()
+        out += trunk(self.post_pre, self.post_convs, self.post_proj) + [self.post_flows[0].m, self.post_flows[0].logs]
+        for k in range(4):
+            out += self.post_flows[2 * k + 1].weight_tensors()
+        if self.gin_channels:
+            out += [self.cond.weight, self.cond.bias]
+        return out
+
+    def nll_cl(self, x_cl, lengths, w, g=None, *, noise=None, parts=False):
+        """The likelihood on channel-last x [B, T, C] with lengths [B] and durations w [B, T] -> nll [B]; with ``parts`` also
+        terms [B, 4] (include/ttsdec.h ttsvits_durnll_forward) and z [B, 2, T] after the last flow."""
+        self._check(x_cl)
+        B, T, _ = x_cl.shape
+        if not w.is_cuda or w.dtype != torch.float32:
+            raise NotImplementedError(f"the HIP duration likelihood takes fp32 durations on x's ROCm device ({x_cl.device}), got {w.dtype} on "
+                                      f"{w.device}")
+        if tuple(w.shape) != (B, T):
+            raise ValueError(f"w must be [B, T] = [{B}, {T}], got {tuple(w.shape)}")
+        if noise is None:
+            noise = torch.randn(B, 2, T)  # models.py:95-98: drawn on the CPU generator, then moved
+        if tuple(noise.shape) != (B, 2, T):
+            raise ValueError(f"noise must be [B, 2, T] = [{B}, 2, {T}], got {tuple(noise.shape)}")
+        noise = noise.to(device=x_cl.device, dtype=torch.float32).contiguous()
+        eng = self._nll_engines.get(self._nll_cfg, x_cl.device)
+        eng.ensure_packed(self.nll_weight_tensors())
+        return eng.forward(x_cl.to(torch.float32).contiguous(), lengths.to(device=x_cl.device, dtype=torch.int32).contiguous(),
+                           self._speaker(g, B), w.detach().to(device=x_cl.device).contiguous(), noise, parts)
+
+    def nll(self, x, x_mask, w, g=None, *, noise=None) -> torch.Tensor:
+        """What the reference's ``forward(x, x_mask, w, g=g)`` returns in eval mode: x [B, C, T], w [B, 1, T] -> nll [B]."""
+        self._check(x)
+        if w.dim() != 3 or w.shape[1] != 1:
+            raise ValueError(f"w must be [B, 1, T], got {tuple(w.shape)}")
+        return self.nll_cl(self._channel_last(x), self._lengths(x_mask), w[:, 0], g, noise=noise)
 
     def weight_tensors(self) -> List[torch.Tensor]:
         """ttsdur_pack_weights' order (include/ttsdec.h): the reverse path's parameters; flows.1 and post_* are not read."""
@@ -1029,7 +1105,8 @@ class StochasticDurationPredictor(_DurationBase):
 
     def forward(self, x, x_mask, w=None, g=None, reverse=False, noise_scale=1.0, *, noise=None):
         if not reverse:
-            raise NotImplementedError("only the reverse (inference) direction of the stochastic duration predictor is on the HIP path")
+            raise NotImplementedError("forward() of the HIP stochastic duration predictor runs the reverse (inference) direction only; the "
+                                      "likelihood of given durations is nll(x, x_mask, w, g=g)")
         self._check(x)
         return self.logw_cl(self._channel_last(x), self._lengths(x_mask), g, noise_scale, noise).unsqueeze(1)
 
@@ -1495,6 +1572,31 @@ def duration_discriminator_scores(net_g, net_dur_disc, x, x_lengths, y, y_length
     return y_dur_hat_r, y_dur_hat_g, (hidden_x, x_mask, logw_, logw)
 
 
+def duration_loss(net_g, x, x_lengths, y, y_lengths, sid=None, *, mas_noise_scale=None, noise=None):
+    """The duration loss of a given utterance, SynthesizerTrn.forward up to models.py:1267 in eval mode, on ``forced_alignment``'s
+    body -> (l_length [B], attn [B, 1, T_y, T_x], x_mask [B, 1, T_x], (hidden_x [B, H, T_x], logw, logw_ [B, 1, T_x])).  With a
+    StochasticDurationPredictor l_length = dp.nll(x, x_mask, w, g=g) / sum(x_mask) and logw is its reverse pass at noise_scale
+    1.0; with a DurationPredictor logw = dp(x, x_mask, g=g) and l_length = sum((logw - logw_)^2) / sum(x_mask).  The divisor is
+    the whole batch's token count, as in the reference; ``l_length.sum()`` is the reference's VL/dur.  The one host read is the
+    alignment's status word.  ``noise`` (test hook): the triple (forced_alignment's noise, the likelihood's draw e_q [B, 2, T_x]
+    or None, the reverse pass's draw [B, 2, T_x] or None)."""
+    if noise is not None and not (isinstance(noise, (tuple, list)) and len(noise) == 3):
+        raise ValueError("noise must be a triple: (forced_alignment's noise, the likelihood's draw [B, 2, T_x] or None, the reverse pass's "
+                         "draw [B, 2, T_x] or None)")
+    e_fa, e_q, e_w = noise if noise is not None else (None, None, None)
+    attn, w, logw_, _, xs, t_x, x_mask, g = _forced_alignment(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, e_fa,
+                                                              {"dp": (StochasticDurationPredictor, DurationPredictor)}, "vits2.duration_loss")
+    dp = net_g.dp
+    n_tokens = torch.sum(x_mask)
+    if isinstance(dp, StochasticDurationPredictor):
+        l_length = dp.nll_cl(xs, t_x, w[:, 0], g, noise=e_q) / n_tokens
+        logw = dp.logw_cl(xs, t_x, g, 1.0, e_w).unsqueeze(1)
+    else:
+        logw = dp.logw_cl(xs, t_x, g).unsqueeze(1)
+        l_length = torch.sum((logw - logw_) ** 2, [1, 2]) / n_tokens
+    return l_length, attn, x_mask, (xs.transpose(1, 2), logw, logw_)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # Audio front-end (mel_processing.py, csrc/spec.hip) in front of voice conversion and forced alignment
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1530,3 +1632,10 @@ def forced_alignment_from_audio(net_g, x, x_lengths, wav, wav_lengths, sid=None,
     """``forced_alignment`` from waveforms (see voice_conversion_from_audio)."""
     y, y_lengths = _spec_from_audio(net_g, wav, wav_lengths, n_fft, hop_size, win_size, sampling_rate, n_mels, fmin, fmax, mel_basis)
     return forced_alignment(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale=mas_noise_scale, noise=noise)
+
+
+def duration_loss_from_audio(net_g, x, x_lengths, wav, wav_lengths, sid=None, *, n_fft, hop_size, win_size, sampling_rate, n_mels=None,
+                             fmin=0.0, fmax=None, mel_basis=None, mas_noise_scale=None, noise=None):
+    """``duration_loss`` from waveforms (see voice_conversion_from_audio)."""
+    y, y_lengths = _spec_from_audio(net_g, wav, wav_lengths, n_fft, hop_size, win_size, sampling_rate, n_mels, fmin, fmax, mel_basis)
+    return duration_loss(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale=mas_noise_scale, noise=noise)
