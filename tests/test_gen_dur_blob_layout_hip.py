@@ -1,5 +1,6 @@
-"""The packed generator and duration-predictor blobs do not move: ttsgen_pack_weights and ttsdur_pack_weights on fixed weights give
-the bytes they gave when tests/golden/gen_dur_blob_sha256.json was recorded - conv weights tap-major, the transposed convs as their
+"""The packed generator and duration-predictor blobs do not move: ttsgen_pack_weights, ttsdur_pack_weights and
+ttsvits_durnll_pack_weights on fixed weights give the bytes they gave when tests/golden/gen_dur_blob_sha256.json was recorded - conv
+weights tap-major, the transposed convs as their
 polyphase 3-tap weight with the bias once per phase, the duration convs K-major, the vectors, each at its offset - and so do the
 split-fp16 weight planes that ttsvits_generator_pack_planes makes from the bound blob, in a buffer zeroed first (the alignment gaps are
 never written), also where only some layers have planes.
@@ -7,7 +8,8 @@ never written), also where only some layers have planes.
 Weights are test_blob_layout_hip.hashed (closed form, no RNG stream).  The tensor sizes and their order are written out below from
 include/ttsdec.h, independently of the library's own layout walk.  The recorded hashes were taken on an MI355X from the library of
 commit 293bf2f ("Add the VITS2 duration discriminators on HIP: V1 and V2 probabilities"), the parent of the commit that introduced
-the weight records of csrc/generator.hip and csrc/duration.hip:
+the weight records of csrc/generator.hip and csrc/duration.hip; the durnll rows from the library of commit e4aad43 ("Add the VITS2
+duration likelihood on HIP: SDP forward, l_length, VL/dur"), where the likelihood handle still had a record struct of its own:
 
     TTSDEC_LIB=<that build's libttsdec.so> python tests/test_gen_dur_blob_layout_hip.py      prints the JSON"""
 import ctypes as C
@@ -20,7 +22,8 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-PACKED = ("gen_small", "gen_small_g", "sdp_small", "sdp_small_g", "dp_small", "dp_small_g")  # test_layout_host.family_dims keys
+PACKED = ("gen_small", "gen_small_g", "sdp_small", "sdp_small_g", "dp_small", "dp_small_g", "durnll_small",
+          "durnll_small_g")  # test_layout_host.family_dims keys
 # the planes buffer: every layer split; then the two mixed handles of test_generator_split_host (conv_pre and the resblocks exact: only
 # ups[0] has planes; one dilation keeps the stage exact: conv_pre and ups[0] have planes)
 PLANES = {"planes_gen_small": None, "planes_mixed_12_24": dict(initial=12, c0=24, rates=(2,), dil=(1, 1, 1)),
@@ -54,6 +57,16 @@ def dur_sizes(_lib, d):
     return out + ([Cc * d.gin_channels, Cc] if d.gin_channels else [])
 
 
+def durnll_sizes(d):
+    """elements per source tensor of ttsvits_durnll_pack_weights, in its order (include/ttsdec.h)"""
+    Cc = d.in_channels
+    dds = [Cc * 3, Cc, Cc * Cc, Cc, Cc, Cc, Cc, Cc] * 3
+    flow = [Cc, Cc] + dds + [29 * Cc, 29]
+    out = [Cc * Cc, Cc] + dds + [Cc * Cc, Cc] + [2, 2] + flow * d.n_flows  # pre, convs, proj; flows.0; flows.{2k+1}
+    out += [Cc, Cc] + dds + [Cc * Cc, Cc] + [2, 2] + flow * 4  # post_pre [C, 1, 1], post_convs, post_proj; post_flows.0; post_flows.{1, 3, 5, 7}
+    return out + ([Cc * d.gin_channels, Cc] if d.gin_channels else [])
+
+
 def _pack(_lib, lib, fam, d, h):
     """-> the packed blob (a device tensor) of hashed weights"""
     import torch
@@ -61,7 +74,7 @@ def _pack(_lib, lib, fam, d, h):
     from test_blob_layout_hip import hashed
 
     fn = lambda what: getattr(lib, f"{fam}_{what}")
-    sizes = gen_sizes(d) if fam == "ttsgen" else dur_sizes(_lib, d)
+    sizes = {"ttsgen": gen_sizes, "ttsvits_durnll": durnll_sizes, "ttsdur": lambda d: dur_sizes(_lib, d)}[fam](d)
     assert fn("num_weight_tensors")(h) == len(sizes)
     dev = [torch.from_numpy(hashed(n, i)).to("cuda:0") for i, n in enumerate(sizes)]
     arr = (C.c_void_p * len(dev))(*[t.data_ptr() for t in dev])

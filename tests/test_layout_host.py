@@ -58,6 +58,7 @@ def family_dims(_lib):
     for name, C_, F_, gin in (("small", 32, 48, 0), ("small_g", 32, 48, 4), ("model", 192, 256, 0), ("model_g", 192, 256, 256)):
         out["sdp_" + name] = ("ttsdur", _lib.DurDims(_lib.DUR_SDP, C_, 192, 3, 4, gin))
         out["dp_" + name] = ("ttsdur", _lib.DurDims(_lib.DUR_DP, C_, F_, 3, 0, gin))
+        out["durnll_" + name] = ("ttsvits_durnll", _lib.DurNllDims(C_, 3, 4, gin))
     out["post_small"] = ("ttspost", _lib.PostDims(13, 8, 16, 5, 3, 0))
     out["post_small_g"] = ("ttspost", _lib.PostDims(16, 8, 16, 5, 3, 8))
     out["post_model"] = ("ttspost", _lib.PostDims(513, 192, 192, 5, 16, 0))
@@ -115,7 +116,8 @@ def reported_sizes(lib, _lib):
 
 # As the library of commit e178cdf ("VITS2 flow path: one templated kernel per step, one layout per workspace") reported them, before
 # the size functions of these families became their carve routines' totals; the mel_analysis_ws rows as the library of commit 3e4a5ff
-# ("Add Tacotron audio analysis on HIP") reported them.  Bytes.
+# ("Add Tacotron audio analysis on HIP") reported them; the durnll rows as the library of commit e4aad43 ("Add the VITS2 duration
+# likelihood on HIP") reported them, before the two SDP handles shared their records.  Bytes.
 RECORDED = {
     "dec_small_mel/packed": [1472256],
     "dec_small_mel/decode_ws": [112896, 118784, 129280],
@@ -161,6 +163,14 @@ RECORDED = {
     "sdp_model_g/ws": [4096, 229632, 1850368],
     "dp_model_g/packed": [1581056],
     "dp_model_g/ws": [1792, 77312, 616704],
+    "durnll_small/packed": [235776],
+    "durnll_small/ws": [2048, 39936, 317696],
+    "durnll_small_g/packed": [236544],
+    "durnll_small_g/ws": [2048, 39936, 317696],
+    "durnll_model/packed": [5270784],
+    "durnll_model/ws": [4608, 230656, 1855488],
+    "durnll_model_g/packed": [5468160],
+    "durnll_model_g/ws": [4608, 230656, 1855488],
     "post_small/packed": [77824],
     "post_small/ws": [3840, 68864, 541440],
     "post_small_g/packed": [84480],
@@ -184,7 +194,7 @@ RECORDED = {
     "align_ws": [256, 256, 256, 4864, 4864, 4864, 38400, 38400, 38400],
     "gen_small_g/ws_group2": [1792, 113920, 614656],
     "gen_model/ws_group2": [198656, 14553088, 78647296],
-    "refused": [0, 177],
+    "refused": [0, 197],
 }
 
 

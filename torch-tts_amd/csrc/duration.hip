@@ -18,7 +18,11 @@
 // the epilogues; nll_reduce_kernel sums each utterance's tokens.  dds_layer_kernel<false> is the reverse path's kernel as it was.
 // At n_flows = 4: 1 (cond(g)) + 1 (pre) + 3 + 3 (post_convs) + 4 x 3 (post_flows) + 4 x 3 (flows) + 1 (sums) = 33 launches.
 // Every weight has one record (KConv: a K-major conv weight with its bias; Vec, layout.h: a tensor copied as given), made by one
-// walk at ttsdur_create; ttsdur_pack_weights and the forward calls read offsets, shapes and source indices from the records.
+// walk at *_create; *_pack_weights and the forward calls read offsets, shapes and source indices from the records.  The two
+// handle types are one struct, and the SDP has one record set (Sdp: pre, the main Trunk, flow[k] = flows.{2k+1}; post_pre, the
+// posterior Trunk, pflow[k] = post_flows.{2k+1}) that Walk::sdp walks for both: all of it for ttsvits_durnll_* (full), without
+// flow[0] and the posterior half for ttsdur_* kind 0, whose reverse pass runs flow[n_flows-1] .. flow[1].  Both directions open
+// with run_trunk (cond(g), pre, proj(convs)) and carve one workspace shape (carve_sdp; the log-det sums only when full).
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -50,40 +54,31 @@ struct DdsLayer {           // one DDSConv layer: convs_sep [C, 1, 3] -> [3][C] 
   Pair n1, n2;
 };
 typedef DdsLayer DdsW[3];   // one DDSConv
-struct DurBlob {
-  // kind 0
-  KConv pre;                 // [C][C]
+struct Flow {               // one ConvFlow: pre [C, 1, 1], [C]; its DDSConv; proj [C][29]
+  Pair pre;
   DdsW convs;
-  KConv proj;                // [C][C]
-  Vec ea_m, ea_logs;         // [2], [2]
-  Pair f_pre[8];             // [C], [C] (flows.{2k+1}, k = 1 .. n_flows-1)
-  DdsW f_convs[8];
-  KConv f_proj[8];           // [C][29]
-  // kind 1
-  KConv c1, c2;              // [3C][F], [3F][F]
+  KConv proj;
+};
+struct Trunk {              // a conditioning path behind its pre: the DDSConv, proj [C][C], then the ElementwiseAffine its flows open with
+  DdsW convs;
+  KConv proj;
+  Vec m, logs;              // [2], [2]
+};
+struct Sdp {                // the StochasticDurationPredictor's records, the same struct in both handles
+  KConv pre;                // [C][C]
+  Trunk main;               // convs, proj, flows.0
+  Flow flow[8];             // flow[k] is flows.{2k+1}; flow[0] (flows.1) the likelihood handle only
+  Pair post_pre;            // [C, 1, 1], [C]: from here on the likelihood handle only
+  Trunk post;               // post_convs, post_proj, post_flows.0
+  Flow pflow[4];            // post_flows.{1, 3, 5, 7}
+};
+struct DurBlob {
+  Sdp sdp;                   // kind 0, and ttsvits_durnll_*
+  KConv c1, c2;              // kind 1: [3C][F], [3F][F]
   Pair n1, n2, p;            // [F], [F]; proj: [F], [1]
   Pair cond;                 // [C, gin], [C]
   size_t total;
-  int n_src;                 // source tensors of ttsdur_pack_weights
-};
-struct NllBlob {             // ttsvits_durnll_*: every parameter of the SDP, in the order include/ttsdec.h documents
-  KConv pre;
-  DdsW convs;
-  KConv proj;
-  Vec ea_m, ea_logs;         // flows.0
-  Pair f_pre[8];             // flows.{2k+1}, k = 0 .. n_flows-1 (flows.1 included)
-  DdsW f_convs[8];
-  KConv f_proj[8];
-  Pair post_pre;             // [C, 1, 1], [C]
-  DdsW post_convs;
-  KConv post_proj;
-  Vec pea_m, pea_logs;       // post_flows.0
-  Pair pf_pre[4];            // post_flows.{1, 3, 5, 7}
-  DdsW pf_convs[4];
-  KConv pf_proj[4];
-  Pair cond;
-  size_t total;
-  int n_src;
+  int n_src;                 // source tensors of *_pack_weights
 };
 // the one walk over the blob: offsets in blob order, source indices in the order include/ttsdec.h documents (src ends as their count)
 struct Walk : BlobWalk {
@@ -103,17 +98,38 @@ struct Walk : BlobWalk {
       l.n2 = pair(C, C);
     }
   }
+  void flow(Flow& f, int C) {
+    f.pre = pair(C, C);
+    dds(f.convs, C);
+    f.proj = conv(kProj, C, 1);
+  }
+  void trunk(Trunk& t, int C) {
+    dds(t.convs, C);
+    t.proj = conv(C, C, 1);
+    t.m = vec(2);
+    t.logs = vec(2);
+  }
+  // full: every parameter of the module (ttsvits_durnll_*); else what the reverse pass reads: no flows.1, no post_*
+  void sdp(Sdp& s, int C, int n_flows, bool full) {
+    s.pre = conv(C, C, 1);
+    trunk(s.main, C);
+    for (int k = full ? 0 : 1; k < n_flows; ++k) flow(s.flow[k], C);
+    if (!full) return;
+    s.post_pre = pair(C, C);
+    trunk(s.post, C);
+    for (Flow& f : s.pflow) flow(f, C);
+  }
+};
+
+struct DurHandle : HandleBase {  // what both handle types are
+  ttsdur_dims d;  // (the likelihood's dims as kind 0)
+  bool full;      // Walk::sdp
+  DurBlob bl;
 };
 }  // namespace
 
-struct ttsdur_handle : HandleBase {
-  ttsdur_dims d;
-  DurBlob bl;
-};
-struct ttsvits_durnll_handle : HandleBase {
-  ttsvits_durnll_dims d;
-  NllBlob bl;
-};
+struct ttsdur_handle : DurHandle {};
+struct ttsvits_durnll_handle : DurHandle {};
 
 namespace {
 
@@ -127,22 +143,13 @@ bool dims_ok(const ttsdur_dims& d) {
   return true;
 }
 
-DurBlob make_layout(const ttsdur_dims& d) {
+DurBlob make_layout(const ttsdur_dims& d, bool full) {
   DurBlob L;
   memset(&L, 0, sizeof(L));
   Walk w;
   const int C = d.in_channels;
   if (d.kind == 0) {
-    L.pre = w.conv(C, C, 1);
-    w.dds(L.convs, C);
-    L.proj = w.conv(C, C, 1);
-    L.ea_m = w.vec(2);
-    L.ea_logs = w.vec(2);
-    for (int k = 0; k < d.n_flows - 1; ++k) {
-      L.f_pre[k] = w.pair(C, C);  // [C, 1, 1], [C]
-      w.dds(L.f_convs[k], C);
-      L.f_proj[k] = w.conv(kProj, C, 1);
-    }
+    w.sdp(L.sdp, C, d.n_flows, full);
   } else {
     const int F = d.filter_channels;
     L.c1 = w.conv(F, C, 3);
@@ -157,45 +164,31 @@ DurBlob make_layout(const ttsdur_dims& d) {
   return L;
 }
 
-bool nll_dims_ok(const ttsvits_durnll_dims& d) {  // what kind 0 above accepts
-  return dims_ok(ttsdur_dims{0, d.in_channels, d.in_channels, d.kernel_size, d.n_flows, d.gin_channels});
-}
-
-NllBlob make_nll_layout(const ttsvits_durnll_dims& d) {
-  NllBlob L;
-  memset(&L, 0, sizeof(L));
-  Walk w;
-  const int C = d.in_channels;
-  auto flow = [&](Pair& pre, DdsW& convs, KConv& proj) {
-    pre = w.pair(C, C);
-    w.dds(convs, C);
-    proj = w.conv(kProj, C, 1);
-  };
-  L.pre = w.conv(C, C, 1);
-  w.dds(L.convs, C);
-  L.proj = w.conv(C, C, 1);
-  L.ea_m = w.vec(2);
-  L.ea_logs = w.vec(2);
-  for (int k = 0; k < d.n_flows; ++k) flow(L.f_pre[k], L.f_convs[k], L.f_proj[k]);
-  L.post_pre = w.pair(C, C);
-  w.dds(L.post_convs, C);
-  L.post_proj = w.conv(C, C, 1);
-  L.pea_m = w.vec(2);
-  L.pea_logs = w.vec(2);
-  for (int k = 0; k < 4; ++k) flow(L.pf_pre[k], L.pf_convs[k], L.pf_proj[k]);
-  if (d.gin_channels > 0) L.cond = w.pair((size_t)C * d.gin_channels, C);
-  L.total = w.cv.off;
-  L.n_src = w.src;
-  return L;
+template <typename Handle>
+int create(const ttsdur_dims& d, bool full, Handle** out) {
+  *out = nullptr;
+  if (!dims_ok(d)) return TTSDEC_ERR_DIMS;
+  Handle* h = new (std::nothrow) Handle();
+  if (!h) return TTSDEC_ERR_INVALID_ARG;
+  h->d = d;
+  h->full = full;
+  h->bl = make_layout(d, full);
+  h->device = current_device_or_minus1();
+  *out = h;
+  return TTSDEC_OK;
 }
 
 // The workspaces of the two predictors (carved as layout.h's Carver comment says)
-struct SdpWs { float *XP, *XA, *XB, *XC, *Z, *condv; };  // four [M, C] activations; [B, 2, T] the flows' state; [B, C] cond(g)
-SdpWs carve_sdp(Carver& cv, const ttsdur_dims& d, size_t B, size_t T) {
-  const size_t MC = B * T * d.in_channels;
-  SdpWs w;
+// the SDP's: four [M, C] activations (in the likelihood XP holds pre's output, then g_q = x + h_w); [B, 2, T] the flows' state;
+// full: [B, T] the per-token log-det sums of the posterior and the main flows; [B, C] cond(g)
+struct SdpWs { float *XP, *XA, *XB, *XC, *Z, *LDQ, *LD, *condv; };
+SdpWs carve_sdp(Carver& cv, const DurHandle& h, size_t B, size_t T) {
+  const size_t MC = B * T * h.d.in_channels;
+  SdpWs w{};
   w.XP = cv.take(MC); w.XA = cv.take(MC); w.XB = cv.take(MC); w.XC = cv.take(MC);
-  w.Z = cv.take(2 * B * T); w.condv = cv.take(B * d.in_channels);
+  w.Z = cv.take(2 * B * T);
+  if (h.full) { w.LDQ = cv.take(B * T); w.LD = cv.take(B * T); }
+  w.condv = cv.take(B * h.d.in_channels);
   return w;
 }
 struct DpWs { float *H1, *condv; };  // [M, F] conv_1's output; [B, C] cond(g)
@@ -204,20 +197,11 @@ DpWs carve_dp(Carver& cv, const ttsdur_dims& d, size_t B, size_t T) {
   w.H1 = cv.take(B * T * d.filter_channels); w.condv = cv.take(B * d.in_channels);
   return w;
 }
-// the likelihood's: the SDP's buffers (XP holds pre's output, then g_q = x + h_w) and the per-token log-det sums of the posterior
-// and the main flows [B, T]
-struct NllWs { float *XP, *XA, *XB, *XC, *Z, *LDQ, *LD, *condv; };
-NllWs carve_nll(Carver& cv, const ttsvits_durnll_dims& d, size_t B, size_t T) {
-  const size_t MC = B * T * d.in_channels;
-  NllWs w;
-  w.XP = cv.take(MC); w.XA = cv.take(MC); w.XB = cv.take(MC); w.XC = cv.take(MC);
-  w.Z = cv.take(2 * B * T); w.LDQ = cv.take(B * T); w.LD = cv.take(B * T); w.condv = cv.take(B * d.in_channels);
-  return w;
-}
-size_t carved_bytes(const ttsdur_dims& d, int B, int T) {
+size_t carved_bytes(const DurHandle* h, int B, int T) {  // *_workspace_bytes
+  if (!h || B <= 0 || T <= 0) return 0;
   Carver cv{nullptr};
-  if (d.kind == 0) carve_sdp(cv, d, B, T);
-  else carve_dp(cv, d, B, T);
+  if (h->d.kind == 0) carve_sdp(cv, *h, B, T);
+  else carve_dp(cv, h->d, B, T);
   return cv.bytes();
 }
 
@@ -749,7 +733,7 @@ size_t dds_lds(int C) { return (size_t)3 * kRows * C * sizeof(float); }
 size_t nll_lds(int C) { return max(dds_lds(C), (size_t)kRows * (C + kProj) * sizeof(float)); }
 size_t pw_lds(int Cin, int taps, int N) { return (size_t)kRows * (taps * Cin + N) * sizeof(float); }
 
-// ttsdur_pack_weights' steps, one per record: from src into the blob b
+// *_pack_weights' steps, one per record: from src into the blob b
 void pack_conv(const float* const* src, float* b, const KConv& c, hipStream_t st) {
   hipLaunchKernelGGL(pack_kmajor_kernel, grid1(c.n()), dim3(256), 0, st, src[c.src], b + c.w, c.N, c.Cin, c.taps);
   launch_copy(src[c.src + 1], b + c.b, c.N, st);
@@ -767,8 +751,47 @@ void pack_dds(const float* const* src, float* b, const DdsW& w, hipStream_t st) 
     pack_pair(src, b, l.n2, st);
   }
 }
+void pack_flow(const float* const* src, float* b, const Flow& f, hipStream_t st) {
+  pack_pair(src, b, f.pre, st);
+  pack_dds(src, b, f.convs, st);
+  pack_conv(src, b, f.proj, st);
+}
+void pack_trunk(const float* const* src, float* b, const Trunk& t, hipStream_t st) {
+  pack_dds(src, b, t.convs, st);
+  pack_conv(src, b, t.proj, st);
+  pack_vec(src, b, t.m, st);
+  pack_vec(src, b, t.logs, st);
+}
+// both *_pack_weights: the records in the order the walk made them
+int pack_weights(DurHandle* h, const float* const* src, int n_src, void* blob, hipStream_t st) {
+  if (!h) return TTSDEC_ERR_INVALID_ARG;
+  const int rc = pack_begin(h, src, n_src, h->bl.n_src, false, blob, h->bl.total * sizeof(float), st);
+  if (rc != TTSDEC_OK) return rc;
+  const ttsdur_dims& d = h->d;
+  const DurBlob& L = h->bl;
+  float* b = static_cast<float*>(blob);
+  if (d.kind == 0) {
+    const Sdp& s = L.sdp;
+    pack_conv(src, b, s.pre, st);
+    pack_trunk(src, b, s.main, st);
+    for (int k = h->full ? 0 : 1; k < d.n_flows; ++k) pack_flow(src, b, s.flow[k], st);
+    if (h->full) {
+      pack_pair(src, b, s.post_pre, st);
+      pack_trunk(src, b, s.post, st);
+      for (const Flow& f : s.pflow) pack_flow(src, b, f, st);
+    }
+  } else {
+    pack_conv(src, b, L.c1, st);
+    pack_pair(src, b, L.n1, st);
+    pack_conv(src, b, L.c2, st);
+    pack_pair(src, b, L.n2, st);
+    pack_pair(src, b, L.p, st);
+  }
+  if (d.gin_channels > 0) pack_pair(src, b, L.cond, st);
+  return pack_end(h, b);
+}
 
-template <bool kNll = false>
+template <bool kNll>
 void run_dds(const float* b, const DdsW& w, DdsArgs a, const float* x_first, float* bufA, float* bufB, int tail, hipStream_t st) {
   const unsigned nblk = (unsigned)((a.M + kRows - 1) / kRows);
   const float* in = x_first;
@@ -787,16 +810,40 @@ void run_dds(const float* b, const DdsW& w, DdsArgs a, const float* x_first, flo
   }
 }
 
-int check_call(ttsdur_handle* h, int kind, const float* x, const int* lengths, const float* g, int B, int T, float* logw, void* ws,
-               size_t ws_bytes) {
-  if (!h || !x || !lengths || !logw || !ws || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
+// The guards in front of the forward calls, in the order their codes take precedence.  args_ok: the call's own pointers.
+int check_call(const DurHandle* h, int kind, bool args_ok, const float* g, int B, int T, const void* ws, size_t ws_bytes) {
+  if (!h || !args_ok || !ws || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
   if (h->d.kind != kind) return TTSDEC_ERR_INVALID_ARG;
   if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
   if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
   if ((size_t)B * T > (size_t)1 << 30) return TTSDEC_ERR_DIMS;
-  if (ws_bytes < carved_bytes(h->d, B, T) || (reinterpret_cast<uintptr_t>(ws) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (ws_bytes < carved_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(ws) & 255)) return TTSDEC_ERR_WORKSPACE;
   if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   return TTSDEC_OK;
+}
+
+DdsArgs dds_args(const DurHandle* h, const int* lengths, int B, int T) {  // what every DDSConv launch of a call starts from
+  DdsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.lengths = lengths; a.C = h->d.in_channels; a.T = T; a.M = B * T; a.zscale = 1.f; a.sqrt_c = sqrtf((float)a.C);
+  return a;
+}
+
+// models.py:79-85, the opening of both directions: cond(g); x = pre(x) (+ cond(g)) -> XP; x = proj(convs(x, x_mask)) * x_mask -> XC
+template <bool kNll>
+void run_trunk(const DurHandle* h, const DdsArgs& a, const float* x, const float* g, int B, const SdpWs& w, hipStream_t st) {
+  const Sdp& s = h->bl.sdp;
+  const float* b = h->blob;
+  const int C = a.C;
+  if (g) launch_cond(g, b + h->bl.cond.w.off, b + h->bl.cond.b.off, w.condv, B, C, h->d.gin_channels, st);
+  PwArgs p;
+  memset(&p, 0, sizeof(p));
+  p.x = x; p.Cin = C; p.taps = 1; p.W = b + s.pre.w; p.bias = b + s.pre.b; p.N = C; p.out_rowvec = g ? w.condv : nullptr;
+  p.out = w.XP; p.lengths = a.lengths; p.T = a.T; p.M = a.M;
+  hipLaunchKernelGGL(pw_conv_kernel, dim3((unsigned)((a.M + kRows - 1) / kRows)), dim3(kThreads), pw_lds(C, 1, C), st, p);
+  DdsArgs c = a;
+  c.tw = b + s.main.proj.w; c.tb = b + s.main.proj.b; c.xout = w.XC;  // (layer 2's tail writes xout)
+  run_dds<kNll>(b, s.main.convs, c, w.XP, w.XA, w.XB, TAIL_PROJ, st);
 }
 
 }  // namespace
@@ -805,15 +852,7 @@ extern "C" {
 
 int ttsdur_create(const ttsdur_dims* dims, ttsdur_handle** out) {
   if (!dims || !out) return TTSDEC_ERR_INVALID_ARG;
-  *out = nullptr;
-  if (!dims_ok(*dims)) return TTSDEC_ERR_DIMS;
-  ttsdur_handle* h = new (std::nothrow) ttsdur_handle();
-  if (!h) return TTSDEC_ERR_INVALID_ARG;
-  h->d = *dims;
-  h->bl = make_layout(*dims);
-  h->device = current_device_or_minus1();
-  *out = h;
-  return TTSDEC_OK;
+  return create(*dims, false, out);
 }
 int ttsdur_destroy(ttsdur_handle* h) {
   delete h;
@@ -822,90 +861,43 @@ int ttsdur_destroy(ttsdur_handle* h) {
 const char* ttsdur_last_hip_error(const ttsdur_handle* h) { return last_hip_error(h); }
 int ttsdur_num_weight_tensors(const ttsdur_handle* h) { return h ? h->bl.n_src : TTSDEC_ERR_INVALID_ARG; }
 size_t ttsdur_packed_bytes(const ttsdur_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
-
 int ttsdur_pack_weights(ttsdur_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = pack_begin(h, src, n_src, ttsdur_num_weight_tensors(h), false, blob, ttsdur_packed_bytes(h), st);
-  if (rc != TTSDEC_OK) return rc;
-  const ttsdur_dims& d = h->d;
-  const DurBlob& L = h->bl;
-  float* b = static_cast<float*>(blob);
-  if (d.kind == 0) {
-    pack_conv(src, b, L.pre, st);
-    pack_dds(src, b, L.convs, st);
-    pack_conv(src, b, L.proj, st);
-    pack_vec(src, b, L.ea_m, st);
-    pack_vec(src, b, L.ea_logs, st);
-    for (int f = 0; f < d.n_flows - 1; ++f) {
-      pack_pair(src, b, L.f_pre[f], st);
-      pack_dds(src, b, L.f_convs[f], st);
-      pack_conv(src, b, L.f_proj[f], st);
-    }
-  } else {
-    pack_conv(src, b, L.c1, st);
-    pack_pair(src, b, L.n1, st);
-    pack_conv(src, b, L.c2, st);
-    pack_pair(src, b, L.n2, st);
-    pack_pair(src, b, L.p, st);
-  }
-  if (d.gin_channels > 0) pack_pair(src, b, L.cond, st);
-  return pack_end(h, b);
+  return pack_weights(h, src, n_src, blob, static_cast<hipStream_t>(stream));
 }
-
 int ttsdur_bind_weights(ttsdur_handle* h, const void* blob) { return bind_blob(h, blob); }
-
-size_t ttsdur_workspace_bytes(const ttsdur_handle* h, int B, int T) {
-  if (!h || B <= 0 || T <= 0) return 0;
-  return carved_bytes(h->d, B, T);
-}
+size_t ttsdur_workspace_bytes(const ttsdur_handle* h, int B, int T) { return carved_bytes(h, B, T); }
 
 int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths, const float* g, const float* noise, float noise_scale, int B,
                        int T, float* logw, void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = check_call(h, 0, x, lengths, g, B, T, logw, workspace, workspace_bytes);
+  int rc = check_call(h, 0, x && lengths && logw, g, B, T, workspace, workspace_bytes);
   if (rc != TTSDEC_OK) return rc;
-  if (!noise) return TTSDEC_ERR_INVALID_ARG;
+  if (!noise) return TTSDEC_ERR_INVALID_ARG;  // (behind the guards above: an unbound handle answers NOT_BOUND first)
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const ttsdur_dims& d = h->d;
-  const DurBlob& L = h->bl;
+  const Sdp& s = h->bl.sdp;
   const float* b = h->blob;
-  const int C = d.in_channels, M = B * T;
+  const int n_flows = h->d.n_flows;
   Carver cv{static_cast<float*>(workspace)};
-  const SdpWs w = carve_sdp(cv, d, B, T);
-  float *XP = w.XP, *XA = w.XA, *XB = w.XB, *XC = w.XC, *Z = w.Z, *condv = w.condv;
-  const unsigned nblk = (unsigned)((M + kRows - 1) / kRows);
-  if (g) launch_cond(g, b + L.cond.w.off, b + L.cond.b.off, condv, B, C, d.gin_channels, st);
-  {  // models.py:80-84: x = pre(x) (+ cond(g))
-    PwArgs p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.Cin = C; p.taps = 1; p.W = b + L.pre.w; p.bias = b + L.pre.b; p.N = C; p.out_rowvec = g ? condv : nullptr;
-    p.out = XP; p.lengths = lengths; p.T = T; p.M = M;
-    hipLaunchKernelGGL(pw_conv_kernel, dim3(nblk), dim3(kThreads), pw_lds(C, 1, C), st, p);
-  }
-  DdsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.lengths = lengths; a.C = C; a.T = T; a.M = M; a.zscale = 1.f; a.sqrt_c = sqrtf((float)C);
-  {  // :85-86: x = proj(convs(x, x_mask)) * x_mask -> XC
-    DdsArgs c = a;
-    c.tw = b + L.proj.w; c.tb = b + L.proj.b; c.xout = XC;
-    run_dds(b, L.convs, c, XP, XA, XB, TAIL_PROJ, st);
-    // (run_dds hands layer 2 xout = XC through c.xout: the tail writes it)
-  }
-  // :127-133: [Flip, ConvFlow_{n-1}, Flip, ..., ConvFlow_1, Flip, ElementwiseAffine]; z = noise * noise_scale
+  const SdpWs w = carve_sdp(cv, *h, B, T);
+  const DdsArgs a = dds_args(h, lengths, B, T);
+  run_trunk<false>(h, a, x, g, B, w, st);
+  // :127-133: the flows reversed, flows.1 dropped: [Flip, flow[n_flows-1], Flip, ..., flow[1], Flip, ElementwiseAffine];
+  // z = noise * noise_scale
   int c0 = 1;  // the first Flip
-  for (int f = d.n_flows - 2; f >= 0; --f) {
+  for (int k = n_flows - 1; k >= 1; --k) {
+    const Flow& f = s.flow[k];
     DdsArgs c = a;
-    c.zin = f == d.n_flows - 2 ? noise : Z;
-    c.zscale = f == d.n_flows - 2 ? noise_scale : 1.f;
+    c.zin = k == n_flows - 1 ? noise : w.Z;
+    c.zscale = k == n_flows - 1 ? noise_scale : 1.f;
     c.c0 = c0;
-    c.pre_w = b + L.f_pre[f].w.off; c.pre_b = b + L.f_pre[f].b.off; c.gadd = XC;
-    c.tw = b + L.f_proj[f].w; c.tb = b + L.f_proj[f].b;
-    c.zout = Z;
-    if (f == 0) {
+    c.pre_w = b + f.pre.w.off; c.pre_b = b + f.pre.b.off; c.gadd = w.XC;
+    c.tw = b + f.proj.w; c.tb = b + f.proj.b;
+    c.zout = w.Z;
+    if (k == 1) {
       c.logw = logw;
-      c.ea_m = b + L.ea_m.off;
-      c.ea_logs = b + L.ea_logs.off;
+      c.ea_m = b + s.main.m.off;
+      c.ea_logs = b + s.main.logs.off;
     }
-    run_dds(b, L.f_convs[f], c, nullptr, XA, XB, TAIL_FLOW, st);
+    run_dds<false>(b, f.convs, c, nullptr, w.XA, w.XB, TAIL_FLOW, st);
     c0 ^= 1;  // the Flip after it
   }
   return record_hip_error(h, "sdp_reverse");
@@ -913,7 +905,7 @@ int ttsdur_sdp_reverse(ttsdur_handle* h, const float* x, const int32_t* lengths,
 
 int ttsdur_dp_forward(ttsdur_handle* h, const float* x, const int32_t* lengths, const float* g, int B, int T, float* logw, void* workspace,
                       size_t workspace_bytes, void* stream) {
-  int rc = check_call(h, 1, x, lengths, g, B, T, logw, workspace, workspace_bytes);
+  int rc = check_call(h, 1, x && lengths && logw, g, B, T, workspace, workspace_bytes);
   if (rc != TTSDEC_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ttsdur_dims& d = h->d;
@@ -965,15 +957,7 @@ int ttsdur_expand(ttsdur_handle* h, const int32_t* cum, const float* m, const fl
 // ---------------------------------------------------------------------------------------------------------------------------
 int ttsvits_durnll_create(const ttsvits_durnll_dims* dims, ttsvits_durnll_handle** out) {
   if (!dims || !out) return TTSDEC_ERR_INVALID_ARG;
-  *out = nullptr;
-  if (!nll_dims_ok(*dims)) return TTSDEC_ERR_DIMS;
-  ttsvits_durnll_handle* h = new (std::nothrow) ttsvits_durnll_handle();
-  if (!h) return TTSDEC_ERR_INVALID_ARG;
-  h->d = *dims;
-  h->bl = make_nll_layout(*dims);
-  h->device = current_device_or_minus1();
-  *out = h;
-  return TTSDEC_OK;
+  return create(ttsdur_dims{0, dims->in_channels, dims->in_channels, dims->kernel_size, dims->n_flows, dims->gin_channels}, true, out);
 }
 int ttsvits_durnll_destroy(ttsvits_durnll_handle* h) {
   delete h;
@@ -982,101 +966,50 @@ int ttsvits_durnll_destroy(ttsvits_durnll_handle* h) {
 const char* ttsvits_durnll_last_hip_error(const ttsvits_durnll_handle* h) { return last_hip_error(h); }
 int ttsvits_durnll_num_weight_tensors(const ttsvits_durnll_handle* h) { return h ? h->bl.n_src : TTSDEC_ERR_INVALID_ARG; }
 size_t ttsvits_durnll_packed_bytes(const ttsvits_durnll_handle* h) { return h ? h->bl.total * sizeof(float) : 0; }
-
 int ttsvits_durnll_pack_weights(ttsvits_durnll_handle* h, const float* const* src, int n_src, void* blob, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = pack_begin(h, src, n_src, ttsvits_durnll_num_weight_tensors(h), false, blob, ttsvits_durnll_packed_bytes(h), st);
-  if (rc != TTSDEC_OK) return rc;
-  const NllBlob& L = h->bl;
-  float* b = static_cast<float*>(blob);
-  auto flow = [&](const Pair& pre, const DdsW& convs, const KConv& proj) {
-    pack_pair(src, b, pre, st);
-    pack_dds(src, b, convs, st);
-    pack_conv(src, b, proj, st);
-  };
-  pack_conv(src, b, L.pre, st);
-  pack_dds(src, b, L.convs, st);
-  pack_conv(src, b, L.proj, st);
-  pack_vec(src, b, L.ea_m, st);
-  pack_vec(src, b, L.ea_logs, st);
-  for (int f = 0; f < h->d.n_flows; ++f) flow(L.f_pre[f], L.f_convs[f], L.f_proj[f]);
-  pack_pair(src, b, L.post_pre, st);
-  pack_dds(src, b, L.post_convs, st);
-  pack_conv(src, b, L.post_proj, st);
-  pack_vec(src, b, L.pea_m, st);
-  pack_vec(src, b, L.pea_logs, st);
-  for (int f = 0; f < 4; ++f) flow(L.pf_pre[f], L.pf_convs[f], L.pf_proj[f]);
-  if (h->d.gin_channels > 0) pack_pair(src, b, L.cond, st);
-  return pack_end(h, b);
+  return pack_weights(h, src, n_src, blob, static_cast<hipStream_t>(stream));
 }
-
 int ttsvits_durnll_bind_weights(ttsvits_durnll_handle* h, const void* blob) { return bind_blob(h, blob); }
-
-size_t ttsvits_durnll_workspace_bytes(const ttsvits_durnll_handle* h, int B, int T) {
-  if (!h || B <= 0 || T <= 0) return 0;
-  Carver cv{nullptr};
-  carve_nll(cv, h->d, B, T);
-  return cv.bytes();
-}
+size_t ttsvits_durnll_workspace_bytes(const ttsvits_durnll_handle* h, int B, int T) { return carved_bytes(h, B, T); }
 
 int ttsvits_durnll_forward(ttsvits_durnll_handle* h, const float* x, const int32_t* lengths, const float* g, const float* w, const float* noise,
                            int B, int T, float* nll_out, float* terms_out, float* z_out, void* workspace, size_t workspace_bytes,
                            void* stream) {
-  if (!h || !x || !lengths || !w || !noise || !nll_out || !workspace || B <= 0 || T <= 0) return TTSDEC_ERR_INVALID_ARG;
-  if (g != nullptr && h->d.gin_channels <= 0) return TTSDEC_ERR_INVALID_ARG;
-  if (!h->blob) return TTSDEC_ERR_NOT_BOUND;
-  if ((size_t)B * T > (size_t)1 << 30) return TTSDEC_ERR_DIMS;
-  if (workspace_bytes < ttsvits_durnll_workspace_bytes(h, B, T) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
-  if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
+  int rc = check_call(h, 0, x && lengths && w && noise && nll_out, g, B, T, workspace, workspace_bytes);
+  if (rc != TTSDEC_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const ttsvits_durnll_dims& d = h->d;
-  const NllBlob& L = h->bl;
+  const Sdp& s = h->bl.sdp;
   const float* b = h->blob;
-  const int C = d.in_channels, M = B * T;
   Carver cv{static_cast<float*>(workspace)};
-  const NllWs ws = carve_nll(cv, d, B, T);
-  const unsigned nblk = (unsigned)((M + kRows - 1) / kRows);
-  if (g) launch_cond(g, b + L.cond.w.off, b + L.cond.b.off, ws.condv, B, C, d.gin_channels, st);
-  {  // models.py:79-83: x = pre(x) (+ cond(g))
-    PwArgs p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.Cin = C; p.taps = 1; p.W = b + L.pre.w; p.bias = b + L.pre.b; p.N = C; p.out_rowvec = g ? ws.condv : nullptr;
-    p.out = ws.XP; p.lengths = lengths; p.T = T; p.M = M;
-    hipLaunchKernelGGL(pw_conv_kernel, dim3(nblk), dim3(kThreads), pw_lds(C, 1, C), st, p);
-  }
-  DdsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.lengths = lengths; a.C = C; a.T = T; a.M = M; a.zscale = 1.f; a.sqrt_c = sqrtf((float)C); a.w = w;
-  {  // :84-85: x = proj(convs(x, x_mask)) * x_mask -> XC
-    DdsArgs c = a;
-    c.tw = b + L.proj.w; c.tb = b + L.proj.b; c.xout = ws.XC;
-    run_dds<true>(b, L.convs, c, ws.XP, ws.XA, ws.XB, TAIL_PROJ, st);
-  }
+  const SdpWs ws = carve_sdp(cv, *h, B, T);
+  DdsArgs a = dds_args(h, lengths, B, T);
+  a.w = w;
+  run_trunk<true>(h, a, x, g, B, ws, st);
   {  // :92-96: g_q = x + post_proj(post_convs(post_pre(w))) * x_mask -> XP; z_q = post_flows.0(e_q * x_mask) -> Z, LDQ
     DdsArgs c = a;
-    c.pre_w = b + L.post_pre.w.off; c.pre_b = b + L.post_pre.b.off;
-    c.tw = b + L.post_proj.w; c.tb = b + L.post_proj.b; c.tadd = ws.XC; c.xout = ws.XP;
-    c.eq = noise; c.ea_m = b + L.pea_m.off; c.ea_logs = b + L.pea_logs.off; c.zout = ws.Z; c.ldinit = ws.LDQ;
-    run_dds<true>(b, L.post_convs, c, nullptr, ws.XA, ws.XB, TAIL_PROJ, st);
+    c.pre_w = b + s.post_pre.w.off; c.pre_b = b + s.post_pre.b.off;
+    c.tw = b + s.post.proj.w; c.tb = b + s.post.proj.b; c.tadd = ws.XC; c.xout = ws.XP;
+    c.eq = noise; c.ea_m = b + s.post.m.off; c.ea_logs = b + s.post.logs.off; c.zout = ws.Z; c.ldinit = ws.LDQ;
+    run_dds<true>(b, s.post.convs, c, nullptr, ws.XA, ws.XB, TAIL_PROJ, st);
   }
   // a ConvFlow forward and the Flip after it (modules.py:486-514): x0 is the physical channel c0 of Z
   int c0 = 0;
-  auto flow = [&](const Pair& pre, const DdsW& convs, const KConv& proj, const float* cond, float* ldacc, bool split) {
+  auto flow = [&](const Flow& f, const float* cond, float* ldacc, bool split) {
     DdsArgs c = a;
     c.zin = ws.Z; c.zout = ws.Z; c.c0 = c0;
-    c.pre_w = b + pre.w.off; c.pre_b = b + pre.b.off; c.gadd = cond;
-    c.tw = b + proj.w; c.tb = b + proj.b;
+    c.pre_w = b + f.pre.w.off; c.pre_b = b + f.pre.b.off; c.gadd = cond;
+    c.tw = b + f.proj.w; c.tb = b + f.proj.b;
     c.ldacc = ldacc;
     if (split) {  // :103-117, and flows.0
       c.split = 1;
-      c.ea_m = b + L.ea_m.off; c.ea_logs = b + L.ea_logs.off; c.ldinit = ws.LD;
+      c.ea_m = b + s.main.m.off; c.ea_logs = b + s.main.logs.off; c.ldinit = ws.LD;
     }
-    run_dds<true>(b, convs, c, nullptr, ws.XA, ws.XB, TAIL_FWD, st);
+    run_dds<true>(b, f.convs, c, nullptr, ws.XA, ws.XB, TAIL_FWD, st);
     c0 ^= 1;
   };
-  for (int f = 0; f < 4; ++f) flow(L.pf_pre[f], L.pf_convs[f], L.pf_proj[f], ws.XP, ws.LDQ, f == 3);
+  for (int k = 0; k < 4; ++k) flow(s.pflow[k], ws.XP, ws.LDQ, k == 3);
   // (four Flips: channel 0 is z_u again, and c0 == 0)
-  for (int f = 0; f < d.n_flows; ++f) flow(L.f_pre[f], L.f_convs[f], L.f_proj[f], ws.XC, ws.LD, false);
+  for (int k = 0; k < h->d.n_flows; ++k) flow(s.flow[k], ws.XC, ws.LD, false);
   hipLaunchKernelGGL(nll_reduce_kernel, dim3((unsigned)B), dim3(64), 0, st, noise, ws.Z, ws.LDQ, ws.LD, lengths, T, c0, nll_out, terms_out, z_out);
   return record_hip_error(h, "durnll_forward");
 }

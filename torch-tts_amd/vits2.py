@@ -970,8 +970,6 @@ class DurNllEngine(Handle):
         return (nll, terms, z) if parts else nll
 
 
-
-
 class _TokenOperandsMixin:
     """The reference's [B, C, T] / [B, 1, T] operands as the token-row kernels take them (duration predictors and discriminators)."""
 
@@ -1038,20 +1036,33 @@ class StochasticDurationPredictor(_DurationBase):
         self._nll_cfg = dict(in_channels=in_channels, kernel_size=kernel_size, n_flows=n_flows, gin_channels=gin_channels)
         self._nll_engines = EngineCache(DurNllEngine)
 
+    @staticmethod
+    def _trunk_tensors(pre, convs, proj, flows) -> List[torch.Tensor]:
+        """A conditioning path, then the ElementwiseAffine its flows open with."""
+        return [pre.weight, pre.bias] + convs.weight_tensors() + [proj.weight, proj.bias, flows[0].m, flows[0].logs]
+
+    @staticmethod
+    def _flow_tensors(flows, ks) -> List[torch.Tensor]:
+        """The ConvFlows flows.{2k+1} for k in ks."""
+        return [t for k in ks for t in flows[2 * k + 1].weight_tensors()]
+
+    def _cond_tensors(self) -> List[torch.Tensor]:
+        return [self.cond.weight, self.cond.bias] if self.gin_channels else []
+
     def nll_weight_tensors(self) -> List[torch.Tensor]:
         """ttsvits_durnll_pack_weights' order (include/ttsdec.h): every parameter of the module."""
-        def trunk(pre, convs, proj):
-            return [pre.weight, pre.bias] + convs.weight_tensors() + [proj.weight, proj.bias]
+        return (self._trunk_tensors(self.pre, self.convs, self.proj, self.flows) + self._flow_tensors(self.flows, range(self.n_flows))
+                + self._trunk_tensors(self.post_pre, self.post_convs, self.post_proj, self.post_flows)
+                + self._flow_tensors(self.post_flows, range(4)) + self._cond_tensors())
 
-        out = trunk(self.pre, self.convs, self.proj) + [self.flows[0].m, self.flows[0].logs]
-        for k in range(self.n_flows):
-            out += self.flows[2 * k + 1].weight_tensors()
-        out += trunk(self.post_pre, self.post_convs, self.post_proj) + [self.post_flows[0].m, self.post_flows[0].logs]
-        for k in range(4):
-            out += self.post_flows[2 * k + 1].weight_tensors()
-        if self.gin_channels:
-            out += [self.cond.weight, self.cond.bias]
-        return out
+    @staticmethod
+    def _noise(noise, B: int, T: int, device) -> torch.Tensor:
+        """The noise operand of either direction: the caller's, or the reference's draw (models.py:95-98, 129-132)."""
+        if noise is None:
+            noise = torch.randn(B, 2, T)  # drawn on the CPU generator, then moved
+        if tuple(noise.shape) != (B, 2, T):
+            raise ValueError(f"noise must be [B, 2, T] = [{B}, 2, {T}], got {tuple(noise.shape)}")
+        return noise.to(device=device, dtype=torch.float32).contiguous()
 
     def nll_cl(self, x_cl, lengths, w, g=None, *, noise=None, parts=False):
         """The likelihood on channel-last x [B, T, C] with lengths [B] and durations w [B, T] -> nll [B]; with ``parts`` also
@@ -1063,11 +1074,7 @@ class StochasticDurationPredictor(_DurationBase):
                                       f"{w.device}")
         if tuple(w.shape) != (B, T):
             raise ValueError(f"w must be [B, T] = [{B}, {T}], got {tuple(w.shape)}")
-        if noise is None:
-            noise = torch.randn(B, 2, T)  # models.py:95-98: drawn on the CPU generator, then moved
-        if tuple(noise.shape) != (B, 2, T):
-            raise ValueError(f"noise must be [B, 2, T] = [{B}, 2, {T}], got {tuple(noise.shape)}")
-        noise = noise.to(device=x_cl.device, dtype=torch.float32).contiguous()
+        noise = self._noise(noise, B, T, x_cl.device)
         eng = self._nll_engines.get(self._nll_cfg, x_cl.device)
         eng.ensure_packed(self.nll_weight_tensors())
         return eng.forward(x_cl.to(torch.float32).contiguous(), lengths.to(device=x_cl.device, dtype=torch.int32).contiguous(),
@@ -1081,24 +1088,15 @@ class StochasticDurationPredictor(_DurationBase):
         return self.nll_cl(self._channel_last(x), self._lengths(x_mask), w[:, 0], g, noise=noise)
 
     def weight_tensors(self) -> List[torch.Tensor]:
-        """ttsdur_pack_weights' order (include/ttsdec.h): the reverse path's parameters; flows.1 and post_* are not read."""
-        out = [self.pre.weight, self.pre.bias] + self.convs.weight_tensors() + [self.proj.weight, self.proj.bias]
-        out += [self.flows[0].m, self.flows[0].logs]
-        for k in range(1, self.n_flows):
-            out += self.flows[2 * k + 1].weight_tensors()
-        if self.gin_channels:
-            out += [self.cond.weight, self.cond.bias]
-        return out
+        """ttsdur_pack_weights' order (include/ttsdec.h): what the reverse pass reads, the main half without flows.1."""
+        return (self._trunk_tensors(self.pre, self.convs, self.proj, self.flows) + self._flow_tensors(self.flows, range(1, self.n_flows))
+                + self._cond_tensors())
 
     def logw_cl(self, x_cl, lengths, g=None, noise_scale=1.0, noise=None) -> torch.Tensor:
         """Reverse pass on channel-last x [B, T, C] with lengths [B] -> logw [B, T] (``infer`` chains it)."""
         self._check(x_cl)
         B, T, _ = x_cl.shape
-        if noise is None:
-            noise = torch.randn(B, 2, T)  # models.py:129-132: drawn on the CPU generator, then moved
-        if tuple(noise.shape) != (B, 2, T):
-            raise ValueError(f"noise must be [B, 2, T] = [{B}, 2, {T}], got {tuple(noise.shape)}")
-        noise = noise.to(device=x_cl.device, dtype=torch.float32).contiguous()
+        noise = self._noise(noise, B, T, x_cl.device)
         eng = self._engine(x_cl.device)
         return eng.logw(x_cl.to(torch.float32).contiguous(), lengths.to(device=x_cl.device, dtype=torch.int32).contiguous(),
                         self._speaker(g, B), noise, noise_scale)
