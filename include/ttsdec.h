@@ -50,7 +50,8 @@ extern "C" {
  * the generator with its arithmetic as a call argument; then ttsdec_resample_workspace_bytes and ttsdec_resample, sample-rate
  * conversion in front of ttsdec_mel_analysis; then ttsvits_disc_*, the waveform discriminators, a second handle kind under
  * ttsvits_ with a struct of its own; then ttsvits_durdisc_*, the duration discriminators, a third one; then ttsvits_durnll_*, the
- * stochastic duration predictor's likelihood, a fourth.) */
+ * stochastic duration predictor's likelihood, a fourth; then ttsvits_kl_loss_workspace_bytes, ttsvits_kl_loss,
+ * ttsvits_slice_segments and ttsvits_sliced_l1, the glue of the validation step.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -648,6 +649,47 @@ int ttsvits_spec_to_mel(ttsvits_handle* h, const float* spec, const int32_t* fra
 int ttsvits_mel_spectrogram(ttsvits_handle* h, const float* wav, const int32_t* lengths, int B, int N, const float* window, int n_fft, int hop_size,
                             int win_size, const float* mel_basis, int n_mels, float* mel, int T, int32_t* status, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* The glue of the validation step: what SynthesizerTrn.forward (models.py:1269-1276) and the trainer (train.py:357-373, 416-418) do
+ * between the encoders, the alignment, the generator and the loss terms - the prior expanded along the alignment, losses.kl_loss
+ * (losses.py:37-46), commons.slice_segments (commons.py:50-56) and F.l1_loss on a slice.  Weightless like the alignment calls: the
+ * handle (of any dims, bound or not) gives its device and its error text.  The calls enqueue only.  Exact fp32; every sum has a
+ * fixed order (no atomics), so a call repeats bit for bit and an utterance's own sum does not depend on the batch around it.
+ * Sizes are checked before any pointer: TTSDEC_ERR_INVALID_ARG for a size <= 0, TTSDEC_ERR_DIMS beyond the limits below, then NULL
+ * (or misaligned) pointers, then TTSDEC_ERR_WORKSPACE.  B <= 65535; tensors of up to 2^31 elements. */
+/* Scratch of one ttsvits_kl_loss call: one partial sum per frame (256-byte aligned); 0 for a NULL handle or a size <= 0. */
+size_t ttsvits_kl_loss_workspace_bytes(const ttsvits_handle* h, int B, int T_y);
+/* kl_loss(z_p, logs_q, m_p, logs_p, y_mask) with the prior still per token, in one pass over the four operands:
+ *   z_p, logs_q  [B, T_y, C] channel-last fp32, 16-byte aligned; C a multiple of 4 up to 4096 (as ttsvits_neg_cent)
+ *   m_p, logs_p  [B, T_x, C] channel-last, unexpanded
+ *   frame_token  [B, T_y] int32 as ttsvits_maximum_path writes it (-1: no token), or NULL: the prior is per frame already
+ *                (T_x == T_y, else TTSDEC_ERR_INVALID_ARG)
+ *   t_y          [B] int32 (device): frames of each utterance; frames at or past it do not count
+ *   m_p_exp, logs_p_exp   each NULL, or [B, T_y, C]: the token's row at every frame, exact zeros where a frame has no token -
+ *                what the reference's two matmuls by the one-hot path give (models.py:1270-1271); the losses never read them
+ *   kl_rows      [B]: each utterance's sum of logs_p - logs_q - 0.5 + 0.5 (z_p - m_p)^2 exp(-2 logs_p) over its t_y[b] x C elements
+ *   kl           [2]: the sum of kl_rows, and that sum / sum(t_y) - the reference's kl_loss (its divisor counts frames, not
+ *                frames x channels)
+ * Sums go per frame (one wave, lane order), then per utterance over its own t_y[b] frame sums, then over the batch. */
+int ttsvits_kl_loss(ttsvits_handle* h, const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, const int32_t* frame_token,
+                    const int32_t* t_y, int B, int T_y, int T_x, int C, float* m_p_exp, float* logs_p_exp, float* kl_rows, float* kl,
+                    void* workspace, size_t workspace_bytes, void* stream);
+/* commons.slice_segments as one launch with no host read: x is viewed as [B, outer, T, inner] fp32, ids is [B] int64 (ids_int64 != 0)
+ * or int32 (device), and out[b, o, t, i] = x[b, o, ids[b] * scale + t, i] for t < seg, out [B, outer, seg, inner].  The view serves a
+ * channel-last z (outer 1, inner C), a channel-first mel (outer n_mels, inner 1) and a waveform (outer = inner = 1, scale = hop).
+ * seg <= T (else TTSDEC_ERR_DIMS), scale >= 1.  16-byte loads are used only where inner is a multiple of 4 and x and out are 16-byte
+ * aligned; any alignment is accepted.
+ *   status  [1] int32 (device): 0, or 1 when some ids[b] * scale is below 0 or beyond T - seg (the reference raises a shape error
+ *           there); that utterance's slice is exact zeros. */
+int ttsvits_slice_segments(ttsvits_handle* h, const float* x, const void* ids, int ids_int64, int B, int outer, int T, int inner, int seg, int scale,
+                           float* out, int32_t* status, void* stream);
+/* F.l1_loss(slice_segments(a, ids, seg), y) without the slice in memory: a [B, C, T_a], y [B, C, seg] fp32, ids as above, or NULL:
+ * plain L1 of two tensors of one shape (seg == T_a, else TTSDEC_ERR_INVALID_ARG).
+ *   l1_rows [B]: each utterance's sum of |a[b, c, ids[b] + t] - y[b, c, t]| over its C x seg elements
+ *   l1      [2]: the sum of l1_rows, and that sum / (B C seg) - the reference's mean
+ *   status  as for ttsvits_slice_segments (an utterance out of range counts as a slice of zeros) */
+int ttsvits_sliced_l1(ttsvits_handle* h, const float* a, const float* y, const void* ids, int ids_int64, int B, int C, int T_a, int seg,
+                      float* l1_rows, float* l1, int32_t* status, void* stream);
 
 /* Mel -> waveform for the Tacotron path: the reference's tacotron/inference.py:13-22 (synth_audio) with AudioFrontend.mel_inv /
  * .decode (tacotron/data/audio.py:69-76) and m_rev (tacotron/data/dataset.py:183-184) - torchaudio's InverseMelScale,

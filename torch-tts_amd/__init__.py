@@ -10,7 +10,8 @@ from .postnet import Conv1dFix, MelPostnet, MelPostnet2
 from .style import GST, GST_VAE, STL, VAE, MultiHeadAttention, ReferenceEncoder, StyleEngine
 from .tacotron import Encoder2, Tacotron, build_tacotron, lengths_to_mask
 from . import vits2  # noqa: F401  (TextEncoder, ResidualCouplingTransformersBlock, Generator, StochasticDurationPredictor, DurationPredictor, infer,
-#                             PosteriorEncoder, voice_conversion)
+#                             PosteriorEncoder, voice_conversion, forced_alignment, duration_loss, synthesizer_forward, validation_losses,
+#                             kl_loss, slice_segments, rand_slice_segments)
 from .vits2 import (DiscriminatorP, DiscriminatorS, DurationDiscriminatorV1, DurationDiscriminatorV2, DurationPredictor, Generator,
                     MultiPeriodDiscriminator, PosteriorEncoder, StochasticDurationPredictor)
 from . import audio  # noqa: F401  (AudioFrontend.mel_inv / decode, m_rev, synth_audio)

@@ -228,6 +228,11 @@ FAMILIES = (
         "spectrogram": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
         "spec_to_mel": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
         "mel_spectrogram": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, sz, vp]),
+        # the validation step's glue (csrc/evalstep.hip)
+        "kl_loss_workspace_bytes": _ws_bytes,  # (h, B, T_y)
+        "kl_loss": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),  # h, z_p, logs_q, m_p, logs_p, frame_token, t_y, B, T_y, T_x, C, m_p_exp, logs_p_exp, kl_rows, kl, ws, bytes, stream
+        "slice_segments": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),  # h, x, ids, ids_int64, B, outer, T, inner, seg, scale, out, status, stream
+        "sliced_l1": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),  # h, a, y, ids, ids_int64, B, C, T_a, seg, l1_rows, l1, status, stream
         # the generator with its arithmetic as a call argument: these take a ttsgen handle (vits2.GenEngine)
         "generator_planes_bytes": (sz, [vp]),
         "generator_pack_planes": (i32, [vp, vp, vp]),  # gen, planes, stream

@@ -32,6 +32,10 @@
                                              feeds and gets from them
 * ``duration_loss(net_g, x, ..., y, ...)`` - SynthesizerTrn.forward up to ``l_length`` (models.py:1214-1267), the VL/dur of the
                                              reference's validation, and ``duration_loss_from_audio``
+* ``synthesizer_forward(net_g, x, ..., y, ...)`` - SynthesizerTrn.forward as a whole (models.py:1214-1286) in eval mode: its eight results
+* ``validation_losses(net_g, net_d, ...)`` - the loss terms of train.py:341-425, forward only, and ``validation_losses_from_audio``;
+                                             ``kl_loss`` (losses.py:37-46), ``slice_segments`` / ``rand_slice_segments`` (commons.py:50-66)
+                                             (``ttsvits_kl_loss`` / ``ttsvits_slice_segments`` / ``ttsvits_sliced_l1``)
 
 All hold the reference's parameters (so checkpoints load) and run inference through the HIP library
 (``ttsvits_*`` / ``ttsgen_*`` / ``ttsdur_*`` / ``ttspost_*`` in include/ttsdec.h).  The library works on channel-last activations;
@@ -217,10 +221,12 @@ class VitsEngine(Handle):
         return out
 
     def maximum_path(self, neg_cent: torch.Tensor, t_y: torch.Tensor, t_x: torch.Tensor, dtype: Optional[torch.dtype] = torch.float32,
-                     z_p=None, m_p=None, logs_p=None):
+                     z_p=None, m_p=None, logs_p=None, also=None):
         """neg_cent [B, T_y, T_x] contiguous fp32, t_y / t_x [B] int32 (device) -> path [B, T_y, T_x] of ``dtype`` (None: not
         written), frame_token [B, T_y] int32, dur [B, T_x] int32 (include/ttsdec.h ttsvits_maximum_path).  With z_p, m_p, logs_p given,
-        neg_cent is an output buffer and the call is ttsvits_align.  Reads the status word back: the call's one host sync."""
+        neg_cent is an output buffer and the call is ttsvits_align.  Reads the status word back: the call's one host sync.
+        ``also``: (flag, message) - a device flag [1] int32 of the caller's, read in the same transfer; ValueError(message) when it
+        is set and the search itself refused nothing."""
         B, T_y, T_x = neg_cent.shape
         if T_x > _lib.ALIGN_MAX_TX:
             raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsvits_maximum_path", f"T_x = {T_x} tokens: the search is built for up to {_lib.ALIGN_MAX_TX}")
@@ -239,13 +245,18 @@ class VitsEngine(Handle):
                                           self._PATH_DTYPES[kdt], ft.data_ptr(), dur.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
                                           _stream(self.device))
         self._err(rc, name)
-        flags = int(status.item())
+        if also is None:
+            flags, more = int(status.item()), 0
+        else:
+            flags, more = torch.cat([status, also[0].to(torch.int32).reshape(1)]).tolist()
         if flags & 4:
             raise ValueError(f"an utterance's length from the mask exceeds the tensor [T_y, T_x] = [{T_y}, {T_x}]")
         if flags & 1:
             raise ValueError("an utterance has no frames or no tokens (t_y < 1 or t_x < 1): monotonic alignment search is undefined")
         if flags & 2:
             raise ValueError("an utterance has fewer frames than tokens (t_y < t_x): no monotonic path gives every token a frame")
+        if more:
+            raise ValueError(also[1])
         if path is not None and path.dtype != dtype:
             path = path.to(dtype)
         return path, ft, dur
@@ -294,6 +305,54 @@ class VitsEngine(Handle):
                                                mel_basis.data_ptr(), n_mels, mel.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
         self._err(rc, "ttsvits_spec_to_mel")
         return mel
+
+    # ---- the validation step's glue (weightless; csrc/evalstep.hip) ----
+    def kl_loss(self, z_p, logs_q, m_p, logs_p, frame_token: Optional[torch.Tensor], t_y: torch.Tensor, expand: bool = False):
+        """z_p, logs_q [B, T_y, C], m_p, logs_p [B, T_x, C] contiguous fp32 channel-last, frame_token [B, T_y] int32 or None (the
+        prior is per frame), t_y [B] int32 (device) -> (kl [2]: the sum and the reference's kl_loss, kl_rows [B], m_p_exp,
+        logs_p_exp [B, T_y, C] or None, None without ``expand``) (include/ttsdec.h ttsvits_kl_loss).  No host read."""
+        B, T_y, Cc = z_p.shape
+        T_x = m_p.shape[1]
+        nbytes = int(self._lib.ttsvits_kl_loss_workspace_bytes(self._h, B, T_y))
+        if not nbytes:
+            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsvits_kl_loss", f"B = {B}, T_y = {T_y}: more than 65535 utterances or 2^31 frames")
+        ws = self.workspace("kl", nbytes)
+        kl = torch.empty(2, device=self.device)
+        rows = torch.empty(B, device=self.device)
+        m_exp = torch.empty(B, T_y, Cc, device=self.device) if expand else None
+        logs_exp = torch.empty(B, T_y, Cc, device=self.device) if expand else None
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsvits_kl_loss(self._h, z_p.data_ptr(), logs_q.data_ptr(), m_p.data_ptr(), logs_p.data_ptr(), _ptr(frame_token),
+                                          t_y.data_ptr(), B, T_y, T_x, Cc, _ptr(m_exp), _ptr(logs_exp), rows.data_ptr(), kl.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), _stream(self.device))
+        self._err(rc, "ttsvits_kl_loss")
+        return kl, rows, m_exp, logs_exp
+
+    def slice_segments(self, x: torch.Tensor, ids: torch.Tensor, outer: int, T: int, inner: int, seg: int, scale: int = 1):
+        """x contiguous fp32 viewed as [B, outer, T, inner], ids [B] int64 / int32 (device) -> (out [B, outer, seg, inner] flat as
+        [B, outer * seg * inner], status [1] int32 on the device: 1 = a start outside [0, T - seg], that slice zeros)
+        (ttsvits_slice_segments).  No host read."""
+        B = x.shape[0]
+        out = torch.empty(B, outer * seg * inner, device=self.device)
+        status = torch.empty(1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsvits_slice_segments(self._h, x.data_ptr(), ids.data_ptr(), int(ids.dtype == torch.int64), B, outer, T, inner, seg, scale,
+                                                 out.data_ptr(), status.data_ptr(), _stream(self.device))
+        self._err(rc, "ttsvits_slice_segments")
+        return out, status
+
+    def sliced_l1(self, a: torch.Tensor, y: torch.Tensor, ids: Optional[torch.Tensor]):
+        """a [B, C, T_a], y [B, C, seg] contiguous fp32, ids [B] int64 / int32 (device) or None (seg == T_a) -> (l1 [2]: the sum
+        of |a[b, c, ids[b] + t] - y[b, c, t]| and its mean, l1_rows [B], status [1]) (ttsvits_sliced_l1).  No host read."""
+        B, Cc, T_a = a.shape
+        l1 = torch.empty(2, device=self.device)
+        rows = torch.empty(B, device=self.device)
+        status = torch.empty(1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsvits_sliced_l1(self._h, a.data_ptr(), y.data_ptr(), _ptr(ids), int(ids is not None and ids.dtype == torch.int64), B, Cc,
+                                            T_a, y.shape[2], rows.data_ptr(), l1.data_ptr(), status.data_ptr(), _stream(self.device))
+        self._err(rc, "ttsvits_sliced_l1")
+        return l1, rows, status
 
 
 _DEFAULT_FLOW = dict(flow_hidden=4, flow_kernel=1, flow_wn_layers=1, n_flows=0, flow_tf_layers=0, flow_tf_heads=1, flow_tf_kernel=1)
@@ -1473,13 +1532,14 @@ def maximum_path(neg_cent, mask):
     return eng.maximum_path(neg_cent.detach().to(torch.float32).contiguous(), t_y, t_x, neg_cent.dtype)[0]
 
 
-def _align_cl(eng: VitsEngine, z_cl, m_cl, logs_cl, t_y, t_x, mas_noise_scale=None, noise=None):
-    """neg_cent and the search on channel-last operands -> (path [B, T_y, T_x] fp32, frame_token, dur, neg_cent)."""
+def _align_cl(eng: VitsEngine, z_cl, m_cl, logs_cl, t_y, t_x, mas_noise_scale=None, noise=None, also=None):
+    """neg_cent and the search on channel-last operands -> (path [B, T_y, T_x] fp32, frame_token, dur, neg_cent).  also: see
+    VitsEngine.maximum_path."""
     z_cl, m_cl, logs_cl = (t.detach().to(torch.float32).contiguous() for t in (z_cl, m_cl, logs_cl))
     if mas_noise_scale is None:
         B, T_y, _ = z_cl.shape
         nc = torch.empty(B, T_y, m_cl.shape[1], device=z_cl.device)
-        path, ft, dur = eng.maximum_path(nc, t_y, t_x, torch.float32, z_cl, m_cl, logs_cl)
+        path, ft, dur = eng.maximum_path(nc, t_y, t_x, torch.float32, z_cl, m_cl, logs_cl, also=also)
         return path, ft, dur, nc
     # models.py:1241-1247 on the unmasked cost matrix, as the reference computes it
     nc = eng.neg_cent(z_cl, m_cl, logs_cl, None, None)
@@ -1488,7 +1548,7 @@ def _align_cl(eng: VitsEngine, z_cl, m_cl, logs_cl, t_y, t_x, mas_noise_scale=No
     if tuple(noise.shape) != tuple(nc.shape):
         raise ValueError(f"noise must be [B, T_y, T_x] = {tuple(nc.shape)}, got {tuple(noise.shape)}")
     nc = (nc + torch.std(nc) * noise.to(device=nc.device, dtype=torch.float32) * mas_noise_scale).contiguous()
-    path, ft, dur = eng.maximum_path(nc, t_y, t_x, torch.float32)
+    path, ft, dur = eng.maximum_path(nc, t_y, t_x, torch.float32, also=also)
     return path, ft, dur, nc
 
 
@@ -1522,6 +1582,18 @@ def forced_alignment(net_g, x, x_lengths, y, y_lengths, sid=None, *, mas_noise_s
 def _forced_alignment(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, noise, more_parts, caller):
     """forced_alignment's body -> its four results, then what ``duration_discriminator_scores`` goes on with: the text encoder's
     x channel-last [B, T_x, H], t_x [B] int32, x_mask [B, 1, T_x] and g.  more_parts: further drop-ins of net_g the caller needs."""
+    p = _alignment_parts(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, noise, more_parts, caller)
+    zs = (p.z_cl.transpose(1, 2), p.zp_cl.transpose(1, 2), p.m_cl.transpose(1, 2), p.logs_cl.transpose(1, 2))
+    return p.attn, p.w, p.logw_, zs, p.xs, p.t_x, p.x_mask, p.g
+
+
+def _alignment_parts(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, noise, more_parts, caller, also=None):
+    """The encoders, the flow and the search, channel-last -> a namespace of everything they computed: attn [B, 1, T_y, T_x], w,
+    logw_, x_mask, g, t_x, t_y, frame_token ``ft`` [B, T_y] int32, the weightless engine ``eng``, and channel-last xs [B, T_x, H],
+    m_cl / logs_cl [B, T_x, inter] (the unexpanded prior), z_cl / zp_cl / mq_cl / logsq_cl [B, T_y, inter].  also: see
+    VitsEngine.maximum_path."""
+    from types import SimpleNamespace
+
     parts = {"enc_p": TextEncoder, "enc_q": PosteriorEncoder, "flow": ResidualCouplingTransformersBlock, **more_parts}
     for name, cls in parts.items():
         mod = getattr(net_g, name, None)
@@ -1536,15 +1608,15 @@ def _forced_alignment(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, n
     t_x = x_lengths.to(device=dev, dtype=torch.int32).contiguous()
     t_y = y_lengths.to(device=dev, dtype=torch.int32).contiguous()
     xs, m_cl, logs_cl = enc_p.forward_cl(x, t_x, g=g if enc_p.gin_channels else None)
-    z_cl, _, _ = enc_q.forward_cl(y, t_y, g=g, noise=e_q)
+    z_cl, mq_cl, logsq_cl = enc_q.forward_cl(y, t_y, g=g, noise=e_q)
     zp_cl = flow.forward_cl(z_cl, t_y, g)
     eng = flow._engines.get(flow._dims(), dev)  # (the flow's own handle: the calls are weightless)
-    path, _, dur, _ = _align_cl(eng, zp_cl, m_cl, logs_cl, t_y, t_x, mas_noise_scale, e_mas)
+    path, ft, dur, _ = _align_cl(eng, zp_cl, m_cl, logs_cl, t_y, t_x, mas_noise_scale, e_mas, also)
     w = dur.to(torch.float32).unsqueeze(1)
     x_mask = (torch.arange(x.shape[1], device=dev)[None, :] < t_x[:, None]).unsqueeze(1).to(torch.float32)
     logw_ = torch.log(w + 1e-6) * x_mask
-    zs = (z_cl.transpose(1, 2), zp_cl.transpose(1, 2), m_cl.transpose(1, 2), logs_cl.transpose(1, 2))
-    return path.unsqueeze(1), w, logw_, zs, xs, t_x, x_mask, g
+    return SimpleNamespace(attn=path.unsqueeze(1), w=w, logw_=logw_, xs=xs, t_x=t_x, t_y=t_y, x_mask=x_mask, g=g, ft=ft, eng=eng, m_cl=m_cl,
+                           logs_cl=logs_cl, z_cl=z_cl, zp_cl=zp_cl, mq_cl=mq_cl, logsq_cl=logsq_cl)
 
 
 def duration_discriminator_scores(net_g, net_dur_disc, x, x_lengths, y, y_lengths, sid=None, *, noise_scale_w=1.0, mas_noise_scale=None,
@@ -1584,7 +1656,12 @@ def duration_loss(net_g, x, x_lengths, y, y_lengths, sid=None, *, mas_noise_scal
     e_fa, e_q, e_w = noise if noise is not None else (None, None, None)
     attn, w, logw_, _, xs, t_x, x_mask, g = _forced_alignment(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, e_fa,
                                                               {"dp": (StochasticDurationPredictor, DurationPredictor)}, "vits2.duration_loss")
-    dp = net_g.dp
+    l_length, logw = _duration_terms(net_g.dp, xs, t_x, x_mask, w, logw_, g, e_q, e_w)
+    return l_length, attn, x_mask, (xs.transpose(1, 2), logw, logw_)
+
+
+def _duration_terms(dp, xs, t_x, x_mask, w, logw_, g, e_q, e_w):
+    """models.py:1257-1267 on the alignment's w and logw_ -> (l_length [B], logw [B, 1, T_x])."""
     n_tokens = torch.sum(x_mask)
     if isinstance(dp, StochasticDurationPredictor):
         l_length = dp.nll_cl(xs, t_x, w[:, 0], g, noise=e_q) / n_tokens
@@ -1592,7 +1669,7 @@ def duration_loss(net_g, x, x_lengths, y, y_lengths, sid=None, *, mas_noise_scal
     else:
         logw = dp.logw_cl(xs, t_x, g).unsqueeze(1)
         l_length = torch.sum((logw - logw_) ** 2, [1, 2]) / n_tokens
-    return l_length, attn, x_mask, (xs.transpose(1, 2), logw, logw_)
+    return l_length, logw
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1637,3 +1714,214 @@ def duration_loss_from_audio(net_g, x, x_lengths, wav, wav_lengths, sid=None, *,
     """``duration_loss`` from waveforms (see voice_conversion_from_audio)."""
     y, y_lengths = _spec_from_audio(net_g, wav, wav_lengths, n_fft, hop_size, win_size, sampling_rate, n_mels, fmin, fmax, mel_basis)
     return duration_loss(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale=mas_noise_scale, noise=noise)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The validation step (SynthesizerTrn.forward as a whole, models.py:1214-1286, and the forward half of train.py:341-425): the prior
+# expanded along the alignment, kl_loss, slice_segments and the mel L1 through ttsvits_kl_loss / ttsvits_slice_segments /
+# ttsvits_sliced_l1 (csrc/evalstep.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+_WEIGHTLESS = nn.Module()  # inference_only's rules for the functions that hold no parameters
+
+
+def _fp32_operands(owner: str, **tensors) -> None:
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{owner}: {name} must be a tensor, got {type(t).__name__}")
+        inference_only(_WEIGHTLESS, owner, t, fp32=True)
+
+
+def _prefix_lengths(mask: torch.Tensor, B: int, T: int, owner: str) -> torch.Tensor:
+    """t [B] int32 of a [B, 1, T] mask of ones up to each utterance's length and zeros from there; ValueError for any other mask (the
+    kernels take lengths).  One host read."""
+    if mask.dim() != 3 or tuple(mask.shape) != (B, 1, T):
+        raise ValueError(f"{owner}: the mask must be [B, 1, T] = [{B}, 1, {T}], got {tuple(mask.shape)}")
+    m = mask[:, 0, :]
+    t = (m != 0).sum(1)
+    prefix = (torch.arange(T, device=mask.device)[None, :] < t[:, None]).to(m.dtype)
+    if not bool(torch.equal(m, prefix)):
+        raise ValueError(f"{owner}: the mask is not a prefix mask (ones up to each utterance's length, zeros from there)")
+    return t.to(torch.int32).contiguous()
+
+
+def kl_loss(z_p, logs_q, m_p, logs_p, z_mask):
+    """losses.kl_loss (losses.py:37-46): z_p, logs_q, m_p, logs_p [B, C, T] fp32 on a ROCm device, z_mask [B, 1, T] a prefix mask ->
+    sum((logs_p - logs_q - 0.5 + 0.5 (z_p - m_p)^2 exp(-2 logs_p)) * z_mask) / sum(z_mask), a 0-dim tensor, in one pass of
+    ttsvits_kl_loss.  C a multiple of 4.  The one host read checks the mask."""
+    _fp32_operands("kl_loss", z_p=z_p, logs_q=logs_q, m_p=m_p, logs_p=logs_p, z_mask=z_mask)
+    if z_p.dim() != 3 or not (z_p.shape == logs_q.shape == m_p.shape == logs_p.shape) or z_p.shape[1] % 4:
+        raise ValueError(f"z_p, logs_q, m_p and logs_p must be [B, C, T] of one shape with C a multiple of 4, got {tuple(z_p.shape)}, "
+                         f"{tuple(logs_q.shape)}, {tuple(m_p.shape)}, {tuple(logs_p.shape)}")
+    B, _, T = z_p.shape
+    t_y = _prefix_lengths(z_mask, B, T, "kl_loss")
+    cl = _DurationBase._channel_last
+    kl, _, _, _ = _align_engine(z_p.device).kl_loss(cl(z_p.detach()), cl(logs_q.detach()), cl(m_p.detach()), cl(logs_p.detach()), None, t_y)
+    return kl[1]
+
+
+def _check_slice(x, segment_size: int, owner: str) -> None:
+    _fp32_operands(owner, x=x)
+    if x.dim() != 3:
+        raise ValueError(f"{owner}: x must be [B, C, T], got {tuple(x.shape)}")
+    if not 1 <= int(segment_size) <= x.shape[2]:
+        raise ValueError(f"{owner}: segment_size = {segment_size} outside [1, T] = [1, {x.shape[2]}]")
+
+
+def _ids_on(ids, B: int, device, owner: str) -> torch.Tensor:
+    ids = torch.as_tensor(ids).to(device)
+    if tuple(ids.shape) != (B,) or ids.dtype.is_floating_point:
+        raise ValueError(f"{owner}: ids_str must be [B] = [{B}] integers, got {tuple(ids.shape)} {ids.dtype}")
+    return (ids if ids.dtype in (torch.int64, torch.int32) else ids.to(torch.int64)).contiguous()
+
+
+def slice_segments(x, ids_str, segment_size=4):
+    """commons.slice_segments (commons.py:50-56): x [B, C, T] fp32 on a ROCm device, ids_str [B] integers -> x[b, :, ids_str[b] :
+    ids_str[b] + segment_size] as [B, C, segment_size], in one launch of ttsvits_slice_segments.  A start below 0 or beyond
+    T - segment_size, where the reference raises a shape error, is a ValueError here: the one host read is that status word."""
+    _check_slice(x, segment_size, "slice_segments")
+    B, Cc, T = x.shape
+    ids = _ids_on(ids_str, B, x.device, "slice_segments")
+    out, status = _align_engine(x.device).slice_segments(x.detach().contiguous(), ids, Cc, T, 1, int(segment_size))
+    if int(status.item()):
+        raise ValueError(f"slice_segments: a start in ids_str lies outside [0, T - segment_size] = [0, {T - int(segment_size)}]")
+    return out.view(B, Cc, int(segment_size))
+
+
+def rand_slice_segments(x, x_lengths=None, segment_size=4, *, u=None):
+    """commons.rand_slice_segments (commons.py:59-66) -> (slices [B, C, segment_size], ids_str [B] int64): ids_str = (u * (x_lengths -
+    segment_size + 1)).long() with u = torch.rand([B]), the reference's draw; ``u`` (keyword, test hook) replaces it.  An utterance
+    shorter than segment_size - 1 can draw a negative start: ValueError (see slice_segments)."""
+    _check_slice(x, segment_size, "rand_slice_segments")
+    B, _, T = x.shape
+    ids_str = _draw_ids(B, T if x_lengths is None else x_lengths, int(segment_size), x.device, u)
+    return slice_segments(x, ids_str, segment_size), ids_str
+
+
+def _draw_ids(B: int, lengths, seg: int, device, u=None) -> torch.Tensor:
+    """commons.py:63-64: the start of every utterance's segment, [B] int64 on the device."""
+    if u is None:
+        u = torch.rand([B])
+    u = torch.as_tensor(u, dtype=torch.float32).to(device)
+    if tuple(u.shape) != (B,):
+        raise ValueError(f"u must be [B] = [{B}], got {tuple(u.shape)}")
+    ids_str_max = (lengths.to(device) if isinstance(lengths, torch.Tensor) else lengths) - seg + 1
+    return (u * ids_str_max).to(dtype=torch.long)
+
+
+def _synthesizer_parts(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, noise, ids_slice, expand, caller, wav_limit=None):
+    """SynthesizerTrn.forward on the drop-ins, channel-last from the encoders to the generator -> (the alignment's namespace with
+    l_length, logw, ids_slice, o [B, 1, seg * hop], kl [2] / m_exp / logs_exp of ttsvits_kl_loss added).  expand: write the
+    expanded prior.  wav_limit: (samples of the waveform tensor, hop, samples of a segment) - the waveform's slice is checked
+    with the latent's.  The start of every slice is checked on the device and read with the alignment's status word."""
+    if noise is not None and not (isinstance(noise, (tuple, list)) and len(noise) == 3):
+        raise ValueError("noise must be a triple: (forced_alignment's noise, the likelihood's draw [B, 2, T_x] or None, the reverse pass's "
+                         "draw [B, 2, T_x] or None)")
+    e_fa, e_q, e_w = noise if noise is not None else (None, None, None)
+    for name, cls in {"dp": (StochasticDurationPredictor, DurationPredictor), "dec": Generator}.items():  # (before any device work)
+        if not isinstance(getattr(net_g, name, None), cls):
+            raise TypeError(f"net_g.{name} is {type(getattr(net_g, name, None)).__name__}, not the HIP drop-in: swap it in (INTEGRATION.md) - "
+                            "there is no fallback")
+    if not x.is_cuda or not y.is_cuda:
+        raise NotImplementedError(f"{caller} runs on a ROCm device only: move the model, the ids and the spectrogram there")
+    seg = int(net_g.segment_size)
+    B, _, T_y = y.shape
+    if not 1 <= seg <= T_y:
+        raise ValueError(f"{caller}: net_g.segment_size = {seg} frames outside [1, T_y] = [1, {T_y}]")
+    dev = y.device
+    ids = _draw_ids(B, y_lengths, seg, dev) if ids_slice is None else _ids_on(ids_slice, B, dev, caller).to(torch.int64)
+    bad = (ids < 0) | (ids > T_y - seg)
+    if wav_limit is not None:
+        n_wav, hop, seg_wav = wav_limit
+        bad = bad | (ids * hop > n_wav - seg_wav)
+    also = (bad.any().to(torch.int32).reshape(1),
+            f"{caller}: a segment starts outside its tensor (start < 0 - an utterance shorter than the segment - or start + segment beyond "
+            "the frames or the samples)")
+    p = _alignment_parts(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, e_fa,
+                         {"dp": (StochasticDurationPredictor, DurationPredictor), "dec": Generator}, caller, also)
+    p.l_length, p.logw = _duration_terms(net_g.dp, p.xs, p.t_x, p.x_mask, p.w, p.logw_, p.g, e_q, e_w)
+    p.kl, _, p.m_exp, p.logs_exp = p.eng.kl_loss(p.zp_cl, p.logsq_cl, p.m_cl, p.logs_cl, p.ft, p.t_y, expand)
+    Cc = p.z_cl.shape[2]
+    z_slice, _ = p.eng.slice_segments(p.z_cl, ids, 1, T_y, Cc, seg)
+    p.o = net_g.dec.forward_cl(z_slice.view(B, seg, Cc), p.g).unsqueeze(1)
+    p.ids_slice = ids
+    p.y_mask = (torch.arange(T_y, device=dev)[None, :] < p.t_y[:, None]).unsqueeze(1).to(torch.float32)
+    return p
+
+
+def synthesizer_forward(net_g, x, x_lengths, y, y_lengths, sid=None, *, mas_noise_scale=None, noise=None, ids_slice=None):
+    """SynthesizerTrn.forward (models.py:1214-1286) in eval mode for a model whose enc_p / enc_q / flow / dp / dec are this module's
+    drop-ins: x [B, T_x] ids, y [B, spec, T_y] -> the reference's eight results (o [B, 1, segment_size * hop], l_length [B], attn
+    [B, 1, T_y, T_x], ids_slice [B] int64, x_mask, y_mask, (z, z_p, m_p, logs_p, m_q, logs_q) [B, inter, T_y] with the prior
+    expanded along the alignment, (x [B, H, T_x], logw, logw_ [B, 1, T_x])).  ``net_g.segment_size`` is in frames.  Channel-last
+    from the encoders to the generator; the prior is gathered through the search's frame_token (ttsvits_kl_loss), the latent's
+    segment is one launch (ttsvits_slice_segments).  The one host read is the alignment's status word, which also carries the
+    check of the segment starts (ValueError).  ``noise`` (test hook): duration_loss's triple; ``ids_slice`` (test hook)
+    replaces the draw (torch.rand([B]) * (y_lengths - segment_size + 1)).long()."""
+    p = _synthesizer_parts(net_g, x, x_lengths, y, y_lengths, sid, mas_noise_scale, noise, ids_slice, True, "vits2.synthesizer_forward")
+    tr = lambda t: t.transpose(1, 2)  # noqa: E731
+    return (p.o, p.l_length, p.attn, p.ids_slice, p.x_mask, p.y_mask,
+            (tr(p.z_cl), tr(p.zp_cl), tr(p.m_exp), tr(p.logs_exp), tr(p.mq_cl), tr(p.logsq_cl)), (tr(p.xs), p.logw, p.logw_))
+
+
+def validation_losses(net_g, net_d, x, x_lengths, spec, spec_lengths, wav, *, n_fft, hop_size, win_size, sampling_rate, n_mels, fmin=0.0,
+                      fmax=None, mel_basis=None, segment_size, c_mel=10.0, c_kl=0.2, net_dur_disc=None, sid=None, mas_noise_scale=None,
+                      noise=None, ids_slice=None):
+    """The loss terms of one batch, train.py:341-425 forward only, in eval mode and without gradients: x [B, T_x] ids, spec
+    [B, spec, T_y] what net_g.enc_q reads, wav [B, 1, N] -> a dict of 0-dim device tensors ``loss_disc``, ``loss_gen``, ``loss_fm``,
+    ``loss_mel`` (x c_mel), ``loss_dur``, ``loss_kl`` (x c_kl), ``loss_gen_all`` = loss_gen + loss_fm + loss_mel + loss_dur +
+    loss_kl (+ loss_dur_gen), with ``net_dur_disc`` also ``loss_dur_disc`` and ``loss_dur_gen``, and ``ids_slice`` [B].
+    ``segment_size`` is in samples and must be net_g.segment_size * hop_size; c_mel / c_kl default to the reference's ModelConfig
+    (cli.py: 10.0, 0.2).  mel is spec when net_g.enc_q reads n_mels channels, else spec_to_mel_torch(spec); loss_mel is the L1 of
+    its segment against mel_spectrogram_torch(o) without the segment in memory (ttsvits_sliced_l1); loss_kl comes from the
+    unexpanded prior and the search's frame_token (ttsvits_kl_loss); the waveform's segment is one launch.  The one host read is
+    the alignment's status word.  ``noise`` / ``ids_slice``: see synthesizer_forward."""
+    if not isinstance(net_d, MultiPeriodDiscriminator):
+        raise TypeError(f"net_d is {type(net_d).__name__}, not the HIP drop-in: swap it in (INTEGRATION.md) - there is no fallback")
+    if net_dur_disc is not None and not isinstance(net_dur_disc, _DurationDiscriminatorBase):
+        raise TypeError(f"net_dur_disc is {type(net_dur_disc).__name__}, not the HIP drop-in: swap it in (INTEGRATION.md) - there is no fallback")
+    enc_q = getattr(net_g, "enc_q", None)
+    if not isinstance(enc_q, PosteriorEncoder):
+        raise TypeError(f"net_g.enc_q is {type(enc_q).__name__}, not the HIP drop-in: swap it in (INTEGRATION.md) - there is no fallback")
+    _fp32_operands("vits2.validation_losses", spec=spec, wav=wav)
+    if wav.dim() != 3 or wav.shape[1] != 1 or wav.shape[0] != spec.shape[0]:
+        raise ValueError(f"wav must be [B, 1, N] = [{spec.shape[0]}, 1, N], got {tuple(wav.shape)}")
+    seg_frames = int(getattr(net_g, "segment_size", 0))
+    if int(segment_size) != seg_frames * int(hop_size):
+        raise ValueError(f"segment_size = {segment_size} samples is not net_g.segment_size * hop_size = {seg_frames} * {hop_size}")
+    B, _, N = wav.shape
+    if not 1 <= int(segment_size) <= N:
+        raise ValueError(f"segment_size = {segment_size} samples outside [1, N] = [1, {N}]")
+    mel = spec if enc_q.in_channels == n_mels else spec_to_mel_torch(spec, n_fft, n_mels, sampling_rate, fmin, fmax, mel_basis=mel_basis)
+    p = _synthesizer_parts(net_g, x, x_lengths, spec, spec_lengths, sid, mas_noise_scale, noise, ids_slice, False, "vits2.validation_losses",
+                           (N, int(hop_size), int(segment_size)))
+    y_hat_mel = mel_spectrogram_torch(p.o.squeeze(1), n_fft, n_mels, sampling_rate, hop_size, win_size, fmin, fmax, mel_basis=mel_basis)
+    if y_hat_mel.shape[2] != seg_frames:
+        raise ValueError(f"the mel of a generated segment has {y_hat_mel.shape[2]} frames, the segment {seg_frames}: n_fft, hop_size and "
+                         "segment_size do not fit (the reference's F.l1_loss fails there too)")
+    l1, _, _ = p.eng.sliced_l1(mel.detach().contiguous(), y_hat_mel.contiguous(), p.ids_slice)
+    y, _ = p.eng.slice_segments(wav.detach().contiguous(), p.ids_slice, 1, N, 1, int(segment_size), int(hop_size))
+    y_d_hat_r, y_d_hat_g, fmap_r, fmap_g = net_d(y.view(B, 1, int(segment_size)), p.o)
+    r_losses, g_losses = discriminator_loss(y_d_hat_r, y_d_hat_g)
+    out = {"loss_disc": r_losses.sum() + g_losses.sum(), "loss_gen": generator_loss(y_d_hat_g).sum(), "loss_fm": feature_loss(fmap_r, fmap_g),
+           "loss_mel": l1[1] * c_mel, "loss_dur": torch.sum(p.l_length.float()), "loss_kl": p.kl[1] * c_kl}
+    out["loss_gen_all"] = out["loss_gen"] + out["loss_fm"] + out["loss_mel"] + out["loss_dur"] + out["loss_kl"]
+    if net_dur_disc is not None:
+        as_list = lambda v: [v] if isinstance(v, torch.Tensor) else v  # noqa: E731  (V1 returns tensors, V2 lists: train.py wraps them)
+        y_dur_hat_r, y_dur_hat_g = net_dur_disc(p.xs.transpose(1, 2), p.x_mask, p.logw_, p.logw)
+        dr, dg = discriminator_loss(as_list(y_dur_hat_r), as_list(y_dur_hat_g))
+        out["loss_dur_disc"] = dr.sum() + dg.sum()
+        out["loss_dur_gen"] = generator_loss(as_list(y_dur_hat_g)).sum()
+        out["loss_gen_all"] = out["loss_gen_all"] + out["loss_dur_gen"]
+    out["ids_slice"] = p.ids_slice
+    return out
+
+
+def validation_losses_from_audio(net_g, net_d, x, x_lengths, wav, wav_lengths, *, n_fft, hop_size, win_size, sampling_rate, n_mels, fmin=0.0,
+                                 fmax=None, mel_basis=None, segment_size, **kwargs):
+    """``validation_losses`` with the spectrogram made from wav [B, 1, N] (or [B, N]) and wav_lengths [B] samples, as the
+    reference's data loader would have (see voice_conversion_from_audio); the keywords are validation_losses'."""
+    wav2 = wav[:, 0] if wav.dim() == 3 else wav
+    spec, spec_lengths = _spec_from_audio(net_g, wav2, wav_lengths, n_fft, hop_size, win_size, sampling_rate, n_mels, fmin, fmax, mel_basis)
+    return validation_losses(net_g, net_d, x, x_lengths, spec, spec_lengths, wav2.unsqueeze(1), n_fft=n_fft, hop_size=hop_size, win_size=win_size,
+                             sampling_rate=sampling_rate, n_mels=n_mels, fmin=fmin, fmax=fmax, mel_basis=mel_basis, segment_size=segment_size,
+                             **kwargs)
