@@ -7,6 +7,7 @@ import os
 import pytest
 import torch
 
+import batch_regime_cases as _regime_cases
 from oracle import tacotron_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -177,7 +178,8 @@ def test_golden_cell_step(golden, H):
 # --------------------------------------------------------------------------
 # oracle on the same seeded inputs, LJSpeech dims (BASELINE.json configs[1] and [2])
 # --------------------------------------------------------------------------
-@pytest.mark.parametrize("B,L,T,lengths", [(64, 120, 24, None), (256, 120, 6, None), (150, 33, 6, None), (5, 37, 10, [37, 30, 12, 37, 1]), (1, 9, 12, None)])
+@pytest.mark.parametrize("B,L,T,lengths", [(64, 120, 24, None), (256, 120, 6, None), (150, 33, 6, None), (5, 37, 10, [37, 30, 12, 37, 1]), (1, 9, 12, None)]
+                         + _regime_cases.LJSPEECH_CASES)  # (97 - 128 utterances: level 1, lstm_dec alone on the 64 x 8 tile, K 1536 deep)
 def test_ljspeech_dims_vs_oracle(H, B, L, T, lengths):
     dims = O.DecoderDims()
     wts = O.random_decoder_weights(dims, seed=42, nonzero_init_state=True)
@@ -1376,7 +1378,12 @@ def test_all_step_orders_and_layouts_vs_oracle(H, prec, monkeypatch):
     wts = O.random_decoder_weights(dims, seed=21, nonzero_init_state=True)    #  register-weight projection all apply)
     T_ = 18  # >= 15 steps: the captured-graph path (unless switched off)
     opts = _STEP_OPTIONS
-    for B in (3, 40, 70):  # stand-alone small tile / 64x8 lean tile / 64x16 lean tile of the two-role launches
+    # B = 3: the stand-alone small tile as the LSTM role; 40: the lean 64 x 8 tile (exact fp32: its 32-row form); 70: the lean
+    # 64 x 16 tile in split-fp16 - exact fp32 stays on the 32-row lean tile up to 96 utterances (kLean8MaxRowsF32); 100: the lean
+    # 64 x 16 tile in exact fp32 too (the ATTN_LEAN attention pass beside it), and launch_lstm's stand-alone 64 x 8 tile in both
+    # arithmetics under overlap=0 (both LSTMs) and overlap=1 (lstm_dec)
+    assert _regime_cases.OPTION_MATRIX_B == (3, 40, 70, 100)  # (test_batch_regimes_host.py: no row of these is near an argmax tie)
+    for B in _regime_cases.OPTION_MATRIX_B:
         mem = O.synthetic_memory(B, 11, dims.d_ctx, lengths=[11] * (B - 1) + [4], seed=7)
         masks = O.synthetic_masks(T_, B, dims.d_pre, seed=9)
         oy, os_, ow = O.decode(wts, dims, mem, max_steps=T_ - 1, masks=masks)
