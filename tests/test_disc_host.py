@@ -40,11 +40,13 @@ def _conv(sd, prefix):
     return w, sd[prefix + ".bias"].double()
 
 
-def reference_disc(sd, d, x):
+def reference_disc(sd, d, x, period=None, stride=3, prefix=None):
     """fp64 restatement of discriminators.<d> (models.py:1034-1053 for d >= 1, :1072-1083 for d = 0) with torch functional ops on
-    the state dict sd of a MultiPeriodDiscriminator.  x [B, 1, T] -> (scores [B, L], fmap list) in the reference's shapes."""
+    the state dict sd of a MultiPeriodDiscriminator.  x [B, 1, T] -> (scores [B, L], fmap list) in the reference's shapes.
+    A DiscriminatorP of other dims (d >= 1): its `period` (default PERIODS[d]) and `stride` as arguments, the kernel size from the
+    weights, and `prefix` where its keys start ("" for the state dict of a DiscriminatorP on its own)."""
     x = x.double()
-    pre = f"discriminators.{d}."
+    pre = f"discriminators.{d}." if prefix is None else prefix
     fmap = []
     if d == 0:
         for i, (stride, groups, pad) in enumerate([(1, 1, 7), (4, 4, 20), (4, 16, 20), (4, 64, 20), (4, 256, 20), (1, 1, 2)]):
@@ -54,7 +56,7 @@ def reference_disc(sd, d, x):
         w, b = _conv(sd, pre + "conv_post")
         x = F.conv1d(x, w, b, padding=1)
     else:
-        p = PERIODS[d]
+        p = PERIODS[d] if period is None else period
         b_, c, t = x.shape
         if t % p != 0:
             x = F.pad(x, (0, p - t % p), "reflect")
@@ -62,7 +64,7 @@ def reference_disc(sd, d, x):
         for i in range(5):
             w, b = _conv(sd, f"{pre}convs.{i}")
             k = w.shape[2]
-            x = F.leaky_relu(F.conv2d(x, w, b, stride=(3 if i < 4 else 1, 1), padding=((k - 1) // 2, 0)), LRELU_SLOPE)
+            x = F.leaky_relu(F.conv2d(x, w, b, stride=(stride if i < 4 else 1, 1), padding=((k - 1) // 2, 0)), LRELU_SLOPE)
             fmap.append(x)
         w, b = _conv(sd, pre + "conv_post")
         x = F.conv2d(x, w, b, padding=(1, 0))

@@ -96,9 +96,12 @@ def spline_inverse(x, uw, uh, ud, tail=5.0, slip=()):
     return out
 
 
-def conv_flow_reverse(sd, p, z, x_mask, g, slip=()):
-    """modules.ConvFlow.forward(reverse=True) (modules.py:484-516), in_channels 2, num_bins 10."""
+def conv_flow_reverse(sd, p, z, x_mask, g, slip=(), probe=None):
+    """modules.ConvFlow.forward(reverse=True) (modules.py:484-516), in_channels 2, num_bins 10.  probe: a list that receives the
+    spline's in-length inputs x1."""
     x0, x1 = z[:, :1], z[:, 1:]
+    if probe is not None:
+        probe.append(x1[x_mask.expand_as(x1) > 0])
     C = sd[p + ".pre.weight"].shape[0]
     h = F.conv1d(x0, sd[p + ".pre.weight"].double(), sd[p + ".pre.bias"].double())
     h = dds_conv(sd, p + ".convs", h, x_mask, g=g, slip=slip)
@@ -110,9 +113,10 @@ def conv_flow_reverse(sd, p, z, x_mask, g, slip=()):
     return torch.cat([x0, y1], 1) * x_mask
 
 
-def sdp_reverse(sd, x, x_mask, noise, noise_scale=1.0, g=None, n_flows=4, slip=()):
+def sdp_reverse(sd, x, x_mask, noise, noise_scale=1.0, g=None, n_flows=4, slip=(), probe=None):
     """StochasticDurationPredictor.forward(reverse=True) (models.py:80-137) with the noise given: -> logw [B, 1, T] fp64.
-    slip: test aid - 'keep_dropped_flow', 'drop_wrong_flow', 'missing_flip', 'tanh_gelu', 'no_dilation', 'searchsorted_no_eps'."""
+    slip: test aid - 'keep_dropped_flow', 'drop_wrong_flow', 'missing_flip', 'tanh_gelu', 'no_dilation', 'searchsorted_no_eps';
+    probe: a list that receives every inverse spline's in-length inputs, in the order the splines run."""
     x, x_mask, noise = x.double(), x_mask.double(), noise.double()
     x = F.conv1d(x, sd["pre.weight"].double(), sd["pre.bias"].double())
     if g is not None:
@@ -136,7 +140,7 @@ def sdp_reverse(sd, x, x_mask, noise, noise_scale=1.0, g=None, n_flows=4, slip=(
         elif f == "ea":
             z = (z - sd["flows.0.m"].double()) * torch.exp(-sd["flows.0.logs"].double()) * x_mask
         else:
-            z = conv_flow_reverse(sd, f, z, x_mask, x, slip=slip)
+            z = conv_flow_reverse(sd, f, z, x_mask, x, slip=slip, probe=probe)
     return z[:, :1]
 
 

@@ -298,10 +298,23 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void disc_conv_ke
 // The tile is fixed - 64 x 64, K-sequential - whatever M is: an output's k-order then depends on nothing but the layer, and a row
 // gets the same bits alone and in any batch.  (Every dense conv here has Co >= 128; the wide ones carry the family's work at
 // M of 10^4 .. 10^5 rows, where the 64 x 64 tile stages half the bytes per multiply-add of the 32 x 32 split-K one.)
+//
+// Beyond the reference's own K (5 taps of 1024 channels) one fp32 accumulator per output is too long a chain: at 15 taps of 512
+// and 1024 channels (K = 7 680, 15 360) its rounding error reached the parity bar of rtol 1e-4 / atol 1e-5 on its own
+// (tests/test_dims_corners_hip.py, 1.02 of it at K = 7 680), four times the error of a blocked CPU sum.  Such layers take the
+// 32 x 32 tile whose four MFMA waves each sum a quarter of every K tile (the row GEMM's small-M tile), so no accumulator sums more
+// than 5 120 products in any accepted configuration.  The choice depends on the layer alone, like the tile above.
 typedef TileCfg<2, 2, 1, 4> ConvTile;
+typedef TileCfg<1, 1, 4, 4> LongKTile;
+constexpr int kMaxSeqK = 5 * 1024;
+template <class Cfg>
+void launch_conv_tile(const ConvArgs& a, hipStream_t st) {
+  const size_t mt = ((size_t)a.M + Cfg::BM - 1) / Cfg::BM, nt = ((size_t)a.Co + Cfg::BN - 1) / Cfg::BN;
+  hipLaunchKernelGGL((disc_conv_kernel<Cfg>), dim3((unsigned)(mt * nt)), dim3(kGemmThreads), 0, st, a);
+}
 void launch_conv(const ConvArgs& a, hipStream_t st) {
-  const size_t mt = ((size_t)a.M + ConvTile::BM - 1) / ConvTile::BM, nt = ((size_t)a.Co + ConvTile::BN - 1) / ConvTile::BN;
-  hipLaunchKernelGGL((disc_conv_kernel<ConvTile>), dim3((unsigned)(mt * nt)), dim3(kGemmThreads), 0, st, a);
+  if (a.k * a.Ci > kMaxSeqK) launch_conv_tile<LongKTile>(a, st);
+  else launch_conv_tile<ConvTile>(a, st);
 }
 
 // conv_post (C -> 1, 3 taps, models.py:1032 / 1070): one wave per output.  The taps inside the column are one run of floats

@@ -729,8 +729,9 @@ __global__ __launch_bounds__(64) void nll_reduce_kernel(const float* eq, const f
 }
 
 size_t dds_lds(int C) { return (size_t)3 * kRows * C * sizeof(float); }
-// the likelihood's launches: dds_lds, and room for the 29 projected columns behind Y where C < 16 leaves less than that
-size_t nll_lds(int C) { return max(dds_lds(C), (size_t)kRows * (C + kProj) * sizeof(float)); }
+// a DDSConv launch of either direction: dds_lds, and room for the 29 projected columns of a flow tail behind Y where C < 16 leaves
+// less than that (Y [kRows][29] starts at kRows * C floats: at C = 4, 8, 12 it ends past 3 * kRows * C)
+size_t flow_lds(int C) { return max(dds_lds(C), (size_t)kRows * (C + kProj) * sizeof(float)); }
 size_t pw_lds(int Cin, int taps, int N) { return (size_t)kRows * (taps * Cin + N) * sizeof(float); }
 
 // *_pack_weights' steps, one per record: from src into the blob b
@@ -805,7 +806,7 @@ void run_dds(const float* b, const DdsW& w, DdsArgs a, const float* x_first, flo
     l.tail = i == 2 ? tail : TAIL_NONE;
     float* out = (i % 2 == 0) ? bufA : bufB;
     if (i < 2) l.xout = out;
-    hipLaunchKernelGGL(dds_layer_kernel<kNll>, dim3(nblk), dim3(kThreads), kNll ? nll_lds(a.C) : dds_lds(a.C), st, l);
+    hipLaunchKernelGGL(dds_layer_kernel<kNll>, dim3(nblk), dim3(kThreads), flow_lds(a.C), st, l);
     in = out;
   }
 }
