@@ -110,6 +110,7 @@ class DurNllDims(C.Structure):  # include/ttsdec.h ttsvits_durnll_dims
 DUR_SDP, DUR_DP = 0, 1  # include/ttsdec.h ttsdur_dims.kind
 PATH_F32, PATH_F16, PATH_BF16 = 0, 1, 2  # include/ttsdec.h TTSVITS_PATH_*
 ALIGN_MAX_TX = 1024  # tokens per utterance ttsvits_maximum_path is built for
+VITS_MAX_HEAD_WIDTH = 256  # channels per attention head ttsvits_create accepts (csrc/vits2.hip dims_ok)
 
 
 class DurDims(C.Structure):  # include/ttsdec.h ttsdur_dims

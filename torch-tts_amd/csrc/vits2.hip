@@ -1401,9 +1401,14 @@ bool dims_ok(const ttsvits_dims& d) {
   const int v[] = {d.inter_channels, d.hidden_channels, d.filter_channels, d.flow_hidden};
   for (int x : v)
     if (x <= 0 || (x & 3)) return false;
-  if ((d.inter_channels / 2) & 3) return false;
+  // (the halves of a coupling are rows of the GEMM core; a handle without flows - a text encoder's - only emits m and logs)
+  if (d.n_flows > 0 && ((d.inter_channels / 2) & 3)) return false;
   if (d.n_vocab <= 0 || d.n_heads <= 0 || d.hidden_channels % d.n_heads) return false;
   if (d.flow_tf_heads <= 0 || (d.inter_channels / 2) % d.flow_tf_heads) return false;
+  // the attention kernels hold a head of up to 256 columns (run_stack; mha_kernel's ND).  The text encoder's call runs its stack
+  // whatever n_layers is, the flow's only when there is a coupling layer: refused here, before a call could launch anything
+  if (d.hidden_channels / d.n_heads > 256) return false;
+  if (d.n_flows > 0 && d.inter_channels / 2 / d.flow_tf_heads > 256) return false;
   if (d.n_layers < 0 || d.n_layers > kMaxLayers || d.flow_tf_layers < 0 || d.flow_tf_layers > kMaxLayers) return false;
   if (d.n_flows < 0 || d.n_flows > kMaxFlows || d.flow_wn_layers < 1 || d.flow_wn_layers > kMaxWn) return false;
   if (!(d.kernel_size & 1) || !(d.flow_kernel & 1) || !(d.flow_tf_kernel & 1) || d.kernel_size < 1 || d.flow_kernel < 1 || d.flow_tf_kernel < 1)

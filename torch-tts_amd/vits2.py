@@ -154,7 +154,18 @@ class VitsEngine(Handle):
 
     def __init__(self, dims: Dict[str, int], device: torch.device):
         dims = dict(dict(gin_channels=0, cond_layer_idx=0), **dims)
-        super().__init__(dims, _lib.VitsDims(*[int(dims[n]) for n, _ in _lib.VitsDims._fields_]), device)
+        try:
+            super().__init__(dims, _lib.VitsDims(*[int(dims[n]) for n, _ in _lib.VitsDims._fields_]), device)
+        except _lib.DimsNotBuilt:
+            # the one refusal of ttsvits_create that is not about a single field: a head wider than the attention kernels hold
+            stacks = [("the text encoder", dims["hidden_channels"], dims["n_heads"])]
+            if dims["n_flows"] > 0:
+                stacks.append(("the flow's pre_transformer", dims["inter_channels"] // 2, dims["flow_tf_heads"]))
+            for owner, ch, heads in stacks:
+                if ch > 0 and heads > 0 and ch // heads > _lib.VITS_MAX_HEAD_WIDTH:
+                    raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsvits_create", f"head width {ch // heads} ({ch} channels / {heads} heads) of {owner}: the "
+                                            f"attention kernels are built for up to {_lib.VITS_MAX_HEAD_WIDTH}") from None
+            raise
         self.status = torch.zeros(1, dtype=torch.int32, device=device)  # bit 0: an id outside the table (ttsvits_text_encoder)
 
     def text_encoder(self, ids: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor] = None):
@@ -389,9 +400,13 @@ class TextEncoder(PackedWeightsMixin, nn.Module):
         inference_only(self, "text encoder")
         eng = self._engines.get(self._dims(), x.device)
         eng.set_precision(self.precision)
-        spk = [self.encoder.spk_emb_linear.weight, self.encoder.spk_emb_linear.bias] if self.gin_channels else []
-        eng.ensure_packed([self.emb.weight] + spk + self.encoder.weight_tensors() + [self.proj.weight, self.proj.bias])
+        eng.ensure_packed(self.weight_tensors())
         return eng.text_encoder(x, x_lengths, g)
+
+    def weight_tensors(self) -> List[torch.Tensor]:
+        """ttsvits_pack_weights' order (include/ttsdec.h) up to the text encoder's last tensor; a handle without flows takes no more."""
+        spk = [self.encoder.spk_emb_linear.weight, self.encoder.spk_emb_linear.bias] if self.gin_channels else []
+        return [self.emb.weight] + spk + self.encoder.weight_tensors() + [self.proj.weight, self.proj.bias]
 
 
 class _WN(nn.Module):
@@ -491,16 +506,16 @@ class ResidualCouplingTransformersBlock(PackedWeightsMixin, nn.Module):
         inference_only(self, "flow")
         eng = self._engines.get(self._dims(), z_cl.device)
         eng.set_precision(self.precision)
-
-        def tensors() -> List[Optional[torch.Tensor]]:
-            # emb, (spk_emb_linear.{weight,bias},) proj.weight, proj.bias of the (absent) text encoder
-            ts: List[Optional[torch.Tensor]] = [None] * (5 if self.gin_channels else 3)
-            for i in range(self.n_flows):
-                ts += self.flows[2 * i].weight_tensors()  # (materialises the weight-normed conv weights)
-            return ts
-
-        eng.ensure_packed(tensors, key_tensors=list(self.parameters()))
+        eng.ensure_packed(self.weight_tensors, key_tensors=list(self.parameters()))
         return eng
+
+    def weight_tensors(self) -> List[Optional[torch.Tensor]]:
+        """ttsvits_pack_weights' order (include/ttsdec.h): None for the tensors of the (absent) text encoder."""
+        # emb, (spk_emb_linear.{weight,bias},) proj.weight, proj.bias
+        ts: List[Optional[torch.Tensor]] = [None] * (5 if self.gin_channels else 3)
+        for i in range(self.n_flows):
+            ts += self.flows[2 * i].weight_tensors()  # (materialises the weight-normed conv weights)
+        return ts
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
