@@ -241,7 +241,12 @@ int ttsdec_pack_weights(ttsdec_handle* h, const float* const* src /*host array o
 int ttsdec_bind_weights(ttsdec_handle* h, const void* blob);
 
 /* Decoder workspace (recurrent state + scratch) for a batch of B utterances with
- * memory length L.  The state persists in the workspace between ttsdec_decode calls. */
+ * memory length L.  The state persists in the workspace between ttsdec_decode calls.
+ * Size limit (also ttsenc_workspace_bytes and ttsenc_style_workspace_bytes): the LSTM kernels reach their operands through one
+ * buffer descriptor of 0x7FFFF000 bytes (just under 2 GiB), so a (B, L) whose workspace would be that large or larger is refused
+ * - the query returns 0 and the calls that take the workspace return TTSDEC_ERR_WORKSPACE - and a handle whose packed blob
+ * would be (ttsdec_create, ttsenc_create, ttsenc_style_create) is refused with TTSDEC_ERR_DIMS.  It takes a batch in the
+ * ten-thousands to get there. */
 size_t ttsdec_workspace_bytes(const ttsdec_handle* h, int B, int L);
 
 /*
@@ -419,6 +424,7 @@ int ttsenc_num_weight_tensors(const ttsenc_handle* h);
 size_t ttsenc_packed_bytes(const ttsenc_handle* h);
 int ttsenc_pack_weights(ttsenc_handle* h, const float* const* src, int n_src, void* blob, void* stream);
 int ttsenc_bind_weights(ttsenc_handle* h, const void* blob);
+/* 0 for a (B, L) beyond the size limit stated at ttsdec_workspace_bytes. */
 size_t ttsenc_workspace_bytes(const ttsenc_handle* h, int B, int L);
 /* ids [B, L] int64 (0 = padding), lengths [B] int32 on the device; L_out = max(lengths) (host-known:
  * the reference pads its output to the longest utterance, rnn.py:126); memory [B, L_out, d_out].
@@ -496,6 +502,7 @@ size_t ttsenc_style_packed_bytes(const ttsenc_style_handle* h);
  * channels-last order f * C + c, b_ih + b_hh, and the token keys / values tanh(embed) . W_key^T, . W_value^T (input-independent). */
 int ttsenc_style_pack_weights(ttsenc_style_handle* h, const float* const* src, int n_src, void* blob, void* stream);
 int ttsenc_style_bind_weights(ttsenc_style_handle* h, const void* blob);
+/* 0 for a (B, T) beyond the size limit stated at ttsdec_workspace_bytes. */
 size_t ttsenc_style_workspace_bytes(const ttsenc_style_handle* h, int B, int T);
 /* x: frame (b, t) at x + (b * T + t) * ldx, n_mels floats (ldx >= n_mels, a multiple of 4 is not required).
  * lengths [B] int32 on the device or NULL (every row runs all T' = T after n_convs stages steps); a row's LSTM runs

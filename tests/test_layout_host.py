@@ -208,6 +208,75 @@ def test_reported_sizes_are_the_recorded_ones():
     assert got["refused"][0] == 0 and got["refused"][1] > 60
 
 
+# ---- the reach of the LSTM kernels' one-descriptor loaders (csrc/gemm_tile.h DmaDesc::PerPlane, csrc/layout.h within_dma_reach):
+# a workspace or a packed blob that reaches the descriptor's range is refused ----
+BUF_RANGE = 0x7FFFF000  # csrc/common.h kBufRange
+B_TOP = 1 << 30         # (the layouts round B up in int arithmetic: stay clear of INT_MAX)
+
+
+def _style_dims(_lib, n_mels, filters, d_enc):
+    f = (C.c_int32 * _lib.STYLE_MAX_CONVS)(*filters)
+    return _lib.StyleDims(n_mels=n_mels, n_convs=len(filters), filters=f, d_enc=d_enc, kind=_lib.STYLE_ENCODER, bn_eps=1e-5)
+
+
+def _reach_families(_lib):
+    """-> {name: (create / destroy prefix, dims, name of the workspace query, L or T)}"""
+    return {"ttsdec": ("ttsdec", _lib.Dims(80, 1, 256, 512, 1024, 1024, 0.1, 0.5, 5, 512, 5, 1e-5, _lib.CELL_TACO2PROD, 0, _lib.POSTNET_TYPE_MEL),
+                       "ttsdec_workspace_bytes", 37),
+            "ttsenc": ("ttsenc", _lib.EncDims(148, 512, 512, 5, 1e-5), "ttsenc_workspace_bytes", 37),
+            "ttsenc_style": ("ttsenc_style", _style_dims(_lib, 80, (32, 32, 64, 64, 128, 128), 128), "ttsenc_style_workspace_bytes", 37)}
+
+
+def test_the_range_constant_is_the_librarys():
+    import re
+
+    src = open(os.path.join(ROOT, "torch-tts_amd", "csrc", "common.h")).read()
+    assert [int(v, 16) for v in re.findall(r"constexpr unsigned kBufRange = (0x[0-9A-Fa-f]+)u;", src)] == [BUF_RANGE]
+
+
+def test_workspace_queries_refuse_what_reaches_the_descriptor_range():
+    from torch_tts_amd import _lib
+
+    lib = _lib.load()
+    for name, (fam, d, query, L) in _reach_families(_lib).items():
+        h = C.c_void_p()
+        assert getattr(lib, fam + "_create")(C.byref(d), C.byref(h)) == _lib.OK, name
+        ws = lambda B: getattr(lib, query)(h, B, L)
+        assert ws(1) != 0 and ws(B_TOP) == 0, name
+        lo, hi, seen = 1, B_TOP, {}  # ws(lo) != 0, ws(hi) == 0
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            seen[mid] = ws(mid)
+            lo, hi = (mid, hi) if seen[mid] else (lo, mid)
+        print(name, "largest B", lo, "bytes", ws(lo), "of", BUF_RANGE)
+        assert 0 < ws(lo) < BUF_RANGE and ws(lo + 1) == 0, (name, lo, ws(lo), ws(lo + 1))
+        assert all((v != 0) == (B <= lo) for B, v in seen.items()), name  # (what the bisection stands on)
+        # non-decreasing up to there: a geometric ladder from 1, and every B of the last stretch
+        ladder = sorted({min(lo, int(1.07 ** i)) for i in range(400)} | set(range(max(1, lo - 130), lo + 1)))
+        sizes = [ws(B) for B in ladder]
+        assert all(a <= b for a, b in zip(sizes, sizes[1:])), name
+        assert getattr(lib, fam + "_destroy")(h) == _lib.OK
+
+
+def test_create_refuses_a_blob_that_reaches_the_descriptor_range():
+    """Dims whose only offence is the size of the packed blob; one size below, the same dims are accepted and stay below the range."""
+    from torch_tts_amd import _lib
+
+    lib = _lib.load()
+    dec = lambda H: _lib.Dims(80, 1, 256, 512, H, H, 0.1, 0.5, 0, 0, 5, 1e-5, _lib.CELL_TACO2PROD, 0, _lib.POSTNET_TYPE_MEL)
+    cases = {"ttsdec": (dec(2048), dec(4096)),  # the LSTM matrices, ~13.2 H^2 elements in three forms of 4 bytes each: 2.7 GB at H = 4096
+             "ttsenc": (_lib.EncDims(148, 512, 8192, 5, 1e-5), _lib.EncDims(148, 512, 16384, 5, 1e-5)),  # w_hh: 2 x 4 (d_out / 2)^2
+             "ttsenc_style": (_style_dims(_lib, 128, (1024,), 1024), _style_dims(_lib, 256, (1024,), 1024))}  # w_ih: 4 d_enc x 1024 x n_mels / 2
+    for fam, (fits, too_big) in cases.items():
+        h = C.c_void_p()
+        assert getattr(lib, fam + "_create")(C.byref(fits), C.byref(h)) == _lib.OK, fam
+        assert 0 < getattr(lib, fam + "_packed_bytes")(h) < BUF_RANGE, fam
+        assert getattr(lib, fam + "_destroy")(h) == _lib.OK
+        h = C.c_void_p()
+        assert getattr(lib, fam + "_create")(C.byref(too_big), C.byref(h)) == _lib.ERR_DIMS, fam
+        assert not h.value, fam
+
+
 if __name__ == "__main__":
     sys.path.insert(0, ROOT)
     from torch_tts_amd import _lib

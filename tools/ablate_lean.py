@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-launch times of the decode step (ttsdec_profile_step: every launch on its own, no hand-off waits) under the GEMM core's
-measurement ablations (option profile_ablation -> the kernels' dbg switch): 0 = none, 1 = every tile load reads the 16-byte
-zero block (same instruction stream, no memory traffic), 3 = no LDS-DMA inside the K loop, 4 = no MFMAs.  LJSpeech dims."""
+measurement ablations (option profile_ablation -> the kernels' dbg switch): 0 = none, 1 = every tile load is out of
+its descriptor's range and reads nothing (same instruction stream, no memory traffic), 3 = no LDS-DMA inside the K loop, 4 = no MFMAs.  LJSpeech dims."""
 import argparse
 import json
 import os

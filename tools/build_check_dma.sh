@@ -1,6 +1,6 @@
 #!/bin/bash
-# Debug build of libttsdec.so whose buffer-descriptor loaders (csrc/gemm_tile.h kBufDma) check every lane's first address of
-# every K segment against the per-lane pointer form before issuing anything: a disagreeing lane is taken out of range and
+# Debug build of libttsdec.so whose GEMM loader waves (csrc/gemm_tile.h) check every lane's first address of every K segment -
+# descriptor base + offsets - against the operand loader's row_ptr before issuing anything: a disagreeing lane is taken out of range and
 # printed, never dereferenced.  Output: torch-tts_amd/lib/libttsdec_check.so (use with TTSDEC_LIB=...).
 set -e
 cd "$(dirname "$0")/.."

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(kGemmThreads) void tile_kernel(const f16* ah, const
   const size_t a_off = (size_t)(z * kc / kChunkK) * kM * kChunkK, w_off = (size_t)(z * kc / kChunkK) * kN * kChunkK;
   const LoaderPlain<2> la{chunked(make_seg1(ah + a_off, kK, kc), kM), chunked(make_seg1(al + a_off, kK, kc), kM), by * Cfg::BM, kM};
   const LoaderPlain<2> lb{chunked(make_seg1(wh + w_off, kK, kc), kN), chunked(make_seg1(wl + w_off, kK, kc), kN), bx * Cfg::BN, kN};
-  gemm_tile<Cfg>(la, lb, smem, true, dbg);
+  gemm_tile<Cfg, LoaderPlain<2>, LoaderPlain<2>, NoGate, DmaDesc::PerPlane>(la, lb, smem, true, dbg);  // (the LSTM kernels' form)
   float s = 0.f;
   for (int e = threadIdx.x; e < Cfg::BM * Cfg::BN; e += kGemmThreads) s += smem[(e / Cfg::BN) * Cfg::LDO + e % Cfg::BN];
   sink[(size_t)blockIdx.x * kGemmThreads + threadIdx.x] = s;

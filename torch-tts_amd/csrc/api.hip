@@ -282,6 +282,7 @@ struct StepBufs {
   unsigned long long* loop_stamps;  // measurement only: launch start times of one graph replay [kLoopStampSlots][kLoopStampNodes] (common.h)
   unsigned int* dep;  // arrival counters of the two-role launches: [DEP_KINDS][32-row blocks][kDepLine] (common.h), dep_bytes in all
   size_t dep_bytes;
+  size_t bytes;  // the whole layout, or 0: refused (layout.h within_dma_reach)
   int dep_blocks;  // 32-row blocks of the batch: dep + kind * dep_blocks * kDepLine is a hand-off kind's counter array
 };
 
@@ -309,6 +310,7 @@ StepBufs carve(Carver& cv, const ttsdec_dims& d, int B, int Lm) {
   s.dep_blocks = (B + 31) / 32;
   s.dep_bytes = (size_t)DEP_KINDS * s.dep_blocks * kDepLine * sizeof(unsigned int);
   s.dep = reinterpret_cast<unsigned int*>(cv.take(s.dep_bytes / sizeof(float)));
+  s.bytes = within_dma_reach(cv.bytes());
   return s;
 }
 
@@ -935,6 +937,10 @@ int ttsdec_create(const ttsdec_dims* dims, ttsdec_handle** out) {
   if (!h) return TTSDEC_ERR_INVALID_ARG;
   h->d = *dims;
   h->bl = make_blob_layout(*dims);
+  if (!within_dma_reach(h->bl.total * sizeof(float))) {
+    delete h;
+    return TTSDEC_ERR_DIMS;
+  }
   h->streams_ready = false;
   h->gexec = nullptr;
   h->graph = nullptr;
@@ -1090,8 +1096,7 @@ int ttsdec_bind_weights(ttsdec_handle* h, const void* blob) {
 size_t ttsdec_workspace_bytes(const ttsdec_handle* h, int B, int L) {
   if (!h || B <= 0 || L <= 0) return 0;
   Carver cv{nullptr};
-  carve(cv, h->d, B, L);
-  return cv.bytes();
+  return carve(cv, h->d, B, L).bytes;
 }
 
 // stamp_loop (ttsdec_profile_loop): every step kernel records its start time (common.h loop_stamp) in the workspace
@@ -1112,7 +1117,7 @@ static int decode_impl(ttsdec_handle* h, const float* memory, int B, int L, int 
   if (rc != TTSDEC_OK) return rc;
   Carver cv{static_cast<float*>(workspace)};
   const StepBufs sb = carve(cv, h->d, B, L);
-  if (workspace_bytes < cv.bytes() || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (!sb.bytes || workspace_bytes < sb.bytes || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ttsdec_dims& d = h->d;
 
@@ -1212,7 +1217,7 @@ int ttsdec_profile_loop(ttsdec_handle* h, const float* memory, int B, int L, int
   if (n_out < order.n || order.n >= kLoopStampNodes) return TTSDEC_ERR_INVALID_ARG;
   Carver cv{static_cast<float*>(workspace)};
   const StepBufs sb = carve(cv, h->d, B, L);
-  if (workspace_bytes < cv.bytes()) return TTSDEC_ERR_WORKSPACE;
+  if (!sb.bytes || workspace_bytes < sb.bytes) return TTSDEC_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   int rc = decode_impl(h, memory, B, L, 0, n_steps, n_steps, -1e30f, 0, dropout_mode, masks, seed, nullptr, 0, nullptr, y, s, w, T_out, workspace,
                        workspace_bytes, stream, true);
@@ -1418,7 +1423,7 @@ int ttsdec_cell_step(ttsdec_handle* h, const float* x, const float* memory, int 
   if (rc != TTSDEC_OK) return rc;
   Carver cv{static_cast<float*>(workspace)};
   const StepBufs sb = carve(cv, h->d, B, L);
-  if (workspace_bytes < cv.bytes() || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (!sb.bytes || workspace_bytes < sb.bytes || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ttsdec_dims& d = h->d;
   const size_t b = (size_t)B;
@@ -1511,7 +1516,7 @@ int ttsdec_profile_step(ttsdec_handle* h, const float* memory, int B, int L, int
   if (rc != TTSDEC_OK) return rc;
   Carver cv{static_cast<float*>(workspace)};
   const StepBufs sb = carve(cv, h->d, B, L);
-  if (workspace_bytes < cv.bytes() || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (!sb.bytes || workspace_bytes < sb.bytes || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   StepIo io;
   memset(&io, 0, sizeof(io));

@@ -232,10 +232,10 @@ __device__ __forceinline__ __attribute__((address_space(1))) T* as_g(T* p) {
   return (__attribute__((address_space(1))) T*)p;
 }
 
-// 16 zero bytes in device memory: out-of-range tile elements are loaded from here, so
-// a loader only ever selects an ADDRESS (every lane always issues its load).
-__device__ __attribute__((aligned(16))) float g_zero4[4] = {0.f, 0.f, 0.f, 0.f};
-__device__ __forceinline__ gbyte* zero_addr() { return (gbyte*)g_zero4; }
+// Range in bytes (num_records) of every buffer descriptor of the GEMM core's loaders (gemm_tile.h), and so also the per-lane
+// offset that marks a lane out of range: it reads nothing and zeros land in its LDS slot.  Host code reads it too - an
+// allocation that one descriptor must span has to be smaller (layout.h within_dma_reach).
+constexpr unsigned kBufRange = 0x7FFFF000u;
 
 // segment s of a Seg3 with EB-byte elements: pointer to (row, k = 0) and length in elements
 template <int EB>

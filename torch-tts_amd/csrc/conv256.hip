@@ -40,7 +40,7 @@ constexpr int kRowB = 128;                     // bytes of a row piece per step:
 constexpr int kSlot = kT256 * kRowB;           // one operand's bytes per step (32 KiB)
 constexpr int kSlots = 5;                      // ring of operand slots: B(s), A(s), B(s + 1), A(s + 1), B(s + 2) = 160 KiB
 constexpr int kThreads256 = 512;
-constexpr unsigned kOob = 0x7FFFF000u;         // (gemm_tile.h kBufRange: an offset no buffer reaches -> the lane's 16 bytes are zeros)
+constexpr unsigned kOob = 0x7FFFF000u;         // (common.h kBufRange: an offset no buffer reaches -> the lane's 16 bytes are zeros)
 
 typedef __attribute__((address_space(3))) void lds_void256;
 

@@ -39,7 +39,7 @@ struct LoaderConv {
   }
   __device__ __forceinline__ long col_off(int c16) const { return (long)c16 * 16; }
   __device__ __forceinline__ long tile_inc(int rowb) const { return rowb; }
-  // buffer-descriptor form (gemm_tile kBufDma): based at THIS workgroup's first im2col row - so the per-lane offsets stay small
+  // descriptor base (gemm_tile.h DmaDesc::PerSegment): at THIS workgroup's first im2col row - so the per-lane offsets stay small
   // whatever the size of x (Postnet at 2048 x 600 frames: 2.5 GB) - which for the batch's first frames lies `taps/2` frames
   // in front of x: only lanes whose k is inside the row's window [k_lo, k_hi) are ever in range, and those address x itself
   __device__ __forceinline__ const void* seg_base(int, int plane) const {
@@ -99,7 +99,7 @@ struct LoaderW {
   }
   __device__ __forceinline__ long col_off(int c16) const { return (long)c16 * 16; }
   __device__ __forceinline__ long tile_inc(int rowb) const { return rowb; }
-  // buffer-descriptor form (gemm_tile kBufDma; row-major weights): based at this workgroup's first weight row
+  // descriptor base (row-major weights): at this workgroup's first weight row
   __device__ __forceinline__ const void* seg_base(int i, int plane) const {
     const Seg3& s = plane == 0 ? w : w_lo;
     const int ld = i == 0 ? s.ld0 : (i == 1 ? s.ld1 : s.ld2);
@@ -215,13 +215,13 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void gemm_rows_ke
     LoaderConvDil<EB> la{{g.a.p0}, m0, g.M, g.T, g.Cin, g.taps, g.K, g.dil > 1 ? g.dil : 1};
     if constexpr (EB == 2) la.xp[1] = g.a_lo.p0;
     const LoaderW<EB> lb{make_seg1(g.W, g.ldw, g.K), make_seg1(g.W_lo, g.ldw, g.K), n0, g.N};
-    gemm_tile<Cfg, LoaderConvDil<EB>, LoaderW<EB>, NoGate, 2>(la, lb, smem, live);
+    gemm_tile<Cfg, LoaderConvDil<EB>, LoaderW<EB>, NoGate, DmaDesc::PerSegment>(la, lb, smem, live);
   } else if (AK == A_CONV) {
     const LoaderConv<EB> la{g.a.p0, g.a_lo.p0, m0, g.M, g.T, g.Cin, g.taps, g.K};
     const LoaderW<EB> lb{make_seg1(g.W, g.ldw, g.K), make_seg1(g.W_lo, g.ldw, g.K), n0, g.N};
     // (one K segment, both operands based at the workgroup's own first row: the buffer-descriptor loaders of gemm_tile.h apply
     // whatever the operand sizes)
-    gemm_tile<Cfg, LoaderConv<EB>, LoaderW<EB>, NoGate, 2>(la, lb, smem, live);
+    gemm_tile<Cfg, LoaderConv<EB>, LoaderW<EB>, NoGate, DmaDesc::PerSegment>(la, lb, smem, live);
   } else {
     Seg3 s = g.a, s_lo = g.a_lo;
     if (g.teacher != nullptr && g.t > 0 && as_g(g.teacher_flags)[g.t - 1] != 0) {
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void gemm_rows_ke
     const Seg3 wsl = make_seg3(wl, g.ldw, k0, wl + (size_t)k0 * EB, g.ldw, k1, wl + (size_t)(k0 + k1) * EB, g.ldw, k2);
     const LoaderW<EB> lb{ws, wsl, n0, g.N};
     const LoaderPlain<EB, true> la{s, s_lo, m0, g.M};
-    gemm_tile<Cfg, LoaderPlain<EB, true>, LoaderW<EB>, NoGate, 2>(la, lb, smem, live);
+    gemm_tile<Cfg, LoaderPlain<EB, true>, LoaderW<EB>, NoGate, DmaDesc::PerSegment>(la, lb, smem, live);
   }
   if (!live) return;
 

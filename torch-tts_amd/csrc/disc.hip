@@ -281,7 +281,7 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void disc_conv_ke
   const int m0 = (int)(blockIdx.x / NT) * BM, n0 = (int)(blockIdx.x % NT) * BN;
   const LoaderConvH la{g.in, m0, g.M, g.Hi, g.Ho, g.Ci, g.k, g.stride, g.pad};
   const LoaderRowsW lb{g.w, n0, g.Co, g.k * g.Ci};
-  gemm_tile<Cfg, LoaderConvH, LoaderRowsW, NoGate, 2>(la, lb, smem);
+  gemm_tile<Cfg, LoaderConvH, LoaderRowsW, NoGate, DmaDesc::PerSegment>(la, lb, smem);
   // models.py:1046-1047: leaky_relu(conv + bias); four columns per thread, one 16-byte store
   constexpr int Q = BN / 4;
   for (int e = threadIdx.x; e < BM * Q; e += kGemmThreads) {

@@ -18,7 +18,7 @@ namespace {
 struct EncBlob {  // offsets in floats
   size_t emb, conv_w[3], alpha[3], beta[3], w_ih, w_hh[2], h0, c0, total;
 };
-struct EncWs {  // offsets in bytes
+struct EncWs {  // offsets in bytes; total = 0: refused (layout.h within_dma_reach)
   size_t x, act[2], cat, gx, h[2][2], c[2], planes, total;
 };
 }  // namespace
@@ -61,7 +61,7 @@ EncWs make_ws(const ttsenc_dims& d, int B, int Lm) {
     W.c[dir] = take((size_t)B * H);
   }
   W.planes = take(M * 2 * E);  // hi + lo fp16 planes of one GEMM's A operand
-  W.total = cv.bytes();
+  W.total = within_dma_reach(cv.bytes());
   return W;
 }
 }  // namespace
@@ -78,6 +78,10 @@ int ttsenc_create(const ttsenc_dims* dims, ttsenc_handle** out) {
   if (!h) return TTSDEC_ERR_INVALID_ARG;
   h->d = d;
   h->bl = make_layout(d);
+  if (!within_dma_reach(h->bl.total * sizeof(float))) {
+    delete h;
+    return TTSDEC_ERR_DIMS;
+  }
   h->device = current_device_or_minus1();
   *out = h;
   return TTSDEC_OK;
@@ -144,7 +148,7 @@ int ttsenc_forward(ttsenc_handle* h, const int64_t* ids, const int32_t* lengths,
   if (!device_is_current(h->device)) return TTSDEC_ERR_DEVICE;
   const ttsenc_dims& d = h->d;
   const EncWs W = make_ws(d, B, L);
-  if (workspace_bytes < W.total || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  if (!W.total || workspace_bytes < W.total || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const EncBlob& bl = h->bl;
   const float* blob = h->blob;

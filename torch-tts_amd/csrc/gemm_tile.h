@@ -18,21 +18,24 @@
 // wave (.,.,wk) taking the wk-th 128-byte slice (intra-workgroup split-K, summed through
 // LDS in the epilogue).
 //
-// Staging: direct-to-LDS loads (global_load_lds_dwordx4, 16 B per lane, 1 KiB per wave
-// instruction) into a ring of S stages.  The ring is never drained: each iteration waits
-// with a COUNTED s_waitcnt vmcnt(N) for the oldest tile only and crosses one raw s_barrier.
+// Staging: direct-to-LDS buffer loads (buffer_load_dwordx4 ... lds, 16 B per lane, 1 KiB per
+// wave instruction) into a ring of S stages: a wave-uniform descriptor, a per-lane byte
+// offset computed once per K segment and a scalar K offset that advances per tile (see
+// DmaDesc below).  The ring is never drained: each iteration waits with a COUNTED
+// s_waitcnt vmcnt(N) for the oldest tile only and crosses one raw s_barrier.
 // (__syncthreads() would drain it: it waits vmcnt(0) while an LDS-DMA is pending.)
 //
 // An LDS-DMA writes wave-uniform base + lane*16, i.e. the LDS image is linear (unpadded
 // rows of ROWB bytes).  Bank conflicts of the ds_read_b128 fragment reads are removed by an
-// XOR swizzle of the 16-byte column index applied to the per-lane SOURCE address and again
+// XOR swizzle of the 16-byte column index applied to the per-lane SOURCE offset and again
 // on the read:  LDS(row, c) = global(row, c ^ swz(row)),  swz = (row>>1)&7 for 128-B rows
 // (two rows per 256-B bank row), row&15 for 256/512-B rows.  The 16 lanes of a ds_read_b128
 // group then hit 16 distinct 16-B slots.
 //
-// Out-of-range tile elements (row >= M, k >= K, conv padding) take their source address
-// from a 16-byte zero block, so every lane always issues its load and the per-tile
-// instruction stream - hence the vmcnt arithmetic - is the same for every tile.
+// Out-of-range tile elements (row >= M, k >= K, conv padding) carry an offset beyond the
+// descriptor's range (kBufRange): such a lane reads nothing and the DMA writes ZEROS to its
+// LDS slot.  Every lane always issues its load, so the per-tile instruction stream - hence
+// the vmcnt arithmetic - is the same for every tile.
 //
 // K order inside a 128-byte slice.  fp32: lane half h = lane>>5 supplies k = 16h + 4q + e
 // for MFMA (q, e) (64-byte slices of the lean fp32 tile: k = 8h + 4q + e, q < 2).  fp16: k16-step s uses the 16-byte column 2s + h, i.e. k = 16s + 8h + j.
@@ -79,7 +82,7 @@ struct TileCfg {
   static constexpr int ROWS_PER_INST = 64 / C16;             // tile rows one wave instruction covers
   // LDS-DMA instructions per loader wave per A / B plane tile.  A plane tile smaller than 4 KiB (2 KiB: 32 rows of
   // 64 bytes) still costs every loader wave one instruction - the vmcnt arithmetic wants the same count in every
-  // wave - but the waves beyond the tile read the zero block into a dummy slot behind the ring.
+  // wave - but the waves beyond the tile issue it out of range: zeros into a dummy slot behind the ring.
   static constexpr int NA = BM * ROWB >= 4096 ? BM * ROWB / 4096 : 1;
   static constexpr int NB = BN * ROWB >= 4096 ? BN * ROWB / 4096 : 1;
   static constexpr bool kDummy = BM * ROWB < 4096 || BN * ROWB < 4096;
@@ -107,7 +110,6 @@ struct TileCfg {
 };
 
 typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void global_void;
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -118,19 +120,23 @@ __device__ __forceinline__ void wait_vmcnt() {
 //   int   nseg() / seglen(s)       uniform: number of K segments and their lengths in elements
 //                                  (the torch.cat pieces of the reference); A and B agree
 //   bool  row_ok(r)                tile row r (0 <= r < BM or BN) exists
-//   gbyte* row_ptr(r, s, plane)    address of element k = 0 of segment s in tile row r
+//   void* seg_base(s, plane)       uniform: what the descriptor of segment s is based at
 //                                  (plane 0 = fp32 or fp16 hi, plane 1 = fp16 lo)
+//   unsigned row_off(r, s)         bytes from seg_base(s, .) to element k = 0 of segment s in tile row r (the planes share it);
+//                                  kBufRange for a row that is out of the picture in this segment
 //   long  col_off(c16)             byte offset of the row's 16-byte column c16 (c16 * 16 for row-major operands)
-//   long  tile_inc(rowb)           pointer advance from one K tile to the next (rowb for row-major operands)
-//   kRange / k_lo(r) / k_hi(r)     optional per-row valid k window in elements (conv padding)
+//   long  tile_inc(rowb)           byte advance from one K tile to the next (rowb for row-major operands)
+//   bool  kRange                   true: k_lo(r) / k_hi(r) give a per-row valid k window in elements (conv padding)
+//   gbyte* row_ptr(r, s, plane)    the address seg_base + row_off stands for, stated independently: only the
+//                                  TTSDEC_CHECK_DMA debug build (tools/build_check_dma.sh) reads it, to compare the two
 // The K loop walks the segments tile by tile (each segment zero-padded up to a multiple of
-// KT), so per tile a lane's source address is just "previous + ROWB": one 64-bit add per
-// load.  A lane whose row or k is out of range reads the 16-byte zero block instead.
+// KT): per tile only the SCALAR offset advances, by tile_inc.  A lane whose row or k is out
+// of range takes kBufRange as its offset instead.
 //
 // Wave roles (512-thread workgroup, two waves per SIMD):
 //   waves 0-3  MFMA waves: fragment reads (one tile ahead, double-buffered registers) and
 //              the dependent MFMA chain, nothing else in their instruction stream;
-//   waves 4-7  loader waves: address updates and LDS-DMA issue (an LDS-DMA costs its
+//   waves 4-7  loader waves: scalar offset updates and LDS-DMA issue (an LDS-DMA costs its
 //              issuing wave ~60-185 cycles; on a co-resident wave that overlaps the MFMAs).
 // Per K tile there is one workgroup barrier: loaders arrive once their part of tile t+1
 // has landed (counted vmcnt), MFMA waves once tile t-1's MFMAs are issued; after it the
@@ -152,23 +158,22 @@ struct NoGate {
   __device__ __forceinline__ void mark(int) const {}
 };
 
-// kBufDma (round 4): the loader waves issue their LDS-DMA as buffer_load_dwordx4 ... lds - a wave-uniform descriptor of the
-// K segment's base, a per-lane byte offset that is computed ONCE per segment (row offset + swizzled column) and a SCALAR K
-// offset that advances per tile - instead of global_load_lds with a 64-bit per-lane address that every instruction updates
-// (two 64-bit adds and a select in the vector ALU per DMA).  Why it matters: a loader wave shares its SIMD with an MFMA wave,
-// and beside a dense MFMA chain a partner wave's vector-ALU instructions issue at 8-21 cycles each (tools/
-// ubench_f32_partner.hip, ubench_f32_barrier_phase.hip: 64 v_add_u32 beside 16 dependent fp32 MFMAs take 1344 cycles, the chain
-// itself 968), so it was the LOADERS' per-tile instruction stream - ~40 VALU + 4 DMA - that set the pace of the fp32 K loop:
-// 1725 cycles per 32-k tile for 1024 cycles of MFMA, 640 for the loader waves alone.  With scalar bookkeeping only:
-// ~1100 in the micro-benchmark.  Out-of-range lanes (rows past the matrix, the zero padding of a segment's last tile, the
-// trailing dummy tiles) carry an offset beyond the descriptor's range: such a lane reads nothing and the DMA writes ZEROS to
-// its LDS slot (tools/ubench_buffer_lds_oob.hip; the scalar offset is part of the range check on gfx950, so a valid lane needs
-// offset + K advance < kBufRange: operands below 2 GiB - the callers that set kBufDma are the LSTM kernels).
-// Loaders used with kBufDma provide  seg_base(s, plane)  (uniform pointer) and  row_off(r, s)  (bytes from it).
-// kBufDma = 1: ONE descriptor per operand plane for all K segments (the LSTM kernels: segments of one allocation, their distances
-// ride in the scalar offset); kBufDma = 2: a descriptor per K segment, rebuilt where the segment is entered (the generic row /
-// conv GEMMs: segments may come from different allocations; based at the workgroup's own first row, so any operand size).
-constexpr unsigned kBufRange = 0x7FFFF000u;  // num_records of every descriptor = the offset that marks a lane out of range
+// How the loader waves address an operand.  A DMA's source is descriptor base + per-lane offset + scalar offset; the per-lane
+// offset (row_off + swizzled col_off) is computed ONCE per segment and only the scalar offset moves per tile, because a loader
+// wave shares its SIMD with an MFMA wave and beside a dense MFMA chain every vector-ALU instruction of the partner wave is
+// expensive ("Round 4").  Out-of-range lanes (rows past the matrix, the zero padding of a segment's last tile,
+// the trailing dummy tiles) carry the offset kBufRange (common.h) = num_records of every descriptor (tools/
+// ubench_buffer_lds_oob.hip).  The scalar offset takes part in the range check on gfx950, so a VALID lane needs
+// per-lane offset + scalar offset < kBufRange - what each form has to guarantee:
+//   PerPlane    ONE descriptor per operand plane for all K segments, based at the lowest of the segment pointers; a segment's
+//               distance from it rides in the scalar offset.  For operands whose segments are slices of one allocation SMALLER
+//               than kBufRange - the LSTM kernels: the call's workspace and the packed weight blob, which the host refuses at
+//               that size (layout.h within_dma_reach).  A descriptor per segment would keep 3 x planes x 2 base pointers alive
+//               in scalar registers across the K loop of kernels that sit at the scalar-register limit: spills.
+//   PerSegment  a descriptor per K segment, rebuilt where the segment is entered (the generic row / conv GEMMs: segments may
+//               come from different allocations).  Their loaders base it at the workgroup's own first row, so the offsets
+//               cover one tile's rows and K extent: any operand size.
+enum class DmaDesc { PerPlane, PerSegment };
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
   // (the pointer is wave-uniform by construction - kernel arguments - but say so: a descriptor the compiler believes to be
   // lane-varying becomes a waterfall loop around every load)
@@ -179,13 +184,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
 
 // Dilated implicit im2col (decode_kernels.hip LoaderConvDil): an A loader with kTapJump = true steps its K walk by
 // tile_inc(ROWB) per tile and, every tap_tiles(KT) tiles, by tap_jump(KT) bytes more (the (d - 1) * Cin frames a dilated tap
-// skips).  Buffer-descriptor form only (kBufDma); loaders without the member keep the plain walk.
+// skips).  A loader without the member walks by tile_inc alone.
 template <class L, class = void>
 struct TapJumpOf { static constexpr bool value = false; };
 template <class L>
 struct TapJumpOf<L, std::void_t<decltype(L::kTapJump)>> { static constexpr bool value = L::kTapJump; };
 
-template <class Cfg, class LoaderA, class LoaderB, class Gate = NoGate, int kBufDma = 0>
+template <class Cfg, class LoaderA, class LoaderB, class Gate, DmaDesc kDesc>
 __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, float* smem, bool live = true,
                                           int dbg = 0, const Gate gate = Gate()) {
   // `live` (does this launch have anything to do?) typically comes from a control-block load
@@ -233,13 +238,12 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
   const int half = lane >> 5;
   const int l32 = lane & 31;
 
-  if (is_loader && kBufDma) {
-    // ====================== loader waves, buffer-descriptor form ======================
-    if constexpr (kBufDma) {
-    // ONE descriptor per operand plane, based at the lowest of the operand's segment pointers; a segment's distance from it is
-    // folded into the per-lane offsets below.  (The segments of an LSTM operand are slices of one allocation - the decoder
-    // workspace, the packed weight blob - so the distances are far below the 2-GiB range; api.hip refuses larger ones.)  A
-    // descriptor per segment kept 3 x planes x 2 base pointers alive in scalar registers across the K loop: spills.
+  if (is_loader) {
+    // =========================== loader waves ===========================
+    // loader w issues, per plane, instructions i = 0..NA-1 covering A-tile rows
+    // (w*NA + i)*RPI + lane/C16; this lane's 16-byte column is (lane % C16) ^ swz(row).
+    constexpr bool kPerSeg = kDesc == DmaDesc::PerSegment;
+    // PerPlane: the base of plane p's one descriptor
     auto lowest = [&](const auto& ld_, int p) {
       const char* b0 = static_cast<const char*>(ld_.seg_base(0, p));
       const char* b1 = nseg > 1 ? static_cast<const char*>(ld_.seg_base(1, p)) : b0;
@@ -250,7 +254,7 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
     // distance of plane p's segment sg from that plane's base: uniform, added to the SCALAR offset (the planes of an operand
     // need not be laid out alike, so it cannot ride in the per-lane offsets that the planes share)
     auto seg_delta = [&](const auto& ld_, int sg, int p) {
-      if constexpr (kBufDma == 2) return 0u;  // (a descriptor per segment: no distances)
+      if constexpr (kPerSeg) return 0u;  // (a descriptor per segment: no distances)
       const char* b = static_cast<const char*>(ld_.seg_base(sg < nseg ? sg : 0, p));
       return (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b - lowest(ld_, p)));
     };
@@ -265,7 +269,7 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
     unsigned va[3][NA], vb[3][NB];  // per-lane byte offset inside a segment (row + swizzled column), per K segment; planes share it
     int ca[NA], cb[NB];             // element offset of the lane's column inside a tile
     // Per-row valid k windows (LoaderA::kRange: conv padding).  The per-lane test - two compares and a select in front of every
-    // DMA - is what the buffer form exists to avoid, so each instruction also gets the k range in which ALL its lanes are
+    // DMA - is what the once-per-segment offsets exist to avoid, so each instruction also gets the k range in which ALL its lanes are
     // valid (wave-uniform, computed once): tiles inside it take the test-free path; only the tiles at an utterance's first
     // and last frames take the per-lane one.
     int aklo[NA], akhi[NA], alo_all[NA], ahi_all[NA];
@@ -298,8 +302,8 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
       for (int sg = 0; sg < 3; ++sg) vb[sg][i] = ok ? lb.row_off(row, sg) + (unsigned)lb.col_off(c16) : kBufRange;
     }
 #ifdef TTSDEC_CHECK_DMA
-    // Debug build (tools/build_check_dma.sh): every lane's first address of every segment and plane against the per-lane
-    // pointer form; a lane that disagrees is taken out of range (reads nothing) and reported - never dereferenced.
+    // Debug build (tools/build_check_dma.sh): every lane's first address of every segment and plane against the loader's
+    // row_ptr; a lane that disagrees is taken out of range (reads nothing) and reported - never dereferenced.
 #pragma unroll
     for (int sg = 0; sg < 3; ++sg) {
       if (sg >= nseg) continue;
@@ -309,7 +313,7 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
         for (int i = 0; i < NA; ++i) {
           const int row = (wave * NA + i) * RPI + lane / C16;
           const int c16 = (lane % C16) ^ Cfg::swz(row);
-          if (va[sg][i] != kBufRange && (gbyte*)(kBufDma == 2 ? la.seg_base(sg, p) : lowest(la, p)) + dla[p][sg] + va[sg][i] != la.row_ptr(row, sg, p) + la.col_off(c16)) {
+          if (va[sg][i] != kBufRange && (gbyte*)(kPerSeg ? la.seg_base(sg, p) : lowest(la, p)) + dla[p][sg] + va[sg][i] != la.row_ptr(row, sg, p) + la.col_off(c16)) {
             printf("DMA address mismatch A seg %d plane %d row %d c16 %d\n", sg, p, row, c16);
             va[sg][i] = kBufRange;
           }
@@ -318,7 +322,7 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
         for (int i = 0; i < NB; ++i) {
           const int row = (wave * NB + i) * RPI + lane / C16;
           const int c16 = (lane % C16) ^ Cfg::swz(row);
-          if (vb[sg][i] != kBufRange && (gbyte*)(kBufDma == 2 ? lb.seg_base(sg, p) : lowest(lb, p)) + dlb[p][sg] + vb[sg][i] != lb.row_ptr(row, sg, p) + lb.col_off(c16)) {
+          if (vb[sg][i] != kBufRange && (gbyte*)(kPerSeg ? lb.seg_base(sg, p) : lowest(lb, p)) + dlb[p][sg] + vb[sg][i] != lb.row_ptr(row, sg, p) + lb.col_off(c16)) {
             printf("DMA address mismatch B seg %d plane %d row %d c16 %d\n", sg, p, row, c16);
             vb[sg][i] = kBufRange;
           }
@@ -331,13 +335,13 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
     __amdgpu_buffer_rsrc_t ra[NP], rb[NP];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
-      ra[p] = make_rsrc(kBufDma == 2 ? la.seg_base(0, p) : lowest(la, p));
-      rb[p] = make_rsrc(kBufDma == 2 ? lb.seg_base(0, p) : lowest(lb, p));
+      ra[p] = make_rsrc(kPerSeg ? la.seg_base(0, p) : lowest(la, p));
+      rb[p] = make_rsrc(kPerSeg ? lb.seg_base(0, p) : lowest(lb, p));
     }
     unsigned cva[NA], cvb[NB];
     unsigned cda[NP], cdb[NP];  // the current segment's distance from the base, per plane (uniform)
     auto enter_seg = [&](int sg) {  // uniform sg
-      if constexpr (kBufDma == 2) {
+      if constexpr (kPerSeg) {
         if (sg > 0) {
 #pragma unroll
           for (int p = 0; p < NP; ++p) {
@@ -440,130 +444,6 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
         else { left = 0x7fffffff; seg_len = 0; }  // every further tile is "partial" with nothing valid
       }
     };
-#pragma unroll
-    for (int t = 0; t < S - 1; ++t) issue_tile();
-    const int nk_run = live ? nk : 0;
-    if (live && !Cfg::kBig) {
-      wait_vmcnt<(S - 2) * Cfg::NLOADS>();  // tile 0 landed
-      __builtin_amdgcn_s_barrier();         // B0
-    }
-    for (int t = 0; t < nk_run; ++t) {
-      wait_vmcnt<Cfg::kWaitCnt>();
-      __builtin_amdgcn_s_barrier();
-      if (wave8 == 4) gate.mark(t);
-      gate_at(t + S - 1);
-      if (dbg != 3) issue_tile();
-    }
-    wait_vmcnt<0>();
-    }
-  } else if (is_loader) {
-    // =========================== loader waves ===========================
-    // loader w issues, per plane, instructions i = 0..NA-1 covering A-tile rows
-    // (w*NA + i)*RPI + lane/C16; this lane's 16-byte column is (lane % C16) ^ swz(row).
-    gbyte *qa0[NP][NA], *qa1[NP][NA], *qa2[NP][NA], *cura[NP][NA];
-    gbyte *qb0[NP][NB], *qb1[NP][NB], *qb2[NP][NB], *curb[NP][NB];
-    int ca[NA], cb[NB];      // element offset of the lane's column
-    long inca[NA], incb[NB];  // byte increment per tile
-    int aklo[NA], akhi[NA];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int row = (wave * NA + i) * RPI + lane / C16;
-      const bool ok = row < BM && la.row_ok(row) && dbg != 1;
-      const int c16 = (lane % C16) ^ Cfg::swz(row);
-      ca[i] = c16 * EPC;
-      inca[i] = ok ? la.tile_inc(ROWB) : 0;
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        qa0[p][i] = ok ? la.row_ptr(row, 0, p) + la.col_off(c16) : zero_addr();
-        qa1[p][i] = ok ? la.row_ptr(row, 1, p) + la.col_off(c16) : zero_addr();
-        qa2[p][i] = ok ? la.row_ptr(row, 2, p) + la.col_off(c16) : zero_addr();
-        cura[p][i] = qa0[p][i];
-      }
-      if (LoaderA::kRange) {
-        aklo[i] = ok ? la.k_lo(row) : 0;
-        akhi[i] = ok ? la.k_hi(row) : 0;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const int row = (wave * NB + i) * RPI + lane / C16;
-      const bool ok = row < BN && lb.row_ok(row) && dbg != 1;
-      const int c16 = (lane % C16) ^ Cfg::swz(row);
-      cb[i] = c16 * EPC;
-      incb[i] = ok ? lb.tile_inc(ROWB) : 0;
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        qb0[p][i] = ok ? lb.row_ptr(row, 0, p) + lb.col_off(c16) : zero_addr();
-        qb1[p][i] = ok ? lb.row_ptr(row, 1, p) + lb.col_off(c16) : zero_addr();
-        qb2[p][i] = ok ? lb.row_ptr(row, 2, p) + lb.col_off(c16) : zero_addr();
-        curb[p][i] = qb0[p][i];
-      }
-    }
-    int seg = 0, left = nt0, seg_len = len0, kpos = 0, istage = 0;
-
-    auto issue_tile = [&]() {
-      char* st = lds + istage * Cfg::kStageBytes;
-      const bool partial = (kpos + KT > seg_len);  // uniform: last, zero-padded tile of a segment (or past the end)
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-          gbyte* ptr = cura[p][i];
-          if (LoaderA::kRange)  // the seg_len bound also covers the zero-block tiles past the last segment
-            ptr = (kpos + ca[i] >= aklo[i] && kpos + ca[i] < akhi[i] && kpos + ca[i] < seg_len) ? ptr : zero_addr();
-          else
-            ptr = (partial && kpos + ca[i] >= seg_len) ? zero_addr() : ptr;
-          char* dst = st + p * Cfg::kPlaneABytes + (wave * NA + i) * 1024;
-          if (Cfg::kDummy && (wave * NA + i) * 1024 >= Cfg::kPlaneABytes) dst = lds + Cfg::kDummyOff + wave * 1024;
-          // (size and cache-policy arguments of the builtin must be literals)
-          if constexpr (Gate::kAuxA == 16) __builtin_amdgcn_global_load_lds((global_void*)ptr, (lds_void*)dst, 16, 0, 16);
-          else __builtin_amdgcn_global_load_lds((global_void*)ptr, (lds_void*)dst, 16, 0, 0);
-          cura[p][i] += inca[i];
-        }
-      }
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-          gbyte* ptr = (partial && kpos + cb[i] >= seg_len) ? zero_addr() : curb[p][i];
-          char* dstc = st + NP * Cfg::kPlaneABytes + p * Cfg::kPlaneBBytes + (wave * NB + i) * 1024;
-          if (Cfg::kDummy && (wave * NB + i) * 1024 >= Cfg::kPlaneBBytes) dstc = lds + Cfg::kDummyOff + wave * 1024;
-          lds_void* dst = (lds_void*)dstc;
-          // (size and cache-policy arguments of the builtin must be literals)
-          if constexpr (Cfg::kAuxB == 2) __builtin_amdgcn_global_load_lds((global_void*)ptr, dst, 16, 0, 2);
-          else __builtin_amdgcn_global_load_lds((global_void*)ptr, dst, 16, 0, 0);
-          curb[p][i] += incb[i];
-        }
-      }
-      istage = (istage + 1 == S) ? 0 : istage + 1;
-      kpos += KT;
-      if (--left == 0) {  // next segment (or, past the last one, zero-block loads that keep vmcnt uniform)
-        ++seg;
-        kpos = 0;
-        if (seg == 1 && nseg > 1) {
-          left = nt1; seg_len = len1;
-#pragma unroll
-          for (int p = 0; p < NP; ++p) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) cura[p][i] = qa1[p][i];
-#pragma unroll
-            for (int i = 0; i < NB; ++i) curb[p][i] = qb1[p][i];
-          }
-        } else if (seg == 2 && nseg > 2) {
-          left = nt2; seg_len = len2;
-#pragma unroll
-          for (int p = 0; p < NP; ++p) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) cura[p][i] = qa2[p][i];
-#pragma unroll
-            for (int i = 0; i < NB; ++i) curb[p][i] = qb2[p][i];
-          }
-        } else {
-          left = 0x7fffffff; seg_len = 0;  // every further tile is "partial" with nothing valid
-        }
-      }
-    };
-
     // tiles 0 .. S-2 in flight
 #pragma unroll
     for (int t = 0; t < S - 1; ++t) issue_tile();
@@ -581,7 +461,7 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
       gate_at(t + S - 1);
       if (dbg != 3) issue_tile();         // tile t+S-1 into that stage (dbg 3: measurement ablation)
     }
-    wait_vmcnt<0>();  // trailing zero-block loads must land before the ring is reused
+    wait_vmcnt<0>();  // the trailing out-of-range loads must land before the ring is reused
   } else {
     // ============================ MFMA waves ============================
     const int arow = wm * 32 + l32, brow = wn * 32 + l32;

@@ -136,7 +136,7 @@ struct LstmArgs {
   Ctrl* ctrl;
   int slot;
   int node;  // position of the launch in the step order (measurement: common.h loop_stamp)
-  int dbg;  // measurement ablations (ttsdec_profile_step only): 1 = every load reads the zero block
+  int dbg;  // measurement ablations (ttsdec_profile_step only): 1 = every load is out of range (reads nothing, zeros into LDS)
   int tag;  // 1 = the decoder LSTM of a decode step (separate kernel symbol for profilers), else 0
   int live_lag;  // 1: this cell runs in the same launch as the frame kernel of its step (see lstm_body)
   // Two-role launch: K segment dep_seg of the A operand is produced by the other role of this very launch (dep_which 0: frame

@@ -28,6 +28,14 @@ struct Carver {
   size_t bytes() const { return (off + slack) * sizeof(float); }
 };
 
+// The LSTM kernels of the ttsdec_, ttsenc_ and ttsenc_style_ families address each GEMM operand through ONE buffer descriptor
+// based at the lowest of its K segments (gemm_tile.h DmaDesc::PerPlane).  Every segment of their A operand lies in the call's
+// workspace (the style encoder's last state buffer: in enc_out, which has the size of a workspace buffer), every segment of
+// their B operand in the packed blob, so neither allocation may reach the descriptor's range: beyond it a lane would count as
+// out of range and zeros, not data, would land in LDS.  -> bytes, or 0 = refused.  The workspace walks of the three families
+// end in this call, so *_workspace_bytes and the calls that carve the workspace give one answer; *_create asks it of the blob.
+inline size_t within_dma_reach(size_t bytes) { return bytes < kBufRange ? bytes : 0; }
+
 // A weight blob is walked once, at *_create, into one record per weight; layout, pack, the tensor count and the forward calls read
 // the records.  BlobWalk is what every family's walk starts from: the carver hands out the offsets in blob order, src the source
 // indices in the order include/ttsdec.h documents - the two orders are the same - so src, at the end, is *_num_weight_tensors.

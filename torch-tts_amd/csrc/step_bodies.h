@@ -10,9 +10,9 @@ namespace ttsdec {
 
 // rows m0.. of an [M, K] activation made of up to three K segments; EB-byte elements,
 // plane 1 (fp16 lo) comes from a second Seg3 of identical shape
-// kWgBase: the buffer-descriptor form is based at THIS workgroup's first row (per-lane offsets stay small whatever the operand's
+// kWgBase: the descriptor (gemm_tile.h DmaDesc) is based at THIS workgroup's first row (per-lane offsets stay small whatever the operand's
 // size: the generic row GEMMs); false: at the segment's own pointer, the row block's offset riding in the per-lane offsets (the
-// LSTM kernels: library-internal operands far below 2 GiB - and six 64-bit base computations fewer in kernels that sit at the
+// LSTM kernels: operands inside the workspace and the blob, which the host keeps below the descriptor's range - and six 64-bit base computations fewer in kernels that sit at the
 // scalar-register limit; with them the split-fp16 two-role kernels spilled to scratch and the step went from 61.6 to 89.5 us).
 template <int EB, bool kWgBase = false>
 struct LoaderPlain {
@@ -25,11 +25,9 @@ struct LoaderPlain {
   __device__ __forceinline__ gbyte* row_ptr(int r, int i, int plane) const {
     return seg_row_ptr<EB>(plane == 0 ? s : s_lo, m0 + r, i);
   }
-  __device__ __forceinline__ int k_lo(int) const { return 0; }
-  __device__ __forceinline__ int k_hi(int) const { return 0; }
   __device__ __forceinline__ long col_off(int c16) const { return seg_col_off(s, c16); }
   __device__ __forceinline__ long tile_inc(int rowb) const { return seg_tile_inc(s, rowb); }
-  // buffer-descriptor form (gemm_tile kBufDma): the segment's base (uniform) and a row's byte offset from it
+  // the segment's descriptor base (uniform) and a row's byte offset from it
   __device__ __forceinline__ const void* seg_base(int i, int plane) const {
     const Seg3& q = plane == 0 ? s : s_lo;
     const char* p = static_cast<const char*>(i == 0 ? q.p0 : (i == 1 ? q.p1 : q.p2));
@@ -72,7 +70,6 @@ struct LoaderWLstm {
   }
   __device__ __forceinline__ long col_off(int c16) const { return w.mpad != 0 ? (long)(c16 >> 2) * 64 * kChunkBytes + (c16 & 3) * 16 : (long)c16 * 16; }
   __device__ __forceinline__ long tile_inc(int rowb) const { return w.mpad != 0 ? (long)(rowb / kChunkBytes) * 64 * kChunkBytes : (long)rowb; }
-  // buffer-descriptor form (gemm_tile kBufDma)
   __device__ __forceinline__ const void* seg_base(int i, int plane) const {
     const Seg3& s = plane == 0 ? w : w_lo;
     return i == 0 ? s.p0 : (i == 1 ? s.p1 : s.p2);
@@ -201,7 +198,7 @@ __device__ __forceinline__ void lstm_body(LstmArgs g, float* smem, int bx, int b
       }
     }
   }
-  gemm_tile<Cfg, LoaderPlain<EB>, LoaderWLstm<BU, EB>, RoleGateT<kWhole>, 1>(la, lb, smem, live, g.dbg, gate);
+  gemm_tile<Cfg, LoaderPlain<EB>, LoaderWLstm<BU, EB>, RoleGateT<kWhole>, DmaDesc::PerPlane>(la, lb, smem, live, g.dbg, gate);
   if (!live) return;
   if constexpr (!kEarlyEpi) load_epi();
 

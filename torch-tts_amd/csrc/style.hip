@@ -29,7 +29,7 @@ struct StyleBlob {  // offsets in floats
 struct StyleWs {
   float *act[2], *gx, *h, *c;
   int* steps;
-  size_t total;
+  size_t total;  // bytes, or 0: refused (layout.h within_dma_reach)
 };
 struct StageDims {  // per conv stage: output sizes
   int T[kMaxConvs], F[kMaxConvs];
@@ -107,7 +107,7 @@ StyleWs carve(const ttsenc_style_dims& d, int B, int T, float* base) {
   W.h = cv.take((size_t)B * d.d_enc);
   W.c = cv.take((size_t)B * d.d_enc);
   W.steps = reinterpret_cast<int*>(cv.take(B));
-  W.total = cv.bytes();
+  W.total = within_dma_reach(cv.bytes());
   return W;
 }
 
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void style_conv_k
   const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
   const LoaderConv2d la{g.in, m0, g.M, g.Ti, g.Fi, g.Ci, g.To, g.Fo};
   const LoaderConvW lb{g.w, n0, g.Co, g.Ci};
-  gemm_tile<Cfg, LoaderConv2d, LoaderConvW, NoGate, 2>(la, lb, smem);
+  gemm_tile<Cfg, LoaderConv2d, LoaderConvW, NoGate, DmaDesc::PerSegment>(la, lb, smem);
   // style.py:54-56: relu(bn(conv + bias)), BN in eval mode as v * alpha + beta; four columns per thread, one 16-byte store
   constexpr int Q = BN / 4;
   for (int e = threadIdx.x; e < BM * Q; e += kGemmThreads) {
@@ -394,6 +394,10 @@ int ttsenc_style_create(const ttsenc_style_dims* dims, ttsenc_style_handle** out
   for (int i = 0; i < d.n_convs; ++i) f = half_up(f);
   h->f_last = f;
   h->bl = make_layout(d, f);
+  if (!within_dma_reach(h->bl.total * sizeof(float))) {
+    delete h;
+    return TTSDEC_ERR_DIMS;
+  }
   h->device = current_device_or_minus1();
   *out = h;
   return TTSDEC_OK;
@@ -478,7 +482,8 @@ int ttsenc_style_forward(ttsenc_style_handle* h, const float* x, int ldx, const 
   const StageDims s = stage_dims(d, T);
   // (32-bit row indices in the conv loaders and the GEMMs)
   if ((size_t)B * s.T[0] * s.F[0] > 0x7fffffffu / 2) return TTSDEC_ERR_INVALID_ARG;
-  if (workspace_bytes < carve(d, B, T, nullptr).total || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
+  const size_t need = carve(d, B, T, nullptr).total;
+  if (!need || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255)) return TTSDEC_ERR_WORKSPACE;
   const StyleWs W = carve(d, B, T, static_cast<float*>(workspace));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const StyleBlob& bl = h->bl;
