@@ -35,7 +35,8 @@
 // Out-of-range tile elements (row >= M, k >= K, conv padding) carry an offset beyond the
 // descriptor's range (kBufRange): such a lane reads nothing and the DMA writes ZEROS to its
 // LDS slot.  Every lane always issues its load, so the per-tile instruction stream - hence
-// the vmcnt arithmetic - is the same for every tile.
+// the vmcnt arithmetic - is the same for every tile.  Nothing is issued past the walk's last
+// tile: its last S-1 iterations wait with descending counts instead (the peeled tail below).
 //
 // K order inside a 128-byte slice.  fp32: lane half h = lane>>5 supplies k = 16h + 4q + e
 // for MFMA (q, e) (64-byte slices of the lean fp32 tile: k = 8h + 4q + e, q < 2).  fp16: k16-step s uses the 16-byte column 2s + h, i.e. k = 16s + 8h + j.
@@ -161,8 +162,8 @@ struct NoGate {
 // How the loader waves address an operand.  A DMA's source is descriptor base + per-lane offset + scalar offset; the per-lane
 // offset (row_off + swizzled col_off) is computed ONCE per segment and only the scalar offset moves per tile, because a loader
 // wave shares its SIMD with an MFMA wave and beside a dense MFMA chain every vector-ALU instruction of the partner wave is
-// expensive ("Round 4").  Out-of-range lanes (rows past the matrix, the zero padding of a segment's last tile,
-// the trailing dummy tiles) carry the offset kBufRange (common.h) = num_records of every descriptor (tools/
+// expensive ("Round 4").  Out-of-range lanes (rows past the matrix, the zero padding of a segment's last tile)
+// carry the offset kBufRange (common.h) = num_records of every descriptor (tools/
 // ubench_buffer_lds_oob.hip).  The scalar offset takes part in the range check on gfx950, so a VALID lane needs
 // per-lane offset + scalar offset < kBufRange - what each form has to guarantee:
 //   PerPlane    ONE descriptor per operand plane for all K segments, based at the lowest of the segment pointers; a segment's
@@ -193,9 +194,10 @@ struct TapJumpOf<L, std::void_t<decltype(L::kTapJump)>> { static constexpr bool 
 template <class Cfg, class LoaderA, class LoaderB, class Gate, DmaDesc kDesc>
 __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, float* smem, bool live = true,
                                           int dbg = 0, const Gate gate = Gate()) {
-  // `live` (does this launch have anything to do?) typically comes from a control-block load
-  // that is still in flight: it is first looked at AFTER the loader waves have issued their
-  // prologue DMAs, so its latency hides under theirs.  A dead launch drains and falls through.
+  // `live` (does this launch have anything to do?) typically comes from a control-block load.  An ungated call looks at it
+  // first AFTER the loader waves have issued their prologue DMAs; a gated one (and a caller that predicates its own early
+  // loads with it, as lstm_body does) needs it in front of them.  Moving it behind the prologue there as well was measured and
+  // dropped ("K-walk ends").  A dead launch drains what it issued and falls through.
   constexpr int BM = Cfg::BM, BN = Cfg::BN, KT = Cfg::KT, C16 = Cfg::C16, RPI = Cfg::ROWS_PER_INST;
   constexpr int NA = Cfg::NA, NB = Cfg::NB, NP = Cfg::NP, EB = Cfg::EB, ROWB = Cfg::ROWB;
   constexpr int LDO = Cfg::LDO, S = Cfg::STAGES;
@@ -215,7 +217,9 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
   const int nk = nt0 + (nseg > 1 ? nt1 : 0) + (nseg > 2 ? nt2 : 0);
   // first tile of the gated segment (uniform), or -1
   auto first_tile = [&](int seg) { return (!live || seg < 0 || seg >= nseg) ? -1 : (seg == 0 ? 0 : (seg == 1 ? nt0 : nt0 + nt1)); };
-  const int gate_tile = first_tile(gate.seg);
+  // (an empty gated segment at the end of the walk has no tile: no gate for ANY wave - the loaders' steady loop ends at tile
+  // nk-1, and a barrier only the MFMA waves crossed would hang the workgroup)
+  const int gate_tile = first_tile(gate.seg) < nk ? first_tile(gate.seg) : -1;
   auto gate_sync = [&]() {  // every wave of the workgroup, at the same point of the tile sequence
     if (wave8 == 4) gate.wait();
     __builtin_amdgcn_s_barrier();
@@ -435,24 +439,28 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
           tap_left = tap_tiles;
         }
       }
-      if (--left == 0) {  // next segment (or, past the last one, out-of-range loads that keep vmcnt uniform)
+      if (--left == 0) {  // next segment (the walk never issues past its last tile)
         ++seg;
         kpos = 0;
         soa = sob = 0;
         if (seg == 1 && nseg > 1) { left = nt1; seg_len = len1; enter_seg(1); }
         else if (seg == 2 && nseg > 2) { left = nt2; seg_len = len2; enter_seg(2); }
-        else { left = 0x7fffffff; seg_len = 0; }  // every further tile is "partial" with nothing valid
+        else { left = 0x7fffffff; seg_len = 0; }  // (a tile past the end would be "partial" with nothing valid)
       }
     };
-    // tiles 0 .. S-2 in flight
-#pragma unroll
-    for (int t = 0; t < S - 1; ++t) issue_tile();
+    // tiles 0 .. S-2 in flight (a walk shorter than that: all of it - nothing is ever issued past the last tile)
+    // (a loop, not S-1 copies of issue_tile: unrolled, the split-fp16 two-role kernels - at the register limit - spilled)
+    const int n_pro = nk < S - 1 ? nk : S - 1;
+    for (int t = 0; t < n_pro; ++t) issue_tile();
     const int nk_run = live ? nk : 0;
     if (live && !Cfg::kBig) {
-      wait_vmcnt<(S - 2) * Cfg::NLOADS>();  // tile 0 landed
-      __builtin_amdgcn_s_barrier();         // B0
+      // tile 0 landed (a walk shorter than the ring drains: its few tiles are all in flight together anyway)
+      if (nk >= S - 1) wait_vmcnt<(S - 2) * Cfg::NLOADS>();
+      else wait_vmcnt<0>();
+      __builtin_amdgcn_s_barrier();  // B0
     }
-    for (int t = 0; t < nk_run; ++t) {
+    // Steady part: iteration t refills the stage tile t-1 occupied with tile t+S-1, while there is such a tile.
+    for (int t = 0; t < nk_run - (S - 1); ++t) {
       // small tiles: this wave's part of tile t+1 has landed (fragments are read one tile ahead);
       // big tiles: tile t has landed (fragments are read right after this barrier)
       wait_vmcnt<Cfg::kWaitCnt>();
@@ -461,7 +469,20 @@ __device__ __forceinline__ void gemm_tile(const LoaderA& la, const LoaderB& lb, 
       gate_at(t + S - 1);
       if (dbg != 3) issue_tile();         // tile t+S-1 into that stage (dbg 3: measurement ablation)
     }
-    wait_vmcnt<0>();  // the trailing out-of-range loads must land before the ring is reused
+    // Tail, peeled: the last S-1 iterations (all of a shorter walk) issue nothing - their DMAs, all out of range, only kept the
+    // counted wait uniform, beside the last tiles' MFMA chains - and wait with descending counts instead.  With r iterations
+    // still to come after this one, only the walk's last r + 1 tiles can be in flight: the small tiles, read one tile ahead,
+    // may leave r - 1 of them pending, the big ones r.  The last wait is vmcnt(0): nothing is pending when the ring is reused.
+    static_for<S - 1>([&](auto jc) {
+      constexpr int r = S - 2 - decltype(jc)::value;
+      constexpr int keep = Cfg::kBig ? r : (r > 0 ? r - 1 : 0);
+      if (nk_run > r) {
+        wait_vmcnt<keep * Cfg::NLOADS>();
+        __builtin_amdgcn_s_barrier();
+        if (wave8 == 4) gate.mark(nk_run - 1 - r);
+      }
+    });
+    wait_vmcnt<0>();  // (a dead launch's prologue tiles; nothing else can be pending here)
   } else {
     // ============================ MFMA waves ============================
     const int arow = wm * 32 + l32, brow = wn * 32 + l32;
