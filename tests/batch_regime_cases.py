@@ -3,7 +3,7 @@ the GPU; test_hip_parity.py's LJSpeech-dims and option-matrix cases are restated
 
 The tile an LSTM launch runs on and the launch sequence of a decode step are functions of the batch a call sees (DESIGN.md
 section 6), so every case sits on an edge of that table - the last batch of one row, the first of the next.  The expected
-launch names are the kOrder* tables of csrc/api.hip, restated once, next to the batch sizes.
+launch names are what step_order / node_name of csrc/api.hip give, restated once, next to the batch sizes.
 
 Every oracle result is computed once per process (functools.lru_cache) and never written to."""
 import functools
@@ -26,7 +26,7 @@ REDUCED_WEIGHT_SEED = 21
 T_STEPS = 18  # >= 15 steps: the captured-graph path
 L_MEM = 11
 
-# csrc/api.hip, the names of kOrderProdH2 / kOrderProdH2Q / kOrderProdH / kOrderProdHF (head_proj holds at these dims)
+# csrc/api.hip step_order with the projection as a head role (head_proj holds at these dims): level 2, level 2 with the query role, level 1, level 0
 THREE = frozenset({"proj+prenet+lstm_att", "query", "attention+lstm_dec"})
 TWO = frozenset({"proj+prenet+lstm_att", "query+attention+lstm_dec"})
 LEVEL1 = frozenset({"proj+prenet+lstm_att", "query", "attention", "lstm_dec"})
@@ -164,7 +164,7 @@ def option_matrix_oracle(B):
 # ---------------------------------------------------------------------------------------------------------------------
 TACO2 = dict(d_mel=80, r=1, d_pre=256, d_ctx=512, h_att=1024, h_dec=1024)  # config-rdh.yaml, as test_taco2_cell_rdh_dims_vs_oracle
 TACO2_T, TACO2_L = 4, 23
-TACO2_NAMES = frozenset({"proj+prenet+lstm_att", "lstm_dec", "query", "attention"})  # csrc/api.hip kOrderTaco2H
+TACO2_NAMES = frozenset({"proj+prenet+lstm_att", "lstm_dec", "query", "attention"})  # csrc/api.hip step_order: Taco2, level 1, head projection
 TACO2_B = (96, 129)  # 96: the 64 x 8 stand-alone tile (K over two waves); 129: the 64 x 16 one, three row blocks, the last one row
 
 

@@ -105,7 +105,6 @@ constexpr int kProjSplit = 4;
 struct ttsdec_handle : HandleBase {  // (device -1: no HIP device was available at create; host-only queries still work)
   ttsdec_dims d;
   BlobLayout bl;
-  bool use_graph;   // replay a captured hipGraph instead of launching every kernel (option "graph")
   // Two-role launches (fused_kernels.hip) where they apply: 1 = frame || lstm_att; 2 = also attention || lstm_dec;
   // 0 = off; -1 (default) = by batch size: level 2 up to 320 utterances, level 1 above.  Measured us per step for levels
   // 1 / 2 (end of round 2): B = 128 69.0 / 53.7, B = 192 66.2 / 59.5, B = 256 77.2 / 70.2.  Until the attention role's row sums
@@ -114,9 +113,14 @@ struct ttsdec_handle : HandleBase {  // (device -1: no HIP device was available 
   // every LSTM workgroup waited for the slowest of them.  (Split-fp16; exact fp32: see overlap_level.)
   // Option "overlap" = 0 / 1 / 2 (a larger value means 2).
   int overlap;
-  bool chunk_a, chunk_b;  // chunked layout of the activation planes / LSTM weight planes (options "chunk_a" / "chunk_b")
-  bool proj_regw;         // mel/stop projection on the register-weight kernel where it applies (option "proj_regw")
-  int opt_graph, opt_chunk_a, opt_chunk_b, opt_proj_regw;  // the options behind those four: -1 = default (on), 0, 1
+  // Four on / off options: -1 = default (on), 0, 1.
+  int opt_graph;                  // replay a captured hipGraph instead of launching every kernel (option "graph")
+  int opt_chunk_a, opt_chunk_b;   // chunked layout of the activation planes / LSTM weight planes (options "chunk_a" / "chunk_b")
+  int opt_proj_regw;              // mel/stop projection on the register-weight kernel where it applies (option "proj_regw")
+  bool use_graph() const { return opt_graph != 0; }
+  bool chunk_a() const { return opt_chunk_a != 0; }
+  bool chunk_b() const { return opt_chunk_b != 0; }
+  bool proj_regw() const { return opt_proj_regw != 0; }
   int head_proj;          // that projection as a role at the head of the NEXT step's frame launch: 1 / 0, -1 = by batch size; TTSDEC_HEAD_PROJ
   int attn_form;          // measurement: the form of the exact-fp32 attention pass on the 64 x 16 tile (include/ttsdec.h)
   int query_role;         // attention query as a job of the attention role's workgroups (step_order): 1 / 0, -1 = default
@@ -175,7 +179,7 @@ inline int query_split(const ttsdec_dims& d) { return split_of(query_k(d), query
 // launch: 128.6 -> 121.4 us per step at B = 256, 56.2 -> 54.4 at B = 32, 54.0 -> 50.2 at B = 1; profiles/r03_w_fp32_head_proj.txt.)
 inline bool proj_regw_shapes(const ttsdec_handle* h) {
   const ttsdec_dims& d = h->d;
-  return h->proj_regw && use_frame(d) && !((d.h_att | d.h_dec | d.d_ctx) & 7) && proj_split(proj_k(d)) > 0 && proj_n(d) <= 192;
+  return h->proj_regw() && use_frame(d) && !((d.h_att | d.h_dec | d.d_ctx) & 7) && proj_split(proj_k(d)) > 0 && proj_n(d) <= 192;
 }
 inline bool proj_regw(const ttsdec_handle* h, int prec) {
   return proj_regw_shapes(h) && (prec || h->head_proj != 0);  // (exact fp32: as a head role - head_proj() - only)
@@ -278,7 +282,6 @@ struct StepBufs {
   float *xpre0, *xpre, *ctx, *h_att[2], *c_att, *h_dec[2], *c_dec, *q, *ynext, *w[2];
   f16 *xpre_h, *xpre_l, *ctx_h, *ctx_l, *h_att_h[2], *h_att_l[2], *h_dec_h[2], *h_dec_l[2];
   float* jparts;  // split-K partial sums of the mel/stop projection [kProjSplit][B, proj_ldp]
-  float *pa, *pd;  // fp32 partial gate sums [B, 4H] of the two LSTMs' early parts (two-role step)
   unsigned long long* loop_stamps;  // measurement only: launch start times of one graph replay [kLoopStampSlots][kLoopStampNodes] (common.h)
   unsigned int* dep;  // arrival counters of the two-role launches: [DEP_KINDS][32-row blocks][kDepLine] (common.h), dep_bytes in all
   size_t dep_bytes;
@@ -305,7 +308,9 @@ StepBufs carve(Carver& cv, const ttsdec_dims& d, int B, int Lm) {
     s.h_dec_h[i] = takeh(bp * d.h_dec); s.h_dec_l[i] = takeh(bp * d.h_dec);
   }
   s.jparts = cv.take((size_t)kProjSplit * b * proj_ldp(d));
-  s.pa = cv.take(b * 4 * d.h_att); s.pd = cv.take(b * 4 * d.h_dec);
+  // (unused: two [B, 4H] spans that a retired scheme parked gate sums in; kept so that every offset behind them, and the size
+  // ttsdec_workspace_bytes reports, stay what callers have allocated for)
+  cv.take_off(b * 4 * d.h_att); cv.take_off(b * 4 * d.h_dec);
   s.loop_stamps = reinterpret_cast<unsigned long long*>(cv.take(kLoopStampSlots * kLoopStampNodes * 2));
   s.dep_blocks = (B + 31) / 32;
   s.dep_bytes = (size_t)DEP_KINDS * s.dep_blocks * kDepLine * sizeof(unsigned int);
@@ -341,20 +346,18 @@ struct StepIo {
 // N_QTD = N_TD whose attention-role workgroups first compute the query GEMM between them (then no N_Q in the step).
 // N_JF = [proj(t-1) | frame] as one launch (no LSTM role).
 enum Node { N_F, N_FIN, N_P0, N_P1, N_A, N_Q, N_T, N_D, N_J, N_FA, N_TD, N_AG, N_DG, N_JFA, N_JFIN, N_QTD, N_JF };
-// PART_GATED: the whole cell with the segment that waits for the other role of the launch LAST
-enum LstmPart { PART_WHOLE = 0, PART_EARLY = 1, PART_LATE = 2, PART_GATED = 3 };
 
 constexpr int kMaxKernelsPerStep = 7;
 struct StepOrder {
   int n;
   Node nodes[kMaxKernelsPerStep];
-  const char* names[kMaxKernelsPerStep];
 };
 
 // split-fp16 needs every K segment to be whole 16-byte columns of fp16 (multiples of 8)
 bool split_ok(const ttsdec_dims& d) { return !((d.d_pre | d.d_ctx | d.h_att | d.h_dec) & 7); }
 // launch order of one step: the Prod cell attends between its two LSTMs, the Taco2 cell after both
-const StepOrder& step_order(const ttsdec_handle* h, int B);
+StepOrder step_order(const ttsdec_handle* h, int B);
+const char* node_name(Node n);
 bool head_proj(const ttsdec_handle* h);
 bool query_role(const ttsdec_handle* h, int B);
 int& option_ref(ttsdec_handle* h, int o);
@@ -364,7 +367,7 @@ int lstm_prec(const ttsdec_handle* h) {
   return (h->precision == TTSDEC_PREC_SPLIT_F16 && split_ok(h->d) && h->wmax_dec < kSplitMax) ? 1 : 0;
 }
 // rows per chunk of the activation planes when they are in the chunked layout (common.h Seg3), 0 = row-major
-int act_mpad(const ttsdec_handle* h, int B) { return (lstm_prec(h) && chunk_ok(h->d) && h->chunk_a) ? rows_pad(B) : 0; }
+int act_mpad(const ttsdec_handle* h, int B) { return (lstm_prec(h) && chunk_ok(h->d) && h->chunk_a()) ? rows_pad(B) : 0; }
 
 // ---- GEMM operands by precision: fp32 | split-fp16 hi + lo planes | one bf16 plane ----
 struct Planes {  // what a GEMM reads as a / a_lo (fp32 and bf16: the same pointer twice)
@@ -404,42 +407,63 @@ int read_wmax(ttsdec_handle* h, hipStream_t st) {
   return TTSDEC_OK;
 }
 
-void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, Node node, hipStream_t st) {
-  const ttsdec_dims& d = h->d;
-  const BlobLayout& bl = h->bl;
-  const float* blob = h->blob;
-  const int p = (io.use_ctrl ? io.slot : io.t) & 1;
-  Ctrl* ctrl = io.use_ctrl ? sb.ctrl : nullptr;
-  const int B = io.B, P = d.d_pre, D = d.d_ctx, Ha = d.h_att, Hd = d.h_dec;
-  const float keep_scale = 1.0f / (1.0f - d.p_dropout);
-  const int prec = lstm_prec(h);
-  auto plane = [&](size_t float_off) { return reinterpret_cast<const f16*>(blob + float_off); };
-  const int mpad = act_mpad(h, B);
-  auto act = [&](Seg3 s) { return chunked(s, mpad); };  // an activation-plane segment list in the layout in use
-  auto dep = [&](int kind) { return sb.dep + (size_t)kind * sb.dep_blocks * kDepLine; };  // a hand-off kind's arrival counters
-  // An activation as a GEMM's a / a_lo: its (hi, lo) planes in the layout in use, or fp32 (twice).
-  struct Act {
-    Seg3 a, a_lo;
-  };
-  auto pick = [&](bool planes, Seg3 f32, Seg3 hi, Seg3 lo) { return planes ? Act{act(hi), act(lo)} : Act{f32, f32}; };
+// An activation as a GEMM's a / a_lo: its (hi, lo) planes in the layout in use, or fp32 (twice).
+struct Act {
+  Seg3 a, a_lo;
+};
+// One K segment of an LSTM cell's gates GEMM; each operand three ways: [0] fp32, [1] / [2] the split-fp16 hi / lo plane
+struct KSeg {
+  const void* a[3];  // the activation [B, k]
+  int k;
+  const void* w[3];  // its columns of W_ih or W_hh
+  int ldw;           // their leading "dimension": row-major elements per row, or (chunked) the matrix's chunks per unit block
+};
+// The K walk of a cell, as indices into {0: seg0 = x_pre (attention LSTM) or h_att (decoder LSTM), 1: ctx, 2: the cell's own h}.
+// A cell that is a role of a two-role launch (gated) walks the segment that the launch's other role writes LAST, behind the
+// gate.  The exact-fp32 outputs are pinned to these three summation orders.
+constexpr int kSegOrder[3][3] = {
+    {0, 1, 2},  // whole cell: cat[seg0, ctx | h] (decoder_cell.py:187, :191)
+    {1, 2, 0},  // gated attention LSTM: x_pre is written by the frame role of the same launch
+    {2, 0, 1},  // gated decoder LSTM: ctx is written by the attention role of the same launch
+};
+
+// The argument builders of a step's launches: one per kind of kernel argument, over what all of them read.
+struct StepArgs {
+  const ttsdec_handle* h; const StepBufs& sb; const StepIo& io;
+  const ttsdec_dims& d; const BlobLayout& bl; const float* blob;  // (the handle's)
+  int p;  // buffer parity of the step: the state it reads is in buffers p, what it writes in 1 - p
+  Ctrl* ctrl;
+  int B, P, D, Ha, Hd, prec, mpad;
+
+  StepArgs(const ttsdec_handle* h_, const StepBufs& sb_, const StepIo& io_)
+      : h(h_), sb(sb_), io(io_), d(h_->d), bl(h_->bl), blob(h_->blob), p((io_.use_ctrl ? io_.slot : io_.t) & 1),
+        ctrl(io_.use_ctrl ? sb_.ctrl : nullptr), B(io_.B), P(d.d_pre), D(d.d_ctx), Ha(d.h_att), Hd(d.h_dec), prec(lstm_prec(h_)),
+        mpad(act_mpad(h_, io_.B)) {}
+
+  const f16* plane(size_t float_off) const { return reinterpret_cast<const f16*>(blob + float_off); }
+  Seg3 act(Seg3 s) const { return chunked(s, mpad); }  // an activation-plane segment list in the layout in use
+  unsigned int* dep(int kind) const { return sb.dep + (size_t)kind * sb.dep_blocks * kDepLine; }  // a hand-off kind's arrival counters
+  float keep_scale() const { return 1.0f / (1.0f - d.p_dropout); }
+  Act pick(bool planes, Seg3 f32, Seg3 hi, Seg3 lo) const { return planes ? Act{act(hi), act(lo)} : Act{f32, f32}; }
   // cat[h_att, h_dec] of buffer parity q: the Taco2 cell's query and projection input, cat[h0, h1, zeros] (decoder_cell.py:126, :136)
-  auto h01_in = [&](int q, bool planes) {
+  Act h01_in(int q, bool planes) const {
     return pick(planes, make_seg2(sb.h_att[q], Ha, Ha, sb.h_dec[q], Hd, Hd), make_seg2(sb.h_att_h[q], Ha, Ha, sb.h_dec_h[q], Hd, Hd),
                 make_seg2(sb.h_att_l[q], Ha, Ha, sb.h_dec_l[q], Hd, Hd));
-  };
+  }
   // query_layer input: h_att (Prod, decoder_cell.py:188)
-  auto query_in = [&](int q, bool planes) {
+  Act query_in(int q, bool planes) const {
     if (is_taco2(d)) return h01_in(q, planes);
     return pick(planes, make_seg1(sb.h_att[q], Ha, Ha), make_seg1(sb.h_att_h[q], Ha, Ha), make_seg1(sb.h_att_l[q], Ha, Ha));
-  };
+  }
   // projection input: cat[h_dec, ctx] (Prod, decoder_cell.py:192)
-  auto proj_in = [&](int q, bool planes) {
+  Act proj_in(int q, bool planes) const {
     if (is_taco2(d)) return h01_in(q, planes);
     return pick(planes, make_seg2(sb.h_dec[q], Hd, Hd, sb.ctx, D, D), make_seg2(sb.h_dec_h[q], Hd, Hd, sb.ctx_h, D, D),
                 make_seg2(sb.h_dec_l[q], Hd, Hd, sb.ctx_l, D, D));
-  };
+  }
 
-  auto frame_args = [&](bool fin_only) {
+  // The frame kernel (fin_only: its end-of-call form); signals: as the producer role of a two-role launch
+  FrameArgs frame(bool fin_only, bool signals = false) const {
     FrameArgs f;
     memset(&f, 0, sizeof(f));
     const int Ph = pre_hidden(d);
@@ -457,82 +481,53 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
     f.prec = prec ? PREC_F16S : PREC_F32;
     f.Ph = Ph; f.P = P;
     f.dropout_mode = io.dropout_mode; f.masks = io.masks; f.mask_step_stride = (size_t)B * (Ph + P);
-    f.seed = io.seed; f.keep_scale = keep_scale;
+    f.seed = io.seed; f.keep_scale = keep_scale();
     f.xpre = sb.xpre;
     if (prec) { f.xpre_h = sb.xpre_h; f.xpre_l = sb.xpre_l; f.out_mpad = mpad; }
     f.M = B; f.ctrl = ctrl; f.slot = io.slot; f.node = io.node_pos; f.t = io.t;
+    if (signals) { f.dep_signal = 1; f.dep_cnt = dep(DEP_FRAME); }
     return f;
-  };
-  // One LSTM cell as a whole, or cut along its K axis (fused_kernels.hip): EARLY = the segments that do not wait
-  // for the launch just before the cell (raw gate sums parked in `partial`), LATE = the segment that does, plus
-  // the parked sums, then the cell update.  which = 0: attention LSTM, cat[x_pre, ctx_prev | h_att]
-  // (decoder_cell.py:187), early = [ctx_prev | h_att]; which = 1: decoder LSTM, cat[h_att, ctx | h_dec] (:191),
-  // early = [h_att | h_dec].
-  auto lstm_args = [&](int which, LstmPart part) {
+  }
+
+  // One LSTM cell.  which = 0: attention LSTM, cat[x_pre, ctx_prev | h_att] (decoder_cell.py:187); which = 1: decoder LSTM,
+  // cat[h_att, ctx | h_dec] (:191).  gated: as the consumer role of a two-role launch (fused_kernels.hip) - the same cell, its
+  // K segments in the order kSegOrder gives, with a gate before the last one.  (Always LstmArgs mode 0: the whole cell.)
+  LstmArgs lstm(int which, bool gated) const {
     LstmArgs a;
     memset(&a, 0, sizeof(a));
     a.prec = prec;
     const int H = which ? Hd : Ha;
     const int k0 = which ? Ha : P;  // W_ih = [seg0 | ctx] columns
-    const void *x0, *x0l, *x1, *x1l, *x2, *x2l;
-    if (which == 0) {
-      x0 = prec ? (const void*)sb.xpre_h : sb.xpre; x0l = prec ? (const void*)sb.xpre_l : sb.xpre;
-      x2 = prec ? (const void*)sb.h_att_h[p] : sb.h_att[p]; x2l = prec ? (const void*)sb.h_att_l[p] : sb.h_att[p];
-    } else {
-      x0 = prec ? (const void*)sb.h_att_h[1 - p] : sb.h_att[1 - p]; x0l = prec ? (const void*)sb.h_att_l[1 - p] : sb.h_att[1 - p];
-      x2 = prec ? (const void*)sb.h_dec_h[p] : sb.h_dec[p]; x2l = prec ? (const void*)sb.h_dec_l[p] : sb.h_dec[p];
-    }
-    x1 = prec ? (const void*)sb.ctx_h : sb.ctx; x1l = prec ? (const void*)sb.ctx_l : sb.ctx;
-    const bool ck = prec && chunk_ok(d) && h->chunk_b;
+    const bool ck = prec && chunk_ok(d) && h->chunk_b();
     const Mat &ih = which ? bl.dec_ih : bl.att_ih, &hh = which ? bl.dec_hh : bl.att_hh;
     const f16 *wih_h = plane(ck ? ih.ch : ih.h), *wih_l = plane(ck ? ih.cl : ih.l), *whh_h = plane(ck ? hh.ch : hh.h), *whh_l = plane(ck ? hh.cl : hh.l);
     const float *wih = blob + ih.w, *whh = blob + hh.w;
     // column k0 of W_ih: row-major + k0 elements; chunked: chunk k0 / 32 of unit block 0 = k0 / 32 * (64 rows * 32) elements
     const size_t w1_off = ck ? (size_t)k0 * 64 : (size_t)k0;
-    auto W0 = [&](bool lo) { return prec ? (const void*)(lo ? wih_l : wih_h) : (const void*)wih; };
-    auto W1 = [&](bool lo) { return prec ? (const void*)((lo ? wih_l : wih_h) + w1_off) : (const void*)(wih + k0); };
-    auto W2 = [&](bool lo) { return prec ? (const void*)(lo ? whh_l : whh_h) : (const void*)whh; };
-    // leading "dimension" of a weight segment: row-major elements per row, or (chunked) the matrix's chunks per unit block
     const int wld_ih = ck ? (k0 + D) / kChunkK : k0 + D, wld_hh = ck ? H / kChunkK : H;
-    if (part == PART_WHOLE) {
-      a.a = act(make_seg3(x0, k0, k0, x1, D, D, x2, H, H)); a.a_lo = act(make_seg3(x0l, k0, k0, x1l, D, D, x2l, H, H));
-      a.w = make_seg3(W0(false), wld_ih, k0, W1(false), wld_ih, D, W2(false), wld_hh, H);
-      a.w_lo = make_seg3(W0(true), wld_ih, k0, W1(true), wld_ih, D, W2(true), wld_hh, H);
-      a.K = k0 + D + H;
-    } else if (part == PART_GATED && which == 0) {
-      // [ctx_prev | h_att | x_pre]: x_pre is written by the frame role of the same launch
-      a.a = act(make_seg3(x1, D, D, x2, H, H, x0, k0, k0)); a.a_lo = act(make_seg3(x1l, D, D, x2l, H, H, x0l, k0, k0));
-      a.w = make_seg3(W1(false), wld_ih, D, W2(false), wld_hh, H, W0(false), wld_ih, k0);
-      a.w_lo = make_seg3(W1(true), wld_ih, D, W2(true), wld_hh, H, W0(true), wld_ih, k0);
-      a.K = k0 + D + H;
+    const KSeg seg[3] = {
+        which ? KSeg{{sb.h_att[1 - p], sb.h_att_h[1 - p], sb.h_att_l[1 - p]}, k0, {wih, wih_h, wih_l}, wld_ih}
+              : KSeg{{sb.xpre, sb.xpre_h, sb.xpre_l}, k0, {wih, wih_h, wih_l}, wld_ih},
+        KSeg{{sb.ctx, sb.ctx_h, sb.ctx_l}, D, {wih + k0, wih_h + w1_off, wih_l + w1_off}, wld_ih},
+        which ? KSeg{{sb.h_dec[p], sb.h_dec_h[p], sb.h_dec_l[p]}, H, {whh, whh_h, whh_l}, wld_hh}
+              : KSeg{{sb.h_att[p], sb.h_att_h[p], sb.h_att_l[p]}, H, {whh, whh_h, whh_l}, wld_hh},
+    };
+    const int* o = kSegOrder[gated ? 1 + which : 0];
+    const KSeg &s0 = seg[o[0]], &s1 = seg[o[1]], &s2 = seg[o[2]];
+    auto a_segs = [&](int f) { return act(make_seg3(s0.a[f], s0.k, s0.k, s1.a[f], s1.k, s1.k, s2.a[f], s2.k, s2.k)); };
+    auto w_segs = [&](int f) { return make_seg3(s0.w[f], s0.ldw, s0.k, s1.w[f], s1.ldw, s1.k, s2.w[f], s2.ldw, s2.k); };
+    a.a = a_segs(prec ? 1 : 0); a.a_lo = a_segs(prec ? 2 : 0);
+    a.w = w_segs(prec ? 1 : 0); a.w_lo = w_segs(prec ? 2 : 0);
+    a.K = k0 + D + H;
+    if (gated && which == 0) {
       a.dep_n = frame_grid_size(32, P); a.dep_seg = 2; a.dep_which = 0;  // (the frame workgroups of one 32-row block)
       a.dep_cnt = dep(DEP_FRAME);
       a.live_lag = 1;  // (same launch as the frame kernel: see lstm_body)
-    } else if (part == PART_GATED) {
-      // [h_dec | h_att | ctx]: ctx is written by the attention role of the same launch, so it goes last; the exact-fp32 outputs
-      // are pinned to this summation order
-      a.a = act(make_seg3(x2, H, H, x0, k0, k0, x1, D, D)); a.a_lo = act(make_seg3(x2l, H, H, x0l, k0, k0, x1l, D, D));
-      a.w = make_seg3(W2(false), wld_hh, H, W0(false), wld_ih, k0, W1(false), wld_ih, D);
-      a.w_lo = make_seg3(W2(true), wld_hh, H, W0(true), wld_ih, k0, W1(true), wld_ih, D);
-      a.K = k0 + D + H;
+    } else if (gated) {
       a.dep_n = 32; a.dep_rows = 1; a.dep_seg = 2; a.dep_which = 1;  // (one attention workgroup per batch row)
       a.dep_cnt = dep(DEP_ATTN);
-    } else if (which == 0 ? part == PART_EARLY : part == PART_LATE) {
-      // [ctx (| h_att)]: the attention LSTM's early part, or the decoder LSTM's late part (ctx alone)
-      const int kh = which == 0 ? H : 0;
-      a.a = act(make_seg2(x1, D, D, x2, H, kh)); a.a_lo = act(make_seg2(x1l, D, D, x2l, H, kh));
-      a.w = make_seg2(W1(false), wld_ih, D, W2(false), wld_hh, kh); a.w_lo = make_seg2(W1(true), wld_ih, D, W2(true), wld_hh, kh);
-      a.K = D + kh;
-    } else {
-      // [seg0 (| h_dec)]: the attention LSTM's late part (x_pre alone), or the decoder LSTM's early part
-      const int kh = which == 1 ? H : 0;
-      a.a = act(make_seg2(x0, k0, k0, x2, H, kh)); a.a_lo = act(make_seg2(x0l, k0, k0, x2l, H, kh));
-      a.w = make_seg2(W0(false), wld_ih, k0, W2(false), wld_hh, kh); a.w_lo = make_seg2(W0(true), wld_ih, k0, W2(true), wld_hh, kh);
-      a.K = k0 + kh;
     }
     if (ck) { a.w.mpad = 1; a.w_lo.mpad = 1; }  // (flag: LoaderWLstm reads the chunked weight image)
-    a.mode = part == PART_GATED ? 0 : (int)part;
-    a.partial = which ? sb.pd : sb.pa;
     if (prec) { a.h_out_h = which ? sb.h_dec_h[1 - p] : sb.h_att_h[1 - p]; a.h_out_l = which ? sb.h_dec_l[1 - p] : sb.h_att_l[1 - p]; a.out_mpad = mpad; }
     a.bsum = blob + (which ? bl.dec_b : bl.att_b);
     a.h_prev = which ? sb.h_dec[p] : sb.h_att[p];
@@ -541,186 +536,166 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
     a.M = B; a.H = H; a.pz = d.p_zoneout; a.ctrl = ctrl; a.slot = io.slot; a.node = io.node_pos; a.dbg = io.dbg;
     a.tag = which;
     return a;
-  };
-  auto attn_args = [&]() {
+  }
+
+  // The attention pass; signals: as the producer role of a two-role launch
+  AttnArgs attn(bool signals = false) const {
     AttnArgs a;
     memset(&a, 0, sizeof(a));
     if (prec) { a.ctx_h = sb.ctx_h; a.ctx_l = sb.ctx_l; a.out_mpad = mpad; }
     a.memory = io.memory; a.q = sb.q; a.q_parts = query_split(d); a.q_stride = (size_t)B * D;
     a.w_prev = sb.w[p]; a.w_new = sb.w[1 - p]; a.w_out = io.w; a.ctx = sb.ctx;
     a.B = B; a.L = io.L; a.D = D; a.t_rel = io.t_rel; a.t_stride = io.t_stride; a.ctrl = ctrl; a.slot = io.slot; a.node = io.node_pos;
+    if (signals) { a.dep_signal = 1; a.dep_cnt = dep(DEP_ATTN); }
     return a;
-  };
-
-  // the attention query GEMM (decoder_cell.py:188 -> attention.py:105) as a job of the attention role's workgroups
-  auto query_role_args = [&]() {
-    ProjArgs pq;
-    memset(&pq, 0, sizeof(pq));
-    pq.prec = prec ? PREC_F16S : PREC_F32;
-    const Act in = query_in(1 - p, prec != 0);
-    pq.a = in.a; pq.a_lo = in.a_lo;
-    set_weight(pq, bl.wq, blob, pq.prec);
-    pq.ldw = query_ld(d); pq.M = B; pq.N = D; pq.K = query_k(d); pq.ksplit = proj_split(pq.K);
-    pq.split_stride = (size_t)B * D; pq.out = sb.q; pq.ldo = D; pq.ctrl = ctrl; pq.slot = io.slot; pq.mode = PROJ_QUERY;
-    pq.dep_cnt = dep(DEP_QUERY);
-    return pq;
-  };
-  auto query_attn_args = [&](const ProjArgs& pq) {
-    AttnArgs a = attn_args();
-    a.dep_signal = 1; a.dep_cnt = dep(DEP_ATTN);
+  }
+  // ... whose workgroups first compute the query tiles of pq between them
+  AttnArgs attn_after_query(const ProjArgs& pq) const {
+    AttnArgs a = attn(true);
     a.q_parts = pq.ksplit;
     a.q_tiles = proj_grid_size(B, D, pq.ksplit); a.q_wait_n = proj_grid_size(32, D, pq.ksplit); a.q_cnt = pq.dep_cnt;
     return a;
-  };
+  }
+
+  // What the query and projection GEMMs share, on either kernel (Args: GemmArgs / ProjArgs): [B, N] = in[B, K] * W^T, W = m's
+  // first K of ldw columns
+  template <class Args>
+  Args gemm(const Act& in, const Mat& m, int gprec, int ldw, int N, int K) const {
+    Args g;
+    memset(&g, 0, sizeof(g));
+    g.a = in.a; g.a_lo = in.a_lo; g.prec = gprec;
+    set_weight(g, m, blob, gprec);
+    g.ldw = ldw; g.M = B; g.N = N; g.K = K;
+    g.ctrl = ctrl; g.slot = io.slot;
+    return g;
+  }
+  template <class Args>  // its split-K form: slab z of ksplit to out + z * [B, ldo]
+  void split_k(Args& g, int ksplit, float* out, int ldo) const {
+    g.ksplit = ksplit; g.split_stride = (size_t)B * ldo; g.out = out; g.ldo = ldo;
+  }
+  void gemm_place(GemmArgs& g) const { g.node = io.node_pos; g.t = io.t; }
+
+  // PreNet layer 0 / 1 as a GEMM of its own (the three-launch form)
+  GemmArgs prenet_gemm(int layer) const {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    const int Ph = pre_hidden(d);
+    const Mat& m = layer ? bl.pre1 : bl.pre0;  // [Ph, d_mel] / [P, Ph]
+    g.K = g.ldw = (int)m.cols; g.N = g.ldo = (int)m.rows;
+    g.a = make_seg1(layer ? sb.xpre0 : sb.ynext, g.K, g.K);
+    g.W = blob + m.w; g.bias = blob + (layer ? bl.pre1_b : bl.pre0_b);
+    g.out = layer ? sb.xpre : sb.xpre0;
+    if (layer && prec) { g.out_h = sb.xpre_h; g.out_l = sb.xpre_l; g.out_kind = 1; }
+    g.M = B; g.ctrl = ctrl; g.slot = io.slot;
+    g.dropout_mode = io.dropout_mode;
+    // masks of one step: layer 0 [B, Ph] then layer 1 [B, P]
+    g.mask_step_stride = (size_t)B * (Ph + P);
+    g.mask_layer_off = layer ? (size_t)B * Ph : 0;
+    g.masks = io.masks ? io.masks + g.mask_layer_off : nullptr;
+    g.seed = io.seed; g.layer = layer; g.keep_scale = keep_scale();
+    g.r = d.r; g.d_mel = d.d_mel;
+    gemm_place(g);
+    return g;
+  }
+  // The attention query (decoder_cell.py:188 -> attention.py:105) from the new h_att (split-fp16 planes: the LSTM epilogues
+  // emitted them for h, the pack step for the weights): as a GEMM of its own ...
+  GemmArgs query_gemm() const {
+    GemmArgs g = gemm<GemmArgs>(query_in(1 - p, prec != 0), bl.wq, prec ? PREC_F16S : PREC_F32, query_ld(d), D, query_k(d));
+    split_k(g, query_split(d), sb.q, D);
+    g.kchunk = g.K / g.ksplit;
+    gemm_place(g);
+    return g;
+  }
+  // ... or as a job of the attention role's workgroups
+  ProjArgs query_role() const {
+    ProjArgs pq = gemm<ProjArgs>(query_in(1 - p, prec != 0), bl.wq, prec ? PREC_F16S : PREC_F32, query_ld(d), D, query_k(d));
+    split_k(pq, proj_split(pq.K), sb.q, D);
+    pq.mode = PROJ_QUERY;
+    pq.dep_cnt = dep(DEP_QUERY);
+    return pq;
+  }
+  // The mel/stop projection of the step whose new state is in buffers q, in arithmetic jprec: on the register-weight kernel
+  // (mode: PROJ_STEP / PROJ_HEAD / PROJ_FINAL) ...
+  ProjArgs proj_role(int q, int jprec, int mode) const {
+    ProjArgs pa = gemm<ProjArgs>(proj_in(q, jprec != PREC_F32), bl.proj, jprec, proj_ld(d), proj_n(d), proj_k(d));
+    split_k(pa, proj_parts(h, prec), sb.jparts, proj_ldp(d));
+    pa.node = io.node_pos;
+    pa.mode = mode;
+    return pa;
+  }
+  // ... or on the LDS-staged GEMM
+  GemmArgs proj_gemm(int q, int jprec) const {
+    GemmArgs g = gemm<GemmArgs>(proj_in(q, jprec != PREC_F32), bl.proj, jprec, proj_ld(d), proj_n(d), proj_k(d));
+    gemm_place(g);
+    if (use_frame(d)) {
+      // raw split-K partial sums; bias, leaky-ReLU, y / s / stop rule happen in the next frame kernel
+      split_k(g, split_of(g.K, kProjSplit), sb.jparts, proj_ldp(d));
+      g.kchunk = g.K / g.ksplit;
+      return g;
+    }
+    g.bias = blob + bl.proj_b;
+    g.y_out = io.y; g.s_out = io.s; g.ynext = sb.ynext; g.r = d.r; g.d_mel = d.d_mel;
+    g.t_rel = io.t_rel; g.t_stride = io.t_stride; g.stop_thr = 0.f; g.check_stop = 0;
+    return g;
+  }
+};
+
+// One launch of a step: which arguments, which launcher
+void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, Node node, hipStream_t st) {
+  const StepArgs s(h, sb, io);
   const int attn_variant = h->attn_form > 0 ? h->attn_form : 0;  // (measurement: fused_kernels.hip attn_lstm_f32_wide)
   switch (node) {
-    case N_F:
-    case N_FIN:
-      launch_frame(frame_args(node == N_FIN), st);
-      break;
-    case N_FA: {
-      FrameArgs f = frame_args(false);
-      f.dep_signal = 1; f.dep_cnt = dep(DEP_FRAME);
-      launch_frame_lstm(f, lstm_args(0, PART_GATED), st);
-      break;
-    }
-    case N_TD: {
-      AttnArgs a = attn_args();
-      a.dep_signal = 1; a.dep_cnt = dep(DEP_ATTN);
-      launch_attn_lstm(a, lstm_args(1, PART_GATED), nullptr, st, attn_variant);
-      break;
-    }
+    case N_F: launch_frame(s.frame(false), st); break;
+    case N_FIN: launch_frame(s.frame(true), st); break;
+    case N_FA: launch_frame_lstm(s.frame(false, true), s.lstm(0, true), st); break;
+    case N_A: launch_lstm(s.lstm(0, false), st); break;
+    case N_D: launch_lstm(s.lstm(1, false), st); break;
+    case N_T: launch_attn(s.attn(), st); break;
+    case N_TD: launch_attn_lstm(s.attn(true), s.lstm(1, true), nullptr, st, attn_variant); break;
     case N_QTD: {
-      const ProjArgs pq = query_role_args();
-      launch_attn_lstm(query_attn_args(pq), lstm_args(1, PART_GATED), &pq, st, attn_variant);
+      const ProjArgs pq = s.query_role();
+      launch_attn_lstm(s.attn_after_query(pq), s.lstm(1, true), &pq, st, attn_variant);
       break;
     }
     case N_AG:
     case N_DG: {
-      LstmArgs l = lstm_args(node == N_DG ? 1 : 0, PART_GATED);
+      LstmArgs l = s.lstm(node == N_DG ? 1 : 0, true);
       l.dep_n = 0;  // (alone: nothing to wait for)
       launch_lstm_lean(l, st);
       break;
     }
-    case N_A: launch_lstm(lstm_args(0, PART_WHOLE), st); break;
-    case N_D: launch_lstm(lstm_args(1, PART_WHOLE), st); break;
-    case N_T: launch_attn(attn_args(), st); break;
-    case N_P0:
-    case N_P1: {
-      const int layer = node == N_P0 ? 0 : 1;
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      const int Ph = pre_hidden(d);
-      if (layer == 0) {
-        g.a = make_seg1(sb.ynext, d.d_mel, d.d_mel);
-        g.W = blob + bl.pre0.w; g.ldw = d.d_mel; g.K = d.d_mel; g.bias = blob + bl.pre0_b;
-        g.out = sb.xpre0; g.N = Ph; g.ldo = Ph;
-      } else {
-        g.a = make_seg1(sb.xpre0, Ph, Ph);
-        g.W = blob + bl.pre1.w; g.ldw = Ph; g.K = Ph; g.bias = blob + bl.pre1_b;
-        g.out = sb.xpre; g.N = P; g.ldo = P;
-        if (prec) { g.out_h = sb.xpre_h; g.out_l = sb.xpre_l; g.out_kind = 1; }
-      }
-      g.M = B;
-      g.dropout_mode = io.dropout_mode;
-      // masks of one step: layer 0 [B, Ph] then layer 1 [B, P]
-      g.mask_step_stride = (size_t)B * (Ph + P);
-      g.mask_layer_off = layer ? (size_t)B * Ph : 0;
-      g.masks = io.masks ? io.masks + g.mask_layer_off : nullptr;
-      g.seed = io.seed; g.layer = layer; g.keep_scale = keep_scale;
-      g.r = d.r; g.d_mel = d.d_mel;
-      g.ctrl = ctrl; g.slot = io.slot; g.node = io.node_pos; g.t = io.t;
-      launch_gemm(g, A_PLAIN, EPI_RELU_DROPOUT, st);
-      break;
-    }
-    case N_Q: {
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      // (split-fp16 planes: the LSTM epilogues emitted them for h, the pack step for the weights)
-      const Act in = query_in(1 - p, prec != 0);
-      g.a = in.a; g.a_lo = in.a_lo; g.prec = prec ? PREC_F16S : PREC_F32;
-      set_weight(g, bl.wq, blob, g.prec);
-      g.ldw = query_ld(d); g.K = query_k(d); g.M = B; g.N = D; g.out = sb.q; g.ldo = D;
-      g.ksplit = query_split(d); g.kchunk = g.K / g.ksplit; g.split_stride = (size_t)B * D;
-      g.ctrl = ctrl; g.slot = io.slot; g.node = io.node_pos; g.t = io.t;
-      launch_gemm(g, A_PLAIN, EPI_PLAIN, st);
-      break;
-    }
+    case N_P0: launch_gemm(s.prenet_gemm(0), A_PLAIN, EPI_RELU_DROPOUT, st); break;
+    case N_P1: launch_gemm(s.prenet_gemm(1), A_PLAIN, EPI_RELU_DROPOUT, st); break;
+    case N_Q: launch_gemm(s.query_gemm(), A_PLAIN, EPI_PLAIN, st); break;
     case N_JFA:
     case N_JF:
     case N_JFIN:
     case N_J: {
-      // N_J: at the end of step t (buffer parity p).  N_JFA: the same GEMM for step t-1, at the head of step t's launch -
-      // step t-1's outputs are this step's "previous" buffers.  N_JFIN: io.slot carries the last step's parity.
+      // N_J: at the end of step t, whose new state is in buffers 1 - p.  N_JFA / N_JF: the same GEMM for step t-1, at the head of
+      // step t's launch - step t-1's outputs are this step's "previous" buffers p.  N_JFIN: io.slot carries the last step's parity.
       const bool head = node == N_JFA || node == N_JF;
-      const int p = head ? 1 - ((io.use_ctrl ? io.slot : io.t) & 1) : ((io.use_ctrl ? io.slot : io.t) & 1);
-      const int jprec = (prec && use_frame(d)) ? PREC_F16S : PREC_F32;  // (the three-launch form keeps the projection on fp32)
-      const Act in = proj_in(1 - p, jprec != PREC_F32);
-      if (proj_regw(h, prec)) {  // (same slabs, from the kernel that keeps its weight fragments in registers)
-        ProjArgs pa;
-        memset(&pa, 0, sizeof(pa));
-        pa.a = in.a; pa.a_lo = in.a_lo; pa.ldw = proj_ld(d); pa.prec = jprec;
-        set_weight(pa, bl.proj, blob, jprec);
-        pa.M = B; pa.N = proj_n(d); pa.K = proj_k(d); pa.ksplit = proj_parts(h, prec); pa.split_stride = (size_t)B * proj_ldp(d);
-        pa.out = sb.jparts; pa.ldo = proj_ldp(d); pa.ctrl = ctrl; pa.slot = io.slot; pa.node = io.node_pos;
-        pa.mode = head ? PROJ_HEAD : (node == N_JFIN ? PROJ_FINAL : PROJ_STEP);
-        if (head) {
-          FrameArgs f = frame_args(false);
-          f.dep_signal = 1; f.dep_cnt = dep(DEP_FRAME);
-          pa.dep_cnt = f.wait_cnt = dep(DEP_PROJ);
-          f.wait_n = proj_grid_size(32, pa.N, pa.ksplit);  // (the projection workgroups of one 32-row block)
-          if (node == N_JF) {  // no LSTM role behind the frame role: nobody to signal
-            f.dep_signal = 0;
-            launch_proj_frame(pa, f, st);
-            break;
-          }
-          launch_proj_frame_lstm(pa, f, lstm_args(0, PART_GATED), st);
-        } else {
-          launch_proj(pa, st);
-        }
+      const int q = head ? s.p : 1 - s.p;
+      const int jprec = (s.prec && use_frame(s.d)) ? PREC_F16S : PREC_F32;  // (the three-launch form keeps the projection on fp32)
+      if (!proj_regw(h, s.prec)) {
+        launch_gemm(s.proj_gemm(q, jprec), A_PLAIN, use_frame(s.d) ? EPI_PLAIN : EPI_PROJ, st);
         break;
       }
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.a = in.a; g.a_lo = in.a_lo; g.prec = jprec;
-      set_weight(g, bl.proj, blob, jprec);
-      g.ldw = proj_ld(d); g.K = proj_k(d); g.M = B; g.N = proj_n(d);
-      g.ctrl = ctrl; g.slot = io.slot; g.node = io.node_pos; g.t = io.t;
-      if (use_frame(d)) {
-        // raw split-K partial sums; bias, leaky-ReLU, y / s / stop rule happen in the next frame kernel
-        g.out = sb.jparts; g.ldo = proj_ldp(d);
-        g.ksplit = split_of(g.K, kProjSplit); g.kchunk = g.K / g.ksplit; g.split_stride = (size_t)B * proj_ldp(d);
-        launch_gemm(g, A_PLAIN, EPI_PLAIN, st);
+      // (same slabs, from the kernel that keeps its weight fragments in registers)
+      ProjArgs pa = s.proj_role(q, jprec, head ? PROJ_HEAD : (node == N_JFIN ? PROJ_FINAL : PROJ_STEP));
+      if (!head) {
+        launch_proj(pa, st);
         break;
       }
-      g.bias = blob + bl.proj_b;
-      g.y_out = io.y; g.s_out = io.s; g.ynext = sb.ynext; g.r = d.r; g.d_mel = d.d_mel;
-      g.t_rel = io.t_rel; g.t_stride = io.t_stride; g.stop_thr = 0.f; g.check_stop = 0;
-      launch_gemm(g, A_PLAIN, EPI_PROJ, st);
+      FrameArgs f = s.frame(false, node == N_JFA);  // (N_JF: no LSTM role behind the frame role, nobody to signal - no dep_cnt)
+      pa.dep_cnt = f.wait_cnt = s.dep(DEP_PROJ);
+      f.wait_n = proj_grid_size(32, pa.N, pa.ksplit);  // (the projection workgroups of one 32-row block)
+      if (node == N_JF) launch_proj_frame(pa, f, st);
+      else launch_proj_frame_lstm(pa, f, s.lstm(0, true), st);
       break;
     }
   }
 }
 
-const StepOrder kOrderProd = {7, {N_P0, N_P1, N_A, N_Q, N_T, N_D, N_J},   // decoder_cell.py:185-192
-                              {"prenet0", "prenet1", "lstm_att", "query", "attention", "lstm_dec", "proj"}};
-const StepOrder kOrderTaco2 = {7, {N_P0, N_P1, N_A, N_D, N_Q, N_T, N_J},  // decoder_cell.py:116-136
-                               {"prenet0", "prenet1", "lstm_att", "lstm_dec", "query", "attention", "proj"}};
-const StepOrder kOrderProdF = {6, {N_F, N_A, N_Q, N_T, N_D, N_J}, {"prenet", "lstm_att", "query", "attention", "lstm_dec", "proj"}};
-const StepOrder kOrderTaco2F = {6, {N_F, N_A, N_D, N_Q, N_T, N_J}, {"prenet", "lstm_att", "lstm_dec", "query", "attention", "proj"}};
-const StepOrder kOrderProdO = {5, {N_FA, N_Q, N_T, N_D, N_J}, {"prenet+lstm_att", "query", "attention", "lstm_dec", "proj"}};
-// ... and where one role per launch stays the rule: the projection at the head of the frame kernel's launch
-const StepOrder kOrderProdHF = {5, {N_JF, N_A, N_Q, N_T, N_D}, {"proj+prenet", "lstm_att", "query", "attention", "lstm_dec"}};
-const StepOrder kOrderTaco2HF = {5, {N_JF, N_A, N_D, N_Q, N_T}, {"proj+prenet", "lstm_att", "lstm_dec", "query", "attention"}};
-const StepOrder kOrderTaco2O = {5, {N_FA, N_D, N_Q, N_T, N_J}, {"prenet+lstm_att", "lstm_dec", "query", "attention", "proj"}};
-const StepOrder kOrderTaco2H = {4, {N_JFA, N_D, N_Q, N_T}, {"proj+prenet+lstm_att", "lstm_dec", "query", "attention"}};
-const StepOrder kOrderProdO2 = {4, {N_FA, N_Q, N_TD, N_J}, {"prenet+lstm_att", "query", "attention+lstm_dec", "proj"}};
-// ... with step t-1's projection at the head of step t's first launch
-const StepOrder kOrderProdH = {4, {N_JFA, N_Q, N_T, N_D}, {"proj+prenet+lstm_att", "query", "attention", "lstm_dec"}};
-const StepOrder kOrderProdH2 = {3, {N_JFA, N_Q, N_TD}, {"proj+prenet+lstm_att", "query", "attention+lstm_dec"}};
-// ... and with the query as a job of the attention role's workgroups: two launches per step
-const StepOrder kOrderProdO2Q = {3, {N_FA, N_QTD, N_J}, {"prenet+lstm_att", "query+attention+lstm_dec", "proj"}};
-const StepOrder kOrderProdH2Q = {2, {N_JFA, N_QTD}, {"proj+prenet+lstm_att", "query+attention+lstm_dec"}};
 // the two-role step: LJSpeech-type cell, either arithmetic mode
 int overlap_level(const ttsdec_handle* h, int B) {
   const ttsdec_dims& d = h->d;
@@ -780,17 +755,47 @@ bool query_role(const ttsdec_handle* h, int B) {
   const bool range = lstm_prec(h) ? (B >= 64 && B <= 384) : (B >= 192 && B <= 256);
   return range && proj_grid_size(B, d.d_ctx, ps) <= B;
 }
-const StepOrder& step_order(const ttsdec_handle* h, int B) {
-  const ttsdec_dims& d = h->d;
-  if (const int lv = overlap_level(h, B)) {
-    if (is_taco2(d)) return head_proj(h) ? kOrderTaco2H : kOrderTaco2O;
-    if (lv >= 2 && query_role(h, B)) return head_proj(h) ? kOrderProdH2Q : kOrderProdO2Q;
-    if (head_proj(h)) return lv >= 2 ? kOrderProdH2 : kOrderProdH;
-    return lv >= 2 ? kOrderProdO2 : kOrderProdO;
+// The launch's name in profiles (ttsdec_profile_step / _loop; bench.py's byte model splits it at '+' into the roles it holds)
+const char* node_name(Node n) {
+  switch (n) {
+    case N_P0: return "prenet0";
+    case N_P1: return "prenet1";
+    case N_F: return "prenet";
+    case N_JF: return "proj+prenet";
+    case N_FA: return "prenet+lstm_att";
+    case N_JFA: return "proj+prenet+lstm_att";
+    case N_A: return "lstm_att";
+    case N_Q: return "query";
+    case N_T: return "attention";
+    case N_D: return "lstm_dec";
+    case N_TD: return "attention+lstm_dec";
+    case N_QTD: return "query+attention+lstm_dec";
+    case N_J: return "proj";
+    default: return nullptr;  // (N_FIN, N_JFIN, N_AG, N_DG: in no step order)
   }
-  if (use_frame(d) && head_proj(h)) return is_taco2(d) ? kOrderTaco2HF : kOrderProdHF;
-  if (use_frame(d)) return is_taco2(d) ? kOrderTaco2F : kOrderProdF;
-  return is_taco2(d) ? kOrderTaco2 : kOrderProd;
+}
+StepOrder step_order(const ttsdec_handle* h, int B) {
+  const ttsdec_dims& d = h->d;
+  const int lv = overlap_level(h, B);
+  const bool head = head_proj(h);  // step t-1's projection at the head of step t's first launch (implies use_frame)
+  StepOrder o = {0, {}};
+  auto add = [&](Node n) { o.nodes[o.n++] = n; };
+  // the frame: PreNet layers alone, the frame kernel, or the frame kernel with lstm_att as the launch's second role
+  if (lv) add(head ? N_JFA : N_FA);
+  else if (use_frame(d)) add(head ? N_JF : N_F);
+  else { add(N_P0); add(N_P1); }
+  if (!lv) add(N_A);
+  if (is_taco2(d)) {  // decoder_cell.py:116-136
+    add(N_D); add(N_Q); add(N_T);
+  } else if (lv < 2) {  // decoder_cell.py:185-192
+    add(N_Q); add(N_T); add(N_D);
+  } else if (!query_role(h, B)) {
+    add(N_Q); add(N_TD);
+  } else {
+    add(N_QTD);  // the query as a job of the attention role's workgroups: two launches per step
+  }
+  if (!head) add(N_J);
+  return o;
 }
 
 bool has_two_role_node(const StepOrder& order) {
@@ -803,7 +808,7 @@ bool has_two_role_node(const StepOrder& order) {
 // kernel at the end of step t also produces the context bmm(w_t, memory) that step t+1 starts
 // from, decoder_cell.py:118.)
 void launch_step_serial(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io0, hipStream_t st) {
-  const StepOrder& order = step_order(h, io0.B);
+  const StepOrder order = step_order(h, io0.B);
   StepIo io = io0;
   for (int i = 0; i < order.n; ++i) {
     io.node_pos = i;
@@ -877,14 +882,6 @@ int& option_ref(ttsdec_handle* h, int o) {
     default: return h->opt_graph;
   }
 }
-// the derived switches the launch code reads (-1 = library default)
-void refresh_options(ttsdec_handle* h) {
-  h->use_graph = h->opt_graph != 0;
-  h->chunk_a = h->opt_chunk_a != 0;
-  h->chunk_b = h->opt_chunk_b != 0;
-  h->proj_regw = h->opt_proj_regw != 0;
-  drop_graph(h);  // a captured graph bakes the launch sequence in
-}
 void apply_env_options(ttsdec_handle* h) {
   if (const char* e = getenv("TTSDEC_OPTIONS")) {
     std::string str(e);
@@ -905,7 +902,6 @@ void apply_env_options(ttsdec_handle* h) {
       pos = end + 1;
     }
   }
-  refresh_options(h);
 }
 }  // namespace
 
@@ -986,7 +982,7 @@ int ttsdec_get_precision(const ttsdec_handle* h) {
 int ttsdec_set_option(ttsdec_handle* h, int option, int value) {
   if (!h || option < 0 || option >= TTSDEC_OPT_COUNT) return TTSDEC_ERR_INVALID_ARG;
   option_ref(h, option) = value;
-  refresh_options(h);
+  drop_graph(h);  // a captured graph bakes the launch sequence in
   return TTSDEC_OK;
 }
 
@@ -1164,7 +1160,7 @@ static int decode_impl(ttsdec_handle* h, const float* memory, int B, int L, int 
   StepIo io;
   memset(&io, 0, sizeof(io));
   io.B = B; io.L = L; io.use_ctrl = true;
-  if (h->use_graph && n_steps >= kGraphSlots / 2) {
+  if (h->use_graph() && n_steps >= kGraphSlots / 2) {
     rc = ensure_graph(h, sb, workspace, B, L);
     if (rc != TTSDEC_OK) return rc;
     for (int done = 0; done < n_steps; done += kGraphSlots) HIP_TRY(h, hipGraphLaunch(h->gexec, st));
@@ -1211,8 +1207,8 @@ int ttsdec_profile_loop(ttsdec_handle* h, const float* memory, int B, int L, int
                         uint64_t seed, float* y, float* s, float* w, int32_t* T_out, void* workspace, size_t workspace_bytes, void* stream,
                         float* ms_out, const char** names_out, int n_out, int* n_kernels, float* step_ms) {
   if (!h || !ms_out || !workspace || n_steps < 2 * kGraphSlots || n_steps % kGraphSlots) return TTSDEC_ERR_INVALID_ARG;
-  if (!h->use_graph) return TTSDEC_ERR_INVALID_ARG;  // (it is the replayed graph this function looks into)
-  const StepOrder& order = step_order(h, B);
+  if (!h->use_graph()) return TTSDEC_ERR_INVALID_ARG;  // (it is the replayed graph this function looks into)
+  const StepOrder order = step_order(h, B);
   if (n_kernels) *n_kernels = order.n;
   if (n_out < order.n || order.n >= kLoopStampNodes) return TTSDEC_ERR_INVALID_ARG;
   Carver cv{static_cast<float*>(workspace)};
@@ -1240,7 +1236,7 @@ int ttsdec_profile_loop(ttsdec_handle* h, const float* memory, int B, int L, int
       ++cnt;
     }
     ms_out[k] = (float)(sum / cnt);
-    if (names_out) names_out[k] = order.names[k];
+    if (names_out) names_out[k] = node_name(order.nodes[k]);
     total += ms_out[k];
   }
   if (step_ms) *step_ms = (float)total;
@@ -1506,7 +1502,7 @@ int ttsdec_profile_step(ttsdec_handle* h, const float* memory, int B, int L, int
                         size_t workspace_bytes, void* stream, float* ms_out, const char** names_out, int n_out,
                         int* n_kernels) {
   if (!h || !memory || !y || !s || !w || !workspace || !ms_out || iters <= 0) return TTSDEC_ERR_INVALID_ARG;
-  const StepOrder& order = step_order(h, B);
+  const StepOrder order = step_order(h, B);
   if (n_kernels) *n_kernels = order.n;
   if (n_out < order.n) return TTSDEC_ERR_INVALID_ARG;
   if (dropout_mode == TTSDEC_DROPOUT_MASKS && !masks) return TTSDEC_ERR_INVALID_ARG;
@@ -1533,7 +1529,7 @@ int ttsdec_profile_step(ttsdec_handle* h, const float* memory, int B, int L, int
   Node nodes[kMaxKernelsPerStep + 4];
   const char* names[kMaxKernelsPerStep + 4];
   int nn = 0;
-  for (int k = 0; k < order.n; ++k) { nodes[nn] = order.nodes[k]; names[nn++] = order.names[k]; }
+  for (int k = 0; k < order.n; ++k) { nodes[nn] = order.nodes[k]; names[nn++] = node_name(order.nodes[k]); }
   if (!is_taco2(h->d) && has_two_role_node(order) && n_out >= order.n + 4) {
     const Node extra[4] = {N_F, N_AG, N_T, N_DG};
     const char* extra_names[4] = {"prenet(alone)", "lstm_att_lean(alone)", "attention(alone)", "lstm_dec_lean(alone)"};

@@ -120,6 +120,9 @@ struct LstmArgs {
   // mode 0: whole cell.  mode 1: gates GEMM over the given segments only, raw sums stored to
   // partial [M, 4H] (PyTorch gate order) - the part of the cell that does not wait for the kernel
   // just before it.  mode 2: the remaining segments, + partial, then the cell update.
+  // No caller sets mode 1 any more (the two-launch split it served was measured and dropped, fused_kernels.hip): the decode
+  // step runs mode 0, the encoders mode 2 in sequence mode.  The field and the store path stay: with them taken out, in each of
+  // five forms tried, launch_lstm's 32-row exact-fp32 tile ran 0.3-0.5 us per step slower at B = 64 (profiles/README.md).
   int mode;
   float* partial;
   // Sequence mode (packed LSTM over a padded batch, Encoder2's BiLSTM): seq_lens != nullptr.
