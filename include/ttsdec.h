@@ -51,7 +51,8 @@ extern "C" {
  * conversion in front of ttsdec_mel_analysis; then ttsvits_disc_*, the waveform discriminators, a second handle kind under
  * ttsvits_ with a struct of its own; then ttsvits_durdisc_*, the duration discriminators, a third one; then ttsvits_durnll_*, the
  * stochastic duration predictor's likelihood, a fourth; then ttsvits_kl_loss_workspace_bytes, ttsvits_kl_loss,
- * ttsvits_slice_segments and ttsvits_sliced_l1, the glue of the validation step.) */
+ * ttsvits_slice_segments and ttsvits_sliced_l1, the glue of the validation step; then ttsdec_val_losses_workspace_bytes,
+ * ttsdec_val_losses and ttsdec_mel_loss, the loss terms of the Tacotron validation step.) */
 
 enum {
   TTSDEC_OK = 0,
@@ -797,6 +798,56 @@ size_t ttsdec_resample_workspace_bytes(const ttsdec_handle* h, int orig_freq, in
 int ttsdec_resample(ttsdec_handle* h, const float* wave, const int32_t* lengths, int B, int n_samples, int orig_freq, int new_freq,
                     int lowpass_filter_width, float rolloff, float* out, int n_out, int32_t* lengths_out, int32_t* status,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* The loss terms of the Tacotron validation step: what the reference's run_training_step (tacotron/tacotron.py:100-138) and
+ * TacotronTask.train_forward (tacotron/tacotron_lightning.py:50-99) compute from the forward's outputs - mel_loss_fn on the frames
+ * and on their differences, with and without a mask, the pos_weight BCE on the stop logits, alignment_std_loss and
+ * alignment_max_loss.  Weightless like the calls above (the handle gives the device and the error text); enqueues only; exact fp32.
+ *   y, y_post [B, T, D] fp32; y_post may be NULL.  y and x may both be NULL: the frame terms are then left out (zero).
+ *   x         [B, T_x, D], T_x >= T: only its first T frames count; indexed by its own batch stride (no x[:, :T] copy).
+ *   s         [B, T] stop logits, or NULL.
+ *   w         [B, S, L] attention weights of the S decoder steps, or NULL (S and L are then ignored).
+ *   lengths   [B] int32 frames of each utterance (device), len_b = clamp(lengths[b], 0, T); NULL: every utterance has T frames.
+ *   rows      [B, 9] out, the per-utterance sums:
+ *               0 / 1  A_y, A_p        sum over t < len_b and d of |y - x| (|y_post - x|)
+ *               2 / 3  Dall_y, Dall_p  sum over t < T - 1 and d of |(y[t+1] - y[t]) - (x[t+1] - x[t])|
+ *               4 / 5  Dmsk_y, Dmsk_p  the same over t + 1 < len_b
+ *               6      BCE             sum over t < T of (1 - z) s + (1 + (pos_weight - 1) z) (log1p(exp(-|s|)) + max(-s, 0)), z = (t < len_b)
+ *               7 / 8  V, M            sum over the steps of max(var, 0) and of 1 - max_l w, with S0 = sum_l w, m1 = sum_l w l and
+ *                                      var = sum_l w (l - m1)^2 + m1^2 (1 - S0): the reference's sum w l^2 - (sum w l)^2, without the
+ *                                      cancellation of that form in fp32
+ *   terms     [16] out; with N = sum_b len_b and N1 = sum_b max(len_b - 1, 0):
+ *               0 / 1  mel, mel_post            sum A / (D N)                 mel_loss_fn(., x, xmask, 1)
+ *               2 / 3  dmel_all, dmel_post_all  sum Dall / (B (T - 1) D)      run_training_step's unmasked difference term
+ *               4 / 5  dmel, dmel_post          sum Dmsk / (D N1)             TacotronTask's xmask[:, 1:] form
+ *               6      stop                     sum BCE / (B T)
+ *               7      w_std                    sqrt(sum V / (B S))
+ *               8      w_max                    sum M / (B S)
+ *               9 / 10 N, N1 as floats;  11 .. 15 zero, as are the terms of an operand that is NULL
+ *             A divisor of zero gives NaN, as the reference's 0 / 0 does: terms 0 and 1 when every length is 0, terms 4 and 5
+ *             when no length exceeds 1, terms 2 and 3 when T = 1.  The other terms are unaffected.
+ *   workspace ttsdec_val_losses_workspace_bytes(h, B, T, S) bytes (S = 0 without w), 256-byte aligned: the per-frame and per-step
+ *             sums.  Nothing beyond the reported size is touched.
+ * A workgroup of the frame pass owns TTSDEC_VAL_FRAME_RUN consecutive frames of one utterance and reads the one frame behind its
+ * run besides: y, y_post and x are read once (the halo frames twice), s and w once.  16-byte loads where D is a multiple of 4 and
+ * y, y_post and x are 16-byte aligned, 4-byte loads otherwise, with the same lane-to-channel map: the results do not depend on it.
+ * Every sum runs in a fixed order that depends on D, T, S, L and the utterance's own length only: no atomics, a row of `rows` is
+ * bit for bit what the utterance gets alone, and a call repeats bit for bit.
+ * TTSDEC_ERR_INVALID_ARG for h NULL or a size <= 0 (S, L: with w) or T_x < T; TTSDEC_ERR_DIMS for B > 65535, D > 1024 or a tensor
+ * of more than 2^31 elements; then NULL pointers (rows, terms; y without x or x without y; y_post without y; no operand at all);
+ * then TTSDEC_ERR_WORKSPACE; then TTSDEC_ERR_DEVICE.
+ *
+ * ttsdec_mel_loss is the plain form behind mel_loss_fn(y, x, mask, order) (tacotron.py:59-84): order 0 (|y - x| weighted by
+ * clip(mean_d x, 0.1) of the frame where y > x), 1 (L1) or 2 (squared error, the root of the mean), over t < len_b with lengths
+ * (sum / (D N)) and over every frame without (sum / (B T D)).  rows [B]: the per-utterance sums; out [1].  The same frame pass
+ * and the same refusals (order outside 0 .. 2: TTSDEC_ERR_INVALID_ARG); workspace: ttsdec_val_losses_workspace_bytes(h, B, T, 0). */
+#define TTSDEC_VAL_FRAME_RUN 32
+size_t ttsdec_val_losses_workspace_bytes(const ttsdec_handle* h, int B, int T, int S); /* 0: refused */
+int ttsdec_val_losses(ttsdec_handle* h, const float* y, const float* y_post, const float* x, int T_x, const float* s, const float* w,
+                      const int32_t* lengths, int B, int T, int D, int S, int L, float pos_weight, float* rows, float* terms,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int ttsdec_mel_loss(ttsdec_handle* h, const float* y, const float* x, int T_x, const int32_t* lengths, int B, int T, int D, int order,
+                    float* rows, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * VITS2 HiFi-GAN generator (latent z -> waveform): Generator.forward, vits2/models.py:900-974, with ResBlock1.forward

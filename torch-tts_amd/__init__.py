@@ -8,7 +8,8 @@ from .decoder_cell import LSTMZoneoutCell, PreNet, StepwiseMonotonicAttention, T
 from .engine import Engine, EngineDims
 from .postnet import Conv1dFix, MelPostnet, MelPostnet2
 from .style import GST, GST_VAE, STL, VAE, MultiHeadAttention, ReferenceEncoder, StyleEngine
-from .tacotron import Encoder2, Tacotron, build_tacotron, lengths_to_mask
+from .tacotron import (Encoder2, Tacotron, alignment_max_loss, alignment_std_loss, build_tacotron, lengths_to_mask, mel_loss_fn,
+                       run_validation_step, stop_loss, task_forward, validation_terms)
 from . import vits2  # noqa: F401  (TextEncoder, ResidualCouplingTransformersBlock, Generator, StochasticDurationPredictor, DurationPredictor, infer,
 #                             PosteriorEncoder, voice_conversion, forced_alignment, duration_loss, synthesizer_forward, validation_losses,
 #                             kl_loss, slice_segments, rand_slice_segments)
@@ -24,4 +25,5 @@ __all__ = [
     "Generator", "StochasticDurationPredictor", "DurationPredictor", "PosteriorEncoder",
     "DiscriminatorS", "DiscriminatorP", "MultiPeriodDiscriminator", "DurationDiscriminatorV1", "DurationDiscriminatorV2",
     "ReferenceEncoder", "STL", "GST", "VAE", "GST_VAE", "MultiHeadAttention", "StyleEngine",
+    "mel_loss_fn", "alignment_max_loss", "alignment_std_loss", "stop_loss", "validation_terms", "run_validation_step", "task_forward",
 ]

@@ -168,6 +168,14 @@ FAMILIES = (
             vp, sz, vp,                       # workspace, workspace_bytes, stream
         ]),
         "zero_tail": (i32, [vp, vp, vp, i32, i32, C.c_int64, i32, i32, vp]),  # h, x, lengths, B, T, batch_stride, C, len_div, stream
+        # the Tacotron validation step's loss terms (csrc/valstep.hip)
+        "val_losses_workspace_bytes": (sz, [vp, i32, i32, i32]),  # (h, B, T, S)
+        "val_losses": (i32, [
+            vp, vp, vp, vp, i32, vp, vp, vp,      # h, y, y_post, x, T_x, s, w, lengths
+            i32, i32, i32, i32, i32, f32,         # B, T, D, S, L, pos_weight
+            vp, vp, vp, sz, vp,                   # rows, terms, workspace, workspace_bytes, stream
+        ]),
+        "mel_loss": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),  # h, y, x, T_x, lengths, B, T, D, order, rows, out, ws, bytes, stream
         "postnet_workspace_bytes": _ws_bytes,
         "postnet": (i32, [vp, vp, i32, i32, i32, vp, vp, sz, vp]),
         "postnet_ragged": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]),  # h, y, lengths, B, T, precision, y_post, ws, bytes, stream

@@ -228,3 +228,43 @@ def mel_postnet2(post, x: Tensor) -> Tensor:
         h = blk[8](blk[7](blk[6](conv1d_fix(blk[5], h))))
         x = x + conv1d_fix(blk[9], h).transpose(1, 2)
     return x
+
+
+# ---- the loss functions of the training loop (tacotron.py:59-97, 120-123), for grad-enabled operands ----
+def mel_loss_fn(y: Tensor, x: Tensor, mask: Optional[Tensor] = None, order: int = 1) -> Tensor:
+    """mel_loss_fn, tacotron.py:59-84: order 0 = |y - x| weighted by clip(mean_d x, 0.1) where y > x, 1 = L1, anything else = root
+    mean square; with a mask [B, T, 1] the mean over the masked frames."""
+    _require_device(y, "y")
+    d = y - x
+    if order == 0:
+        vol = x.detach().mean(dim=2, keepdim=True).clip(min=0.1)
+        el = torch.where(d > 0, vol * d, -d)
+    elif order == 1:
+        el = d.abs()
+    else:
+        el = d * d
+    loss = el.mean() if mask is None else (el * mask).mean(dim=2).sum() / mask.sum()
+    return loss if order in (0, 1) else loss.sqrt()
+
+
+def alignment_max_loss(w: Tensor) -> Tensor:
+    """tacotron.py:87-89: the mean of 1 - max_l w."""
+    _require_device(w, "w")
+    return (1 - w.max(dim=2).values).mean()
+
+
+def alignment_std_loss(w: Tensor) -> Tensor:
+    """tacotron.py:92-97: sqrt(mean(clip(sum_l w l^2 - (sum_l w l)^2, 0)))."""
+    _require_device(w, "w")
+    pos = torch.arange(w.shape[2], device=w.device)[None, None, :]
+    var = (w * pos.square()).sum(dim=2) - (w * pos).sum(dim=2).square()
+    return var.clip(min=0).mean().sqrt()
+
+
+def stop_loss(s: Tensor, lengths: Tensor, pos_weight: float = 0.1) -> Tensor:
+    """tacotron.py:120-123: BCE-with-logits of the stop logits s [B, T(, 1)] against the prefix mask of lengths, pos_weight on
+    the frames inside the utterance."""
+    _require_device(s, "s")
+    s2 = s.reshape(s.shape[0], -1)
+    z = (torch.arange(s2.shape[1], device=s.device)[None, :] < lengths.to(s.device)[:, None]).to(s.dtype)
+    return F.binary_cross_entropy_with_logits(s2, z, pos_weight=torch.tensor([pos_weight], dtype=s.dtype, device=s.device))

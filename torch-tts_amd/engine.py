@@ -441,6 +441,45 @@ class Engine(Handle):
                                             len_div, _stream(self.device))
         self._err(rc, "ttsdec_zero_tail")
 
+    # ---- the validation step's loss terms (weightless; tacotron.py holds the entry points) ----
+    def val_losses(self, y: Optional[Tensor], y_post: Optional[Tensor], x: Optional[Tensor], s: Optional[Tensor], w: Optional[Tensor],
+                   lengths: Optional[Tensor], pos_weight: float = 0.1, shape: Optional[Tuple[int, int, int]] = None):
+        """y / y_post [B, T, D], x [B, T_x >= T, D], s [B, T], w [B, S, L] contiguous fp32 or None, lengths [B] int32 (device) or None ->
+        (rows [B, 9], terms [16]) (ttsdec_val_losses).  shape: (B, T, D) where y is None.  Enqueues only."""
+        B, T, D = y.shape if y is not None else shape
+        S, L = (w.shape[1], w.shape[2]) if w is not None else (0, 0)
+        nbytes = int(self._lib.ttsdec_val_losses_workspace_bytes(self._h, B, T, S))
+        if not nbytes:
+            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsdec_val_losses", f"B = {B}, T = {T}, S = {S}: needs B <= 65535 and at most 2^31 frames")
+        ws = self.workspace("val_losses", nbytes)
+        rows = torch.empty(B, 9, device=self.device)
+        terms = torch.empty(16, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsdec_val_losses(self._h, _ptr(y), _ptr(y_post), _ptr(x), T if x is None else x.shape[1], _ptr(s), _ptr(w),
+                                             _ptr(lengths), B, T, D, S, L, float(pos_weight), rows.data_ptr(), terms.data_ptr(),
+                                             ws.data_ptr(), nbytes, _stream(self.device))
+        if rc == _lib.ERR_DIMS:
+            raise _lib.DimsNotBuilt(rc, "ttsdec_val_losses", f"B = {B}, D = {D}: needs B <= 65535, D <= 1024 and tensors of at most 2^31 elements")
+        self._err(rc, "ttsdec_val_losses")
+        return rows, terms
+
+    def mel_loss(self, y: Tensor, x: Tensor, lengths: Optional[Tensor], order: int):
+        """y [B, T, D], x [B, T_x >= T, D] contiguous fp32, lengths [B] int32 (device) or None -> (rows [B], out [1]) (ttsdec_mel_loss)."""
+        B, T, D = y.shape
+        nbytes = int(self._lib.ttsdec_val_losses_workspace_bytes(self._h, B, T, 0))
+        if not nbytes:
+            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsdec_mel_loss", f"B = {B}, T = {T}: needs B <= 65535 and at most 2^31 frames")
+        ws = self.workspace("val_losses", nbytes)
+        rows = torch.empty(B, device=self.device)
+        out = torch.empty(1, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttsdec_mel_loss(self._h, y.data_ptr(), x.data_ptr(), x.shape[1], _ptr(lengths), B, T, D, int(order), rows.data_ptr(),
+                                           out.data_ptr(), ws.data_ptr(), nbytes, _stream(self.device))
+        if rc == _lib.ERR_DIMS:
+            raise _lib.DimsNotBuilt(rc, "ttsdec_mel_loss", f"B = {B}, D = {D}: needs B <= 65535, D <= 1024 and tensors of at most 2^31 elements")
+        self._err(rc, "ttsdec_mel_loss")
+        return rows, out
+
     def postnet(self, y: Tensor, precision: int = _lib.POSTNET_F32, lengths: Optional[Tensor] = None) -> Tensor:
         _require_device(y, "y")
         B, T, _ = y.shape
