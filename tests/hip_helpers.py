@@ -177,22 +177,32 @@ def device_cus(device=0):
     return torch.cuda.get_device_properties(device).multi_processor_count
 
 
-def postnet_bf16_emulation(y, pw, num_layers=3):
+def postnet_bf16_emulation(y, pw, num_layers=3, acc=torch.float32, leak=False):
     """The bf16 Postnet's own arithmetic on the CPU: operands rounded to bf16 between the layers, fp32 accumulation, fp32 BN +
-    isru, the residual in fp32.  y [B, T, d_mel] fp32; pw: oracle-style MelPostnet weights."""
+    isru, the residual in fp32.  y [B, T, d_mel] fp32; pw: oracle-style MelPostnet weights; the padding is the weight's
+    (taps - 1) / 2, as in O.mel_postnet.
+    acc=torch.float64: the same roundings with the sums (and BN + isru) in fp64 - a yardstick for how far summation order alone moves
+    the result.  leak=True (taps > 1): a deliberately WRONG emulation, in which the last frame of every utterance also receives the
+    first tap past its window (taps / 2 + 1) applied to frame 0 of the next utterance - the row that follows it in the flattened
+    [B * T, C] activation, i.e. what a conv whose window is not clipped at an utterance's edge would compute.  The tests show that
+    the bf16 bar tells it from the right one."""
     from oracle import tacotron_oracle as O
 
     def rb(x):
         return x.to(torch.bfloat16).to(torch.float32)
 
-    xc = rb(y).transpose(1, 2)
+    xc = rb(y).transpose(1, 2).to(acc)
     for i in range(num_layers):
-        xc = torch.nn.functional.conv1d(xc, rb(pw[f"conv.{i}.0.weight"]), None, padding=2)
-        inv = 1.0 / torch.sqrt(pw[f"conv.{i}.1.running_var"] + 1e-5)
-        alpha = pw[f"conv.{i}.1.weight"] * inv
-        beta = pw[f"conv.{i}.1.bias"] - pw[f"conv.{i}.1.running_mean"] * alpha
-        xc = rb(O.isru(xc * alpha[None, :, None] + beta[None, :, None]))
-    return y + torch.nn.functional.linear(xc.transpose(1, 2), rb(pw["fc_out.weight"]))
+        w = rb(pw[f"conv.{i}.0.weight"]).to(acc)
+        src = xc
+        xc = torch.nn.functional.conv1d(src, w, None, padding=(w.shape[2] - 1) // 2)
+        if leak:
+            xc[:, :, -1] += torch.roll(src[:, :, 0], -1, 0) @ w[:, :, w.shape[2] // 2 + 1].T
+        inv = 1.0 / torch.sqrt(pw[f"conv.{i}.1.running_var"].to(acc) + 1e-5)
+        alpha = pw[f"conv.{i}.1.weight"].to(acc) * inv
+        beta = pw[f"conv.{i}.1.bias"].to(acc) - pw[f"conv.{i}.1.running_mean"].to(acc) * alpha
+        xc = rb(O.isru(xc * alpha[None, :, None] + beta[None, :, None])).to(acc)
+    return (y.to(acc) + torch.nn.functional.linear(xc.transpose(1, 2), rb(pw["fc_out.weight"]).to(acc))).to(torch.float32)
 
 
 WS_GUARD = 4096  # bytes on each side of a guarded workspace
