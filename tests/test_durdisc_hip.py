@@ -1,23 +1,18 @@
 """GPU parity of the VITS2 duration discriminators (ttsvits_durdisc_* through torch_tts_amd.DurationDiscriminatorV1 / V2 and
 vits2.duration_discriminator_scores) against the fp64 restatement of tests/test_durdisc_host.py and the reference's recorded
 outputs.  The bar is the project's rtol 1e-4 / atol 1e-5 (tests/test_disc_host.py), on logits, probabilities and trunk output."""
+import copy
 import functools
 
 import pytest
 import torch
 
 import recipes
-from test_durdisc_host import ATOL, RTOL, _close, length_mask, load_golden, make_net, reference_durdisc
+from test_durdisc_host import ATOL, RTOL, SHAPES, _close, length_mask, load_golden, make_net, shape_case
 
 pytestmark = pytest.mark.gpu
 
-# in_channels, filter_channels, T, lengths:
-#   in != filter, N no multiple of 32, K = 72 no multiple of the K tile;  the model's own widths, M = 111 no multiple of a row
-#   tile, one utterance of a single token;  one token in all: the convs see only padding;  F = 256;  the row kernels' two- and
-#   four-piece forms (F > 256, F > 512), each with a last piece only some lanes hold
-SHAPES = {"c24f40": (24, 40, 9, [9, 4]), "c192": (192, 192, 37, [37, 20, 1]), "one": (24, 40, 1, [1]), "f256": (192, 256, 5, [5, 2]),
-          "f260": (8, 260, 3, [3, 1]), "f516": (8, 516, 2, [2, 1])}
-CASES = [(v, s) for v in (1, 2) for s in SHAPES]
+CASES = [(v, s) for v in (1, 2) for s in SHAPES]  # (the table: tests/test_durdisc_host.py, which also holds its margin condition)
 
 
 def _V():
@@ -29,16 +24,10 @@ def _V():
 @functools.lru_cache(maxsize=None)
 def case(version, shape):
     """The module on the device, its inputs, and the oracle's results - computed once and shared, never modified."""
-    C, F, T_, lengths = SHAPES[shape]
-    B, s = len(lengths), 100 * version + sum(ord(c) for c in shape)
-    net = make_net(version, C, F, 70 + s)
-    x = recipes.seeded_randn(6000 + s, B, C, T_)
-    dur_r = torch.log(recipes.seeded_ids(7000 + s, 8, B, 1, T_, low=1).float())
-    dur_hat = 0.8 + 0.7 * recipes.seeded_randn(8000 + s, B, 1, T_)
-    mask = length_mask(lengths, T_)
-    h, logits, probs = reference_durdisc(net.state_dict(), version, x, mask, [dur_r, dur_hat])
-    return dict(net=net.cuda(), x=x.cuda(), mask=mask.cuda(), dur_r=dur_r.cuda(), dur_hat=dur_hat.cuda(), lengths=lengths, h=h, logits=logits,
-                probs=probs, bias=net.state_dict()["output_layer.0.bias"].double().cpu())
+    c = shape_case(version, shape)
+    net = copy.deepcopy(c["net"])
+    return dict(net=net.cuda(), x=c["x"].cuda(), mask=c["mask"].cuda(), dur_r=c["dur_r"].cuda(), dur_hat=c["dur_hat"].cuda(), lengths=c["lengths"],
+                h=c["h"], logits=c["logits"], probs=c["probs"], bias=net.state_dict()["output_layer.0.bias"].double().cpu())
 
 
 def _pair(version, out):

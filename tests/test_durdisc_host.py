@@ -2,6 +2,7 @@
 reference's record, the ttsvits_durdisc_* C ABI's symbols, sizes and refusals, and the fp64 restatement below - the oracle of
 tests/test_durdisc_hip.py - against the reference's own outputs (tests/golden/make_golden_durdisc.py).  No GPU needed."""
 import ctypes as C
+import functools
 import json
 import os
 import re
@@ -39,18 +40,19 @@ def length_mask(lengths, T_):
 
 
 def _norm(sd, name, x):  # modules.LayerNorm: over the channels, eps 1e-5
-    return F.layer_norm(x.transpose(1, -1), (x.shape[1],), sd[name + ".gamma"].double(), sd[name + ".beta"].double(), 1e-5).transpose(1, -1)
+    return F.layer_norm(x.transpose(1, -1), (x.shape[1],), sd[name + ".gamma"].to(x.dtype), sd[name + ".beta"].to(x.dtype), 1e-5).transpose(1, -1)
 
 
 def _conv(sd, name, x):
-    return F.conv1d(x, sd[name + ".weight"].double(), sd[name + ".bias"].double(), padding=1)
+    return F.conv1d(x, sd[name + ".weight"].to(x.dtype), sd[name + ".bias"].to(x.dtype), padding=1)
 
 
-def reference_durdisc(sd, version, x, x_mask, durs):
-    """fp64 restatement of DurationDiscriminatorV<version>.forward (models.py:238-257 / 312-329) and forward_probability
-    (:222-236 / 298-310) with torch functional ops on a state dict: x [B, C, T], x_mask [B, 1, T], durs: [B, 1, T] each ->
-    (trunk h [B, F, T], logits and probabilities [B, T, 1] per duration)."""
-    x, m = x.double(), x_mask.double()
+def reference_durdisc(sd, version, x, x_mask, durs, dtype=torch.float64):
+    """Restatement of DurationDiscriminatorV<version>.forward (models.py:238-257 / 312-329) and forward_probability
+    (:222-236 / 298-310) with torch functional ops on a state dict, in fp64 (the oracle; torch.float32: the same ops, for the margin
+    condition below): x [B, C, T], x_mask [B, 1, T], durs: [B, 1, T] each -> (trunk h [B, F, T], logits and probabilities
+    [B, T, 1] per duration)."""
+    x, m = x.to(dtype), x_mask.to(dtype)
     v2 = version == 2
     h = _conv(sd, "conv_1", x * m)
     if v2:
@@ -60,29 +62,81 @@ def reference_durdisc(sd, version, x, x_mask, durs):
         h = _norm(sd, "norm_2", torch.relu(h))
     logits, probs = [], []
     for dur in durs:
-        logit = reference_logit(sd, version, h, m, dur)
+        logit = reference_logit(sd, version, h, m, dur, dtype)
         logits.append(logit)
         probs.append(torch.sigmoid(logit))
     return h, logits, probs
 
 
-def reference_logit(sd, version, h, m, dur):
-    """forward_probability up to the Sigmoid, fp64: h [B, F, T] -> [B, T, 1]."""
+def reference_logit(sd, version, h, m, dur, dtype=torch.float64):
+    """forward_probability up to the Sigmoid: h [B, F, T] -> [B, T, 1]."""
     v2 = version == 2
-    h, m = h.double(), m.double()
-    d = F.conv1d(dur.double(), sd["dur_proj.weight"].double(), sd["dur_proj.bias"].double())
+    h, m = h.to(dtype), m.to(dtype)
+    d = F.conv1d(dur.to(dtype), sd["dur_proj.weight"].to(dtype), sd["dur_proj.bias"].to(dtype))
     u = _conv(sd, "pre_out_conv_1", torch.cat([h, d], 1) * m)
     if v2:
         u = _norm(sd, "pre_out_norm_1", torch.relu(u))
     u = _conv(sd, "pre_out_conv_2", u * m)
     if v2:
         u = _norm(sd, "pre_out_norm_2", torch.relu(u))
-    return F.linear((u * m).transpose(1, 2), sd["output_layer.0.weight"].double(), sd["output_layer.0.bias"].double())
+    return F.linear((u * m).transpose(1, 2), sd["output_layer.0.weight"].to(dtype), sd["output_layer.0.bias"].to(dtype))
+
+
+# The parity table of tests/test_durdisc_hip.py (here, so that the margin condition below sees the same cases) - in_channels,
+# filter_channels, T, lengths:
+#   in != filter, N no multiple of 32, K = 72 no multiple of the K tile;  the model's own widths, M = 111 no multiple of a row
+#   tile, one utterance of a single token;  one token in all: the convs see only padding;  F = 256;  the row kernels' two- and
+#   four-piece forms (F > 256, F > 512), each with a last piece only some lanes hold;
+#   the ends of what ttsvits_durdisc_create accepts: C = F = 4;  F = 512 (two whole pieces), 768 (three whole), 772 (the fourth
+#   piece partial) and 1024 (four whole);  C = 1024 into F = 4;  C = F = 1024
+SHAPES = {"c24f40": (24, 40, 9, [9, 4]), "c192": (192, 192, 37, [37, 20, 1]), "one": (24, 40, 1, [1]), "f256": (192, 256, 5, [5, 2]),
+          "f260": (8, 260, 3, [3, 1]), "f516": (8, 516, 2, [2, 1]),
+          "c4f4": (4, 4, 5, [5, 2, 1]), "f512": (8, 512, 3, [3, 1]), "f768": (12, 768, 2, [2, 1]), "f772": (8, 772, 2, [2, 1]),
+          "c1024f4": (1024, 4, 3, [3, 1]), "max": (1024, 1024, 3, [3, 1])}
+MARGIN = 0.5  # of the bar: how far the fp32 restatement may lie from the fp64 one
+
+
+@functools.lru_cache(maxsize=None)
+def shape_case(version, shape):
+    """The CPU module of a SHAPES entry with its seeded inputs and the oracle's results - computed once, shared, never modified."""
+    C_in, F_ch, T_, lengths = SHAPES[shape]
+    B, s = len(lengths), 100 * version + sum(ord(c) for c in shape)
+    net = make_net(version, C_in, F_ch, 70 + s)
+    x = recipes.seeded_randn(6000 + s, B, C_in, T_)
+    dur_r = torch.log(recipes.seeded_ids(7000 + s, 8, B, 1, T_, low=1).float())
+    dur_hat = 0.8 + 0.7 * recipes.seeded_randn(8000 + s, B, 1, T_)
+    mask = length_mask(lengths, T_)
+    h, logits, probs = reference_durdisc(net.state_dict(), version, x, mask, [dur_r, dur_hat])
+    return dict(net=net, x=x, mask=mask, dur_r=dur_r, dur_hat=dur_hat, lengths=lengths, h=h, logits=logits, probs=probs)
+
+
+def bar_ratio(got, ref):
+    """max |got - ref| / (ATOL + RTOL |ref|): <= 1 is inside the parity bar."""
+    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    return float(((got - ref).abs() / (ATOL + RTOL * ref.abs())).max())
+
+
+@pytest.mark.parametrize("version,shape", [(v, s) for v in (1, 2) for s in SHAPES])
+def test_fp32_restatement_stays_within_half_of_the_bar_of_fp64(version, shape):
+    """The condition the GPU parity bar rests on - a condition on the case, not a measurement: the same ops in fp32 on the CPU
+    differ from the fp64 oracle by at most half of the bar on the trunk (times the mask, as the GPU test compares it), on both
+    logits and on both probabilities."""
+    c = shape_case(version, shape)
+    h, logits, probs = reference_durdisc(c["net"].state_dict(), version, c["x"], c["mask"], [c["dur_r"], c["dur_hat"]], torch.float32)
+    assert h.dtype == torch.float32 and c["h"].dtype == torch.float64
+    m = c["mask"].double()
+    worst = {"trunk": bar_ratio(h * c["mask"], c["h"] * m), "logit": max(bar_ratio(a, b) for a, b in zip(logits, c["logits"])),
+             "prob": max(bar_ratio(a, b) for a, b in zip(probs, c["probs"]))}
+    print(f"v{version} {shape}: fp32 restatement at " + ", ".join(f"{k} {v:.4f}" for k, v in worst.items()) + " of the bar")
+    assert max(worst.values()) <= MARGIN, (version, shape, worst)
 
 
 def _close(a, b, what):
     a, b = a.detach().cpu().double(), b.detach().cpu().double()
     assert a.shape == b.shape, (what, a.shape, b.shape)
+    if a.numel():
+        print(f"{what}: {float(((a - b).abs() / (ATOL + RTOL * b.abs())).max()):.4f} of the bar")
     torch.testing.assert_close(a, b, rtol=RTOL, atol=ATOL, msg=lambda m: f"{what}: {m}")
 
 

@@ -19,35 +19,13 @@ import pytest
 import torch
 
 import torch_tts_amd as T
+from style_corner_cases import randomize
 from test_style_host import CASES, _config, bar_ratio, case_inputs, make_module, stock_outputs
 from torch_tts_amd import style as S
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 RAGGED = (1, 63, 64, 127, 128)  # with T itself: one step by the clip, the last length of one step, the first of two, ...
-
-
-def randomize(m, seed):
-    """Fresh modules have zero biases and unit BatchNorm: move them (as the fixture's generator does), so that nothing cancels."""
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for k, v in m.state_dict().items():
-            if k.endswith("running_var"):
-                v.copy_(0.5 + torch.rand(v.shape, generator=g))
-            elif k.endswith("running_mean"):
-                v.add_(0.1 * torch.randn(v.shape, generator=g))
-            elif ".bns." in k and k.endswith(".weight"):
-                v.copy_(1.5 + 0.5 * torch.rand(v.shape, generator=g))
-            elif k.endswith("logvar_linear.bias"):
-                v.copy_(-1.0 + 0.5 * torch.randn(v.shape, generator=g))
-            elif k.endswith("mean_linear.bias"):
-                v.copy_(0.7 + 0.5 * torch.randn(v.shape, generator=g))
-            elif "bias" in k:
-                v.add_(0.1 * torch.randn(v.shape, generator=g))
-            elif k.endswith("convs.0.weight"):
-                v.mul_(3.0)
-    m.invalidate()
-    return m.eval()
 
 
 def lengths_for(B, T_):

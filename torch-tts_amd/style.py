@@ -156,10 +156,18 @@ class _StyleBase(PackedWeightsMixin, nn.Module):
                 and all(p.dtype == torch.float32 for p in self.parameters()) and self._dims_built())
 
     def _dims_built(self) -> bool:
+        """ttsenc_style_create's rule (csrc/style.hip), so that a module it would refuse takes the stock path instead of raising."""
         d = self.style_dims()
-        ok = all(f % 4 == 0 for f in d["filters"]) and len(d["filters"]) <= _lib.STYLE_MAX_CONVS and d["d_enc"] % 4 == 0 and d["d_enc"] <= 1024
-        ok = ok and d["d_emb"] <= 1024 and d["d_vae"] <= 256 and d["n_tokens"] <= 64 and d["n_heads"] <= 16
-        return ok and (d["n_heads"] == 0 or d["d_emb"] % d["n_heads"] == 0)
+        f, kind = d["filters"], d["kind"]
+        ok = d["n_mels"] > 0 and 1 <= len(f) <= _lib.STYLE_MAX_CONVS and all(0 < c <= 1024 and c % 4 == 0 for c in f)
+        ok = ok and 0 < d["d_enc"] <= 1024 and d["d_enc"] % 4 == 0
+        if kind != _lib.STYLE_ENCODER:
+            ok = ok and 0 < d["d_emb"] <= 1024
+        if kind in (_lib.STYLE_VAE, _lib.STYLE_GST_VAE):
+            ok = ok and 0 < d["d_vae"] <= 256
+        if kind in (_lib.STYLE_GST, _lib.STYLE_GST_VAE):
+            ok = ok and 0 < d["n_tokens"] <= 64 and 0 < d["n_heads"] <= 16 and d["d_emb"] % d["n_heads"] == 0
+        return ok
 
     def _hip_forward(self, inputs, input_lengths, eps):
         _host_lengths_check(input_lengths, inputs.shape[1])
