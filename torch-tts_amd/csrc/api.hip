@@ -369,30 +369,10 @@ int lstm_prec(const ttsdec_handle* h) {
 // rows per chunk of the activation planes when they are in the chunked layout (common.h Seg3), 0 = row-major
 int act_mpad(const ttsdec_handle* h, int B) { return (lstm_prec(h) && chunk_ok(h->d) && h->chunk_a()) ? rows_pad(B) : 0; }
 
-// ---- GEMM operands by precision: fp32 | split-fp16 hi + lo planes | one bf16 plane ----
-struct Planes {  // what a GEMM reads as a / a_lo (fp32 and bf16: the same pointer twice)
-  const void *p0, *p1;
-};
-template <class Args>  // GemmArgs / ProjArgs
-void set_weight(Args& g, const Mat& m, const float* blob, int prec) {
-  g.W = blob + (prec == PREC_F16S ? m.h : (prec == PREC_BF16 ? m.b : m.w));
-  g.W_lo = prec == PREC_F16S ? blob + m.l : g.W;
-}
-// x [n] fp32 as a first layer reads it: x itself, or its 16-bit form made in buf
-Planes act_input(int prec, const float* x, char* buf, size_t n, hipStream_t st) {
-  if (prec == PREC_F32) return {x, x};
-  f16* p = reinterpret_cast<f16*>(buf);
-  if (prec == PREC_BF16) { launch_to_bf16(x, buf, n, st); return {p, p}; }
-  launch_split(x, p, p + n, n, st);
-  return {p, p + n};
-}
-// the result [n = M * N] of g goes to buf in the form of `prec`: -> as the next layer reads it.  (16-bit modes leave g.out alone.)
-Planes set_output(GemmArgs& g, int prec, char* buf, size_t n) {
-  if (prec == PREC_F32) { g.out = reinterpret_cast<float*>(buf); return {buf, buf}; }
-  g.out_kind = prec == PREC_F16S ? 1 : 2;
-  g.out_h = reinterpret_cast<f16*>(buf);
-  if (prec == PREC_F16S) g.out_l = g.out_h + n;
-  return {g.out_h, prec == PREC_F16S ? g.out_l : g.out_h};
+// matrix m of the decoder blob as a GEMM's W / W_lo in `prec` (kernels.h Planes): its fp32 copy | hi + lo planes | bf16 plane
+Planes weight(const Mat& m, const float* blob, int prec) {
+  if (prec == PREC_F16S) return {blob + m.h, blob + m.l};
+  return planes_f32(blob + (prec == PREC_BF16 ? m.b : m.w));
 }
 
 // reads the two weight maxima back from the blob header (one small synchronous copy)
@@ -561,11 +541,7 @@ struct StepArgs {
   // first K of ldw columns
   template <class Args>
   Args gemm(const Act& in, const Mat& m, int gprec, int ldw, int N, int K) const {
-    Args g;
-    memset(&g, 0, sizeof(g));
-    g.a = in.a; g.a_lo = in.a_lo; g.prec = gprec;
-    set_weight(g, m, blob, gprec);
-    g.ldw = ldw; g.M = B; g.N = N; g.K = K;
+    Args g = gemm_args_seg<Args>(in.a, in.a_lo, weight(m, blob, gprec), ldw, gprec, B, N, K);
     g.ctrl = ctrl; g.slot = io.slot;
     return g;
   }
@@ -577,16 +553,13 @@ struct StepArgs {
 
   // PreNet layer 0 / 1 as a GEMM of its own (the three-launch form)
   GemmArgs prenet_gemm(int layer) const {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
     const int Ph = pre_hidden(d);
     const Mat& m = layer ? bl.pre1 : bl.pre0;  // [Ph, d_mel] / [P, Ph]
-    g.K = g.ldw = (int)m.cols; g.N = g.ldo = (int)m.rows;
-    g.a = make_seg1(layer ? sb.xpre0 : sb.ynext, g.K, g.K);
-    g.W = blob + m.w; g.bias = blob + (layer ? bl.pre1_b : bl.pre0_b);
+    GemmArgs g = gemm_args(planes_f32(layer ? sb.xpre0 : sb.ynext), (int)m.cols, weight(m, blob, PREC_F32), PREC_F32, B, (int)m.rows, (int)m.cols);
+    g.bias = blob + (layer ? bl.pre1_b : bl.pre0_b);
     g.out = layer ? sb.xpre : sb.xpre0;
     if (layer && prec) { g.out_h = sb.xpre_h; g.out_l = sb.xpre_l; g.out_kind = 1; }
-    g.M = B; g.ctrl = ctrl; g.slot = io.slot;
+    g.ctrl = ctrl; g.slot = io.slot;
     g.dropout_mode = io.dropout_mode;
     // masks of one step: layer 0 [B, Ph] then layer 1 [B, P]
     g.mask_step_stride = (size_t)B * (Ph + P);
@@ -664,9 +637,9 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
       launch_lstm_lean(l, st);
       break;
     }
-    case N_P0: launch_gemm(s.prenet_gemm(0), A_PLAIN, EPI_RELU_DROPOUT, st); break;
-    case N_P1: launch_gemm(s.prenet_gemm(1), A_PLAIN, EPI_RELU_DROPOUT, st); break;
-    case N_Q: launch_gemm(s.query_gemm(), A_PLAIN, EPI_PLAIN, st); break;
+    case N_P0: launch_gemm<A_PLAIN, EPI_RELU_DROPOUT>(s.prenet_gemm(0), st); break;
+    case N_P1: launch_gemm<A_PLAIN, EPI_RELU_DROPOUT>(s.prenet_gemm(1), st); break;
+    case N_Q: launch_gemm<A_PLAIN, EPI_PLAIN>(s.query_gemm(), st); break;
     case N_JFA:
     case N_JF:
     case N_JFIN:
@@ -677,7 +650,8 @@ void launch_node(const ttsdec_handle* h, const StepBufs& sb, const StepIo& io, N
       const int q = head ? s.p : 1 - s.p;
       const int jprec = (s.prec && use_frame(s.d)) ? PREC_F16S : PREC_F32;  // (the three-launch form keeps the projection on fp32)
       if (!proj_regw(h, s.prec)) {
-        launch_gemm(s.proj_gemm(q, jprec), A_PLAIN, use_frame(s.d) ? EPI_PLAIN : EPI_PROJ, st);
+        if (use_frame(s.d)) launch_gemm<A_PLAIN, EPI_PLAIN>(s.proj_gemm(q, jprec), st);
+        else launch_gemm<A_PLAIN, EPI_PROJ>(s.proj_gemm(q, jprec), st);
         break;
       }
       // (same slabs, from the kernel that keeps its weight fragments in registers)
@@ -1300,14 +1274,8 @@ static int postnet_impl(ttsdec_handle* h, const float* y, const int32_t* lengths
   const int Hh = d.postnet_hidden;
   // one layer on input a [M, cin]: a conv over `taps` frames (A_CONV), or taps = 0: a plain GEMM
   auto layer = [&](Planes a, int cin, int taps, const Mat& w) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.prec = prec;
-    g.a = make_seg1(a.p0, cin, cin); g.a_lo = make_seg1(a.p1, cin, cin);
-    if (taps) { g.T = T; g.Cin = cin; g.taps = taps; }
-    set_weight(g, w, h->blob, prec);
-    g.ldw = g.K = (int)w.cols; g.M = (int)M; g.N = g.ldo = (int)w.rows;
-    return g;
+    const Planes wp = weight(w, h->blob, prec);
+    return taps ? conv_gemm_args(a, wp, prec, (int)M, T, cin, taps, (int)w.rows) : gemm_args(a, cin, wp, prec, (int)M, (int)w.rows, cin);
   };
   // ragged batches: the tail of a [M, C] activation in the form of `prec` (fp32 rows, a bf16 plane, or a hi / lo fp16 plane pair)
   const int ew = prec == PREC_F32 ? 1 : 2;  // elements per 32-bit word
@@ -1340,7 +1308,7 @@ static int postnet_impl(ttsdec_handle* h, const float* y, const int32_t* lengths
         GemmArgs g = layer(a, c ? Hh : d.d_mel, d.postnet_kernel, L.p2[i][c]);
         g.alpha = h->blob + L.p2_alpha[i][c]; g.beta = h->blob + L.p2_beta[i][c];
         a = set_output(g, prec, pw.act[c], M * Hh);
-        launch_gemm(g, A_CONV, EPI_BN_LRELU, st);
+        launch_gemm<A_CONV, EPI_BN_LRELU>(g, st);
         mask(a, Hh);
       }
       GemmArgs g = layer(a, Hh, d.postnet_kernel, L.p2[i][2]);  // conv3 + residual
@@ -1349,7 +1317,7 @@ static int postnet_impl(ttsdec_handle* h, const float* y, const int32_t* lengths
       float* xnew = last ? y_post : reinterpret_cast<float*>(pw.xbuf[i & 1]);
       if (!last) x = set_output(g, prec, prec == PREC_F32 ? reinterpret_cast<char*>(xnew) : pw.xpl[i & 1], M * d.d_mel);
       g.out = xnew;  // (the 16-bit modes keep the fp32 stream beside the planes: the next layer's residual)
-      launch_gemm(g, A_CONV, EPI_RESIDUAL, st);
+      launch_gemm<A_CONV, EPI_RESIDUAL>(g, st);
       mask_f32(xnew);
       if (!last && prec != PREC_F32) mask(x, d.d_mel);
       xcur = xnew;
@@ -1376,12 +1344,12 @@ static int postnet_impl(ttsdec_handle* h, const float* y, const int32_t* lengths
       mask(in, Hh);
       continue;
     }
-    launch_gemm(g, A_CONV, EPI_BN_ISRU, st);
+    launch_gemm<A_CONV, EPI_BN_ISRU>(g, st);
     mask(in, Hh);
   }
   GemmArgs g = layer(in, Hh, 0, L.fc);
   g.resid = y; g.out = y_post;
-  launch_gemm(g, A_PLAIN, EPI_RESIDUAL, st);
+  launch_gemm<A_PLAIN, EPI_RESIDUAL>(g, st);
   mask_f32(y_post);
   return record_hip_error(h, "postnet");
 }

@@ -387,19 +387,26 @@ __global__ __launch_bounds__(kGemmThreads, Cfg::kWavesPerSimd) void gemm_rows_ke
   report_range(over, g.ctrl);
 }
 
+// One tile's launch: a workgroup per BM x BN outputs, gridDim.z = z (the K slices of a split-K EPI_PLAIN GEMM; 1 otherwise).
+template <class Cfg, int AK, int EK>
+static void launch_tile(const GemmArgs& a, hipStream_t st, int z = 1) {
+  const dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM, z);
+  hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
+}
+
 template <int AK, int EK, int PREC>
 static void launch_gemm_cfg(const GemmArgs& a, hipStream_t st) {
   // Pick the tile so the grid covers the 256 CUs when it can; small M uses 32x32 tiles
   // with the four MFMA waves splitting K.
   const long tiles_big = (long)((a.M + 63) / 64) * ((a.N + 63) / 64);
+  // split-K (EPI_PLAIN) is the 64 x 64 and 32 x 32 tiles': the 128 x 128 and lean tiles below launch one slice whatever ksplit says
+  const int z = (EK == EPI_PLAIN && a.ksplit > 1) ? a.ksplit : 1;
   if constexpr (PREC == PREC_F16S && EK == EPI_PLAIN) {
     // the step's small split-K GEMMs (query, mel/stop projection): 32x32 tiles on two MFMA waves that split a
     // 128-element K tile, so the grid stays as wide as the exact path's (these launches are latency-bound)
     if (tiles_big < 512) {
       using Cfg = TileCfg<1, 1, 2, 4, PREC_F16S>;
-      dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM, a.ksplit > 1 ? a.ksplit : 1);
-      hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
-      return;
+      return launch_tile<Cfg, AK, EK>(a, st, z);
     }
   }
   if constexpr (PREC != PREC_F32) {
@@ -414,9 +421,7 @@ static void launch_gemm_cfg(const GemmArgs& a, hipStream_t st) {
       static const bool lean_skinny = getenv("TTSDEC_NO_LEAN_SKINNY") == nullptr;
       if (lean_skinny && a.K <= 256 && a.M >= 2048) {
         using Cfg = TileCfg<2, 2, 1, 4, PREC_F16S, 0, 1, 1, 1>;
-        dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM);
-        hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
-        return;
+        return launch_tile<Cfg, AK, EK>(a, st);
       }
     }
     if (a.N >= 128 && a.M >= 2048) {
@@ -424,36 +429,24 @@ static void launch_gemm_cfg(const GemmArgs& a, hipStream_t st) {
       // this ran on until round 3 for the same bytes in flight (Postnet 256 x 600: split-fp16 3.44 -> 3.32 ms, bf16 1.26 ->
       // 1.19 ms, VITS2 flow 6.18 -> 6.13 ms, same box, bit-identical; profiles/r03_x_big_tile_full_depth.txt)
       using Cfg = TileCfg<2, 2, 1, 2, PREC, 0, 2, 2, 0>;
-      dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM);
-      hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
-      return;
+      return launch_tile<Cfg, AK, EK>(a, st);
     }
   }
   if (PREC != PREC_F32 || (a.fixed_tile != 1 && a.M >= 64 && tiles_big >= 512)) {  // (fixed_tile: kernels.h)
     // 64x64 tiles; ring: fp32 4 x 16 KiB, bf16 5 x 16 KiB, split-fp16 4 x 32 KiB
     using Cfg = TileCfg<2, 2, 1, (PREC == PREC_BF16 ? 5 : 4), PREC>;
-    dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM, (EK == EPI_PLAIN && a.ksplit > 1) ? a.ksplit : 1);
-    hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
+    launch_tile<Cfg, AK, EK>(a, st, z);
   } else {
     using Cfg = TileCfg<1, 1, 4, 4>;
-    dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM, (EK == EPI_PLAIN && a.ksplit > 1) ? a.ksplit : 1);
-    hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
+    launch_tile<Cfg, AK, EK>(a, st, z);
   }
 }
 
 // the generator's convs (A_CONV_DIL + EPI_LRELU2, exact fp32): a 128 x 32 tile where N is 32 (HiFi-GAN's last stage - the 64 x 64
 // tile would leave half its columns empty), the 64 x 64 tile elsewhere; both have 32-k tiles (LoaderConvDil's tap walk)
 static void launch_gemm_dil(const GemmArgs& a, hipStream_t st) {
-  constexpr int AK = A_CONV_DIL, EK = EPI_LRELU2;
-  if (a.N <= 32) {
-    using Cfg = TileCfg<4, 1, 1, 4>;
-    dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM);
-    hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
-  } else {
-    using Cfg = TileCfg<2, 2, 1, 4>;
-    dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM);
-    hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
-  }
+  if (a.N <= 32) launch_tile<TileCfg<4, 1, 1, 4>, A_CONV_DIL, EPI_LRELU2>(a, st);
+  else launch_tile<TileCfg<2, 2, 1, 4>, A_CONV_DIL, EPI_LRELU2>(a, st);
 }
 
 // ... and in split-fp16 (ttsvits_generator_forward): the 128 x 128 tile with full-depth stages (64 k) of launch_gemm_cfg for
@@ -465,47 +458,47 @@ static void launch_gemm_dil(const GemmArgs& a, hipStream_t st) {
 static void launch_gemm_dil_f16s(const GemmArgs& a, hipStream_t st) {
   constexpr int AK = A_CONV_DIL, EK = EPI_LRELU2;
   static const bool lean = getenv("TTSGEN_SPLIT_NO_LEAN") == nullptr;
-  auto go = [&](auto cfg) {
-    using Cfg = decltype(cfg);
-    dim3 grid((a.N + Cfg::BN - 1) / Cfg::BN, (a.M + Cfg::BM - 1) / Cfg::BM);
-    hipLaunchKernelGGL((gemm_rows_kernel<Cfg, AK, EK>), grid, dim3(kGemmThreads), 0, st, a);
-  };
-  if (a.N >= 128 && a.M >= 2048) go(TileCfg<2, 2, 1, 2, PREC_F16S, 0, 2, 2, 0>{});
-  else if (!lean) go(TileCfg<2, 2, 1, 4, PREC_F16S>{});
-  else if (a.N <= 32) go(TileCfg<4, 1, 1, 3, PREC_F16S, 0, 1, 1, 1>{});
-  else go(TileCfg<2, 2, 1, 4, PREC_F16S, 0, 1, 1, 1>{});
+  if (a.N >= 128 && a.M >= 2048) launch_tile<TileCfg<2, 2, 1, 2, PREC_F16S, 0, 2, 2, 0>, AK, EK>(a, st);
+  else if (!lean) launch_tile<TileCfg<2, 2, 1, 4, PREC_F16S>, AK, EK>(a, st);
+  else if (a.N <= 32) launch_tile<TileCfg<4, 1, 1, 3, PREC_F16S, 0, 1, 1, 1>, AK, EK>(a, st);
+  else launch_tile<TileCfg<2, 2, 1, 4, PREC_F16S, 0, 1, 1, 1>, AK, EK>(a, st);
 }
 
+// The pairs of (A operand, epilogue) that exist, and the arithmetic each runs in by GemmArgs::prec:
+//   A_PLAIN + EPI_RELU_DROPOUT, EPI_PROJ          exact fp32 whatever prec says
+//   A_PLAIN + EPI_PLAIN                           exact fp32 or split-fp16 (bf16 runs as fp32)
+//   A_PLAIN + EPI_RESIDUAL, EPI_GENERIC           exact fp32, split-fp16 or bf16
+//   A_CONV  + EPI_BN_ISRU, EPI_BN_LRELU, EPI_BN_ISRLU, EPI_RESIDUAL, EPI_GENERIC   exact fp32, split-fp16 or bf16
+//   A_CONV_DIL + EPI_LRELU2                       exact fp32 or split-fp16 (bf16: no kernel, nothing is launched)
+// Any other pair is a link error at its call site.
 template <int AK, int EK>
-static void launch_gemm_prec(const GemmArgs& a, hipStream_t st) {
-  if (a.prec == PREC_F16S) return launch_gemm_cfg<AK, EK, PREC_F16S>(a, st);
-  if (a.prec == PREC_BF16) return launch_gemm_cfg<AK, EK, PREC_BF16>(a, st);
-  return launch_gemm_cfg<AK, EK, PREC_F32>(a, st);
-}
-
-void launch_gemm(const GemmArgs& a, AKind ak, EpiKind ek, hipStream_t st) {
+void launch_gemm(const GemmArgs& a, hipStream_t st) {
+  constexpr bool kHasF16S = EK != EPI_RELU_DROPOUT && EK != EPI_PROJ, kHasBf16 = kHasF16S && EK != EPI_PLAIN;
   if (a.M <= 0 || a.N <= 0) return;
-  if (ak == A_CONV_DIL) {
-    if (ek == EPI_LRELU2 && a.prec == PREC_F32) launch_gemm_dil(a, st);
-    else if (ek == EPI_LRELU2 && a.prec == PREC_F16S) launch_gemm_dil_f16s(a, st);
-    return;
-  }
-  if (ak == A_CONV && ek == EPI_BN_ISRU) return launch_gemm_prec<A_CONV, EPI_BN_ISRU>(a, st);
-  if (ak == A_CONV && ek == EPI_BN_LRELU) return launch_gemm_prec<A_CONV, EPI_BN_LRELU>(a, st);
-  if (ak == A_CONV && ek == EPI_BN_ISRLU) return launch_gemm_prec<A_CONV, EPI_BN_ISRLU>(a, st);
-  if (ak == A_CONV && ek == EPI_RESIDUAL) return launch_gemm_prec<A_CONV, EPI_RESIDUAL>(a, st);
-  if (ak == A_CONV && ek == EPI_GENERIC) return launch_gemm_prec<A_CONV, EPI_GENERIC>(a, st);
-  if (ek == EPI_GENERIC) return launch_gemm_prec<A_PLAIN, EPI_GENERIC>(a, st);
-  switch (ek) {
-    case EPI_PLAIN:
-      if (a.prec == PREC_F16S) return launch_gemm_cfg<A_PLAIN, EPI_PLAIN, PREC_F16S>(a, st);
-      return launch_gemm_cfg<A_PLAIN, EPI_PLAIN, PREC_F32>(a, st);
-    case EPI_RELU_DROPOUT: return launch_gemm_cfg<A_PLAIN, EPI_RELU_DROPOUT, PREC_F32>(a, st);
-    case EPI_PROJ: return launch_gemm_cfg<A_PLAIN, EPI_PROJ, PREC_F32>(a, st);
-    case EPI_RESIDUAL: return launch_gemm_prec<A_PLAIN, EPI_RESIDUAL>(a, st);
-    default: return;
+  if constexpr (AK == A_CONV_DIL) {
+    if (a.prec == PREC_F32) launch_gemm_dil(a, st);
+    else if (a.prec == PREC_F16S) launch_gemm_dil_f16s(a, st);
+  } else {
+    if constexpr (kHasF16S) {
+      if (a.prec == PREC_F16S) return launch_gemm_cfg<AK, EK, PREC_F16S>(a, st);
+    }
+    if constexpr (kHasBf16) {
+      if (a.prec == PREC_BF16) return launch_gemm_cfg<AK, EK, PREC_BF16>(a, st);
+    }
+    launch_gemm_cfg<AK, EK, PREC_F32>(a, st);
   }
 }
+template void launch_gemm<A_PLAIN, EPI_PLAIN>(const GemmArgs&, hipStream_t);
+template void launch_gemm<A_PLAIN, EPI_RELU_DROPOUT>(const GemmArgs&, hipStream_t);
+template void launch_gemm<A_PLAIN, EPI_PROJ>(const GemmArgs&, hipStream_t);
+template void launch_gemm<A_PLAIN, EPI_RESIDUAL>(const GemmArgs&, hipStream_t);
+template void launch_gemm<A_PLAIN, EPI_GENERIC>(const GemmArgs&, hipStream_t);
+template void launch_gemm<A_CONV, EPI_BN_ISRU>(const GemmArgs&, hipStream_t);
+template void launch_gemm<A_CONV, EPI_BN_LRELU>(const GemmArgs&, hipStream_t);
+template void launch_gemm<A_CONV, EPI_BN_ISRLU>(const GemmArgs&, hipStream_t);
+template void launch_gemm<A_CONV, EPI_RESIDUAL>(const GemmArgs&, hipStream_t);
+template void launch_gemm<A_CONV, EPI_GENERIC>(const GemmArgs&, hipStream_t);
+template void launch_gemm<A_CONV_DIL, EPI_LRELU2>(const GemmArgs&, hipStream_t);
 
 // ===========================================================================
 // LSTM cell launches (body: step_bodies.h lstm_body)

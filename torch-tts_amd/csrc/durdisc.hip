@@ -259,18 +259,12 @@ void launch_rows(void (*k1)(Args), void (*k2)(Args), void (*k4)(Args), const Arg
 
 // out [M, c.N] = [mask *] [relu](conv_3(a [M, c.K]) [+ bias]); M = rows of period T
 void conv(const float* blob, const Conv& c, const float* a, float* out, int M, int T, bool bias, int act, const float* mask, hipStream_t st) {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.M = M; g.N = c.N; g.K = kTaps * c.K; g.ldw = kTaps * c.K;
-  g.T = T; g.Cin = c.K; g.taps = kTaps;
-  g.a = make_seg1(a, c.K, c.K); g.a_lo = g.a;
-  g.W = blob + c.w; g.W_lo = g.W;
-  g.prec = PREC_F32;
+  GemmArgs g = conv_gemm_args(planes_f32(a), planes_f32(blob + c.w), PREC_F32, M, T, c.K, kTaps, c.N);
   g.bias = bias ? blob + c.b : nullptr;
   g.act = act; g.row_mask = mask;
-  g.out = out; g.ldo = c.N;
+  g.out = out;
   g.fixed_tile = 1;
-  launch_gemm(g, A_CONV, EPI_GENERIC, st);
+  launch_gemm<A_CONV, EPI_GENERIC>(g, st);
 }
 
 struct DurDiscWs {

@@ -164,43 +164,24 @@ int ttsenc_forward(ttsenc_handle* h, const int64_t* ids, const int32_t* lengths,
   // In split-fp16 mode the convs and the input projection run on two fp16 planes per operand (gemm_tile.h): one elementwise
   // pass makes the hi / lo planes of each A operand.
   const bool split = h->precision == TTSDEC_PREC_SPLIT_F16 && !(E & 7);  // (ttsenc_set_precision; exact fp32 MFMAs otherwise)
-  f16* ph = reinterpret_cast<f16*>(ws + W.planes);
+  const int prec = split ? PREC_F16S : PREC_F32;
+  void* ph = ws + W.planes;
   const float* in = x;
   for (int i = 0; i < 3; ++i) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = make_seg1(in, E, E); g.a_lo = g.a;
-    g.T = L; g.Cin = E; g.taps = d.conv_kernel;
-    set_weight_contiguous(g, blob + bl.conv_w[i], (size_t)E * d.conv_kernel * E, split);
-    g.ldw = d.conv_kernel * E; g.K = d.conv_kernel * E;
-    if (split) {
-      const size_t n = (size_t)M * E;
-      launch_split(in, ph, ph + n, n, st);
-      g.a = make_seg1(ph, E, E); g.a_lo = make_seg1(ph + n, E, E);
-      g.prec = PREC_F16S;
-    }
-    g.M = M; g.N = E;
+    GemmArgs g = conv_gemm_args(act_input(prec, in, ph, (size_t)M * E, st),
+                                weight_contiguous(blob + bl.conv_w[i], (size_t)E * d.conv_kernel * E, split), prec, M, L, E, d.conv_kernel, E);
     g.alpha = blob + bl.alpha[i]; g.beta = blob + bl.beta[i];
-    if (i < 2) { g.out = F(W.act[i]); g.ldo = E; in = g.out; }
+    if (i < 2) { g.out = F(W.act[i]); in = g.out; }
     else { g.out = cat; g.ldo = 2 * E; }
-    launch_gemm(g, A_CONV, EPI_BN_ISRLU, st);
+    launch_gemm<A_CONV, EPI_BN_ISRLU>(g, st);
   }
   // input projections of both directions for every (b, t): gx [M, 8H] = cat [M, 2E] . W_ih^T
   {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = make_seg1(cat, 2 * E, 2 * E); g.a_lo = g.a;
-    set_weight_contiguous(g, blob + bl.w_ih, (size_t)8 * H * 2 * E, split);
-    g.ldw = 2 * E; g.K = 2 * E; g.M = M; g.N = 8 * H; g.out = gx; g.ldo = 8 * H;
-    if (split) {
-      const size_t n = (size_t)M * 2 * E;
-      launch_split(cat, ph, ph + n, n, st);
-      g.a = make_seg1(ph, 2 * E, 2 * E); g.a_lo = make_seg1(ph + n, 2 * E, 2 * E);
-      g.prec = PREC_F16S;
-      launch_gemm(g, A_PLAIN, EPI_GENERIC, st);  // (the precision-aware plain epilogue: no bias / mask / residual here)
-    } else {
-      launch_gemm(g, A_PLAIN, EPI_PLAIN, st);
-    }
+    GemmArgs g = gemm_args(act_input(prec, cat, ph, (size_t)M * 2 * E, st), 2 * E, weight_contiguous(blob + bl.w_ih, (size_t)8 * H * 2 * E, split),
+                           prec, M, 8 * H, 2 * E);
+    g.out = gx;
+    if (split) launch_gemm<A_PLAIN, EPI_GENERIC>(g, st);  // (the precision-aware plain epilogue: no bias / mask / residual here)
+    else launch_gemm<A_PLAIN, EPI_PLAIN>(g, st);
   }
   // initial state (rnn.py:117-118: rnn_h0 / rnn_c0 chunked over the two directions), zero-padded output
   for (int dir = 0; dir < 2; ++dir) {

@@ -243,25 +243,6 @@ __global__ __launch_bounds__(256) void conv_post_tanh_kernel(const float* __rest
   out[m] = tanhf(acc);
 }
 
-// one conv of the generator (its record c, weights in blob): x [M, Cin] channel-last in utterances of T frames, W [N, taps * Cin]
-GemmArgs conv_args(const GConv& c, const float* blob, const float* x, int M, int T, int dil) {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.a = make_seg1(x, c.Cin, c.K());
-  g.a_lo = g.a;
-  g.T = T; g.Cin = c.Cin; g.taps = c.taps; g.dil = dil;
-  g.W = blob + c.w; g.W_lo = g.W; g.ldw = c.K(); g.prec = PREC_F32;
-  g.M = M; g.N = c.N; g.K = c.K();
-  g.bias = blob + c.b;
-  g.ldo = c.N;
-  g.slope2 = kLrelu;
-  return g;
-}
-
-// the planes of an n-element tensor held in n floats: hi, then lo
-f16* plane_hi(const float* p) { return reinterpret_cast<f16*>(const_cast<float*>(p)); }
-f16* plane_lo(const float* p, size_t n) { return plane_hi(p) + n; }
-
 // ttsgen_pack_weights' step for one conv: its weight and bias from src into the blob b
 void pack_conv(const float* const* src, float* b, const GConv& c, hipStream_t st) {
   if (c.u > 0) {
@@ -275,7 +256,7 @@ void pack_conv(const float* const* src, float* b, const GConv& c, hipStream_t st
 }
 // ttsvits_generator_pack_planes' step: the planes of a split conv's packed weight, from the blob b into the planes buffer p
 void split_conv(const float* b, float* p, const GConv& c, hipStream_t st) {
-  if (c.split) launch_split(b + c.w, plane_hi(p + c.p), plane_lo(p + c.p, c.n()), c.n(), st);
+  if (c.split) planes_split(b + c.w, p + c.p, c.n(), st);
 }
 
 // the forward pass over one group of G utterances; n_stages < n_up stops early (ttsgen_forward_stages).  planes == nullptr: exact
@@ -290,38 +271,31 @@ void run_group(const ttsgen_handle* h, const float* planes, const float* z, cons
   float *Y = w.Y, *X = w.X, *LX = w.LX, *H = w.H, *R = w.R, *LR = w.LR, *condv = w.condv;
   const int C0 = d.upsample_initial_channel;
   auto split = [&](const GConv& c) { return planes != nullptr && c.split; };  // this call runs c in split-fp16
-  // one conv: x as fp32, or (a split layer) as the planes its producer left, with the weight planes at c.p
+  // one conv of the generator (its record c): x [M, Cin] channel-last in utterances of Tx frames, W [N, taps * Cin] - x as fp32, or
+  // (a split layer) as the planes its producer left, with the weight planes at c.p.  (The planes of an n-element tensor are held
+  // in n floats: hi, then lo.)
   auto conv = [&](const GConv& c, const float* x, int M, int Tx, int dil) {
-    GemmArgs a = conv_args(c, b, x, M, Tx, dil);
-    if (split(c)) {
-      a.a = make_seg1(plane_hi(x), c.Cin, c.K());
-      a.a_lo = make_seg1(plane_lo(x, (size_t)M * c.Cin), c.Cin, c.K());
-      a.W = plane_hi(planes + c.p);
-      a.W_lo = plane_lo(planes + c.p, c.n());
-      a.prec = PREC_F16S;
-    }
+    const bool s = split(c);
+    GemmArgs a = conv_gemm_args(s ? planes_at(x, (size_t)M * c.Cin) : planes_f32(x), s ? planes_at(planes + c.p, c.n()) : planes_f32(b + c.w),
+                                s ? PREC_F16S : PREC_F32, M, Tx, c.Cin, c.taps, c.N, dil);
+    a.bias = b + c.b;
+    a.slope2 = kLrelu;
     return a;
   };
   // launches it with its activated output in dst: fp32, or the planes a split consumer reads (as_planes)
   auto launch = [&](GemmArgs& a, float* dst, bool as_planes) {
     const size_t n = (size_t)a.M * a.N;
-    if (!as_planes) {
-      a.out2 = dst;
-    } else if (a.prec == PREC_F16S) {
-      a.out_kind = 1;
-      a.out_h = plane_hi(dst);
-      a.out_l = plane_lo(dst, n);
-    } else {
-      a.out2 = w.tmp;  // (an exact layer in front of a split one)
-    }
-    launch_gemm(a, A_CONV_DIL, EPI_LRELU2, st);
-    if (as_planes && a.prec != PREC_F16S) launch_split(w.tmp, plane_hi(dst), plane_lo(dst, n), n, st);
+    if (!as_planes) a.out2 = dst;
+    else if (a.prec == PREC_F16S) set_output(a, PREC_F16S, dst, n);
+    else a.out2 = w.tmp;  // (an exact layer in front of a split one)
+    launch_gemm<A_CONV_DIL, EPI_LRELU2>(a, st);
+    if (as_planes && a.prec != PREC_F16S) planes_split(w.tmp, dst, n, st);
   };
   if (g != nullptr) launch_cond(g, b + L.cond_w.off, b + L.cond_b.off, condv, G, C0, d.gin_channels, st);
   // models.py:948-950: x = conv_pre(x) (+ cond(g)); the first stage reads lrelu(x, 0.1) (:953)
   {
     const size_t nz = (size_t)G * T * d.initial_channel;
-    if (split(L.pre)) launch_split(z, plane_hi(w.zp), plane_lo(w.zp, nz), nz, st);
+    if (split(L.pre)) planes_split(z, w.zp, nz, st);
     GemmArgs a = conv(L.pre, split(L.pre) ? w.zp : z, G * T, T, 1);
     a.rowvec = g != nullptr ? condv : nullptr;
     a.slope2 = n_stages == 0 && d.n_up == 0 ? kLreluLast : kLrelu;
@@ -370,7 +344,7 @@ void run_group(const ttsgen_handle* h, const float* planes, const float* z, cons
           } else {
             c2.out = Ssum;
             c2.out2 = nullptr;
-            launch_gemm(c2, A_CONV_DIL, EPI_LRELU2, st);
+            launch_gemm<A_CONV_DIL, EPI_LRELU2>(c2, st);
           }
         }
       }

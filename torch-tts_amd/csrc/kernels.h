@@ -1,5 +1,7 @@
 // Internal launch interface between the C ABI (api.hip) and the kernels.
 #pragma once
+#include <string.h>
+
 #include <string>
 
 #include "common.h"
@@ -94,13 +96,65 @@ struct GemmArgs {
   int fixed_tile;
 };
 
-void launch_gemm(const GemmArgs& a, AKind ak, EpiKind ek, hipStream_t st);
+// The kinds are template arguments: only the pairs instantiated in decode_kernels.hip exist (the list and their precisions are
+// there), any other pair fails to link.
+template <int AK, int EK>
+void launch_gemm(const GemmArgs& a, hipStream_t st);
+
+// ---- GEMM operands by precision: fp32 | split-fp16 hi + lo planes | one bf16 plane ----
+void launch_split(const float* src, f16* hi, f16* lo, size_t n, hipStream_t st);
+void launch_to_bf16(const float* src, void* dst, size_t n, hipStream_t st);
+struct Planes {  // what a GEMM reads as a / a_lo or W / W_lo (fp32 and bf16: the same pointer twice)
+  const void *p0, *p1;
+};
+inline Planes planes_f32(const float* x) { return {x, x}; }
+// the split-fp16 planes of an n-element tensor kept back to back: hi at p, lo n halfs behind it
+inline Planes planes_at(const void* p, size_t n) { return {p, static_cast<const f16*>(p) + n}; }
+// ... made now, from x [n] into buf
+inline Planes planes_split(const float* x, void* buf, size_t n, hipStream_t st) {
+  f16* p = static_cast<f16*>(buf);
+  launch_split(x, p, p + n, n, st);
+  return planes_at(p, n);
+}
+// x [n] fp32 as a first layer reads it in `prec`: x itself, or its 16-bit form made in buf
+inline Planes act_input(int prec, const float* x, void* buf, size_t n, hipStream_t st) {
+  if (prec == PREC_F32) return planes_f32(x);
+  if (prec == PREC_F16S) return planes_split(x, buf, n, st);
+  launch_to_bf16(x, buf, n, st);
+  return {buf, buf};
+}
+// the result [n = M * N] of g goes to buf in the form of `prec`: -> as the next layer reads it.  (16-bit modes leave g.out alone.)
+inline Planes set_output(GemmArgs& g, int prec, void* buf, size_t n) {
+  if (prec == PREC_F32) { g.out = static_cast<float*>(buf); return {buf, buf}; }
+  g.out_kind = prec == PREC_F16S ? 1 : 2;
+  g.out_h = static_cast<f16*>(buf);
+  if (prec == PREC_F16S) g.out_l = g.out_h + n;
+  return prec == PREC_F16S ? planes_at(buf, n) : Planes{buf, buf};
+}
 // The packed-weight convention of the encoder and VITS2 blobs: fp32 [n_w] | split-fp16 hi [n_w] | lo [n_w], back to back.
-// Points g at the fp32 copy at W, or (split) at the two planes behind it.
-inline void set_weight_contiguous(GemmArgs& g, const float* W, size_t n_w, bool split) {
-  const f16* hi = reinterpret_cast<const f16*>(W + n_w);
-  g.W = split ? static_cast<const void*>(hi) : W;
-  g.W_lo = split ? static_cast<const void*>(hi + n_w) : W;
+// The fp32 copy at W, or (split) the two planes behind it.  (The decoder blob's own producer: api.hip weight.)
+inline Planes weight_contiguous(const float* W, size_t n_w, bool split) { return split ? planes_at(W + n_w, n_w) : planes_f32(W); }
+
+// ---- the builders: a zeroed argument struct with every operand and shape field of the GEMM set; ldo = N ----
+// A caller adds what is its own: epilogue operands, an ldo that is not N, split-K / fixed_tile, the step-control fields.
+// out [M, N] = A [M, K] . W [N, K]^T with A in the K segments a / a_lo and W's rows ldw elements apart (Args: GemmArgs / ProjArgs)
+template <class Args>
+Args gemm_args_seg(const Seg3& a, const Seg3& a_lo, Planes w, int ldw, int prec, int M, int N, int K) {
+  Args g;
+  memset(&g, 0, sizeof(g));
+  g.a = a; g.a_lo = a_lo; g.W = w.p0; g.W_lo = w.p1; g.ldw = ldw; g.prec = prec;
+  g.M = M; g.N = N; g.K = K; g.ldo = N;
+  return g;
+}
+// the plain row GEMM: A [M, K] with leading dimension lda against a dense W [N, K]
+inline GemmArgs gemm_args(Planes a, int lda, Planes w, int prec, int M, int N, int K) {
+  return gemm_args_seg<GemmArgs>(make_seg1(a.p0, lda, K), make_seg1(a.p1, lda, K), w, K, prec, M, N, K);
+}
+// Conv1d over `taps` frames (A_CONV; dil: A_CONV_DIL) of x [M, Cin], utterances of T frames, against W [N, taps * Cin] tap-major
+inline GemmArgs conv_gemm_args(Planes x, Planes w, int prec, int M, int T, int Cin, int taps, int N, int dil = 0) {
+  GemmArgs g = gemm_args(x, Cin, w, prec, M, N, taps * Cin);
+  g.T = T; g.Cin = Cin; g.taps = taps; g.dil = dil;
+  return g;
 }
 
 // ---- LSTM zoneout cell: gates GEMM + cell update fused ----
@@ -315,14 +369,13 @@ void launch_add_vec(const float* a, const float* b, float* out, int n, hipStream
 void launch_copy(const float* src, float* dst, size_t n, hipStream_t st);
 // the speaker conditioning cond(g) of the VITS2 generator and duration predictors: out [B, N] = g [B, K] . W [N, K]^T + bias
 void launch_cond(const float* g, const float* W, const float* bias, float* out, int B, int N, int K, hipStream_t st);
-void launch_split(const float* src, f16* hi, f16* lo, size_t n, hipStream_t st);
+// (launch_split / launch_to_bf16: with the GEMM operands, above)
 // src [M, K] row-major -> split-fp16 planes in the chunked layout [K / 32][mpad][32] (common.h Seg3)
 void launch_split_frame_order(const float* src, f16* hi, f16* lo, int N, int K, int layer, hipStream_t st);  // PreNet planes, frame kernel's lane order
 void launch_split_chunked(const float* src, f16* hi, f16* lo, int M, int K, int mpad, hipStream_t st);
 // LSTM weight matrix src [4H, K] (PyTorch gate blocks i,f,g,o) -> chunked split-fp16 planes
 // [H / 16][K / 32][gate * 16 + unit % 16][32]  (step_bodies.h LoaderWLstm); needs H % 16 == 0, K % 32 == 0
 void launch_pack_lstm_chunked(const float* src, f16* hi, f16* lo, int H, int K, hipStream_t st);
-void launch_to_bf16(const float* src, void* dst, size_t n, hipStream_t st);
 // conv256.hip: out[M, N] bf16 = isru(conv_k(x [M = B * T, Cin] bf16, w [N, taps * Cin] bf16) * alpha[n] + beta[n]) on 256 x 256 tiles;
 // false = not that kernel's shape (Cin % 64, N % 256, odd taps, 32-bit offsets): the caller keeps the shared GEMM
 bool launch_conv256_bf16(const void* x, const void* w, const float* alpha, const float* beta, void* out, int M, int T, int Cin, int taps, int N,

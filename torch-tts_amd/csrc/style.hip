@@ -514,12 +514,10 @@ int ttsenc_style_forward(ttsenc_style_handle* h, const float* x, int ldx, const 
     launch_conv(a, st);
   }
   {  // gx [B * T', 4H] = feat [B * T', F' * C] . W_ih^T
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
     const int feat = Fp * C;
-    g.a = make_seg1(W.act[(K - 1) & 1], feat, feat); g.a_lo = g.a;
-    g.W = g.W_lo = blob + bl.w_ih; g.ldw = feat; g.K = feat; g.M = B * Tp; g.N = 4 * H; g.out = W.gx; g.ldo = 4 * H;
-    launch_gemm(g, A_PLAIN, EPI_PLAIN, st);
+    GemmArgs g = gemm_args(planes_f32(W.act[(K - 1) & 1]), feat, planes_f32(blob + bl.w_ih), PREC_F32, B * Tp, 4 * H, feat);
+    g.out = W.gx;
+    launch_gemm<A_PLAIN, EPI_PLAIN>(g, st);
   }
   // The recurrence from a zero state (style.py:70).  Step t reads state buffer t & 1 and writes the other; a row past its own
   // step count carries its state over, so after T' steps buffer T' & 1 holds every row's last hidden state: that one is enc_out.

@@ -25,7 +25,7 @@ namespace {
 constexpr int kMaxLayers = 12, kMaxFlows = 8, kMaxWn = 8, kMaxPostWn = 32;
 
 // One linear or conv weight [N, taps, K] (tap-major, as the GEMM core reads it) with its bias [N].  Offsets in floats.  The weight
-// takes 2 n() floats: fp32 | fp16 hi plane | fp16 lo plane back to back (set_weight_contiguous).  src: its weight among the pack
+// takes 2 n() floats: fp32 | fp16 hi plane | fp16 lo plane back to back (kernels.h weight_contiguous).  src: its weight among the pack
 // call's source tensors, the bias right behind it.
 struct Lin {
   size_t w, b;
@@ -1192,30 +1192,16 @@ struct Epi {  // what a call chooses besides its weight, input and output
 void gemm_generic(const GemmCtx& cx, const float* blob, const Lin& l, const float* a, const f16* a_pl, float* out, int M, int T, hipStream_t st,
                   const Epi& e = {}) {
   const int K = l.K;
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.M = M; g.N = l.N; g.bias = blob + l.b; g.out = out; g.ldo = l.N; g.act = e.act; g.row_mask = e.row_mask; g.resid = e.resid;
-  const void *a0 = a, *a1 = a;
   const bool split = cx.split && !(K & 7);
-  set_weight_contiguous(g, blob + l.w, l.n(), split);
-  if (e.out_pl != nullptr) { g.out_kind = 1; g.out_h = e.out_pl; g.out_l = e.out_pl + (size_t)M * l.N; }
-  if (split) {
-    const f16* ph = a_pl;
-    if (ph == nullptr) {
-      launch_split(a, cx.planes, cx.planes + (size_t)M * K, (size_t)M * K, st);
-      ph = cx.planes;
-    }
-    a0 = ph; a1 = ph + (size_t)M * K;
-    g.prec = PREC_F16S;
-  }
-  g.a = make_seg1(a0, K, K); g.a_lo = make_seg1(a1, K, K);
-  g.ldw = l.taps * K; g.K = l.taps * K;
-  if (l.taps > 1) {
-    g.T = T; g.Cin = K; g.taps = l.taps;
-    launch_gemm(g, A_CONV, EPI_GENERIC, st);
-  } else {
-    launch_gemm(g, A_PLAIN, EPI_GENERIC, st);
-  }
+  const int prec = split ? PREC_F16S : PREC_F32;
+  const size_t na = (size_t)M * K;
+  const Planes ap = !split ? planes_f32(a) : (a_pl != nullptr ? planes_at(a_pl, na) : planes_split(a, cx.planes, na, st));
+  const Planes wp = weight_contiguous(blob + l.w, l.n(), split);
+  GemmArgs g = l.taps > 1 ? conv_gemm_args(ap, wp, prec, M, T, K, l.taps, l.N) : gemm_args(ap, K, wp, prec, M, l.N, l.taps * K);
+  g.bias = blob + l.b; g.out = out; g.act = e.act; g.row_mask = e.row_mask; g.resid = e.resid;
+  if (e.out_pl != nullptr) set_output(g, PREC_F16S, e.out_pl, (size_t)M * l.N);
+  if (l.taps > 1) launch_gemm<A_CONV, EPI_GENERIC>(g, st);
+  else launch_gemm<A_PLAIN, EPI_GENERIC>(g, st);
 }
 
 struct StackWs {
