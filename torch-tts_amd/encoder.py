@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import EngineCache, Handle, PackedWeightsMixin, _require_device, _stream
+from .engine import STREAM, WS, EngineCache, Handle, PackedWeightsMixin, _require_device
 
 
 class _ISRLU(nn.Module):
@@ -62,12 +62,9 @@ class EncoderEngine(Handle):
         self.status.zero_()
         self._status_pending = True
         lens = lengths.to(device=self.device, dtype=torch.int32).contiguous()
-        ws = self.workspace("forward", self._lib.ttsenc_workspace_bytes(self._h, B, L))
+        ws = self.sized_workspace("forward", "ttsenc_workspace_bytes", B, L)
         memory = torch.empty(B, l_out, self.dims["d_out"], dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsenc_forward(self._h, ids.data_ptr(), lens.data_ptr(), B, L, l_out, memory.data_ptr(), ws.data_ptr(),
-                                          ws.numel(), _stream(self.device), self.status.data_ptr())
-        self._err(rc, "ttsenc_forward")
+        self.call("ttsenc_forward", ids, lens, B, L, l_out, memory, WS(ws), STREAM, self.status)
         return memory
 
 

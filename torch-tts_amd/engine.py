@@ -3,6 +3,7 @@ kernel blob, holds workspaces (PyTorch caching allocator memory) and issues the
 C-ABI calls on torch's current HIP stream."""
 from __future__ import annotations
 
+import contextlib
 import copy
 import ctypes as C
 from dataclasses import dataclass, field
@@ -49,10 +50,6 @@ class EngineDims:
         return self.h_att + self.h_dec + self.d_ctx if self.cell_type == _lib.CELL_TACO2 else self.h_dec + self.d_ctx
 
 
-def _ptr(t: Optional[Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 def _stream(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -63,6 +60,18 @@ def _require_device(t: Tensor, what: str) -> None:
             f"{what} must live on a ROCm device (got {t.device}): this package runs the decoder hot path "
             "only through its HIP kernels and has no CPU fallback"
         )
+
+
+STREAM = object()  # in Handle.call's arguments: the current stream of the handle's device
+
+
+class WS:
+    """In Handle.call's arguments: a workspace tensor, passed as its (pointer, bytes) pair; None: (NULL, 0)."""
+
+    __slots__ = ("t",)
+
+    def __init__(self, t: Optional[Tensor]):
+        self.t = t
 
 
 _EPOCH = [0]
@@ -133,6 +142,25 @@ class Handle:
         if rc != _lib.OK:
             raise _lib.TtsdecError(rc, what, self._fn("last_hip_error")(self._h).decode() if rc == _lib.ERR_HIP else "")
 
+    def call(self, name: str, *args, dims: Optional[str] = None) -> None:
+        """The C function ``name`` (its full name: engines call across prefixes) on this handle, under the handle's device.  args:
+        what include/ttsdec.h declares after the handle, in that order - a tensor stands for its data pointer, WS(t) for a
+        workspace's pointer and byte count, STREAM for the device's current stream; None, numbers and ctypes objects pass as they
+        are.  Raises for a code other than OK; dims: the message of the DimsNotBuilt that ERR_DIMS becomes."""
+        with torch.cuda.device(self.device) if self.device is not None else contextlib.nullcontext():
+            flat = [self._h]
+            for a in args:
+                if isinstance(a, Tensor):
+                    flat.append(a.data_ptr())
+                elif isinstance(a, WS):
+                    flat += (None, 0) if a.t is None else (a.t.data_ptr(), a.t.numel())
+                else:
+                    flat.append(_stream(self.device) if a is STREAM else a)
+            rc = getattr(self._lib, name)(*flat)
+        if rc == _lib.ERR_DIMS and dims is not None:
+            raise _lib.DimsNotBuilt(rc, name, dims)
+        self._err(rc, name)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._fn("destroy")(self._h)
@@ -155,7 +183,7 @@ class Handle:
     def set_precision(self, mode: str) -> None:
         """"f32" (exact fp32 matrix instruction, default) or "split_f16" (hi/lo fp16 planes, 3 products)."""
         code = {"f32": _lib.PREC_F32, "split_f16": _lib.PREC_SPLIT_F16}[mode]
-        self._err(self._fn("set_precision")(self._h, code), f"{self.PREFIX}_set_precision")
+        self.call(f"{self.PREFIX}_set_precision", code)
 
     def precision(self) -> str:
         return {_lib.PREC_F32: "f32", _lib.PREC_SPLIT_F16: "split_f16"}[int(self._fn("get_precision")(self._h))]
@@ -176,11 +204,9 @@ class Handle:
             tc = t.detach().to(torch.float32).contiguous()
             keep.append(tc)
             arr[i] = tc.data_ptr()
-        with torch.cuda.device(self.device):
-            blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=self.device)
-            rc = self._fn("pack_weights")(self._h, arr, n, blob.data_ptr(), _stream(self.device))
-            torch.cuda.current_stream(self.device).synchronize()  # `keep` must outlive the packing kernels
-        self._err(rc, f"{self.PREFIX}_pack_weights")
+        blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=self.device)
+        self.call(f"{self.PREFIX}_pack_weights", arr, n, blob, STREAM)
+        torch.cuda.current_stream(self.device).synchronize()  # `keep` must outlive the packing kernels
         self.blob, self._fingerprint = blob, weights_fingerprint(tensors)
         return blob
 
@@ -203,6 +229,14 @@ class Handle:
             self._ws.pop(kind, None)  # (the old buffer goes back to the allocator first)
             ws = self._ws[kind] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return ws
+
+    def sized_workspace(self, kind: str, fn: str, *args, refusal: Optional[Exception] = None) -> Tensor:
+        """The workspace of ``kind``, at least as large as the library's size query ``fn`` (full name; args: after the handle)
+        reports.  refusal: what to raise where the query answers 0, its way of refusing the sizes."""
+        nbytes = int(getattr(self._lib, fn)(self._h, *args))
+        if not nbytes and refusal is not None:
+            raise refusal
+        return self.workspace(kind, nbytes)
 
     def release_workspaces(self) -> None:
         """Drops every workspace (the next call allocates afresh); assigning None to ``_ws`` does the same."""
@@ -251,7 +285,7 @@ class Engine(Handle):
             raise ValueError("blob size does not match this engine's dims")
         with torch.cuda.device(self.device):
             torch.cuda.current_stream(self.device).synchronize()  # the blob must be complete: its header is read back
-            self._err(self._lib.ttsdec_bind_weights(self._h, blob.data_ptr()), "ttsdec_bind_weights")
+        self.call("ttsdec_bind_weights", blob)
         self.blob = blob
         self._fingerprint = None
 
@@ -262,10 +296,7 @@ class Engine(Handle):
         B, T, n_mels = y.shape
         mag = torch.empty(B, n_fft // 2 + 1, T, device=self.device)
         status = torch.empty(1, dtype=torch.int32, device=self.device) if check else None
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_mel_to_magnitude(self._h, y.data_ptr(), P.data_ptr(), _ptr(frames), B, T, n_mels, n_fft, mag.data_ptr(),
-                                                   _ptr(status), _stream(self.device))
-        self._err(rc, "ttsdec_mel_to_magnitude")
+        self.call("ttsdec_mel_to_magnitude", y, P, frames, B, T, n_mels, n_fft, mag, status, STREAM)
         if check:
             _raise_frame_flags(int(status.item()), T)
         return mag
@@ -276,21 +307,13 @@ class Engine(Handle):
         [B, hop_length * (T - 1)], and with return_state (n_iter >= 1) the last rebuilt spectrum and the final phase factors
         (ttsdec_griffinlim)."""
         B, bins, T = mag.shape
-        nbytes = int(self._lib.ttsdec_griffinlim_workspace_bytes(self._h, B, T, n_fft))
-        if not nbytes:
-            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsdec_griffinlim", f"B = {B}, T = {T}, n_fft = {n_fft}: built for n_fft 256 / 512 / 1024 / 2048, "
-                                    "T >= 2, B <= 65535")
-        ws = self.workspace("griffinlim", nbytes)
+        ws = self.sized_workspace("griffinlim", "ttsdec_griffinlim_workspace_bytes", B, T, n_fft, refusal=_lib.DimsNotBuilt(
+            _lib.ERR_DIMS, "ttsdec_griffinlim", f"B = {B}, T = {T}, n_fft = {n_fft}: built for n_fft 256 / 512 / 1024 / 2048, T >= 2, B <= 65535"))
         wave = torch.empty(B, hop_length * (T - 1), device=self.device)
         state = [torch.empty(B, bins, T, dtype=torch.complex64, device=self.device) for _ in range(2)] if return_state else [None, None]
         status = torch.empty(1, dtype=torch.int32, device=self.device) if check else None
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_griffinlim(self._h, mag.data_ptr(), _ptr(frames), B, T, window.data_ptr(), n_fft, hop_length, _ptr(angles),
-                                             _ptr(tprev), n_iter, momentum, int(normalize), wave.data_ptr(), _ptr(state[0]), _ptr(state[1]),
-                                             _ptr(status), ws.data_ptr(), ws.numel(), _stream(self.device))
-        if rc == _lib.ERR_DIMS:
-            raise _lib.DimsNotBuilt(rc, "ttsdec_griffinlim", f"n_fft = {n_fft}, hop_length = {hop_length}: needs hop_length <= n_fft / 2")
-        self._err(rc, "ttsdec_griffinlim")
+        self.call("ttsdec_griffinlim", mag, frames, B, T, window, n_fft, hop_length, angles, tprev, n_iter, momentum, int(normalize), wave,
+                  state[0], state[1], status, WS(ws), STREAM, dims=f"n_fft = {n_fft}, hop_length = {hop_length}: needs hop_length <= n_fft / 2")
         if check:
             _raise_frame_flags(int(status.item()), T)
         return (wave, state[0], state[1]) if return_state else wave
@@ -303,23 +326,16 @@ class Engine(Handle):
         B, N = wave.shape
         n_fft, (bins, n_mels) = window.numel(), fb.shape
         T = 1 + N // hop_length
-        nbytes = int(self._lib.ttsdec_mel_analysis_workspace_bytes(self._h, B, n_fft, n_mels))
-        if not nbytes:
-            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsdec_mel_analysis", f"B = {B}, n_fft = {n_fft}, n_mels = {n_mels}: built for n_fft 256 / 512 / "
-                                    "1024 / 2048, n_mels <= 256, B <= 65535")
-        ws = self.workspace("mel_analysis", nbytes)
+        ws = self.sized_workspace("mel_analysis", "ttsdec_mel_analysis_workspace_bytes", B, n_fft, n_mels, refusal=_lib.DimsNotBuilt(
+            _lib.ERR_DIMS, "ttsdec_mel_analysis", f"B = {B}, n_fft = {n_fft}, n_mels = {n_mels}: built for n_fft 256 / 512 / 1024 / 2048, "
+            "n_mels <= 256, B <= 65535"))
         spec = torch.empty(B, T, bins, device=self.device) if spectrogram else None
         mel = torch.empty(B, T, n_mels, device=self.device)
         frames = torch.empty(B, dtype=torch.int32, device=self.device)
         status = torch.empty(1, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_mel_analysis(self._h, wave.data_ptr(), _ptr(lengths), B, N, window.data_ptr(), fb.data_ptr(), n_mels, n_fft,
-                                               hop_length, T, _ptr(spec), mel.data_ptr(), frames.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), _stream(self.device))
-        if rc == _lib.ERR_DIMS:
-            raise _lib.DimsNotBuilt(rc, "ttsdec_mel_analysis", f"n_fft = {n_fft}, hop_length = {hop_length}, {N} samples: needs 1 <= hop_length "
-                                    "<= n_fft / 2, at most 2^30 samples and 2^22 frames")
-        self._err(rc, "ttsdec_mel_analysis")
+        self.call("ttsdec_mel_analysis", wave, lengths, B, N, window, fb, n_mels, n_fft, hop_length, T, spec, mel, frames, status, WS(ws), STREAM,
+                  dims=f"n_fft = {n_fft}, hop_length = {hop_length}, {N} samples: needs 1 <= hop_length <= n_fft / 2, at most 2^30 samples and "
+                  "2^22 frames")
         flags = int(status.item())
         if flags & 4:
             raise ValueError(f"an utterance's length exceeds the row's {N} samples")
@@ -335,21 +351,14 @@ class Engine(Handle):
         """wave [B, N] contiguous fp32, lengths [B] int32 (device) or None -> (out [B, n_out], lengths_out [B] int32)
         (ttsdec_resample).  Enqueues only; check: read the status word back (one host sync) and raise for a length beyond the row."""
         B, N = wave.shape
-        nbytes = int(self._lib.ttsdec_resample_workspace_bytes(self._h, orig_freq, new_freq, lowpass_filter_width, rolloff))
-        if not nbytes:
-            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsdec_resample", f"{orig_freq} -> {new_freq} Hz, lowpass_filter_width = {lowpass_filter_width}, "
-                                    f"rolloff = {rolloff}: built for reduced rates <= 1024 and <= 16384 taps")
-        ws = self.workspace("resample", nbytes)
+        ws = self.sized_workspace("resample", "ttsdec_resample_workspace_bytes", orig_freq, new_freq, lowpass_filter_width, rolloff, refusal=_lib.DimsNotBuilt(
+            _lib.ERR_DIMS, "ttsdec_resample", f"{orig_freq} -> {new_freq} Hz, lowpass_filter_width = {lowpass_filter_width}, rolloff = {rolloff}: "
+            "built for reduced rates <= 1024 and <= 16384 taps"))
         out = torch.empty(B, n_out, device=self.device)
         lengths_out = torch.empty(B, dtype=torch.int32, device=self.device)
         status = torch.empty(1, dtype=torch.int32, device=self.device) if check else None
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_resample(self._h, wave.data_ptr(), _ptr(lengths), B, N, orig_freq, new_freq, lowpass_filter_width, rolloff,
-                                           out.data_ptr(), n_out, lengths_out.data_ptr(), _ptr(status), ws.data_ptr(), ws.numel(),
-                                           _stream(self.device))
-        if rc == _lib.ERR_DIMS:
-            raise _lib.DimsNotBuilt(rc, "ttsdec_resample", f"B = {B}, {N} -> {n_out} samples: needs B <= 65535 and at most 2^30 samples")
-        self._err(rc, "ttsdec_resample")
+        self.call("ttsdec_resample", wave, lengths, B, N, orig_freq, new_freq, lowpass_filter_width, rolloff, out, n_out, lengths_out, status,
+                  WS(ws), STREAM, dims=f"B = {B}, {N} -> {n_out} samples: needs B <= 65535 and at most 2^30 samples")
         if check and int(status.item()) & 4:
             raise ValueError(f"an utterance's length exceeds the row's {N} samples")
         return out, lengths_out
@@ -397,15 +406,12 @@ class Engine(Handle):
         B, L, _ = memory.shape
         t_stride = w.shape[1]
         ws = self.step_workspace(B, L)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_decode(
-                self._h, memory.data_ptr(), B, L, t_begin, n_steps, t_stride,
-                float(stop_threshold), int(check_stop), dropout_mode, _ptr(masks), seed & 0xFFFFFFFFFFFFFFFF,
-                _ptr(teacher), 0 if teacher is None else teacher.shape[1], _ptr(teacher_flags),
-                y.data_ptr(), s.data_ptr(), w.data_ptr(), t_out.data_ptr(),
-                ws.data_ptr(), ws.numel(), _stream(self.device),
-            )
-        self._err(rc, "ttsdec_decode")
+        self.call(
+            "ttsdec_decode", memory, B, L, t_begin, n_steps, t_stride,
+            float(stop_threshold), int(check_stop), dropout_mode, masks, seed & 0xFFFFFFFFFFFFFFFF,
+            teacher, 0 if teacher is None else teacher.shape[1], teacher_flags,
+            y, s, w, t_out, WS(ws), STREAM,
+        )
 
     def decode_each(self, memory: Tensor, *, t_begin: int, n_steps: int, stop_threshold: float, dropout_mode: int,
                     masks: Optional[Tensor], seed: int, y: Tensor, s: Tensor, w: Tensor, stop_steps: Tensor, t_out: Tensor) -> None:
@@ -417,14 +423,11 @@ class Engine(Handle):
             raise ValueError("stop_steps must be a contiguous int32 [B] tensor")
         _require_device(stop_steps, "stop_steps")
         ws = self.step_workspace(B, L)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_decode_each(
-                self._h, memory.data_ptr(), B, L, t_begin, n_steps, w.shape[1],
-                float(stop_threshold), dropout_mode, _ptr(masks), seed & 0xFFFFFFFFFFFFFFFF, None, 0, None,
-                y.data_ptr(), s.data_ptr(), w.data_ptr(), stop_steps.data_ptr(), t_out.data_ptr(),
-                ws.data_ptr(), ws.numel(), _stream(self.device),
-            )
-        self._err(rc, "ttsdec_decode_each")
+        self.call(
+            "ttsdec_decode_each", memory, B, L, t_begin, n_steps, w.shape[1],
+            float(stop_threshold), dropout_mode, masks, seed & 0xFFFFFFFFFFFFFFFF, None, 0, None,
+            y, s, w, stop_steps, t_out, WS(ws), STREAM,
+        )
 
     def zero_tail(self, x: Tensor, lengths: Tensor, len_div: int = 1) -> None:
         """Zeroes x[b, lengths[b] // len_div :] in place (ttsdec_zero_tail).  x: fp32 [B, T] or [B, T, C] whose entries x[b] are
@@ -436,10 +439,7 @@ class Engine(Handle):
             raise ValueError("zero_tail: x must be fp32 [B, T] or [B, T, C] with contiguous entries")
         if T == 0:
             return
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_zero_tail(self._h, x.data_ptr(), lengths.data_ptr(), B, T, x.stride(0) if B > 1 else T * Cc, Cc,
-                                            len_div, _stream(self.device))
-        self._err(rc, "ttsdec_zero_tail")
+        self.call("ttsdec_zero_tail", x, lengths, B, T, x.stride(0) if B > 1 else T * Cc, Cc, len_div, STREAM)
 
     # ---- the validation step's loss terms (weightless; tacotron.py holds the entry points) ----
     def val_losses(self, y: Optional[Tensor], y_post: Optional[Tensor], x: Optional[Tensor], s: Optional[Tensor], w: Optional[Tensor],
@@ -448,36 +448,23 @@ class Engine(Handle):
         (rows [B, 9], terms [16]) (ttsdec_val_losses).  shape: (B, T, D) where y is None.  Enqueues only."""
         B, T, D = y.shape if y is not None else shape
         S, L = (w.shape[1], w.shape[2]) if w is not None else (0, 0)
-        nbytes = int(self._lib.ttsdec_val_losses_workspace_bytes(self._h, B, T, S))
-        if not nbytes:
-            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsdec_val_losses", f"B = {B}, T = {T}, S = {S}: needs B <= 65535 and at most 2^31 frames")
-        ws = self.workspace("val_losses", nbytes)
+        ws = self.sized_workspace("val_losses", "ttsdec_val_losses_workspace_bytes", B, T, S, refusal=_lib.DimsNotBuilt(
+            _lib.ERR_DIMS, "ttsdec_val_losses", f"B = {B}, T = {T}, S = {S}: needs B <= 65535 and at most 2^31 frames"))
         rows = torch.empty(B, 9, device=self.device)
         terms = torch.empty(16, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_val_losses(self._h, _ptr(y), _ptr(y_post), _ptr(x), T if x is None else x.shape[1], _ptr(s), _ptr(w),
-                                             _ptr(lengths), B, T, D, S, L, float(pos_weight), rows.data_ptr(), terms.data_ptr(),
-                                             ws.data_ptr(), nbytes, _stream(self.device))
-        if rc == _lib.ERR_DIMS:
-            raise _lib.DimsNotBuilt(rc, "ttsdec_val_losses", f"B = {B}, D = {D}: needs B <= 65535, D <= 1024 and tensors of at most 2^31 elements")
-        self._err(rc, "ttsdec_val_losses")
+        self.call("ttsdec_val_losses", y, y_post, x, T if x is None else x.shape[1], s, w, lengths, B, T, D, S, L, float(pos_weight), rows, terms,
+                  WS(ws), STREAM, dims=f"B = {B}, D = {D}: needs B <= 65535, D <= 1024 and tensors of at most 2^31 elements")
         return rows, terms
 
     def mel_loss(self, y: Tensor, x: Tensor, lengths: Optional[Tensor], order: int):
         """y [B, T, D], x [B, T_x >= T, D] contiguous fp32, lengths [B] int32 (device) or None -> (rows [B], out [1]) (ttsdec_mel_loss)."""
         B, T, D = y.shape
-        nbytes = int(self._lib.ttsdec_val_losses_workspace_bytes(self._h, B, T, 0))
-        if not nbytes:
-            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsdec_mel_loss", f"B = {B}, T = {T}: needs B <= 65535 and at most 2^31 frames")
-        ws = self.workspace("val_losses", nbytes)
+        ws = self.sized_workspace("val_losses", "ttsdec_val_losses_workspace_bytes", B, T, 0, refusal=_lib.DimsNotBuilt(
+            _lib.ERR_DIMS, "ttsdec_mel_loss", f"B = {B}, T = {T}: needs B <= 65535 and at most 2^31 frames"))
         rows = torch.empty(B, device=self.device)
         out = torch.empty(1, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_mel_loss(self._h, y.data_ptr(), x.data_ptr(), x.shape[1], _ptr(lengths), B, T, D, int(order), rows.data_ptr(),
-                                           out.data_ptr(), ws.data_ptr(), nbytes, _stream(self.device))
-        if rc == _lib.ERR_DIMS:
-            raise _lib.DimsNotBuilt(rc, "ttsdec_mel_loss", f"B = {B}, D = {D}: needs B <= 65535, D <= 1024 and tensors of at most 2^31 elements")
-        self._err(rc, "ttsdec_mel_loss")
+        self.call("ttsdec_mel_loss", y, x, x.shape[1], lengths, B, T, D, int(order), rows, out, WS(ws), STREAM,
+                  dims=f"B = {B}, D = {D}: needs B <= 65535, D <= 1024 and tensors of at most 2^31 elements")
         return rows, out
 
     def postnet(self, y: Tensor, precision: int = _lib.POSTNET_F32, lengths: Optional[Tensor] = None) -> Tensor:
@@ -485,17 +472,10 @@ class Engine(Handle):
         B, T, _ = y.shape
         out = torch.empty_like(y)
         ws = self.postnet_workspace(B, T)
-        with torch.cuda.device(self.device):
-            if lengths is None:
-                rc = self._lib.ttsdec_postnet(
-                    self._h, y.data_ptr(), B, T, precision, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device)
-                )
-            else:  # int32 [B] on the device, frames
-                rc = self._lib.ttsdec_postnet_ragged(
-                    self._h, y.data_ptr(), lengths.data_ptr(), B, T, precision, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                    _stream(self.device)
-                )
-        self._err(rc, "ttsdec_postnet" if lengths is None else "ttsdec_postnet_ragged")
+        if lengths is None:
+            self.call("ttsdec_postnet", y, B, T, precision, out, WS(ws), STREAM)
+        else:  # int32 [B] on the device, frames
+            self.call("ttsdec_postnet_ragged", y, lengths, B, T, precision, out, WS(ws), STREAM)
         return out
 
     def cell_step(self, x, memory, w, ctx, h_att, c_att, h_dec, c_dec, dropout_mode, masks, seed, step) -> Tensor:
@@ -503,13 +483,8 @@ class Engine(Handle):
         B, L, _ = memory.shape
         x_dec = torch.empty(B, self.dims.cell_output, dtype=torch.float32, device=self.device)
         ws = self.step_workspace(B, L)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_cell_step(
-                self._h, x.data_ptr(), memory.data_ptr(), B, L, w.data_ptr(), ctx.data_ptr(), h_att.data_ptr(),
-                c_att.data_ptr(), h_dec.data_ptr(), c_dec.data_ptr(), dropout_mode, _ptr(masks),
-                seed & 0xFFFFFFFFFFFFFFFF, step, x_dec.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device),
-            )
-        self._err(rc, "ttsdec_cell_step")
+        self.call("ttsdec_cell_step", x, memory, B, L, w, ctx, h_att, c_att, h_dec, c_dec, dropout_mode, masks, seed & 0xFFFFFFFFFFFFFFFF, step,
+                  x_dec, WS(ws), STREAM)
         return x_dec
 
     def profile_step(self, memory: Tensor, iters: int, dropout_mode: int, masks: Optional[Tensor], seed: int):
@@ -523,13 +498,8 @@ class Engine(Handle):
         ms = (C.c_float * 16)()
         names = (C.c_char_p * 16)()
         nk = C.c_int(0)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_profile_step(
-                self._h, memory.data_ptr(), B, L, iters, dropout_mode, _ptr(masks), seed & 0xFFFFFFFFFFFFFFFF,
-                y.data_ptr(), s.data_ptr(), w.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device),
-                ms, names, 16, C.byref(nk),
-            )
-        self._err(rc, "ttsdec_profile_step")
+        self.call("ttsdec_profile_step", memory, B, L, iters, dropout_mode, masks, seed & 0xFFFFFFFFFFFFFFFF, y, s, w, WS(ws), STREAM,
+                  ms, names, 16, C.byref(nk))
         return {names[i].decode(): float(ms[i]) for i in range(nk.value)}
 
 
@@ -547,13 +517,8 @@ class Engine(Handle):
         names = (C.c_char_p * 16)()
         nk = C.c_int(0)
         step = C.c_float(0.0)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdec_profile_loop(
-                self._h, memory.data_ptr(), B, L, n_steps, dropout_mode, _ptr(masks), seed & 0xFFFFFFFFFFFFFFFF,
-                y.data_ptr(), s.data_ptr(), w.data_ptr(), t_out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device),
-                ms, names, 16, C.byref(nk), C.byref(step),
-            )
-        self._err(rc, "ttsdec_profile_loop")
+        self.call("ttsdec_profile_loop", memory, B, L, n_steps, dropout_mode, masks, seed & 0xFFFFFFFFFFFFFFFF, y, s, w, t_out, WS(ws), STREAM,
+                  ms, names, 16, C.byref(nk), C.byref(step))
         return {names[i].decode(): float(ms[i]) for i in range(nk.value)}, float(step.value)
 
 

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import EngineCache, Handle, PackedWeightsMixin, _ptr, _require_device, _stream
+from .engine import STREAM, WS, EngineCache, Handle, PackedWeightsMixin, _require_device
 
 _HEAD_NAMES = ("encoder.gru.weight_ih_l0", "encoder.gru.weight_hh_l0", "encoder.gru.bias_ih_l0", "encoder.gru.bias_hh_l0",
                "mean_linear.weight", "mean_linear.bias", "logvar_linear.weight", "logvar_linear.bias", "fc_out.weight",
@@ -62,10 +62,7 @@ class StyleEngine(Handle):
         x_out = new(d["d_emb"]) if kind != _lib.STYLE_ENCODER else None
         kl = new(d["d_vae"]) if kind in (_lib.STYLE_VAE, _lib.STYLE_GST_VAE) else None
         ws = self.workspace("forward", self.workspace_bytes(B, T))
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsenc_style_forward(self._h, x.data_ptr(), x.stride(1), _ptr(lengths), _ptr(eps), B, T, enc_out.data_ptr(),
-                                                _ptr(x_out), _ptr(kl), ws.data_ptr(), ws.numel(), _stream(self.device))
-        self._err(rc, "ttsenc_style_forward")
+        self.call("ttsenc_style_forward", x, x.stride(1), lengths, eps, B, T, enc_out, x_out, kl, WS(ws), STREAM)
         return enc_out, x_out, kl
 
 

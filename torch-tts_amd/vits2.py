@@ -51,7 +51,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import EngineCache, Handle, PackedWeightsMixin, _ptr, _require_device, _stream
+from .engine import STREAM, WS, EngineCache, Handle, PackedWeightsMixin, _require_device
 
 
 def speaker_rows(g: Optional[torch.Tensor], B: int, gin_channels: int, owner: str) -> Optional[torch.Tensor]:
@@ -179,12 +179,8 @@ class VitsEngine(Handle):
         x = torch.empty(B, T, H, device=self.device)
         m = torch.empty(B, T, I, device=self.device)
         logs = torch.empty(B, T, I, device=self.device)
-        ws = self.workspace("te", self._lib.ttsvits_text_encoder_workspace_bytes(self._h, B, T))
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsvits_text_encoder(self._h, ids.data_ptr(), lens.data_ptr(), g.data_ptr() if g is not None else None, B, T,
-                                                x.data_ptr(), m.data_ptr(), logs.data_ptr(),
-                                                ws.data_ptr(), ws.numel(), _stream(self.device), self.status.data_ptr())
-        self._err(rc, "ttsvits_text_encoder")
+        ws = self.sized_workspace("te", "ttsvits_text_encoder_workspace_bytes", B, T)
+        self.call("ttsvits_text_encoder", ids, lens, g, B, T, x, m, logs, WS(ws), STREAM, self.status)
         # nn.Embedding raises IndexError on an id outside the table (models.py:370): the kernel clamps and reports through the status
         # word - one host sync here, behind the queued launches (no scan of the ids before them)
         if int(self.status) & 1:
@@ -201,11 +197,8 @@ class VitsEngine(Handle):
         z_cl = z_cl.to(torch.float32).contiguous()
         lens = lengths.to(device=self.device, dtype=torch.int32).contiguous()
         out = torch.empty_like(z_cl)
-        ws = self.workspace("flow", self._lib.ttsvits_flow_workspace_bytes(self._h, B, T))
-        with torch.cuda.device(self.device):
-            rc = getattr(self._lib, fn)(self._h, z_cl.data_ptr(), lens.data_ptr(), g.data_ptr() if g is not None else None, B, T,
-                                        out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
-        self._err(rc, fn)
+        ws = self.sized_workspace("flow", "ttsvits_flow_workspace_bytes", B, T)
+        self.call(fn, z_cl, lens, g, B, T, out, WS(ws), STREAM)
         return out
 
     def flow_reverse(self, z_cl: torch.Tensor, lengths: torch.Tensor, g: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -225,10 +218,7 @@ class VitsEngine(Handle):
         B, T_y, Cc = z_p.shape
         T_x = m_p.shape[1]
         out = torch.empty(B, T_y, T_x, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsvits_neg_cent(self._h, z_p.data_ptr(), m_p.data_ptr(), logs_p.data_ptr(), t_y.data_ptr() if t_y is not None else None,
-                                           t_x.data_ptr() if t_x is not None else None, B, T_y, T_x, Cc, out.data_ptr(), _stream(self.device))
-        self._err(rc, "ttsvits_neg_cent")
+        self.call("ttsvits_neg_cent", z_p, m_p, logs_p, t_y, t_x, B, T_y, T_x, Cc, out, STREAM)
         return out
 
     def maximum_path(self, neg_cent: torch.Tensor, t_y: torch.Tensor, t_x: torch.Tensor, dtype: Optional[torch.dtype] = torch.float32,
@@ -241,21 +231,18 @@ class VitsEngine(Handle):
         B, T_y, T_x = neg_cent.shape
         if T_x > _lib.ALIGN_MAX_TX:
             raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsvits_maximum_path", f"T_x = {T_x} tokens: the search is built for up to {_lib.ALIGN_MAX_TX}")
-        ws = self.workspace("align", int(self._lib.ttsvits_align_workspace_bytes(self._h, B, T_y, T_x)))
+        ws = self.sized_workspace("align", "ttsvits_align_workspace_bytes", B, T_y, T_x)
         # (a dtype the kernel does not store - fp64, integers - is written as fp32 and converted)
         kdt = dtype if dtype in self._PATH_DTYPES else torch.float32
         path = torch.empty(B, T_y, T_x, dtype=kdt, device=self.device) if dtype is not None else None
         ft = torch.empty(B, T_y, dtype=torch.int32, device=self.device)
         dur = torch.empty(B, T_x, dtype=torch.int32, device=self.device)
         status = torch.empty(1, dtype=torch.int32, device=self.device)
-        tail = (B, T_y, T_x) if z_p is None else (B, T_y, T_x, z_p.shape[2], neg_cent.data_ptr())
-        head = (neg_cent.data_ptr(),) if z_p is None else (z_p.data_ptr(), m_p.data_ptr(), logs_p.data_ptr())
-        name = "ttsvits_maximum_path" if z_p is None else "ttsvits_align"
-        with torch.cuda.device(self.device):
-            rc = getattr(self._lib, name)(self._h, *head, t_y.data_ptr(), t_x.data_ptr(), *tail, path.data_ptr() if path is not None else None,
-                                          self._PATH_DTYPES[kdt], ft.data_ptr(), dur.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          _stream(self.device))
-        self._err(rc, name)
+        if z_p is None:
+            self.call("ttsvits_maximum_path", neg_cent, t_y, t_x, B, T_y, T_x, path, self._PATH_DTYPES[kdt], ft, dur, status, WS(ws), STREAM)
+        else:
+            self.call("ttsvits_align", z_p, m_p, logs_p, t_y, t_x, B, T_y, T_x, z_p.shape[2], neg_cent, path, self._PATH_DTYPES[kdt], ft, dur, status,
+                      WS(ws), STREAM)
         if also is None:
             flags, more = int(status.item()), 0
         else:
@@ -274,10 +261,8 @@ class VitsEngine(Handle):
 
     # ---- spectrogram front-end (weightless too; mel_processing.py holds the reference-named entry points) ----
     def _spec_workspace(self, n_fft: int, n_mels: int, name: str) -> torch.Tensor:
-        nbytes = int(self._lib.ttsvits_spec_workspace_bytes(self._h, n_fft, n_mels))
-        if not nbytes:
-            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, name, f"n_fft = {n_fft}, n_mels = {n_mels}: built for n_fft 256 / 512 / 1024 / 2048, n_mels <= 256")
-        return self.workspace("spec", nbytes)
+        return self.sized_workspace("spec", "ttsvits_spec_workspace_bytes", n_fft, n_mels, refusal=_lib.DimsNotBuilt(
+            _lib.ERR_DIMS, name, f"n_fft = {n_fft}, n_mels = {n_mels}: built for n_fft 256 / 512 / 1024 / 2048, n_mels <= 256"))
 
     def spectrogram(self, wav: torch.Tensor, lengths: Optional[torch.Tensor], window: torch.Tensor, n_fft: int, hop_size: int, T: int,
                     mel_basis: Optional[torch.Tensor] = None, *, check: bool = False) -> torch.Tensor:
@@ -290,12 +275,8 @@ class VitsEngine(Handle):
         ws = self._spec_workspace(n_fft, n_mels, name)
         out = torch.empty(B, n_mels or n_fft // 2 + 1, T, device=self.device)
         status = torch.empty(1, dtype=torch.int32, device=self.device) if check else None
-        mel_args = (mel_basis.data_ptr(), n_mels) if n_mels else ()
-        with torch.cuda.device(self.device):
-            rc = getattr(self._lib, name)(self._h, wav.data_ptr(), lengths.data_ptr() if lengths is not None else None, B, N, window.data_ptr(),
-                                          n_fft, hop_size, window.numel(), *mel_args, out.data_ptr(), T,
-                                          status.data_ptr() if check else None, ws.data_ptr(), ws.numel(), _stream(self.device))
-        self._err(rc, name)
+        mel_args = (mel_basis, n_mels) if n_mels else ()
+        self.call(name, wav, lengths, B, N, window, n_fft, hop_size, window.numel(), *mel_args, out, T, status, WS(ws), STREAM)
         if check:
             flags = int(status.item())
             if flags & 4:
@@ -311,10 +292,7 @@ class VitsEngine(Handle):
         n_mels = int(mel_basis.shape[0])
         ws = self._spec_workspace(n_fft, n_mels, "ttsvits_spec_to_mel")
         mel = torch.empty(B, n_mels, T, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsvits_spec_to_mel(self._h, spec.data_ptr(), frames.data_ptr() if frames is not None else None, B, n_fft, T,
-                                               mel_basis.data_ptr(), n_mels, mel.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
-        self._err(rc, "ttsvits_spec_to_mel")
+        self.call("ttsvits_spec_to_mel", spec, frames, B, n_fft, T, mel_basis, n_mels, mel, WS(ws), STREAM)
         return mel
 
     # ---- the validation step's glue (weightless; csrc/evalstep.hip) ----
@@ -324,19 +302,13 @@ class VitsEngine(Handle):
         logs_p_exp [B, T_y, C] or None, None without ``expand``) (include/ttsdec.h ttsvits_kl_loss).  No host read."""
         B, T_y, Cc = z_p.shape
         T_x = m_p.shape[1]
-        nbytes = int(self._lib.ttsvits_kl_loss_workspace_bytes(self._h, B, T_y))
-        if not nbytes:
-            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsvits_kl_loss", f"B = {B}, T_y = {T_y}: more than 65535 utterances or 2^31 frames")
-        ws = self.workspace("kl", nbytes)
+        ws = self.sized_workspace("kl", "ttsvits_kl_loss_workspace_bytes", B, T_y, refusal=_lib.DimsNotBuilt(
+            _lib.ERR_DIMS, "ttsvits_kl_loss", f"B = {B}, T_y = {T_y}: more than 65535 utterances or 2^31 frames"))
         kl = torch.empty(2, device=self.device)
         rows = torch.empty(B, device=self.device)
         m_exp = torch.empty(B, T_y, Cc, device=self.device) if expand else None
         logs_exp = torch.empty(B, T_y, Cc, device=self.device) if expand else None
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsvits_kl_loss(self._h, z_p.data_ptr(), logs_q.data_ptr(), m_p.data_ptr(), logs_p.data_ptr(), _ptr(frame_token),
-                                          t_y.data_ptr(), B, T_y, T_x, Cc, _ptr(m_exp), _ptr(logs_exp), rows.data_ptr(), kl.data_ptr(),
-                                          ws.data_ptr(), ws.numel(), _stream(self.device))
-        self._err(rc, "ttsvits_kl_loss")
+        self.call("ttsvits_kl_loss", z_p, logs_q, m_p, logs_p, frame_token, t_y, B, T_y, T_x, Cc, m_exp, logs_exp, rows, kl, WS(ws), STREAM)
         return kl, rows, m_exp, logs_exp
 
     def slice_segments(self, x: torch.Tensor, ids: torch.Tensor, outer: int, T: int, inner: int, seg: int, scale: int = 1):
@@ -346,10 +318,7 @@ class VitsEngine(Handle):
         B = x.shape[0]
         out = torch.empty(B, outer * seg * inner, device=self.device)
         status = torch.empty(1, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsvits_slice_segments(self._h, x.data_ptr(), ids.data_ptr(), int(ids.dtype == torch.int64), B, outer, T, inner, seg, scale,
-                                                 out.data_ptr(), status.data_ptr(), _stream(self.device))
-        self._err(rc, "ttsvits_slice_segments")
+        self.call("ttsvits_slice_segments", x, ids, int(ids.dtype == torch.int64), B, outer, T, inner, seg, scale, out, status, STREAM)
         return out, status
 
     def sliced_l1(self, a: torch.Tensor, y: torch.Tensor, ids: Optional[torch.Tensor]):
@@ -359,10 +328,7 @@ class VitsEngine(Handle):
         l1 = torch.empty(2, device=self.device)
         rows = torch.empty(B, device=self.device)
         status = torch.empty(1, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsvits_sliced_l1(self._h, a.data_ptr(), y.data_ptr(), _ptr(ids), int(ids is not None and ids.dtype == torch.int64), B, Cc,
-                                            T_a, y.shape[2], rows.data_ptr(), l1.data_ptr(), status.data_ptr(), _stream(self.device))
-        self._err(rc, "ttsvits_sliced_l1")
+        self.call("ttsvits_sliced_l1", a, y, ids, int(ids is not None and ids.dtype == torch.int64), B, Cc, T_a, y.shape[2], rows, l1, status, STREAM)
         return l1, rows, status
 
 
@@ -601,10 +567,8 @@ class GenEngine(Handle):
         a new blob tensor)."""
         nbytes = int(self._lib.ttsvits_generator_planes_bytes(self._h))
         if self._planes is None or self._planes_of is not self.blob:
-            with torch.cuda.device(self.device):
-                planes = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                rc = self._lib.ttsvits_generator_pack_planes(self._h, planes.data_ptr(), _stream(self.device))
-            self._err(rc, "ttsvits_generator_pack_planes")
+            planes = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self.call("ttsvits_generator_pack_planes", planes, STREAM)
             self._planes, self._planes_of = planes, self.blob
         return self._planes
 
@@ -614,17 +578,11 @@ class GenEngine(Handle):
         B, T, _ = z_cl.shape
         prec = _precision_code(precision)
         planes = self.planes() if prec == _lib.PREC_SPLIT_F16 else None
-        nbytes = int(self._lib.ttsvits_generator_workspace_bytes(self._h, prec, B, T))
-        if nbytes == 0:
-            raise NotImplementedError(f"one utterance of {T} frames exceeds the generator's 2-GiB group bound")
-        ws = self.workspace("forward", nbytes)
-        gp = g.data_ptr() if g is not None else None
+        ws = self.sized_workspace("forward", "ttsvits_generator_workspace_bytes", prec, B, T,
+                                  refusal=NotImplementedError(f"one utterance of {T} frames exceeds the generator's 2-GiB group bound"))
         n_up = len(self.dims["upsample_rates"])
-        with torch.cuda.device(self.device):
-            out = torch.empty(B, T * self.up_total, device=self.device) if n_stages is None else None
-            rc = self._lib.ttsvits_generator_forward(self._h, prec, _ptr(planes), z_cl.data_ptr(), gp, B, T, n_up if n_stages is None else n_stages,
-                                                     _ptr(out), ws.data_ptr(), ws.numel(), _stream(self.device))
-        self._err(rc, "ttsvits_generator_forward")
+        out = torch.empty(B, T * self.up_total, device=self.device) if n_stages is None else None
+        self.call("ttsvits_generator_forward", prec, planes, z_cl, g, B, T, n_up if n_stages is None else n_stages, out, WS(ws), STREAM)
         if n_stages is None:
             return out
         rates = self.dims["upsample_rates"][:n_stages]
@@ -757,16 +715,14 @@ class DiscEngine(Handle):
         if nbytes == 0:
             raise _lib.DimsNotBuilt(_lib.ERR_DIMS, "ttsvits_disc_forward", f"B = {B}, T = {T}: an activation's indices leave 32 bits; split the batch")
         Hs = self.heights(T)
-        with torch.cuda.device(self.device):
-            scores = torch.empty(B, Hs[-1] * p, device=self.device)
-            fm, arr, ws = None, None, None
-            if with_fmaps:
-                fm = [torch.empty(B, p, H, C, device=self.device) for H, (C, _, _) in zip(Hs[:-1], self.layers[:-1])]
-                arr = (ctypes.c_void_p * len(fm))(*[t.data_ptr() for t in fm])
-            else:
-                ws = self.workspace("forward", nbytes)
-            rc = self._fn("forward")(self._h, y.data_ptr(), B, T, scores.data_ptr(), arr, _ptr(ws), 0 if ws is None else ws.numel(), _stream(self.device))
-        self._err(rc, "ttsvits_disc_forward")
+        scores = torch.empty(B, Hs[-1] * p, device=self.device)
+        fm, arr, ws = None, None, None
+        if with_fmaps:
+            fm = [torch.empty(B, p, H, C, device=self.device) for H, (C, _, _) in zip(Hs[:-1], self.layers[:-1])]
+            arr = (ctypes.c_void_p * len(fm))(*[t.data_ptr() for t in fm])
+        else:
+            ws = self.workspace("forward", nbytes)
+        self.call("ttsvits_disc_forward", y, B, T, scores, arr, WS(ws), STREAM)
         return scores, fm
 
 
@@ -969,17 +925,12 @@ class DurEngine(Handle):
              noise_scale: float = 1.0) -> torch.Tensor:
         """x_cl [B, T, C] contiguous fp32, lengths [B] int32 (device), g [B, gin] or None; noise [B, 2, T] (SDP) -> logw [B, T]."""
         B, T, _ = x_cl.shape
-        ws = self.workspace("logw", int(self._lib.ttsdur_workspace_bytes(self._h, B, T)))
+        ws = self.sized_workspace("logw", "ttsdur_workspace_bytes", B, T)
         out = torch.empty(B, T, device=self.device)
-        gp = g.data_ptr() if g is not None else None
-        with torch.cuda.device(self.device):
-            if self.dims["kind"] == _lib.DUR_SDP:
-                rc = self._lib.ttsdur_sdp_reverse(self._h, x_cl.data_ptr(), lengths.data_ptr(), gp, noise.data_ptr(), float(noise_scale), B, T,
-                                                  out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
-            else:
-                rc = self._lib.ttsdur_dp_forward(self._h, x_cl.data_ptr(), lengths.data_ptr(), gp, B, T, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                 _stream(self.device))
-        self._err(rc, "ttsdur_sdp_reverse" if self.dims["kind"] == _lib.DUR_SDP else "ttsdur_dp_forward")
+        if self.dims["kind"] == _lib.DUR_SDP:
+            self.call("ttsdur_sdp_reverse", x_cl, lengths, g, noise, float(noise_scale), B, T, out, WS(ws), STREAM)
+        else:
+            self.call("ttsdur_dp_forward", x_cl, lengths, g, B, T, out, WS(ws), STREAM)
         return out
 
     def lengths(self, logw: torch.Tensor, x_lengths: torch.Tensor, length_scale: float):
@@ -988,10 +939,7 @@ class DurEngine(Handle):
         cum = torch.empty(B, T, dtype=torch.int32, device=self.device)
         y_len = torch.empty(B, dtype=torch.int32, device=self.device)
         status = torch.empty(2, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdur_lengths(self._h, logw.data_ptr(), x_lengths.data_ptr(), float(length_scale), B, T, cum.data_ptr(), y_len.data_ptr(),
-                                          status.data_ptr(), _stream(self.device))
-        self._err(rc, "ttsdur_lengths")
+        self.call("ttsdur_lengths", logw, x_lengths, float(length_scale), B, T, cum, y_len, status, STREAM)
         T_y, flags = status.tolist()
         if flags & 1:
             raise ValueError("non-finite duration: exp(logw) * length_scale is inf or nan for some token")
@@ -1009,11 +957,7 @@ class DurEngine(Handle):
         m_p = torch.empty_like(z_p)
         logs_p = torch.empty_like(z_p)
         attn = torch.empty(B, T_y, T, device=self.device) if with_attn else None
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttsdur_expand(self._h, cum.data_ptr(), m_cl.data_ptr(), logs_cl.data_ptr(), eps.data_ptr(), eps.shape[2], float(noise_scale),
-                                         B, T, Cc, T_y, z_p.data_ptr(), m_p.data_ptr(), logs_p.data_ptr(),
-                                         attn.data_ptr() if attn is not None else None, _stream(self.device))
-        self._err(rc, "ttsdur_expand")
+        self.call("ttsdur_expand", cum, m_cl, logs_cl, eps, eps.shape[2], float(noise_scale), B, T, Cc, T_y, z_p, m_p, logs_p, attn, STREAM)
         return z_p, m_p, logs_p, attn
 
 
@@ -1034,13 +978,10 @@ class DurNllEngine(Handle):
         (, terms [B, 4], z [B, 2, T] with ``parts``)."""
         B, T, _ = x_cl.shape
         ws = self.workspace("call", self.workspace_bytes(B, T))
-        with torch.cuda.device(self.device):
-            nll = torch.empty(B, device=self.device)
-            terms = torch.empty(B, 4, device=self.device) if parts else None
-            z = torch.empty(B, 2, T, device=self.device) if parts else None
-            rc = self._fn("forward")(self._h, x_cl.data_ptr(), lengths.data_ptr(), _ptr(g), w.data_ptr(), noise.data_ptr(), B, T, nll.data_ptr(),
-                                     _ptr(terms), _ptr(z), ws.data_ptr(), ws.numel(), _stream(self.device))
-        self._err(rc, "ttsvits_durnll_forward")
+        nll = torch.empty(B, device=self.device)
+        terms = torch.empty(B, 4, device=self.device) if parts else None
+        z = torch.empty(B, 2, T, device=self.device) if parts else None
+        self.call("ttsvits_durnll_forward", x_cl, lengths, g, w, noise, B, T, nll, terms, z, WS(ws), STREAM)
         return (nll, terms, z) if parts else nll
 
 
@@ -1238,31 +1179,24 @@ class DurDiscEngine(Handle):
         return int(self._fn("workspace_bytes")(self._h, B, T, n_dur))
 
     def _workspace(self, B: int, T: int, n_dur: int, what: str) -> torch.Tensor:
-        nbytes = self.workspace_bytes(B, T, n_dur)
-        if nbytes == 0:
-            raise _lib.DimsNotBuilt(_lib.ERR_DIMS, what, f"B = {B}, T = {T}: the row indices leave 32 bits; split the batch")
-        return self.workspace("call", nbytes)
+        return self.sized_workspace("call", "ttsvits_durdisc_workspace_bytes", B, T, n_dur, refusal=_lib.DimsNotBuilt(
+            _lib.ERR_DIMS, what, f"B = {B}, T = {T}: the row indices leave 32 bits; split the batch"))
 
     def trunk(self, x_cl: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
         """x_cl [B, T, C] contiguous fp32, lengths [B] int32 (device) -> hidden [B, T, F], zero at masked tokens."""
         B, T, _ = x_cl.shape
         ws = self._workspace(B, T, 1, "ttsvits_durdisc_trunk")
-        with torch.cuda.device(self.device):
-            out = torch.empty(B, T, self.dims["filter_channels"], device=self.device)
-            rc = self._fn("trunk")(self._h, x_cl.data_ptr(), lengths.data_ptr(), B, T, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device))
-        self._err(rc, "ttsvits_durdisc_trunk")
+        out = torch.empty(B, T, self.dims["filter_channels"], device=self.device)
+        self.call("ttsvits_durdisc_trunk", x_cl, lengths, B, T, out, WS(ws), STREAM)
         return out
 
     def prob(self, hidden_cl: torch.Tensor, lengths: torch.Tensor, dur: torch.Tensor, with_logits: bool = False):
         """hidden_cl [B, T, F], dur [n_dur, B, T] (n_dur 1 or 2), both contiguous fp32 -> (prob [n_dur, B, T], logits or None)."""
         n_dur, B, T = dur.shape
         ws = self._workspace(B, T, n_dur, "ttsvits_durdisc_prob")
-        with torch.cuda.device(self.device):
-            prob = torch.empty(n_dur, B, T, device=self.device)
-            logit = torch.empty_like(prob) if with_logits else None
-            rc = self._fn("prob")(self._h, hidden_cl.data_ptr(), lengths.data_ptr(), dur.data_ptr(), n_dur, B, T, prob.data_ptr(), _ptr(logit),
-                                  ws.data_ptr(), ws.numel(), _stream(self.device))
-        self._err(rc, "ttsvits_durdisc_prob")
+        prob = torch.empty(n_dur, B, T, device=self.device)
+        logit = torch.empty_like(prob) if with_logits else None
+        self.call("ttsvits_durdisc_prob", hidden_cl, lengths, dur, n_dur, B, T, prob, logit, WS(ws), STREAM)
         return prob, logit
 
 
@@ -1424,15 +1358,11 @@ class PostEngine(Handle):
         [B, T, inter] channel-last."""
         B, _, T = y.shape
         I = self.dims["inter_channels"]
-        ws = self.workspace("forward", int(self._lib.ttspost_workspace_bytes(self._h, B, T)))
+        ws = self.sized_workspace("forward", "ttspost_workspace_bytes", B, T)
         z = torch.empty(B, T, I, device=self.device)
         m = torch.empty_like(z)
         logs = torch.empty_like(z)
-        with torch.cuda.device(self.device):
-            rc = self._lib.ttspost_forward(self._h, y.data_ptr(), lengths.data_ptr(), g.data_ptr() if g is not None else None, eps.data_ptr(),
-                                           eps.shape[2], B, T, z.data_ptr(), m.data_ptr(), logs.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           _stream(self.device))
-        self._err(rc, "ttspost_forward")
+        self.call("ttspost_forward", y, lengths, g, eps, eps.shape[2], B, T, z, m, logs, WS(ws), STREAM)
         return z, m, logs
 
 
